@@ -1,9 +1,11 @@
 """bench.py — images/sec of the MSDN train step (BASELINE.json metric) on N MI355X GPUs of one node.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 (for N > 1 the driver launches it under torch.distributed.run, one rank per GPU; gradients are all-reduced with
 RCCL).  Prints ONE JSON line on rank 0: whole-job images/s with inputs resident in HBM, the roofline of the dominant
 kernel (HIP-event timed inside the timed region) and the CPU baseline (the numpy oracle on the host cores).
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy.  Inputs, dropout masks and initial
+weights all come from fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -55,6 +57,31 @@ def keep_masks(B, n, rank, device):
     for step in range(n):
         rng = np.random.default_rng(4000 + step + 100000 * rank)
         out.append(torch.from_numpy((rng.random((B, 4096)) >= 0.5).astype(np.uint8)).to(device))
+    return out
+
+
+DUMP_SAMPLE = 1 << 20      # --dump-outputs: elements written of a larger output (4 MB), at fixed positions
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: each array as <outdir>/<name>.npy in float32.  One of more than DUMP_SAMPLE elements is written as
+    DUMP_SAMPLE elements of its flattened form, at sorted positions drawn from a fixed seed: the same positions for every
+    array of that size, in every run, so that two builds can be compared output for output."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.size > DUMP_SAMPLE:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(outdir, name + '.npy'), a)
+
+
+def msdn_outputs(net):
+    """What a caller of MSDNReplica.step holds after the step: both losses, both depth maps and, per optimizer, the flat
+    buffers of its variables and Adam slots.  Collective under a data-parallel reducer (gather_state): every rank calls it."""
+    net.gather_state()
+    out = {'coarse_loss': net.loss_coarse, 'fine_loss': net.loss_fine, 'coarse': net.coarse, 'fine': net.fine}
+    for name, g in net.groups.items():
+        out.update({f'{name}_var': g.var, f'{name}_m': g.m, f'{name}_v': g.v})
     return out
 
 
@@ -281,7 +308,7 @@ def hbm_roofline_bf16_storage(B, phase, seconds_per_step):
 
 def bench_dcnf(args, lib, device, rank, world):
     """BASELINE config 4: DCNF-lite unary conv stack (src/models.py:50-89), batch 16 -> 768 patches of 100x100x3.
-    A step = unary forward (resize, patches, 5 conv / 3 pool / 3 dense) + unary backward from a synthetic dz: 2.672 GFLOP
+    A step = unary forward (resize, patches, 5 conv / 3 pool / 3 dense) + unary backward from a seeded synthetic dz: 2.672 GFLOP
     per patch forward and twice that backward (no input gradient for the first conv: 2.672 * 2 -
     0.377)."""
     from ann3depth_amd import models
@@ -289,13 +316,16 @@ def bench_dcnf(args, lib, device, rank, world):
     rng = np.random.default_rng(1000 + rank)
     img = torch.from_numpy((rng.integers(0, 256, (B, 480, 640, 3)) / 255).astype(np.float32)).to(device)
     net = models.DCNFUnary(B, device=device)
-    dz = torch.randn((net.P, 1), device=device)
+    rng = np.random.default_rng(5000 + rank)
+    dz = torch.from_numpy(rng.standard_normal((net.P, 1), dtype=np.float32)).to(device)
 
     def step():
         net.forward(img)
         net.backward(dz)
-    steps, warm = min(args.steps, 20), min(args.warmup, 3)
+    steps, warm = args.steps, args.warmup
     dt, recs, warm_recs = warm_then_time(lambda i: step(), lambda: None, steps, warm, lib, 1, True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'z': net.z.view(B, -1, 1), 'unary_grad': net.group.grad})
     roof, _ = roofline_from(recs, with_traffic=False)                 # (the committed PMC passes are MSDN's)
     _, table = roofline_from(warm_recs, with_traffic=False)           # every kernel: from the warm-up steps
     gflop = net.P * (2.672 + 2 * 2.672 - 0.377)
@@ -383,7 +413,12 @@ def main():
     ap.add_argument('--model', default='msdn', choices=['msdn', 'dcnf'],
                     help="msdn = the headline (BASELINE config 2/3/5); dcnf = BASELINE config 4, the DCNF-lite unary stack "
                          "at batch 16 (768 patches): a separate line, 'step' = unary forward + backward")
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32; rank 0; a '
+                         'fixed sample of outputs over 1M elements)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     from ann3depth_amd import _lib, dp, models
     lib = _lib.load()
@@ -416,6 +451,10 @@ def main():
     # headline: coarse-phase train step (what `make train` executes from global_step 0; the heaviest real phase)
     gs0 = 0 if args.phase == 'coarse' else models.SAMPLES_COARSE // B
     dt, (recs, warm_recs) = run_phase(net, img, dep, masks, args.steps, args.warmup, gs0, lib, world, timed_kernels=True)
+    if args.dump_outputs:
+        outputs = msdn_outputs(net)            # now: the fine-phase line below goes on training this replica
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
     value = world * B * args.steps / dt
     roof, _ = roofline_from(recs)                                     # the dominant kernel, event-timed in the timed region
     _, table = roofline_from(warm_recs, with_traffic=False)           # every kernel: event-timed during the warm-up steps
