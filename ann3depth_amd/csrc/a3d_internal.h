@@ -39,7 +39,6 @@ struct GemmPlan {
   int ktiles_per_split;
   int tiles_m, tiles_n;
   int streamk;       // > 0: stream-K launch of this many blocks (splitk == 1)
-  int sk_sliced;     // stream-K shares cut per XCD from eighths of the K axis (bwd-filter; SkSpace in igemm.h)
   size_t ws_bytes;   // split-K / stream-K slabs (0 if neither)
   int ring;          // bf16 plans: 1 + tile configuration of the LDS-DMA kernel for bf16-stored operands (igemm_ring.h), 0 = igemm_bf16
 };
@@ -51,8 +50,6 @@ struct GemmProblem {
   int plain = 0;     // 1: register-staged kernel without split-K only (fused-pool forward)
   int need_reduce = 0;   // 1: the output is stored by the split-K reduction only (rows narrower than the GEMM's N): split-K >= 2, no stream-K
   int no_glds = 0;   // 1: not the LDS-DMA kernels (bf16 output)
-  int gen2_ok = 0;   // 1: the launch may run on the second-generation LDS-DMA kernel (igemm2.h): float32 tensors, 16-byte
-                     //    operands, forward / bwd-data: gathered channels a multiple of 32 and K = taps x channels
   int ring_ok = 0;   // 1: both operands are bf16 tensors whose 16-byte pieces lie inside one filter tap (channels % 8 == 0):
                      //    forward / stride-1 bwd-data may run on igemm_ring.h
 };

@@ -19,11 +19,6 @@
 #include "a3d_internal.h"
 #include "igemm.h"
 
-// cache policy of the once-read streams (weights, Adam slots); -DA3D_DENSE_AUX=0 for the A/B
-#ifndef A3D_DENSE_AUX
-#define A3D_DENSE_AUX kAuxStream
-#endif
-
 namespace a3d {
 
 
@@ -263,11 +258,7 @@ __global__ __launch_bounds__(256) void dense_dw_adam_rows_kernel(const float* __
       for (int v = 0; v < 16; ++v) acc[g][j][v] = 0.f;
   const int krow = k0 + li;
   const bool kok = krow < K;                       // N % CW == 0: a lane's CW columns exist together
-#ifdef A3D_DENSE_NOGEMM
-  const int T = 0;
-#else
   const int T = (M + 1) / 2;
-#endif
   for (int t0 = 0; t0 < T; t0 += 8) {
     float a[8];
     vec bq[8][G];
@@ -459,7 +450,7 @@ __global__ __launch_bounds__(256, SL == 2 ? 4 : 2) void dense_dw_adam_stream_ker
     for (int r = 0; r < 8; ++r) {
       const __amdgpu_buffer_rsrc_t rr = row_rsrc(g, r);
 #pragma unroll
-      for (int h = 0; h < NI; ++h) load_vec_buf<CW, A3D_DENSE_AUX>(rr, piece_off(h), mo[NI * r + h]);
+      for (int h = 0; h < NI; ++h) load_vec_buf<CW, kAuxStream>(rr, piece_off(h), mo[NI * r + h]);
     }
   };
 
@@ -560,9 +551,9 @@ __global__ __launch_bounds__(256, SL == 2 ? 4 : 2) void dense_dw_adam_stream_ker
             mn[j] = __float_as_uint(t);
             chk += __fmul_rn(gr, gr) + fabsf(t);
           }
-          if constexpr (CW == 4) __builtin_amdgcn_raw_buffer_store_b128(mn, rr, (int)off, 0, A3D_DENSE_AUX);
-          else __builtin_amdgcn_raw_buffer_store_b64(mn, rr, (int)off, 0, A3D_DENSE_AUX);
-          load_vec_buf<CW, A3D_DENSE_AUX>(rn, off, mreg[NI * r + h]);
+          if constexpr (CW == 4) __builtin_amdgcn_raw_buffer_store_b128(mn, rr, (int)off, 0, kAuxStream);
+          else __builtin_amdgcn_raw_buffer_store_b64(mn, rr, (int)off, 0, kAuxStream);
+          load_vec_buf<CW, kAuxStream>(rn, off, mreg[NI * r + h]);
           // ApplyAdam's v and var take a NaN where g*g or the new m is not finite (adam_frozen_kernel); a non-finite
           // term makes the piece's sum non-finite, and the per-element work happens only behind that test
           if (!isfinite(chk) & (off != kOOB) & (row < K)) {
@@ -639,7 +630,7 @@ __global__ __launch_bounds__(256) void dense_fwd_stream_kernel(const DenseStream
         // 16 bytes at dword alignment; where a lane's four columns run past N they are the next row's first (or
         // past the buffer: zeros): accumulators of columns that do not exist, never stored
         const int k = kc + 8 * u + 4 * lh + j;
-        load_vec_buf<4, A3D_DENSE_AUX>(rw, ((k < k1) & (col0 < p.N)) ? (uint32_t)(((size_t)k * p.N + col0) * 4) : kOOB, c.w[u][j]);
+        load_vec_buf<4, kAuxStream>(rw, ((k < k1) & (col0 < p.N)) ? (uint32_t)(((size_t)k * p.N + col0) * 4) : kOOB, c.w[u][j]);
       }
 #pragma unroll
       for (int b = 0; b < MB; ++b) {

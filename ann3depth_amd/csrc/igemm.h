@@ -44,9 +44,6 @@ namespace a3d {
 #define A3D_RTSTAMP(var) do { } while (0)
 #endif
 
-#ifndef A3D_PIPE_ALL
-#define A3D_PIPE_ALL 0
-#endif
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -241,15 +238,12 @@ struct IgemmCfg {
   // 1 KiB only), 23 per tile of 24 MFMAs in the bwd-filter kernel, and beside fp32 MFMAs none of them is hidden.
   // The pad kept the two k halves of a wave (rows 4 apart) off each other's banks; without it the rows of the odd 4-groups
   // store their columns XOR 32 (SWZ), which does the same.
-#ifndef A3D_NO_SWZ
-#define A3D_NO_SWZ 0
-#endif
-  static constexpr bool A_SWZ = !A3D_NO_SWZ && (MODE == MODE_BWD_F) && (A_COLS % 64 == 0);
+  static constexpr bool A_SWZ = (MODE == MODE_BWD_F) && (A_COLS % 64 == 0);
   static constexpr int A_LD = A_SWZ ? A_COLS : A_COLS + 4;
   // B: FWD/BWD_F [BK][BN+4] (N contiguous, b32 reads); BWD_D [BN][BK+4] (K contiguous, b128 reads)
   static constexpr int B_ROWS = (MODE == MODE_BWD_D) ? BN : BK;
   static constexpr int B_COLS = (MODE == MODE_BWD_D) ? BK : BN;
-  static constexpr bool B_SWZ = !A3D_NO_SWZ && (MODE != MODE_BWD_D) && (B_COLS % 64 == 0);
+  static constexpr bool B_SWZ = (MODE != MODE_BWD_D) && (B_COLS % 64 == 0);
   static constexpr int B_LD = B_SWZ ? B_COLS : B_COLS + 4;
   static constexpr int A_ELEMS = A_ROWS * A_LD, B_ELEMS = B_ROWS * B_LD;
   static constexpr int PIX = A_ROWS;   // pixel-table entries (rows of the im2col tile)
@@ -426,30 +420,9 @@ struct FilterTTile {
   }
 };
 
-// stream-K share of block b of `nblk`: iterations [first, last) of the tile-major (tile, k-tile) order
+// stream-K share of block b of `nblk`: iterations [first, last) of the `total` tile-major (tile, k-tile) iterations
 __device__ __forceinline__ uint32_t sk_first(uint32_t b, uint32_t nblk, uint32_t total) {
   return (uint32_t)(((unsigned long long)b * total) / nblk);
-}
-// Iteration space a block's share is cut from.  streamk 1: all `tiles` x `nk` iterations, dealt to all blocks.
-// streamk 2 (bwd-filter, grid a multiple of 8): the K axis — the pixels — is cut into eight slices, one per XCD (the
-// remapped ids [x q, (x+1) q) are the blocks of XCD x), and the blocks of an XCD share tiles x (their slice): an XCD then
-// streams only its eighth of x and dz through its L2 instead of all of both (tile-major shares: 601 MB of fabric reads
-// per conv2d_1..3 bwd-filter launch against 47 MB algorithmic).  Every tile then has contributors on all eight XCDs;
-// ascending block id is still ascending k.  The host makes sure a share is no longer than a slice (per <= nk / 8), so a
-// block still ends up with at most two partial tiles = its two slab slots.
-struct SkSpace { uint32_t blocks, j, k0, nk, total; };
-__device__ __forceinline__ SkSpace sk_space(int streamk, uint32_t b, uint32_t nblk, uint32_t tiles, uint32_t nk_total) {
-  SkSpace s;
-  if (streamk == 2) {
-    const uint32_t q = nblk / 8, x = b / q;
-    s.blocks = q; s.j = b - x * q;
-    s.k0 = x * nk_total / 8;
-    s.nk = (x + 1) * nk_total / 8 - s.k0;
-  } else {
-    s.blocks = nblk; s.j = b; s.k0 = 0; s.nk = nk_total;
-  }
-  s.total = tiles * s.nk;
-  return s;
 }
 
 // accumulators of one wave <-> slab, register order: 16 bytes per lane, 1 KiB per wave-instruction
@@ -757,8 +730,8 @@ __device__ __forceinline__ void store_tile_pool_buf(const IgemmParams& p, f32x16
 // What a block does with the accumulators of one share of one tile: a share that covers the tile's whole K range stores it
 // through the mode's epilogue (bias / activation / dropout, the fused 2x2 max pool, the activation gradient), a classic
 // split-K share stores raw sums into its slab, a stream-K share that ends inside the tile leaves the accumulators (and the
-// bias-gradient sums of `do_bias` threads) in the block's slab slot for igemm_fixup_kernel.  Shared by igemm_body and the
-// LDS-DMA kernel of igemm2.h (same accumulator layout: wave (wm, wn), accumulators [TM][TN] of 32x32).
+// bias-gradient sums of `do_bias` threads) in the block's slab slot for igemm_fixup_kernel.  Accumulator layout: wave
+// (wm, wn), accumulators [TM][TN] of 32x32.
 template <int MODE, int BM, int BN, int TM, int TN, int WM, int WN>
 __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x16 (&acc)[TM][TN], const int split, const uint32_t bid,
                                                const int seg, const int kt_begin, const int kt_end, const int nk_total,
@@ -824,18 +797,17 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p, const uint32_t 
   }
   const int tiles_mn = p.tiles_m * p.tiles_n;
   const int nk_total = (p.K + BK - 1) / BK;      // p.ktiles_per_split is in units of this kernel's BK
-  // stream-K share of this block: a contiguous range of the tile-major (tile, k-tile) iterations of its iteration space —
-  // the whole problem (streamk 1), or (streamk 2, bwd-filter) the K slice of the block's XCD: see SkSpace
-  const SkSpace sp = sk_space(p.streamk, bid, nwg, (uint32_t)tiles_mn, (uint32_t)nk_total);
-  uint32_t sk_cur = p.streamk ? sk_first(sp.j, sp.blocks, sp.total) : 0u;
-  const uint32_t sk_end = p.streamk ? sk_first(sp.j + 1, sp.blocks, sp.total) : 1u;
+  // stream-K share of this block: a contiguous range of the tile-major (tile, k-tile) iterations of the whole problem
+  const uint32_t sk_total = (uint32_t)tiles_mn * (uint32_t)nk_total;
+  uint32_t sk_cur = p.streamk ? sk_first(bid, nwg, sk_total) : 0u;
+  const uint32_t sk_end = p.streamk ? sk_first(bid + 1, nwg, sk_total) : 1u;
   for (int seg = 0; sk_cur < sk_end; ++seg) {      // classic launches: exactly one pass
   int split = 0, tmn, kt_begin, kt_end;
   if (p.streamk) {
-    tmn = p.streamk == 1 ? (int)fdiv(sk_cur, p.div_nk) : (int)(sk_cur / sp.nk);
-    const uint32_t kl = sk_cur - (uint32_t)tmn * sp.nk;
-    const uint32_t n = min(sk_end - sk_cur, sp.nk - kl);
-    kt_begin = (int)(sp.k0 + kl);
+    tmn = (int)fdiv(sk_cur, p.div_nk);
+    const uint32_t kl = sk_cur - (uint32_t)tmn * (uint32_t)nk_total;
+    const uint32_t n = min(sk_end - sk_cur, (uint32_t)nk_total - kl);
+    kt_begin = (int)kl;
     kt_end = kt_begin + (int)n;
     sk_cur += n;
   } else {
@@ -1124,7 +1096,7 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p, const uint32_t 
     // chunk u's MFMAs issue, in the requested interleave of one MFMA and its share of the next chunk's ds_reads
     // (bwd-filter 128x128 187 -> 182 us, bwd-data 170 -> 163 us).  The forward kernels and the other tiles are 0-4 %
     // slower that way and keep the plain read-then-multiply form below.
-    constexpr bool PIPE = A3D_PIPE_ALL ? (NWAVES == 8) : ((MODE != MODE_FWD) && NWAVES == 8 && BN == 128);
+    constexpr bool PIPE = (MODE != MODE_FWD) && NWAVES == 8 && BN == 128;
     if constexpr (PIPE) {
       f32x4 af[2][TM], bf[2][TN];
       auto read_frags = [&](int u, int buf) {
@@ -1283,28 +1255,22 @@ __global__ __launch_bounds__(256) void igemm_fixup_kernel(const IgemmParams p, c
   // without work in between.
   if (threadIdx.x == 0) {
     uint32_t n = 0;
-    const uint32_t nx = p.streamk == 2 ? 8u : 1u;
-    for (uint32_t x = 0; x < nx; ++x) {
-      const SkSpace sp = sk_space(p.streamk, x * (nblk / nx), nblk, tiles, nk);
-      if (sp.nk == 0) continue;
-      const uint32_t t0 = tile * sp.nk, t1 = t0 + sp.nk - 1;
-      uint32_t jf = (uint32_t)(((unsigned long long)t0 * sp.blocks) / sp.total), jl = (uint32_t)(((unsigned long long)t1 * sp.blocks) / sp.total);
-      while (jf + 1 < sp.blocks && sk_first(jf + 1, sp.blocks, sp.total) <= t0) ++jf;
-      while (jl + 1 < sp.blocks && sk_first(jl + 1, sp.blocks, sp.total) <= t1) ++jl;
-      for (uint32_t j = jf; j <= jl; ++j) {
-        const uint32_t f = sk_first(j, sp.blocks, sp.total);
-        if (f == sk_first(j + 1, sp.blocks, sp.total)) continue;                      // idle block
-        const uint32_t b = x * (nblk / nx) + j;
-        if (n < MAXC) slots[n] = 2 * b + (f / sp.nk == tile ? 0u : 1u);
-        ++n;
-      }
+    const uint32_t total = tiles * nk, t0 = tile * nk, t1 = t0 + nk - 1;      // nk >= 1 (host)
+    uint32_t jf = (uint32_t)(((unsigned long long)t0 * nblk) / total), jl = (uint32_t)(((unsigned long long)t1 * nblk) / total);
+    while (jf + 1 < nblk && sk_first(jf + 1, nblk, total) <= t0) ++jf;
+    while (jl + 1 < nblk && sk_first(jl + 1, nblk, total) <= t1) ++jl;
+    for (uint32_t b = jf; b <= jl; ++b) {
+      const uint32_t f = sk_first(b, nblk, total);
+      if (f == sk_first(b + 1, nblk, total)) continue;                      // idle block
+      if (n < MAXC) slots[n] = 2 * b + (f / nk == tile ? 0u : 1u);
+      ++n;
     }
     nslots = n < MAXC ? n : MAXC;
   }
   __syncthreads();
   const uint32_t n = nslots;
-  // one contributor that covered the whole K range wrote the tile itself (tile-major shares only)
-  if (n <= 1 && p.streamk == 1) return;
+  // one contributor that covered the whole K range wrote the tile itself
+  if (n <= 1) return;
   const int tile_m = (int)tile / p.tiles_n, tile_n = (int)tile - tile_m * p.tiles_n;
   if (unit < UNITS) {
     const size_t uoff = ((size_t)unit * 64 + lane) * 4;

@@ -25,12 +25,8 @@ struct Bf16Cfg {
   // k-tile: 64 for the plain bf16 kernel (half as many barriers and LDS round trips per MAC as 32; 78 KB of LDS, two
   // blocks per CU), 32 for the two-plane x3 variant (its planes would not fit otherwise)
   static constexpr int BK = X3 ? 32 : 64;
-#ifndef A3D_BF16_WAVES
-#define A3D_BF16_WAVES 8
-#endif
-  // 8 waves of 32 x (BN/2), or (diagnostic / tuning build: -DA3D_BF16_WAVES=4) 4 waves of 64 x (BN/2): twice the MFMAs
-  // per wave, barrier and fragment read, half the wavefronts per CU
-  static constexpr int NWAVES = A3D_BF16_WAVES, NT = 64 * NWAVES, WAVES_M = NWAVES / 2, WAVES_N = 2;
+  // 8 waves of 32 x (BN/2)
+  static constexpr int NWAVES = 8, NT = 64 * NWAVES, WAVES_M = NWAVES / 2, WAVES_N = 2;
   static constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
   static constexpr int TM = WM / 32, TN = WN / 32;
   static_assert(TM >= 1 && TN >= 1 && TM * 32 * WAVES_M == BM && TN * 32 * WAVES_N == BN, "tile");
@@ -303,16 +299,8 @@ __device__ __forceinline__ void igemm_bf16_body(const IgemmParams& p, const uint
   }
 
   // loads of k-tile kt into ra / rb (slot: row-table buffer of that tile, BWD_F); live = false: a tile that does not exist
-  auto stage = [&](auto uni_c, int kt_real, int slot, bool live) {
+  auto stage = [&](auto uni_c, int kt, int slot, bool live) {
     constexpr bool UNI = decltype(uni_c)::value;
-#ifdef A3D_HACK_FIXED_KT
-    // timing-only diagnostic build (never shipped, results are wrong): every iteration stages the FIRST k-tile, so all of
-    // the per-tile address generation is loop-invariant and leaves the loop — what the kernel would cost without it
-    const int kt = kt_begin;
-    (void)kt_real;
-#else
-    const int kt = kt_real;
-#endif
     __amdgpu_buffer_rsrc_t rsA, rsB;
     uint32_t tab_boff = 0;        // UNI: byte offset of the B tile (k-tile table)
     // ---------- A ----------
@@ -563,7 +551,7 @@ __device__ __forceinline__ void igemm_bf16_body(const IgemmParams& p, const uint
 }
 
 template <int MODE, int BM, int BN, bool X3, bool A16 = false, bool B16 = false, bool C16 = false>
-__global__ __launch_bounds__(64 * A3D_BF16_WAVES, A3D_BF16_WAVES / 2) void igemm_bf16_kernel(const IgemmParams p) {
+__global__ __launch_bounds__(512, 4) void igemm_bf16_kernel(const IgemmParams p) {
   igemm_bf16_body<MODE, BM, BN, X3, A16, B16, C16>(p, gridDim.x, blockIdx.x);
 }
 
@@ -571,7 +559,7 @@ __global__ __launch_bounds__(64 * A3D_BF16_WAVES, A3D_BF16_WAVES / 2) void igemm
 // classes of a strided bwd-data (conv2d_4 at batch 64: four GEMMs of 96 tiles each, 14 - 40 us plus a split-K reduction
 // apiece as separate launches).
 template <int MODE, int BM, int BN, bool X3, bool A16, bool B16, bool C16>
-__global__ __launch_bounds__(64 * A3D_BF16_WAVES, A3D_BF16_WAVES / 2) void igemm_bf16_multi_kernel(const IgemmMulti ps) {
+__global__ __launch_bounds__(512, 4) void igemm_bf16_multi_kernel(const IgemmMulti ps) {
   const IgemmParams& p = ps.p[blockIdx.y];
   const uint32_t nwg = (uint32_t)(p.tiles_m * p.tiles_n * p.splitk);
   if (blockIdx.x >= nwg) return;

@@ -41,13 +41,7 @@ static const TileCfg kCfgs[] = {{128, 128, 1.00f, 32}, {128, 96, 1.00f, 32}, {12
                                 // +3-5 % over the register-staged twins; since those stage through buffer loads with
                                 // addresses computed a tile ahead (round 2) they are the faster ones (fine/second
                                 // forward 245 vs 259 us, conv2d_1 325 vs 339 us: profiles/r02_sweep_hot.txt)
-                                {128, 128, 1.10f, 32}, {128, 64, 1.00f, 32},
-                                // second-generation kernel (igemm2.h: LDS-DMA, 4 waves of 64x64, pinned schedule), all three
-                                // modes; takes a launch only when gen2_ok (GemmProblem) — else its register-staged twin, cfg 0.
-                                // Round 6: parity-green and measured on every MSDN layer — 2-5 % behind the 8-wave kernels on
-                                // forward / bwd-data, 15 % behind on bwd-filter (DESIGN.md 3.1i says why): eff 0 = pinned
-                                // plans only (A3D_FORCE_CFG=11 in a tuning process; tools/gen2_check.py, tools/sweep_hot.py)
-                                {128, 128, 0.f, 32}};
+                                {128, 128, 1.10f, 32}, {128, 64, 1.00f, 32}};
 static const int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
 static const int kSlots = 512;               // 256 CUs x 2 resident blocks
 static const size_t kMaxSlabBytes = (size_t)192 << 20;
@@ -68,21 +62,6 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 // call, and plans are cached per problem (plan_gemm).
 // (tuning() / tune_int(): a3d_internal.h, capi.cc)
 static bool env_flag_no_uni() { static const bool v = tune_int("A3D_NO_UNI", 0) != 0; return v; }
-// K-sliced stream-K is built and fuzzed but OFF by default: it removes the bwd-filter launches' fabric over-fetch and
-// costs 0.7 % of the step; A3D_SK_SLICED=1 turns it on
-static bool env_flag_no_sliced() { static const bool v = tune_int("A3D_SK_SLICED", 0) == 0; return v; }
-// K-sliced stream-K (SkSpace): a block's share must fit inside one slice of one tile's K range (at most two partial
-// tiles per block = its two slab slots) and a tile may not have more contributors than the fixup lists (96).
-static bool sk_sliced_ok(int mode, long tiles, int nk, int grid, long* meet_out) {
-  if (mode != MODE_BWD_F || grid % 8 != 0 || nk < 64) return false;
-  const long q = grid / 8, nk_lo = nk / 8, nk_hi = (nk + 7) / 8;
-  const long per = (tiles * nk_hi + q - 1) / q;                 // longest share of any XCD
-  if (per > nk_lo || per < 1) return false;
-  const long meet = 8 * ((nk_hi + per - 1) / per + 1);
-  if (meet > 256) return false;
-  if (meet_out) *meet_out = meet;
-  return true;
-}
 static bool env_flag_no_streamk() { static const bool v = tune_int("A3D_NO_STREAMK", 0) != 0; return v; }
 static bool env_flag_no_kperm() { static const bool v = tune_int("A3D_NO_KPERM", 0) != 0; return v; }
 
@@ -117,15 +96,13 @@ static void timing_end(TimingSlot& slot, hipStream_t st) {
   std::lock_guard<std::mutex> lk(g_timing_mu);
   g_timing.push_back(slot);
 }
-static const int kCfgWavesM[] = {2, 4, 4, 4, 2, 1, 1, 4, 4, 4, 4, 2};
-static const int kCfgNWaves[] = {4, 4, 4, 4, 4, 4, 4, 8, 8, 8, 8, 4};
+static const int kCfgWavesM[] = {2, 4, 4, 4, 2, 1, 1, 4, 4, 4, 4};
+static const int kCfgNWaves[] = {4, 4, 4, 4, 4, 4, 4, 8, 8, 8, 8};
 static const int kFirstGldsCfg = 9;
-static const int kGen2Cfg = 11;
 // the forward-only LDS-DMA kernels of round 1 (igemm_glds.h)
-static inline bool is_glds_cfg(int c) { return c >= kFirstGldsCfg && c < kGen2Cfg; }
+static inline bool is_glds_cfg(int c) { return c >= kFirstGldsCfg; }
 // configurations that run stream-K shares (slabs + igemm_fixup_kernel)
-static inline bool streamk_cfg(int c) { return c < kFirstGldsCfg || c == kGen2Cfg; }
-static bool env_flag_no_gen2() { static const bool v = tune_int("A3D_NO_GEN2", 0) != 0; return v; }
+static inline bool streamk_cfg(int c) { return c < kFirstGldsCfg; }
 
 // bf16 / bf16x3 kernel: BM = 128.  Staging-bound rather than MFMA-bound: the wider tile wins whenever N allows it
 // (even at one block per CU for the two-plane x3 variant); split-K factors: x3 by round 1's sweep
@@ -234,8 +211,8 @@ static GemmPlan plan_gemm_search(const GemmProblem& g, int precision);
 GemmPlan plan_gemm(const GemmProblem& g, int precision) {
   if (tuning()) return plan_gemm_search(g, precision);
   static std::mutex mu;
-  static std::map<std::array<int, 11>, GemmPlan> cache;
-  const std::array<int, 11> key = {g.mode, g.M, g.N, g.K, g.avec, g.bvec, g.plain + 2 * g.need_reduce, g.no_glds, precision, g.ring_ok, g.gen2_ok};
+  static std::map<std::array<int, 10>, GemmPlan> cache;
+  const std::array<int, 10> key = {g.mode, g.M, g.N, g.K, g.avec, g.bvec, g.plain + 2 * g.need_reduce, g.no_glds, precision, g.ring_ok};
   std::lock_guard<std::mutex> lk(mu);
   auto it = cache.find(key);
   if (it != cache.end()) return it->second;
@@ -276,7 +253,6 @@ static GemmPlan plan_gemm_search(const GemmProblem& g, int precision) {
     // 16-byte operands, and have neither the pooling epilogue nor a bf16 output — their register-staged twins do
     int cfg = force_cfg;
     if (is_glds_cfg(cfg) && (g.mode != MODE_FWD || g.avec != 4 || g.bvec != 4 || g.plain || g.no_glds)) cfg -= 2;
-    if (cfg == kGen2Cfg && !g.gen2_ok) cfg = 0;
     const int force_cfg = cfg;
     const int bm = kCfgs[force_cfg].bm, bn = kCfgs[force_cfg].bn;
     const int nk = std::max(1, (g.K + kCfgs[force_cfg].bk - 1) / kCfgs[force_cfg].bk);
@@ -292,8 +268,6 @@ static GemmPlan plan_gemm_search(const GemmProblem& g, int precision) {
     if (force_streamk > 0 && streamk_cfg(force_cfg) && !g.plain && !g.need_reduce) {
       best.splitk = 1; best.ktiles_per_split = nk; best.streamk = force_streamk;
       best.ws_bytes = (size_t)2 * force_streamk * ((size_t)bm * bn + bn) * 4;
-      best.sk_sliced = tune_int("A3D_FORCE_SK_SLICED", 0) &&
-                       sk_sliced_ok(g.mode, (long)best.tiles_m * best.tiles_n, nk, force_streamk, nullptr);
     }
     return best;
   }
@@ -303,7 +277,6 @@ static GemmPlan plan_gemm_search(const GemmProblem& g, int precision) {
   for (int c = 0; c < kNumCfgs; ++c) {
     if (kCfgs[c].eff <= 0.f) continue;
     if (is_glds_cfg(c) && (g.mode != MODE_FWD || g.avec != 4 || g.bvec != 4 || g.plain || g.no_glds)) continue;
-    if (c == kGen2Cfg && (!g.gen2_ok || env_flag_no_gen2())) continue;
     const int bm = kCfgs[c].bm, bn = kCfgs[c].bn;
     const int tm = (g.M + bm - 1) / bm, tn = (g.N + bn - 1) / bn;
     const long tiles = (long)tm * tn;
@@ -341,7 +314,6 @@ static GemmPlan plan_gemm_search(const GemmProblem& g, int precision) {
         best.tiles_n = tn;
         best.ws_bytes = splitk > 1 ? (size_t)splitk * g.M * g.N * 4 : 0;
         best.streamk = 0;
-        best.sk_sliced = 0;
       }
     }
     // stream-K: equal shares of the (tile, k-tile) iterations for one or two blocks per CU — no tile quantisation, and
@@ -355,12 +327,8 @@ static GemmPlan plan_gemm_search(const GemmProblem& g, int precision) {
         const long per = (iters + grid - 1) / grid;
         // blocks meeting in one tile: their slabs are added one after the other by the fixup, so few tiles with very
         // long K (bwd-filter of the 3-channel layers, dense layers) stay with classic split-K and its flat reduction
-        long meet = (nk + per - 1) / per + 1;
-        // bwd-filter: K (the pixel axis) in eight slices, one per XCD — each XCD streams its own eighth of x and dz
-        long meet_sliced = 0;
-        const bool sliced = !env_flag_no_sliced() && sk_sliced_ok(g.mode, tiles, nk, grid, &meet_sliced);
-        if (force_streamk <= 0 && ((sliced ? meet_sliced > 48 : meet > 16) || tiles < 24)) continue;
-        if (sliced) meet = meet_sliced / 4;
+        const long meet = (nk + per - 1) / per + 1;
+        if (force_streamk <= 0 && (meet > 16 || tiles < 24)) continue;
         double t = (double)bm * bn * per * 32.0 / (96.5e3 * kCfgs[c].eff) * (grid <= 256 ? 0.62 : 1.0);
         // ~1.5 slabs per block are written and read back, then the split tiles are written once more
         const double slabs = std::min<double>(1.5 * grid, 2.0 * tiles) * bm * bn * 4.0;
@@ -376,7 +344,6 @@ static GemmPlan plan_gemm_search(const GemmProblem& g, int precision) {
           best.tiles_m = tm;
           best.tiles_n = tn;
           best.streamk = grid;
-          best.sk_sliced = sliced ? 1 : 0;
           best.ws_bytes = (size_t)2 * grid * ((size_t)bm * bn + bn) * 4;
         }
       }
@@ -565,7 +532,7 @@ int launch_igemm(int mode, const GemmPlan& plan, int avec, int bvec, IgemmParams
   if (plan.streamk > 0) {
     if (!ws) return set_error(A3D_EWORKSPACE, "igemm: stream-K needs a workspace");
     const size_t tile_elems = (size_t)kCfgs[plan.cfg].bm * kCfgs[plan.cfg].bn;
-    p.streamk = plan.sk_sliced ? 2 : 1;
+    p.streamk = 1;
     p.sk_ws = static_cast<float*>(ws);
     p.sk_bias = p.sk_ws + (size_t)2 * plan.streamk * tile_elems;
     p.div_nk = make_fastdiv((uint32_t)std::max(1, (p.K + 31) / 32));
@@ -581,9 +548,9 @@ int launch_igemm(int mode, const GemmPlan& plan, int avec, int bvec, IgemmParams
   p.dbg = tune_int("A3D_DBG", 0);
   static const bool plan_log = tune_int("A3D_PLAN_LOG", 0) != 0;       // tuning aid: one line per launch on stderr
   if (plan_log)
-    fprintf(stderr, "a3d plan: mode %d M %d N %d K %d -> %s %d (%dx%d) splitk %d streamk %d%s grid %u\n", mode, p.M, p.N, p.K,
+    fprintf(stderr, "a3d plan: mode %d M %d N %d K %d -> %s %d (%dx%d) splitk %d streamk %d grid %u\n", mode, p.M, p.N, p.K,
             plan.ring ? "ring" : "cfg", plan.ring ? plan.ring - 1 : plan.cfg, plan.ring ? kRingCfgs[plan.ring - 1].bm : kCfgs[plan.cfg].bm,
-            plan.ring ? kRingCfgs[plan.ring - 1].bn : kCfgs[plan.cfg].bn, plan.splitk, plan.streamk, plan.sk_sliced ? " (K-sliced)" : "", grid);
+            plan.ring ? kRingCfgs[plan.ring - 1].bn : kCfgs[plan.cfg].bn, plan.splitk, plan.streamk, grid);
   TimingSlot slot{};
   {
     a3d_timing_record& r = slot.rec;
@@ -596,7 +563,7 @@ int launch_igemm(int mode, const GemmPlan& plan, int avec, int bvec, IgemmParams
     } else {
       r.bm = kCfgs[plan.cfg].bm; r.bn = kCfgs[plan.cfg].bn; r.waves_m = kCfgWavesM[plan.cfg];
       r.nwaves = kCfgNWaves[plan.cfg]; r.bk = kCfgs[plan.cfg].bk;
-      r.lds_dma = plan.cfg == kGen2Cfg ? 5 : (plan.cfg >= kFirstGldsCfg && avec == 4 && bvec == 4);
+      r.lds_dma = plan.cfg >= kFirstGldsCfg && avec == 4 && bvec == 4;
     }
     r.avec = avec; r.bvec = bvec; r.splitk = plan.splitk; r.m = p.M; r.n = p.N; r.k = p.K; r.ms = 0.f;
     r.flops = 2.0 * p.M * p.N * p.K;
@@ -766,29 +733,13 @@ struct ConvProblem {
   GemmProblem g;
 };
 
-// May this layer / direction run on the second-generation kernel (igemm2.h)?  By the descriptor alone: the callers clear the
-// flag again when an operand is not 16-byte aligned or the launch takes another form (window runs, dense streams).
-static bool gen2_desc_ok(const a3d_conv_desc* d, int mode) {
-  if (d->precision != A3D_PREC_F32 || d->storage) return false;
-  if (mode == MODE_FWD) return d->c % 32 == 0 && d->ldx % 4 == 0 && d->k % 4 == 0;
-  if (mode == MODE_BWD_D) return d->k % 32 == 0 && d->ldy % 4 == 0;
-  return d->c % 4 == 0 && d->ldx % 4 == 0 && d->k % 4 == 0 && d->ldy % 4 == 0;
-}
-
 static GemmProblem fwd_problem(const a3d_conv_desc* d) {
   GemmProblem g;
   g.mode = MODE_FWD;
   g.M = d->n * d->ho * d->wo; g.N = d->k; g.K = d->r * d->s * d->c;
   g.avec = (d->c % 4 == 0 && d->ldx % 4 == 0) ? 4 : 1;
   g.bvec = (d->k % 4 == 0) ? 4 : 1;
-  g.gen2_ok = gen2_desc_ok(d, MODE_FWD);
   return g;
-}
-// workspace of a problem whichever of the two kernel generations a launch ends up on
-static size_t plan_ws_either(GemmProblem g, int precision) {
-  size_t need = plan_gemm(g, precision).ws_bytes;
-  if (g.gen2_ok) { g.gen2_ok = 0; need = std::max(need, plan_gemm(g, precision).ws_bytes); }
-  return need;
 }
 static GemmProblem bwd_d_problem(const a3d_conv_desc* d) {
   GemmProblem g;
@@ -796,7 +747,6 @@ static GemmProblem bwd_d_problem(const a3d_conv_desc* d) {
   g.M = d->n * d->h * d->w; g.N = d->c; g.K = d->r * d->s * d->k;
   g.avec = (d->k % 4 == 0 && d->ldy % 4 == 0) ? 4 : 1;
   g.bvec = (d->k % 4 == 0) ? 4 : 1;
-  g.gen2_ok = gen2_desc_ok(d, MODE_BWD_D);
   return g;
 }
 static GemmProblem bwd_f_problem(const a3d_conv_desc* d) {
@@ -805,7 +755,6 @@ static GemmProblem bwd_f_problem(const a3d_conv_desc* d) {
   g.M = d->r * d->s * d->c; g.N = d->k; g.K = d->n * d->ho * d->wo;
   g.avec = (d->c % 4 == 0 && d->ldx % 4 == 0) ? 4 : 1;
   g.bvec = (d->k % 4 == 0 && d->ldy % 4 == 0) ? 4 : 1;
-  g.gen2_ok = gen2_desc_ok(d, MODE_BWD_F);
   return g;
 }
 
@@ -910,7 +859,7 @@ size_t a3d_conv2d_fwd_ws_bytes(const a3d_conv_desc* d) {
   if (check_desc(d) != A3D_OK) return 0;
   if (stencil1_applicable(d)) return 0;
   // (a maximum over the paths a launch may take: which one it is also depends on the operands' alignment)
-  size_t need = plan_ws_either(fwd_problem(d), d->precision);
+  size_t need = plan_gemm(fwd_problem(d), d->precision).ws_bytes;
   {                                              // ... the LDS-DMA kernel's plan among them (its split-K slabs: dense layers)
     const int both = A3D_STORE_X_BF16 | A3D_STORE_W_BF16;
     GemmProblem g = fwd_problem(d);
@@ -1077,7 +1026,6 @@ static int conv_fwd_impl(const a3d_conv_desc* d, const float* x, const float* w,
   RunForm rf{};
   const bool prepared = (d->hints & A3D_HINT_W_PREPARED) != 0;
   const bool run = run_form_ok(d, x, &rf) && (prepared || (ws && ws_bytes >= run_filter_bytes(d, rf)));
-  if (run || g.avec != 4 || g.bvec != 4 || (out2 && out2->ptr)) g.gen2_ok = 0;
   // (the prepared layout was chosen for a 16-byte aligned x — fwd_filter_form — and this launch reads it with THAT row padding)
   A3D_CHECK_ARG(!prepared || (run && aligned16(w) && aligned16(x)),
                 "conv2d_fwd: A3D_HINT_W_PREPARED on a launch that reads the filter as stored, or with x off the 16-byte grid");
@@ -1234,7 +1182,7 @@ static bool bwd_d_class(const a3d_conv_desc* d, int ph, int pw, BwdDClass* c) {
 size_t a3d_conv2d_bwd_data_ws_bytes(const a3d_conv_desc* d) {
   if (check_desc(d) != A3D_OK) return 0;
   if (d->stride == 1) {
-    size_t need = plan_ws_either(bwd_d_problem(d), d->precision);
+    size_t need = plan_gemm(bwd_d_problem(d), d->precision).ws_bytes;
     const int both = A3D_STORE_Y_BF16 | A3D_STORE_W_BF16;
     GemmProblem g = bwd_d_problem(d);
     g.ring_ok = d->precision == A3D_PREC_BF16 && (d->storage & both) == both && d->c % 8 == 0 && d->k % 8 == 0;
@@ -1246,7 +1194,7 @@ size_t a3d_conv2d_bwd_data_ws_bytes(const a3d_conv_desc* d) {
   for (int ph = 0; ph < d->stride; ++ph)
     for (int pw = 0; pw < d->stride; ++pw) {
       BwdDClass c;
-      if (bwd_d_class(d, ph, pw, &c)) need = std::max(need, plan_ws_either(c.g, d->precision));
+      if (bwd_d_class(d, ph, pw, &c)) need = std::max(need, plan_gemm(c.g, d->precision).ws_bytes);
     }
   return need;
 }
@@ -1278,7 +1226,6 @@ int a3d_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w,
       GemmProblem g = c.g;
       if (!vec_ok_a) g.avec = 1;
       if (!vec_ok_b) g.bvec = 1;
-      if (g.avec != 4 || g.bvec != 4 || g.K == 0) g.gen2_ok = 0;
       IgemmParams p;
       fill_common(p, g);
       rc = apply_storage(p, g, d->precision, d->storage & A3D_STORE_Y_BF16, d->storage & A3D_STORE_W_BF16,
@@ -1350,7 +1297,6 @@ int a3d_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w,
         IgemmParams& p = multi.p[i];
         GemmProblem g = bwd_d_problem(d);
         g.M = p.M; g.K = p.K; g.avec = multi_avec; g.bvec = multi_bvec;
-        if (g.avec != 4 || g.bvec != 4 || g.K == 0) g.gen2_ok = 0;
         GemmPlan plan = plan_gemm(g, d->precision);
         if (plan.ws_bytes > ws_bytes)
           return set_error(A3D_EWORKSPACE, "conv2d_bwd_data: need %zu workspace bytes", plan.ws_bytes);
@@ -1493,11 +1439,6 @@ size_t a3d_conv2d_bwd_filter_ws_bytes(const a3d_conv_desc* d) {
   GemmProblem g0 = bwd_f_problem(d);
   GemmPlan plan = plan_gemm(g0, d->precision);       // the plan without the LDS-DMA kernel: a launch may fall back to it (a dw
   size_t need = plan.ws_bytes + (plan.splitk > 1 ? (size_t)plan.splitk * d->k * 4 : 0);      // off the 16-byte grid: ADVICE r4)
-  if (g0.gen2_ok) {                                  // ... or to the first-generation kernel (operands off the 16-byte grid)
-    g0.gen2_ok = 0;
-    const GemmPlan p1 = plan_gemm(g0, d->precision);
-    need = std::max(need, p1.ws_bytes + (p1.splitk > 1 ? (size_t)p1.splitk * d->k * 4 : 0));
-  }
   if (bwd_f_ring_ok(d)) {
     g0.ring_ok = 1;
     GemmPlan pr = plan_gemm(g0, d->precision);
@@ -1539,7 +1480,6 @@ int a3d_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* d
     ws_used = run_filter_bytes(d, rf);
     out = static_cast<float*>(ws);
   }
-  if (run || g.avec != 4 || g.bvec != 4) g.gen2_ok = 0;
   IgemmParams p;
   fill_common(p, g);
   rc = apply_storage(p, g, d->precision, d->storage & A3D_STORE_X_BF16, d->storage & A3D_STORE_Y_BF16, false, d->c, d->ldx,
@@ -1597,7 +1537,7 @@ size_t a3d_dense_fwd_ws_bytes(int m, int k, int n) {
   a3d_conv_desc d = dense_desc(m, k, n);
   if (check_desc(&d) != A3D_OK) return 0;
   // the GEMM a3d_dense_fwd plans (never the few-channel convolution paths: a dense layer of <= 4 inputs is still a GEMM)
-  return std::max(plan_ws_either(fwd_problem(&d), A3D_PREC_F32), dense_stream_ws_bytes(m, k, n));
+  return std::max(plan_gemm(fwd_problem(&d), A3D_PREC_F32).ws_bytes, dense_stream_ws_bytes(m, k, n));
 }
 
 int a3d_dense_fwd(int m, int k, int n, const float* x, const float* w, const float* bias, float* y, int act,
@@ -1625,7 +1565,6 @@ int a3d_dense_fwd_ex2(int m, int k, int n, const float* x, const float* w, const
       !tune_int("A3D_NO_DENSE_KERNELS", 0))
     return dense_fwd_stream(m, k, n, x, w, bias, y, act, drop_keep, 2.f, ws, ws_bytes, static_cast<hipStream_t>(stream));
   GemmProblem g = fwd_problem(&d);
-  g.gen2_ok = 0;                                // dense layers: rows of weights, not 128-row pixel tiles
   if (!aligned16(x)) g.avec = 1;
   if (!aligned16(w)) g.bvec = 1;
   IgemmParams p;
@@ -1676,7 +1615,6 @@ int a3d_dense_bwd_data_ex2(int m, int k, int n, const float* dz, const float* w,
   if (rc != A3D_OK) return rc;
   A3D_CHECK_ARG(dz && w && dx, "dense_bwd_data: null tensor");
   GemmProblem g = bwd_d_problem(&d);
-  g.gen2_ok = 0;                                // dense layers: rows of weights, not 128-row pixel tiles
   if (!aligned16(dz)) g.avec = 1;
   if (!aligned16(w)) g.bvec = 1;
   IgemmParams p;

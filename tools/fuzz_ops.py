@@ -419,20 +419,17 @@ def run_image_form(n, h, w, c, k, ks, st):
 def force_plan():
     """Half of the cases pin a tile config and either a split-K factor or a stream-K grid (the planner's own picks cover
     only a few of the combinations the kernels support)."""
-    for v in ('A3D_FORCE_CFG', 'A3D_FORCE_SPLITK', 'A3D_FORCE_STREAMK', 'A3D_FORCE_SK_SLICED'):
+    for v in ('A3D_FORCE_CFG', 'A3D_FORCE_SPLITK', 'A3D_FORCE_STREAMK'):
         os.environ.pop(v, None)
     u = rng.random()
     if u < 0.5:
         return 'auto'
-    os.environ['A3D_FORCE_CFG'] = str(int(rng.integers(0, 12)))      # 11: the second-generation kernel (its twin where it does not apply)
+    os.environ['A3D_FORCE_CFG'] = str(int(rng.integers(0, 11)))
     if u < 0.75:
         os.environ['A3D_FORCE_SPLITK'] = str(int(rng.choice([1, 2, 3, 5, 8, 13])))
         return 'cfg%s sk%s' % (os.environ['A3D_FORCE_CFG'], os.environ['A3D_FORCE_SPLITK'])
     os.environ['A3D_FORCE_STREAMK'] = str(int(rng.choice([1, 2, 3, 7, 8, 32, 64, 100, 256, 512, 700])))
-    if rng.random() < 0.5:        # bwd-filter shares cut from per-XCD K slices (where the shape allows it)
-        os.environ['A3D_FORCE_SK_SLICED'] = '1'
-    return 'cfg%s streamk%s%s' % (os.environ['A3D_FORCE_CFG'], os.environ['A3D_FORCE_STREAMK'],
-                                  ' sliced' if 'A3D_FORCE_SK_SLICED' in os.environ else '')
+    return 'cfg%s streamk%s' % (os.environ['A3D_FORCE_CFG'], os.environ['A3D_FORCE_STREAMK'])
 
 
 t_end = time.time() + budget
@@ -442,7 +439,7 @@ while time.time() < t_end:
     u = rng.random()
     if u < 0.05 * R5:
         # round 5's kernels: their own plans, no forced tiles
-        for v in ('A3D_FORCE_CFG', 'A3D_FORCE_SPLITK', 'A3D_FORCE_STREAMK', 'A3D_FORCE_SK_SLICED'):
+        for v in ('A3D_FORCE_CFG', 'A3D_FORCE_SPLITK', 'A3D_FORCE_STREAMK'):
             os.environ.pop(v, None)
         forced = 'auto'
         kind = int(rng.integers(0, 3))
@@ -458,7 +455,7 @@ while time.time() < t_end:
             err = run_image_form(*case)
             case = ('bf16 image form',) + case
     elif u < 0.05 * R5 + 0.05:
-        for v in ('A3D_FORCE_CFG', 'A3D_FORCE_SPLITK', 'A3D_FORCE_STREAMK', 'A3D_FORCE_SK_SLICED'):
+        for v in ('A3D_FORCE_CFG', 'A3D_FORCE_SPLITK', 'A3D_FORCE_STREAMK'):
             os.environ.pop(v, None)                       # both paths on the weight-streaming kernels
         forced = 'auto'
         case, err = run_dense_adam()
@@ -478,7 +475,7 @@ while time.time() < t_end:
         err = max(e16 * TOL / TOL_BF16_OUT, e32 * TOL / TOL_BF16_DW)      # each judged against its own tolerance
         case = ('conv bf16s',) + case
     elif u < 0.50:
-        for v in ('A3D_FORCE_CFG', 'A3D_FORCE_SPLITK', 'A3D_FORCE_STREAMK', 'A3D_FORCE_SK_SLICED'):
+        for v in ('A3D_FORCE_CFG', 'A3D_FORCE_SPLITK', 'A3D_FORCE_STREAMK'):
             os.environ.pop(v, None)
         forced = 'auto'
         case = conv_case_bf16s()

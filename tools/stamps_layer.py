@@ -17,7 +17,7 @@ name, mode = sys.argv[1], sys.argv[2]
 if len(sys.argv) > 3 and int(sys.argv[3]) >= 0:
     os.environ['A3D_FORCE_CFG'] = sys.argv[3]
     os.environ['A3D_FORCE_SPLITK'] = sys.argv[4] if len(sys.argv) > 4 else '1'
-EXTRA = [('gemm', 25, 40, 2400, 256, 1, 1, 'VALID'), ('gemmT', 25, 40, 256, 2400, 1, 1, 'VALID')]      # plain GEMMs as 1x1 convs (tools/gen2_ab.py)
+EXTRA = [('gemm', 25, 40, 2400, 256, 1, 1, 'VALID'), ('gemmT', 25, 40, 256, 2400, 1, 1, 'VALID')]      # plain GEMMs as 1x1 convs
 _, h, w, c, k, ks, st, pad = next(l for l in LAYERS + EXTRA if l[0] == name)
 d = ops.conv_desc(B, h, w, c, k, ks, ks, st, pad)
 x = torch.randn((B, h, w, c), device='cuda')

@@ -37,7 +37,7 @@ for name, h, w, c, k, ks, st, pad in LAYERS:
     for mode, fn in modes.items():
         clear(); t_auto = timeit(fn)
         res = []
-        for ci in (0, 1, 4, 7, 8, 9, 10, 11):
+        for ci in (0, 1, 4, 7, 8, 9, 10):
             for kind, vals in (('sk', (1, 2, 3, 4, 6, 8, 13, 16, 32, 64, 128)), ('st', (256, 512))):
                 for v in vals:
                     clear(); os.environ['A3D_FORCE_CFG'] = str(ci)
