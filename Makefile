@@ -72,6 +72,14 @@ endif
 train: ${DATA_DIR}
 	${SCRIPT} ${SCRIPT_PARAMETERS} ${DATASET}
 
+# the newest checkpoint of ${CKPT_DIR}/${MODEL}_${RUNID} on ${DATA_DIR}/${DATASET}/test.tfrecords (ann3depth_amd/evaluate.py);
+# more flags through EVAL_ARGS, e.g. EVAL_ARGS="--resolution record --predictions pred.npy"
+EVAL_ARGS ?=
+.PHONY: evaluate
+evaluate:
+	python3 -O -m ann3depth_amd.evaluate --ckptdir=${CKPT_DIR} --datadir=${DATA_DIR} --model=${MODEL} --id=${RUNID} \
+		--batchsize=${BATCHSIZE} ${EVAL_ARGS} ${DATASET}
+
 # raw downloads -> PNG pairs of one size (the reference's `make preprocess`, Makefile:118-121), without h5py / scipy.misc;
 # NYU only (tools/data_preprocessor.py)
 .PHONY: preprocess

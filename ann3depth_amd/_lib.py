@@ -84,6 +84,9 @@ SIGNATURES = {
                                        c_size_t, _P]),
     'a3d_conv2d_fwd_ex2': (c_int, [_D, _P, _P, _P, _P, c_int, POINTER(SecondOutput), _P, c_size_t, _P]),
     'a3d_silog_loss_bwd_ex': (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_int, _P]),
+    'a3d_depth_metrics_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'a3d_depth_metrics': (c_int, [c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, c_float, c_float, c_float, c_float, _P, _P,
+                                  c_size_t, _P]),
     'a3d_cast_bf16': (c_int, [c_size_t, _P, _P, c_int, _P]),
     'a3d_cast_rows': (c_int, [c_size_t, c_int, _P, c_int, c_int, _P, c_int, c_int, _P]),
     'a3d_pad_channels_bf16': (c_int, [c_size_t, c_int, _P, c_int, _P, _P]),

@@ -298,6 +298,88 @@ class ShuffleBatch:
         return out_images, out_depths
 
 
+class OrderedBatch(ShuffleBatch):
+    """tf.train.batch(..., allow_smaller_final_batch=True) over the records of `records` (one epoch for the test split):
+    every record comes out exactly once and in file order, B at a time; the last batch may hold fewer than B, and the
+    dequeue after it raises OutOfRangeError.  Readers decode in parallel into slots of the same staging pool as
+    ShuffleBatch (same allocate / dequeue / release / materialise / kind interface, uint8 staging included), but a reader
+    takes its records AND their slots in one step under the queue lock, so the records that hold slots are always the
+    next ones in file order and the consumer never waits behind a full queue for a record nobody could decode."""
+
+    def __init__(self, records, convert, batch_size, capacity, num_threads=2, in_flight_batches=3):
+        super().__init__(records, convert, batch_size, capacity, 0, num_threads=num_threads,
+                         in_flight_batches=in_flight_batches)
+        self.next_seq = 0           # file-order number of the next record a reader takes
+        self.head = 0               # file-order number of the next record dequeue() hands out
+        self.done = {}              # decoded records: number -> slot
+        self.total = None           # number of records, once the source ran dry
+
+    def _produce(self):
+        try:
+            while True:
+                with self.cv:
+                    while (not self.closed and self.total is None
+                           and (self.next_seq - self.head >= self.capacity or not self.free)):
+                        self.cv.wait()
+                    if self.closed or self.total is not None:
+                        return
+                    want = max(1, min(self.RECORDS_PER_CALL, len(self.free), self.capacity - (self.next_seq - self.head)))
+                    try:
+                        recs = self._next_records(want)
+                    except StopIteration:
+                        self.total = self.next_seq
+                        self.cv.notify_all()
+                        self.ready.notify_all()
+                        return
+                    first = self.next_seq
+                    self.next_seq += len(recs)
+                    slots = [self.free.popleft() for _ in recs]
+                self._decode(recs, slots)                                    # C code, outside the GIL
+                with self.cv:
+                    for j, slot in enumerate(slots):
+                        self.done[first + j] = slot
+                    self.ready.notify()
+        except BaseException as e:                  # surfaced by dequeue(): never swallow a corrupt record
+            with self.cv:
+                self.error = e
+                self.ready.notify_all()
+        finally:
+            with self.cv:
+                self.live -= 1
+                self.ready.notify_all()
+
+    def dequeue(self):
+        """-> list of at most batch_size slot numbers, in file order (their contents stay valid until release())."""
+        self.start()
+        with self.cv:
+            while True:
+                if self.error is not None:
+                    raise self.error
+                want = self.B if self.total is None else min(self.B, self.total - self.head)
+                if want <= 0:
+                    raise OutOfRangeError('all records of the epoch have been dequeued')
+                if all(self.head + j in self.done for j in range(want)):
+                    break
+                if self.live == 0:
+                    raise OutOfRangeError('input queue is closed')
+                self.ready.wait()
+            picks = [self.done.pop(self.head + j) for j in range(want)]
+            self.head += want
+            self._wake_producers(want)
+        return picks
+
+    def next_batch(self, out_images=None, out_depths=None):
+        """Dequeue into fresh host arrays ([b,H,W,3], [b,H',W',1]) float32, b <= batch_size."""
+        slots = self.dequeue()
+        out_images = np.empty((len(slots),) + self.images.shape[1:], np.float32)
+        out_depths = np.empty((len(slots),) + self.depths.shape[1:], np.float32)
+        for b, s in enumerate(slots):
+            out_images[b] = self.materialise(s, 0)
+            out_depths[b] = self.materialise(s, 1)
+        self.release(slots)
+        return out_images, out_depths
+
+
 class BatchHandle:
     """What `inputs()` returns in place of a TF tensor: one output (0 = inputs, 1 = targets) of a ShuffleBatch."""
 
@@ -306,9 +388,11 @@ class BatchHandle:
 
 
 def inputs(datadir, dataset, batch_size=32, train_or_test='train', epochs=None, rank=0, world=1, seed=None,
-           num_threads=None):
+           num_threads=None, shuffle=True):
     """src/data.py:28-55.  Returns (inputs, targets) handles; `inputs.pipeline.next_batch()` dequeues
-    ([B,H,W,3], [B,H',W',1]) float32 arrays, `.dequeue()` the slots of the staging pool."""
+    ([B,H,W,3], [B,H',W',1]) float32 arrays, `.dequeue()` the slots of the staging pool.  shuffle=False: the records in
+    file order, each once per epoch, the last batch possibly short (OrderedBatch) — what evaluation on the test split
+    reads."""
     epochs = epochs if train_or_test == 'train' else 1
     pipeline = _get_pipeline(dataset)
     base_dir = os.path.join(datadir, dataset)
@@ -317,6 +401,10 @@ def inputs(datadir, dataset, batch_size=32, train_or_test='train', epochs=None, 
         if not os.path.exists(f):
             raise FileNotFoundError(f)
     records = pipeline.reader(files, epochs, rank, world)
+    if not shuffle:
+        sb = OrderedBatch(records, pipeline.convert, batch_size, capacity=4 * batch_size,    # no shuffle: a short lookahead
+                          num_threads=num_threads or default_reader_threads())
+        return BatchHandle(sb, 0), BatchHandle(sb, 1)
     sb = ShuffleBatch(records, pipeline.convert, batch_size, capacity=20 * batch_size,
                       min_after_dequeue=5 * batch_size, num_threads=num_threads or default_reader_threads(),
                       seed=seed)

@@ -1,0 +1,253 @@
+"""Evaluation driver: restore an MSDN checkpoint and measure it on the test split.
+
+The converter writes ``test.tfrecords`` beside ``train.tfrecords`` (tools/data_tf_converter.py, src/data.py:58-59);
+training never reads it.  This driver reads every test record once, in file order (data.OrderedBatch), runs the
+network's forward without targets (MSDNReplica.predict: dropout off, no loss, weights untouched) and reports the held-out
+error metrics of Eigen et al. 2014, Table 1, for the coarse and the coarse + fine output (ops.depth_metrics on the GPU,
+ops.summarize_depth_metrics on the host), plus the training objective on the test split.
+
+    python -m ann3depth_amd.evaluate nyu --model msdn --id r1 [--checkpoint PATH] [--resolution grid|record] ...
+
+Output: one JSON line on stdout, ``<ckptdir>/<model>_<id>/eval-<global_step>.json`` and TensorBoard scalars
+``eval/{coarse,fine}/<metric>`` at the checkpoint's global step.  Exit code 2 when there is nothing to evaluate (no
+checkpoint, no test split) or the request is unsupported (DCNF, more than one process).
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import _lib, data, ops, summary, tfckpt
+from .ann3depth import latest_checkpoint
+
+OUTPUTS = ('coarse', 'fine')
+
+
+def _say(msg):
+    print(f'evaluate: {msg}', file=sys.stderr, flush=True)
+
+
+class EvalOp:
+    """The test split's batches on the device, in file order.  Like models.TrainOp: the staging pool is pinned memory,
+    a batch is DMA'd on a copy stream into one of two device buffers, and batch k+1 is in flight while batch k computes.
+    run(fn) calls fn(images, depths, n) on the current stream with batch k's device tensors (B rows, the first n of them
+    this batch's records; each uint8 when every record of the batch staged that feature as pixel values) and returns
+    what fn returns; OutOfRangeError after the last batch."""
+
+    def __init__(self, pipeline, batchsize, device):
+        self.pipeline, self.B = pipeline, batchsize
+        pipeline.allocate(lambda shape: torch.empty(shape, dtype=torch.float32).pin_memory().numpy(),
+                          lambda shape: torch.empty(shape, dtype=torch.uint8).pin_memory().numpy())
+        self.pool = (torch.from_numpy(pipeline.images), torch.from_numpy(pipeline.depths))
+        self.pool_u8 = None
+        if pipeline.images_u8 is not None:
+            self.pool_u8 = (torch.from_numpy(pipeline.images_u8), torch.from_numpy(pipeline.depths_u8))
+        self.dev = [tuple(torch.empty((batchsize,) + tuple(p.shape[1:]), device=device) for p in self.pool)
+                    for _ in range(2)]
+        self.dev_u8 = [tuple(torch.empty((batchsize,) + tuple(p.shape[1:]), device=device, dtype=torch.uint8)
+                             for p in self.pool) for _ in range(2)] if self.pool_u8 is not None else None
+        self.cur = [None, None]
+        self.copy_stream = torch.cuda.Stream(device=device)
+        self.copied = [None, None]
+        self.consumed = [None, None]
+        self.held = [[], []]
+        self.k = 0
+        self.end = None
+        self._prefetch(0)
+        self._prefetch(1)
+
+    def _prefetch(self, j):
+        if self.end is not None:
+            return
+        i = j & 1
+        try:
+            slots = self.pipeline.dequeue()
+        except BaseException as e:          # raised when batch j would have been consumed
+            self.end = (j, e)
+            return
+        if self.consumed[i] is not None:
+            self.copy_stream.wait_event(self.consumed[i])
+        pl = self.pipeline
+        cur = []
+        kinds = int(np.bitwise_and.reduce(pl.kind[slots])) if self.pool_u8 is not None else 0
+        for which in (0, 1):
+            as_u8 = bool(kinds & (1 << which))
+            if not as_u8 and self.pool_u8 is not None:
+                for s in slots:
+                    pl.materialise(s, which)
+            cur.append((self.dev_u8 if as_u8 else self.dev)[i][which])
+        ids = (ctypes.c_int32 * len(slots))(*slots)
+        with torch.cuda.stream(self.copy_stream):
+            for which in (0, 1):
+                src = (self.pool_u8 if cur[which].dtype == torch.uint8 else self.pool)[which]
+                ops.check(_lib.load().a3d_h2d_gather(cur[which].data_ptr(), src.data_ptr(), ids, len(slots), len(src),
+                                                     src[0].numel() * src.element_size(), self.copy_stream.cuda_stream),
+                          'a3d_h2d_gather')
+            ev = torch.cuda.Event()
+            ev.record(self.copy_stream)
+        self.cur[i] = tuple(cur)
+        self.copied[i] = ev
+        self.held[i] = slots
+
+    def run(self, fn):
+        i = self.k & 1
+        if self.end is not None and self.end[0] == self.k:
+            raise self.end[1]
+        cur = torch.cuda.current_stream()
+        cur.wait_event(self.copied[i])
+        out = fn(self.cur[i][0], self.cur[i][1], len(self.held[i]))
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        self.consumed[i] = ev
+        self.copied[i].synchronize()
+        self.pipeline.release(self.held[i])
+        self.held[i] = []
+        self.k += 1
+        self._prefetch(self.k + 1)
+        return out
+
+
+class Evaluator:
+    """The per-batch work: predict, targets on the grid (the training step's resize), metric rows and the objective."""
+
+    def __init__(self, replica, resolution='grid', min_depth=0., max_depth=float('inf'), clamp_lo=1e-3,
+                 clamp_hi=float('inf'), keep_predictions=False):
+        from .models import OUT_H, OUT_W
+        self.rep, self.resolution = replica, resolution
+        self.kw = dict(min_depth=min_depth, max_depth=max_depth, clamp_lo=clamp_lo, clamp_hi=clamp_hi)
+        dev = replica.device
+        self.t = torch.empty((replica.B, OUT_H, OUT_W), device=dev)
+        self.silog_ws = {}              # per batch size: the arrival ticket of a3d_silog_loss_fwd sits at ws[2 * b]
+        self.rows = {o: [] for o in OUTPUTS}
+        self.losses = {o: [] for o in OUTPUTS}
+        self.counts = []
+        self.predictions = [] if keep_predictions else None
+
+    def __call__(self, images, depths, n):
+        coarse, fine = self.rep.predict(images, n)
+        ops.resize_bilinear_tf1(depths[:n], self.t[:n].view(n, self.t.shape[1], self.t.shape[2], 1))
+        target = self.t[:n] if self.resolution == 'grid' else depths[:n]
+        for name, out in zip(OUTPUTS, (coarse, fine)):
+            self.rows[name].append(ops.depth_metrics(out[:n], target, **self.kw))
+            loss = torch.empty(1, device=out.device)
+            ws = self.silog_ws.get(n)
+            if ws is None:
+                ws = self.silog_ws[n] = ops.silog_ws(n, out.device)
+            ops.silog_loss_fwd(out[:n], self.t[:n], loss, ws)                    # the mean over these n images
+            self.losses[name].append(loss)
+        self.counts.append(n)
+        if self.predictions is not None:
+            self.predictions.append(fine[:n].clone())
+
+    def results(self):
+        torch.cuda.synchronize()
+        out = {}
+        n = np.asarray(self.counts, np.float64)
+        for name in OUTPUTS:
+            res = ops.summarize_depth_metrics(torch.cat(self.rows[name]))
+            per_batch = torch.cat(self.losses[name]).double().cpu().numpy()
+            res['silog'] = float((per_batch * n).sum() / n.sum())
+            out[name] = res
+        return out
+
+
+def find_checkpoint(args, run_dir):
+    if args.checkpoint:
+        path = args.checkpoint
+        return path if (os.path.isfile(path) or tfckpt.is_bundle(path)) else None
+    return latest_checkpoint(run_dir)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if args.model == 'dcnf':
+        _say('DCNF evaluation (CRF inference per image) is not implemented; only --model msdn can be evaluated.')
+        return 2
+    if args.model != 'msdn':
+        _say(f'unknown model {args.model!r}; only msdn can be evaluated.')
+        return 2
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        _say('evaluation runs in one process on one GPU; start it without a distributed launcher.')
+        return 2
+    run_dir = os.path.join(args.ckptdir, args.model + ('' if not args.id else f'_{args.id}'))
+    ckpt = find_checkpoint(args, run_dir)
+    if not ckpt:
+        _say(f'no checkpoint found ({args.checkpoint or run_dir}); refusing to evaluate untrained weights.')
+        return 2
+    try:
+        inputs, _ = data.inputs(args.datadir, args.dataset, args.batchsize, train_or_test='test', shuffle=False)
+    except FileNotFoundError as e:
+        _say(f'no test split: {e} is missing.')
+        return 2
+    if not torch.cuda.is_available():
+        raise RuntimeError('ann3depth_amd needs an MI355X: evaluation has no CPU fallback')
+    from .models import MSDNReplica
+    dev = torch.device('cuda', torch.cuda.current_device())
+    replica = MSDNReplica(args.batchsize, device=dev, precision=args.precision, keep_dense_grads=False)
+    _say(f'restoring {ckpt}')
+    if tfckpt.is_bundle(ckpt):                       # as ann3depth.Session.__enter__ restores
+        replica.load_tf_variables(tfckpt.read_bundle(ckpt))
+    else:
+        replica.load_state_dict(torch.load(ckpt, map_location=dev))
+    step = replica.global_step
+    pipeline = inputs.pipeline
+    ev = Evaluator(replica, args.resolution, args.min_depth, args.max_depth, args.clamp_lo, args.clamp_hi,
+                   keep_predictions=bool(args.predictions))
+    op = EvalOp(pipeline, args.batchsize, dev)
+    try:
+        while True:
+            try:
+                op.run(ev)
+            except data.OutOfRangeError:
+                break
+    finally:
+        pipeline.close()
+    res = ev.results()
+    records = int(sum(ev.counts))
+    out = {'checkpoint': ckpt, 'global_step': step, 'dataset': args.dataset, 'records': records,
+           'resolution': args.resolution, 'precision': args.precision,
+           'min_depth': args.min_depth, 'max_depth': args.max_depth, 'clamp_lo': args.clamp_lo, 'clamp_hi': args.clamp_hi,
+           **res}
+    if args.predictions:
+        np.save(args.predictions, torch.cat(ev.predictions).cpu().numpy() if ev.predictions else
+                np.zeros((0,) + tuple(replica.fine.shape[1:3]), np.float32))
+    os.makedirs(run_dir, exist_ok=True)
+    with open(os.path.join(run_dir, f'eval-{step}.json'), 'w') as f:
+        json.dump(out, f, indent=1)
+    events = summary.EventFileWriter(run_dir)
+    events.add_scalars(step, {f'eval/{o}/{k}': float(v) for o in OUTPUTS for k, v in res[o].items()})
+    events.close()
+    print(json.dumps(out), flush=True)
+    return 0
+
+
+def parse_args(argv=None):
+    """The training driver's flags that apply to evaluation (src/ann3depth.py:221-254), plus the evaluation's own."""
+    p = argparse.ArgumentParser(description='Evaluate an MSDN checkpoint on <datadir>/<dataset>/test.tfrecords.')
+    p.add_argument('dataset', default='nyu', type=str, help='The dataset to use.')
+    p.add_argument('--model', '-m', default='msdn', type=str, help='Model name (msdn).')
+    p.add_argument('--batchsize', '-b', default=32, type=int, help='Batchsize')
+    p.add_argument('--ckptdir', '-p', default='checkpoints', help='Checkpoint directory')
+    p.add_argument('--id', default='', type=str, help='Checkpoint path suffix.')
+    p.add_argument('--datadir', '-d', default='data', type=str, help='The data directory containing the datasets.')
+    p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16x3', 'bf16', 'bf16s'],
+                   help='Arithmetic of the conv contractions, as in training.')
+    p.add_argument('--checkpoint', default='', type=str,
+                   help='A .pt file or TF bundle prefix instead of the newest checkpoint of <ckptdir>/<model>_<id>.')
+    p.add_argument('--resolution', default='grid', choices=['grid', 'record'],
+                   help='grid: targets resized to 55x74 as the training step does; record: the depth map as stored, '
+                        'the prediction resampled at its pixels.')
+    p.add_argument('--min-depth', default=0., type=float, help='Valid targets are > this.')
+    p.add_argument('--max-depth', default=float('inf'), type=float, help='Valid targets are <= this.')
+    p.add_argument('--clamp-lo', default=1e-3, type=float, help='Predictions are clamped to at least this.')
+    p.add_argument('--clamp-hi', default=float('inf'), type=float, help='Predictions are clamped to at most this.')
+    p.add_argument('--predictions', default='', type=str, help='Write the fine predictions [N,55,74] to this .npy.')
+    return p.parse_args(argv)
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -725,8 +725,11 @@ class MSDNReplica:
         phase (1 coarse / 2 fine / 3 none trained) runs every conv that feeds a max pool fused with it: the pre-pool
         activations c0, c1, f1 are then NOT written.  The network being trained also records the position of each
         maximum (a0, a1 / af1): MaxPoolGrad routes dy to that position and the fused ReluGrad only asks whether the
-        maximum is positive, so the backward needs nothing else of c0 / c1 / f1.  phase None keeps every activation."""
-        if images.shape[:3] == depths.shape[:3]:
+        maximum is positive, so the backward needs nothing else of c0 / c1 / f1.  phase None keeps every activation.
+        depths None (predict()): the input images are already in self.x, no target is resized and no loss computed."""
+        if depths is None:
+            pass
+        elif images.shape[:3] == depths.shape[:3]:
             ops.resize_bilinear_tf1_pair(images, self.x, depths, self.t)
         else:
             ops.resize_bilinear_tf1(images, self.x)
@@ -833,10 +836,30 @@ class MSDNReplica:
                 self._pool(self.f1, self.cat, extra=self.coarse, c=63)                        # pool + concat fused
             self._conv('fine/second/conv2d', self.cat, self.f2)
             self._conv('fine/third', self.f2, self.fine)
-            ops.silog_loss_fwd(self.fine, self.t, self.loss_fine, self.ws_f)
-        ops.silog_loss_fwd(self.coarse, self.t, self.loss_coarse, self.ws_c)
+            if depths is not None:
+                ops.silog_loss_fwd(self.fine, self.t, self.loss_fine, self.ws_f)
+        if depths is not None:
+            ops.silog_loss_fwd(self.coarse, self.t, self.loss_coarse, self.ws_c)
         if join:
             self._join()
+
+    def predict(self, images, n=None):
+        """The network's depth maps for a batch of images, without targets: (coarse, fine), each [B, 55, 74] float32
+        (views of this replica's buffers, valid until its next forward).  images [m, H, W, 3] float32, or the uint8 pixel
+        values of converter-written records, m <= B; only rows [0, n) (default m) are read, rows n .. B of the network
+        input are zero, so a short last batch runs at the replica's B and its rows [0, n) are those of a full batch.
+        The phase-3 forward (conv + pool fused, no argmax recorded) with dropout off, tf.layers.dropout(training=False)
+        (src/models.py:230).  Weights, gradients, Adam slots and global_step are left as they are; the side stream is
+        joined before returning."""
+        B = self.B
+        n = images.shape[0] if n is None else int(n)
+        if not 0 < n <= min(B, images.shape[0]):
+            raise ValueError(f'predict: n = {n} rows of a batch of {images.shape[0]} images, replica batch {B}')
+        ops.resize_bilinear_tf1(images[:n], self.x[:n])
+        if n < B:
+            self.x[n:].zero_()
+        self.forward(images, None, None, join=True, phase=3)
+        return self.coarse.view(B, OUT_H, OUT_W), self.fine.view(B, OUT_H, OUT_W)
 
     def _sharded_in_flight(self):
         """The deferred dense bucket is a reduce-scatter feeding only the m slot: nothing in the forward needs it, it is due

@@ -340,6 +340,70 @@ def silog_loss_bwd(out, tgt, ws, dout, dout16=None):
     return dout
 
 
+METRIC_COLUMNS = ('n', 'abs_rel', 'sq_rel', 'sq', 'log', 'log_sq', 'log10', 'delta1', 'delta2', 'delta3', 'nonfinite')
+# A3D_METRIC_* (include/a3d.h): the per-image sums of a3d_depth_metrics, in this column order
+
+
+def depth_metrics(pred, target, *, min_depth=0., max_depth=float('inf'), clamp_lo=1e-3, clamp_hi=float('inf'), rows=None):
+    """Per-image error sums of Eigen et al. 2014, section 4: pred [n, ph, pw(, 1)] float32 on the model grid; target
+    [n, th, tw(, 1)] float32 or the uint8 pixel values of a converter-written record.  A target of another size than the
+    prediction is compared at its own pixels, the prediction sampled there as ResizeBilinear (align_corners=False) would
+    resample it.  Returns float64 [n, 11] (`rows`, or a new tensor) with the columns of METRIC_COLUMNS; see
+    summarize_depth_metrics for the metrics.  Stream-ordered, no synchronisation."""
+    n = pred.shape[0]
+    if target.shape[0] != n:
+        raise ValueError(f'depth_metrics: {n} predictions, {target.shape[0]} targets')
+    if pred.dtype != torch.float32 or target.dtype not in (torch.float32, torch.uint8):
+        raise TypeError('depth_metrics: pred float32, target float32 or uint8')
+    if not (pred.is_contiguous() and target.is_contiguous()):
+        raise ValueError('depth_metrics: contiguous tensors only')
+    ph, pw = pred.shape[1], pred.shape[2]
+    th, tw = target.shape[1], target.shape[2]
+    if pred[0].numel() != ph * pw or target[0].numel() != th * tw:
+        raise ValueError('depth_metrics: one channel only')
+    if rows is None:
+        rows = torch.empty((n, len(METRIC_COLUMNS)), dtype=torch.float64, device=pred.device)
+    assert rows.dtype == torch.float64 and rows.is_contiguous() and rows.shape[0] >= n and rows.shape[1] == len(METRIC_COLUMNS)
+    lib = _lib.load()
+    need = lib.a3d_depth_metrics_ws_bytes(n, th, tw)
+    ws, cap = _ws().get(need, pred.device)
+    check(lib.a3d_depth_metrics(n, ph, pw, _ptr(pred), th, tw, _ptr(target), int(target.dtype == torch.uint8), min_depth,
+                                max_depth, clamp_lo, clamp_hi, _ptr(rows), ws, cap, _stream()), 'a3d_depth_metrics')
+    return rows
+
+
+def summarize_depth_metrics(rows):
+    """The metrics of Eigen et al. 2014, Table 1, from depth_metrics rows (any number of batches stacked), on the host in
+    float64.  With q the clamped prediction, t the target and N the valid pixels of ALL images:
+      abs_rel  = sum |q - t| / t / N                sq_rel = sum (q - t)^2 / t / N
+      rmse     = sqrt(sum (q - t)^2 / N)            rmse_log = sqrt(sum (ln q - ln t)^2 / N)
+      log10    = sum |log10 q - log10 t| / N
+      delta_k  = share of pixels with max(q / t, t / q) < 1.25^k, k = 1, 2, 3
+      rmse_si  = sqrt(mean over the images with n > 0 of  sum d^2 / n - (sum d / n)^2),  d = ln q - ln t: eq. (1) with
+                 lambda = 1, per image, as the paper reports its scale-invariant error
+    and pixels = N, images = rows, images_without_valid_pixels, nonfinite = valid pixels whose prediction was not finite
+    (left out of every other sum).  A metric over no pixels is NaN."""
+    import numpy as np
+    r = (rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)).astype(np.float64)
+    r = r.reshape(-1, len(METRIC_COLUMNS))
+    col = {c: r[:, i] for i, c in enumerate(METRIC_COLUMNS)}
+    N = float(col['n'].sum())
+
+    def mean(c):
+        return float(col[c].sum()) / N if N > 0 else float('nan')
+    have = col['n'] > 0
+    nv = col['n'][have]
+    per_image = col['log_sq'][have] / nv - np.square(col['log'][have] / nv) if have.any() else np.zeros(0)
+    return {
+        'abs_rel': mean('abs_rel'), 'sq_rel': mean('sq_rel'), 'rmse': float(np.sqrt(mean('sq'))),
+        'rmse_log': float(np.sqrt(mean('log_sq'))), 'log10': mean('log10'),
+        'rmse_si': float(np.sqrt(max(per_image.mean(), 0.0))) if per_image.size else float('nan'),
+        'delta1': mean('delta1'), 'delta2': mean('delta2'), 'delta3': mean('delta3'),
+        'pixels': int(N), 'images': int(r.shape[0]), 'images_without_valid_pixels': int((~have).sum()),
+        'nonfinite': int(col['nonfinite'].sum()),
+    }
+
+
 def adam_apply_tf1(var, m, v, g, lr, beta1, beta2, eps, beta1_power, beta2_power, grad_scale=1.0, poisoned=None):
     """poisoned: optional int32[1] device tensor; bit 0 is set when the update left a non-finite weight behind."""
     if poisoned is not None:

@@ -257,6 +257,37 @@ int a3d_silog_loss_bwd(int b, int npix, const float* out, const float* tgt, cons
 int a3d_silog_loss_bwd_ex(int b, int npix, const float* out, const float* tgt, const float* ws, float* dout, void* dout_bf16,
                           int ld_bf16, void* stream);
 
+/* Held-out depth error sums of Eigen et al. 2014, section 4 (Table 1), for the test split the converter writes beside the
+ * training split (src/data.py:58-59: <datadir>/<dataset>/test.tfrecords).  pred [n, ph, pw] float32 (the model grid,
+ * 55 x 74); target [n, th, tw] float32, or (target_u8 != 0) the uint8 pixel values k of a3d_record_decode_u8, read as
+ * fl(fl(fl(k / 255) - 0.5) + 0.5) like a3d_resize_bilinear_tf1_ex.  When th x tw differs from ph x pw the prediction is
+ * sampled at each target pixel with the legacy ResizeBilinear(align_corners=False) mapping: the value is bit-identical to
+ * what a3d_resize_bilinear_tf1 writes at that pixel.
+ * Per pixel: the target t is valid iff finite and min_depth < t <= max_depth; at a valid pixel a non-finite sampled
+ * prediction is counted in column 10 and nowhere else, a finite one is clamped, q = min(max(p, clamp_lo), clamp_hi).
+ * Terms are fp32 (logf, log10f, correctly rounded division), accumulated in fp64 in a fixed order: the same bits on
+ * every run.  rows [n][A3D_METRIC_COLS] doubles, one row per image:
+ *   0 n valid pixels   1 sum |q-t|/t   2 sum (q-t)^2/t   3 sum (q-t)^2   4 sum d, d = ln q - ln t   5 sum d^2
+ *   6 sum |log10 q - log10 t|   7, 8, 9 count of max(q/t, t/q) < 1.25, 1.25^2, 1.25^3 (ratio in fp32)   10 non-finite q
+ * ws: a3d_depth_metrics_ws_bytes(n, th, tw) bytes (per-workgroup partial sums; 0 = bad shape).  Nothing outside rows[0, n)
+ * and the workspace is written.  Bad arguments: A3D_EINVAL, small workspace: A3D_EWORKSPACE, both before any launch. */
+#define A3D_METRIC_COLS 11
+#define A3D_METRIC_N 0
+#define A3D_METRIC_ABS_REL 1
+#define A3D_METRIC_SQ_REL 2
+#define A3D_METRIC_SQ 3
+#define A3D_METRIC_LOG 4
+#define A3D_METRIC_LOG_SQ 5
+#define A3D_METRIC_LOG10 6
+#define A3D_METRIC_DELTA1 7
+#define A3D_METRIC_DELTA2 8
+#define A3D_METRIC_DELTA3 9
+#define A3D_METRIC_NONFINITE 10
+size_t a3d_depth_metrics_ws_bytes(int n, int th, int tw);
+int a3d_depth_metrics(int n, int ph, int pw, const float* pred, int th, int tw, const void* target, int target_u8,
+                      float min_depth, float max_depth, float clamp_lo, float clamp_hi, double* rows, void* ws,
+                      size_t ws_bytes, void* stream);
+
 /* Keep mask of tf.layers.dropout(rate, training=True) (src/models.py:230): keep[i] = floor((1-rate) + u_i),
  * u from Philox4x32-10 keyed by (seed, step).  TF's own random stream is not reproducible, so parity tests pass
  * the mask in; the training driver draws it with this kernel. */

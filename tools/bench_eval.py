@@ -1,0 +1,98 @@
+"""Evaluation's costs on one GPU: MSDNReplica.predict from resident batches, ops.depth_metrics at the model grid and at
+full record resolution (achieved GB/s), and the evaluation loop end to end (ordered reader -> pinned -> H2D -> predict ->
+metrics) on a synthetic converter-written test shard, as a fraction of the resident predict rate.
+    python tools/bench_eval.py [n_records] > profiles/bench_eval.json"""
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from ann3depth_amd import data, evaluate, models, ops, tfrecord  # noqa: E402
+
+
+def timed(fn, iters=20, warmup=3):
+    """Mean ms per call from events around `iters` back-to-back calls on the current stream."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def main():
+    n_records = int(sys.argv[1]) if len(sys.argv) > 1 else 320
+    rng = np.random.default_rng(0)
+    out = {'device': torch.cuda.get_device_name(0)}
+    predict_ms = {}
+    for B, prec in ((32, 'fp32'), (64, 'bf16s')):
+        net = models.MSDNReplica(B, device='cuda:0', precision=prec)
+        img = torch.from_numpy(rng.integers(0, 256, (B, 480, 640, 3)).astype(np.uint8)).cuda()
+        ms = timed(lambda: net.predict(img))
+        predict_ms[(B, prec)] = ms
+        out[f'predict_ms_b{B}_{prec}'] = round(ms, 4)
+        out[f'predict_images_per_s_b{B}_{prec}'] = round(B / ms * 1e3, 1)
+        del net
+        torch.cuda.empty_cache()
+    B = 32
+    pred = torch.from_numpy(rng.uniform(0.1, 9, (B, 55, 74)).astype(np.float32)).cuda()
+    rows = torch.empty((B, len(ops.METRIC_COLUMNS)), dtype=torch.float64, device='cuda')
+    cases = {'grid_f32': torch.from_numpy(rng.uniform(0.1, 9, (B, 55, 74)).astype(np.float32)).cuda(),
+             'record_u8': torch.from_numpy(rng.integers(0, 256, (B, 480, 640)).astype(np.uint8)).cuda(),
+             'record_f32': torch.from_numpy(rng.uniform(0.1, 9, (B, 480, 640)).astype(np.float32)).cuda()}
+    for name, tgt in cases.items():
+        ms = timed(lambda: ops.depth_metrics(pred, tgt, rows=rows), iters=200, warmup=10)
+        nbytes = tgt.numel() * tgt.element_size() + pred.numel() * 4
+        out[f'depth_metrics_us_b{B}_{name}'] = round(ms * 1e3, 2)
+        out[f'depth_metrics_GBps_b{B}_{name}'] = round(nbytes / (ms * 1e-3) / 1e9, 1)
+        out[f'depth_metrics_share_of_predict_b{B}_{name}'] = round(ms / predict_ms[(32, 'fp32')], 4)
+    # end to end: the driver's loop (EvalOp + Evaluator) on a converter-written NYU-shaped test shard in /dev/shm
+    root = tempfile.mkdtemp(dir='/dev/shm' if os.path.isdir('/dev/shm') else None)
+    os.makedirs(os.path.join(root, 'nyu'))
+    img = rng.integers(0, 256, (480, 640, 3)).astype(np.float32) / np.float32(255) - np.float32(.5)
+    dep = rng.integers(0, 256, (480, 640, 1)).astype(np.float32) / np.float32(255) - np.float32(.5)
+    with tfrecord.TFRecordWriter(os.path.join(root, 'nyu', 'test.tfrecords')) as w:
+        for _ in range(n_records):
+            w.write_example(img, dep)
+    net = models.MSDNReplica(B, device='cuda:0')
+    for res in ('grid', 'grid', 'record'):           # the first pass warms the shard's pages and the pinned allocator
+        inputs, _ = data.inputs(root, 'nyu', B, 'test', shuffle=False)
+        ev = evaluate.Evaluator(net, res)
+        t0 = time.perf_counter()
+        op = evaluate.EvalOp(inputs.pipeline, B, net.device)      # (allocates and pins the staging pool)
+        op.run(ev)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        while True:
+            try:
+                op.run(ev)
+            except data.OutOfRangeError:
+                break
+        ev.results()
+        t2 = time.perf_counter()
+        inputs.pipeline.close()
+        # whole pass (pool allocation and the first batch's decode included) and the batches after the first
+        rate_all, rate = sum(ev.counts) / (t2 - t0), (sum(ev.counts) - ev.counts[0]) / (t2 - t1)
+        out[f'evaluate_images_per_s_b{B}_{res}_whole_pass'] = round(rate_all, 1)
+        out[f'evaluate_images_per_s_b{B}_{res}'] = round(rate, 1)
+        out[f'evaluate_fraction_of_resident_predict_b{B}_{res}'] = round(rate / (B / predict_ms[(32, 'fp32')] * 1e3), 3)
+    out['evaluate_records'] = n_records
+    out['reader_threads'] = data.default_reader_threads()
+    for f in os.listdir(os.path.join(root, 'nyu')):
+        os.remove(os.path.join(root, 'nyu', f))
+    os.rmdir(os.path.join(root, 'nyu'))
+    os.rmdir(root)
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
