@@ -126,10 +126,11 @@ class MSDNReplica:
     """One data-parallel replica of the MSDN training graph (src/models.py:203-367) on one GPU."""
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, global_step=0, beta2=1.0, reducer=None,
-                 precision='fp32', keep_dense_grads=True):
+                 precision='fp32', keep_dense_grads=True, overlap=True):
         """precision: arithmetic of the conv contractions — 'fp32' (exact, the parity default), 'bf16x3' (split
         operands on the bf16 matrix cores, ~1e-5) or 'bf16' (BASELINE config 5).  Tensors stay float32 in HBM; the
-        Cin = 3 layers, the dense layers and everything element-wise always compute in fp32."""
+        Cin = 3 layers, the dense layers and everything element-wise always compute in fp32.
+        overlap=False: everything on the current stream (the one-stream schedule the two-stream one must equal bit for bit)."""
         # keep_dense_grads=False (the training driver and bench.py on one GPU): under the reference's frozen optimizer the
         # gradient of the two dense kernels (268 MB) goes straight from the matrix cores into ApplyAdam's m slot
         # (ops.dense_bwd_filter_adam_tf1) and is never written; grad('coarse/dense/...') is then stale.  A data-parallel
@@ -141,7 +142,6 @@ class MSDNReplica:
         # layers' filters, fine/second's output (fine/third is a single-output-channel stencil on fp32), and the
         # tensors of the dense layers' small side (x, y, dz, dx: a few MB; dense_0's 201 MB of weights are read as bf16).
         self.bf16s = precision == 'bf16s'
-        self.fine_first_bf16 = self.conv0_image = self.fuse_casts = False
         self._c4_32_fresh = False
         if self.bf16s:
             precision = 'bf16'
@@ -151,26 +151,22 @@ class MSDNReplica:
         self.global_step = global_step
         self.reducer = reducer
         dev = self.device
-        # Second HIP stream (A3D_OVERLAP=0 turns it off): the fine network's forward — MFMA-bound, and in the coarse phase
+        # Second HIP stream (overlap=False turns it off): the fine network's forward — MFMA-bound, and in the coarse phase
         # needed only for its loss — runs beside the stretch of the coarse chain that is HBM-bound (dense forward, loss,
         # dense backward + ApplyAdam, conv2d_4 backward) and is joined before the large conv backward GEMMs start.
         # Measured on one MI355X at B = 32 (round 2): coarse-phase step 3.42 -> 3.32 ms.  The two kinds of kernel share
         # CUs only as far as the register file allows (two 8-wave GEMM blocks fill a SIMD's 512 registers), so the gain
         # is a quarter of the stretch, not all of it.  The dominant bwd-filter GEMMs run after the join, alone.
-        self.overlap = os.environ.get('A3D_OVERLAP', '1') == '1'
-        # A3D_SHARE_CU: which fine-network GEMMs are launched with A3D_HINT_SHARE_CU (at most two wavefronts per SIMD, so
-        # that the dense layers' weight-streaming kernels find room on every CU): 1 = both (default: 2.939 ms per step,
-        # alternating runs), 3 = fine/second only (2.947), 2 = fine/first only (2.98), 0 = none (2.985).  (fine/first's
+        self.overlap = overlap
+        # Beside the side stream, both fine-network GEMMs are launched with A3D_HINT_SHARE_CU (at most two wavefronts per
+        # SIMD, so that the dense layers' weight-streaming kernels find room on every CU): 2.939 ms per step (alternating
+        # runs) against 2.947 with fine/second only, 2.98 with fine/first only, 2.985 with neither.  (fine/first's
         # few-channel kernel keeps three chunks in flight per wave under the hint; with its stand-alone schedule it lost.)
         # Starting fine/first earlier (beside the coarse conv stack) or later (after the dense forward) both lose: an
         # MFMA-bound grid beside another MFMA-bound grid only takes CU slots from it.
-        share = int(os.environ.get('A3D_SHARE_CU', '1')) if (self.overlap and dev.type == 'cuda') else 0
-        self._share_names = {0: (), 1: ('fine/first/conv2d', 'fine/second/conv2d'), 2: ('fine/first/conv2d',),
-                             3: ('fine/second/conv2d',)}[share]
         self._shared_desc = {}
         # the few-channel forwards' filters in the layout their kernels read, repacked when the weights change instead of on
-        # every call (a3d_conv2d_fwd_prepare_filter; A3D_PREPARED_FILTERS=0: per call, as before round 5)
-        self.prepare_filters = os.environ.get('A3D_PREPARED_FILTERS', '1') != '0' and self.device.type == 'cuda'
+        # every call (a3d_conv2d_fwd_prepare_filter)
         self._prep = {}
         self._alone = ()          # fine-network GEMMs of the current forward that nothing runs beside (fine phase: fine/second)
         self._deferred = None     # (all-reduce handle, group, grad scale): CoarseDense bucket still in flight, see step()
@@ -193,18 +189,15 @@ class MSDNReplica:
         self._poison = None       # device flag: a non-finite gradient reached one of this rank's slices
         self._poison_seen = []    # [(event, pinned host copy of the all-rank MAX of the flag)] of earlier steps
         # conv + ReLU + max pool in one kernel inside step(): the pre-pool activations c0, c1, f1 are never written
-        # (the network being trained keeps one byte per pool window instead, see forward())
-        self.fuse_pool = precision == 'fp32' and os.environ.get('A3D_NO_FUSED_POOL', '0') != '1'
-        # bf16 storage: conv2d_1's pool in the LDS-DMA kernel's epilogue (argmax bytes + a bf16 MaxPoolGrad by index)
-        self.pool1_fused = self.bf16s and os.environ.get('A3D_BF16S_POOL1', '1') != '0'
-        self.pool0_fused = self.bf16s and os.environ.get('A3D_BF16S_POOL0', '1') != '0'
+        # (the network being trained keeps one byte per pool window instead, see forward()).  'bf16s' fuses all three in
+        # every phase, conv2d_1's pool in the LDS-DMA kernel's epilogue (argmax bytes + a bf16 MaxPoolGrad by index).
+        self.fuse_pool = precision == 'fp32'
         self.side = None
         if self.overlap and dev.type == 'cuda':
             # below the main stream's queue priority: a CU slot that frees up goes to the HBM-bound kernel first
             handle = ctypes.c_void_p()
             with torch.cuda.device(dev):
-                ops.check(_lib.load().a3d_stream_create(int(os.environ.get('A3D_SIDE_PRIORITY', '1')), ctypes.byref(handle)),
-                          'a3d_stream_create')
+                ops.check(_lib.load().a3d_stream_create(1, ctypes.byref(handle)), 'a3d_stream_create')
             self.side = torch.cuda.ExternalStream(handle.value, device=dev)
             self._side_handle = handle.value       # ExternalStream does not own it: returned in __del__
         shapes = collections.OrderedDict()
@@ -240,8 +233,8 @@ class MSDNReplica:
         self.x = buf(B, NET_H, NET_W, 3)
         self.t = buf(B, OUT_H, OUT_W, 1)
         # c0 / c1 exist only where a forward writes them: never under 'bf16s' with its pools in the conv epilogues (83 MB at B = 64)
-        self.c0 = None if self.pool0_fused else abuf(B, 55, 74, 96)
-        self.c1 = None if self.pool1_fused else abuf(B, 27, 37, 256)
+        self.c0 = None if self.bf16s else buf(B, 55, 74, 96)
+        self.c1 = None if self.bf16s else buf(B, 27, 37, 256)
         self.p0 = abuf(B, 27, 37, 96); self.p1 = abuf(B, 13, 18, 256)
         self.c2 = abuf(B, 13, 18, 384); self.c3 = abuf(B, 13, 18, 384); self.c4 = abuf(B, 6, 8, 256)
         self.drop = buf(B, 4096)
@@ -269,22 +262,21 @@ class MSDNReplica:
             self.c4_32 = buf(B, 6, 8, 256)                                          # the fp32 copy of c4 dense_0's filter gradient reads
             self.dz0_16 = torch.empty((B, 4096), device=dev, dtype=torch.bfloat16)  # dense_0's bwd-data takes dz0 as bf16
             # dense_1 ([4096, 4070]: rows of 8140 bytes, not whole 16-byte pieces) on the LDS-DMA kernel too: a bf16 copy of
-            # its kernel with rows of 4072 elements (the two pad columns zero, the bias padded alike); x (= drop), dz and y cross
-            # to that layout and back by a3d_cast_rows (0.5 - 1 MB each).  Its master weights, gradient and ApplyAdam stay fp32.
+            # its kernel with rows of 4072 elements (the two pad columns zero, the bias padded alike).  Its master weights,
+            # gradient and ApplyAdam stay fp32.
             # bf16 x / dz into the dense layers: the LDS-DMA kernel takes them as a weight stream of at most 64 rows (ring_plan,
             # igemm_host.hip); a larger batch keeps the dense layers' small side fp32 (B = 65..383 had no kernel)
+            # and dense_1 on the fp32 kernels.
+            # round 5: the casts between the bf16 conv stack and the fp32 dense side (c4 -> c4_32, drop -> drop16, coarse ->
+            # cat[..., 63], dz1 -> dz1_16, dz0 -> dz0_16) leave through the reductions that produce their sources
+            # (a3d_second_output) instead of five 5-us launches
             self.dense_bf16_x = B <= 64
-            # round 5: the casts between the bf16 conv stack and the fp32 dense side leave through the reductions that produce
-            # their sources (a3d_second_output) instead of five 5-us launches; A3D_BF16S_FUSE_CASTS=0: separate launches
-            self.fuse_casts = os.environ.get('A3D_BF16S_FUSE_CASTS', '1') != '0'
-            self.dense1_bf16 = os.environ.get('A3D_BF16S_DENSE1', '1') != '0' and self.dense_bf16_x
             if not self.dense_bf16_x:
                 self.dc4_32 = buf(B, 6, 8, 256)
             NP = (OUT_H * OUT_W + 7) // 8 * 8
             self.w1pad = torch.zeros((4096, NP), device=dev, dtype=torch.bfloat16)
             self.b1pad = torch.zeros((1, NP), device=dev)
             self.drop16 = torch.empty((B, 4096), device=dev, dtype=torch.bfloat16)
-            self.y1pad = torch.empty((B, NP), device=dev)
             self.dz1_16 = torch.zeros((B, NP), device=dev, dtype=torch.bfloat16)       # (columns 4070.. stay zero)
         # descriptors
         def D(*a):
@@ -301,20 +293,16 @@ class MSDNReplica:
         }
         # conv -> ReLU -> pool blocks on the 3-channel image: filter gradient straight from the POOLED map's gradient (MaxPoolGrad
         # by index + ReluGrad while the kernel stages its operand): dc0 / df1 (50 / 131 MB at B = 32) are never written or read.
-        # fp32 arithmetic on the fp32 image in every precision mode.  A3D_FEWCH_POOLED=0: the separate launches.
+        # fp32 arithmetic on the fp32 image in every precision mode but 'bf16s'.
         self.d_few = {}
-        if os.environ.get('A3D_FEWCH_POOLED', '1') != '0' and dev.type == 'cuda':
+        if dev.type == 'cuda':
             # 'bf16s' (config 5): the same launch in bf16 arithmetic (fewch16.hip: fp32 image, bf16 pooled tensors, both operands
-            # transposed into LDS); A3D_BF16S_FEWCH16=0: fp32 arithmetic for fine/first, igemm_bf16 + MaxPoolGrad for conv2d_0
-            few_prec = 'bf16' if (self.bf16s and os.environ.get('A3D_BF16S_FEWCH16', '1') != '0') else 'fp32'
+            # transposed into LDS); conv2d_0 there: 68 + 11 us at B = 64 against 78 + 5 + 18 for igemm_bf16 + MaxPoolGrad by index
+            few_prec = 'bf16' if self.bf16s else 'fp32'
             for n, dd in (('coarse/conv/conv2d_0', ops.conv_desc(B, NET_H, NET_W, 3, 96, 11, 11, 4, 'VALID', precision=few_prec)),
                           ('fine/first/conv2d', ops.conv_desc(B, NET_H, NET_W, 3, 63, 9, 9, 2, 'VALID', precision=few_prec))):
                 if ops.conv2d_bwd_filter_pooled_supported(dd):
                     self.d_few[n] = dd
-            if self.bf16s and os.environ.get('A3D_BF16S_FEWCH0', '1') == '0':
-                # A3D_BF16S_FEWCH0=0: config 5's conv2d_0 on igemm_bf16 + MaxPoolGrad by index (78 + 5 + 18 us at B = 64; the fused
-                # kernel: 68 + 11 since its staging lost its lane masks, 91 + 11 before)
-                self.d_few.pop('coarse/conv/conv2d_0', None)
         # bf16 storage: per layer, which tensors of the forward / bwd-data / bwd-filter call are bf16 (ops.STORE_*), and
         # the bf16 copies of the kernels (refreshed whenever the fp32 masters change)
         self.store = {}
@@ -323,32 +311,22 @@ class MSDNReplica:
             X, W, Y = ops.STORE_X, ops.STORE_W, ops.STORE_Y
             for n in ('coarse/conv/conv2d_1', 'coarse/conv/conv2d_2', 'coarse/conv/conv2d_3', 'coarse/conv/conv2d_4'):
                 self.store[n] = {'fwd': X | W | Y, 'bwd_d': X | W | Y, 'bwd_f': X | Y}
-            # conv2d_0 takes the fp32 image through the bf16 kernel (window runs of 36 floats, 16-byte loads) and writes c0
-            # as bf16; its filter stays fp32 (padded per call).  At B = 64: forward 93 us + pool against 204 us for the fp32
-            # conv + pool fusion, bwd-filter 108 us against 221 us.
-            n = 'coarse/conv/conv2d_0'
-            self.store[n] = {'fwd': Y, 'bwd_d': 0, 'bwd_f': Y}
-            # fine/first keeps fp32 arithmetic (its window runs start 24 bytes apart: 8-byte loads only, which the bf16
-            # kernel does not take): conv + ReLU + max pool in one kernel, of which only the pooled map (bf16) and an argmax
-            # byte per window reach HBM — f1, the largest activation of the model, is never written; its gradient comes
-            # back fp32
-            for n in ('fine/first/conv2d',):
-                self.d[n] = ops.with_storage(self.d[n], 0)
-                self.d[n].precision = ops.PREC['fp32']
-                self.store[n] = {'fwd': Y, 'bwd_d': 0, 'bwd_f': 0}
+            # conv2d_0's filter gradient where the pooled launch (d_few) does not take the shape: the fp32 image and a bf16 dc0
+            # through the bf16 kernel (window runs of 36 floats, 16-byte loads), 108 us against 221 us in fp32 at B = 64
+            self.store['coarse/conv/conv2d_0'] = {'bwd_f': Y}
+            # fine/first's filter gradient there stays fp32 (its window runs start 24 bytes apart: 8-byte loads only, which
+            # the bf16 kernel does not take)
+            self.d['fine/first/conv2d'].precision = ops.PREC['fp32']
             # f2 stays fp32 (fine/third is a single-output-channel stencil on fp32); df2 comes back from that layer's fused
             # backward as bf16, so fine/second's bwd-data and bwd-filter read two bf16 operands (the LDS-DMA kernel)
             self.store['fine/second/conv2d'] = {'fwd': X | W, 'bwd_d': W | X | Y, 'bwd_f': X | Y}
-            # ... except where fine/first has no backward (coarse phase, and once nothing trains any more): there its forward
-            # runs on the bf16 pipe from a 4-channel bf16 copy of the image (8-byte pixels: window runs 16 bytes apart),
-            # 0.41 -> 0.10 ms at B = 64, conv + ReLU + max pool in one launch (f1 is never written there either)
-            # round 5: also where it trains (fine phase) — config 5's arithmetic is bf16 throughout, the fp32 few-channel kernel
-            # took 0.38 ms of that phase's 1.73 at B = 64.  A3D_BF16S_FINE1=0: the fp32 conv + pool there, as before.
-            self.fine_first_bf16 = os.environ.get('A3D_BF16S_FINE1', '1') != '0'
+            # fine/first's forward runs on the bf16 pipe from a 4-channel bf16 copy of the image (8-byte pixels: window runs
+            # 16 bytes apart), conv + ReLU + max pool in one launch: f1, the largest activation of the model, is never written.
+            # 0.41 -> 0.10 ms at B = 64 where the layer does not train; where it trains (fine phase, round 5) the fp32
+            # few-channel kernel took 0.38 ms of that phase's 1.73.
             self.x4 = torch.empty((B, NET_H, NET_W, 4), device=dev, dtype=torch.bfloat16)
             # round 5: conv2d_0's forward from the same 4-channel bf16 image (conv3.hip's bf16 form, straight from L2) instead
-            # of the fp32 image through igemm_bf16's window runs.  A3D_BF16S_CONV0_IMAGE=0: as before.
-            self.conv0_image = os.environ.get('A3D_BF16S_CONV0_IMAGE', '1') != '0' and self.pool0_fused
+            # of the fp32 image through igemm_bf16's window runs
             self.w0_4 = torch.zeros((11, 11, 4, 96), device=dev)
             self.d0_4 = ops.with_storage(ops.conv_desc(B, NET_H, NET_W, 4, 96, 11, 11, 4, 'VALID', ldy=96, precision='bf16'),
                                          X | Y)
@@ -356,7 +334,7 @@ class MSDNReplica:
             self.d4 = ops.with_storage(ops.conv_desc(B, NET_H, NET_W, 4, 63, 9, 9, 2, 'VALID', ldy=64, precision='bf16'),
                                        X | Y)
             for n in list(self.store) + ['coarse/dense/dense_0']:
-                if n == 'coarse/dense/dense_0' or self.store[n]['fwd'] & W:
+                if n == 'coarse/dense/dense_0' or self.store[n].get('fwd', 0) & W:
                     self.wcopy[n] = torch.empty(self.shapes[n + '/kernel'], device=dev, dtype=torch.bfloat16)
             self.refresh_weight_copies()
 
@@ -370,11 +348,13 @@ class MSDNReplica:
             except Exception:          # noqa: BLE001 - interpreter shutdown: the driver reclaims the stream
                 pass
 
+    SHARE_CU = ('fine/first/conv2d', 'fine/second/conv2d')     # forwards hinted A3D_HINT_SHARE_CU beside the side stream
+
     def _desc(self, name, which):
         """The layer's conv descriptor for 'fwd' | 'bwd_d' | 'bwd_f', with that call's storage bits."""
         d = self.d[name]
         bits = self.store.get(name, {}).get(which, 0)
-        if which == 'fwd' and name in self._share_names and name not in self._alone:
+        if which == 'fwd' and self.side is not None and name in self.SHARE_CU and name not in self._alone:
             # a fine-network GEMM on the side stream beside the dense layers' weight streams: leave those room on every CU
             key = (name, bits)
             if key not in self._shared_desc:
@@ -392,7 +372,7 @@ class MSDNReplica:
 
     def _prepared(self, key, desc, w):
         """(descriptor, filter) for a few-channel forward: the prepared copy and the descriptor that says so, where the launch has one."""
-        if not self.prepare_filters:
+        if self.device.type != 'cuda':
             return desc, w
         pf = self._prep.get(key)
         if pf is None:
@@ -662,18 +642,6 @@ class MSDNReplica:
         d, w = self._fwd_operands(name)
         ops.conv2d_fwd(d, x, w, self._v(name + '/bias'), y, 'relu' if self.conv[name].relu else None)
 
-    def _pool(self, x, y, extra=None, c=None):
-        if self.bf16s:
-            ops.maxpool2x2_fwd_bf16(x, y, extra=extra, c=c)
-        else:
-            ops.maxpool2x2_fwd(x, y, extra=extra)
-
-    def _pool_bwd(self, x, dy, dx, c=None):
-        if self.bf16s:
-            ops.maxpool2x2_bwd_bf16(x, dy, dx, relu_mask=True, c=c)
-        else:
-            ops.maxpool2x2_bwd(x, dy, dx, relu_mask=True)
-
     @contextlib.contextmanager
     def _beside(self):
         """Enqueue the body on the side stream, ordered after everything enqueued on the current stream so far."""
@@ -696,7 +664,7 @@ class MSDNReplica:
         src = {'c0': (self.c0, self.p0, self.a0, 1), 'c1': (self.c1, self.p1, self.a1, 1),
                'f1': (self.f1, self.cat, self.af1, 2)}[which]
         full, pooled, arg, phase = src
-        if self.pooled_fwd != phase and not (self.bf16s and which == 'f1') and not (self.pool1_fused and which == 'c1') and not (self.pool0_fused and which == 'c0'):
+        if self.pooled_fwd != phase and not self.bf16s:
             return full
         if full is None:          # 'bf16s': the tensor does not exist at all
             full = torch.empty((pooled.shape[0],) + {'c0': (55, 74, 96), 'c1': (27, 37, 256), 'f1': (110, 148, 63)}[which],
@@ -739,9 +707,9 @@ class MSDNReplica:
         # fine phase: the main queue has nothing left to run beside fine/second (the coarse backward does not exist there and
         # the fine backward waits for this forward), so the launch takes the whole CU instead of leaving room (A3D_HINT_SHARE_CU)
         self._alone = ('fine/second/conv2d',) if phase == 2 else ()
-        if self.bf16s and (phase in (1, 3) or self.fine_first_bf16 or self.conv0_image) and not (self.fuse_pool and phase in (1, 2, 3)):
-            # the fine network's 4-channel bf16 image, on the main stream: the side stream's chain (fine/first .. loss) is
-            # the longer one at the join, the main stream idles there
+        if self.bf16s:
+            # the 4-channel bf16 image of conv2d_0's and fine/first's forwards, on the main stream: the side stream's chain
+            # (fine/first .. loss) is the longer one at the join, the main stream idles there
             ops.pad_channels_bf16(self.x, self.x4)
         fused = self.fuse_pool and phase in (1, 2, 3)
         self.pooled_fwd = phase if fused else None
@@ -751,34 +719,22 @@ class MSDNReplica:
             self._conv_pool('coarse/conv/conv2d_0', self.x, self.p0, self.a0 if train else None)
             self._conv_pool('coarse/conv/conv2d_1', self.p0, self.p1, self.a1 if train else None)
         elif self.bf16s:
-            if self.pool0_fused and self.conv0_image:
-                d, w = self._prepared(('conv2d_0/image', 0, 0, 0), self.d0_4, self.w0_4)
-                ops.conv2d_pool_fwd(d, self.x4, w, self._v('coarse/conv/conv2d_0/bias'), self.p0, 'relu', self.a0)
-            elif self.pool0_fused:
-                self._conv_pool('coarse/conv/conv2d_0', self.x, self.p0, self.a0)
-            else:
-                self._conv('coarse/conv/conv2d_0', self.x, self.c0)
-                self._pool(self.c0, self.p0)
-            if self.pool1_fused:        # conv + ReLU + pool in the LDS-DMA kernel's epilogue: c1 (33 MB at B = 64) is never written
-                self._conv_pool('coarse/conv/conv2d_1', self.p0, self.p1, self.a1)
-            else:
-                self._conv('coarse/conv/conv2d_1', self.p0, self.c1)
-                self._pool(self.c1, self.p1)
+            d, w = self._prepared(('conv2d_0/image', 0, 0, 0), self.d0_4, self.w0_4)
+            ops.conv2d_pool_fwd(d, self.x4, w, self._v('coarse/conv/conv2d_0/bias'), self.p0, 'relu', self.a0)
+            # conv + ReLU + pool in the LDS-DMA kernel's epilogue: c1 (33 MB at B = 64) is never written
+            self._conv_pool('coarse/conv/conv2d_1', self.p0, self.p1, self.a1)
         else:
             self._conv('coarse/conv/conv2d_0', self.x, self.c0)
-            self._pool(self.c0, self.p0)
+            ops.maxpool2x2_fwd(self.c0, self.p0)
             self._conv('coarse/conv/conv2d_1', self.p0, self.c1)
-            self._pool(self.c1, self.p1)
+            ops.maxpool2x2_fwd(self.c1, self.p1)
         def fine_first():
             with self._beside():    # beside the two weight-streaming dense layers
                 if lean_fine:
                     self._conv_pool('fine/first/conv2d', self.x, self.cat, self.af1 if phase == 2 else None)   # cat[..., :63]
-                elif self.bf16s and phase in (1, 3):        # conv + ReLU + pool in one launch: f1 is never written
-                    self._fine_first_image_form()
-                elif self.bf16s and self.fine_first_bf16:   # the same launch where the layer trains: it also records the window positions
-                    self._fine_first_image_form(self.af1)
-                elif self.bf16s:
-                    self._conv_pool('fine/first/conv2d', self.x, self.cat, self.af1)
+                elif self.bf16s:    # conv + ReLU + pool in one launch: f1 is never written; where the layer trains (not in
+                    # phases 1 and 3) it also records the window positions
+                    self._fine_first_image_form(None if phase in (1, 3) else self.af1)
                 else:
                     self._conv('fine/first/conv2d', self.x, self.f1)
         # where the side stream starts: ahead of conv2d_4's forward.  The fine forward is the longer chain of the stretch
@@ -789,7 +745,7 @@ class MSDNReplica:
         self._conv('coarse/conv/conv2d_3', self.c2, self.c3)
         fine_first()
         self._c4_32_fresh = False
-        if self.bf16s and self.dense_bf16_x and self.fuse_casts and phase == 1:
+        if self.bf16s and self.dense_bf16_x and phase == 1:
             # c4 also as float32 (dense_0's filter gradient reads it in that type) from the same reduction
             n4 = 'coarse/conv/conv2d_4'
             ops.conv2d_fwd(self._desc(n4, 'fwd'), self.c3, self._w(n4), self._v(n4 + '/bias'), self.c4, 'relu',
@@ -804,7 +760,7 @@ class MSDNReplica:
             # (its bf16 copy for dense_1 leaves through the same reduction: a3d_second_output, round 5)
             ops.dense_fwd_ex(self.c4.view(B, -1), self.wcopy['coarse/dense/dense_0'], b, self.drop, 'relu',
                              drop_keep=keep_mask, precision='bf16', storage=ops.STORE_W | ops.STORE_X,
-                             out2=ops.second_output(self.drop16) if (self.dense1_bf16 and self.fuse_casts) else None)
+                             out2=ops.second_output(self.drop16))
         elif self.bf16s:            # more than 64 rows: the LDS-DMA kernel's weight-stream tiles do not apply; fp32 x, bf16 weight copy
             ops.cast_bf16(self.c4, self.c4_32)
             ops.dense_fwd_ex(self.c4_32.view(B, -1), self.wcopy['coarse/dense/dense_0'], b, self.drop, 'relu',
@@ -812,19 +768,13 @@ class MSDNReplica:
         else:
             ops.dense_fwd(self.c4.view(B, -1), w, b, self.drop, 'relu', drop_keep=keep_mask)     # relu + dropout fused
         w, b = self._kb('coarse/dense/dense_1')
-        cat_done = False
-        if self.bf16s and self.dense1_bf16 and self.fuse_casts:
+        cat_done = self.bf16s and self.dense_bf16_x
+        if cat_done:
             # the padded GEMM (4072 columns) writes the 4070-column depth map AND channel 63 of the concat buffer from its
             # reduction: no cast_rows, no copy_channel launch
             ops.dense_fwd_ex(self.drop16, self.w1pad, self.b1pad, self.coarse.view(B, -1), None, precision='bf16',
                              storage=ops.STORE_W | ops.STORE_X, n=self.w1pad.shape[1],
                              out2=ops.second_output(self.cat, cols=OUT_H * OUT_W, step=64, offset=63, ld=OUT_H * OUT_W))
-            cat_done = True
-        elif self.bf16s and self.dense1_bf16:
-            ops.cast_bf16(self.drop, self.drop16)
-            ops.dense_fwd_ex(self.drop16, self.w1pad, self.b1pad, self.y1pad, None, precision='bf16',
-                             storage=ops.STORE_W | ops.STORE_X)
-            ops.cast_rows(self.y1pad, self.coarse.view(B, -1))
         else:
             ops.dense_fwd(self.drop, w, b, self.coarse.view(B, -1))
         with self._beside():
@@ -833,7 +783,7 @@ class MSDNReplica:
             elif lean_fine or self.bf16s:
                 ops.copy_channel(self.coarse, 0, self.cat, 63)                                # tf.concat([pool, coarse])
             else:
-                self._pool(self.f1, self.cat, extra=self.coarse, c=63)                        # pool + concat fused
+                ops.maxpool2x2_fwd(self.f1, self.cat, extra=self.coarse)                      # pool + concat fused
             self._conv('fine/second/conv2d', self.cat, self.f2)
             self._conv('fine/third', self.f2, self.fine)
             if depths is not None:
@@ -888,9 +838,9 @@ class MSDNReplica:
     # ---- backward of loss_coarse wrt coarse/* : src/models.py:318-324 ----
     def backward_coarse(self, after_dense=None, after_conv2=None, after_dense1=None):
         B = self.B
-        fused16 = self.bf16s and self.dense1_bf16 and self.fuse_casts
+        bf16_x = self.bf16s and self.dense_bf16_x
         ops.silog_loss_bwd(self.coarse, self.t, self.ws_c, self.dz1.view(B, OUT_H, OUT_W, 1),
-                           dout16=self.dz1_16 if fused16 else None)       # (dz1 a second time as bf16 rows of 4072: dense_1's bwd-data)
+                           dout16=self.dz1_16 if bf16_x else None)        # (dz1 a second time as bf16 rows of 4072: dense_1's bwd-data)
         self.settle()              # a reduce-scatter of the previous step may still be reading the dense gradient buffer
         n = 'coarse/dense/dense_1'
         self._bwd_filter(n, self.drop, self.dz1)
@@ -898,22 +848,18 @@ class MSDNReplica:
             after_dense1()         # dense_1's gradient (67 MB) is complete: first piece of the dense bucket
         # dropout-grad (x2 on kept units) and dense_0's ReluGrad in one mask: drop > 0  <=>  kept and relu active
         # (train=False, src/models.py:230: tf.layers.dropout is the identity; only the ReluGrad remains)
-        if self.bf16s and self.dense1_bf16:
-            if not fused16:
-                ops.cast_rows(self.dz1, self.dz1_16)
+        if bf16_x:
             ops.dense_bwd_data_ex(self.dz1_16, self.w1pad, self.dz0, mask=self.drop, scale=2.0 if self.dropout_on else 1.0,
                                   precision='bf16', storage=ops.STORE_W | ops.STORE_Y,
-                                  out2=ops.second_output(self.dz0_16) if fused16 else None)     # dz0 as bf16 too: dense_0's bwd-data
+                                  out2=ops.second_output(self.dz0_16))     # dz0 as bf16 too: dense_0's bwd-data
         else:
             ops.dense_bwd_data(self.dz1, self._v(n + '/kernel'), self.dz0, mask=self.drop, scale=2.0 if self.dropout_on else 1.0)
         n = 'coarse/dense/dense_0'
-        if self.bf16s and self.dense_bf16_x and not self._c4_32_fresh:   # the filter gradient takes c4 on the dense layers' fp32 side
-            ops.cast_bf16(self.c4, self.c4_32)      # (B > 64: the forward already made this copy; fused casts: conv2d_4's reduction did)
+        if bf16_x and not self._c4_32_fresh:    # the filter gradient takes c4 on the dense layers' fp32 side
+            ops.cast_bf16(self.c4, self.c4_32)      # (B > 64: the forward already made this copy; phase 1: conv2d_4's reduction did)
         flat = (self.c4_32 if self.bf16s else self.c4).view(B, -1)
         self._bwd_filter(n, flat, self.dz0)
-        if self.bf16s and self.dense_bf16_x:   # dz0 -> bf16 (1 MB); dc4 leaves as bf16, masked by the bf16 c4: no fp32 detour
-            if not fused16:
-                ops.cast_bf16(self.dz0, self.dz0_16)
+        if bf16_x:      # dc4 leaves as bf16, masked by the bf16 c4: no fp32 detour
             ops.dense_bwd_data_ex(self.dz0_16, self.wcopy[n], self.dc4.view(B, -1), mask=self.c4.view(B, -1), scale=1.0,
                                   precision='bf16', storage=ops.STORE_W | ops.STORE_X | ops.STORE_Y)
         elif self.bf16s:            # B > 64: fp32 dz0 and mask against the bf16 weight copy, dc4 through an fp32 buffer
@@ -943,24 +889,25 @@ class MSDNReplica:
         if after_conv2 is not None:
             after_conv2()          # gradients of conv2d_2..4 (the tail of the CoarseConv buffer) are complete
         self._bwd_data(n, self.dc2, self.dp1)
-        if self.pooled_fwd == 1 or self.pool1_fused:
+        pooled = self.pooled_fwd == 1 or self.bf16s         # the forward recorded a0 / a1 instead of writing c0 / c1
+        if pooled:
             ops.maxpool2x2_bwd_idx(self.a1, self.p1, self.dp1, self.dc1, relu_mask=True)
         else:
-            self._pool_bwd(self.c1, self.dp1, self.dc1)
+            ops.maxpool2x2_bwd(self.c1, self.dp1, self.dc1, relu_mask=True)
         n = 'coarse/conv/conv2d_1'
         dw(n, self.p0, self.dc1)
         self._bwd_data(n, self.dc1, self.dp0)
         n = 'coarse/conv/conv2d_0'
-        if (self.pooled_fwd == 1 or self.pool0_fused) and n in self.d_few:
+        if pooled and n in self.d_few:
             ops.conv2d_bwd_filter_pooled(self.d_few[n], self.x, self.dp0, self.p0, self.a0, self._g(n + '/kernel'),
                                          self._g(n + '/bias'))
             return
         if self.dc0 is None:
             self.dc0 = torch.empty((self.B, 55, 74, 96), device=self.device, dtype=self.dp0.dtype)
-        if self.pooled_fwd == 1 or self.pool0_fused:
+        if pooled:
             ops.maxpool2x2_bwd_idx(self.a0, self.p0, self.dp0, self.dc0, relu_mask=True)
         else:
-            self._pool_bwd(self.c0, self.dp0, self.dc0)
+            ops.maxpool2x2_bwd(self.c0, self.dp0, self.dc0, relu_mask=True)
         dw(n, self.x, self.dc0)
 
     # ---- backward of loss_fine wrt fine/* : src/models.py:333-338 ----
@@ -989,7 +936,7 @@ class MSDNReplica:
         if self.pooled_fwd == 2 or self.bf16s:                                 # both read channels 0..62 of dcat
             ops.maxpool2x2_bwd_idx(self.af1, self.cat, self.dcat, self.df1, relu_mask=True)
         else:
-            self._pool_bwd(self.f1, self.dcat, self.df1, c=63)
+            ops.maxpool2x2_bwd(self.f1, self.dcat, self.df1, relu_mask=True)
         self._bwd_filter(n, self.x, self.df1)
 
     # ---- one session.run(train_op) ----
@@ -1112,7 +1059,7 @@ class DCNFUnary:
         self.desc = {}
         # conv + ReLU + max pool in one kernel (fp32): the pre-pool activations (1.6 + 1.3 GB at batch 16) are never
         # written, one argmax byte per pool window serves the backward (see MSDNReplica.forward)
-        self.fuse_pool = precision == 'fp32' and os.environ.get('A3D_NO_FUSED_POOL', '0') != '1'
+        self.fuse_pool = precision == 'fp32'
         self.argmax, self.conv_hw = {}, {}
         self.few_pooled = False
         self.act['x'] = buf(P, DCNF_PATCH, DCNF_PATCH, 3)
@@ -1131,7 +1078,7 @@ class DCNFUnary:
         for n, i, o, _ in DCNF_DENSES:
             self.act[n] = buf(P, o)
         self.z = self.act['dense_2']
-        self.few_pooled = (self.fuse_pool and dev.type == 'cuda' and os.environ.get('A3D_FEWCH_POOLED', '1') != '0'
+        self.few_pooled = (self.fuse_pool and dev.type == 'cuda'
                            and ops.conv2d_bwd_filter_pooled_supported(self.desc['conv2d']))
 
     def var(self, name):
