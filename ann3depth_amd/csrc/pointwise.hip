@@ -341,9 +341,10 @@ __device__ __forceinline__ float masked_log(float v) {
 
 // kSilogParts blocks per sample (one sample is 4070 pixels at MSDN's size: with one block per sample 32 CUs each walked a
 // chain of load latencies and logarithms — 29 us on the step's critical path; now every CU holds one short piece).  Block
-// (b, part) leaves its partial sums in ws[2nb+1 + 2(b*parts+part) ..]; the block that finishes last (ticket in ws[2nb],
-// which wraps back to 0: nothing to re-initialise between calls) adds each sample's parts in part order — the same sum
-// whatever the timing — writes ws[2b] = sum d^2, ws[2b+1] = sum d for the backward kernel, and the batch mean.  The
+// (b, part) leaves its partial sums in ws[2nb+1 + 2(b*parts+part) ..]; the block that finishes last (ticket in ws[0],
+// which wraps back to 0: nothing to re-initialise between calls, and no batch size puts a sum there, so one workspace
+// serves calls of different batch sizes) adds each sample's parts in part order — the same sum whatever the timing —
+// writes ws[1+2b] = sum d^2, ws[2+2b] = sum d for the backward kernel, and the batch mean.  The
 // partials cross CUs as write-through stores, drained before the ticket, and are read back past the L1
 // (MI355X_MICROARCH.md, inter-workgroup visibility).
 constexpr int kSilogParts = A3D_SILOG_PARTS;
@@ -390,7 +391,7 @@ __global__ __launch_bounds__(256) void silog_fwd_kernel(const float* __restrict_
     __hip_atomic_store(&partials[2 * blockIdx.x + 1], red[1][0] + red[1][1] + red[1][2] + red[1][3], __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    last = atomicInc(reinterpret_cast<unsigned*>(ws + 2 * nb), total - 1u) == total - 1u;
+    last = atomicInc(reinterpret_cast<unsigned*>(ws), total - 1u) == total - 1u;
   }
   __syncthreads();
   if (!last || threadIdx.x >= 64) return;
@@ -402,8 +403,8 @@ __global__ __launch_bounds__(256) void silog_fwd_kernel(const float* __restrict_
       a2 += __hip_atomic_load(&partials[2 * (i * kSilogParts + q)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       a1 += __hip_atomic_load(&partials[2 * (i * kSilogParts + q) + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    ws[2 * i] = a2;
-    ws[2 * i + 1] = a1;
+    ws[1 + 2 * i] = a2;
+    ws[2 + 2 * i] = a1;
     s += a2 - c * (a1 * a1);
   }
   s = wave_sum(s);
@@ -423,7 +424,7 @@ __global__ __launch_bounds__(256) void silog_bwd_kernel(const float* __restrict_
     float g = 0.f;
     if (!isnan(lo)) {
       const float d = __fsub_rn(lo, masked_log(tgt[i]));
-      const float sd = ws[2 * smp + 1];
+      const float sd = ws[2 * smp + 2];
       g = __fdiv_rn(__fmul_rn(__fsub_rn(__fmul_rn(2.f, d), __fmul_rn(__fmul_rn(2.f, c), sd)), inv_b), arg);
     }
     dout[i] = g;
@@ -442,6 +443,12 @@ __device__ __forceinline__ void adam_one(float& var, float& m, float& v, float g
   var = __fsub_rn(var, __fdiv_rn(__fmul_rn(m, alpha), __fadd_rn(sq, eps)));
 }
 
+// what a3d_adam_apply_tf1_flag reports: the update CHANGED this value into a non-finite one (a NaN that stays a NaN, an
+// infinity that stays that infinity: nothing the other ranks' copies lack)
+__device__ __forceinline__ bool turned_non_finite(float before, float after) {
+  return !isfinite(after) && !(after == before || (isnan(after) && isnan(before)));
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ var, float* __restrict__ m,
                                                    float* __restrict__ v, const float* __restrict__ g, size_t count,
                                                    float omb1, float omb2, float alpha, float eps, float gscale,
@@ -457,7 +464,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ var, floa
       float gj = use_scale ? __fmul_rn(g4[j], gscale) : g4[j];
       float wj = w4[j], mj = m4[j], vj = v4[j];
       adam_one(wj, mj, vj, gj, omb1, omb2, alpha, eps);
-      bad |= !isfinite(wj);
+      bad |= turned_non_finite(w4[j], wj) || turned_non_finite(v4[j], vj);
       w4[j] = wj; m4[j] = mj; v4[j] = vj;
     }
     reinterpret_cast<f32x4*>(var)[i] = w4;
@@ -468,8 +475,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ var, floa
     const size_t i = nvec * 4 + threadIdx.x;
     if (i < count) {
       float gj = use_scale ? __fmul_rn(g[i], gscale) : g[i];
+      const float w0 = var[i], v0 = v[i];
       adam_one(var[i], m[i], v[i], gj, omb1, omb2, alpha, eps);
-      bad |= !isfinite(var[i]);
+      bad |= turned_non_finite(w0, var[i]) || turned_non_finite(v0, v[i]);
     }
   }
   if (poisoned && bad) atomicOr(poisoned, 1u);
@@ -495,7 +503,7 @@ __global__ __launch_bounds__(256) void adam_frozen_kernel(float* __restrict__ va
       const float gj = use_scale ? __fmul_rn(g4[j], gscale) : g4[j];
       m4[j] = __fadd_rn(m4[j], __fmul_rn(__fsub_rn(gj, m4[j]), omb1));
       const bool g_poison = !isfinite(__fmul_rn(gj, gj));
-      if (g_poison || !isfinite(m4[j])) {             // rare; `bad` only when it changes something (a NaN stays a NaN)
+      if (g_poison || !isfinite(m4[j])) {             // rare; `bad` only when it changes something (turned_non_finite)
         const size_t e = 4 * i + j;
         bad |= !isnan(var[e]) || (g_poison && !isnan(v[e]));
         if (g_poison) v[e] = qnan;
@@ -523,7 +531,9 @@ __global__ __launch_bounds__(256) void adam_frozen_kernel(float* __restrict__ va
 
 // ------------------------------------------------------------------ dropout keep mask (Philox4x32-10)
 // TF draws U[0,1) from its own Philox stream, which is not reproducible outside TF; this is the same generator
-// family keyed by (seed, step), one counter per 4 mask bytes.  keep = floor(keep_prob + u)  (nn.dropout, TF 1.3).
+// family keyed by (seed, step), one counter per 4 mask bytes.  keep = floor(keep_prob + u)  (nn.dropout, TF 1.3), written
+// as the comparison below: the same byte wherever the sum is below 2, and 1 instead of 2 where rate = 0 meets
+// u = 1 - 2^-24 (fl(1 + u) = 2, tie to even).
 __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
   const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
   const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
@@ -549,7 +559,7 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(uint8_t* __restrict__
       const size_t i = q * 4 + j;
       if (i < count) {
         const float u = (float)(c[j] >> 8) * (1.0f / 16777216.0f);      // 24 random bits -> [0,1)
-        keep[i] = (uint8_t)floorf(keep_prob + u);
+        keep[i] = __fadd_rn(keep_prob, u) >= 1.0f ? 1 : 0;
       }
     }
   }

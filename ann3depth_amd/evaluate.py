@@ -121,7 +121,7 @@ class Evaluator:
         self.kw = dict(min_depth=min_depth, max_depth=max_depth, clamp_lo=clamp_lo, clamp_hi=clamp_hi)
         dev = replica.device
         self.t = torch.empty((replica.B, OUT_H, OUT_W), device=dev)
-        self.silog_ws = {}              # per batch size: the arrival ticket of a3d_silog_loss_fwd sits at ws[2 * b]
+        self.silog_ws = {}              # per batch size (a3d_silog_loss_fwd's per-sample sums and partials)
         self.rows = {o: [] for o in OUTPUTS}
         self.losses = {o: [] for o in OUTPUTS}
         self.counts = []

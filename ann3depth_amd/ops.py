@@ -318,7 +318,8 @@ SILOG_PARTS = 8                      # A3D_SILOG_PARTS (include/a3d.h)
 
 
 def silog_ws(b, device):
-    """Workspace of silog_loss_fwd / _bwd for a batch of b: A3D_SILOG_WS_FLOATS(b) zeros (the ticket must start at zero)."""
+    """Workspace of silog_loss_fwd / _bwd for a batch of b (or any smaller one): A3D_SILOG_WS_FLOATS(b) zeros (the ticket, its
+    first word, must start at zero)."""
     return torch.zeros(2 * b + 1 + 2 * b * SILOG_PARTS, device=device)
 
 
@@ -405,7 +406,7 @@ def summarize_depth_metrics(rows):
 
 
 def adam_apply_tf1(var, m, v, g, lr, beta1, beta2, eps, beta1_power, beta2_power, grad_scale=1.0, poisoned=None):
-    """poisoned: optional int32[1] device tensor; bit 0 is set when the update left a non-finite weight behind."""
+    """poisoned: optional int32[1] device tensor; bit 0 is set when the update turned an element of var or v non-finite."""
     if poisoned is not None:
         check(_lib.load().a3d_adam_apply_tf1_flag(var.numel(), _ptr(var), _ptr(m), _ptr(v), _ptr(g), lr, beta1, beta2, eps,
                                                   beta1_power, beta2_power, grad_scale, _ptr(poisoned), _stream()),

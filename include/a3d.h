@@ -244,8 +244,9 @@ int a3d_resize_bilinear_tf1_ex(int n, int h, int w, int c0, const void* x0, int 
 int a3d_extract_patches(int n, int h, int w, int c, const float* x, int k, int stride, float* y, void* stream);
 
 /* Scale-invariant log loss (src/models.py:255-275).  out/tgt [b, npix]; loss: 1 float.  ws: A3D_SILOG_WS_FLOATS(b)
- * floats — [0, 2b) the per-sample sums the backward call reads, [2b] the arrival ticket of the single launch (zero before
- * the FIRST call, zero again after every call), then the partial sums of the A3D_SILOG_PARTS blocks that share a sample. */
+ * floats — [0] the arrival ticket of the single launch (zero before the FIRST call, zero again after every call; at the
+ * same place for every b, so a workspace sized for the largest batch serves calls of any smaller one in between), [1, 2b]
+ * the per-sample sums the backward call reads, then the partial sums of the A3D_SILOG_PARTS blocks that share a sample. */
 #define A3D_SILOG_PARTS 8
 #define A3D_SILOG_WS_FLOATS(b) ((b) * 2 + 1 + (b) * 2 * A3D_SILOG_PARTS)
 int a3d_silog_loss_fwd(int b, int npix, const float* out, const float* tgt, float* loss, float* ws, void* stream);
@@ -288,9 +289,12 @@ int a3d_depth_metrics(int n, int ph, int pw, const float* pred, int th, int tw, 
                       float min_depth, float max_depth, float clamp_lo, float clamp_hi, double* rows, void* ws,
                       size_t ws_bytes, void* stream);
 
-/* Keep mask of tf.layers.dropout(rate, training=True) (src/models.py:230): keep[i] = floor((1-rate) + u_i),
- * u from Philox4x32-10 keyed by (seed, step).  TF's own random stream is not reproducible, so parity tests pass
- * the mask in; the training driver draws it with this kernel. */
+/* Keep mask of tf.layers.dropout(rate, training=True) (src/models.py:230): keep[i] = 1 if fl((1-rate) + u_i) >= 1, else 0
+ * — TF-1.3's floor((1-rate) + u_i), except that the byte is 1, never 2, where rate = 0 meets u_i = 1 - 2^-24 and the float32
+ * sum rounds to 2.  0 <= rate < 1 (A3D_EINVAL otherwise); keep[count..] is not written.  u_i = (w >> 8) * 2^-24 with w word
+ * i % 4 of the Philox4x32-10 block whose counter is (q lo, q hi, step lo, step hi), q = i / 4, and whose key is (seed lo,
+ * seed hi): all 64 bits of seed and step count.  TF's own random stream is not reproducible, so parity tests pass the
+ * mask in; the training driver draws it with this kernel, which tests/test_gpu_pointwise.py holds to a numpy Philox. */
 int a3d_dropout_keep_mask(size_t count, uint64_t seed, uint64_t step, float rate, uint8_t* keep, void* stream);
 
 /* a3d_dense_fwd / a3d_dense_bwd_data with the arithmetic and storage of a3d_conv_desc: precision A3D_PREC_*, storage
@@ -311,7 +315,12 @@ int a3d_dense_bwd_data_ex2(int m, int k, int n, const float* dz, const float* w,
                            void* stream);
 
 /* float32 <-> bf16 (round to nearest even) of `count` elements: weight copies after ApplyAdam, and the two small tensors
- * that cross between the bf16 conv stack and the float32 dense layers (to_bf16 != 0: src float32 -> dst bf16). */
+ * that cross between the bf16 conv stack and the float32 dense layers (to_bf16 != 0: src float32 -> dst bf16).
+ * To bf16: ties go to the even neighbour, values past the largest bf16 go to infinity, the sign of zero is kept, float32
+ * denormals are NOT flushed (they round like any other value, as torch's cast does: 0x00018000 -> 0x0002), and a NaN gives
+ * a quiet NaN (sign and the top payload bits kept, the quiet bit set; callers must not rely on the payload).  To float32:
+ * exact for every bit pattern, bf16 denormals included.  a3d_cast_rows, a3d_pad_channels_bf16, a3d_copy_channel_bf16 and
+ * every other bf16 store of the pointwise kernels round the same way. */
 int a3d_cast_bf16(size_t count, const void* src, void* dst, int to_bf16, void* stream);
 /* The same between matrices of different row pitches: dst[r][c] = src[r][c] for c < cols, zero for cols <= c < ld_dst
  * (src_bf16 / dst_bf16: the element types).  The bf16 copy of tf.layers.dense's [4096, 4070] kernel (src/models.py:231)
@@ -371,8 +380,11 @@ int a3d_adam_apply_tf1(size_t count, float* var, float* m, float* v, const float
 /* The same ApplyAdam over one rank's SLICE of a parameter group (data-parallel replicas that reduce-scatter their
  * gradients instead of all-reducing them: each rank updates only the slice whose gradient sum it received — what
  * replaces the parameter server's per-variable update of src/ann3depth.py:77-92).  `poisoned` (device, may be NULL)
- * gets bit 0 set when the update left a non-finite value in var[0..count) — the only case in which the reference's
- * frozen optimizer (beta2 = 1) changes a weight at all, and the one the other ranks must then be told about. */
+ * gets bit 0 set when the update CHANGED an element of var[0..count) or v[0..count) into a non-finite value — the only
+ * case in which the reference's frozen optimizer (beta2 = 1) changes a weight at all, and the one the other ranks must then
+ * be told about: their copies of the slice no longer match its owner's.  A NaN that stays a NaN, an infinity that stays
+ * that infinity, and a non-finite value that was there on entry do not set it (the other ranks already hold them), so a
+ * weight once poisoned does not ask for a resync at every later step.  Both kernels behind this call report the same. */
 int a3d_adam_apply_tf1_flag(size_t count, float* var, float* m, float* v, const float* g, float lr, float beta1,
                             float beta2, float eps, float beta1_power, float beta2_power, float grad_scale,
                             unsigned int* poisoned, void* stream);
