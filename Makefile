@@ -73,7 +73,8 @@ train: ${DATA_DIR}
 	${SCRIPT} ${SCRIPT_PARAMETERS} ${DATASET}
 
 # the newest checkpoint of ${CKPT_DIR}/${MODEL}_${RUNID} on ${DATA_DIR}/${DATASET}/test.tfrecords (ann3depth_amd/evaluate.py);
-# more flags through EVAL_ARGS, e.g. EVAL_ARGS="--resolution record --predictions pred.npy"
+# MODEL=msdn (coarse and fine output) or MODEL=dcnf (unary output and the CRF's MAP depths); more flags through EVAL_ARGS,
+# e.g. EVAL_ARGS="--resolution record --predictions pred.npy"
 EVAL_ARGS ?=
 .PHONY: evaluate
 evaluate:

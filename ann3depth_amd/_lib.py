@@ -105,6 +105,7 @@ SIGNATURES = {
     'a3d_superpixel_hist': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P]),
     'a3d_pair_similarity': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P, _P, c_float, _P, _P, _P]),
     'a3d_crf_loss': (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_int, c_float, _P, _P, _P, _P]),
+    'a3d_crf_map': (c_int, [c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, _P]),
     'a3d_sgd_apply': (c_int, [c_size_t, _P, _P, c_float, _P]),
     'a3d_conv2d_pool_fwd': (c_int, [_D, _P, _P, _P, _P, c_int, _P, c_int, _P, c_size_t, _P]),
     'a3d_maxpool2x2_bwd_idx': (c_int, [c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P, c_int, _P]),

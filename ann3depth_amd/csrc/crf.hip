@@ -1,6 +1,7 @@
 // crf.hip — the pairwise part and the CRF negative log-likelihood of ann3depth's DCNF model
 // (src/models.py:20-48,91-177): 40x40 "superpixel" statistics, pair similarities, the 48x48 system A = I + D - R per
-// image (LU with partial pivoting in LDS, one wavefront per image), the loss and its gradient wrt the unary output z.
+// image (LU with partial pivoting in LDS, one wavefront per image), the loss and its gradient wrt the unary output z;
+// and, for evaluation, the field's MAP depths A^-1 z (crf_map_kernel), which the reference never forms.
 // A is a constant for the gradient: TF 1.3 registers no gradient for scatter_nd_update (oracle/dcnf.py states the
 // assumption).  All of it is tiny next to the unary conv stack; the kernels are written for clarity, not speed.
 #include <algorithm>
@@ -184,6 +185,96 @@ __global__ __launch_bounds__(64) void crf_loss_kernel(const float* __restrict__ 
   }
 }
 
+// MAP depths of the same field: y = A^-1 z.  One wavefront per image, [A | z] in LDS (row stride kMaxSp + 1 dwords: odd,
+// so the 32 lanes of an LDS access group hit 32 banks whether they read a column, one row each, or along one row).  LU
+// with the loss kernel's pivot rule; a row is eliminated with one lane per column, and only the rows whose multiplier
+// is not zero are visited: A is sparse (a superpixel has at most four neighbours, fill-in stays inside the band).
+// Then a column sweep by the whole wavefront: lane j keeps the right-hand side of row j in a register, and once y[i]
+// is known every lane above subtracts its U[j][i] * y[i] (zero coefficients skipped too: r = 0 returns z's bits).
+// A pivot that is zero or not finite or a non-finite component of the solution turns the image's whole row of y into NaN
+// and its status into 1; nothing traps, other images are not touched.  A pair index outside [0, n) is skipped, not
+// used, and does the same to every image (the index lists are the batch's).
+__global__ __launch_bounds__(64) void crf_map_kernel(const float* __restrict__ z, const float* __restrict__ r,
+                                                     const int* __restrict__ left, const int* __restrict__ right,
+                                                     float* __restrict__ y, int* __restrict__ status, int n,
+                                                     int npairs) {
+  __shared__ float U[kMaxSp][kMaxSp + 1];       // column n holds the right-hand side
+  const int b = blockIdx.x, lane = threadIdx.x;
+  for (int i = lane; i < n * n; i += 64) U[i / n][i % n] = 0.f;
+  __syncthreads();
+  bool bad = false;
+  for (int base = 0; base < npairs; base += 64) {       // R[l][r] = R[r][l] = r_q in pair order: a later pair overwrites
+    const int q = base + lane;
+    const bool have = q < npairs;
+    const int lq = have ? left[q] : 0, rq = have ? right[q] : 0;
+    const float vq = have ? r[(size_t)b * npairs + q] : 0.f;
+    const int cnt = min(64, npairs - base);
+    for (int t = 0; t < cnt; ++t) {
+      const int l = __shfl(lq, t, 64), rr = __shfl(rq, t, 64);
+      const float v = __shfl(vq, t, 64);
+      if (l < 0 || l >= n || rr < 0 || rr >= n) { bad = true; continue; }
+      if (lane == 0) {
+        U[l][rr] = v;
+        U[rr][l] = v;
+      }
+    }
+  }
+  __syncthreads();
+  if (lane < n) {                               // A = I + diag(row sums of R) - R, the loss kernel's arithmetic
+    float rs = 0.f;
+    for (int j = 0; j < n; ++j) rs += U[lane][j];
+    for (int j = 0; j < n; ++j) U[lane][j] = (j == lane ? 1.f + rs : 0.f) - U[lane][j];
+    U[lane][n] = z[(size_t)b * n + lane];
+  }
+  __syncthreads();
+  for (int k = 0; k < n && !bad; ++k) {         // `bad` and `arg` are the same in every lane: no divergent barrier
+    float best = -1.f;
+    if (lane >= k && lane < n) {
+      best = fabsf(U[lane][k]);
+      if (!(best == best)) best = INFINITY;     // a NaN is taken as the pivot at once, and ends the image below
+    }
+    int arg = lane;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float ob = __shfl_xor(best, off, 64);
+      const int oa = __shfl_xor(arg, off, 64);
+      if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+    }
+    if (arg != k)
+      for (int j = lane; j <= n; j += 64) { const float t = U[k][j]; U[k][j] = U[arg][j]; U[arg][j] = t; }
+    __syncthreads();
+    const float piv = U[k][k];
+    if (piv == 0.f || !isfinite(piv)) { bad = true; break; }
+    const bool below = lane > k && lane < n;
+    const float f = below ? U[lane][k] / piv : 0.f;       // lane i: the multiplier of row i
+    const float prow = below ? U[k][lane] : 0.f;          // lane j: column j of the pivot row
+    if (f != 0.f) U[lane][n] -= f * U[k][n];
+    unsigned long long todo = __ballot(f != 0.f);         // only the rows that have something to eliminate
+    while (todo) {
+      const int i = __ffsll(todo) - 1;
+      todo &= todo - 1;
+      const float fi = __shfl(f, i, 64);
+      if (below) U[i][lane] -= fi * prow;
+    }
+    __syncthreads();
+  }
+  float rhs = 0.f, yi = 0.f;
+  if (!bad) {
+    if (lane < n) rhs = U[lane][n];
+    for (int i = n - 1; i >= 0; --i) {
+      const float yv = __shfl(rhs, i, 64) / U[i][i];
+      if (lane == i) yi = yv;
+      if (lane < i) {
+        const float u = U[lane][i];
+        if (u != 0.f) rhs -= u * yv;
+      }
+    }
+    bad = __any(lane < n && !isfinite(yi));
+  }
+  if (lane < n) y[(size_t)b * n + lane] = bad ? __builtin_nanf("") : yi;
+  if (lane == 0 && status) status[b] = bad ? 1 : 0;
+}
+
 __global__ __launch_bounds__(64) void mean_kernel(const float* __restrict__ v, int n, float* __restrict__ out) {
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += 64) s += v[i];
@@ -246,6 +337,16 @@ int a3d_crf_loss(int n, int nsp, const float* z, const float* y, const float* r,
   clear_stale_error();
   hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(64), 0, st, loss_per_image, n, loss_mean);
   return check_launch("crf_loss_mean");
+}
+
+int a3d_crf_map(int n, int nsp, const float* z, const float* r, const int32_t* left, const int32_t* right, int npairs,
+                float* y, int32_t* status, void* stream) {
+  A3D_CHECK_ARG(n > 0 && nsp > 0 && nsp <= kMaxSp && npairs > 0 && z && r && left && right && y,
+                "crf_map: bad arguments (at most %d superpixels)", kMaxSp);
+  clear_stale_error();
+  hipLaunchKernelGGL(crf_map_kernel, dim3(n), dim3(64), 0, static_cast<hipStream_t>(stream), z, r, left, right, y,
+                     status, nsp, npairs);
+  return check_launch("crf_map");
 }
 
 int a3d_sgd_apply(size_t count, float* var, const float* g, float lr, void* stream) {

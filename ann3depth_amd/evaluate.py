@@ -1,16 +1,23 @@
-"""Evaluation driver: restore an MSDN checkpoint and measure it on the test split.
+"""Evaluation driver: restore an MSDN or DCNF checkpoint and measure it on the test split.
 
 The converter writes ``test.tfrecords`` beside ``train.tfrecords`` (tools/data_tf_converter.py, src/data.py:58-59);
 training never reads it.  This driver reads every test record once, in file order (data.OrderedBatch), runs the
-network's forward without targets (MSDNReplica.predict: dropout off, no loss, weights untouched) and reports the held-out
-error metrics of Eigen et al. 2014, Table 1, for the coarse and the coarse + fine output (ops.depth_metrics on the GPU,
-ops.summarize_depth_metrics on the host), plus the training objective on the test split.
+network's forward without targets (the replica's predict(): dropout off, no loss, weights untouched) and reports the
+held-out error metrics of Eigen et al. 2014, Table 1 (ops.depth_metrics on the GPU, ops.summarize_depth_metrics on the
+host), plus the training objective on the test split.
 
-    python -m ann3depth_amd.evaluate nyu --model msdn --id r1 [--checkpoint PATH] [--resolution grid|record] ...
+    python -m ann3depth_amd.evaluate nyu --model msdn|dcnf --id r1 [--checkpoint PATH] [--resolution grid|record] ...
+
+msdn: the coarse and the coarse + fine output, each with its scale-invariant log loss ``silog``; ``grid`` is 55 x 74.
+dcnf: ``unary``, the unary stack's z (what the reference draws as its Output image), and ``crf``, the MAP depths
+A^-1 z of the conditional random field (ops.crf_map: one pivoted LU per image; the reference never forms them), both on
+the 6 x 8 superpixel grid and sampled at the target's pixels inside the metrics kernel; ``grid`` is 240 x 320, the size
+the DCNF step resizes its targets to.  The objective is reported once, as ``crf_nll``; ``singular_systems`` counts the
+images whose system had no solution (their crf row is NaN and shows up under ``nonfinite``).
 
 Output: one JSON line on stdout, ``<ckptdir>/<model>_<id>/eval-<global_step>.json`` and TensorBoard scalars
-``eval/{coarse,fine}/<metric>`` at the checkpoint's global step.  Exit code 2 when there is nothing to evaluate (no
-checkpoint, no test split) or the request is unsupported (DCNF, more than one process).
+``eval/<output>/<metric>`` (and ``eval/crf_nll``) at the checkpoint's global step.  Exit code 2 when there is nothing to
+evaluate (no checkpoint, no test split) or the request is unsupported (an unknown model, more than one process).
 """
 import argparse
 import ctypes
@@ -24,7 +31,7 @@ import torch
 from . import _lib, data, ops, summary, tfckpt
 from .ann3depth import latest_checkpoint
 
-OUTPUTS = ('coarse', 'fine')
+OUTPUTS = {'msdn': ('coarse', 'fine'), 'dcnf': ('unary', 'crf')}
 
 
 def _say(msg):
@@ -112,7 +119,8 @@ class EvalOp:
 
 
 class Evaluator:
-    """The per-batch work: predict, targets on the grid (the training step's resize), metric rows and the objective."""
+    """MSDN's per-batch work: predict, targets on the grid (the training step's resize), metric rows, the objective."""
+    outputs = OUTPUTS['msdn']
 
     def __init__(self, replica, resolution='grid', min_depth=0., max_depth=float('inf'), clamp_lo=1e-3,
                  clamp_hi=float('inf'), keep_predictions=False):
@@ -122,16 +130,17 @@ class Evaluator:
         dev = replica.device
         self.t = torch.empty((replica.B, OUT_H, OUT_W), device=dev)
         self.silog_ws = {}              # per batch size (a3d_silog_loss_fwd's per-sample sums and partials)
-        self.rows = {o: [] for o in OUTPUTS}
-        self.losses = {o: [] for o in OUTPUTS}
+        self.rows = {o: [] for o in self.outputs}
+        self.losses = {o: [] for o in self.outputs}
         self.counts = []
         self.predictions = [] if keep_predictions else None
+        self.prediction_shape = (OUT_H, OUT_W)
 
     def __call__(self, images, depths, n):
         coarse, fine = self.rep.predict(images, n)
         ops.resize_bilinear_tf1(depths[:n], self.t[:n].view(n, self.t.shape[1], self.t.shape[2], 1))
         target = self.t[:n] if self.resolution == 'grid' else depths[:n]
-        for name, out in zip(OUTPUTS, (coarse, fine)):
+        for name, out in zip(self.outputs, (coarse, fine)):
             self.rows[name].append(ops.depth_metrics(out[:n], target, **self.kw))
             loss = torch.empty(1, device=out.device)
             ws = self.silog_ws.get(n)
@@ -147,11 +156,49 @@ class Evaluator:
         torch.cuda.synchronize()
         out = {}
         n = np.asarray(self.counts, np.float64)
-        for name in OUTPUTS:
+        for name in self.outputs:
             res = ops.summarize_depth_metrics(torch.cat(self.rows[name]))
             per_batch = torch.cat(self.losses[name]).double().cpu().numpy()
             res['silog'] = float((per_batch * n).sum() / n.sum())
             out[name] = res
+        return out
+
+
+class DCNFEvaluator:
+    """DCNF's per-batch work: predict (unary z and the field's MAP depths), the objective on the same batch, which also
+    leaves the targets at 240 x 320, and the metric rows of both outputs; the 6 x 8 predictions are sampled at the
+    target's pixels inside a3d_depth_metrics."""
+    outputs = OUTPUTS['dcnf']
+
+    def __init__(self, replica, resolution='grid', min_depth=0., max_depth=float('inf'), clamp_lo=1e-3,
+                 clamp_hi=float('inf'), keep_predictions=False):
+        self.rep, self.resolution = replica, resolution
+        self.kw = dict(min_depth=min_depth, max_depth=max_depth, clamp_lo=clamp_lo, clamp_hi=clamp_hi)
+        self.rows = {o: [] for o in self.outputs}
+        self.nll, self.status = [], []
+        self.counts = []
+        self.predictions = [] if keep_predictions else None
+        self.prediction_shape = (replica.rows, replica.cols)
+
+    def __call__(self, images, depths, n):
+        rep = self.rep
+        unary, crf = rep.predict(images, n)
+        self.nll.append(rep.nll(depths, n))                                      # the mean over these n images
+        target = rep.depths240[:n] if self.resolution == 'grid' else depths[:n]
+        for name, out in zip(self.outputs, (unary, crf)):
+            self.rows[name].append(ops.depth_metrics(out[:n], target, **self.kw))
+        self.status.append(rep.status[:n].clone())
+        self.counts.append(n)
+        if self.predictions is not None:
+            self.predictions.append(crf[:n].clone())
+
+    def results(self):
+        torch.cuda.synchronize()
+        n = np.asarray(self.counts, np.float64)
+        out = {name: ops.summarize_depth_metrics(torch.cat(self.rows[name])) for name in self.outputs}
+        per_batch = torch.cat(self.nll).double().cpu().numpy()
+        out['crf_nll'] = float((per_batch * n).sum() / n.sum())
+        out['singular_systems'] = int(torch.cat(self.status).sum().item())
         return out
 
 
@@ -164,11 +211,8 @@ def find_checkpoint(args, run_dir):
 
 def main(argv=None):
     args = parse_args(argv)
-    if args.model == 'dcnf':
-        _say('DCNF evaluation (CRF inference per image) is not implemented; only --model msdn can be evaluated.')
-        return 2
-    if args.model != 'msdn':
-        _say(f'unknown model {args.model!r}; only msdn can be evaluated.')
+    if args.model not in OUTPUTS:
+        _say(f'unknown model {args.model!r}; msdn and dcnf can be evaluated.')
         return 2
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         _say('evaluation runs in one process on one GPU; start it without a distributed launcher.')
@@ -185,9 +229,12 @@ def main(argv=None):
         return 2
     if not torch.cuda.is_available():
         raise RuntimeError('ann3depth_amd needs an MI355X: evaluation has no CPU fallback')
-    from .models import MSDNReplica
+    from .models import DCNFReplica, MSDNReplica
     dev = torch.device('cuda', torch.cuda.current_device())
-    replica = MSDNReplica(args.batchsize, device=dev, precision=args.precision, keep_dense_grads=False)
+    if args.model == 'dcnf':
+        replica = DCNFReplica(args.batchsize, device=dev, precision=args.precision)
+    else:
+        replica = MSDNReplica(args.batchsize, device=dev, precision=args.precision, keep_dense_grads=False)
     _say(f'restoring {ckpt}')
     if tfckpt.is_bundle(ckpt):                       # as ann3depth.Session.__enter__ restores
         replica.load_tf_variables(tfckpt.read_bundle(ckpt))
@@ -195,7 +242,8 @@ def main(argv=None):
         replica.load_state_dict(torch.load(ckpt, map_location=dev))
     step = replica.global_step
     pipeline = inputs.pipeline
-    ev = Evaluator(replica, args.resolution, args.min_depth, args.max_depth, args.clamp_lo, args.clamp_hi,
+    evaluator = DCNFEvaluator if args.model == 'dcnf' else Evaluator
+    ev = evaluator(replica, args.resolution, args.min_depth, args.max_depth, args.clamp_lo, args.clamp_hi,
                    keep_predictions=bool(args.predictions))
     op = EvalOp(pipeline, args.batchsize, dev)
     try:
@@ -214,12 +262,15 @@ def main(argv=None):
            **res}
     if args.predictions:
         np.save(args.predictions, torch.cat(ev.predictions).cpu().numpy() if ev.predictions else
-                np.zeros((0,) + tuple(replica.fine.shape[1:3]), np.float32))
+                np.zeros((0,) + ev.prediction_shape, np.float32))
     os.makedirs(run_dir, exist_ok=True)
     with open(os.path.join(run_dir, f'eval-{step}.json'), 'w') as f:
         json.dump(out, f, indent=1)
     events = summary.EventFileWriter(run_dir)
-    events.add_scalars(step, {f'eval/{o}/{k}': float(v) for o in OUTPUTS for k, v in res[o].items()})
+    scalars = {f'eval/{o}/{k}': float(v) for o in ev.outputs for k, v in res[o].items()}
+    if 'crf_nll' in res:
+        scalars['eval/crf_nll'] = res['crf_nll']
+    events.add_scalars(step, scalars)
     events.close()
     print(json.dumps(out), flush=True)
     return 0
@@ -227,9 +278,10 @@ def main(argv=None):
 
 def parse_args(argv=None):
     """The training driver's flags that apply to evaluation (src/ann3depth.py:221-254), plus the evaluation's own."""
-    p = argparse.ArgumentParser(description='Evaluate an MSDN checkpoint on <datadir>/<dataset>/test.tfrecords.')
+    p = argparse.ArgumentParser(
+        description='Evaluate an MSDN or DCNF checkpoint on <datadir>/<dataset>/test.tfrecords.')
     p.add_argument('dataset', default='nyu', type=str, help='The dataset to use.')
-    p.add_argument('--model', '-m', default='msdn', type=str, help='Model name (msdn).')
+    p.add_argument('--model', '-m', default='msdn', type=str, help='Model name (msdn, dcnf).')
     p.add_argument('--batchsize', '-b', default=32, type=int, help='Batchsize')
     p.add_argument('--ckptdir', '-p', default='checkpoints', help='Checkpoint directory')
     p.add_argument('--id', default='', type=str, help='Checkpoint path suffix.')
@@ -239,13 +291,14 @@ def parse_args(argv=None):
     p.add_argument('--checkpoint', default='', type=str,
                    help='A .pt file or TF bundle prefix instead of the newest checkpoint of <ckptdir>/<model>_<id>.')
     p.add_argument('--resolution', default='grid', choices=['grid', 'record'],
-                   help='grid: targets resized to 55x74 as the training step does; record: the depth map as stored, '
-                        'the prediction resampled at its pixels.')
+                   help='grid: targets resized as the training step does (msdn 55x74, dcnf 240x320); record: the depth '
+                        'map as stored.  A prediction on another grid than the target is resampled at its pixels.')
     p.add_argument('--min-depth', default=0., type=float, help='Valid targets are > this.')
     p.add_argument('--max-depth', default=float('inf'), type=float, help='Valid targets are <= this.')
     p.add_argument('--clamp-lo', default=1e-3, type=float, help='Predictions are clamped to at least this.')
     p.add_argument('--clamp-hi', default=float('inf'), type=float, help='Predictions are clamped to at most this.')
-    p.add_argument('--predictions', default='', type=str, help='Write the fine predictions [N,55,74] to this .npy.')
+    p.add_argument('--predictions', default='', type=str,
+                   help='Write the fine (msdn, [N,55,74]) or crf (dcnf, [N,6,8]) predictions to this .npy.')
     return p.parse_args(argv)
 
 

@@ -1087,14 +1087,19 @@ class DCNFUnary:
     def grad(self, name):
         return self.group.view(self.group.grad, DCNF_PREFIX + name)
 
-    def forward(self, images):
+    def forward(self, images, record_argmax=True):
         ops.resize_bilinear_tf1(images, self.resized)                           # src/models.py:180
+        return self.forward_resized(record_argmax)
+
+    def forward_resized(self, record_argmax=True):
+        """The stack over self.resized as it stands.  record_argmax=False (DCNFReplica.predict): the fused conv + pool
+        does not write the pool positions, which only a backward reads."""
         ops.extract_patches(self.resized, DCNF_PATCH, DCNF_SP, self.act['x'])   # :50-59
         t = self.act['x']
         for n, _, _, _ in DCNF_CONVS:
             if self.fuse_pool and n in DCNF_POOL_AFTER:
                 t = ops.conv2d_pool_fwd(self.desc[n], t, self.var(n + '/kernel'), self.var(n + '/bias'),
-                                        self.act[n + '/pool'], 'relu', self.argmax[n])
+                                        self.act[n + '/pool'], 'relu', self.argmax[n] if record_argmax else None)
                 continue
             ops.conv2d_fwd(self.desc[n], t, self.var(n + '/kernel'), self.var(n + '/bias'), self.act[n], 'relu')
             t = self.act[n]
@@ -1231,6 +1236,8 @@ class DCNFReplica:
         self.y = torch.empty((batchsize, self.nsp, 1), device=dev)
         self.output = torch.empty((batchsize, DCNF_IMG_H, DCNF_IMG_W, 1), device=dev)
         self.sims = self.r = self.loss = self.loss_per_image = self.dz = None
+        self.crf = torch.empty((batchsize, self.nsp), device=dev)                          # predict(): the MAP depths
+        self.status = torch.empty((batchsize,), dtype=torch.int32, device=dev)
 
     def pair_var(self, name):
         return self.pair_group.view(self.pair_group.var, DCNF_PAIR_PREFIX + name)
@@ -1251,6 +1258,41 @@ class DCNFReplica:
         self.loss, self.loss_per_image, self.dz = ops.crf_loss(u.z.view(self.B, self.nsp), self.y.view(self.B, self.nsp),
                                                                self.r, self.left, self.right, DCNF_EPSILON)  # :129-177
         return self.loss
+
+    def predict(self, images, n=None):
+        """The model's depths for a batch of images, without targets: (unary, crf), each [B, rows, cols] float32 (views
+        of this replica's buffers, valid until its next forward).  unary is z, what the reference draws as `Output`
+        (src/models.py:187-191); crf is the field's MAP estimate A^-1 z (ops.crf_map), which the reference never forms.
+        images [m, H, W, 3] float32, or the uint8 pixel values of converter-written records, m <= B; only rows [0, n)
+        (default m) are read, rows n .. B of the network input are zero, so a short last batch runs at the replica's B
+        and its rows [0, n) are those of a full batch.  Leaves the pair weights in self.r and, per image, 1 in
+        self.status where the system was singular (that row of crf is NaN).  Weights, gradients and global_step are
+        left as they are."""
+        B, u = self.B, self.unary
+        n = images.shape[0] if n is None else int(n)
+        if not 0 < n <= min(B, images.shape[0]):
+            raise ValueError(f'predict: n = {n} rows of a batch of {images.shape[0]} images, replica batch {B}')
+        ops.resize_bilinear_tf1(images[:n], u.resized[:n])                                # src/models.py:180
+        if n < B:
+            u.resized[n:].zero_()
+        u.forward_resized(record_argmax=False)
+        ops.superpixel_hist(u.resized, DCNF_SP, self.hist)
+        self.sims, self.r = ops.pair_similarity(u.resized, DCNF_SP, self.hist, self.left, self.right,
+                                                self.pair_var('kernel'), self.pair_var('bias'), DCNF_GAMMA)
+        self.crf, self.status = ops.crf_map(u.z.view(B, self.nsp), self.r, self.left, self.right, self.crf, self.status)
+        return u.z.view(B, self.rows, self.cols), self.crf.view(B, self.rows, self.cols)
+
+    def nll(self, depths, n):
+        """The training objective (src/models.py:129-177) on rows [0, n) of the batch predict() just ran, from the z
+        and r it left: the mean of the n images' CRF negative log-likelihoods, [1] float32 on the device."""
+        n = int(n)
+        if self.r is None or not 0 < n <= min(self.B, depths.shape[0]):
+            raise ValueError(f'nll: n = {n} rows of {depths.shape[0]} depth maps, replica batch {self.B}, after predict()')
+        ops.resize_bilinear_tf1(depths[:n], self.depths240[:n])                           # src/models.py:181
+        ops.superpixel_mean(self.depths240[:n], DCNF_SP, self.y[:n])                      # :131-132
+        mean, _, _ = ops.crf_loss(self.unary.z.view(self.B, self.nsp)[:n], self.y.view(self.B, self.nsp)[:n],
+                                  self.r[:n], self.left, self.right, DCNF_EPSILON)
+        return mean
 
     def step(self, images, depths, keep_mask=None):
         self.forward(images, depths)

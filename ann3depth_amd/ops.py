@@ -553,6 +553,29 @@ def crf_loss(z, y, r, left, right, eps=1e-7):
     return mean, per, dz
 
 
+def crf_map(z, r, left, right, y=None, status=None):
+    """The field's MAP depths y = A^-1 z, A = I + D - R from the pair weights r (a3d_crf_map): z [n,P], r [n,Q] ->
+    (y [n,P] float32, status [n] int32; 1 where the image's system was singular or not finite and its row of y is NaN)."""
+    n, nsp = z.shape[0], z.shape[1]
+    if r.shape[0] != n or r[0].numel() != left.numel() or left.numel() != right.numel():
+        raise ValueError(f'crf_map: z {tuple(z.shape)}, r {tuple(r.shape)}, {left.numel()} / {right.numel()} pair indices')
+    if z.dtype != torch.float32 or r.dtype != torch.float32 or left.dtype != torch.int32 or right.dtype != torch.int32:
+        raise TypeError('crf_map: z, r float32; left, right int32')
+    y = y if y is not None else torch.empty((n, nsp), dtype=torch.float32, device=z.device)
+    status = status if status is not None else torch.empty((n,), dtype=torch.int32, device=z.device)
+    if y.dtype != torch.float32 or status.dtype != torch.int32:
+        raise TypeError('crf_map: y float32, status int32')
+    if tuple(y.shape) != (n, nsp) or status.numel() != n:
+        raise ValueError(f'crf_map: y {tuple(y.shape)} / status {tuple(status.shape)} for {n} images of {nsp} superpixels')
+    if not all(t.is_contiguous() for t in (z, r, left, right, y, status)):
+        raise ValueError('crf_map: contiguous tensors only')
+    if any(t.device != z.device for t in (r, left, right, y, status)):
+        raise ValueError('crf_map: all tensors on one device')
+    check(_lib.load().a3d_crf_map(n, nsp, _ptr(z), _ptr(r), _ptr(left), _ptr(right), left.numel(), _ptr(y), _ptr(status),
+                                  _stream()), 'a3d_crf_map')
+    return y, status
+
+
 def dropout_keep_mask(keep, seed, step, rate=0.5):
     """Fill the uint8 tensor `keep` with the Bernoulli(1-rate) keep mask of training step `step`."""
     check(_lib.load().a3d_dropout_keep_mask(keep.numel(), seed, step, rate, _ptr(keep), _stream()),

@@ -414,6 +414,20 @@ int a3d_crf_loss(int n, int nsp, const float* z, const float* y, const float* r,
                  const int32_t* right, int npairs, float eps, float* loss_per_image, float* loss_mean, float* dz,
                  void* stream);
 
+/* The MAP depths of the same field, y = A^-1 z with A = I + D - R of get_A (src/models.py:136-143): per image
+ * R[left[q]][right[q]] = R[right[q]][left[q]] = r[q] (a later pair overwrites an earlier one), D = diag(row sums of R).
+ * The reference does NOT compute this: it uses A only inside the likelihood (determinant and inverse, :145-177) and draws
+ * the unary output z as its `Output` image (:187-191); the closed-form maximiser of Liu et al. 2015 is this library's
+ * addition, for evaluation.  One LU with partial pivoting per image (largest magnitude, ties to the lowest row); r may be
+ * negative, A need not be positive definite.
+ * z, y: [n,nsp]; r: [n,npairs]; status: [n] or NULL; nsp <= 64.  An image whose system has a zero or non-finite pivot
+ * or a non-finite solution component gets its WHOLE row of y set to NaN and status 1, every other image status 0; no
+ * other image is affected and nothing traps.  A pair index outside [0,nsp) is never used as an index: left / right are
+ * shared by the batch, so it flags EVERY image in that way.  The same bits on every run; nothing outside y[0, n*nsp)
+ * and status[0, n) is written. */
+int a3d_crf_map(int n, int nsp, const float* z, const float* r, const int32_t* left, const int32_t* right, int npairs,
+                float* y, int32_t* status, void* stream);
+
 /* tf.train.GradientDescentOptimizer (src/models.py:198): var -= lr * g. */
 int a3d_sgd_apply(size_t count, float* var, const float* g, float lr, void* stream);
 

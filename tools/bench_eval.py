@@ -1,7 +1,11 @@
 """Evaluation's costs on one GPU: MSDNReplica.predict from resident batches, ops.depth_metrics at the model grid and at
 full record resolution (achieved GB/s), and the evaluation loop end to end (ordered reader -> pinned -> H2D -> predict ->
 metrics) on a synthetic converter-written test shard, as a fraction of the resident predict rate.
-    python tools/bench_eval.py [n_records] > profiles/bench_eval.json"""
+    python tools/bench_eval.py [n_records] > profiles/bench_eval.json
+With `dcnf` as the second argument, the same for DCNF at batch 16 (BASELINE config 4's batch): DCNFReplica.predict, its
+parts that are not the unary stack (ops.crf_map alone, at 16 and 64 images, and the pairwise features), the objective,
+and the loop end to end.
+    python tools/bench_eval.py 320 dcnf > profiles/bench_eval_dcnf.json"""
 import json
 import os
 import sys
@@ -29,8 +33,88 @@ def timed(fn, iters=20, warmup=3):
     return a.elapsed_time(b) / iters
 
 
+def write_shard(n_records, rng):
+    """A converter-written NYU-shaped test shard in /dev/shm; returns the data directory."""
+    root = tempfile.mkdtemp(dir='/dev/shm' if os.path.isdir('/dev/shm') else None)
+    os.makedirs(os.path.join(root, 'nyu'))
+    img = rng.integers(0, 256, (480, 640, 3)).astype(np.float32) / np.float32(255) - np.float32(.5)
+    dep = rng.integers(0, 256, (480, 640, 1)).astype(np.float32) / np.float32(255) - np.float32(.5)
+    with tfrecord.TFRecordWriter(os.path.join(root, 'nyu', 'test.tfrecords')) as w:
+        for _ in range(n_records):
+            w.write_example(img, dep)
+    return root
+
+
+def remove_shard(root):
+    for f in os.listdir(os.path.join(root, 'nyu')):
+        os.remove(os.path.join(root, 'nyu', f))
+    os.rmdir(os.path.join(root, 'nyu'))
+    os.rmdir(root)
+
+
+def loop_rates(root, B, net, ev):
+    """The driver's loop (EvalOp + the model's evaluator) over the shard: images per second of the whole pass (pool
+    allocation and the first batch's decode included) and of the batches after the first."""
+    inputs, _ = data.inputs(root, 'nyu', B, 'test', shuffle=False)
+    t0 = time.perf_counter()
+    op = evaluate.EvalOp(inputs.pipeline, B, net.device)      # (allocates and pins the staging pool)
+    op.run(ev)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    while True:
+        try:
+            op.run(ev)
+        except data.OutOfRangeError:
+            break
+    ev.results()
+    t2 = time.perf_counter()
+    inputs.pipeline.close()
+    return sum(ev.counts) / (t2 - t0), (sum(ev.counts) - ev.counts[0]) / (t2 - t1)
+
+
+def main_dcnf(n_records):
+    B = 16
+    rng = np.random.default_rng(0)
+    out = {'device': torch.cuda.get_device_name(0), 'model': 'dcnf', 'batch': B}
+    net = models.DCNFReplica(B, device='cuda:0')
+    img = torch.from_numpy(rng.integers(0, 256, (B, 480, 640, 3)).astype(np.uint8)).cuda()
+    dep = torch.from_numpy(rng.integers(0, 256, (B, 480, 640, 1)).astype(np.uint8)).cuda()
+    predict_ms = timed(lambda: net.predict(img))
+    out[f'predict_ms_b{B}'] = round(predict_ms, 4)
+    out[f'predict_images_per_s_b{B}'] = round(B / predict_ms * 1e3, 1)
+    out[f'nll_us_b{B}'] = round(timed(lambda: net.nll(dep, B), iters=100, warmup=10) * 1e3, 2)
+    u = net.unary
+
+    def pairwise():
+        ops.superpixel_hist(u.resized, models.DCNF_SP, net.hist)
+        ops.pair_similarity(u.resized, models.DCNF_SP, net.hist, net.left, net.right, net.pair_var('kernel'),
+                            net.pair_var('bias'), models.DCNF_GAMMA)
+    out[f'pairwise_us_b{B}'] = round(timed(pairwise, iters=200, warmup=10) * 1e3, 2)
+    for n in (B, 64):                 # a3d_crf_map alone: one wavefront per image; pair weights as the layer produces them
+        z = torch.from_numpy(rng.standard_normal((n, net.nsp)).astype(np.float32)).cuda()
+        r = torch.from_numpy(rng.uniform(-0.1, 0.7, (n, net.left.numel())).astype(np.float32)).cuda()
+        y = torch.empty_like(z)
+        status = torch.empty((n,), dtype=torch.int32, device='cuda')
+        us = timed(lambda: ops.crf_map(z, r, net.left, net.right, y, status), iters=500, warmup=20) * 1e3
+        out[f'crf_map_us_b{n}'] = round(us, 2)
+        if n == B:
+            out[f'crf_map_share_of_predict_b{B}'] = round(us * 1e-3 / predict_ms, 5)
+    root = write_shard(n_records, rng)
+    for res in ('grid', 'grid', 'record'):           # the first pass warms the shard's pages and the pinned allocator
+        rate_all, rate = loop_rates(root, B, net, evaluate.DCNFEvaluator(net, res))
+        out[f'evaluate_images_per_s_b{B}_{res}_whole_pass'] = round(rate_all, 1)
+        out[f'evaluate_images_per_s_b{B}_{res}'] = round(rate, 1)
+        out[f'evaluate_fraction_of_resident_predict_b{B}_{res}'] = round(rate / (B / predict_ms * 1e3), 3)
+    out['evaluate_records'] = n_records
+    out['reader_threads'] = data.default_reader_threads()
+    remove_shard(root)
+    print(json.dumps(out))
+
+
 def main():
     n_records = int(sys.argv[1]) if len(sys.argv) > 1 else 320
+    if len(sys.argv) > 2 and sys.argv[2] == 'dcnf':
+        return main_dcnf(n_records)
     rng = np.random.default_rng(0)
     out = {'device': torch.cuda.get_device_name(0)}
     predict_ms = {}
@@ -56,41 +140,16 @@ def main():
         out[f'depth_metrics_GBps_b{B}_{name}'] = round(nbytes / (ms * 1e-3) / 1e9, 1)
         out[f'depth_metrics_share_of_predict_b{B}_{name}'] = round(ms / predict_ms[(32, 'fp32')], 4)
     # end to end: the driver's loop (EvalOp + Evaluator) on a converter-written NYU-shaped test shard in /dev/shm
-    root = tempfile.mkdtemp(dir='/dev/shm' if os.path.isdir('/dev/shm') else None)
-    os.makedirs(os.path.join(root, 'nyu'))
-    img = rng.integers(0, 256, (480, 640, 3)).astype(np.float32) / np.float32(255) - np.float32(.5)
-    dep = rng.integers(0, 256, (480, 640, 1)).astype(np.float32) / np.float32(255) - np.float32(.5)
-    with tfrecord.TFRecordWriter(os.path.join(root, 'nyu', 'test.tfrecords')) as w:
-        for _ in range(n_records):
-            w.write_example(img, dep)
+    root = write_shard(n_records, rng)
     net = models.MSDNReplica(B, device='cuda:0')
     for res in ('grid', 'grid', 'record'):           # the first pass warms the shard's pages and the pinned allocator
-        inputs, _ = data.inputs(root, 'nyu', B, 'test', shuffle=False)
-        ev = evaluate.Evaluator(net, res)
-        t0 = time.perf_counter()
-        op = evaluate.EvalOp(inputs.pipeline, B, net.device)      # (allocates and pins the staging pool)
-        op.run(ev)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        while True:
-            try:
-                op.run(ev)
-            except data.OutOfRangeError:
-                break
-        ev.results()
-        t2 = time.perf_counter()
-        inputs.pipeline.close()
-        # whole pass (pool allocation and the first batch's decode included) and the batches after the first
-        rate_all, rate = sum(ev.counts) / (t2 - t0), (sum(ev.counts) - ev.counts[0]) / (t2 - t1)
+        rate_all, rate = loop_rates(root, B, net, evaluate.Evaluator(net, res))
         out[f'evaluate_images_per_s_b{B}_{res}_whole_pass'] = round(rate_all, 1)
         out[f'evaluate_images_per_s_b{B}_{res}'] = round(rate, 1)
         out[f'evaluate_fraction_of_resident_predict_b{B}_{res}'] = round(rate / (B / predict_ms[(32, 'fp32')] * 1e3), 3)
     out['evaluate_records'] = n_records
     out['reader_threads'] = data.default_reader_threads()
-    for f in os.listdir(os.path.join(root, 'nyu')):
-        os.remove(os.path.join(root, 'nyu', f))
-    os.rmdir(os.path.join(root, 'nyu'))
-    os.rmdir(root)
+    remove_shard(root)
     print(json.dumps(out))
 
 
