@@ -68,9 +68,11 @@ SCRIPT := python3 -O -m torch.distributed.run --nnodes=1 --nproc-per-node ${GPUS
 		  -m ann3depth_amd.ann3depth
 endif
 
+# flags that are not the reference's go through TRAIN_ARGS, e.g. TRAIN_ARGS="--beta2 0.999 --augment eigen"
+TRAIN_ARGS ?=
 .PHONY: train
 train: ${DATA_DIR}
-	${SCRIPT} ${SCRIPT_PARAMETERS} ${DATASET}
+	${SCRIPT} ${SCRIPT_PARAMETERS} ${TRAIN_ARGS} ${DATASET}
 
 # the newest checkpoint of ${CKPT_DIR}/${MODEL}_${RUNID} on ${DATA_DIR}/${DATASET}/test.tfrecords (ann3depth_amd/evaluate.py);
 # MODEL=msdn (coarse and fine output) or MODEL=dcnf (unary output and the CRF's MAP depths); more flags through EVAL_ARGS,

@@ -68,6 +68,8 @@ SIGNATURES = {
     'a3d_resize_bilinear_tf1_pair': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, _P, _P]),
     'a3d_resize_bilinear_tf1_ex': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int,
                                            _P, _P]),
+    'a3d_warp_bilinear_pair': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int,
+                                       _P, _P, _P]),
     'a3d_extract_patches': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, _P]),
     'a3d_silog_loss_fwd': (c_int, [c_int, c_int, _P, _P, _P, _P, _P]),
     'a3d_silog_loss_bwd': (c_int, [c_int, c_int, _P, _P, _P, _P, _P]),

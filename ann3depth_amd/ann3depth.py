@@ -20,7 +20,7 @@ import time
 
 import torch
 
-from . import _lib, data, dp, models, summary, tfckpt, tracehook
+from . import _lib, augment, data, dp, models, summary, tfckpt, tracehook
 
 
 def main(argv=None):
@@ -42,6 +42,11 @@ def main(argv=None):
     if args.job_name not in ('worker', 'local'):
         logger.warning(f'No suitable job description found! {args.job_name}')
         return 0
+    if args.augment != 'none' and args.model != 'msdn':
+        logger.error(f'--augment {args.augment} is the augmentation of Eigen et al. 2014 and applies to --model msdn only: '
+                     f'{args.model or "(no model)"} is not trained with it (dcnf computes its pairwise features from the '
+                     f'resized image, and the paper behind it does not augment this way).')
+        return 2
 
     run_id = args.model + ('' if not args.id else f'_{args.id}')
     ckptdir = str(os.path.join(args.ckptdir, run_id))                    # src/ann3depth.py:73-75
@@ -92,6 +97,8 @@ def setup_model(args, rank=0, world=1):
     if args.beta2 is not None:
         model.beta2 = args.beta2
     model.precision = args.precision
+    if hasattr(model, 'augment'):                                        # main() has refused the models that have none
+        model.augment = augment.Eigen2014() if args.augment == 'eigen' else None
     inputs, targets = data.inputs(args.datadir, args.dataset, args.batchsize, rank=rank, world=world,
                                   seed=args.seed + rank)
     return model(inputs, targets)
@@ -313,7 +320,8 @@ def latest_checkpoint(ckptdir):
 
 
 def parse_args(argv=None):
-    """The reference's flags verbatim (src/ann3depth.py:221-254), plus --beta2 / --seed / --trace-every / --profiler."""
+    """The reference's flags verbatim (src/ann3depth.py:221-254), plus --beta2 / --augment / --seed / --trace-every /
+    --profiler."""
     parser = argparse.ArgumentParser()
     parser.add_argument('dataset', default='nyu', type=str, help='The dataset to use.')
     parser.add_argument('--model', '-m', default='', type=str, help='Enter a model name.')
@@ -334,6 +342,9 @@ def parse_args(argv=None):
                         help='NON-REFERENCE: Adam beta2 (the reference hard-codes 1, which freezes the weights).')
     parser.add_argument('--precision', default='fp32', choices=['fp32', 'bf16x3', 'bf16', 'bf16s'],
                         help='NON-REFERENCE unless fp32: arithmetic of the conv contractions.')
+    parser.add_argument('--augment', default='none', choices=['none', 'eigen'],
+                        help='NON-REFERENCE: train-time augmentation of the input batch on the GPU (msdn only). eigen: scale, '
+                             'rotation, translation, flip and colour of Eigen et al. 2014, section 3.4.')
     parser.add_argument('--seed', default=0, type=int, help='Shuffle-queue seed.')
     parser.add_argument('--tf-checkpoints', action='store_true',
                         help='Also write every checkpoint as a TensorFlow V2 bundle (model.ckpt-N.index/.data-*).')

@@ -304,6 +304,69 @@ __global__ __launch_bounds__(256) void resize_kernel(const ResizePair p) {
   }
 }
 
+// ------------------------------------------------------------------ affine warp + resize (train-time augmentation)
+// The resize above with an affine map of source space between the output grid and the taps (include/a3d.h,
+// a3d_warp_bilinear_pair).  A rotated output row crosses many source lines, so the output is cut into kWarpTH x kWarpTW
+// pixel tiles, one block per tile: a tile's taps fall in a compact source patch.  A 32-lane half wave walks the
+// (pixel, channel) elements of one tile row, which are contiguous in the output.  Coordinates are clamped before they
+// become indices (fmaxf sends a NaN to 0): no read leaves the image whatever the table holds.
+constexpr int kWarpTW = 32, kWarpTH = 256 / kWarpTW, kWarpBlocks = 4096;
+struct WarpPair { ResizeOne t[2]; const float* table; int n; };
+template <typename SRC>
+__device__ __forceinline__ void warp_tiles(const ResizeOne& r, int n, bool second, const float* __restrict__ table,
+                                           const float* lut) {
+  const int tiles_x = (r.ow + kWarpTW - 1) / kWarpTW, tiles_y = (r.oh + kWarpTH - 1) / kWarpTH;
+  const int per_image = tiles_x * tiles_y, tiles = n * per_image;
+  const int line = r.w * r.c;
+  const float xmax = (float)(r.w - 1), ymax = (float)(r.h - 1);
+  const int ry = threadIdx.x / kWarpTW, lane = threadIdx.x % kWarpTW;
+  auto tap = [&](const SRC* p, int i) -> float {
+    if constexpr (sizeof(SRC) == 1) return lut[p[i]];
+    else return p[i];
+  };
+  for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int b = t / per_image, q = t - b * per_image, ty = q / tiles_x, tx = q - ty * tiles_x;
+    const float* m = table + b * A3D_WARP_STRIDE;
+    const float m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5];
+    const float g0 = m[6], g1 = m[7], g2 = m[8], g3 = m[9], gd = m[10];
+    const int oy = ty * kWarpTH + ry, ox0 = tx * kWarpTW;
+    if (oy >= r.oh) continue;
+    const SRC* img = reinterpret_cast<const SRC*>(r.x) + (size_t)b * r.h * line;
+    float* out = r.y + (((size_t)b * r.oh + oy) * r.ow + ox0) * r.c;
+    const int ne = min(kWarpTW, r.ow - ox0) * r.c;
+    const float v = __fmul_rn((float)oy, r.sy);
+    const float a01 = __fmul_rn(m01, v), a11 = __fmul_rn(m11, v);
+    for (int e = lane; e < ne; e += kWarpTW) {
+      const int px = e / r.c, ch = e - px * r.c;
+      const float u = __fmul_rn((float)(ox0 + px), r.sx);
+      float fx = __fadd_rn(__fadd_rn(__fmul_rn(m00, u), a01), m02);
+      float fy = __fadd_rn(__fadd_rn(__fmul_rn(m10, u), a11), m12);
+      fx = fminf(fmaxf(fx, 0.f), xmax);
+      fy = fminf(fmaxf(fy, 0.f), ymax);
+      const int x0 = (int)fx, x1 = min(x0 + 1, r.w - 1), y0 = (int)fy, y1 = min(y0 + 1, r.h - 1);
+      const float lx = __fsub_rn(fx, (float)x0), ly = __fsub_rn(fy, (float)y0);
+      const int o0 = y0 * line + ch, o1 = y1 * line + ch, c0 = x0 * r.c, c1 = x1 * r.c;
+      const float tl = tap(img, o0 + c0), tr = tap(img, o0 + c1);
+      const float bl = tap(img, o1 + c0), br = tap(img, o1 + c1);
+      const float top = __fadd_rn(tl, __fmul_rn(__fsub_rn(tr, tl), lx));
+      const float bot = __fadd_rn(bl, __fmul_rn(__fsub_rn(br, bl), lx));
+      const float gain = second ? gd : ch == 0 ? g0 : ch == 1 ? g1 : ch == 2 ? g2 : g3;
+      out[e] = __fmul_rn(__fadd_rn(top, __fmul_rn(__fsub_rn(bot, top), ly)), gain);
+    }
+  }
+}
+__global__ __launch_bounds__(256) void warp_kernel(const WarpPair p) {
+  const ResizeOne& r = p.t[blockIdx.y];
+  if (r.u8) {
+    __shared__ float lut[256];      // as resize_kernel's
+    lut[threadIdx.x] = __fadd_rn(__fsub_rn(__fdiv_rn((float)threadIdx.x, 255.f), 0.5f), 0.5f);
+    __syncthreads();
+    warp_tiles<uint8_t>(r, p.n, blockIdx.y != 0, p.table, lut);
+  } else {
+    warp_tiles<float>(r, p.n, blockIdx.y != 0, p.table, nullptr);
+  }
+}
+
 // ------------------------------------------------------------------ extract_image_patches (SAME, zero fill)
 __global__ __launch_bounds__(256) void patches_kernel(const float* __restrict__ x, float* __restrict__ y, int n, int h,
                                                       int w, int c, int k, int stride, int ph, int pw, int pad_t,
@@ -834,6 +897,31 @@ int a3d_resize_bilinear_tf1_ex(int n, int h, int w, int c0, const void* x0, int 
   hipLaunchKernelGGL(resize_kernel, dim3((unsigned)std::min(n * std::max(oh0, x1 ? oh1 : oh0), 16384), x1 ? 2 : 1), dim3(256), 0,
                      static_cast<hipStream_t>(stream), p);
   return check_launch("resize_ex");
+}
+
+int a3d_warp_bilinear_pair(int n, int h, int w, int c0, const void* x0, int u8_0, int oh0, int ow0, float* y0, int c1,
+                           const void* x1, int u8_1, int oh1, int ow1, float* y1, const float* table, void* stream) {
+  A3D_CHECK_ARG(n > 0 && h > 0 && w > 0 && c0 > 0 && oh0 > 0 && ow0 > 0 && x0 && y0, "warp_pair: bad arguments");
+  A3D_CHECK_ARG(c0 <= 4, "warp_pair: the table holds 4 channel gains, the first tensor has %d channels", c0);
+  A3D_CHECK_ARG(!x1 || (c1 > 0 && oh1 > 0 && ow1 > 0 && y1), "warp_pair: bad second tensor");
+  A3D_CHECK_ARG(table, "warp_pair: no table");
+  const long long lim = 0x7fffffffLL;       // the kernel's index arithmetic is 32-bit
+  A3D_CHECK_ARG((long long)h * w * std::max(c0, x1 ? c1 : c0) <= lim && (long long)n * A3D_WARP_STRIDE <= lim,
+                "warp_pair: image too large");
+  WarpPair p;
+  p.n = n;
+  p.table = table;
+  p.t[0] = resize_one(h, w, c0, static_cast<const float*>(x0), oh0, ow0, y0, u8_0 ? 1 : 0);
+  p.t[1] = x1 ? resize_one(h, w, c1, static_cast<const float*>(x1), oh1, ow1, y1, u8_1 ? 1 : 0) : p.t[0];
+  auto tiles = [&](int oh, int ow) {
+    return (long long)n * ((oh + kWarpTH - 1) / kWarpTH) * ((ow + kWarpTW - 1) / kWarpTW);
+  };
+  const long long blocks = std::max(tiles(oh0, ow0), x1 ? tiles(oh1, ow1) : 0LL);
+  A3D_CHECK_ARG(blocks <= lim, "warp_pair: output too large");
+  clear_stale_error();
+  hipLaunchKernelGGL(warp_kernel, dim3((unsigned)std::min(blocks, (long long)kWarpBlocks), x1 ? 2 : 1), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), p);
+  return check_launch("warp_pair");
 }
 
 int a3d_extract_patches(int n, int h, int w, int c, const float* x, int k, int stride, float* y, void* stream) {

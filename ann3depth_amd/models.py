@@ -16,7 +16,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, augment as augment_, ops
 
 NET_H, NET_W = 228, 304          # src/models.py:282
 OUT_H, OUT_W = 55, 74            # src/models.py:283
@@ -688,15 +688,19 @@ class MSDNReplica:
         d, w = self._prepared(('fine/first/image', 0, 0, 0), self.d4, self.w4)
         ops.conv2d_pool_fwd(d, self.x4, w, self._v('fine/first/conv2d/bias'), self.cat, 'relu', argmax)
 
-    def forward(self, images, depths, keep_mask, join=True, phase=None):
+    def forward(self, images, depths, keep_mask, join=True, phase=None, warp=None):
         """join=False leaves the fine network's forward in flight on the side stream (step() joins later).
         phase (1 coarse / 2 fine / 3 none trained) runs every conv that feeds a max pool fused with it: the pre-pool
         activations c0, c1, f1 are then NOT written.  The network being trained also records the position of each
         maximum (a0, a1 / af1): MaxPoolGrad routes dy to that position and the fused ReluGrad only asks whether the
         maximum is positive, so the backward needs nothing else of c0 / c1 / f1.  phase None keeps every activation.
-        depths None (predict()): the input images are already in self.x, no target is resized and no loss computed."""
+        depths None (predict()): the input images are already in self.x, no target is resized and no loss computed.
+        warp (NON-REFERENCE, train-time augmentation): a device table [B, 12] of ops.warp_bilinear_pair, which then takes
+        the place of the resize launch; images and depths are stored at the same size."""
         if depths is None:
             pass
+        elif warp is not None:
+            ops.warp_bilinear_pair(images, self.x, depths, self.t, warp)
         elif images.shape[:3] == depths.shape[:3]:
             ops.resize_bilinear_tf1_pair(images, self.x, depths, self.t)
         else:
@@ -940,14 +944,14 @@ class MSDNReplica:
         self._bwd_filter(n, self.x, self.df1)
 
     # ---- one session.run(train_op) ----
-    def step(self, images, depths, keep_mask):
+    def step(self, images, depths, keep_mask, warp=None):
         """images [B,H,W,3], depths [B,H',W',1] float32, keep_mask [B,4096] bool/uint8, all on this device.
         Both forwards and both losses run in every phase; gradients + Adam only for the active phase;
-        global_step += 1 always (src/models.py:329,343,356)."""
+        global_step += 1 always (src/models.py:329,343,356).  warp: see forward()."""
         if keep_mask is not None and keep_mask.dtype != torch.uint8:
             keep_mask = keep_mask.to(torch.uint8)
         phase = phase_of(self.global_step, self.B)
-        self.forward(images, depths, keep_mask, join=False, phase=phase)
+        self.forward(images, depths, keep_mask, join=False, phase=phase, warp=warp)
         red = self.reducer
         scale = 1.0 / red.world_size if red is not None else 1.0
         if phase == 1:
@@ -1365,10 +1369,14 @@ class TrainOp:
 
     Input side: the shuffle queue's staging pool is pinned memory; a dequeued batch is B slot numbers, DMA'd to HBM
     on a side stream into one of two device batch buffers.  Batch k+1 is in flight while step k computes, so host
-    decode, PCIe transfer and the training step overlap."""
+    decode, PCIe transfer and the training step overlap.
 
-    def __init__(self, replica, pipeline, seed=0):
+    augment (NON-REFERENCE, an augment.Eigen2014): every batch is warped as it is resized.  Its table is drawn beside the
+    batch's DMA for the global step that will consume it, from (seed, rank, step) alone, and travels under the same event."""
+
+    def __init__(self, replica, pipeline, seed=0, augment=None, rank=0):
         self.replica, self.pipeline, self.seed = replica, pipeline, seed
+        self.augment, self.rank = augment, rank
         dev = replica.device
         self.keep = torch.empty((replica.B, 4096), dtype=torch.uint8, device=dev) if replica.uses_dropout else None
         pipeline.allocate(lambda shape: torch.empty(shape, dtype=torch.float32).pin_memory().numpy(),
@@ -1391,6 +1399,13 @@ class TrainOp:
         self.k = 0                          # batches consumed
         self.end = None                     # (batch index, exception) once the pipeline ran dry
         self.last = None
+        if augment is not None:
+            if tuple(self.pool[0].shape[1:3]) != tuple(self.pool[1].shape[1:3]):
+                raise ValueError(f'augmentation warps the image and its depth map with one map: they must be stored at the '
+                                 f'same size, not {tuple(self.pool[0].shape[1:3])} and {tuple(self.pool[1].shape[1:3])}')
+            self.table_host = [torch.empty((replica.B, augment_.STRIDE), dtype=torch.float32).pin_memory() for _ in range(2)]
+            self.table_dev = [torch.empty((replica.B, augment_.STRIDE), device=dev) for _ in range(2)]
+            self.table_step = [None, None]  # the global step table i was drawn for
         self._prefetch(0)
         self._prefetch(1)
 
@@ -1422,11 +1437,21 @@ class TrainOp:
                 ops.check(_lib.load().a3d_h2d_gather(cur[which].data_ptr(), src.data_ptr(), ids, len(slots), len(src),
                                                      src[0].numel() * src.element_size(), self.copy_stream.cuda_stream),
                           'a3d_h2d_gather')                     # B copies from ONE call (no per-record host-language work)
+            if self.augment is not None:
+                self._table(i, self.replica.global_step + j - self.k)
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
         self.cur[i] = tuple(cur)
         self.copied[i] = ev
         self.held[i] = slots
+
+    def _table(self, i, step):
+        """Draw the table of global step `step` into pinned buffer i and start its copy (the current stream is the copy
+        stream; the earlier copy out of that buffer has finished: run() waited for `copied` before releasing the slots)."""
+        h, w = self.pool[0].shape[1:3]
+        augment_.table(self.augment, self.seed, self.rank, step, self.replica.B, h, w, out=self.table_host[i].numpy())
+        self.table_dev[i].copy_(self.table_host[i], non_blocking=True)
+        self.table_step[i] = step
 
     def run(self):
         r = self.replica
@@ -1434,10 +1459,23 @@ class TrainOp:
         if self.end is not None and self.end[0] == self.k:
             raise self.end[1]
         cur = torch.cuda.current_stream()
+        warp = None
+        if self.augment is not None:
+            if self.table_step[i] != r.global_step:
+                # the batch was prefetched before a checkpoint moved global_step (the first two steps of a resumed run)
+                self.copied[i].synchronize()
+                with torch.cuda.stream(self.copy_stream):
+                    self._table(i, r.global_step)
+                    self.copied[i] = torch.cuda.Event()
+                    self.copied[i].record(self.copy_stream)
+            warp = self.table_dev[i]
         cur.wait_event(self.copied[i])
         if self.keep is not None:
             ops.dropout_keep_mask(self.keep, self.seed, r.global_step)
-        self.last = r.step(self.cur[i][0], self.cur[i][1], self.keep)
+        if warp is None:
+            self.last = r.step(self.cur[i][0], self.cur[i][1], self.keep)
+        else:
+            self.last = r.step(self.cur[i][0], self.cur[i][1], self.keep, warp=warp)
         ev = torch.cuda.Event()
         ev.record(cur)
         self.consumed[i] = ev
@@ -1459,6 +1497,7 @@ class _MultiScaleDeepNetwork:
     reducer = None       # set by the driver when world_size > 1
     seed = 3000
     precision = 'fp32'   # --precision: 'fp32' | 'bf16x3' | 'bf16' (see MSDNReplica)
+    augment = None       # NON-REFERENCE, --augment eigen: an augment.Eigen2014 (train-time augmentation of the input batch)
 
     def __call__(self, images, depths, train=True):
         assert images.pipeline is depths.pipeline, 'inputs and targets must come from the same data.inputs() call'
@@ -1470,7 +1509,9 @@ class _MultiScaleDeepNetwork:
         if self.reducer is not None:                         # replicas start from rank 0's weights
             for g in replica.groups.values():
                 self.reducer.broadcast(g.var)
-        return TrainOp(replica, images.pipeline, seed=self.seed + 1000 * (self.reducer.rank if self.reducer else 0))
+        rank = self.reducer.rank if self.reducer else 0
+        return TrainOp(replica, images.pipeline, seed=self.seed + 1000 * rank, augment=self.augment if train else None,
+                       rank=rank)
 
 
 class _DistributedConvolutionalNeuralFields:

@@ -308,6 +308,43 @@ def resize_bilinear_tf1_pair(x0, y0, x1, y1):
           'a3d_resize_bilinear_tf1_pair')
 
 
+WARP_STRIDE = 12                     # A3D_WARP_STRIDE (include/a3d.h)
+
+
+def warp_bilinear_pair(x0, y0, x1, y1, table):
+    """resize_bilinear_tf1_pair through a per-image affine map and gains (a3d_warp_bilinear_pair): x0 -> y0 and, unless
+    x1 is None, x1 -> y1.  x0 / x1 [n, h, w, c] float32 or uint8, y0 / y1 float32, table [n, 12] float32, all contiguous
+    tensors of one device."""
+    if x0.dim() != 4 or y0.dim() != 4 or y0.shape[0] != x0.shape[0] or y0.shape[3] != x0.shape[3]:
+        raise ValueError(f'warp_bilinear_pair: {tuple(x0.shape)} -> {tuple(y0.shape)}')
+    n, h, w, c0 = x0.shape
+    if (x1 is None) != (y1 is None):
+        raise ValueError('warp_bilinear_pair: x1 and y1 go together')
+    if x1 is not None and (x1.dim() != 4 or tuple(x1.shape[:3]) != (n, h, w) or y1.dim() != 4
+                           or y1.shape[0] != n or y1.shape[3] != x1.shape[3]):
+        raise ValueError(f'warp_bilinear_pair: second tensor {tuple(x1.shape)} -> {tuple(y1.shape)} beside '
+                         f'{tuple(x0.shape)}')
+    if tuple(table.shape) != (n, WARP_STRIDE) or table.dtype != torch.float32:
+        raise ValueError(f'warp_bilinear_pair: table {tuple(table.shape)} {table.dtype}, want [{n}, {WARP_STRIDE}] float32')
+    for name, t, dtypes in (('x0', x0, (torch.float32, torch.uint8)), ('y0', y0, (torch.float32,)),
+                            ('x1', x1, (torch.float32, torch.uint8)), ('y1', y1, (torch.float32,)),
+                            ('table', table, (torch.float32,))):
+        if t is None:
+            continue
+        if t.dtype not in dtypes:
+            raise ValueError(f'warp_bilinear_pair: {name} is {t.dtype}')
+        if not t.is_cuda or t.device != x0.device:
+            raise ValueError(f'warp_bilinear_pair: {name} is on {t.device}, x0 on {x0.device}')
+        if not t.is_contiguous():
+            raise ValueError(f'warp_bilinear_pair: {name} is not contiguous')
+    second = x1 is not None
+    check(_lib.load().a3d_warp_bilinear_pair(n, h, w, c0, _ptr(x0), int(x0.dtype == torch.uint8), y0.shape[1], y0.shape[2],
+                                             _ptr(y0), x1.shape[3] if second else 0, _ptr(x1),
+                                             int(second and x1.dtype == torch.uint8), y1.shape[1] if second else 0,
+                                             y1.shape[2] if second else 0, _ptr(y1), _ptr(table), _stream()),
+          'a3d_warp_bilinear_pair')
+
+
 def extract_patches(x, k, stride, y):
     n, h, w, c = x.shape
     check(_lib.load().a3d_extract_patches(n, h, w, c, _ptr(x), k, stride, _ptr(y), _stream()), 'a3d_extract_patches')

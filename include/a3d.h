@@ -239,6 +239,25 @@ int a3d_resize_bilinear_tf1_pair(int n, int h, int w, int c0, const float* x0, i
  * bit-identical to resizing the float32 record. */
 int a3d_resize_bilinear_tf1_ex(int n, int h, int w, int c0, const void* x0, int u8_0, int oh0, int ow0, float* y0, int c1,
                                const void* x1, int u8_1, int oh1, int ow1, float* y1, void* stream);
+/* NON-REFERENCE: the train-time augmentation of Eigen et al. 2014, section 3.4, fused into that resize.  Arguments as
+ * a3d_resize_bilinear_tf1_ex (one or two tensors of the same batch and stored h x w, float32 or uint8 each), plus
+ * table: device memory, [n][A3D_WARP_STRIDE] float32, one row per image:
+ *   m00 m01 m02 m10 m11 m12   affine map of source space, in source-pixel units
+ *   g0 g1 g2 g3               gain of channel ch of tensor 0 (c0 <= 4, else A3D_EINVAL)
+ *   gd                        gain of every channel of tensor 1
+ *   0                         reserved
+ * Per output element (ox, oy, ch), every operation a separate correctly rounded fp32 operation (no FMA contraction):
+ *   u  = fl(ox * sx)   v = fl(oy * sy)                     sx = fl(w / ow), sy = fl(h / oh) as the resize forms them
+ *   u' = fl(fl(fl(m00 * u) + fl(m01 * v)) + m02)           v' = fl(fl(fl(m10 * u) + fl(m11 * v)) + m12)
+ *   u' = fminf(fmaxf(u', 0), w - 1)   v' likewise, h - 1   a NaN coordinate lands on 0; no read leaves the image
+ *   x0 = (int)u'   x1 = min(x0 + 1, w - 1)   lx = fl(u' - x0)   rows likewise
+ *   top, bot, out as the resize;   y = fl(out * gain)
+ * The identity row (1 0 0 0 1 0, gains 1) writes the bits a3d_resize_bilinear_tf1_ex writes from finite sources; with
+ * oh = h, ow = w the row (-1 0 w-1 0 1 0) is the horizontal flip.  The same six numbers serve both tensors, whose output
+ * grids differ.  Bad arguments (a NULL table among them): A3D_EINVAL before any launch. */
+#define A3D_WARP_STRIDE 12
+int a3d_warp_bilinear_pair(int n, int h, int w, int c0, const void* x0, int u8_0, int oh0, int ow0, float* y0, int c1,
+                           const void* x1, int u8_1, int oh1, int ow1, float* y1, const float* table, void* stream);
 
 /* tf.extract_image_patches(k x k, stride, SAME) + reshape (src/models.py:53-59): y [n*ph*pw, k, k, c]. */
 int a3d_extract_patches(int n, int h, int w, int c, const float* x, int k, int stride, float* y, void* stream);

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from ann3depth_amd import data, models, tfrecord  # noqa: E402
+from ann3depth_amd import augment, data, models, tfrecord  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 32
@@ -50,9 +50,12 @@ for label, u8 in (('uint8', True), ('float32', False)):
     out['host_threads'] = os.cpu_count()
     sb.close()
 # `make train`'s loop on both transfer paths: converter-written records staged and DMA'd as uint8 pixel values (the default
-# for such records, data.py), and everything as float32 (A3D_NO_U8_RECORDS=1: what round 2 measured)
-for label, env in (('uint8_records', '0'), ('float32_records', '1')):
+# for such records, data.py), and everything as float32 (A3D_NO_U8_RECORDS=1: what round 2 measured); the uint8 path once more
+# with --augment eigen (the table drawn on the host beside the batch's DMA, the warp in place of the resize launch)
+for label, env, aug in (('uint8_records', '0', None), ('float32_records', '1', None),
+                        ('uint8_records_augment_eigen', '0', augment.Eigen2014())):
     os.environ['A3D_NO_U8_RECORDS'] = env
+    models.msdn.augment = aug
     inp, tgt = data.inputs(root, 'nyu', B, seed=0)
     op = models.msdn(inp, tgt)
     op.run(); op.run()
@@ -66,6 +69,7 @@ for label, env in (('uint8_records', '0'), ('float32_records', '1')):
     op.pipeline.close()
     del op
 os.environ.pop('A3D_NO_U8_RECORDS')
+models.msdn.augment = None
 # the same step with its batch resident in HBM (what bench.py times): the ceiling of the loop above
 net = models.MSDNReplica(B, keep_dense_grads=False)
 ti = torch.from_numpy(np.broadcast_to(img + np.float32(.5), (B,) + img.shape).copy()).cuda()
@@ -80,6 +84,8 @@ for _ in range(steps):
 torch.cuda.synchronize()
 out['resident_images_per_s'] = round(B * steps / (time.perf_counter() - t0), 1)
 out['loop_over_resident'] = round(out['train_loop_images_per_s_uint8_records'] / out['resident_images_per_s'], 3)
+out['augment_eigen_loop_over_resident'] = round(out['train_loop_images_per_s_uint8_records_augment_eigen'] /
+                                                out['resident_images_per_s'], 3)
 print(json.dumps(out))
 import shutil
 shutil.rmtree(root, ignore_errors=True)
