@@ -131,6 +131,16 @@ SIGNATURES = {
     'a3d_example_write': (c_int64, [_P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, c_size_t]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_valid.h declares (NON-REFERENCE extension, prefix a3dx_)
+EXT_SIGNATURES = {
+    'a3dx_resize_bilinear_tf1_valid': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int,
+                                               c_int, _P, c_float, c_float, _P]),
+    'a3dx_warp_bilinear_pair_valid': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int,
+                                              c_int, _P, _P, c_float, c_float, _P]),
+    'a3dx_silog_masked_loss_fwd': (c_int, [c_int, c_int, _P, _P, _P, _P, _P]),
+    'a3dx_silog_masked_loss_bwd_ex': (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_int, _P]),
+}
+
 _lib = None
 
 
@@ -146,7 +156,7 @@ def load():
     # the runtime copy torch initialises: two HIP runtimes in one process cannot both own the device.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

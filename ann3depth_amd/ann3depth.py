@@ -47,6 +47,17 @@ def main(argv=None):
                      f'{args.model or "(no model)"} is not trained with it (dcnf computes its pairwise features from the '
                      f'resized image, and the paper behind it does not augment this way).')
         return 2
+    if (args.min_depth is not None or args.max_depth is not None) and args.model != 'msdn':
+        logger.error(f'--min-depth / --max-depth mask the holes of a depth map out of the msdn target and loss: '
+                     f'{args.model or "(no model)"} is not trained with them (dcnf regresses superpixel means, a mean over '
+                     f'a superpixel with holes is a different question).')
+        return 2
+    if args.min_depth is not None or args.max_depth is not None:
+        lo = 0. if args.min_depth is None else args.min_depth
+        hi = float('inf') if args.max_depth is None else args.max_depth
+        if not lo <= hi:
+            logger.error(f'--min-depth {lo} --max-depth {hi}: need min <= max.')
+            return 2
 
     run_id = args.model + ('' if not args.id else f'_{args.id}')
     ckptdir = str(os.path.join(args.ckptdir, run_id))                    # src/ann3depth.py:73-75
@@ -99,6 +110,11 @@ def setup_model(args, rank=0, world=1):
     model.precision = args.precision
     if hasattr(model, 'augment'):                                        # main() has refused the models that have none
         model.augment = augment.Eigen2014() if args.augment == 'eigen' else None
+    if hasattr(model, 'valid_range'):
+        model.valid_range = None
+        if args.min_depth is not None or args.max_depth is not None:
+            model.valid_range = (0. if args.min_depth is None else args.min_depth,
+                                 float('inf') if args.max_depth is None else args.max_depth)
     inputs, targets = data.inputs(args.datadir, args.dataset, args.batchsize, rank=rank, world=world,
                                   seed=args.seed + rank)
     return model(inputs, targets)
@@ -320,8 +336,8 @@ def latest_checkpoint(ckptdir):
 
 
 def parse_args(argv=None):
-    """The reference's flags verbatim (src/ann3depth.py:221-254), plus --beta2 / --augment / --seed / --trace-every /
-    --profiler."""
+    """The reference's flags verbatim (src/ann3depth.py:221-254), plus --beta2 / --augment / --min-depth / --max-depth /
+    --seed / --trace-every / --profiler."""
     parser = argparse.ArgumentParser()
     parser.add_argument('dataset', default='nyu', type=str, help='The dataset to use.')
     parser.add_argument('--model', '-m', default='', type=str, help='Enter a model name.')
@@ -345,6 +361,12 @@ def parse_args(argv=None):
     parser.add_argument('--augment', default='none', choices=['none', 'eigen'],
                         help='NON-REFERENCE: train-time augmentation of the input batch on the GPU (msdn only). eigen: scale, '
                              'rotation, translation, flip and colour of Eigen et al. 2014, section 3.4.')
+    parser.add_argument('--min-depth', default=None, type=float,
+                        help='NON-REFERENCE: the depth maps have holes (msdn only). A target pixel counts iff its stored depth t '
+                             '(the float after the loader\'s +0.5: k/255 for converter-written records) is finite and '
+                             'min < t <= max; the others leave the resized target and both losses. Giving either flag turns '
+                             'the mode on, the other defaults to 0 / +inf.')
+    parser.add_argument('--max-depth', default=None, type=float, help='NON-REFERENCE: see --min-depth.')
     parser.add_argument('--seed', default=0, type=int, help='Shuffle-queue seed.')
     parser.add_argument('--tf-checkpoints', action='store_true',
                         help='Also write every checkpoint as a TensorFlow V2 bundle (model.ckpt-N.index/.data-*).')

@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "a3d_internal.h"
+#include "../../include/a3d_valid.h"
 
 namespace a3d {
 
@@ -260,8 +261,16 @@ __global__ __launch_bounds__(256) void maxpool_bwd_bf16_kernel(const __bf16* __r
 // the row's (pixel, channel) elements with 32-bit arithmetic.  Same separate fp32 operations as before: bit-exact.
 struct ResizeOne { const float* x; float* y; int h, w, c, oh, ow; float sy, sx; int u8; };
 struct ResizePair { ResizeOne t[2]; int n; };
-template <typename SRC>
-__device__ __forceinline__ void resize_rows(const ResizeOne& r, int n, const float* lut) {
+// VALID (NON-REFERENCE, include/a3d_valid.h: a3dx_resize_bilinear_tf1_valid / a3dx_warp_bilinear_pair_valid): the tensor is a depth map with
+// holes.  A tap counts when its weight can be non-zero (tl always, tr iff lx > 0, bl iff ly > 0, br iff both); the output is
+// NaN unless every counting tap t is finite with lo < t <= hi and all four taps are finite.  No depth is invented.
+__device__ __forceinline__ bool taps_valid(float tl, float tr, float bl, float br, float lx, float ly, float lo, float hi) {
+  auto ok = [&](float t) { return isfinite(t) && t > lo && t <= hi; };
+  const bool px = lx > 0.f, py = ly > 0.f;
+  return ok(tl) && (px ? ok(tr) : isfinite(tr)) && (py ? ok(bl) : isfinite(bl)) && (px && py ? ok(br) : isfinite(br));
+}
+template <typename SRC, bool VALID = false>
+__device__ __forceinline__ void resize_rows(const ResizeOne& r, int n, const float* lut, float lo = 0.f, float hi = 0.f) {
   const int rows = n * r.oh;
   const SRC* src = reinterpret_cast<const SRC*>(r.x);
   for (int row = blockIdx.x; row < rows; row += gridDim.x) {
@@ -286,7 +295,11 @@ __device__ __forceinline__ void resize_rows(const ResizeOne& r, int n, const flo
       const float bl = tap(l1, x0 * r.c + ch), br = tap(l1, x1 * r.c + ch);
       const float top = __fadd_rn(tl, __fmul_rn(__fsub_rn(tr, tl), lx));
       const float bot = __fadd_rn(bl, __fmul_rn(__fsub_rn(br, bl), lx));
-      out[e] = __fadd_rn(top, __fmul_rn(__fsub_rn(bot, top), ly));
+      float y = __fadd_rn(top, __fmul_rn(__fsub_rn(bot, top), ly));
+      if constexpr (VALID) {
+        if (!taps_valid(tl, tr, bl, br, lx, ly, lo, hi)) y = __builtin_nanf("");
+      }
+      out[e] = y;
     }
   }
 }
@@ -303,6 +316,24 @@ __global__ __launch_bounds__(256) void resize_kernel(const ResizePair p) {
     resize_rows<float>(r, p.n, nullptr);
   }
 }
+// the same launch with tensor 1 (blockIdx.y == 1, always present) resized validity-aware; tensor 0 exactly as above
+struct ResizePairValid { ResizeOne t[2]; int n; float lo, hi; };
+__global__ __launch_bounds__(256) void resize_valid_kernel(const ResizePairValid p) {
+  const ResizeOne& r = p.t[blockIdx.y];
+  const bool depth = blockIdx.y != 0;
+  __shared__ float lut[256];        // as resize_kernel's
+  if (r.u8) {
+    lut[threadIdx.x] = __fadd_rn(__fsub_rn(__fdiv_rn((float)threadIdx.x, 255.f), 0.5f), 0.5f);
+    __syncthreads();
+  }
+  if (depth) {
+    if (r.u8) resize_rows<uint8_t, true>(r, p.n, lut, p.lo, p.hi);
+    else resize_rows<float, true>(r, p.n, nullptr, p.lo, p.hi);
+  } else {
+    if (r.u8) resize_rows<uint8_t>(r, p.n, lut);
+    else resize_rows<float>(r, p.n, nullptr);
+  }
+}
 
 // ------------------------------------------------------------------ affine warp + resize (train-time augmentation)
 // The resize above with an affine map of source space between the output grid and the taps (include/a3d.h,
@@ -312,9 +343,9 @@ __global__ __launch_bounds__(256) void resize_kernel(const ResizePair p) {
 // become indices (fmaxf sends a NaN to 0): no read leaves the image whatever the table holds.
 constexpr int kWarpTW = 32, kWarpTH = 256 / kWarpTW, kWarpBlocks = 4096;
 struct WarpPair { ResizeOne t[2]; const float* table; int n; };
-template <typename SRC>
+template <typename SRC, bool VALID = false>
 __device__ __forceinline__ void warp_tiles(const ResizeOne& r, int n, bool second, const float* __restrict__ table,
-                                           const float* lut) {
+                                           const float* lut, float lo = 0.f, float hi = 0.f) {
   const int tiles_x = (r.ow + kWarpTW - 1) / kWarpTW, tiles_y = (r.oh + kWarpTH - 1) / kWarpTH;
   const int per_image = tiles_x * tiles_y, tiles = n * per_image;
   const int line = r.w * r.c;
@@ -351,7 +382,11 @@ __device__ __forceinline__ void warp_tiles(const ResizeOne& r, int n, bool secon
       const float top = __fadd_rn(tl, __fmul_rn(__fsub_rn(tr, tl), lx));
       const float bot = __fadd_rn(bl, __fmul_rn(__fsub_rn(br, bl), lx));
       const float gain = second ? gd : ch == 0 ? g0 : ch == 1 ? g1 : ch == 2 ? g2 : g3;
-      out[e] = __fmul_rn(__fadd_rn(top, __fmul_rn(__fsub_rn(bot, top), ly)), gain);
+      float y = __fmul_rn(__fadd_rn(top, __fmul_rn(__fsub_rn(bot, top), ly)), gain);
+      if constexpr (VALID) {       // on the stored values, before the gain
+        if (!taps_valid(tl, tr, bl, br, lx, ly, lo, hi)) y = __builtin_nanf("");
+      }
+      out[e] = y;
     }
   }
 }
@@ -364,6 +399,23 @@ __global__ __launch_bounds__(256) void warp_kernel(const WarpPair p) {
     warp_tiles<uint8_t>(r, p.n, blockIdx.y != 0, p.table, lut);
   } else {
     warp_tiles<float>(r, p.n, blockIdx.y != 0, p.table, nullptr);
+  }
+}
+struct WarpPairValid { ResizeOne t[2]; const float* table; int n; float lo, hi; };
+__global__ __launch_bounds__(256) void warp_valid_kernel(const WarpPairValid p) {
+  const ResizeOne& r = p.t[blockIdx.y];
+  const bool depth = blockIdx.y != 0;
+  __shared__ float lut[256];        // as resize_kernel's
+  if (r.u8) {
+    lut[threadIdx.x] = __fadd_rn(__fsub_rn(__fdiv_rn((float)threadIdx.x, 255.f), 0.5f), 0.5f);
+    __syncthreads();
+  }
+  if (depth) {
+    if (r.u8) warp_tiles<uint8_t, true>(r, p.n, true, p.table, lut, p.lo, p.hi);
+    else warp_tiles<float, true>(r, p.n, true, p.table, nullptr, p.lo, p.hi);
+  } else {
+    if (r.u8) warp_tiles<uint8_t>(r, p.n, false, p.table, lut);
+    else warp_tiles<float>(r, p.n, false, p.table, nullptr);
   }
 }
 
@@ -410,19 +462,31 @@ __device__ __forceinline__ float masked_log(float v) {
 // writes ws[1+2b] = sum d^2, ws[2+2b] = sum d for the backward kernel, and the batch mean.  The
 // partials cross CUs as write-through stores, drained before the ticket, and are read back past the L1
 // (MI355X_MICROARCH.md, inter-workgroup visibility).
+//
+// MASKED (NON-REFERENCE, a3dx_silog_masked_loss_fwd): a target that is not finite is a hole and is left out of the sums;
+// a third value per block and per sample, the number n of pixels that count, travels beside the two sums (K = 3 floats
+// where the plain kernel has 2), and the sample's term is (npix / n) (s2 - (0.5 / n) s1^2), 0 when n = 0.  Same parts, same
+// reductions, same last block: with no hole and npix = 4070 the constants are the plain kernel's and so are the bits.
 constexpr int kSilogParts = A3D_SILOG_PARTS;
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+template <bool MASKED>
 __global__ __launch_bounds__(256) void silog_fwd_kernel(const float* __restrict__ out, const float* __restrict__ tgt,
                                                         float* __restrict__ ws, float* __restrict__ loss, int npix, int nb,
                                                         float c) {
-  __shared__ float red[2][4];
+  constexpr int K = MASKED ? 3 : 2;
+  __shared__ float red[K][4];
   __shared__ unsigned last;
   const int b = blockIdx.x / kSilogParts, part = blockIdx.x % kSilogParts;
   const int chunk = (npix + kSilogParts - 1) / kSilogParts;
   const int lo = part * chunk, hi = min(npix, lo + chunk);
   const float* o = out + (size_t)b * npix;
   const float* t = tgt + (size_t)b * npix;
-  float* partials = ws + 2 * nb + 1;
-  float s2 = 0.f, s1 = 0.f;
+  float* partials = ws + K * nb + 1;
+  float s2 = 0.f, s1 = 0.f, cnt = 0.f;
   // four elements per thread and round, all eight loads issued before the first logarithm
   for (int i0 = lo + threadIdx.x; i0 < hi; i0 += 4 * 256) {
     float ov[4], tv[4];
@@ -435,6 +499,10 @@ __global__ __launch_bounds__(256) void silog_fwd_kernel(const float* __restrict_
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       if (i0 + u * 256 >= hi) break;
+      if constexpr (MASKED) {
+        if (!isfinite(tv[u])) continue;
+        cnt += 1.f;
+      }
       const float d = __fsub_rn(masked_log(ov[u]), masked_log(tv[u]));
       s2 += d * d;
       s1 += d;
@@ -446,34 +514,58 @@ __global__ __launch_bounds__(256) void silog_fwd_kernel(const float* __restrict_
     red[0][threadIdx.x >> 6] = s2;
     red[1][threadIdx.x >> 6] = s1;
   }
+  if constexpr (MASKED) {
+    cnt = wave_sum(cnt);            // whole numbers below 2^24: exact in any order
+    if ((threadIdx.x & 63) == 0) red[2][threadIdx.x >> 6] = cnt;
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
     const unsigned total = (unsigned)(nb * kSilogParts);
-    __hip_atomic_store(&partials[2 * blockIdx.x], red[0][0] + red[0][1] + red[0][2] + red[0][3], __ATOMIC_RELAXED,
+    __hip_atomic_store(&partials[K * blockIdx.x], red[0][0] + red[0][1] + red[0][2] + red[0][3], __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&partials[2 * blockIdx.x + 1], red[1][0] + red[1][1] + red[1][2] + red[1][3], __ATOMIC_RELAXED,
+    __hip_atomic_store(&partials[K * blockIdx.x + 1], red[1][0] + red[1][1] + red[1][2] + red[1][3], __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (MASKED)
+      __hip_atomic_store(&partials[K * blockIdx.x + 2], red[2][0] + red[2][1] + red[2][2] + red[2][3], __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     last = atomicInc(reinterpret_cast<unsigned*>(ws), total - 1u) == total - 1u;
   }
   __syncthreads();
   if (!last || threadIdx.x >= 64) return;
   float s = 0.f;
+  double valid = 0.0;
   for (int i = threadIdx.x; i < nb; i += 64) {
-    float a2 = 0.f, a1 = 0.f;
+    float a2 = 0.f, a1 = 0.f, an = 0.f;
 #pragma unroll
     for (int q = 0; q < kSilogParts; ++q) {
-      a2 += __hip_atomic_load(&partials[2 * (i * kSilogParts + q)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      a1 += __hip_atomic_load(&partials[2 * (i * kSilogParts + q) + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      a2 += __hip_atomic_load(&partials[K * (i * kSilogParts + q)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      a1 += __hip_atomic_load(&partials[K * (i * kSilogParts + q) + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if constexpr (MASKED)
+        an += __hip_atomic_load(&partials[K * (i * kSilogParts + q) + 2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    ws[1 + 2 * i] = a2;
-    ws[2 + 2 * i] = a1;
-    s += a2 - c * (a1 * a1);
+    ws[1 + K * i] = a2;
+    ws[2 + K * i] = a1;
+    if constexpr (MASKED) {
+      ws[3 + K * i] = an;
+      valid += (double)an;
+      if (an > 0.f) {
+        const float cn = (float)(0.5 / (double)an), rn = (float)((double)npix / (double)an);
+        s += rn * (a2 - cn * (a1 * a1));
+      }
+    } else {
+      s += a2 - c * (a1 * a1);
+    }
   }
   s = wave_sum(s);
-  if (threadIdx.x == 0) loss[0] = s / (float)nb;
+  if constexpr (MASKED) valid = wave_sum(valid);
+  if (threadIdx.x == 0) {
+    loss[0] = s / (float)nb;
+    if constexpr (MASKED) loss[1] = (float)(valid / ((double)nb * (double)npix));
+  }
 }
 
+template <bool MASKED>
 __global__ __launch_bounds__(256) void silog_bwd_kernel(const float* __restrict__ out, const float* __restrict__ tgt,
                                                         const float* __restrict__ ws, float* __restrict__ dout, int b,
                                                         int npix, float c, float inv_b, __bf16* __restrict__ dout16 = nullptr,
@@ -485,7 +577,16 @@ __global__ __launch_bounds__(256) void silog_bwd_kernel(const float* __restrict_
     const float arg = __fadd_rn(o, 1e-8f);
     const float lo = logf(arg);
     float g = 0.f;
-    if (!isnan(lo)) {
+    if constexpr (MASKED) {
+      const float t = tgt[i];
+      if (!isnan(lo) && isfinite(t)) {          // a pixel that counts: its sample has n >= 1
+        const float d = __fsub_rn(lo, masked_log(t));
+        const float sd = ws[3 * smp + 2];
+        const double n = (double)ws[3 * smp + 3];
+        const float cn = (float)(0.5 / n), rn = (float)((double)npix / n);
+        g = __fdiv_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fmul_rn(2.f, d), __fmul_rn(__fmul_rn(2.f, cn), sd)), inv_b), rn), arg);
+      }
+    } else if (!isnan(lo)) {
       const float d = __fsub_rn(lo, masked_log(tgt[i]));
       const float sd = ws[2 * smp + 2];
       g = __fdiv_rn(__fmul_rn(__fsub_rn(__fmul_rn(2.f, d), __fmul_rn(__fmul_rn(2.f, c), sd)), inv_b), arg);
@@ -924,6 +1025,55 @@ int a3d_warp_bilinear_pair(int n, int h, int w, int c0, const void* x0, int u8_0
   return check_launch("warp_pair");
 }
 
+int a3dx_resize_bilinear_tf1_valid(int n, int h, int w, int c0, const void* x0, int u8_0, int oh0, int ow0, float* y0, int c1,
+                                  const void* x1, int u8_1, int oh1, int ow1, float* y1, float min_depth, float max_depth,
+                                  void* stream) {
+  A3D_CHECK_ARG(n > 0 && h > 0 && w > 0 && c0 > 0 && oh0 > 0 && ow0 > 0 && x0 && y0, "resize_valid: bad arguments");
+  A3D_CHECK_ARG(x1 && c1 > 0 && oh1 > 0 && ow1 > 0 && y1, "resize_valid: the second tensor, the depth map, is required");
+  A3D_CHECK_ARG(min_depth <= max_depth, "resize_valid: thresholds %g, %g (NaN, or min_depth > max_depth)", (double)min_depth,
+                (double)max_depth);
+  ResizePairValid p;
+  p.n = n;
+  p.lo = min_depth;
+  p.hi = max_depth;
+  p.t[0] = resize_one(h, w, c0, static_cast<const float*>(x0), oh0, ow0, y0, u8_0 ? 1 : 0);
+  p.t[1] = resize_one(h, w, c1, static_cast<const float*>(x1), oh1, ow1, y1, u8_1 ? 1 : 0);
+  clear_stale_error();
+  hipLaunchKernelGGL(resize_valid_kernel, dim3((unsigned)std::min(n * std::max(oh0, oh1), 16384), 2), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), p);
+  return check_launch("resize_valid");
+}
+
+int a3dx_warp_bilinear_pair_valid(int n, int h, int w, int c0, const void* x0, int u8_0, int oh0, int ow0, float* y0, int c1,
+                                 const void* x1, int u8_1, int oh1, int ow1, float* y1, const float* table, float min_depth,
+                                 float max_depth, void* stream) {
+  A3D_CHECK_ARG(n > 0 && h > 0 && w > 0 && c0 > 0 && oh0 > 0 && ow0 > 0 && x0 && y0, "warp_pair_valid: bad arguments");
+  A3D_CHECK_ARG(c0 <= 4, "warp_pair_valid: the table holds 4 channel gains, the first tensor has %d channels", c0);
+  A3D_CHECK_ARG(x1 && c1 > 0 && oh1 > 0 && ow1 > 0 && y1, "warp_pair_valid: the second tensor, the depth map, is required");
+  A3D_CHECK_ARG(table, "warp_pair_valid: no table");
+  A3D_CHECK_ARG(min_depth <= max_depth, "warp_pair_valid: thresholds %g, %g (NaN, or min_depth > max_depth)",
+                (double)min_depth, (double)max_depth);
+  const long long lim = 0x7fffffffLL;       // the kernel's index arithmetic is 32-bit
+  A3D_CHECK_ARG((long long)h * w * std::max(c0, c1) <= lim && (long long)n * A3D_WARP_STRIDE <= lim,
+                "warp_pair_valid: image too large");
+  WarpPairValid p;
+  p.n = n;
+  p.table = table;
+  p.lo = min_depth;
+  p.hi = max_depth;
+  p.t[0] = resize_one(h, w, c0, static_cast<const float*>(x0), oh0, ow0, y0, u8_0 ? 1 : 0);
+  p.t[1] = resize_one(h, w, c1, static_cast<const float*>(x1), oh1, ow1, y1, u8_1 ? 1 : 0);
+  auto tiles = [&](int oh, int ow) {
+    return (long long)n * ((oh + kWarpTH - 1) / kWarpTH) * ((ow + kWarpTW - 1) / kWarpTW);
+  };
+  const long long blocks = std::max(tiles(oh0, ow0), tiles(oh1, ow1));
+  A3D_CHECK_ARG(blocks <= lim, "warp_pair_valid: output too large");
+  clear_stale_error();
+  hipLaunchKernelGGL(warp_valid_kernel, dim3((unsigned)std::min(blocks, (long long)kWarpBlocks), 2), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), p);
+  return check_launch("warp_pair_valid");
+}
+
 int a3d_extract_patches(int n, int h, int w, int c, const float* x, int k, int stride, float* y, void* stream) {
   A3D_CHECK_ARG(n > 0 && h > 0 && w > 0 && c > 0 && k > 0 && stride > 0 && x && y, "patches: bad arguments");
   const int ph = (h + stride - 1) / stride, pw = (w + stride - 1) / stride;
@@ -941,7 +1091,7 @@ int a3d_silog_loss_fwd(int b, int npix, const float* out, const float* tgt, floa
   A3D_CHECK_ARG(b > 0 && npix > 0 && out && tgt && loss && ws, "silog_fwd: bad arguments");
   hipStream_t st = static_cast<hipStream_t>(stream);
   clear_stale_error();
-  hipLaunchKernelGGL(silog_fwd_kernel, dim3(b * kSilogParts), dim3(256), 0, st, out, tgt, ws, loss, npix, b, kSilogC);
+  hipLaunchKernelGGL(silog_fwd_kernel<false>, dim3(b * kSilogParts), dim3(256), 0, st, out, tgt, ws, loss, npix, b, kSilogC);
   return check_launch("silog_fwd");
 }
 
@@ -950,7 +1100,7 @@ int a3d_silog_loss_bwd(int b, int npix, const float* out, const float* tgt, cons
   A3D_CHECK_ARG(b > 0 && npix > 0 && out && tgt && ws && dout, "silog_bwd: bad arguments");
   const size_t total = (size_t)b * npix;
   clear_stale_error();
-  hipLaunchKernelGGL(silog_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), out, tgt,
+  hipLaunchKernelGGL(silog_bwd_kernel<false>, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), out, tgt,
                      ws, dout, b, npix, kSilogC, 1.0f / (float)b);
   return check_launch("silog_bwd");
 }
@@ -960,9 +1110,29 @@ int a3d_silog_loss_bwd_ex(int b, int npix, const float* out, const float* tgt, c
   A3D_CHECK_ARG(b > 0 && npix > 0 && out && tgt && ws && dout && (!dout_bf16 || ld_bf16 >= npix), "silog_bwd: bad arguments");
   const size_t total = (size_t)b * npix;
   clear_stale_error();
-  hipLaunchKernelGGL(silog_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), out, tgt,
+  hipLaunchKernelGGL(silog_bwd_kernel<false>, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), out, tgt,
                      ws, dout, b, npix, kSilogC, 1.0f / (float)b, static_cast<__bf16*>(dout_bf16), ld_bf16);
   return check_launch("silog_bwd");
+}
+
+int a3dx_silog_masked_loss_fwd(int b, int npix, const float* out, const float* tgt, float* loss, float* ws, void* stream) {
+  A3D_CHECK_ARG(b > 0 && npix > 0 && out && tgt && loss && ws, "silog_masked_fwd: bad arguments");
+  A3D_CHECK_ARG(npix <= (1 << 24), "silog_masked_fwd: %d pixels per sample, the count is kept in a float", npix);
+  clear_stale_error();
+  hipLaunchKernelGGL(silog_fwd_kernel<true>, dim3(b * kSilogParts), dim3(256), 0, static_cast<hipStream_t>(stream), out, tgt,
+                     ws, loss, npix, b, 0.f);
+  return check_launch("silog_masked_fwd");
+}
+
+int a3dx_silog_masked_loss_bwd_ex(int b, int npix, const float* out, const float* tgt, const float* ws, float* dout,
+                                 void* dout_bf16, int ld_bf16, void* stream) {
+  A3D_CHECK_ARG(b > 0 && npix > 0 && out && tgt && ws && dout && (!dout_bf16 || ld_bf16 >= npix),
+                "silog_masked_bwd: bad arguments");
+  const size_t total = (size_t)b * npix;
+  clear_stale_error();
+  hipLaunchKernelGGL(silog_bwd_kernel<true>, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), out, tgt,
+                     ws, dout, b, npix, 0.f, 1.0f / (float)b, static_cast<__bf16*>(dout_bf16), ld_bf16);
+  return check_launch("silog_masked_bwd");
 }
 
 int a3d_dropout_keep_mask(size_t count, uint64_t seed, uint64_t step, float rate, uint8_t* keep, void* stream) {

@@ -126,11 +126,20 @@ class MSDNReplica:
     """One data-parallel replica of the MSDN training graph (src/models.py:203-367) on one GPU."""
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, global_step=0, beta2=1.0, reducer=None,
-                 precision='fp32', keep_dense_grads=True, overlap=True):
+                 precision='fp32', keep_dense_grads=True, overlap=True, valid_range=None):
         """precision: arithmetic of the conv contractions — 'fp32' (exact, the parity default), 'bf16x3' (split
         operands on the bf16 matrix cores, ~1e-5) or 'bf16' (BASELINE config 5).  Tensors stay float32 in HBM; the
         Cin = 3 layers, the dense layers and everything element-wise always compute in fp32.
-        overlap=False: everything on the current stream (the one-stream schedule the two-stream one must equal bit for bit)."""
+        overlap=False: everything on the current stream (the one-stream schedule the two-stream one must equal bit for bit).
+        valid_range (NON-REFERENCE): (min_depth, max_depth) — the depth maps have holes.  The target is resized (or warped)
+        validity-aware: an element whose taps are not all finite and in (min_depth, max_depth] becomes NaN, and both losses
+        run over the finite targets only (ops.silog_masked_loss_fwd).  None: the reference's step, launch for launch."""
+        if valid_range is not None:
+            lo, hi = (float(v) for v in valid_range)
+            if not lo <= hi:
+                raise ValueError(f'valid_range {valid_range!r}: (min_depth, max_depth) with min_depth <= max_depth')
+            valid_range = (lo, hi)
+        self.valid_range = valid_range
         # keep_dense_grads=False (the training driver and bench.py on one GPU): under the reference's frozen optimizer the
         # gradient of the two dense kernels (268 MB) goes straight from the matrix cores into ApplyAdam's m slot
         # (ops.dense_bwd_filter_adam_tf1) and is never written; grad('coarse/dense/...') is then stale.  A data-parallel
@@ -244,12 +253,17 @@ class MSDNReplica:
         self.f2 = buf(B, OUT_H, OUT_W, 64)
         self.fine = buf(B, OUT_H, OUT_W, 1)
         self.loss_coarse = buf(1); self.loss_fine = buf(1)
+        if valid_range is not None:       # the masked loss writes the valid fraction of the target behind the loss
+            self.loss_pair_c = buf(2); self.loss_pair_f = buf(2)
+            self.loss_coarse = self.loss_pair_c[:1]; self.loss_fine = self.loss_pair_f[:1]
         # window positions of the pool maxima (all MaxPoolGrad needs besides the pooled values, see forward())
         self.a0 = torch.empty((B, 27, 37, 96), dtype=torch.uint8, device=dev)
         self.a1 = torch.empty((B, 13, 18, 256), dtype=torch.uint8, device=dev)
         self.af1 = torch.empty((B, OUT_H, OUT_W, 63), dtype=torch.uint8, device=dev)
         self.pooled_fwd = None            # which network ran conv + pool fused in the last forward
-        self.ws_c = ops.silog_ws(B, dev); self.ws_f = ops.silog_ws(B, dev)   # per-sample sums + arrival ticket + partials
+        silog_ws = ops.silog_ws if valid_range is None else ops.silog_masked_ws
+        self.ws_c = silog_ws(B, dev); self.ws_f = silog_ws(B, dev)           # per-sample sums + arrival ticket + partials
+        self.t_one = buf(B, 1, 1, 1) if valid_range is not None else None    # see ops.resize_bilinear_tf1_valid
         # gradients wrt pre-activations
         self.dz1 = buf(B, OUT_H * OUT_W); self.dz0 = buf(B, 4096)
         self.dc4 = abuf(B, 6, 8, 256); self.dc3 = abuf(B, 13, 18, 384); self.dc2 = abuf(B, 13, 18, 384)
@@ -602,13 +616,17 @@ class MSDNReplica:
 
     def summary_scalars(self, out):
         """Tags as the reference's name scopes 'loss' (src/models.py:288) and 'optimizers' (:347)."""
-        return {'loss/coarse_loss': float(out['coarse_loss']), 'loss/fine_loss': float(out['fine_loss']),
-                'optimizers/Phase': out['phase']}
+        rec = {'loss/coarse_loss': float(out['coarse_loss']), 'loss/fine_loss': float(out['fine_loss']),
+               'optimizers/Phase': out['phase']}
+        if self.valid_range is not None:                 # NON-REFERENCE: share of the target pixels that hold a depth
+            rec['valid_fraction'] = float(self.loss_pair_c[1])
+        return rec
 
     def summary_images(self):
         """src/models.py:292-296: (tag, batch, max_outputs)."""
+        target = self.t if self.valid_range is None else torch.nan_to_num(self.t[:3], nan=0.0)    # a hole is shown as 0
         return [('summaries/Input', self.x, 3), ('summaries/Coarse', self.coarse, 3), ('summaries/Fine', self.fine, 3),
-                ('summaries/Target', self.t, 3)]
+                ('summaries/Target', target, 3)]
 
     def broadcast_state(self, dist, src=0):
         """Non-chief replicas take the chief's variables, slots, beta powers and global_step."""
@@ -699,6 +717,15 @@ class MSDNReplica:
         the place of the resize launch; images and depths are stored at the same size."""
         if depths is None:
             pass
+        elif self.valid_range is not None:
+            lo, hi = self.valid_range
+            if warp is not None:
+                ops.warp_bilinear_pair_valid(images, self.x, depths, self.t, warp, lo, hi)
+            elif images.shape[:3] == depths.shape[:3]:
+                ops.resize_bilinear_tf1_pair_valid(images, self.x, depths, self.t, lo, hi)
+            else:
+                ops.resize_bilinear_tf1(images, self.x)
+                ops.resize_bilinear_tf1_valid(depths, self.t, lo, hi, scratch=self.t_one)
         elif warp is not None:
             ops.warp_bilinear_pair(images, self.x, depths, self.t, warp)
         elif images.shape[:3] == depths.shape[:3]:
@@ -791,9 +818,15 @@ class MSDNReplica:
             self._conv('fine/second/conv2d', self.cat, self.f2)
             self._conv('fine/third', self.f2, self.fine)
             if depths is not None:
-                ops.silog_loss_fwd(self.fine, self.t, self.loss_fine, self.ws_f)
+                if self.valid_range is None:
+                    ops.silog_loss_fwd(self.fine, self.t, self.loss_fine, self.ws_f)
+                else:
+                    ops.silog_masked_loss_fwd(self.fine, self.t, self.loss_pair_f, self.ws_f)
         if depths is not None:
-            ops.silog_loss_fwd(self.coarse, self.t, self.loss_coarse, self.ws_c)
+            if self.valid_range is None:
+                ops.silog_loss_fwd(self.coarse, self.t, self.loss_coarse, self.ws_c)
+            else:
+                ops.silog_masked_loss_fwd(self.coarse, self.t, self.loss_pair_c, self.ws_c)
         if join:
             self._join()
 
@@ -843,8 +876,9 @@ class MSDNReplica:
     def backward_coarse(self, after_dense=None, after_conv2=None, after_dense1=None):
         B = self.B
         bf16_x = self.bf16s and self.dense_bf16_x
-        ops.silog_loss_bwd(self.coarse, self.t, self.ws_c, self.dz1.view(B, OUT_H, OUT_W, 1),
-                           dout16=self.dz1_16 if bf16_x else None)        # (dz1 a second time as bf16 rows of 4072: dense_1's bwd-data)
+        silog_bwd = ops.silog_loss_bwd if self.valid_range is None else ops.silog_masked_loss_bwd
+        silog_bwd(self.coarse, self.t, self.ws_c, self.dz1.view(B, OUT_H, OUT_W, 1),
+                  dout16=self.dz1_16 if bf16_x else None)        # (dz1 a second time as bf16 rows of 4072: dense_1's bwd-data)
         self.settle()              # a reduce-scatter of the previous step may still be reading the dense gradient buffer
         n = 'coarse/dense/dense_1'
         self._bwd_filter(n, self.drop, self.dz1)
@@ -917,7 +951,8 @@ class MSDNReplica:
     # ---- backward of loss_fine wrt fine/* : src/models.py:333-338 ----
     def backward_fine(self):
         self._join()                                                          # the fine forward ran on the side stream
-        ops.silog_loss_bwd(self.fine, self.t, self.ws_f, self.dfine)
+        silog_bwd = ops.silog_loss_bwd if self.valid_range is None else ops.silog_masked_loss_bwd
+        silog_bwd(self.fine, self.t, self.ws_f, self.dfine)
         n = 'fine/third'
         if ops.conv2d_bwd_both_supported(self.d[n]):
             # filter, bias and input gradient (+ fine/second's ReluGrad) in one pass over f2
@@ -1498,13 +1533,15 @@ class _MultiScaleDeepNetwork:
     seed = 3000
     precision = 'fp32'   # --precision: 'fp32' | 'bf16x3' | 'bf16' (see MSDNReplica)
     augment = None       # NON-REFERENCE, --augment eigen: an augment.Eigen2014 (train-time augmentation of the input batch)
+    valid_range = None   # NON-REFERENCE, --min-depth / --max-depth: (min, max), the depth maps have holes (see MSDNReplica)
 
     def __call__(self, images, depths, train=True):
         assert images.pipeline is depths.pipeline, 'inputs and targets must come from the same data.inputs() call'
         self.train = train
         replica = MSDNReplica(images.pipeline.B, device=torch.device('cuda', torch.cuda.current_device()),
                               seed=self.seed, beta2=self.beta2, reducer=self.reducer, precision=self.precision,
-                              keep_dense_grads=False)        # one GPU + the reference's optimizer: dW feeds ApplyAdam directly
+                              keep_dense_grads=False,        # one GPU + the reference's optimizer: dW feeds ApplyAdam directly
+                              valid_range=self.valid_range)
         replica.uses_dropout = bool(train)                   # train=False: tf.layers.dropout(training=False), src/models.py:230
         if self.reducer is not None:                         # replicas start from rank 0's weights
             for g in replica.groups.values():

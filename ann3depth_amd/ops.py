@@ -311,38 +311,91 @@ def resize_bilinear_tf1_pair(x0, y0, x1, y1):
 WARP_STRIDE = 12                     # A3D_WARP_STRIDE (include/a3d.h)
 
 
-def warp_bilinear_pair(x0, y0, x1, y1, table):
-    """resize_bilinear_tf1_pair through a per-image affine map and gains (a3d_warp_bilinear_pair): x0 -> y0 and, unless
-    x1 is None, x1 -> y1.  x0 / x1 [n, h, w, c] float32 or uint8, y0 / y1 float32, table [n, 12] float32, all contiguous
-    tensors of one device."""
+def _check_pair(who, x0, y0, x1, y1, table):
+    """The argument checks of warp_bilinear_pair and the validity-aware pair launches (table None: a launch without one)."""
     if x0.dim() != 4 or y0.dim() != 4 or y0.shape[0] != x0.shape[0] or y0.shape[3] != x0.shape[3]:
-        raise ValueError(f'warp_bilinear_pair: {tuple(x0.shape)} -> {tuple(y0.shape)}')
+        raise ValueError(f'{who}: {tuple(x0.shape)} -> {tuple(y0.shape)}')
     n, h, w, c0 = x0.shape
     if (x1 is None) != (y1 is None):
-        raise ValueError('warp_bilinear_pair: x1 and y1 go together')
+        raise ValueError(f'{who}: x1 and y1 go together')
     if x1 is not None and (x1.dim() != 4 or tuple(x1.shape[:3]) != (n, h, w) or y1.dim() != 4
                            or y1.shape[0] != n or y1.shape[3] != x1.shape[3]):
-        raise ValueError(f'warp_bilinear_pair: second tensor {tuple(x1.shape)} -> {tuple(y1.shape)} beside '
+        raise ValueError(f'{who}: second tensor {tuple(x1.shape)} -> {tuple(y1.shape)} beside '
                          f'{tuple(x0.shape)}')
-    if tuple(table.shape) != (n, WARP_STRIDE) or table.dtype != torch.float32:
-        raise ValueError(f'warp_bilinear_pair: table {tuple(table.shape)} {table.dtype}, want [{n}, {WARP_STRIDE}] float32')
+    if table is not None and (tuple(table.shape) != (n, WARP_STRIDE) or table.dtype != torch.float32):
+        raise ValueError(f'{who}: table {tuple(table.shape)} {table.dtype}, want [{n}, {WARP_STRIDE}] float32')
     for name, t, dtypes in (('x0', x0, (torch.float32, torch.uint8)), ('y0', y0, (torch.float32,)),
                             ('x1', x1, (torch.float32, torch.uint8)), ('y1', y1, (torch.float32,)),
                             ('table', table, (torch.float32,))):
         if t is None:
             continue
         if t.dtype not in dtypes:
-            raise ValueError(f'warp_bilinear_pair: {name} is {t.dtype}')
+            raise ValueError(f'{who}: {name} is {t.dtype}')
         if not t.is_cuda or t.device != x0.device:
-            raise ValueError(f'warp_bilinear_pair: {name} is on {t.device}, x0 on {x0.device}')
+            raise ValueError(f'{who}: {name} is on {t.device}, x0 on {x0.device}')
         if not t.is_contiguous():
-            raise ValueError(f'warp_bilinear_pair: {name} is not contiguous')
+            raise ValueError(f'{who}: {name} is not contiguous')
+    return n, h, w, c0
+
+
+def warp_bilinear_pair(x0, y0, x1, y1, table):
+    """resize_bilinear_tf1_pair through a per-image affine map and gains (a3d_warp_bilinear_pair): x0 -> y0 and, unless
+    x1 is None, x1 -> y1.  x0 / x1 [n, h, w, c] float32 or uint8, y0 / y1 float32, table [n, 12] float32, all contiguous
+    tensors of one device."""
+    if table is None:
+        raise ValueError('warp_bilinear_pair: no table')
+    n, h, w, c0 = _check_pair('warp_bilinear_pair', x0, y0, x1, y1, table)
     second = x1 is not None
     check(_lib.load().a3d_warp_bilinear_pair(n, h, w, c0, _ptr(x0), int(x0.dtype == torch.uint8), y0.shape[1], y0.shape[2],
                                              _ptr(y0), x1.shape[3] if second else 0, _ptr(x1),
                                              int(second and x1.dtype == torch.uint8), y1.shape[1] if second else 0,
                                              y1.shape[2] if second else 0, _ptr(y1), _ptr(table), _stream()),
           'a3d_warp_bilinear_pair')
+
+
+def _valid_range(who, x1, min_depth, max_depth):
+    if x1 is None:
+        raise ValueError(f'{who}: the depth map x1 is required')
+    lo, hi = float(min_depth), float(max_depth)
+    if not lo <= hi:
+        raise ValueError(f'{who}: min_depth {lo}, max_depth {hi}')
+    return lo, hi
+
+
+def resize_bilinear_tf1_pair_valid(x0, y0, x1, y1, min_depth=0., max_depth=float('inf')):
+    """NON-REFERENCE: resize_bilinear_tf1_pair for a depth map x1 with holes (a3dx_resize_bilinear_tf1_valid): an element of
+    y1 whose counting taps are not all finite and in (min_depth, max_depth] is NaN, every other bit of y0 and y1 is the
+    plain launch's.  Tensors as warp_bilinear_pair's."""
+    who = 'resize_bilinear_tf1_pair_valid'
+    lo, hi = _valid_range(who, x1, min_depth, max_depth)
+    n, h, w, c0 = _check_pair(who, x0, y0, x1, y1, None)
+    check(_lib.load().a3dx_resize_bilinear_tf1_valid(n, h, w, c0, _ptr(x0), int(x0.dtype == torch.uint8), y0.shape[1], y0.shape[2],
+                                                    _ptr(y0), x1.shape[3], _ptr(x1), int(x1.dtype == torch.uint8), y1.shape[1],
+                                                    y1.shape[2], _ptr(y1), lo, hi, _stream()),
+          'a3dx_resize_bilinear_tf1_valid')
+
+
+def resize_bilinear_tf1_valid(x, y, min_depth=0., max_depth=float('inf'), scratch=None):
+    """NON-REFERENCE: the depth map x alone (stored at another size than its image).  The entry point's tensor 0 is then x
+    itself, resized to one pixel per image into `scratch` ([n, 1, 1, c] float32, allocated here when None)."""
+    if scratch is None:
+        scratch = torch.empty((x.shape[0], 1, 1, x.shape[3]), device=x.device)
+    resize_bilinear_tf1_pair_valid(x, scratch, x, y, min_depth, max_depth)
+    return y
+
+
+def warp_bilinear_pair_valid(x0, y0, x1, y1, table, min_depth=0., max_depth=float('inf')):
+    """NON-REFERENCE: warp_bilinear_pair for a depth map x1 with holes (a3dx_warp_bilinear_pair_valid); the thresholds are
+    compared with the stored depth, before the table's depth gain."""
+    who = 'warp_bilinear_pair_valid'
+    if table is None:
+        raise ValueError(f'{who}: no table')
+    lo, hi = _valid_range(who, x1, min_depth, max_depth)
+    n, h, w, c0 = _check_pair(who, x0, y0, x1, y1, table)
+    check(_lib.load().a3dx_warp_bilinear_pair_valid(n, h, w, c0, _ptr(x0), int(x0.dtype == torch.uint8), y0.shape[1], y0.shape[2],
+                                                   _ptr(y0), x1.shape[3], _ptr(x1), int(x1.dtype == torch.uint8), y1.shape[1],
+                                                   y1.shape[2], _ptr(y1), _ptr(table), lo, hi, _stream()),
+          'a3dx_warp_bilinear_pair_valid')
 
 
 def extract_patches(x, k, stride, y):
@@ -375,6 +428,35 @@ def silog_loss_bwd(out, tgt, ws, dout, dout16=None):
     npix = out.numel() // b
     check(_lib.load().a3d_silog_loss_bwd_ex(b, npix, _ptr(out), _ptr(tgt), _ptr(ws), _ptr(dout), _ptr(dout16),
                                             0 if dout16 is None else dout16.shape[-1], _stream()), 'a3d_silog_loss_bwd_ex')
+    return dout
+
+
+def silog_masked_ws(b, device):
+    """Workspace of silog_masked_loss_fwd / _bwd for a batch of b (or any smaller one): A3DX_SILOG_MASKED_WS_FLOATS(b)
+    zeros (the ticket, its first word, must start at zero)."""
+    return torch.zeros(3 * b + 1 + 3 * b * SILOG_PARTS, device=device)
+
+
+def silog_masked_loss_fwd(out, tgt, loss, ws):
+    """NON-REFERENCE: the loss over the finite targets only (a3dx_silog_masked_loss_fwd).  loss: 2 floats, the loss and the
+    fraction of valid target pixels."""
+    b = out.shape[0]
+    assert ws.numel() >= 3 * b + 1 + 3 * b * SILOG_PARTS, \
+        'silog workspace too small: allocate it with ops.silog_masked_ws(b, device)'
+    assert loss.numel() >= 2 and loss.is_contiguous(), 'silog_masked_loss_fwd writes two floats'
+    npix = out.numel() // b
+    check(_lib.load().a3dx_silog_masked_loss_fwd(b, npix, _ptr(out), _ptr(tgt), _ptr(loss), _ptr(ws), _stream()),
+          'a3dx_silog_masked_loss_fwd')
+    return loss
+
+
+def silog_masked_loss_bwd(out, tgt, ws, dout, dout16=None):
+    """dout16 as silog_loss_bwd's."""
+    b = out.shape[0]
+    npix = out.numel() // b
+    check(_lib.load().a3dx_silog_masked_loss_bwd_ex(b, npix, _ptr(out), _ptr(tgt), _ptr(ws), _ptr(dout), _ptr(dout16),
+                                                   0 if dout16 is None else dout16.shape[-1], _stream()),
+          'a3dx_silog_masked_loss_bwd_ex')
     return dout
 
 
