@@ -65,7 +65,8 @@ __global__ __launch_bounds__(256) void superpixel_hist_kernel(const float* __res
   hist[((size_t)b * rows * cols + p) * 256 + threadIdx.x] = (float)bins[threadIdx.x];
 }
 
-// similarity() of both feature kinds for one (image, pair) + the pairwise dense layer (2 -> 1)
+// similarity() of both feature kinds for one (image, pair) + the pairwise dense layer (2 -> 1).  A pair with an index
+// outside [0, nsp) gets NaN similarities and a NaN r in every image; the other pairs do not notice.
 __global__ __launch_bounds__(256) void pair_similarity_kernel(const float* __restrict__ x, const float* __restrict__ hist,
                                                               const int* __restrict__ left, const int* __restrict__ right,
                                                               const float* __restrict__ dw, const float* __restrict__ db,
@@ -75,6 +76,13 @@ __global__ __launch_bounds__(256) void pair_similarity_kernel(const float* __res
   const int cols = w / sp, nsp = (h / sp) * cols;
   const int q = blockIdx.x % npairs, b = blockIdx.x / npairs;
   const int pl = left[q], pr = right[q];
+  if (pl < 0 || pl >= nsp || pr < 0 || pr >= nsp) {       // the whole block: nothing is indexed with a bad superpixel
+    if (threadIdx.x == 0) {
+      const size_t o = (size_t)b * npairs + q;
+      sims[2 * o] = sims[2 * o + 1] = r[o] = __builtin_nanf("");
+    }
+    return;
+  }
   float sc = 0.f;
   for (int i = threadIdx.x; i < sp * sp; i += 256) {
     const int dy = i / sp, dx = i % sp;
@@ -100,6 +108,7 @@ __global__ __launch_bounds__(256) void pair_similarity_kernel(const float* __res
 
 // One wavefront per image.  A = I + D - R from the pair weights, LU with partial pivoting on [A | z] in LDS:
 // det(A) = +-prod(pivots), w = A^-1 z by back substitution; then energy, partition function, loss, d loss / d z.
+// A pair index outside [0, n) is skipped, not used, and turns every image's loss and dz into NaN (as crf_map_kernel).
 constexpr int kMaxSp = 64;
 __global__ __launch_bounds__(64) void crf_loss_kernel(const float* __restrict__ z, const float* __restrict__ y,
                                                       const float* __restrict__ r, const int* __restrict__ left,
@@ -109,17 +118,23 @@ __global__ __launch_bounds__(64) void crf_loss_kernel(const float* __restrict__ 
   __shared__ float A[kMaxSp][kMaxSp + 1];
   __shared__ float U[kMaxSp][kMaxSp + 2];      // working copy, column n holds the right-hand side
   __shared__ float wv[kMaxSp];
+  __shared__ int bad_index;
   const int b = blockIdx.x, lane = threadIdx.x;
   for (int i = lane; i < n * n; i += 64) A[i / n][i % n] = 0.f;
   __syncthreads();
-  if (lane == 0) {                              // scatter the pair weights: R[l][r] = R[r][l] = r_q (no duplicates)
+  if (lane == 0) {                              // scatter the pair weights in pair order: R[l][r] = R[r][l] = r_q
+    int skipped = 0;
     for (int q = 0; q < npairs; ++q) {
+      const int l = left[q], rr = right[q];
+      if (l < 0 || l >= n || rr < 0 || rr >= n) { skipped = 1; continue; }     // skipped, never indexed with
       const float v = r[(size_t)b * npairs + q];
-      A[left[q]][right[q]] = v;
-      A[right[q]][left[q]] = v;
+      A[l][rr] = v;
+      A[rr][l] = v;
     }
+    bad_index = skipped;
   }
   __syncthreads();
+  const bool bad = bad_index != 0;              // the index lists are the batch's: every image ends as NaN
   const float zi = lane < n ? z[(size_t)b * n + lane] : 0.f;
   const float yi = lane < n ? y[(size_t)b * n + lane] : 0.f;
   if (lane < n) {                               // A = I + diag(row sums of R) - R
@@ -176,12 +191,12 @@ __global__ __launch_bounds__(64) void crf_loss_kernel(const float* __restrict__ 
   const float ex = expf(g);
   const float Z = fac * ex + eps;
   const float u = expf(-energy) / Z;
-  if (lane == 0) loss_img[b] = -logf(u + eps);
+  if (lane == 0) loss_img[b] = bad ? __builtin_nanf("") : -logf(u + eps);
   if (lane < n) {
     const float dE = -2.f * yi + 2.f * zi;
     const float dg = 2.f * wi + 2.f * eps * zsum - 2.f * zi;
     const float du = u * (-dE) - (u / Z) * (fac * ex * dg);
-    dz[(size_t)b * n + lane] = (-du / (u + eps)) * inv_batch;
+    dz[(size_t)b * n + lane] = bad ? __builtin_nanf("") : (-du / (u + eps)) * inv_batch;
   }
 }
 

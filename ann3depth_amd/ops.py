@@ -651,9 +651,23 @@ def superpixel_hist(x, sp, out=None):
 
 
 def pair_similarity(x, sp, hist, left, right, dense_w, dense_b, gamma=1.0):
-    """pairwise_part (src/models.py:108-127): returns (sims [n,Q,2], r [n,Q])."""
+    """pairwise_part (src/models.py:108-127): returns (sims [n,Q,2], r [n,Q]).  x [n,h,w,3], hist [n,P,256] float32;
+    left, right [Q] int32; dense_w 2 and dense_b 1 float32 values.  A pair with an index outside [0, P) gets NaN."""
+    if x.dim() != 4 or x.shape[3] != 3 or sp <= 0 or x.shape[1] % sp or x.shape[2] % sp:
+        raise ValueError(f'pair_similarity: x {tuple(x.shape)} is not [n, h, w, 3] with h, w multiples of sp = {sp}')
     n, h, w, _ = x.shape
     q = left.numel()
+    if (n == 0 or q == 0 or right.numel() != q or tuple(hist.shape) != (n, (h // sp) * (w // sp), 256)
+            or dense_w.numel() != 2 or dense_b.numel() != 1):
+        raise ValueError(f'pair_similarity: x {tuple(x.shape)}, sp {sp}, hist {tuple(hist.shape)}, {q} / '
+                         f'{right.numel()} pair indices, dense kernel {tuple(dense_w.shape)}, bias {tuple(dense_b.shape)}')
+    if (any(t.dtype != torch.float32 for t in (x, hist, dense_w, dense_b)) or left.dtype != torch.int32
+            or right.dtype != torch.int32):
+        raise TypeError('pair_similarity: x, hist, dense_w, dense_b float32; left, right int32')
+    if not all(t.is_contiguous() for t in (x, hist, left, right, dense_w, dense_b)):
+        raise ValueError('pair_similarity: contiguous tensors only')
+    if any(t.device != x.device for t in (hist, left, right, dense_w, dense_b)):
+        raise ValueError('pair_similarity: all tensors on one device')
     sims = torch.empty((n, q, 2), dtype=torch.float32, device=x.device)
     r = torch.empty((n, q), dtype=torch.float32, device=x.device)
     check(_lib.load().a3d_pair_similarity(n, h, w, _ptr(x), sp, _ptr(hist), _ptr(left), _ptr(right), q, _ptr(dense_w),
@@ -662,8 +676,22 @@ def pair_similarity(x, sp, hist, left, right, dense_w, dense_b, gamma=1.0):
 
 
 def crf_loss(z, y, r, left, right, eps=1e-7):
-    """loss_part (src/models.py:129-177): returns (mean loss [1], per-image loss [n], d mean / d z [n,P])."""
+    """loss_part (src/models.py:129-177): returns (mean loss [1], per-image loss [n], d mean / d z [n,P]).  z, y [n,P],
+    r [n,Q] float32; left, right [Q] int32.  A pair index outside [0, P) turns every loss and all of dz into NaN."""
+    if z.dim() != 2 or r.dim() != 2:
+        raise ValueError(f'crf_loss: z {tuple(z.shape)} and r {tuple(r.shape)} must be [n, P] and [n, Q]')
     n, nsp = z.shape[0], z.shape[1]
+    if (n == 0 or tuple(y.shape) != (n, nsp) or r.shape[0] != n or left.numel() == 0 or r.shape[1] != left.numel()
+            or left.numel() != right.numel()):
+        raise ValueError(f'crf_loss: z {tuple(z.shape)}, y {tuple(y.shape)}, r {tuple(r.shape)}, {left.numel()} / '
+                         f'{right.numel()} pair indices')
+    if (z.dtype != torch.float32 or y.dtype != torch.float32 or r.dtype != torch.float32 or left.dtype != torch.int32
+            or right.dtype != torch.int32):
+        raise TypeError('crf_loss: z, y, r float32; left, right int32')
+    if not all(t.is_contiguous() for t in (z, y, r, left, right)):
+        raise ValueError('crf_loss: contiguous tensors only')
+    if any(t.device != z.device for t in (y, r, left, right)):
+        raise ValueError('crf_loss: all tensors on one device')
     per = torch.empty((n,), dtype=torch.float32, device=z.device)
     mean = torch.empty((1,), dtype=torch.float32, device=z.device)
     dz = torch.empty((n, nsp), dtype=torch.float32, device=z.device)
