@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/a3d.h"
+#include "igemm_plan.h"
 
 namespace a3d {
 
@@ -25,37 +26,7 @@ inline int check_launch(const char* what) {
   return A3D_OK;
 }
 
-// Environment switches (capi.cc).  tune_int: A/B and sweep switches — the environment is consulted ONLY in a process started
-// with A3D_TUNING=1 (the tools under tools/ set it); anywhere else the default is returned and nothing reads the environment.
-bool tuning();
-int tune_int(const char* name, int dflt);
-
-// ---- implicit-GEMM front end (igemm_host.hip) ----
-struct GemmPlan {
-  int prec;          // A3D_PREC_*: 0 = fp32 kernel (cfg valid), else bf16 kernel (bf16_bn valid)
-  int bf16_bn;       // 128 or 64
-  int cfg;           // index into the config table
-  int splitk;
-  int ktiles_per_split;
-  int tiles_m, tiles_n;
-  int streamk;       // > 0: stream-K launch of this many blocks (splitk == 1)
-  size_t ws_bytes;   // split-K / stream-K slabs (0 if neither)
-  int ring;          // bf16 plans: 1 + tile configuration of the LDS-DMA kernel for bf16-stored operands (igemm_ring.h), 0 = igemm_bf16
-};
-
-struct GemmProblem {
-  int mode;          // MODE_*
-  int M, N, K;
-  int avec, bvec;    // 1 or 4
-  int plain = 0;     // 1: register-staged kernel without split-K only (fused-pool forward)
-  int need_reduce = 0;   // 1: the output is stored by the split-K reduction only (rows narrower than the GEMM's N): split-K >= 2, no stream-K
-  int no_glds = 0;   // 1: not the LDS-DMA kernels (bf16 output)
-  int ring_ok = 0;   // 1: both operands are bf16 tensors whose 16-byte pieces lie inside one filter tap (channels % 8 == 0):
-                     //    forward / stride-1 bwd-data may run on igemm_ring.h
-};
-
-GemmPlan plan_gemm(const GemmProblem& g, int precision = 0);
-
+// ---- implicit-GEMM front end: the planner (igemm_plan.h, igemm_plan.cc) and the launches (igemm_host.hip) ----
 struct IgemmParams;
 int launch_igemm(int mode, const GemmPlan& plan, int avec, int bvec, IgemmParams& p, void* ws, hipStream_t st);
 

@@ -17,6 +17,8 @@
 
 #include <type_traits>
 
+#include "igemm_plan.h"   // MODE_*
+
 namespace a3d {
 
 // In-kernel phase stamps for a separate diagnostic build (make STAMPS=1 -> tools/ab/): where a K-tile iteration spends
@@ -129,7 +131,6 @@ __device__ __forceinline__ void load_vec_buf(__amdgpu_buffer_rsrc_t r, uint32_t 
   }
 }
 
-enum { MODE_FWD = 0, MODE_BWD_D = 1, MODE_BWD_F = 2 };
 enum { EPI_RELU = 1, EPI_SIGMOID = 2 };
 
 struct IgemmParams {

@@ -1,16 +1,15 @@
-// igemm_host.hip — tile/split-K planning, dispatch, split-K reduction, bias-gradient column sums, and the
-// conv2d / dense entry points of include/a3d.h.
+// igemm_host.hip — dispatch of a planned GEMM (the plans: igemm_plan.cc), split-K reduction, bias-gradient column sums,
+// opt-in launch timing, and the conv2d / dense entry points of include/a3d.h.
 #include <algorithm>
-#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <map>
 #include <mutex>
 #include <vector>
 
 #include "a3d_internal.h"
 #include "igemm.h"
+#include "igemm_cfgs.h"
 
 namespace a3d {
 
@@ -25,27 +24,6 @@ int launch_igemm_multi_bwd_d(int avec, int bvec, IgemmMulti& ps, unsigned grid_x
 int launch_igemm_bf16_multi_bwd_d(int bn, IgemmMulti& ps, unsigned grid_x, unsigned count, hipStream_t st);
 int launch_igemm_ring(int mode, int cfg, IgemmParams& p, unsigned grid, hipStream_t st);
 
-// tile configurations of the LDS-DMA bf16 kernel (igemm_ring.hip: A3D_RING_CFGS + the 96-column bwd-data tile)
-struct RingTile { int bm, bn; };
-static const RingTile kRingCfgs[] = {{256, 128}, {256, 64}, {256, 256}, {128, 128}, {256, 96}, {512, 64}, {64, 128}};
-
-struct TileCfg {
-  int bm, bn;
-  float eff;   // relative efficiency of the configuration, fitted (tools/fit_planner.py); 0 = only via A3D_FORCE_CFG
-  int bk;
-};
-static const TileCfg kCfgs[] = {{128, 128, 1.00f, 32}, {128, 96, 1.00f, 32}, {128, 64, 0.92f, 32}, {128, 32, 0.60f, 32},
-                                {64, 64, 0.98f, 32},   {32, 128, 0.90f, 32}, {64, 128, 1.00f, 32},
-                                {128, 128, 1.15f, 32}, {128, 64, 1.05f, 32},      // 8-wave blocks
-                                // LDS-DMA staged (igemm_glds.h), same order as A3D_GLDS_CFGS; forward only.  Round 1:
-                                // +3-5 % over the register-staged twins; since those stage through buffer loads with
-                                // addresses computed a tile ahead (round 2) they are the faster ones (fine/second
-                                // forward 245 vs 259 us, conv2d_1 325 vs 339 us: profiles/r02_sweep_hot.txt)
-                                {128, 128, 1.10f, 32}, {128, 64, 1.00f, 32}};
-static const int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
-static const int kSlots = 512;               // 256 CUs x 2 resident blocks
-static const size_t kMaxSlabBytes = (size_t)192 << 20;
-
 #ifdef A3D_STAMPS
 static unsigned long long* g_stamps = nullptr;
 static unsigned g_stamp_grid = 0;
@@ -54,16 +32,9 @@ static const size_t kStampBytes = (size_t)8 << 20;
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// Tuning aids (tools/sweep_igemm.py): A3D_FORCE_CFG / A3D_FORCE_SPLITK pin the tile config / split-K factor.  Every switch
-// below goes through tune_int(): none of them is read in a process that was not started with A3D_TUNING=1.
-// A/B switches of the staging fast paths (tools/bench_layers.py); read once per tuning process
-// The A3D_FORCE_* / A3D_NO_* / A3D_BF16_BN switches of the sweep and fuzz tools are consulted on every launch ONLY in
-// a process started with A3D_TUNING=1 (the tools set it); otherwise nothing below reads the environment after its first
-// call, and plans are cached per problem (plan_gemm).
-// (tuning() / tune_int(): a3d_internal.h, capi.cc)
-static bool env_flag_no_uni() { static const bool v = tune_int("A3D_NO_UNI", 0) != 0; return v; }
-static bool env_flag_no_streamk() { static const bool v = tune_int("A3D_NO_STREAMK", 0) != 0; return v; }
-static bool env_flag_no_kperm() { static const bool v = tune_int("A3D_NO_KPERM", 0) != 0; return v; }
+// The switches read below (A3D_PLAN_LOG, A3D_DBG, A3D_FEWCH, ...) and the planner's (A3D_FORCE_*, A3D_BF16_BN, A3D_RING*) all go
+// through tune_int() (igemm_plan.h, capi.cc): the environment is consulted on every launch ONLY in a process started with
+// A3D_TUNING=1, as the sweep and fuzz tools do; otherwise nothing reads it, and plans are cached per problem (plan_gemm).
 
 // ---- opt-in launch timing (a3d_timing_*) ----
 struct TimingSlot {
@@ -96,260 +67,27 @@ static void timing_end(TimingSlot& slot, hipStream_t st) {
   std::lock_guard<std::mutex> lk(g_timing_mu);
   g_timing.push_back(slot);
 }
-static const int kCfgWavesM[] = {2, 4, 4, 4, 2, 1, 1, 4, 4, 4, 4};
-static const int kCfgNWaves[] = {4, 4, 4, 4, 4, 4, 4, 8, 8, 8, 8};
-static const int kFirstGldsCfg = 9;
-// the forward-only LDS-DMA kernels of round 1 (igemm_glds.h)
-static inline bool is_glds_cfg(int c) { return c >= kFirstGldsCfg; }
-// configurations that run stream-K shares (slabs + igemm_fixup_kernel)
-static inline bool streamk_cfg(int c) { return c < kFirstGldsCfg; }
-
-// bf16 / bf16x3 kernel: BM = 128.  Staging-bound rather than MFMA-bound: the wider tile wins whenever N allows it
-// (even at one block per CU for the two-plane x3 variant); split-K factors: x3 by round 1's sweep
-// (profiles/r01_sweep_bf16.txt: ~600 blocks with >= 12 k-tiles each), plain bf16 by round 3's, below.
-// bf16-stored operands, forward / stride-1 bwd-data: igemm_ring.h.  One block of eight waves per CU works on a 256-row tile
-// (128 rows, two blocks per CU, where 256-row tiles would leave a third of the chip idle); never split (a launch that small
-// stays on igemm_bf16's split-K).  A3D_RING=0 turns the kernel off, A3D_RING_CFG pins a tile (tuning processes).
-static bool ring_plan(const GemmProblem& g, GemmPlan& pl) {
-  static const bool off = tune_int("A3D_RING", 1) == 0;
-  if (!g.ring_ok || (g.plain && g.mode != MODE_FWD)) return false;      // (plain = the forward with the 2x2 max pool fused: never split)
-  if (g.mode != MODE_BWD_F && g.M <= 64 && g.N >= 1024 && g.K >= 1024) {      // (not under A3D_RING: bf16 x / dz have no other kernel)
-    // a dense layer of a small batch: a weight stream.  64-row tiles of 128 columns, K split until ~512 blocks (three per
-    // CU) pull on HBM; the slabs are a few MB
-    pl.ring = 1 + 6;
-    pl.tiles_m = 1;
-    pl.tiles_n = (g.N + 127) / 128;
-    const int nk = std::max(1, (g.K + 63) / 64);
-    int splitk = (int)std::min<long>(std::max<long>(512 / pl.tiles_n, 1), std::max(1, nk / 4));
-    if (tune_int("A3D_FORCE_SPLITK", 0) > 0) splitk = std::min(tune_int("A3D_FORCE_SPLITK", 0), nk);
-    if (g.need_reduce && nk >= 2) splitk = std::max(splitk, 2);      // rows narrower than the GEMM: stored by the reduction
-    const int kps = (nk + splitk - 1) / splitk;
-    pl.splitk = (nk + kps - 1) / kps;
-    pl.ktiles_per_split = kps;
-    pl.ws_bytes = pl.splitk > 1 ? (size_t)pl.splitk * g.M * g.N * 4 : 0;
-    return true;
-  }
-  if (off && !g.plain) return false;              // (a pooled forward on bf16 inputs has no other kernel: ADVICE r4)
-  if (g.need_reduce) return false;                // the tiles below are never split: igemm_bf16's split-K stores the narrower rows
-  if (g.mode == MODE_BWD_F) {
-    // filter gradient: few tiles (M = r s Cin rows) over a long pixel axis — 256-row tiles, split-K until every CU has one block
-    static const bool off_f = tune_int("A3D_RING_BWDF", 1) == 0;
-    if (off_f || g.M < 512 || g.N < 64 || g.K < 64 * 64) return false;      // (short pixel axes stay with igemm_bf16's finer tiles)
-    int cfg = g.N <= 64 ? 1 : (g.N % 256 == 0 ? 2 : 0);
-    const int forced = tune_int("A3D_RING_CFG", -1);
-    if (forced >= 0 && forced <= 3) cfg = forced;
-    const int bm = kRingCfgs[cfg].bm, bn = kRingCfgs[cfg].bn;
-    pl.tiles_m = (g.M + bm - 1) / bm;
-    pl.tiles_n = (g.N + bn - 1) / bn;
-    const long tiles = (long)pl.tiles_m * pl.tiles_n;
-    const int nk = std::max(1, (g.K + 63) / 64);
-    int splitk = (int)std::min<long>(std::max<long>(256 / tiles, 1), std::max(1, nk / 8));
-    if (tune_int("A3D_FORCE_SPLITK", 0) > 0) splitk = std::min(tune_int("A3D_FORCE_SPLITK", 0), nk);
-    while (splitk > 1 && (size_t)splitk * g.M * g.N * 4 > kMaxSlabBytes) --splitk;
-    const int kps = (nk + splitk - 1) / splitk;
-    pl.ring = 1 + cfg;
-    pl.splitk = (nk + kps - 1) / kps;
-    pl.ktiles_per_split = kps;
-    pl.ws_bytes = pl.splitk > 1 ? (size_t)pl.splitk * g.M * g.N * 4 : 0;
-    return true;
-  }
-  int cfg;
-  if (g.mode == MODE_BWD_D && g.N <= 96 && g.N > 64) cfg = 4;
-  else if (g.N <= 64) cfg = (g.M + 511) / 512 >= 192 ? 5 : 1;      // 64 columns: 512-row tiles (wave tiles of 64 x 64) when they fill the chip
-  else if (g.N % 256 == 0 && (long)((g.M + 255) / 256) * (g.N / 256) >= 192) cfg = 2;
-  else cfg = (long)((g.M + 255) / 256) * ((g.N + 127) / 128) >= 192 ? 0 : 3;
-  const int forced = tune_int("A3D_RING_CFG", -1);
-  if (forced >= 0 && forced <= 6 && !(forced == 4 && g.mode != MODE_BWD_D) && !(forced == 6 && g.plain)) cfg = forced;
-  const int bm = kRingCfgs[cfg].bm, bn = kRingCfgs[cfg].bn;
-  const long tiles = (long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn);
-  if (tiles < 96 && forced < 0 && !g.plain) return false;      // (a pooled forward on bf16 inputs has no other kernel)
-  pl.ring = 1 + cfg;
-  pl.tiles_m = (g.M + bm - 1) / bm;
-  pl.tiles_n = (g.N + bn - 1) / bn;
-  pl.splitk = 1;
-  pl.ktiles_per_split = std::max(1, (g.K + 63) / 64);
-  pl.ws_bytes = 0;
-  return true;
+// The record of a launch that computes an m x n x k GEMM unsplit; callers overwrite what differs (splitk, flops).
+static a3d_timing_record timing_record(int mode, int prec, int bm, int bn, int waves_m, int nwaves, int bk, int avec, int bvec,
+                                       int lds_dma, int m, int n, int k) {
+  a3d_timing_record r{};
+  r.mode = mode; r.prec = prec; r.bm = bm; r.bn = bn; r.waves_m = waves_m; r.nwaves = nwaves; r.bk = bk;
+  r.avec = avec; r.bvec = bvec; r.lds_dma = lds_dma; r.splitk = 1; r.m = m; r.n = n; r.k = k; r.ms = 0.f;
+  r.flops = 2.0 * m * n * k;
+  return r;
 }
-
-static GemmPlan plan_gemm_bf16(const GemmProblem& g, int precision) {
-  GemmPlan pl{};
-  pl.prec = precision;
-  if (precision == A3D_PREC_BF16 && ring_plan(g, pl)) return pl;
-  pl.bf16_bn = g.N <= 64 ? 64 : 128;
-  if (tune_int("A3D_BF16_BN", 0) == 64 || tune_int("A3D_BF16_BN", 0) == 128) pl.bf16_bn = tune_int("A3D_BF16_BN", 0);
-  pl.tiles_m = (g.M + 127) / 128;
-  pl.tiles_n = (g.N + pl.bf16_bn - 1) / pl.bf16_bn;
-  const int bk = precision == A3D_PREC_BF16X3 ? 32 : 64;        // Bf16Cfg::BK: the plain bf16 kernel takes k-tiles of 64
-  const int nk = std::max(1, (g.K + bk - 1) / bk);
-  const long tiles = (long)pl.tiles_m * pl.tiles_n;
-  int splitk = (int)std::min<long>(std::max<long>(768 / tiles, 1), std::max(1, nk * (bk / 32) / 12));
-  if (precision == A3D_PREC_BF16) {
-    // Plain bf16 kernel, measured (profiles/r03_bf16_splitk_sweep.txt): one 128 x 128 block keeps a CU's staging path
-    // nearly as busy as two do (0.87 us per k-tile alone, 1.47 us each when two share the CU), so splitting K pays only
-    // until every CU has ONE block (two of the lighter 128 x 64 ones); past that it just adds a slab of the whole
-    // output per factor (conv2d_2 / conv2d_3 forward and bwd-data at batch 64: 351 tiles, 53 / 71 us unsplit against
-    // 72 / 85 us split in two).
-    const long target = pl.bf16_bn == 128 ? 256 : 512;
-    splitk = (int)std::min<long>(std::max<long>(target / tiles, 1), std::max(1, nk / 4));
-  }
-  if (tune_int("A3D_FORCE_SPLITK", 0) > 0) splitk = std::min(tune_int("A3D_FORCE_SPLITK", 0), std::max(1, nk));
-  if (g.need_reduce && nk >= 2) splitk = std::max(splitk, 2);
-  if (g.plain) splitk = 1;                      // fused pool: whole K ranges only
-  while (splitk > 1 && (size_t)splitk * g.M * g.N * 4 > kMaxSlabBytes) --splitk;
-  const int kps = (nk + splitk - 1) / splitk;
-  pl.splitk = (nk + kps - 1) / kps;
-  pl.ktiles_per_split = kps;
-  pl.ws_bytes = pl.splitk > 1 ? (size_t)pl.splitk * g.M * g.N * 4 : 0;
-  return pl;
-}
-
-static GemmPlan plan_gemm_search(const GemmProblem& g, int precision);
-
-// The search below walks 11 tile configurations x ~50 split factors: once per distinct problem, not once per launch
-// (a training step launches the same ~50 problems over and over).
-GemmPlan plan_gemm(const GemmProblem& g, int precision) {
-  if (tuning()) return plan_gemm_search(g, precision);
-  static std::mutex mu;
-  static std::map<std::array<int, 10>, GemmPlan> cache;
-  const std::array<int, 10> key = {g.mode, g.M, g.N, g.K, g.avec, g.bvec, g.plain + 2 * g.need_reduce, g.no_glds, precision, g.ring_ok};
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  const GemmPlan plan = plan_gemm_search(g, precision);
-  cache.emplace(key, plan);
-  return plan;
-}
-
-// Measured winners for shapes where the cost model below loses more than 3 % to a configuration of the sweep
-// (tools/sweep_hot.py --assert-auto-within 0.03; profiles/r03_sweep_hot.txt).  The model's block-slot count is that of
-// the 8-wave tiles (two per CU); 4-wave 64x64 blocks sit four to a CU and want several thousand blocks when a handful
-// of tiles carry a K of 10^5 — fine/second's bwd-filter: 64x64 x 128 splits 290 us, the model's pick 315-363 us.
-struct TunedPlan { int mode, M, N, K, cfg, splitk; };
-static const TunedPlan kTuned[] = {
-    {MODE_BWD_F, 1600, 64, 130240, 4, 128},        // fine/second/conv2d bwd-filter at batch 32
-};
-
-static GemmPlan plan_gemm_search(const GemmProblem& g, int precision) {
-  if (precision != A3D_PREC_F32 && g.avec == 4 && g.bvec == 4) return plan_gemm_bf16(g, precision);
-  if (tune_int("A3D_FORCE_CFG", -1) < 0 && !g.plain) {
-    for (const TunedPlan& t : kTuned) {
-      if (t.mode != g.mode || t.M != g.M || t.N != g.N || t.K != g.K) continue;
-      GemmPlan pl{};
-      const int nk = std::max(1, (g.K + 31) / 32), kps = (nk + t.splitk - 1) / t.splitk;
-      pl.cfg = t.cfg; pl.ktiles_per_split = kps; pl.splitk = (nk + kps - 1) / kps;
-      pl.tiles_m = (g.M + kCfgs[t.cfg].bm - 1) / kCfgs[t.cfg].bm; pl.tiles_n = (g.N + kCfgs[t.cfg].bn - 1) / kCfgs[t.cfg].bn;
-      pl.ws_bytes = pl.splitk > 1 ? (size_t)pl.splitk * g.M * g.N * 4 : 0;
-      if (pl.ws_bytes <= kMaxSlabBytes) return pl;
-    }
-  }
-  GemmPlan best{};
-  double best_t = 1e300;
-  const int nk = std::max(1, (g.K + 31) / 32);
-  const int force_cfg = tune_int("A3D_FORCE_CFG", -1), force_split = tune_int("A3D_FORCE_SPLITK", -1);
-  const int force_streamk = std::min(tune_int("A3D_FORCE_STREAMK", 0), 1024);      // tuning aid: stream-K with this many blocks (the fixup lists at most 1024 contributors per tile)
-  if (force_cfg >= 0 && force_cfg < kNumCfgs) {
-    // a pinned configuration still has to be one this problem can run on: the LDS-DMA kernels are forward-only, take
-    // 16-byte operands, and have neither the pooling epilogue nor a bf16 output — their register-staged twins do
-    int cfg = force_cfg;
-    if (is_glds_cfg(cfg) && (g.mode != MODE_FWD || g.avec != 4 || g.bvec != 4 || g.plain || g.no_glds)) cfg -= 2;
-    const int force_cfg = cfg;
-    const int bm = kCfgs[force_cfg].bm, bn = kCfgs[force_cfg].bn;
-    const int nk = std::max(1, (g.K + kCfgs[force_cfg].bk - 1) / kCfgs[force_cfg].bk);
-    int splitk = std::max(1, std::min(force_split > 0 ? force_split : 1, nk));
-    if (g.need_reduce && nk >= 2) splitk = std::max(splitk, 2);      // a narrower output is stored by the split-K reduction
-    if (g.plain) splitk = 1;                     // the fused pool takes whole K ranges
-    while (splitk > 1 && (size_t)splitk * g.M * g.N * 4 > kMaxSlabBytes) --splitk;
-    int kps = (nk + splitk - 1) / splitk;
-    splitk = (nk + kps - 1) / kps;
-    best.cfg = force_cfg; best.splitk = splitk; best.ktiles_per_split = kps;
-    best.tiles_m = (g.M + bm - 1) / bm; best.tiles_n = (g.N + bn - 1) / bn;
-    best.ws_bytes = splitk > 1 ? (size_t)splitk * g.M * g.N * 4 : 0;
-    if (force_streamk > 0 && streamk_cfg(force_cfg) && !g.plain && !g.need_reduce) {
-      best.splitk = 1; best.ktiles_per_split = nk; best.streamk = force_streamk;
-      best.ws_bytes = (size_t)2 * force_streamk * ((size_t)bm * bn + bn) * 4;
-    }
-    return best;
-  }
-  // Cost model calibrated on MI355X with tools/sweep_igemm.py (profiles/r01_sweep_igemm.txt): a block progresses at
-  // ~96.5 GMAC/s when two share a CU and ~1.6x that when alone; split-K costs one slab write+read at ~3 TB/s.
-  // Model picks are within 1.15x (mostly 1.05x) of the best measured configuration for every MSDN layer/direction.
-  for (int c = 0; c < kNumCfgs; ++c) {
-    if (kCfgs[c].eff <= 0.f) continue;
-    if (is_glds_cfg(c) && (g.mode != MODE_FWD || g.avec != 4 || g.bvec != 4 || g.plain || g.no_glds)) continue;
-    const int bm = kCfgs[c].bm, bn = kCfgs[c].bn;
-    const int tm = (g.M + bm - 1) / bm, tn = (g.N + bn - 1) / bn;
-    const long tiles = (long)tm * tn;
-    // split-K candidates: every small factor, coarser steps above, and the two factors that fill the chip's block
-    // slots exactly once or twice (tiles * splitk just below 512 / 1024: a kernel of 486 blocks beats one of 648)
-    int wants[48];
-    int nw = 0;
-    for (int w = 1; w <= 24; ++w) wants[nw++] = w;
-    for (int w = 32; w <= 256; w *= 2) { wants[nw++] = w; if (w < 256) wants[nw++] = w + w / 2; }
-    wants[nw++] = (int)std::max<long>(1, kSlots / tiles);
-    wants[nw++] = (int)std::max<long>(1, 2 * kSlots / tiles);
-    for (int wi = 0; wi < nw; ++wi) {
-      const int want = wants[wi];
-      if (want > 1 && g.plain) continue;
-      if (want == 1 && g.need_reduce && nk >= 2) continue;      // (nk == 1: launch_igemm refuses the call, nothing is enqueued)
-      if (want > 1 && want > nk / 2 && !(g.need_reduce && want == 2)) continue;
-      if (want > 1 && (size_t)want * g.M * g.N * 4 > kMaxSlabBytes) continue;
-      const int kps = (nk + want - 1) / want;
-      const int splitk = (nk + kps - 1) / kps;
-      const long blocks = tiles * splitk;
-      double t_b = (double)bm * bn * kps * 32.0 / (96.5e3 * kCfgs[c].eff);                // us
-      if (is_glds_cfg(c) && kps < 40) t_b *= 1.08;     // LDS-DMA pays off on long K ranges only (conv2d_2: 158 vs 146 us)
-      double f;      // kernel time in units of t_b: the slowest CU decides (tools/fit_planner.py)
-      if (blocks <= 256) f = 0.62;
-      else if (blocks <= kSlots) f = 1.0;
-      else f = std::max((double)blocks / kSlots + 0.08, 1.45);
-      double t = t_b * f;
-      if (splitk > 1) t += 2.5 + (double)g.M * g.N * 4.0 * (splitk + 1) / 3.0e6;
-      if (t < best_t) {
-        best_t = t;
-        best.cfg = c;
-        best.splitk = splitk;
-        best.ktiles_per_split = kps;
-        best.tiles_m = tm;
-        best.tiles_n = tn;
-        best.ws_bytes = splitk > 1 ? (size_t)splitk * g.M * g.N * 4 : 0;
-        best.streamk = 0;
-      }
-    }
-    // stream-K: equal shares of the (tile, k-tile) iterations for one or two blocks per CU — no tile quantisation, and
-    // at most two partial slabs per block (register-staged kernels only; the pooling forward never splits)
-    if (streamk_cfg(c) && !g.plain && !g.need_reduce && !env_flag_no_streamk()) {
-      const long iters = tiles * nk;
-      for (int G = 256; G <= 512; G += 256) {
-        if (force_streamk > 0 && G != 256) continue;
-        const int grid = force_streamk > 0 ? force_streamk : G;
-        if (iters < 4L * grid) continue;
-        const long per = (iters + grid - 1) / grid;
-        // blocks meeting in one tile: their slabs are added one after the other by the fixup, so few tiles with very
-        // long K (bwd-filter of the 3-channel layers, dense layers) stay with classic split-K and its flat reduction
-        const long meet = (nk + per - 1) / per + 1;
-        if (force_streamk <= 0 && (meet > 16 || tiles < 24)) continue;
-        double t = (double)bm * bn * per * 32.0 / (96.5e3 * kCfgs[c].eff) * (grid <= 256 ? 0.62 : 1.0);
-        // ~1.5 slabs per block are written and read back, then the split tiles are written once more
-        const double slabs = std::min<double>(1.5 * grid, 2.0 * tiles) * bm * bn * 4.0;
-        // (round 3 refit: 4.5 TB/s for the slab traffic — the fixup reads eight slabs deep; at 3 TB/s the model preferred
-        // split-K 2 for conv2d_1's bwd-data, measured 349 us against 334 for stream-K: profiles/r03_sweep_hot.txt)
-        t += 3.0 + 0.4 * meet + (2.0 * slabs + (double)std::min<long>(tiles, grid) * bm * bn * 4.0) / 4.5e6;
-        if (force_streamk > 0) t = 0;
-        if (t < best_t) {
-          best_t = t;
-          best.cfg = c;
-          best.splitk = 1;
-          best.ktiles_per_split = nk;
-          best.tiles_m = tm;
-          best.tiles_n = tn;
-          best.streamk = grid;
-          best.ws_bytes = (size_t)2 * grid * ((size_t)bm * bn + bn) * 4;
-        }
-      }
-    }
-  }
-  return best;
+// Runs launch() on `st`, between two events when the timing list wants launches like `rec`; returns launch()'s code.  If
+// the events cannot be had, that error is returned and launch() is not called: nothing is enqueued.
+template <typename Launch>
+static int timed_launch(const a3d_timing_record& rec, hipStream_t st, Launch&& launch) {
+  if (!timing_wanted(rec)) return launch();
+  TimingSlot slot{};
+  slot.rec = rec;
+  int rc = timing_begin(slot, st);
+  if (rc != A3D_OK) return rc;
+  rc = launch();
+  timing_end(slot, st);
+  return rc;
 }
 
 // Sums the split-K slabs in slab order (deterministic) and applies the epilogue.  Slab reads are issued four at a
@@ -499,8 +237,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_wide_kernel(const ReducePar
 int launch_splitk_reduce(const ReduceParams& r, hipStream_t st) {
   const size_t total = (size_t)r.M * r.N;
   clear_stale_error();
-  static const bool no_wide = tune_int("A3D_NO_WIDE_REDUCE", 0) != 0;      // A/B aid
-  if (!no_wide && r.vec4 && r.splitk >= 16 && total / 4 <= (size_t)1 << 16) {
+  if (r.vec4 && r.splitk >= 16 && total / 4 <= (size_t)1 << 16) {
     const unsigned blocks_c = (unsigned)((total / 4 + 15) / 16), blocks_b = r.dbias_out ? (unsigned)((r.N + 15) / 16) : 0u;
     hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3(blocks_c + blocks_b), dim3(256), 0, st, r, blocks_c);
     return check_launch("splitk_reduce_wide");
@@ -551,23 +288,18 @@ int launch_igemm(int mode, const GemmPlan& plan, int avec, int bvec, IgemmParams
     fprintf(stderr, "a3d plan: mode %d M %d N %d K %d -> %s %d (%dx%d) splitk %d streamk %d grid %u\n", mode, p.M, p.N, p.K,
             plan.ring ? "ring" : "cfg", plan.ring ? plan.ring - 1 : plan.cfg, plan.ring ? kRingCfgs[plan.ring - 1].bm : kCfgs[plan.cfg].bm,
             plan.ring ? kRingCfgs[plan.ring - 1].bn : kCfgs[plan.cfg].bn, plan.splitk, plan.streamk, grid);
-  TimingSlot slot{};
-  {
-    a3d_timing_record& r = slot.rec;
-    r.mode = mode; r.prec = plan.prec;
-    if (plan.ring) {
-      r.bm = kRingCfgs[plan.ring - 1].bm; r.bn = kRingCfgs[plan.ring - 1].bn; r.waves_m = 0; r.nwaves = 8; r.bk = 64;
-      r.lds_dma = 3;                                        // 3: igemm_ring_kernel
-    } else if (plan.prec != A3D_PREC_F32) {
-      r.bm = 128; r.bn = plan.bf16_bn; r.waves_m = 4; r.nwaves = 8; r.bk = plan.prec == A3D_PREC_BF16X3 ? 32 : 64;
-    } else {
-      r.bm = kCfgs[plan.cfg].bm; r.bn = kCfgs[plan.cfg].bn; r.waves_m = kCfgWavesM[plan.cfg];
-      r.nwaves = kCfgNWaves[plan.cfg]; r.bk = kCfgs[plan.cfg].bk;
-      r.lds_dma = plan.cfg >= kFirstGldsCfg && avec == 4 && bvec == 4;
-    }
-    r.avec = avec; r.bvec = bvec; r.splitk = plan.splitk; r.m = p.M; r.n = p.N; r.k = p.K; r.ms = 0.f;
-    r.flops = 2.0 * p.M * p.N * p.K;
+  a3d_timing_record rec;
+  if (plan.ring) {                                          // lds_dma 3: igemm_ring_kernel
+    const RingTile& t = kRingCfgs[plan.ring - 1];
+    rec = timing_record(mode, plan.prec, t.bm, t.bn, 0, 8, 64, avec, bvec, 3, p.M, p.N, p.K);
+  } else if (plan.prec != A3D_PREC_F32) {
+    rec = timing_record(mode, plan.prec, 128, plan.bf16_bn, 4, 8, plan.prec == A3D_PREC_BF16X3 ? 32 : 64, avec, bvec, 0, p.M, p.N, p.K);
+  } else {
+    const TileCfg& t = kCfgs[plan.cfg];
+    rec = timing_record(mode, plan.prec, t.bm, t.bn, t.waves_m, t.nwaves, t.bk, avec, bvec,
+                        is_glds_cfg(plan.cfg) && avec == 4 && bvec == 4, p.M, p.N, p.K);
   }
+  rec.splitk = plan.splitk;
   // a second output / a narrower output are written by the reduction stage of a classic split-K forward or bwd-data launch
   // (or, the second output, by a copy launch behind an unsplit one): refuse the other combinations BEFORE anything is
   // enqueued — a GEMM that has already stored N columns into rows of c_cols floats cannot be taken back
@@ -575,19 +307,18 @@ int launch_igemm(int mode, const GemmPlan& plan, int avec, int bvec, IgemmParams
   if (plan.streamk > 0) {
     A3D_CHECK_ARG(!p.out2 && !p.c_cols, "second output: not on stream-K launches");
   } else if (plan.splitk > 1) {
-    if (reduce_vec4 || mode == MODE_BWD_F) A3D_CHECK_ARG(!p.out2 && !p.c_cols, "a second output belongs to a forward or bwd-data launch");
+    if (mode == MODE_BWD_F) A3D_CHECK_ARG(!p.out2 && !p.c_cols, "a second output belongs to a forward or bwd-data launch");
   } else {
     A3D_CHECK_ARG(!p.c_cols || p.c_cols == p.N, "this launch has no reduction stage: the output cannot be narrower than the GEMM");
     A3D_CHECK_ARG(!p.out2 || (p.sub_step == 1 && !p.pool), "second output: plain forward / bwd-data launches only");
   }
-  const bool timed = timing_wanted(slot.rec);
-  if (timed && (rc = timing_begin(slot, st)) != A3D_OK) return rc;
-  if (plan.ring) rc = launch_igemm_ring(mode, plan.ring - 1, p, grid, st);
-  else if (plan.prec != A3D_PREC_F32) rc = launch_igemm_bf16(mode, plan.bf16_bn, plan.prec == A3D_PREC_BF16X3, p, grid, st);
-  else if (mode == MODE_FWD) rc = launch_igemm_mode0(plan.cfg, avec, bvec, p, grid, st);
-  else if (mode == MODE_BWD_D) rc = launch_igemm_mode1(plan.cfg, avec, bvec, p, grid, st);
-  else rc = launch_igemm_mode2(plan.cfg, avec, bvec, p, grid, st);
-  if (timed) timing_end(slot, st);
+  rc = timed_launch(rec, st, [&] {
+    if (plan.ring) return launch_igemm_ring(mode, plan.ring - 1, p, grid, st);
+    if (plan.prec != A3D_PREC_F32) return launch_igemm_bf16(mode, plan.bf16_bn, plan.prec == A3D_PREC_BF16X3, p, grid, st);
+    if (mode == MODE_FWD) return launch_igemm_mode0(plan.cfg, avec, bvec, p, grid, st);
+    if (mode == MODE_BWD_D) return launch_igemm_mode1(plan.cfg, avec, bvec, p, grid, st);
+    return launch_igemm_mode2(plan.cfg, avec, bvec, p, grid, st);
+  });
   if (rc != A3D_OK) return rc;
   if (plan.streamk > 0) {
     const unsigned tiles = (unsigned)(plan.tiles_m * plan.tiles_n);
@@ -652,14 +383,12 @@ struct RunForm {
 // gradient, which is never stored (past the tensor's end the descriptor returns zeros).
 static bool run_form_ok(const a3d_conv_desc* d, const float* x, RunForm* rf, bool bwd_filter = false) {
   if (d->pad_t || d->pad_l || d->ldx != d->c || d->c % 4 == 0 || d->c > 4) return false;
-  if (tune_int("A3D_NO_RUNFORM", 0)) return false;
   const int step = d->stride * d->c, row = d->w * d->c;
   int vec = 0;
   bool anywhere = false;
   if (step % 4 == 0 && row % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) vec = 4;
   else if (step % 2 == 0 && row % 2 == 0 && (reinterpret_cast<uintptr_t>(x) & 7) == 0) vec = 2;
-  else if (bwd_filter && d->precision == A3D_PREC_F32 && !d->storage && (reinterpret_cast<uintptr_t>(x) & 3) == 0 &&
-           !tune_int("A3D_NO_RUNFORM_ANYWHERE", 0)) {
+  else if (bwd_filter && d->precision == A3D_PREC_F32 && !d->storage && (reinterpret_cast<uintptr_t>(x) & 3) == 0) {
     vec = 2;
     anywhere = true;
   }
@@ -728,11 +457,6 @@ static int check_desc(const a3d_conv_desc* d) {
   return A3D_OK;
 }
 
-
-struct ConvProblem {
-  GemmProblem g;
-};
-
 static GemmProblem fwd_problem(const a3d_conv_desc* d) {
   GemmProblem g;
   g.mode = MODE_FWD;
@@ -760,7 +484,7 @@ static GemmProblem bwd_f_problem(const a3d_conv_desc* d) {
 
 // a3d_conv_desc.storage -> which GEMM operands are bf16, with the checks a 16-byte bf16 gather needs
 static int apply_storage(IgemmParams& p, GemmProblem& g, int precision, bool a16, bool b16, bool c16, int a_c, int a_ld,
-                         int b_c, int b_ld, const void* a, const void* b, const void* c, int c_c, int c_ld) {
+                         int b_c, int b_ld, const void* a, const void* b, const void* c) {
   if (!a16 && !b16 && !c16) return A3D_OK;
   // a bf16 OUTPUT alone is also served by the fp32 kernels (the 3-channel layers of config 5 keep fp32 arithmetic)
   A3D_CHECK_ARG(precision == A3D_PREC_BF16 || (precision == A3D_PREC_F32 && !a16 && !b16),
@@ -769,7 +493,6 @@ static int apply_storage(IgemmParams& p, GemmProblem& g, int precision, bool a16
   // b_c < 0: a row-major [rows][b_ld] operand read in whole 16-byte chunks (its pad columns must be readable zeros)
   A3D_CHECK_ARG(!b16 || ((b_c < 0 || b_c % 8 == 0) && b_ld % 8 == 0 && aligned16(b)), "bf16 operand: channels / stride must be multiples of 8, base 16-byte aligned");
   A3D_CHECK_ARG(!c16 || aligned16(c), "bf16 output: base must be 16-byte aligned");
-  (void)c_c; (void)c_ld;
   p.a16 = a16; p.b16 = b16; p.c16 = c16;
   if (c16) g.no_glds = 1;
   if (a16) g.avec = 4;
@@ -777,7 +500,6 @@ static int apply_storage(IgemmParams& p, GemmProblem& g, int precision, bool a16
   return A3D_OK;
 }
 
-static int take_second_output(IgemmParams& p, const a3d_second_output* o);
 static void fill_common(IgemmParams& p, const GemmProblem& g) {
   p = IgemmParams{};
   p.M = g.M; p.N = g.N; p.K = g.K;
@@ -790,20 +512,38 @@ static void fill_common(IgemmParams& p, const GemmProblem& g) {
 // buffer descriptors, the wave-uniform tap decode for layers whose gathered channel count is a multiple of BK = 32, and
 // whether the gather can leave the image at all.
 static void fill_staging(IgemmParams& p, int mode, unsigned long long a_elems, unsigned long long b_elems, int taps_r,
-                         int taps_s, int filt_r, int filt_s) {
+                         int taps_s) {
   p.a_elems = a_elems;
   p.b_elems = b_elems;
   p.ntaps = std::max(1, taps_r * taps_s);
   p.cpt = std::max(1, p.Cg / 32);
-  p.uni = (mode != MODE_BWD_F) && p.Cg % 32 == 0 && p.K == p.ntaps * p.Cg && !env_flag_no_uni();
-  p.kperm = p.uni && p.ntaps > 1 && p.cpt > 1 && !env_flag_no_kperm();
+  p.uni = (mode != MODE_BWD_F) && p.Cg % 32 == 0 && p.K == p.ntaps * p.Cg;
+  p.kperm = p.uni && p.ntaps > 1 && p.cpt > 1;
   p.div_cpt = make_fastdiv(p.cpt);
   p.div_taps = make_fastdiv(p.ntaps);
   p.cpt64 = std::max(1, p.Cg / 64);
   p.uni64 = p.uni && p.Cg % 64 == 0;
-  p.kperm64 = p.uni64 && p.ntaps > 1 && p.cpt64 > 1 && !env_flag_no_kperm();
+  p.kperm64 = p.uni64 && p.ntaps > 1 && p.cpt64 > 1;
   p.div_cpt64 = make_fastdiv(p.cpt64);
-  (void)filt_r; (void)filt_s;
+}
+
+// The gather's geometry for a launch that reads d's input image (pixel stride `ld`) through d's windows: filter rows of S
+// taps over Cg gathered channels, the GEMM's pixel axis decoded over d's output grid.
+static void fill_gather(IgemmParams& p, const a3d_conv_desc* d, int ld, int S, int Cg) {
+  p.H = d->h; p.W = d->w; p.ld = ld; p.pHW = d->h * d->w;
+  p.stride = d->stride; p.lstride = ilog2_exact(d->stride); p.pad_t = d->pad_t; p.pad_l = d->pad_l;
+  p.S = S; p.Cg = Cg;
+  p.div_phw = make_fastdiv(d->ho * d->wo); p.div_pw = make_fastdiv(d->wo);
+  p.div_c = make_fastdiv(Cg); p.div_s = make_fastdiv(S);
+  p.div_c_half = make_fastdiv(std::max(1, Cg / 2));
+}
+// ... with the 2x2 max pool in the epilogue: the pixel axis runs over pool windows of four, the output is the pooled map
+static void fill_pool(IgemmParams& p, const a3d_conv_desc* d, uint8_t* argmax, int ld_out) {
+  const int ph = d->ho / 2, pw = d->wo / 2;
+  p.pool = 1;
+  p.argmax = argmax;
+  p.div_phw = make_fastdiv(ph * pw * 4); p.div_pw = make_fastdiv(pw);
+  p.ldc = ld_out;
 }
 
 }  // namespace a3d
@@ -918,9 +658,8 @@ static int conv_fwd_bf16_image(const a3d_conv_desc* d, const float* x, const flo
   const int rlp = (d->s * 2 + 3) / 4 * 4 * 2, np = (d->k + 7) / 8 * 8;      // bf16 elements
   GemmProblem g = fwd_problem(d);
   g.K = d->r * rlp; g.avec = 4; g.bvec = 4; g.no_glds = 1;
-  const int ph = d->ho / 2, pw = d->wo / 2;
   if (pool) {
-    g.M = d->n * ph * pw * 4;
+    g.M = d->n * (d->ho / 2) * (d->wo / 2) * 4;
     g.plain = 1;
   }
   const bool prepared = (d->hints & A3D_HINT_W_PREPARED) != 0;      // w is already the padded bf16 filter (a3d_conv2d_fwd_prepare_filter)
@@ -942,20 +681,10 @@ static int conv_fwd_bf16_image(const a3d_conv_desc* d, const float* x, const flo
   p.a16 = 1; p.b16 = 1; p.c16 = (d->storage & A3D_STORE_Y_BF16) ? 1 : 0;
   p.A = x; p.B = reinterpret_cast<const float*>(wp); p.C = y; p.bias = bias; p.act = act;
   p.npix = g.M; p.nrsc = g.K;
-  p.H = d->h; p.W = d->w; p.ld = 4; p.pHW = d->h * d->w;
-  p.stride = d->stride; p.lstride = ilog2_exact(d->stride); p.pad_t = 0; p.pad_l = 0;
-  p.S = 1; p.Cg = rlp;
-  p.div_phw = make_fastdiv(d->ho * d->wo); p.div_pw = make_fastdiv(d->wo);
-  p.div_c = make_fastdiv(p.Cg); p.div_s = make_fastdiv(1);
-  p.div_c_half = make_fastdiv(p.Cg / 2);
+  fill_gather(p, d, d->ldx, 1, rlp);            // (bf16_image_form_ok: ldx = 4, no padding)
   p.ldb = np; p.ldc = d->ldy;
-  if (pool) {
-    p.pool = 1;
-    p.argmax = argmax;
-    p.div_phw = make_fastdiv(ph * pw * 4); p.div_pw = make_fastdiv(pw);
-    p.ldc = ld_out;
-  }
-  fill_staging(p, MODE_FWD, (unsigned long long)d->n * d->h * d->w * 4, (unsigned long long)g.K * np, d->r, 1, d->r, 1);
+  if (pool) fill_pool(p, d, argmax, ld_out);
+  fill_staging(p, MODE_FWD, (unsigned long long)d->n * d->h * d->w * 4, (unsigned long long)g.K * np, d->r, 1);
   return launch_igemm(MODE_FWD, plan, 4, 4, p, static_cast<char*>(ws) + ws_used, st);
 }
 
@@ -983,48 +712,27 @@ static int conv_fwd_impl(const a3d_conv_desc* d, const float* x, const float* w,
     return stencil1_fwd(d, x, w, bias, y, act, static_cast<hipStream_t>(stream));
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const int m_out = pool ? d->n * (d->ho / 2) * (d->wo / 2) * 4 : d->n * d->ho * d->wo;      // GEMM rows: pixels, or pool windows x 4
+  const bool prepared = (d->hints & A3D_HINT_W_PREPARED) != 0;
   if (bf16_image_form_ok(d, x)) {
     if (!conv3b_applicable(d)) return conv_fwd_bf16_image(d, x, w, bias, y, act, pool, ld_out, argmax, ws, ws_bytes, st);
-    TimingSlot slot{};                          // straight from L2 on the bf16 matrix cores (conv3.hip, conv3b_fwd_kernel)
-    {
-      a3d_timing_record& r = slot.rec;
-      r.mode = MODE_FWD; r.prec = A3D_PREC_BF16; r.bm = 64; r.bn = d->k > 64 ? 96 : 64; r.waves_m = 1; r.nwaves = 1; r.bk = 16;
-      r.avec = 4; r.bvec = 4; r.splitk = 1; r.lds_dma = 2;
-      r.m = pool ? d->n * (d->ho / 2) * (d->wo / 2) * 4 : d->n * d->ho * d->wo; r.n = d->k; r.k = d->r * d->s * 3; r.ms = 0.f;
-      r.flops = 2.0 * r.m * r.n * r.k;          // (algorithmic: the image's three real channels)
-    }
-    const bool timed = timing_wanted(slot.rec);
-    if (timed && (rc = timing_begin(slot, st)) != A3D_OK) return rc;
-    rc = conv3b_fwd(d, x, w, bias, y, act, pool, ld_out, argmax, ws, ws_bytes, st, (d->hints & A3D_HINT_W_PREPARED) != 0);
-    if (timed) timing_end(slot, st);
-    return rc;
+    // straight from L2 on the bf16 matrix cores (conv3.hip, conv3b_fwd_kernel); k, flops: algorithmic, the image's three real channels
+    return timed_launch(timing_record(MODE_FWD, A3D_PREC_BF16, 64, d->k > 64 ? 96 : 64, 1, 1, 16, 4, 4, 2, m_out, d->k, d->r * d->s * 3), st,
+                        [&] { return conv3b_fwd(d, x, w, bias, y, act, pool, ld_out, argmax, ws, ws_bytes, st, prepared); });
   }
-  if (conv3_applicable(d, x)) {                  // few-channel layers: operands straight from L2 (conv3.hip)
-    TimingSlot slot{};
-    {
-      a3d_timing_record& r = slot.rec;
-      r.mode = MODE_FWD; r.prec = A3D_PREC_F32; r.bm = 64; r.bn = d->k > 64 ? 96 : 64; r.waves_m = 1; r.nwaves = 1; r.bk = 8;
-      r.avec = 4; r.bvec = 4; r.splitk = 1; r.lds_dma = 2;          // 2: conv3_fwd_kernel (filter repack included in ms)
-      r.m = pool ? d->n * (d->ho / 2) * (d->wo / 2) * 4 : d->n * d->ho * d->wo; r.n = d->k; r.k = d->r * d->s * d->c; r.ms = 0.f;
-      r.flops = 2.0 * r.m * r.n * r.k;
-    }
-    const bool timed = timing_wanted(slot.rec);
-    if (timed && (rc = timing_begin(slot, st)) != A3D_OK) return rc;
-    rc = conv3_fwd(d, x, w, bias, y, act, pool, ld_out, argmax, ws, ws_bytes, st, (d->hints & A3D_HINT_W_PREPARED) != 0);
-    if (timed) timing_end(slot, st);
-    return rc;
-  }
+  if (conv3_applicable(d, x))                    // few-channel layers: operands straight from L2 (conv3.hip)
+    // lds_dma 2: conv3_fwd_kernel (filter repack included in ms)
+    return timed_launch(timing_record(MODE_FWD, A3D_PREC_F32, 64, d->k > 64 ? 96 : 64, 1, 1, 8, 4, 4, 2, m_out, d->k, d->r * d->s * d->c), st,
+                        [&] { return conv3_fwd(d, x, w, bias, y, act, pool, ld_out, argmax, ws, ws_bytes, st, prepared); });
   GemmProblem g = fwd_problem(d);
-  const int ph = d->ho / 2, pw = d->wo / 2;
   if (pool) {
-    g.M = d->n * ph * pw * 4;
+    g.M = m_out;
     g.plain = 1;
   }
   if (!aligned16(x)) g.avec = 1;
   if (!aligned16(w)) g.bvec = 1;
   if (d->hints & A3D_HINT_SHARE_CU) g.no_glds = 1;      // the register-staged kernels take the hint (launch_one)
   RunForm rf{};
-  const bool prepared = (d->hints & A3D_HINT_W_PREPARED) != 0;
   const bool run = run_form_ok(d, x, &rf) && (prepared || (ws && ws_bytes >= run_filter_bytes(d, rf)));
   // (the prepared layout was chosen for a 16-byte aligned x — fwd_filter_form — and this launch reads it with THAT row padding)
   A3D_CHECK_ARG(!prepared || (run && aligned16(w) && aligned16(x)),
@@ -1056,11 +764,9 @@ static int conv_fwd_impl(const a3d_conv_desc* d, const float* x, const float* w,
     A3D_CHECK_ARG(!sb || ((!pool || sb == A3D_STORE_Y_BF16 || (sb == all16 && d->precision == A3D_PREC_BF16)) &&
                           !(run && (sb & A3D_STORE_W_BF16))),
                   "conv2d_fwd: the fused pool takes float32 inputs (its output may be bf16) or bf16 x, w and y; 3-channel filters stay float32");
-    const IgemmParams keep = p;
     rc = apply_storage(p, g, d->precision, sb & A3D_STORE_X_BF16, sb & A3D_STORE_W_BF16, sb & A3D_STORE_Y_BF16, d->c,
-                       d->ldx, d->k, d->k, x, w, y, d->k, d->ldy);
+                       d->ldx, d->k, d->k, x, w, y);
     if (rc != A3D_OK) return rc;
-    (void)keep;
     // both operands bf16 tensors, whole 16-byte pieces inside one tap: the LDS-DMA kernel may take the launch
     // (pooled: the pooled map's pixel stride and the argmax rows in whole 16-byte pieces too)
     g.ring_ok = p.a16 && p.b16 && !run && d->precision == A3D_PREC_BF16 && d->c % 8 == 0 && d->ldx % 8 == 0 &&
@@ -1073,29 +779,14 @@ static int conv_fwd_impl(const a3d_conv_desc* d, const float* x, const float* w,
   if (ws_used + plan.ws_bytes > ws_bytes)
     return set_error(A3D_EWORKSPACE, "conv2d_fwd: need %zu workspace bytes", ws_used + plan.ws_bytes);
   A3D_CHECK_ARG(!(p.a16 || p.b16) || plan.prec == A3D_PREC_BF16, "conv2d_fwd: bf16 operands need vectorisable tensors");
-  A3D_CHECK_ARG(!p.c16 || plan.prec == A3D_PREC_BF16 || plan.cfg < kFirstGldsCfg, "conv2d_fwd: no bf16 output from the LDS-DMA kernels");
+  A3D_CHECK_ARG(!p.c16 || plan.prec == A3D_PREC_BF16 || !is_glds_cfg(plan.cfg), "conv2d_fwd: no bf16 output from the LDS-DMA kernels");
   p.A = x; p.B = filter; p.C = y; p.bias = bias; p.act = act;
   p.share = (d->hints & A3D_HINT_SHARE_CU) ? 1 : 0;
   p.npix = g.M; p.nrsc = g.K;
-  p.H = d->h; p.W = d->w; p.ld = d->ldx; p.pHW = d->h * d->w;
-  p.stride = d->stride; p.lstride = ilog2_exact(d->stride); p.pad_t = d->pad_t; p.pad_l = d->pad_l;
-  p.S = run ? 1 : d->s; p.Cg = run ? rf.rlp : d->c;
-  p.div_phw = make_fastdiv(d->ho * d->wo); p.div_pw = make_fastdiv(d->wo);
-  p.div_c = make_fastdiv(p.Cg); p.div_s = make_fastdiv(p.S);
-  p.div_c_half = make_fastdiv(std::max(1, p.Cg / 2));
-  p.ldb = run ? run_ldb : d->k; p.ldc = d->ldy;
-  if (pool) {
-    p.pool = 1;
-    p.argmax = argmax;
-    p.div_phw = make_fastdiv(ph * pw * 4); p.div_pw = make_fastdiv(pw);
-    p.ldc = ld_out;
-  }
-  {
-    // nocheck needs the LAST window inside the image: rows (ho-1)*stride + r - 1 < h; columns: the last gathered float
-    const bool inside = (d->ho - 1) * d->stride + d->r <= d->h && (d->wo - 1) * d->stride + d->s <= d->w;
-    fill_staging(p, MODE_FWD, (unsigned long long)d->n * d->h * d->w * d->ldx, (unsigned long long)g.K * (run ? run_ldb : d->k),
-                 run ? d->r : d->r, run ? 1 : d->s, inside ? d->r : 0, inside ? d->s : 0);
-  }
+  fill_gather(p, d, d->ldx, run ? 1 : d->s, run ? rf.rlp : d->c);
+  p.ldb = run_ldb; p.ldc = d->ldy;
+  if (pool) fill_pool(p, d, argmax, ld_out);
+  fill_staging(p, MODE_FWD, (unsigned long long)d->n * d->h * d->w * d->ldx, (unsigned long long)g.K * run_ldb, d->r, run ? 1 : d->s);
   rc = take_second_output(p, out2);
   if (rc != A3D_OK) return rc;
   return launch_igemm(MODE_FWD, plan, g.avec, g.bvec, p, static_cast<char*>(ws) + ws_used, st);
@@ -1212,12 +903,11 @@ int a3d_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w,
   unsigned multi_grid = 0;
   long multi_tiles = 0;
   double multi_flops = 0;
-  const bool try_multi = d->stride == 2 && d->precision == A3D_PREC_F32 && !d->storage && !tune_int("A3D_NO_MULTI", 0) &&
-                         tune_int("A3D_FORCE_CFG", -1) < 0;
+  const bool try_multi = d->stride == 2 && d->precision == A3D_PREC_F32 && !d->storage && tune_int("A3D_FORCE_CFG", -1) < 0;
   // ... and on bf16-stored tensors (BASELINE config 5's conv2d_4): one launch of the bf16 kernel's 128-row tiles
   const int all16 = A3D_STORE_X_BF16 | A3D_STORE_W_BF16 | A3D_STORE_Y_BF16;
   const bool try_multi16 = d->stride == 2 && d->precision == A3D_PREC_BF16 && (d->storage & all16) == all16 && vec_ok_a &&
-                           vec_ok_b && !tune_int("A3D_NO_MULTI", 0) && tune_int("A3D_FORCE_SPLITK", 0) <= 0;
+                           vec_ok_b && tune_int("A3D_FORCE_SPLITK", 0) <= 0;
   int multi16_bn = 0;
   for (int ph = 0; ph < d->stride; ++ph) {
     for (int pw = 0; pw < d->stride; ++pw) {
@@ -1229,7 +919,7 @@ int a3d_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w,
       IgemmParams p;
       fill_common(p, g);
       rc = apply_storage(p, g, d->precision, d->storage & A3D_STORE_Y_BF16, d->storage & A3D_STORE_W_BF16,
-                         d->storage & A3D_STORE_X_BF16, d->k, d->ldy, d->k, d->k, dz, w, dx, d->c, d->ldx);
+                         d->storage & A3D_STORE_X_BF16, d->k, d->ldy, d->k, d->k, dz, w, dx);
       if (rc != A3D_OK) return rc;
       A3D_CHECK_ARG(!p.c16 || !relu_mask || aligned16(relu_mask), "conv2d_bwd_data: bf16 mask must be 16-byte aligned");
       g.ring_ok = d->stride == 1 && p.a16 && p.b16 && d->precision == A3D_PREC_BF16 && d->k % 8 == 0 && d->ldy % 8 == 0 &&
@@ -1261,7 +951,7 @@ int a3d_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w,
       p.sub_step = d->stride; p.sub_ph = ph; p.sub_pw = pw; p.tap_r0 = c.r0; p.tap_s0 = c.s0; p.S_full = d->s;
       p.outW = d->w; p.outHW = d->h * d->w;
       fill_staging(p, MODE_BWD_D, (unsigned long long)d->n * d->ho * d->wo * d->ldy,
-                   (unsigned long long)d->r * d->s * d->c * d->k, c.rp, c.sp, 0, 0);
+                   (unsigned long long)d->r * d->s * d->c * d->k, c.rp, c.sp);
       if (try_multi || multi16) {
         p.splitk = 1; p.ktiles_per_split = plan.ktiles_per_split; p.tiles_m = plan.tiles_m; p.tiles_n = plan.tiles_n;
         p.slab = (size_t)p.M * p.N;
@@ -1277,19 +967,10 @@ int a3d_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w,
     }
   }
   if (try_multi16 && n_multi > 0) {
-    TimingSlot slot{};
-    {
-      a3d_timing_record& r = slot.rec;
-      r.mode = MODE_BWD_D; r.prec = A3D_PREC_BF16; r.bm = 128; r.bn = multi16_bn; r.waves_m = 4; r.nwaves = 8; r.bk = 64;
-      r.avec = 4; r.bvec = 4; r.splitk = 1; r.lds_dma = 0;
-      r.m = d->n * d->h * d->w; r.n = d->c; r.k = d->r * d->s * d->k; r.ms = 0.f;
-      r.flops = multi_flops;
-    }
-    const bool timed = timing_wanted(slot.rec);
-    if (timed && (rc = timing_begin(slot, st)) != A3D_OK) return rc;
-    rc = launch_igemm_bf16_multi_bwd_d(multi16_bn, multi, multi_grid, (unsigned)n_multi, st);
-    if (timed) timing_end(slot, st);
-    return rc;
+    a3d_timing_record rec = timing_record(MODE_BWD_D, A3D_PREC_BF16, 128, multi16_bn, 4, 8, 64, 4, 4, 0, d->n * d->h * d->w, d->c,
+                                          d->r * d->s * d->k);
+    rec.flops = multi_flops;                 // the classes' own, summed: a class runs only the taps that reach it
+    return timed_launch(rec, st, [&] { return launch_igemm_bf16_multi_bwd_d(multi16_bn, multi, multi_grid, (unsigned)n_multi, st); });
   }
   if (try_multi && n_multi > 0) {
     if (multi_tiles < 256) {                 // too little work for 64x64 tiles without split-K: one launch per class
@@ -1305,19 +986,10 @@ int a3d_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w,
       }
       return A3D_OK;
     }
-    TimingSlot slot{};
-    {
-      a3d_timing_record& r = slot.rec;
-      r.mode = MODE_BWD_D; r.prec = A3D_PREC_F32; r.bm = 64; r.bn = 64; r.waves_m = 2; r.nwaves = 4; r.bk = 32;
-      r.avec = multi_avec; r.bvec = multi_bvec; r.splitk = 1; r.lds_dma = 0;
-      r.m = d->n * d->h * d->w; r.n = d->c; r.k = d->r * d->s * d->k; r.ms = 0.f;
-      r.flops = multi_flops;
-    }
-    const bool timed = timing_wanted(slot.rec);
-    if (timed && (rc = timing_begin(slot, st)) != A3D_OK) return rc;
-    rc = launch_igemm_multi_bwd_d(multi_avec, multi_bvec, multi, multi_grid, (unsigned)n_multi, st);
-    if (timed) timing_end(slot, st);
-    return rc;
+    a3d_timing_record rec = timing_record(MODE_BWD_D, A3D_PREC_F32, 64, 64, 2, 4, 32, multi_avec, multi_bvec, 0, d->n * d->h * d->w,
+                                          d->c, d->r * d->s * d->k);
+    rec.flops = multi_flops;
+    return timed_launch(rec, st, [&] { return launch_igemm_multi_bwd_d(multi_avec, multi_bvec, multi, multi_grid, (unsigned)n_multi, st); });
   }
   return A3D_OK;
 }
@@ -1363,20 +1035,9 @@ static bool fewch_wanted(const a3d_conv_desc* d, bool pooled) {
 // the launch as the timing list sees it (a3d_timing_*): lds_dma 4 = fewch_bwdf_kernel, ms includes the slab reduction
 static int fewch_timed(const a3d_conv_desc* d, const float* x, int src, const void* dz, int ldz, const void* pooled_act,
                        const uint8_t* argmax, int ld_arg, float* dw, float* db, void* ws, hipStream_t st) {
-  TimingSlot slot{};
-  {
-    a3d_timing_record& r = slot.rec;
-    r.mode = MODE_BWD_F; r.prec = A3D_PREC_F32; r.bm = 128; r.bn = (d->k + 31) / 32 * 32; r.waves_m = 4; r.nwaves = 4; r.bk = 2;
-    r.avec = 1; r.bvec = 1; r.splitk = 1; r.lds_dma = 4;
-    r.m = d->r * d->s * d->c; r.n = d->k; r.k = d->n * d->ho * d->wo; r.ms = 0.f;
-    r.flops = 2.0 * r.m * r.n * r.k;
-  }
-  const bool timed = timing_wanted(slot.rec);
-  int rc;
-  if (timed && (rc = timing_begin(slot, st)) != A3D_OK) return rc;
-  rc = fewch_bwd_filter(d, x, src, dz, ldz, pooled_act, argmax, ld_arg, dw, db, ws, st);
-  if (timed) timing_end(slot, st);
-  return rc;
+  return timed_launch(timing_record(MODE_BWD_F, A3D_PREC_F32, 128, (d->k + 31) / 32 * 32, 4, 4, 2, 1, 1, 4, d->r * d->s * d->c, d->k,
+                                    d->n * d->ho * d->wo),
+                      st, [&] { return fewch_bwd_filter(d, x, src, dz, ldz, pooled_act, argmax, ld_arg, dw, db, ws, st); });
 }
 
 // config 5: bf16 arithmetic on the fp32 image and bf16 pooled tensors (fewch16.hip); A3D_FEWCH16=0 (tuning processes): refused
@@ -1404,20 +1065,10 @@ int a3d_conv2d_bwd_filter_pooled(const a3d_conv_desc* d, const float* x, const v
                   "conv2d_bwd_filter_pooled: bf16 arithmetic takes bf16 pooled tensors in whole aligned 4-channel groups");
     A3D_CHECK_ARG(fewch_extents_ok(d, true, ld_dpool, 2, ld_argmax), "conv2d_bwd_filter_pooled: pooled tensors of 2 GiB or more");
     if (fewch16_bwdf_ws_bytes(d, true) > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd_filter_pooled: workspace too small");
-    TimingSlot slot{};
-    {
-      a3d_timing_record& r = slot.rec;
-      r.mode = MODE_BWD_F; r.prec = A3D_PREC_BF16; r.bm = 128; r.bn = (d->k + 31) / 32 * 32; r.waves_m = 4; r.nwaves = 4; r.bk = 16;
-      r.avec = 1; r.bvec = 1; r.splitk = 1; r.lds_dma = 4;
-      r.m = d->r * d->s * d->c; r.n = d->k; r.k = d->n * d->ho * d->wo; r.ms = 0.f;
-      r.flops = 2.0 * r.m * r.n * r.k;
-    }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool timed = timing_wanted(slot.rec);
-    if (timed && (rc = timing_begin(slot, st)) != A3D_OK) return rc;
-    rc = fewch16_bwd_filter(d, x, true, dpool, ld_dpool, pooled, argmax, ld_argmax, dw, db, ws, st);
-    if (timed) timing_end(slot, st);
-    return rc;
+    return timed_launch(timing_record(MODE_BWD_F, A3D_PREC_BF16, 128, (d->k + 31) / 32 * 32, 4, 4, 16, 1, 1, 4, d->r * d->s * d->c, d->k,
+                                      d->n * d->ho * d->wo),
+                        st, [&] { return fewch16_bwd_filter(d, x, true, dpool, ld_dpool, pooled, argmax, ld_argmax, dw, db, ws, st); });
   }
   A3D_CHECK_ARG(!d->storage && fewch_bwdf_applicable(d, true),
                 "conv2d_bwd_filter_pooled: an unpadded conv of <= 4 densely packed float32 input channels and 33..96 filters (fp32 "
@@ -1483,7 +1134,7 @@ int a3d_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* d
   IgemmParams p;
   fill_common(p, g);
   rc = apply_storage(p, g, d->precision, d->storage & A3D_STORE_X_BF16, d->storage & A3D_STORE_Y_BF16, false, d->c, d->ldx,
-                     -1, d->ldy, x, dz, dw, d->k, d->k);
+                     -1, d->ldy, x, dz, dw);
   if (rc != A3D_OK) return rc;
   g.ring_ok = !run && p.a16 && p.b16 && bwd_f_ring_ok(d) && aligned16(dw);
   GemmPlan plan = plan_gemm(g, d->precision);
@@ -1503,19 +1154,10 @@ int a3d_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* d
   }
   p.A = x; p.B = dz; p.C = out; p.dbias = db;     // BiasAddGrad = column sums of dz, fused into the same kernel
   p.npix = g.K; p.nrsc = g.M;
-  p.H = d->h; p.W = d->w; p.ld = d->ldx; p.pHW = d->h * d->w;
-  p.stride = d->stride; p.lstride = ilog2_exact(d->stride); p.pad_t = d->pad_t; p.pad_l = d->pad_l;
-  p.S = run ? 1 : d->s; p.Cg = run ? rf.rlp : d->c;
-  p.div_phw = make_fastdiv(d->ho * d->wo); p.div_pw = make_fastdiv(d->wo);
-  p.div_c = make_fastdiv(p.Cg); p.div_s = make_fastdiv(p.S);
-  p.div_c_half = make_fastdiv(std::max(1, p.Cg / 2));
+  fill_gather(p, d, d->ldx, run ? 1 : d->s, run ? rf.rlp : d->c);
   p.ldb = d->ldy; p.ldc = d->k;
-  {
-    const bool inside = (d->ho - 1) * d->stride + d->r <= d->h && (d->wo - 1) * d->stride + d->s <= d->w;
-    fill_staging(p, MODE_BWD_F, (unsigned long long)d->n * d->h * d->w * d->ldx,
-                 (unsigned long long)d->n * d->ho * d->wo * d->ldy, d->r, run ? 1 : d->s, inside ? d->r : 0,
-                 inside ? d->s : 0);
-  }
+  fill_staging(p, MODE_BWD_F, (unsigned long long)d->n * d->h * d->w * d->ldx, (unsigned long long)d->n * d->ho * d->wo * d->ldy, d->r,
+               run ? 1 : d->s);
   if (run) { p.unpad_dst = dw; p.unpad_rl = rf.rl; p.unpad_rlp = rf.rlp; }
   rc = launch_igemm(MODE_BWD_F, plan, g.avec, g.bvec, p, static_cast<char*>(ws) + ws_used, st);
   if (rc != A3D_OK || !run || p.unpad_done) return rc;       // the split-K reduction stored the unpadded filter itself
@@ -1569,7 +1211,7 @@ int a3d_dense_fwd_ex2(int m, int k, int n, const float* x, const float* w, const
   if (!aligned16(w)) g.bvec = 1;
   IgemmParams p;
   fill_common(p, g);
-  rc = apply_storage(p, g, precision, storage & A3D_STORE_X_BF16, storage & A3D_STORE_W_BF16, false, k, k, n, n, x, w, y, n, n);
+  rc = apply_storage(p, g, precision, storage & A3D_STORE_X_BF16, storage & A3D_STORE_W_BF16, false, k, k, n, n, x, w, y);
   if (rc != A3D_OK) return rc;
   g.ring_ok = p.a16 && p.b16 && precision == A3D_PREC_BF16 && k % 8 == 0 && n % 8 == 0 && aligned16(y) && act != A3D_ACT_SIGMOID;
   g.need_reduce = ncols_y != n;                  // rows narrower than the GEMM are stored by the split-K reduction: plan one
@@ -1578,13 +1220,12 @@ int a3d_dense_fwd_ex2(int m, int k, int n, const float* x, const float* w, const
   A3D_CHECK_ARG(!p.a16 || plan.ring, "dense_fwd: a bf16 x is taken by the LDS-DMA kernel only (bf16 weights, k and n multiples of 8)");
   if (plan.ws_bytes > ws_bytes) return set_error(A3D_EWORKSPACE, "dense_fwd: need %zu workspace bytes", plan.ws_bytes);
   p.A = x; p.B = w; p.C = y; p.bias = bias; p.act = act; p.keep = drop_keep; p.mask_scale = 2.f;
-  p.npix = m; p.nrsc = k; p.H = 1; p.W = 1; p.ld = k; p.pHW = 1; p.stride = 1; p.lstride = 0; p.S = 1; p.Cg = k;
-  p.div_phw = make_fastdiv(1); p.div_pw = make_fastdiv(1); p.div_c = make_fastdiv(k); p.div_s = make_fastdiv(1);
-  p.div_c_half = make_fastdiv(std::max(1, k / 2));
+  p.npix = m; p.nrsc = k;
+  fill_gather(p, &d, k, 1, k);                   // one tap over the k inputs of a row
   p.ldb = n; p.ldc = ldy; p.c_cols = ncols_y == n ? 0 : ncols_y;
   rc = take_second_output(p, out2);
   if (rc != A3D_OK) return rc;
-  fill_staging(p, MODE_FWD, (unsigned long long)m * k, (unsigned long long)k * n, 1, 1, 1, 1);
+  fill_staging(p, MODE_FWD, (unsigned long long)m * k, (unsigned long long)k * n, 1, 1);
   return launch_igemm(MODE_FWD, plan, g.avec, g.bvec, p, ws, static_cast<hipStream_t>(stream));
 }
 
@@ -1620,7 +1261,7 @@ int a3d_dense_bwd_data_ex2(int m, int k, int n, const float* dz, const float* w,
   IgemmParams p;
   fill_common(p, g);
   rc = apply_storage(p, g, precision, storage & A3D_STORE_Y_BF16, storage & A3D_STORE_W_BF16, storage & A3D_STORE_X_BF16, n, n, n, n,
-                     dz, w, dx, k, k);
+                     dz, w, dx);
   if (rc != A3D_OK) return rc;
   g.ring_ok = p.a16 && p.b16 && precision == A3D_PREC_BF16 && k % 8 == 0 && n % 8 == 0 && aligned16(dx) &&
               (!mask || (aligned16(mask) && mask_act == A3D_ACT_RELU));
@@ -1629,15 +1270,14 @@ int a3d_dense_bwd_data_ex2(int m, int k, int n, const float* dz, const float* w,
   A3D_CHECK_ARG(!(p.a16 || p.c16) || plan.ring, "dense_bwd_data: bf16 dz / dx are taken by the LDS-DMA kernel only (bf16 weights, k and n multiples of 8, ReLU mask)");
   if (plan.ws_bytes > ws_bytes) return set_error(A3D_EWORKSPACE, "dense_bwd_data: need %zu workspace bytes", plan.ws_bytes);
   p.A = dz; p.B = w; p.C = dx; p.mask = mask; p.mask_scale = scale; p.mask_act = mask_act;
-  p.npix = m; p.nrsc = n; p.H = 1; p.W = 1; p.ld = n; p.pHW = 1; p.stride = 1; p.lstride = 0; p.S = 1;
-  p.Cg = n; p.Cn = k;
-  p.div_phw = make_fastdiv(1); p.div_pw = make_fastdiv(1); p.div_c = make_fastdiv(n); p.div_s = make_fastdiv(1);
-  p.div_c_half = make_fastdiv(std::max(1, n / 2));
+  p.npix = m; p.nrsc = n;
+  fill_gather(p, &d, n, 1, n);                   // one tap over the n gradients of a row
+  p.Cn = k;
   p.ldc = k;
   p.S_full = 1;
   rc = take_second_output(p, out2);
   if (rc != A3D_OK) return rc;
-  fill_staging(p, MODE_BWD_D, (unsigned long long)m * n, (unsigned long long)k * n, 1, 1, 0, 0);
+  fill_staging(p, MODE_BWD_D, (unsigned long long)m * n, (unsigned long long)k * n, 1, 1);
   return launch_igemm(MODE_BWD_D, plan, g.avec, g.bvec, p, ws, static_cast<hipStream_t>(stream));
 }
 

@@ -2,14 +2,10 @@
 // with A3D_MODE defined, so the three modes compile in parallel.
 #include "a3d_internal.h"
 #include "igemm.h"
+#include "igemm_cfgs.h"
 #include "igemm_glds.h"
 
 namespace a3d {
-
-// index, BM, BN, WAVES_M, NWAVES, BK  (keep in step with kCfgs in igemm_host.hip)
-#define A3D_CFGS(X) X(0, 128, 128, 2, 4, 32) X(1, 128, 96, 4, 4, 32) X(2, 128, 64, 4, 4, 32) X(3, 128, 32, 4, 4, 32) \
-                    X(4, 64, 64, 2, 4, 32) X(5, 32, 128, 1, 4, 32) X(6, 64, 128, 1, 4, 32) X(7, 128, 128, 4, 8, 32) \
-                    X(8, 128, 64, 4, 8, 32)
 
 // A3D_HINT_SHARE_CU: the dynamic LDS request is raised until only 8 / NWAVES blocks (two wavefronts per SIMD) fit the
 // CU's 160 KiB, so the other stream's bandwidth-bound kernels find free registers and wave slots on every CU.
@@ -47,10 +43,7 @@ static int launch_vec(int avec, int bvec, IgemmParams& p, unsigned grid, hipStre
   return launch_one<BM, BN, WAVES_M, NWAVES, BK, 1, 1>(p, grid, st);
 }
 
-// LDS-DMA staged variants (igemm_glds.h): index, BM, BN, WAVES_M, NWAVES, index of the register-staged twin used
-// when an operand is not 16-byte vectorisable
-#define A3D_GLDS_CFGS(X) X(9, 128, 128, 4, 8, 7) X(10, 128, 64, 4, 8, 8)
-
+// LDS-DMA staged variants (igemm_glds.h)
 template <int BM, int BN, int WAVES_M, int NWAVES>
 static int launch_glds(IgemmParams& p, unsigned grid, hipStream_t st) {
   using Cfg = GldsCfg<A3D_MODE, BM, BN, WAVES_M, NWAVES>;
@@ -106,7 +99,7 @@ int launch_igemm_multi_bwd_d(int avec, int bvec, IgemmMulti& ps, unsigned grid_x
 // stream-K fixup of a launch made with register-staged config `cfg`
 int A3D_CAT(launch_fixup_mode, A3D_MODE)(int cfg, IgemmParams& p, unsigned tiles, unsigned nblk, hipStream_t st) {
   switch (cfg) {
-#define X(i, bm, bn, wm, nw, bk) \
+#define X(i, bm, bn, wm, nw, bk, eff) \
   case i: return launch_fixup_one<bm, bn, wm, nw>(p, tiles, nblk, st);
     A3D_CFGS(X)
 #undef X
@@ -116,8 +109,8 @@ int A3D_CAT(launch_fixup_mode, A3D_MODE)(int cfg, IgemmParams& p, unsigned tiles
 
 int A3D_CAT(launch_igemm_mode, A3D_MODE)(int cfg, int avec, int bvec, IgemmParams& p, unsigned grid, hipStream_t st) {
   switch (cfg) {
-#define X(i, bm, bn, wm, nw, twin) \
-  case i:                          \
+#define X(i, bm, bn, wm, nw, twin, eff) \
+  case i:                               \
     if (avec == 4 && bvec == 4) return launch_glds<bm, bn, wm, nw>(p, grid, st); \
     cfg = twin;                    \
     break;
@@ -125,7 +118,7 @@ int A3D_CAT(launch_igemm_mode, A3D_MODE)(int cfg, int avec, int bvec, IgemmParam
 #undef X
   }
   switch (cfg) {
-#define X(i, bm, bn, wm, nw, bk) \
+#define X(i, bm, bn, wm, nw, bk, eff) \
   case i: return launch_vec<bm, bn, wm, nw, bk>(avec, bvec, p, grid, st);
     A3D_CFGS(X)
 #undef X

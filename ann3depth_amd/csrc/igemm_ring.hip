@@ -2,12 +2,10 @@
 #include <algorithm>
 
 #include "a3d_internal.h"
+#include "igemm_cfgs.h"
 #include "igemm_ring.h"
 
 namespace a3d {
-
-// index, BM, BN, WAVES_M  (keep in step with kRingCfgs in igemm_host.hip)
-#define A3D_RING_CFGS(X) X(0, 256, 128, 4) X(1, 256, 64, 8) X(2, 256, 256, 4) X(3, 128, 128, 4) X(5, 512, 64, 8) X(6, 64, 128, 2)
 
 template <int MODE, int BM, int BN, int WAVES_M, bool C16>
 static int launch_ring_one(IgemmParams& p, unsigned grid, hipStream_t st) {
@@ -41,11 +39,15 @@ static int launch_ring_mode(int cfg, IgemmParams& p, unsigned grid, hipStream_t 
   switch (cfg) {
 #define X(i, bm, bn, wm) \
   case i: return launch_ring_tile<MODE, bm, bn, wm>(c16, p, grid, st);
-    A3D_RING_CFGS(X)
+    A3D_RING_CFGS_FWD_BWD_D(X)
 #undef X
   }
-  if (MODE == MODE_BWD_D && cfg == 4)      // 96 input channels (conv2d_1's bwd-data): one 96-column tile, k-contiguous filter rows
-    return launch_ring_tile<MODE_BWD_D, 256, 96, 8>(c16, p, grid, st);
+  if (MODE == MODE_BWD_D) switch (cfg) {      // 96 input channels (conv2d_1's bwd-data): one 96-column tile, k-contiguous filter rows
+#define X(i, bm, bn, wm) \
+  case i: return launch_ring_tile<MODE_BWD_D, bm, bn, wm>(c16, p, grid, st);
+    A3D_RING_CFGS_BWD_D_ONLY(X)
+#undef X
+  }
   return set_error(A3D_EINVAL, "igemm ring: unknown config %d", cfg);
 }
 
@@ -53,10 +55,10 @@ int launch_igemm_ring(int mode, int cfg, IgemmParams& p, unsigned grid, hipStrea
   if (mode == MODE_FWD) return launch_ring_mode<MODE_FWD>(cfg, p, grid, st);
   if (mode == MODE_BWD_D) return launch_ring_mode<MODE_BWD_D>(cfg, p, grid, st);
   switch (cfg) {                               // bwd-filter: float32 gradient (or split-K slabs), tiles of at least 128 rows / 64 columns
-    case 0: return launch_ring_tile<MODE_BWD_F, 256, 128, 4>(false, p, grid, st);
-    case 1: return launch_ring_tile<MODE_BWD_F, 256, 64, 8>(false, p, grid, st);
-    case 2: return launch_ring_tile<MODE_BWD_F, 256, 256, 4>(false, p, grid, st);
-    case 3: return launch_ring_tile<MODE_BWD_F, 128, 128, 4>(false, p, grid, st);
+#define X(i, bm, bn, wm) \
+  case i: return launch_ring_tile<MODE_BWD_F, bm, bn, wm>(false, p, grid, st);
+    A3D_RING_CFGS_EVERY_MODE(X)
+#undef X
   }
   return set_error(A3D_EINVAL, "igemm ring: unknown bwd-filter config %d", cfg);
 }

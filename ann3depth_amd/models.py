@@ -279,7 +279,7 @@ class MSDNReplica:
             # its kernel with rows of 4072 elements (the two pad columns zero, the bias padded alike).  Its master weights,
             # gradient and ApplyAdam stay fp32.
             # bf16 x / dz into the dense layers: the LDS-DMA kernel takes them as a weight stream of at most 64 rows (ring_plan,
-            # igemm_host.hip); a larger batch keeps the dense layers' small side fp32 (B = 65..383 had no kernel)
+            # igemm_plan.cc); a larger batch keeps the dense layers' small side fp32 (B = 65..383 had no kernel)
             # and dense_1 on the fp32 kernels.
             # round 5: the casts between the bf16 conv stack and the fp32 dense side (c4 -> c4_32, drop -> drop16, coarse ->
             # cat[..., 63], dz1 -> dz1_16, dz0 -> dz0_16) leave through the reductions that produce their sources

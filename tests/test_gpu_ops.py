@@ -1092,7 +1092,7 @@ def test_a_non_finite_pixel_reaches_only_the_windows_that_contain_it(ops, n, h, 
 
 
 RING_CASES = [
-    # n, h, w, c, k, ks, stride, pad, y bf16?, the tile the planner must pick (igemm_host.hip: kRingCfgs)
+    # n, h, w, c, k, ks, stride, pad, y bf16?, the tile the planner must pick (igemm_cfgs.h: A3D_RING_CFGS)
     (28, 13, 18, 256, 384, 3, 1, 'SAME', True, (128, 128)),     # conv2d_2 kind, 128-row tiles (two blocks per CU), M tail
     (106, 13, 18, 64, 200, 3, 1, 'SAME', True, (256, 128)),      # 256 x 128 tiles, N tail (200 = 128 + 72), K = 576 = 9 k-tiles
     (26, 27, 37, 96, 128, 5, 1, 'SAME', True, (128, 128)),      # conv2d_1's 96 channels: a k-tile straddles two taps; K tail (2400)

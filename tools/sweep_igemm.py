@@ -1,5 +1,6 @@
 """Times every MSDN layer (B=32) x direction under each tile config / split-K of the implicit-GEMM kernel.
-Tuning aid for csrc/igemm_host.hip:plan_gemm; run on the GPU box:  python tools/sweep_igemm.py > gpurun_out/sweep.txt"""
+Tuning aid for csrc/igemm_plan.cc:plan_gemm (the tile configurations: csrc/igemm_cfgs.h); run on the GPU box and keep what
+it prints:  python tools/sweep_igemm.py > sweep.txt"""
 import os
 os.environ.setdefault('A3D_TUNING', '1')   # the library reads its A3D_FORCE_* switches per launch only then
 import sys
