@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "../../include/a3d.h"
 #include "igemm_plan.h"
 
@@ -24,6 +26,12 @@ inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(A3D_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
   return A3D_OK;
+}
+
+// blocks of a grid-stride launch: one thread per unit of work, at most `cap` blocks
+inline unsigned grid_for(size_t total, int per_block = 256, unsigned cap = 8192) {
+  size_t g = (total + per_block - 1) / per_block;
+  return (unsigned)std::min<size_t>(std::max<size_t>(g, 1), cap);
 }
 
 // ---- implicit-GEMM front end: the planner (igemm_plan.h, igemm_plan.cc) and the launches (igemm_host.hip) ----

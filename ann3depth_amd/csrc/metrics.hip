@@ -2,7 +2,7 @@
 // sums every metric of the table is built from (include/a3d.h, A3D_METRIC_*), accumulated in fp64.
 //
 // Compiled with -ffp-contract=off (see Makefile): the prediction sampled at a target pixel must be bit-identical to what
-// a3d_resize_bilinear_tf1 writes for that pixel (pointwise.hip, resize_rows), and the per-pixel terms are the separate
+// a3d_resize_bilinear_tf1 writes for that pixel (resample.hip, resize_rows), and the per-pixel terms are the separate
 // correctly-rounded fp32 operations the test's numpy reference performs.
 //
 // Two launches.  metrics_part_kernel: grid (parts, n); workgroup (part, b) walks a contiguous range of image b's target
@@ -29,7 +29,7 @@ struct MetricsArgs {
   const void* target;
   double* ws;
   int ph, pw, th, tw, npix, chunk, parts, u8;
-  float sy, sx;                           // legacy ResizeBilinear scales in / out (resize_one in pointwise.hip)
+  float sy, sx;                           // legacy ResizeBilinear scales in / out (resize_one in resample.hip)
   float min_depth, max_depth, clamp_lo, clamp_hi;
 };
 
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(kThreads) void metrics_part_kernel(const MetricsArg
   __shared__ float lut[256];
   __shared__ double red[kThreads / 64][kCols];
   if constexpr (U8 != 0) {
-    // the float the converter stored plus the loader's 0.5, as resize_kernel's table (pointwise.hip)
+    // the float the converter stored plus the loader's 0.5, as resize_kernel's table (fill_u8_lut, resample.hip)
     lut[threadIdx.x] = __fadd_rn(__fsub_rn(__fdiv_rn((float)threadIdx.x, 255.f), 0.5f), 0.5f);
     __syncthreads();
   }

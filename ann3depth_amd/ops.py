@@ -151,19 +151,14 @@ def maxpool2x2_bwd_idx(argmax, y_pooled, dy, dx, relu_mask=True):
     n, h, w, c = dx.shape
     if y_pooled.dtype == torch.bfloat16 and dx.dtype == torch.bfloat16:      # bf16 storage throughout (conv2d_1 of config 5)
         assert dy.dtype == torch.bfloat16
-        check(_lib.load().a3d_maxpool2x2_bwd_idx_bf16s(n, h, w, c, _ptr(argmax), _ptr(y_pooled), y_pooled.shape[-1], _ptr(dy),
-                                                       dy.shape[-1], _ptr(dx), int(relu_mask), _stream()),
-              'a3d_maxpool2x2_bwd_idx_bf16s')
-        return dx
-    if y_pooled.dtype == torch.bfloat16:         # bf16 storage: pooled values and dy bf16, dx float32
+        name = 'a3d_maxpool2x2_bwd_idx_bf16s'
+    elif y_pooled.dtype == torch.bfloat16:       # bf16 storage: pooled values and dy bf16, dx float32
         assert dy.dtype == torch.bfloat16 and dx.dtype == torch.float32
-        check(_lib.load().a3d_maxpool2x2_bwd_idx_bf16(n, h, w, c, _ptr(argmax), _ptr(y_pooled), y_pooled.shape[-1], _ptr(dy),
-                                                      dy.shape[-1], _ptr(dx), int(relu_mask), _stream()),
-              'a3d_maxpool2x2_bwd_idx_bf16')
-        return dx
-    check(_lib.load().a3d_maxpool2x2_bwd_idx(n, h, w, c, _ptr(argmax), _ptr(y_pooled), y_pooled.shape[-1], _ptr(dy),
-                                             dy.shape[-1], _ptr(dx), int(relu_mask), _stream()),
-          'a3d_maxpool2x2_bwd_idx')
+        name = 'a3d_maxpool2x2_bwd_idx_bf16'
+    else:
+        name = 'a3d_maxpool2x2_bwd_idx'
+    check(getattr(_lib.load(), name)(n, h, w, c, _ptr(argmax), _ptr(y_pooled), y_pooled.shape[-1], _ptr(dy), dy.shape[-1],
+                                     _ptr(dx), int(relu_mask), _stream()), name)
     return dx
 
 
@@ -280,12 +275,21 @@ def maxpool2x2_bwd(x, dy, dx, relu_mask=True):
     return dx
 
 
+def _pair_args(x0, y0, x1=None, y1=None):
+    """(n, h, w, c0, x0, u8_0, oh0, ow0, y0, c1, x1, u8_1, oh1, ow1, y1): what the _ex, warp and validity-aware entry
+    points all begin with.  x1 None: no second tensor, zeros and null pointers."""
+    def one(x, y):
+        if x is None:
+            return 0, None, 0, 0, 0, None
+        return x.shape[3], _ptr(x), int(x.dtype == torch.uint8), y.shape[1], y.shape[2], _ptr(y)
+    return tuple(x0.shape[:3]) + one(x0, y0) + one(x1, y1)
+
+
 def resize_bilinear_tf1(x, y):
     """x float32, or uint8 pixel values k of a converter-written record (the kernel reads fl(fl(fl(k/255) - .5) + .5))."""
     n, h, w, c = x.shape
     if x.dtype == torch.uint8:
-        check(_lib.load().a3d_resize_bilinear_tf1_ex(n, h, w, c, _ptr(x), 1, y.shape[1], y.shape[2], _ptr(y), 0, None, 0, 0, 0,
-                                                     None, _stream()), 'a3d_resize_bilinear_tf1_ex')
+        check(_lib.load().a3d_resize_bilinear_tf1_ex(*_pair_args(x, y), _stream()), 'a3d_resize_bilinear_tf1_ex')
         return y
     check(_lib.load().a3d_resize_bilinear_tf1(n, h, w, c, _ptr(x), y.shape[1], y.shape[2], _ptr(y), _stream()),
           'a3d_resize_bilinear_tf1')
@@ -298,10 +302,7 @@ def resize_bilinear_tf1_pair(x0, y0, x1, y1):
     n, h, w, c0 = x0.shape
     assert x1.shape[:3] == (n, h, w)
     if x0.dtype == torch.uint8 or x1.dtype == torch.uint8:
-        check(_lib.load().a3d_resize_bilinear_tf1_ex(n, h, w, c0, _ptr(x0), int(x0.dtype == torch.uint8), y0.shape[1],
-                                                     y0.shape[2], _ptr(y0), x1.shape[3], _ptr(x1),
-                                                     int(x1.dtype == torch.uint8), y1.shape[1], y1.shape[2], _ptr(y1),
-                                                     _stream()), 'a3d_resize_bilinear_tf1_ex')
+        check(_lib.load().a3d_resize_bilinear_tf1_ex(*_pair_args(x0, y0, x1, y1), _stream()), 'a3d_resize_bilinear_tf1_ex')
         return
     check(_lib.load().a3d_resize_bilinear_tf1_pair(n, h, w, c0, _ptr(x0), y0.shape[1], y0.shape[2], _ptr(y0), x1.shape[3],
                                                    _ptr(x1), y1.shape[1], y1.shape[2], _ptr(y1), _stream()),
@@ -344,13 +345,8 @@ def warp_bilinear_pair(x0, y0, x1, y1, table):
     tensors of one device."""
     if table is None:
         raise ValueError('warp_bilinear_pair: no table')
-    n, h, w, c0 = _check_pair('warp_bilinear_pair', x0, y0, x1, y1, table)
-    second = x1 is not None
-    check(_lib.load().a3d_warp_bilinear_pair(n, h, w, c0, _ptr(x0), int(x0.dtype == torch.uint8), y0.shape[1], y0.shape[2],
-                                             _ptr(y0), x1.shape[3] if second else 0, _ptr(x1),
-                                             int(second and x1.dtype == torch.uint8), y1.shape[1] if second else 0,
-                                             y1.shape[2] if second else 0, _ptr(y1), _ptr(table), _stream()),
-          'a3d_warp_bilinear_pair')
+    _check_pair('warp_bilinear_pair', x0, y0, x1, y1, table)
+    check(_lib.load().a3d_warp_bilinear_pair(*_pair_args(x0, y0, x1, y1), _ptr(table), _stream()), 'a3d_warp_bilinear_pair')
 
 
 def _valid_range(who, x1, min_depth, max_depth):
@@ -368,10 +364,8 @@ def resize_bilinear_tf1_pair_valid(x0, y0, x1, y1, min_depth=0., max_depth=float
     plain launch's.  Tensors as warp_bilinear_pair's."""
     who = 'resize_bilinear_tf1_pair_valid'
     lo, hi = _valid_range(who, x1, min_depth, max_depth)
-    n, h, w, c0 = _check_pair(who, x0, y0, x1, y1, None)
-    check(_lib.load().a3dx_resize_bilinear_tf1_valid(n, h, w, c0, _ptr(x0), int(x0.dtype == torch.uint8), y0.shape[1], y0.shape[2],
-                                                    _ptr(y0), x1.shape[3], _ptr(x1), int(x1.dtype == torch.uint8), y1.shape[1],
-                                                    y1.shape[2], _ptr(y1), lo, hi, _stream()),
+    _check_pair(who, x0, y0, x1, y1, None)
+    check(_lib.load().a3dx_resize_bilinear_tf1_valid(*_pair_args(x0, y0, x1, y1), lo, hi, _stream()),
           'a3dx_resize_bilinear_tf1_valid')
 
 
@@ -391,10 +385,8 @@ def warp_bilinear_pair_valid(x0, y0, x1, y1, table, min_depth=0., max_depth=floa
     if table is None:
         raise ValueError(f'{who}: no table')
     lo, hi = _valid_range(who, x1, min_depth, max_depth)
-    n, h, w, c0 = _check_pair(who, x0, y0, x1, y1, table)
-    check(_lib.load().a3dx_warp_bilinear_pair_valid(n, h, w, c0, _ptr(x0), int(x0.dtype == torch.uint8), y0.shape[1], y0.shape[2],
-                                                   _ptr(y0), x1.shape[3], _ptr(x1), int(x1.dtype == torch.uint8), y1.shape[1],
-                                                   y1.shape[2], _ptr(y1), _ptr(table), lo, hi, _stream()),
+    _check_pair(who, x0, y0, x1, y1, table)
+    check(_lib.load().a3dx_warp_bilinear_pair_valid(*_pair_args(x0, y0, x1, y1), _ptr(table), lo, hi, _stream()),
           'a3dx_warp_bilinear_pair_valid')
 
 

@@ -1,5 +1,5 @@
-"""Host references (numpy only) of the exact operations in ann3depth_amd/csrc/pointwise.hip that oracle/tf13_ops.py does
-not already restate: the Philox4x32-10 keep mask of a3d_dropout_keep_mask, round-to-nearest-even float32 -> bf16, the
+"""Host references (numpy only) of the exact operations in ann3depth_amd/csrc/pointwise.hip and pool.hip that
+oracle/tf13_ops.py does not already restate: the Philox4x32-10 keep mask of a3d_dropout_keep_mask, round-to-nearest-even float32 -> bf16, the
 max-pool gradient routed by recorded argmax bytes, and the meaning of a3d_adam_apply_tf1_flag's `poisoned` bit.  Each is a
 restatement of the contract in include/a3d.h; tests/test_pointwise_ref.py pins them to published vectors, torch's CPU
 cast and the oracle, and tests/test_gpu_pointwise.py holds the kernels to them bit for bit."""

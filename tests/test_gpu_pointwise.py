@@ -1,4 +1,5 @@
-"""The HBM-bound kernels of ann3depth_amd/csrc/pointwise.hip held to exact host references at their edges: tails of the
+"""The HBM-bound kernels of ann3depth_amd/csrc/pointwise.hip, pool.hip and resample.hip held to exact host references at
+their edges: tails of the
 vector bodies, grid-stride loops past the launch's block cap, pitches wider than the channel count, odd sizes, ties,
 signed zeros, denormals, non-finite values.  Every comparison is bit-exact (values, or the uint16 / uint8 bits) except the
 loss and its gradient, which keep the 2e-6 / 1e-5 of tests/test_gpu_ops.py::test_silog_loss against the float64 oracle.
@@ -6,8 +7,9 @@ Every output tensor is a window of a larger allocation filled with a sentinel: p
 before and after the tensor must keep it.  References: oracle/tf13_ops.py (T) and tests/pointwise_ref.py (R), the latter
 pinned on the CPU by tests/test_pointwise_ref.py.
 
-That the file bites was checked with mutated copies of pointwise.hip, one value changed per build (never an index, bound
-or stride), bound through A3D_LIB; each made the tests named here fail and no other:
+That the file bites was checked with mutated copies of the sources, one value changed per build (never an index, bound
+or stride), bound through A3D_LIB; each made the tests named here fail and no other (kernels under the names they had
+then: maxpool_bwd_bf16_kernel is now maxpool_bwd_kernel<__bf16>, the bf16 -> fp32 idx form maxpool_bwd_idx_kernel<__bf16>):
   a Philox multiplier; k1 += the other Weyl constant; c[j] >> 9; step_lo / step_hi swapped
                                                    -> test_dropout_keep_mask_is_the_philox_stream_of_its_contract (all 8),
                                                       _seed_and_step_use_all_64_bits, _rates (all 3)
@@ -275,7 +277,7 @@ def test_silog_gradient_of_a_sample_that_holds_a_minus_infinite_log(ops):
     assert_same_bf16(g16[:, :npix], R.bf16_round(g))
 
 
-# ================================================================================================ bf16 pool kernels
+# ================================================================================================ pool kernels
 def pool_values(rng, shape, pad_from=None):
     """bf16-valued float32: post-ReLU normals (about half exact zeros, ties everywhere) with a few -0.0; channels from
     `pad_from` on (pad channels of a wider pitch) hold a huge value no kernel may read."""
@@ -292,21 +294,40 @@ POOL16_CASES = [
     (1, 27, 37, 96, 96, 96), (2, 4, 6, 1, 1, 1),
     (24, 55, 74, 96, 96, 96),               # 2.30 M outputs: past 8192 blocks x 256
 ]
+# The float32 entry points run the same templated bodies on a dense x: the small cases with ldx == c.  The bf16 cases keep
+# the ids they always had.
+POOL_FP32_CASES = [(3, 5, 4, 3, 3, 4), (2, 2, 2, 1, 1, 2), (2, 4, 6, 1, 1, 1), (2, 3, 3, 64, 64, 72)]
+POOL_DTYPE_CASES = ([pytest.param('bf16', *case, id='-'.join(map(str, case))) for case in POOL16_CASES] +
+                    [pytest.param('fp32', *case, id='fp32-' + '-'.join(map(str, case))) for case in POOL_FP32_CASES])
 
 
-@pytest.mark.parametrize('n,h,w,c,ldx,ldy', POOL16_CASES)
-def test_maxpool2x2_fwd_bf16_against_the_oracle(ops, n, h, w, c, ldx, ldy):
-    """a3d_maxpool2x2_fwd_bf16 vs T.maxpool2x2_fwd (exact on bf16 values), the concatenated float32 channel vs R.bf16_round."""
+@pytest.mark.parametrize('dtype,n,h,w,c,ldx,ldy', POOL_DTYPE_CASES)
+def test_maxpool2x2_fwd_bf16_against_the_oracle(ops, dtype, n, h, w, c, ldx, ldy):
+    """a3d_maxpool2x2_fwd_bf16 vs T.maxpool2x2_fwd (exact on bf16 values), the concatenated float32 channel vs R.bf16_round.
+    fp32: a3d_maxpool2x2_fwd, the same body, on the same values; its concatenated channel is `extra` itself."""
     rng = np.random.default_rng(h * 1000 + w * 10 + c)
     ho, wo = h // 2, w // 2
     x = pool_values(rng, (n, h, w, ldx), pad_from=c)
-    xd = dev16(R.bf16_round(x))
     ref = T.maxpool2x2_fwd(x[..., :c])
     extras = [None]
     if ldy > c:
         e = (rng.standard_normal((n, ho, wo)) * 3).astype(np.float32)        # not bf16-representable
         e.reshape(-1)[:2] = np.array([0x3F808000, 0x3F818000], np.uint32).view(np.float32)[:e.size]     # ties
         extras.append(e)
+    if dtype == 'fp32':
+        xd = dev(x)
+        for extra in extras:
+            y = Guarded(n * ho * wo * ldy)
+            ops.maxpool2x2_fwd(xd, y.view(n, ho, wo, ldy), None if extra is None else dev(extra))
+            got = y.host(n, ho, wo, ldy)
+            np.testing.assert_array_equal(got[..., :c], ref)
+            used = c
+            if extra is not None:
+                np.testing.assert_array_equal(got[..., c].view(np.uint32), extra.view(np.uint32))       # a copy: no rounding
+                used = c + 1
+            assert (got[..., used:] == SENT).all()
+        return
+    xd = dev16(R.bf16_round(x))
     for extra in extras:
         y = Guarded(n * ho * wo * ldy, BF16)
         ops.maxpool2x2_fwd_bf16(xd, y.view(n, ho, wo, ldy), None if extra is None else dev(extra), c=c)
@@ -319,18 +340,31 @@ def test_maxpool2x2_fwd_bf16_against_the_oracle(ops, n, h, w, c, ldx, ldy):
         assert (got[..., used:] == SENT16).all()
 
 
-@pytest.mark.parametrize('n,h,w,c,ldx,ldy', POOL16_CASES)
-def test_maxpool2x2_bwd_bf16_against_the_oracle(ops, n, h, w, c, ldx, ldy):
+@pytest.mark.parametrize('dtype,n,h,w,c,ldx,ldy', POOL_DTYPE_CASES)
+def test_maxpool2x2_bwd_bf16_against_the_oracle(ops, dtype, n, h, w, c, ldx, ldy):
     """a3d_maxpool2x2_bwd_bf16 vs T.maxpool2x2_bwd / T.relu_grad: first maximum in scan order on exact ties (-0.0 and +0.0
-    are a tie), dx at x's pitch with its pad channels untouched, the row / column VALID flooring cuts zero."""
+    are a tie), dx at x's pitch with its pad channels untouched, the row / column VALID flooring cuts zero.
+    fp32: a3d_maxpool2x2_bwd, the same body, on the same values (x and dx dense, dy at its pitch)."""
     rng = np.random.default_rng(h * 1000 + w * 10 + c + 1)
     ho, wo = h // 2, w // 2
     lddy = ldy
     x = pool_values(rng, (n, h, w, ldx), pad_from=c)
     dy = R.bf16_values(rng.standard_normal((n, ho, wo, lddy)).astype(np.float32))
     dy[..., c:] = 3e38
-    xd, dyd = dev16(R.bf16_round(x)), dev16(R.bf16_round(dy))
     plain = T.maxpool2x2_bwd(x[..., :c], dy[..., :c])
+    if dtype == 'fp32':
+        xd, dyd = dev(x), dev(dy)
+        for relu_mask, ref in ((False, plain), (True, T.relu_grad(plain, x))):
+            dx = Guarded(n * h * w * c)
+            ops.maxpool2x2_bwd(xd, dyd, dx.view(n, h, w, c), relu_mask=relu_mask)
+            got = dx.host(n, h, w, c)
+            np.testing.assert_array_equal(got, ref)              # 3e38 in dy's pad channels would show if one were read
+            if h % 2:
+                assert (got[:, -1].view(np.uint32) & 0x7FFFFFFF == 0).all()
+            if w % 2:
+                assert (got[:, :, -1].view(np.uint32) & 0x7FFFFFFF == 0).all()
+        return
+    xd, dyd = dev16(R.bf16_round(x)), dev16(R.bf16_round(dy))
     for relu_mask, ref in ((False, plain), (True, T.relu_grad(plain, x[..., :c]))):
         dx = Guarded(n * h * w * ldx, BF16)
         ops.maxpool2x2_bwd_bf16(xd, dyd, dx.view(n, h, w, ldx), relu_mask=relu_mask, c=c)
@@ -693,3 +727,19 @@ def test_extract_patches_with_uneven_padding(ops, n, h, w, c, k, stride):
     y = Guarded(ref.size)
     ops.extract_patches(dev(x), k, stride, y.view(ref.shape[0] * ref.shape[1], k, k, c))
     np.testing.assert_array_equal(y.host(*ref.shape), ref)
+
+
+# ================================================================================================ collective stand-in
+def test_comm_standin_keeps_to_its_destination_when_blocks_outnumber_the_pieces(ops):
+    """a3d_comm_standin with more workgroups than 16-byte pieces to write: a block whose write share is empty (its first
+    piece lies past the end) must write nothing.  The reduce-scatter of an 8 KB bucket at world size 8 (1 KB written) over
+    24 workgroups, and 16 bytes written for 1 MB read."""
+    from ann3depth_amd import _lib
+    for read_bytes, write_bytes in ((8192, 1024), (1 << 20, 16)):
+        src = torch.ones(read_bytes // 4, device='cuda')
+        dst = Guarded(write_bytes // 4, guard=4096, offset=4096)
+        rc = _lib.load().a3d_comm_standin(ctypes.c_void_p(src.data_ptr()), read_bytes, ctypes.c_void_p(dst.t.data_ptr()),
+                                          write_bytes, 24, 400.0, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc == 0                          # A3D_OK
+        torch.cuda.synchronize()
+        dst.host()                              # asserts the guard elements before and after
