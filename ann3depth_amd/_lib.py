@@ -141,6 +141,13 @@ EXT_SIGNATURES = {
     'a3dx_silog_masked_loss_bwd_ex': (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_int, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_pairwise.h declares (NON-REFERENCE extension, prefix a3dp_)
+PAIR_SIGNATURES = {
+    'a3dp_crf_loss_grad': (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_int, c_float, _P, _P, _P, _P, _P]),
+    'a3dp_pair_dense_bwd': (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    'a3dp_sgd_apply_floor': (c_int, [c_size_t, _P, _P, c_float, c_float, _P]),
+}
+
 _lib = None
 
 
@@ -156,7 +163,7 @@ def load():
     # the runtime copy torch initialises: two HIP runtimes in one process cannot both own the device.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(PAIR_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

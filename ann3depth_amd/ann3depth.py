@@ -52,6 +52,10 @@ def main(argv=None):
                      f'{args.model or "(no model)"} is not trained with them (dcnf regresses superpixel means, a mean over '
                      f'a superpixel with holes is a different question).')
         return 2
+    if args.train_pairwise and not hasattr(getattr(models, args.model, None), 'train_pairwise'):
+        logger.error(f'--train-pairwise learns the pairwise weights of the CRF of --model dcnf (Liu et al. 2015): '
+                     f'{args.model or "(no model)"} has no such layer.')
+        return 2
     if args.min_depth is not None or args.max_depth is not None:
         lo = 0. if args.min_depth is None else args.min_depth
         hi = float('inf') if args.max_depth is None else args.max_depth
@@ -115,6 +119,8 @@ def setup_model(args, rank=0, world=1):
         if args.min_depth is not None or args.max_depth is not None:
             model.valid_range = (0. if args.min_depth is None else args.min_depth,
                                  float('inf') if args.max_depth is None else args.max_depth)
+    if hasattr(model, 'train_pairwise'):                                 # main() has refused the models that have none
+        model.train_pairwise = bool(args.train_pairwise)
     inputs, targets = data.inputs(args.datadir, args.dataset, args.batchsize, rank=rank, world=world,
                                   seed=args.seed + rank)
     return model(inputs, targets)
@@ -337,7 +343,7 @@ def latest_checkpoint(ckptdir):
 
 def parse_args(argv=None):
     """The reference's flags verbatim (src/ann3depth.py:221-254), plus --beta2 / --augment / --min-depth / --max-depth /
-    --seed / --trace-every / --profiler."""
+    --train-pairwise / --seed / --trace-every / --profiler."""
     parser = argparse.ArgumentParser()
     parser.add_argument('dataset', default='nyu', type=str, help='The dataset to use.')
     parser.add_argument('--model', '-m', default='', type=str, help='Enter a model name.')
@@ -367,6 +373,10 @@ def parse_args(argv=None):
                              'min < t <= max; the others leave the resized target and both losses. Giving either flag turns '
                              'the mode on, the other defaults to 0 / +inf.')
     parser.add_argument('--max-depth', default=None, type=float, help='NON-REFERENCE: see --min-depth.')
+    parser.add_argument('--train-pairwise', action='store_true',
+                        help='NON-REFERENCE: learn the pairwise dense layer of the CRF (dcnf only). The reference leaves it at '
+                             'its initial draw (TF 1.3 has no gradient for scatter_nd_update); with this flag the loss is also '
+                             'differentiated through the CRF matrix and the layer descends at 0.1, kept >= 0 (Liu et al. 2015).')
     parser.add_argument('--seed', default=0, type=int, help='Shuffle-queue seed.')
     parser.add_argument('--tf-checkpoints', action='store_true',
                         help='Also write every checkpoint as a TensorFlow V2 bundle (model.ckpt-N.index/.data-*).')

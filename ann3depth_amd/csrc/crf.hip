@@ -4,9 +4,13 @@
 // and, for evaluation, the field's MAP depths A^-1 z (crf_map_kernel), which the reference never forms.
 // A is a constant for the gradient: TF 1.3 registers no gradient for scatter_nd_update (oracle/dcnf.py states the
 // assumption).  All of it is tiny next to the unary conv stack; the kernels are written for clarity, not speed.
+// NON-REFERENCE (include/a3d_pairwise.h, --train-pairwise): the same loss kernel can also carry the identity through its
+// LU and write d loss / d r, the gradient TF 1.3 lacks; pair_dense_bwd_kernel takes it to the pairwise dense layer and
+// sgd_floor_kernel keeps that layer's weights >= 0 (Liu et al. 2015, eq. 9-14).
 #include <algorithm>
 
 #include "a3d_internal.h"
+#include "a3d_pairwise.h"
 
 namespace a3d {
 
@@ -109,17 +113,29 @@ __global__ __launch_bounds__(256) void pair_similarity_kernel(const float* __res
 // One wavefront per image.  A = I + D - R from the pair weights, LU with partial pivoting on [A | z] in LDS:
 // det(A) = +-prod(pivots), w = A^-1 z by back substitution; then energy, partition function, loss, d loss / d z.
 // A pair index outside [0, n) is skipped, not used, and turns every image's loss and dz into NaN (as crf_map_kernel).
+//
+// kPairGrad (a3dp_crf_loss_grad) also writes dr = d mean loss / d r [batch, npairs], A no longer a constant.  With
+// dA / dr_q = (e_l - e_r)(e_l - e_r)^T:  dE_q = (y_l - y_r)^2,  dg_q = -(w_l - w_r)^2,  d det = det S_q with
+// S_q = A^-1[l][l] + A^-1[r][r] - A^-1[l][r] - A^-1[r][l], hence dfac_q = -fac / (sqrt(det) + eps) (sqrt(det) / 2) S_q.
+// A^-1 comes from the same elimination: U is [A | z | I], the row exchanges and row operations run over all 2n + 1
+// columns, and the n extra columns are back-substituted with one lane per column.  Every operation that feeds the loss
+// and dz is the one the other instantiation performs, in its order: both write the same bits.  The row stride of U is
+// odd there, so lanes that walk a column, one row each, and lanes that walk along a row hit different banks.
+// A pair whose two cells a later pair overwrote has no part in A: its dr is +0.  The scatter notes the last writer of
+// every cell (where the identity will stand, and once A has been read, in A's place).
 constexpr int kMaxSp = 64;
+template <bool kPairGrad>
 __global__ __launch_bounds__(64) void crf_loss_kernel(const float* __restrict__ z, const float* __restrict__ y,
                                                       const float* __restrict__ r, const int* __restrict__ left,
                                                       const int* __restrict__ right, float* __restrict__ loss_img,
-                                                      float* __restrict__ dz, int n, int npairs, float eps, float fac0,
-                                                      float inv_batch) {
+                                                      float* __restrict__ dz, float* __restrict__ dr, int n, int npairs,
+                                                      float eps, float fac0, float inv_batch) {
   __shared__ float A[kMaxSp][kMaxSp + 1];
-  __shared__ float U[kMaxSp][kMaxSp + 2];      // working copy, column n holds the right-hand side
+  __shared__ float U[kMaxSp][kPairGrad ? 2 * kMaxSp + 3 : kMaxSp + 2];      // working copy: [A | z] or [A | z | I]
   __shared__ float wv[kMaxSp];
   __shared__ int bad_index;
   const int b = blockIdx.x, lane = threadIdx.x;
+  const int last = kPairGrad ? 2 * n : n;      // the last column of U in use; column n holds the right-hand side
   for (int i = lane; i < n * n; i += 64) A[i / n][i % n] = 0.f;
   __syncthreads();
   if (lane == 0) {                              // scatter the pair weights in pair order: R[l][r] = R[r][l] = r_q
@@ -130,6 +146,7 @@ __global__ __launch_bounds__(64) void crf_loss_kernel(const float* __restrict__ 
       const float v = r[(size_t)b * npairs + q];
       A[l][rr] = v;
       A[rr][l] = v;
+      if (kPairGrad) U[l][n + 1 + rr] = U[rr][n + 1 + l] = __int_as_float(q);      // the last writer of both cells
     }
     bad_index = skipped;
   }
@@ -151,6 +168,12 @@ __global__ __launch_bounds__(64) void crf_loss_kernel(const float* __restrict__ 
     for (int j = 0; j < n; ++j) ay += A[lane][j] * y[(size_t)b * n + j];
   const float yAy = wave_sum_f(yi * ay), zy = wave_sum_f(zi * yi), zz = wave_sum_f(zi * zi), zsum = wave_sum_f(zi);
   const float energy = yAy - 2.f * zy + zz;
+  if (kPairGrad && lane < n)                    // A has been read (every lane its own row): the writers move there
+    for (int j = 0; j < n; ++j) {
+      A[lane][j] = U[lane][n + 1 + j];
+      U[lane][n + 1 + j] = j == lane ? 1.f : 0.f;
+    }
+  if (kPairGrad) __syncthreads();
   // LU, one lane per row
   float det = 1.f;
   for (int k = 0; k < n; ++k) {
@@ -163,7 +186,7 @@ __global__ __launch_bounds__(64) void crf_loss_kernel(const float* __restrict__ 
       if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
     }
     if (arg != k) {
-      for (int j = lane; j <= n; j += 64) { const float t = U[k][j]; U[k][j] = U[arg][j]; U[arg][j] = t; }
+      for (int j = lane; j <= last; j += 64) { const float t = U[k][j]; U[k][j] = U[arg][j]; U[arg][j] = t; }
       det = -det;
     }
     __syncthreads();
@@ -171,7 +194,7 @@ __global__ __launch_bounds__(64) void crf_loss_kernel(const float* __restrict__ 
     det *= piv;
     if (lane > k && lane < n) {
       const float f = U[lane][k] / piv;
-      for (int j = k; j <= n; ++j) U[lane][j] -= f * U[k][j];
+      for (int j = k; j <= last; ++j) U[lane][j] -= f * U[k][j];
     }
     __syncthreads();
   }
@@ -182,22 +205,80 @@ __global__ __launch_bounds__(64) void crf_loss_kernel(const float* __restrict__ 
       wv[i] = s / U[i][i];
     }
   }
+  if (kPairGrad && lane < n) {                  // lane c: column c of A^-1, in place
+    const int c = n + 1 + lane;
+    for (int i = n - 1; i >= 0; --i) {
+      float s = U[i][c];
+      for (int j = i + 1; j < n; ++j) s -= U[i][j] * U[j][c];
+      U[i][c] = s / U[i][i];
+    }
+  }
   __syncthreads();
   const float wi = lane < n ? wv[lane] : 0.f;
   // g = z^T (A^-1 + eps) z - z^T z ;  inverseA = inv(A) + eps adds eps to EVERY element (src/models.py:165)
   const float zw = wave_sum_f(zi * wi);
   const float g = zw + eps * zsum * zsum - zz;
-  const float fac = fac0 / (sqrtf(det) + eps);
+  const float sd = sqrtf(det);
+  const float fac = fac0 / (sd + eps);
   const float ex = expf(g);
   const float Z = fac * ex + eps;
   const float u = expf(-energy) / Z;
-  if (lane == 0) loss_img[b] = bad ? __builtin_nanf("") : -logf(u + eps);
+  const float loss = -logf(u + eps);
+  if (lane == 0) loss_img[b] = bad ? __builtin_nanf("") : loss;
   if (lane < n) {
     const float dE = -2.f * yi + 2.f * zi;
     const float dg = 2.f * wi + 2.f * eps * zsum - 2.f * zi;
     const float du = u * (-dE) - (u / Z) * (fac * ex * dg);
     dz[(size_t)b * n + lane] = bad ? __builtin_nanf("") : (-du / (u + eps)) * inv_batch;
   }
+  if (kPairGrad) {
+    const bool nan_row = bad || !(loss == loss);              // a negative determinant among them: sd is NaN
+    const float dfac_s = -(fac / (sd + eps) * (sd * 0.5f));   // dfac_q = dfac_s * S_q
+    for (int q = lane; q < npairs; q += 64) {
+      float v = __builtin_nanf("");
+      if (!nan_row) {                                         // not bad: l and rr are inside [0, n)
+        const int l = left[q], rr = right[q];
+        v = 0.f;
+        if (__float_as_int(A[l][rr]) == q) {                  // else a later pair overwrote both cells
+          const float dy = y[(size_t)b * n + l] - y[(size_t)b * n + rr], dw = wv[l] - wv[rr];
+          const float S = U[l][n + 1 + l] + U[rr][n + 1 + rr] - U[l][n + 1 + rr] - U[rr][n + 1 + l];
+          const float dE = dy * dy, dg = -(dw * dw), dfac = dfac_s * S;
+          const float du = u * (-dE) - (u / Z) * (dfac * ex + fac * ex * dg);
+          v = (-du / (u + eps)) * inv_batch;
+        }
+      }
+      dr[(size_t)b * npairs + q] = v;
+    }
+  }
+}
+
+// The pairwise dense layer's backward: dw[k] = sum_i dr[i] sims[i][k], db = sum_i dr[i] over the count = n * npairs pairs of
+// the batch.  ONE block and no atomics: thread t adds pairs t, t + 256, ... in order, then block_sum_256 — the same
+// bits on every run.  k is the number of similarities per pair (1 .. kMaxSims); a NaN in dr reaches every output.
+constexpr int kMaxSims = 8;
+__global__ __launch_bounds__(256) void pair_dense_bwd_kernel(const float* __restrict__ sims, const float* __restrict__ dr,
+                                                             float* __restrict__ dw, float* __restrict__ db,
+                                                             size_t count, int k) {
+  __shared__ float red[4];
+  float acc[kMaxSims], accb = 0.f;
+#pragma unroll
+  for (int j = 0; j < kMaxSims; ++j) acc[j] = 0.f;
+  for (size_t i = threadIdx.x; i < count; i += 256) {
+    const float d = dr[i];
+    accb += d;
+#pragma unroll
+    for (int j = 0; j < kMaxSims; ++j)
+      if (j < k) acc[j] += d * sims[i * k + j];
+  }
+#pragma unroll
+  for (int j = 0; j < kMaxSims; ++j) {
+    if (j < k) {                                // k is the block's: no divergent barrier
+      const float s = block_sum_256(acc[j], red);
+      if (threadIdx.x == 0) dw[j] = s;
+    }
+  }
+  accb = block_sum_256(accb, red);
+  if (threadIdx.x == 0) db[0] = accb;
 }
 
 // MAP depths of the same field: y = A^-1 z.  One wavefront per image, [A | z] in LDS (row stride kMaxSp + 1 dwords: odd,
@@ -304,6 +385,15 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ var, const
     var[i] = __fsub_rn(var[i], __fmul_rn(lr, g[i]));
 }
 
+// projected gradient descent: sgd_kernel's step, then no lower than `floor`.  The comparison keeps a NaN a NaN.
+__global__ __launch_bounds__(256) void sgd_floor_kernel(float* __restrict__ var, const float* __restrict__ g, size_t count,
+                                                        float lr, float floor) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) {
+    const float v = __fsub_rn(var[i], __fmul_rn(lr, g[i]));
+    var[i] = v < floor ? floor : v;
+  }
+}
+
 }  // namespace a3d
 
 using namespace a3d;
@@ -337,21 +427,46 @@ int a3d_pair_similarity(int n, int h, int w, const float* x, int sp, const float
   return check_launch("pair_similarity");
 }
 
-int a3d_crf_loss(int n, int nsp, const float* z, const float* y, const float* r, const int32_t* left,
-                 const int32_t* right, int npairs, float eps, float* loss_per_image, float* loss_mean, float* dz,
-                 void* stream) {
-  A3D_CHECK_ARG(n > 0 && nsp > 0 && nsp <= kMaxSp && npairs > 0 && z && y && r && left && right && loss_per_image &&
-                    loss_mean && dz, "crf_loss: bad arguments (at most %d superpixels)", kMaxSp);
+// a3d_crf_loss (dr == nullptr) and a3dp_crf_loss_grad: the same two launches, the first one in its other instantiation
+static int crf_loss_launch(int n, int nsp, const float* z, const float* y, const float* r, const int32_t* left,
+                           const int32_t* right, int npairs, float eps, float* loss_per_image, float* loss_mean,
+                           float* dz, float* dr, void* stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
   const float fac0 = (float)pow(3.14159265358979323846, nsp / 2.0);
   clear_stale_error();
-  hipLaunchKernelGGL(crf_loss_kernel, dim3(n), dim3(64), 0, st, z, y, r, left, right, loss_per_image, dz, nsp, npairs,
-                     eps, fac0, 1.0f / (float)n);
+  hipLaunchKernelGGL(dr ? crf_loss_kernel<true> : crf_loss_kernel<false>, dim3(n), dim3(64), 0, st, z, y, r, left,
+                     right, loss_per_image, dz, dr, nsp, npairs, eps, fac0, 1.0f / (float)n);
   int rc = check_launch("crf_loss");
   if (rc != A3D_OK) return rc;
   clear_stale_error();
   hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(64), 0, st, loss_per_image, n, loss_mean);
   return check_launch("crf_loss_mean");
+}
+
+int a3d_crf_loss(int n, int nsp, const float* z, const float* y, const float* r, const int32_t* left,
+                 const int32_t* right, int npairs, float eps, float* loss_per_image, float* loss_mean, float* dz,
+                 void* stream) {
+  A3D_CHECK_ARG(n > 0 && nsp > 0 && nsp <= kMaxSp && npairs > 0 && z && y && r && left && right && loss_per_image &&
+                    loss_mean && dz, "crf_loss: bad arguments (at most %d superpixels)", kMaxSp);
+  return crf_loss_launch(n, nsp, z, y, r, left, right, npairs, eps, loss_per_image, loss_mean, dz, nullptr, stream);
+}
+
+int a3dp_crf_loss_grad(int n, int nsp, const float* z, const float* y, const float* r, const int32_t* left,
+                       const int32_t* right, int npairs, float eps, float* loss_per_image, float* loss_mean, float* dz,
+                       float* dr, void* stream) {
+  A3D_CHECK_ARG(n > 0 && nsp > 0 && nsp <= kMaxSp && npairs > 0 && z && y && r && left && right && loss_per_image &&
+                    loss_mean && dz && dr, "crf_loss_grad: bad arguments (at most %d superpixels)", kMaxSp);
+  return crf_loss_launch(n, nsp, z, y, r, left, right, npairs, eps, loss_per_image, loss_mean, dz, dr, stream);
+}
+
+int a3dp_pair_dense_bwd(int n, int npairs, int k, const float* sims, const float* dr, float* dw, float* db,
+                        void* stream) {
+  A3D_CHECK_ARG(n > 0 && npairs > 0 && k >= 1 && k <= kMaxSims && sims && dr && dw && db,
+                "pair_dense_bwd: bad arguments (1 .. %d similarities per pair)", kMaxSims);
+  clear_stale_error();
+  hipLaunchKernelGGL(pair_dense_bwd_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), sims, dr, dw, db,
+                     (size_t)n * (size_t)npairs, k);
+  return check_launch("pair_dense_bwd");
 }
 
 int a3d_crf_map(int n, int nsp, const float* z, const float* r, const int32_t* left, const int32_t* right, int npairs,
@@ -370,6 +485,14 @@ int a3d_sgd_apply(size_t count, float* var, const float* g, float lr, void* stre
   hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)std::min<size_t>((count + 255) / 256, 4096)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), var, g, count, lr);
   return check_launch("sgd");
+}
+
+int a3dp_sgd_apply_floor(size_t count, float* var, const float* g, float lr, float floor, void* stream) {
+  A3D_CHECK_ARG(count > 0 && var && g, "sgd_floor: bad arguments");
+  clear_stale_error();
+  hipLaunchKernelGGL(sgd_floor_kernel, dim3((unsigned)std::min<size_t>((count + 255) / 256, 4096)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), var, g, count, lr, floor);
+  return check_launch("sgd_floor");
 }
 
 }  // extern "C"

@@ -1242,14 +1242,22 @@ class DCNFReplica:
     superpixel pairs, CRF negative log-likelihood, gradient descent (0.1) on what receives a gradient.
 
     TF-1.3 semantics assumed (the oracle states the same, oracle/dcnf.py): scatter_nd_update has no gradient, so the CRF
-    matrix A is a constant for the optimizer — the pairwise dense layer never moves and only the unary stack trains."""
+    matrix A is a constant for the optimizer — the pairwise dense layer never moves and only the unary stack trains.
+
+    train_pairwise (NON-REFERENCE, --train-pairwise): the pairwise dense layer learns too, as in Liu et al. 2015
+    (eq. 9-14).  The loss launch also writes d loss / d r through A^-1 and log|A| (ops.crf_loss_grad: the same loss and
+    dz bits), ops.pair_dense_bwd takes it to the layer's kernel and bias, and the `pairwise` group descends at its
+    learning rate under the projection onto kernel, bias >= 0 (ops.sgd_apply_floor), which construction applies once
+    to the initial values.  The unary group's step is the bits it would be without the flag, given the same pairwise
+    values.  Off (the default), no launch and no buffer of the step differs from the reference form."""
     uses_dropout = False
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, global_step=0, reducer=None,
-                 precision='fp32'):
+                 precision='fp32', train_pairwise=False):
         self.B = batchsize
         self.device = dev = torch.device(device)
         self.reducer = reducer
+        self.train_pairwise = bool(train_pairwise)
         self.global_step = global_step
         self.unary = DCNFUnary(batchsize, dev, params=params, seed=seed, precision=precision)
         self.rows, self.cols = DCNF_IMG_H // DCNF_SP, DCNF_IMG_W // DCNF_SP
@@ -1269,17 +1277,22 @@ class DCNFReplica:
         for n in pshapes:
             self.pair_group.view(self.pair_group.var, n).copy_(
                 torch.from_numpy(np.ascontiguousarray(pw[n], np.float32)))
+        if self.train_pairwise:
+            ops.sgd_apply_floor(self.pair_group.var, self.pair_group.grad, 0.0, 0.0)      # beta >= 0 from the start
         self.groups = collections.OrderedDict([('unary', self.unary.group), ('pairwise', self.pair_group)])
         self.depths240 = torch.empty((batchsize, DCNF_IMG_H, DCNF_IMG_W, 1), device=dev)
         self.hist = torch.empty((batchsize, self.nsp, 256), device=dev)
         self.y = torch.empty((batchsize, self.nsp, 1), device=dev)
         self.output = torch.empty((batchsize, DCNF_IMG_H, DCNF_IMG_W, 1), device=dev)
-        self.sims = self.r = self.loss = self.loss_per_image = self.dz = None
+        self.sims = self.r = self.loss = self.loss_per_image = self.dz = self.dr = None
         self.crf = torch.empty((batchsize, self.nsp), device=dev)                          # predict(): the MAP depths
         self.status = torch.empty((batchsize,), dtype=torch.int32, device=dev)
 
     def pair_var(self, name):
         return self.pair_group.view(self.pair_group.var, DCNF_PAIR_PREFIX + name)
+
+    def pair_grad(self, name):
+        return self.pair_group.view(self.pair_group.grad, DCNF_PAIR_PREFIX + name)
 
     def forward(self, images, depths):
         """z, r and the loss; leaves d loss / d z in self.dz."""
@@ -1294,8 +1307,11 @@ class DCNFReplica:
         self.sims, self.r = ops.pair_similarity(u.resized, DCNF_SP, self.hist, self.left, self.right,
                                                 self.pair_var('kernel'), self.pair_var('bias'), DCNF_GAMMA)  # :115-127
         ops.superpixel_mean(self.depths240, DCNF_SP, self.y)                              # :131-132
-        self.loss, self.loss_per_image, self.dz = ops.crf_loss(u.z.view(self.B, self.nsp), self.y.view(self.B, self.nsp),
-                                                               self.r, self.left, self.right, DCNF_EPSILON)  # :129-177
+        crf_args = (u.z.view(self.B, self.nsp), self.y.view(self.B, self.nsp), self.r, self.left, self.right, DCNF_EPSILON)
+        if self.train_pairwise:                                                           # one launch, not two
+            self.loss, self.loss_per_image, self.dz, self.dr = ops.crf_loss_grad(*crf_args)
+        else:
+            self.loss, self.loss_per_image, self.dz = ops.crf_loss(*crf_args)             # :129-177
         return self.loss
 
     def predict(self, images, n=None):
@@ -1336,13 +1352,19 @@ class DCNFReplica:
     def step(self, images, depths, keep_mask=None):
         self.forward(images, depths)
         self.unary.backward(self.dz)
+        if self.train_pairwise:
+            ops.pair_dense_bwd(self.sims, self.dr, self.pair_grad('kernel'), self.pair_grad('bias'))
         red = self.reducer
         scale = 1.0
         if red is not None:
             red.start(self.unary.group.grad)
+            if self.train_pairwise:
+                red.start(self.pair_group.grad)
             red.finish()
             scale = 1.0 / red.world_size
         self.unary.group.apply_sgd(scale)                                                 # :198-200
+        if self.train_pairwise:
+            ops.sgd_apply_floor(self.pair_group.var, self.pair_group.grad, self.pair_group.lr * scale, 0.0)
         self.global_step += 1
         return {'mean_loss': self.loss}
 
@@ -1559,12 +1581,14 @@ class _DistributedConvolutionalNeuralFields:
     seed = 3000
     precision = 'fp32'
     beta2 = None         # accepted for symmetry with msdn; gradient descent has no beta
+    train_pairwise = False   # NON-REFERENCE, --train-pairwise: the pairwise dense layer learns, >= 0 (see DCNFReplica)
 
     def __call__(self, images, depths, train=True):
         assert images.pipeline is depths.pipeline, 'inputs and targets must come from the same data.inputs() call'
         self.train = train
         replica = DCNFReplica(images.pipeline.B, device=torch.device('cuda', torch.cuda.current_device()),
-                              seed=self.seed, reducer=self.reducer, precision=self.precision)
+                              seed=self.seed, reducer=self.reducer, precision=self.precision,
+                              train_pairwise=self.train_pairwise and train)
         if self.reducer is not None:
             for g in replica.groups.values():
                 self.reducer.broadcast(g.var)

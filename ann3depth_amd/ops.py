@@ -625,6 +625,20 @@ def sgd_apply(var, g, lr):
     check(_lib.load().a3d_sgd_apply(var.numel(), _ptr(var), _ptr(g), lr, _stream()), 'a3d_sgd_apply')
 
 
+def sgd_apply_floor(var, g, lr, floor=0.0):
+    """NON-REFERENCE (a3dp_sgd_apply_floor): sgd_apply's step, then no element below `floor`; a NaN stays a NaN.  var, g:
+    float32 tensors of one size."""
+    if var.numel() == 0 or g.numel() != var.numel():
+        raise ValueError(f'sgd_apply_floor: var {tuple(var.shape)} and g {tuple(g.shape)} must hold the same number of values')
+    if var.dtype != torch.float32 or g.dtype != torch.float32:
+        raise TypeError('sgd_apply_floor: var, g float32')
+    if not (var.is_contiguous() and g.is_contiguous()):
+        raise ValueError('sgd_apply_floor: contiguous tensors only')
+    if g.device != var.device:
+        raise ValueError('sgd_apply_floor: all tensors on one device')
+    check(_lib.load().a3dp_sgd_apply_floor(var.numel(), _ptr(var), _ptr(g), lr, floor, _stream()), 'a3dp_sgd_apply_floor')
+
+
 def superpixel_mean(x, sp, out=None):
     """[n,h,w,c] -> [n,(h/sp)*(w/sp),c] block means (src/models.py:110,132)."""
     n, h, w, c = x.shape
@@ -690,6 +704,53 @@ def crf_loss(z, y, r, left, right, eps=1e-7):
     check(_lib.load().a3d_crf_loss(n, nsp, _ptr(z), _ptr(y), _ptr(r), _ptr(left), _ptr(right), left.numel(), eps,
                                    _ptr(per), _ptr(mean), _ptr(dz), _stream()), 'a3d_crf_loss')
     return mean, per, dz
+
+
+def crf_loss_grad(z, y, r, left, right, eps=1e-7):
+    """NON-REFERENCE (a3dp_crf_loss_grad): crf_loss with the CRF matrix no longer a constant: returns (mean loss [1],
+    per-image loss [n], d mean / d z [n,P], d mean / d r [n,Q]), the first three the bits crf_loss returns.  A pair index
+    outside [0, P) turns all of it into NaN; a pair that a later pair overwrote has a gradient of +0."""
+    if z.dim() != 2 or r.dim() != 2:
+        raise ValueError(f'crf_loss_grad: z {tuple(z.shape)} and r {tuple(r.shape)} must be [n, P] and [n, Q]')
+    n, nsp = z.shape[0], z.shape[1]
+    if (n == 0 or tuple(y.shape) != (n, nsp) or r.shape[0] != n or left.numel() == 0 or r.shape[1] != left.numel()
+            or left.numel() != right.numel()):
+        raise ValueError(f'crf_loss_grad: z {tuple(z.shape)}, y {tuple(y.shape)}, r {tuple(r.shape)}, {left.numel()} / '
+                         f'{right.numel()} pair indices')
+    if (z.dtype != torch.float32 or y.dtype != torch.float32 or r.dtype != torch.float32 or left.dtype != torch.int32
+            or right.dtype != torch.int32):
+        raise TypeError('crf_loss_grad: z, y, r float32; left, right int32')
+    if not all(t.is_contiguous() for t in (z, y, r, left, right)):
+        raise ValueError('crf_loss_grad: contiguous tensors only')
+    if any(t.device != z.device for t in (y, r, left, right)):
+        raise ValueError('crf_loss_grad: all tensors on one device')
+    per = torch.empty((n,), dtype=torch.float32, device=z.device)
+    mean = torch.empty((1,), dtype=torch.float32, device=z.device)
+    dz = torch.empty((n, nsp), dtype=torch.float32, device=z.device)
+    dr = torch.empty_like(r)
+    check(_lib.load().a3dp_crf_loss_grad(n, nsp, _ptr(z), _ptr(y), _ptr(r), _ptr(left), _ptr(right), left.numel(), eps,
+                                         _ptr(per), _ptr(mean), _ptr(dz), _ptr(dr), _stream()), 'a3dp_crf_loss_grad')
+    return mean, per, dz, dr
+
+
+def pair_dense_bwd(sims, dr, dw, db):
+    """NON-REFERENCE (a3dp_pair_dense_bwd): backward of the pairwise dense layer K -> 1.  sims [n,Q,K], dr [n,Q] float32 ->
+    dw (K values) = sum dr * sims, db (1 value) = sum dr, written in place (views of a gradient buffer); 1 <= K <= 8.  One
+    block, a fixed order: the same bits on every run."""
+    if sims.dim() != 3 or dr.dim() != 2 or tuple(sims.shape[:2]) != tuple(dr.shape) or dr.numel() == 0:
+        raise ValueError(f'pair_dense_bwd: sims {tuple(sims.shape)} and dr {tuple(dr.shape)} must be [n, Q, K] and [n, Q]')
+    k = sims.shape[2]
+    if not 1 <= k <= 8 or dw.numel() != k or db.numel() != 1:
+        raise ValueError(f'pair_dense_bwd: {k} similarities per pair (1 .. 8), dw {tuple(dw.shape)}, db {tuple(db.shape)}')
+    if any(t.dtype != torch.float32 for t in (sims, dr, dw, db)):
+        raise TypeError('pair_dense_bwd: sims, dr, dw, db float32')
+    if not all(t.is_contiguous() for t in (sims, dr, dw, db)):
+        raise ValueError('pair_dense_bwd: contiguous tensors only')
+    if any(t.device != sims.device for t in (dr, dw, db)):
+        raise ValueError('pair_dense_bwd: all tensors on one device')
+    check(_lib.load().a3dp_pair_dense_bwd(dr.shape[0], dr.shape[1], k, _ptr(sims), _ptr(dr), _ptr(dw), _ptr(db), _stream()),
+          'a3dp_pair_dense_bwd')
+    return dw, db
 
 
 def crf_map(z, r, left, right, y=None, status=None):

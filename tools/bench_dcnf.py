@@ -1,7 +1,8 @@
 """BASELINE config 4: DCNF unary conv stack, batch 16 (768 patches of 100x100x3), one MI355X.
 Times the forward (resize -> patches -> 5 conv / 3 pool / 3 dense), the unary backward from a synthetic dz, and the
-whole `models.dcnf` train step (+ pairwise part, CRF loss, gradient descent).
-    python tools/bench_dcnf.py [batch] > gpurun_out/dcnf.json"""
+whole `models.dcnf` train step (+ pairwise part, CRF loss, gradient descent).  --train-pairwise: the step that also
+learns the pairwise dense layer (NON-REFERENCE); `crf_loss_ms` is the loss launch alone in the form the step uses.
+    python tools/bench_dcnf.py [batch] [--train-pairwise] > dcnf.json"""
 import json
 import os
 import sys
@@ -10,13 +11,15 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from ann3depth_amd import models  # noqa: E402
+from ann3depth_amd import models, ops  # noqa: E402
 
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
+PAIRWISE = '--train-pairwise' in sys.argv[1:]
+argv = [a for a in sys.argv[1:] if a != '--train-pairwise']
+B = int(argv[0]) if argv else 16
 rng = np.random.default_rng(1000)
 img = torch.from_numpy((rng.integers(0, 256, (B, 480, 640, 3)) / 255).astype(np.float32)).cuda()
 dep = torch.from_numpy(rng.random((B, 55, 74, 1)).astype(np.float32)).cuda()
-rep = models.DCNFReplica(B)
+rep = models.DCNFReplica(B, train_pairwise=True) if PAIRWISE else models.DCNFReplica(B)
 net = rep.unary
 dz = torch.randn((net.P, 1), device='cuda')
 
@@ -37,11 +40,13 @@ t_fwd = timeit(lambda: net.forward(img))
 t_bwd = timeit(lambda: net.backward(dz))
 t_step = timeit(lambda: rep.step(img, dep))
 t_crf = timeit(lambda: rep.forward_crf(dep))
+loss_args = (net.z.view(B, rep.nsp), rep.y.view(B, rep.nsp), rep.r, rep.left, rep.right, models.DCNF_EPSILON)
+t_loss = timeit(lambda: (ops.crf_loss_grad if PAIRWISE else ops.crf_loss)(*loss_args), reps=50)
 gflop_patch = 2.672          # forward GFLOP per patch
 fwd_tf = gflop_patch * net.P / t_fwd           # GFLOP / ms = TFLOP/s
 print(json.dumps({'workload': f'DCNF unary, batch {B} -> {net.P} patches 100x100x3', 'forward_ms': round(t_fwd, 3),
                   'forward_images_per_s': round(B / t_fwd * 1e3, 1), 'forward_tflops': round(fwd_tf, 1),
                   'backward_ms': round(t_bwd, 3), 'dtype': 'f32',
                   'train_step_ms': round(t_step, 3), 'train_step_images_per_s': round(B / t_step * 1e3, 1),
-                  'pairwise_and_crf_loss_ms': round(t_crf, 3),
+                  'pairwise_and_crf_loss_ms': round(t_crf, 3), 'crf_loss_ms': round(t_loss, 4), 'train_pairwise': PAIRWISE,
                   'fwd_bwd_images_per_s': round(B / (t_fwd + t_bwd) * 1e3, 1)}))
