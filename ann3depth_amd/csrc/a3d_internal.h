@@ -34,9 +34,37 @@ inline unsigned grid_for(size_t total, int per_block = 256, unsigned cap = 8192)
   return (unsigned)std::min<size_t>(std::max<size_t>(g, 1), cap);
 }
 
-// ---- implicit-GEMM front end: the planner (igemm_plan.h, igemm_plan.cc) and the launches (igemm_host.hip) ----
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ---- implicit-GEMM launch layer (igemm_launch.hip) under the front end (igemm_host.hip); the planner: igemm_plan.h, igemm_plan.cc ----
 struct IgemmParams;
 int launch_igemm(int mode, const GemmPlan& plan, int avec, int bvec, IgemmParams& p, void* ws, hipStream_t st);
+int take_second_output(IgemmParams& p, const a3d_second_output* o);      // a3d_second_output -> the host-only fields of IgemmParams
+
+// opt-in launch timing (a3d_timing_*)
+struct TimingSlot {
+  hipEvent_t start, stop;
+  a3d_timing_record rec;
+};
+bool timing_wanted(const a3d_timing_record& r);
+int timing_begin(TimingSlot& slot, hipStream_t st);
+void timing_end(TimingSlot& slot, hipStream_t st);
+// The record of a launch that computes an m x n x k GEMM unsplit; callers overwrite what differs (splitk, flops).
+a3d_timing_record timing_record(int mode, int prec, int bm, int bn, int waves_m, int nwaves, int bk, int avec, int bvec, int lds_dma,
+                                int m, int n, int k);
+// Runs launch() on `st`, between two events when the timing list wants launches like `rec`; returns launch()'s code.  If
+// the events cannot be had, that error is returned and launch() is not called: nothing is enqueued.
+template <typename Launch>
+int timed_launch(const a3d_timing_record& rec, hipStream_t st, Launch&& launch) {
+  if (!timing_wanted(rec)) return launch();
+  TimingSlot slot{};
+  slot.rec = rec;
+  int rc = timing_begin(slot, st);
+  if (rc != A3D_OK) return rc;
+  rc = launch();
+  timing_end(slot, st);
+  return rc;
+}
 
 // ---- weight-streaming dense kernels for batches of at most 64 rows (dense.hip) ----
 bool dense_dw_applicable(int m, int k, int n);
@@ -80,7 +108,7 @@ int fewch16_bwd_filter(const a3d_conv_desc* d, const float* x, bool pooled, cons
                        const uint8_t* argmax, int ld_arg, float* dw, float* db, void* ws, hipStream_t st);
 
 // ---- few-channel forward convolution straight from L2 (conv3.hip) ----
-bool conv3_applicable(const a3d_conv_desc* d, const void* x);
+bool conv3_applicable(const a3d_conv_desc* d, unsigned x_off);      // x_off: x's address & 15
 size_t conv3_ws_bytes(const a3d_conv_desc* d);
 int conv3_pack(const a3d_conv_desc* d, const float* w, float* wp, hipStream_t st);
 int conv3_fwd(const a3d_conv_desc* d, const float* x, const float* w, const float* bias, float* y, int act, int pool,

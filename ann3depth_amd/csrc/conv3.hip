@@ -381,13 +381,13 @@ static Conv3Shape conv3_shape(const a3d_conv_desc* d) {
   return s;
 }
 
-bool conv3_applicable(const a3d_conv_desc* d, const void* x) {
+bool conv3_applicable(const a3d_conv_desc* d, unsigned x_off) {
   static const bool off = tune_int("A3D_NO_CONV3", 0) != 0;      // A/B aid (tuning processes only)
   if (off) return false;
   if (d->precision != A3D_PREC_F32 || d->c > 4 || d->pad_t || d->pad_l || d->ldx != d->c) return false;
   if (d->storage & ~A3D_STORE_Y_BF16) return false;
   if (d->k < 33) return false;                          // (one-output-channel layers have their own stencil kernel)
-  if (x && (reinterpret_cast<uintptr_t>(x) & 3)) return false;
+  if (x_off & 3) return false;
   if ((d->ho - 1) * d->stride + d->r > d->h || (d->wo - 1) * d->stride + d->s > d->w) return false;   // VALID geometry
   if ((double)d->n * d->h * d->w * d->c * 4.0 >= 2147483647.0) return false;     // 31-bit byte offsets into the image
   return true;

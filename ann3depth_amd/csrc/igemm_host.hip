@@ -1,11 +1,7 @@
-// igemm_host.hip — dispatch of a planned GEMM (the plans: igemm_plan.cc), split-K reduction, bias-gradient column sums,
-// opt-in launch timing, and the conv2d / dense entry points of include/a3d.h.
+// igemm_host.hip — the conv2d / dense entry points of include/a3d.h: which kernel takes a call (the stencil, conv3 / conv3b, the
+// bf16 image and window-run forms with their filter repacks, fewch / fewch16, the LDS-DMA kernel or the generic GEMM), the workspace
+// that takes, and the kernel's parameters.  The plans: igemm_plan.cc; the launches: igemm_launch.hip.
 #include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <mutex>
-#include <vector>
 
 #include "a3d_internal.h"
 #include "igemm.h"
@@ -13,357 +9,13 @@
 
 namespace a3d {
 
-int launch_igemm_mode0(int cfg, int avec, int bvec, IgemmParams& p, unsigned grid, hipStream_t st);
-int launch_igemm_mode1(int cfg, int avec, int bvec, IgemmParams& p, unsigned grid, hipStream_t st);
-int launch_igemm_mode2(int cfg, int avec, int bvec, IgemmParams& p, unsigned grid, hipStream_t st);
-int launch_igemm_bf16(int mode, int bn, bool x3, IgemmParams& p, unsigned grid, hipStream_t st);   // p.a16/b16/c16 pick the storage variant
-int launch_fixup_mode0(int cfg, IgemmParams& p, unsigned tiles, unsigned nblk, hipStream_t st);
-int launch_fixup_mode1(int cfg, IgemmParams& p, unsigned tiles, unsigned nblk, hipStream_t st);
-int launch_fixup_mode2(int cfg, IgemmParams& p, unsigned tiles, unsigned nblk, hipStream_t st);
 int launch_igemm_multi_bwd_d(int avec, int bvec, IgemmMulti& ps, unsigned grid_x, unsigned count, hipStream_t st);
 int launch_igemm_bf16_multi_bwd_d(int bn, IgemmMulti& ps, unsigned grid_x, unsigned count, hipStream_t st);
-int launch_igemm_ring(int mode, int cfg, IgemmParams& p, unsigned grid, hipStream_t st);
 
-#ifdef A3D_STAMPS
-static unsigned long long* g_stamps = nullptr;
-static unsigned g_stamp_grid = 0;
-static const size_t kStampBytes = (size_t)8 << 20;
-#endif
-
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// The switches read below (A3D_PLAN_LOG, A3D_DBG, A3D_FEWCH, ...) and the planner's (A3D_FORCE_*, A3D_BF16_BN, A3D_RING*) all go
-// through tune_int() (igemm_plan.h, capi.cc): the environment is consulted on every launch ONLY in a process started with
-// A3D_TUNING=1, as the sweep and fuzz tools do; otherwise nothing reads it, and plans are cached per problem (plan_gemm).
-
-// ---- opt-in launch timing (a3d_timing_*) ----
-struct TimingSlot {
-  hipEvent_t start, stop;
-  a3d_timing_record rec;
-};
-static std::mutex g_timing_mu;
-static bool g_timing_on = false;
-static bool g_timing_only = false;          // a3d_timing_select: bracket only launches of one kernel
-static a3d_timing_record g_timing_like{};
-static std::vector<TimingSlot> g_timing;
-
-// Is this launch to be bracketed?  `r` names the kernel about to be launched.
-static bool timing_wanted(const a3d_timing_record& r) {
-  std::lock_guard<std::mutex> lk(g_timing_mu);
-  if (!g_timing_on) return false;
-  if (!g_timing_only) return true;
-  const a3d_timing_record& l = g_timing_like;
-  return r.mode == l.mode && r.prec == l.prec && r.bm == l.bm && r.bn == l.bn && r.waves_m == l.waves_m &&
-         r.nwaves == l.nwaves && r.bk == l.bk && r.avec == l.avec && r.bvec == l.bvec && r.lds_dma == l.lds_dma;
-}
-static int timing_begin(TimingSlot& slot, hipStream_t st) {
-  if (hipEventCreate(&slot.start) != hipSuccess || hipEventCreate(&slot.stop) != hipSuccess)
-    return set_error(A3D_ELAUNCH, "timing: hipEventCreate failed");
-  (void)hipEventRecord(slot.start, st);
-  return A3D_OK;
-}
-static void timing_end(TimingSlot& slot, hipStream_t st) {
-  (void)hipEventRecord(slot.stop, st);
-  std::lock_guard<std::mutex> lk(g_timing_mu);
-  g_timing.push_back(slot);
-}
-// The record of a launch that computes an m x n x k GEMM unsplit; callers overwrite what differs (splitk, flops).
-static a3d_timing_record timing_record(int mode, int prec, int bm, int bn, int waves_m, int nwaves, int bk, int avec, int bvec,
-                                       int lds_dma, int m, int n, int k) {
-  a3d_timing_record r{};
-  r.mode = mode; r.prec = prec; r.bm = bm; r.bn = bn; r.waves_m = waves_m; r.nwaves = nwaves; r.bk = bk;
-  r.avec = avec; r.bvec = bvec; r.lds_dma = lds_dma; r.splitk = 1; r.m = m; r.n = n; r.k = k; r.ms = 0.f;
-  r.flops = 2.0 * m * n * k;
-  return r;
-}
-// Runs launch() on `st`, between two events when the timing list wants launches like `rec`; returns launch()'s code.  If
-// the events cannot be had, that error is returned and launch() is not called: nothing is enqueued.
-template <typename Launch>
-static int timed_launch(const a3d_timing_record& rec, hipStream_t st, Launch&& launch) {
-  if (!timing_wanted(rec)) return launch();
-  TimingSlot slot{};
-  slot.rec = rec;
-  int rc = timing_begin(slot, st);
-  if (rc != A3D_OK) return rc;
-  rc = launch();
-  timing_end(slot, st);
-  return rc;
-}
-
-// Sums the split-K slabs in slab order (deterministic) and applies the epilogue.  Slab reads are issued four at a
-// time into independent registers: a thread's serial chain of `splitk` dependent loads was the cost of this kernel.
-template <typename V>
-__device__ __forceinline__ V slab_sum(const V* ws, size_t slab, int splitk, size_t i) {
-  V s = V(0.f);
-  int z = 0;
-  for (; z + 8 <= splitk; z += 8) {       // eight slabs in flight, added in slab order
-    V t[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) t[u] = ws[(size_t)(z + u) * slab + i];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += t[u];
-  }
-  if (z + 4 <= splitk) {
-    const V a = ws[(size_t)z * slab + i], b = ws[(size_t)(z + 1) * slab + i];
-    const V c = ws[(size_t)(z + 2) * slab + i], d = ws[(size_t)(z + 3) * slab + i];
-    s += a; s += b; s += c; s += d;
-    z += 4;
-  }
-  for (; z < splitk; ++z) s += ws[(size_t)z * slab + i];
-  return s;
-}
-
-// C position (in units of V) of slab position i when the slabs' rows are padded window runs (ReduceParams::row_rlp), or
-// SIZE_MAX for a pad row; nv = V's per row
-__device__ __forceinline__ size_t unpadded_pos(size_t i, int nv, int rl, int rlp) {
-  if (rlp == 0) return i;
-  const size_t row = i / (size_t)nv, c = i - row * (size_t)nv;
-  const size_t rr = row / (size_t)rlp, q = row - rr * (size_t)rlp;
-  return q < (size_t)rl ? (rr * (size_t)rl + q) * (size_t)nv + c : SIZE_MAX;
-}
-template <typename V>
-__device__ __forceinline__ void reduce_wide(const V* src, V* dst, size_t slab, size_t count, int splitk, size_t first, V* lds, int nv,
-                                            int rl, int rlp);
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const ReduceParams p) {
-  const size_t total = (size_t)p.M * p.N;
-  unsigned nblk = gridDim.x;
-  if (p.dbias_splits > 0) {      // up to 256 rows of column-sum partials: blocks of their own, sixteen threads per column
-    __shared__ float lds[256];
-    if (blockIdx.x >= p.dbias_block0) {
-      reduce_wide<float>(p.dbias_ws, p.dbias_out, (size_t)p.N, (size_t)p.N, p.dbias_splits, (size_t)(blockIdx.x - p.dbias_block0) * 16, lds,
-                         0, 0, 0);
-      return;
-    }
-    nblk = p.dbias_block0;
-  } else if (p.dbias_out) {       // N sums of `splitk` values: the grid's first threads do them on the side
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < (size_t)p.N; i += (size_t)gridDim.x * 256)
-      p.dbias_out[i] = slab_sum<float>(p.dbias_ws, (size_t)p.N, p.splitk, i);
-  }
-  if (p.vec4) {   // plain sum of 16-byte columns: bwd-filter slabs (no epilogue, contiguous output)
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const size_t nv = total / 4;
-    const f4* ws4 = reinterpret_cast<const f4*>(p.ws);
-    const size_t slab4 = p.slab / 4;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nv; i += (size_t)nblk * 256) {
-      const size_t o = unpadded_pos(i, p.N / 4, p.row_rl, p.row_rlp);
-      if (o != SIZE_MAX) reinterpret_cast<f4*>(p.C)[o] = slab_sum<f4>(ws4, slab4, p.splitk, i);
-    }
-    return;
-  }
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)nblk * 256) {
-    float s = slab_sum<float>(p.ws, p.slab, p.splitk, i);
-    const int row = (int)(i / p.N), col = (int)(i - (size_t)row * p.N);
-    const size_t o = remap_row(row, p.mode == MODE_BWD_D ? p.sub_step : 1, p.sub_ph, p.sub_pw, p.outW, p.outHW, p.div_phw,
-                               p.div_pw) * p.ldc + col;
-    if (p.mode == MODE_FWD) {
-      if (p.bias) s += p.bias[col];
-      if (p.act == EPI_RELU) s = fmaxf(s, 0.f);
-      else if (p.act == EPI_SIGMOID) s = 1.f / (1.f + expf(-s));
-      if (p.keep) s = p.keep[i] ? s * p.mask_scale : 0.f;
-    } else if (p.mode == MODE_BWD_D) {
-      if (p.mask) {
-        const float y = p.c16 ? (float)reinterpret_cast<const __bf16*>(p.mask)[o] : p.mask[o];
-        s = apply_act_grad(s, y, p.mask_act, p.mask_scale);
-      }
-    }
-    if (p.c_cols == 0 || col < p.c_cols) {
-      if (p.c16) reinterpret_cast<__bf16*>(p.C)[o] = (__bf16)s;
-      else p.C[o] = s;
-    }
-    if (p.C2 && col < p.cols2) {
-      const size_t o2 = ((size_t)row * p.ld2 + col) * p.step2 + p.off2;
-      if (p.c2_16) static_cast<__bf16*>(p.C2)[o2] = (__bf16)(p.c16 ? (float)(__bf16)s : s);
-      else static_cast<float*>(p.C2)[o2] = p.c16 ? (float)(__bf16)s : s;
-    }
-  }
-}
-
-// the second output of a launch that had no reduction stage to write it: a copy of the finished tensor
-__global__ __launch_bounds__(256) void second_output_kernel(const void* C, int c16, int M, int ldc, void* C2, int ld2, int step2, int off2,
-                                                            int c2_16, int cols2) {
-  const size_t total = (size_t)M * cols2;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int row = (int)(i / cols2), col = (int)(i - (size_t)row * cols2);
-    const size_t o = (size_t)row * ldc + col;
-    const float s = c16 ? (float)static_cast<const __bf16*>(C)[o] : static_cast<const float*>(C)[o];
-    const size_t o2 = ((size_t)row * ld2 + col) * step2 + off2;
-    if (c2_16) static_cast<__bf16*>(C2)[o2] = (__bf16)s;
-    else static_cast<float*>(C2)[o2] = s;
-  }
-}
-
-// Many slabs, few outputs (conv2d_0's bwd-filter: 128 slabs of 36 k floats, and its 96 bias sums): one thread per output
-// means 35 blocks on 256 CUs, each walking 128 dependent-latency rounds — 28 us for 18 MB.  Here sixteen threads share
-// an output: thread `part` adds its contiguous sixteenth of the slabs in slab order, the sixteen partial sums meet in
-// LDS and are added in part order.  A fixed order, so still the same bits on every run (a different order than the
-// one-thread sum above: a launch uses one or the other by shape alone, never by timing).
-template <typename V>
-__device__ __forceinline__ void reduce_wide(const V* src, V* dst, size_t slab, size_t count, int splitk, size_t first,
-                                            V* lds, int nv, int rl, int rlp) {
-  const int tid = threadIdx.x, out = tid & 15, part = tid >> 4;
-  const size_t i = first + out;
-  const int per = (splitk + 15) / 16, z0 = part * per, z1 = min(splitk, z0 + per);
-  V s = V(0.f);
-  if (i < count) {
-    int z = z0;
-    for (; z + 4 <= z1; z += 4) {
-      const V a = src[(size_t)z * slab + i], b = src[(size_t)(z + 1) * slab + i];
-      const V c = src[(size_t)(z + 2) * slab + i], d = src[(size_t)(z + 3) * slab + i];
-      s += a; s += b; s += c; s += d;
-    }
-    for (; z < z1; ++z) s += src[(size_t)z * slab + i];
-  }
-  lds[part * 16 + out] = s;
-  __syncthreads();
-  if (part == 0 && i < count) {
-    V t = lds[out];
-#pragma unroll
-    for (int q = 1; q < 16; ++q) t += lds[q * 16 + out];
-    const size_t o = unpadded_pos(i, nv, rl, rlp);
-    if (o != SIZE_MAX) dst[o] = t;
-  }
-}
-__global__ __launch_bounds__(256) void splitk_reduce_wide_kernel(const ReduceParams p, unsigned blocks_c) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  __shared__ f4 lds[256];
-  if (blockIdx.x < blocks_c)
-    reduce_wide<f4>(reinterpret_cast<const f4*>(p.ws), reinterpret_cast<f4*>(p.C), p.slab / 4, (size_t)p.M * p.N / 4,
-                    p.splitk, (size_t)blockIdx.x * 16, lds, p.N / 4, p.row_rl, p.row_rlp);
-  else
-    reduce_wide<float>(p.dbias_ws, p.dbias_out, (size_t)p.N, (size_t)p.N, p.dbias_splits > 0 ? p.dbias_splits : p.splitk, (size_t)(blockIdx.x - blocks_c) * 16,
-                       reinterpret_cast<float*>(lds), 0, 0, 0);
-}
-
-int launch_splitk_reduce(const ReduceParams& r, hipStream_t st) {
-  const size_t total = (size_t)r.M * r.N;
-  clear_stale_error();
-  if (r.vec4 && r.splitk >= 16 && total / 4 <= (size_t)1 << 16) {
-    const unsigned blocks_c = (unsigned)((total / 4 + 15) / 16), blocks_b = r.dbias_out ? (unsigned)((r.N + 15) / 16) : 0u;
-    hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3(blocks_c + blocks_b), dim3(256), 0, st, r, blocks_c);
-    return check_launch("splitk_reduce_wide");
-  }
-  const unsigned g = (unsigned)std::min<size_t>(((r.vec4 ? total / 4 : total) + 255) / 256, 2048);
-  ReduceParams rr = r;
-  rr.dbias_block0 = g;
-  const unsigned gb = (r.dbias_out && r.dbias_splits > 0) ? (unsigned)((r.N + 15) / 16) : 0u;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(g + gb), dim3(256), 0, st, rr);
-  return check_launch("splitk_reduce");
-}
-
-int launch_igemm(int mode, const GemmPlan& plan, int avec, int bvec, IgemmParams& p, void* ws, hipStream_t st) {
-  if (mode == MODE_BWD_D && p.stride != 1)      // strided bwd-data always arrives as stride-1 parity classes
-    return set_error(A3D_EINVAL, "igemm: bwd-data launches are stride-1 problems");
-  p.splitk = plan.splitk;
-  p.ktiles_per_split = plan.ktiles_per_split;
-  p.tiles_m = plan.tiles_m;
-  p.tiles_n = plan.tiles_n;
-  p.slab = (size_t)p.M * p.N;
-  float* final_c = p.C;
-  float* final_dbias = p.dbias;
-  if (plan.splitk > 1) {
-    if (!ws) return set_error(A3D_EWORKSPACE, "igemm: split-K needs a workspace");
-    p.C = static_cast<float*>(ws);
-    if (p.dbias) p.dbias = static_cast<float*>(ws) + (size_t)plan.splitk * p.slab;   // [splitk][N] after the C slabs
-  }
-  unsigned grid = (unsigned)((long)plan.tiles_m * plan.tiles_n * plan.splitk);
-  if (plan.streamk > 0) {
-    if (!ws) return set_error(A3D_EWORKSPACE, "igemm: stream-K needs a workspace");
-    const size_t tile_elems = (size_t)kCfgs[plan.cfg].bm * kCfgs[plan.cfg].bn;
-    p.streamk = 1;
-    p.sk_ws = static_cast<float*>(ws);
-    p.sk_bias = p.sk_ws + (size_t)2 * plan.streamk * tile_elems;
-    p.div_nk = make_fastdiv((uint32_t)std::max(1, (p.K + 31) / 32));
-    grid = (unsigned)plan.streamk;
-  }
-  int rc;
-#ifdef A3D_STAMPS
-  if (!g_stamps) (void)hipMalloc(&g_stamps, kStampBytes);
-  (void)hipMemsetAsync(g_stamps, 0, kStampBytes, st);
-  p.stamps = grid * 8ull * 16 * 8 <= kStampBytes ? g_stamps : nullptr;
-  g_stamp_grid = grid;
-#endif
-  p.dbg = tune_int("A3D_DBG", 0);
-  static const bool plan_log = tune_int("A3D_PLAN_LOG", 0) != 0;       // tuning aid: one line per launch on stderr
-  if (plan_log)
-    fprintf(stderr, "a3d plan: mode %d M %d N %d K %d -> %s %d (%dx%d) splitk %d streamk %d grid %u\n", mode, p.M, p.N, p.K,
-            plan.ring ? "ring" : "cfg", plan.ring ? plan.ring - 1 : plan.cfg, plan.ring ? kRingCfgs[plan.ring - 1].bm : kCfgs[plan.cfg].bm,
-            plan.ring ? kRingCfgs[plan.ring - 1].bn : kCfgs[plan.cfg].bn, plan.splitk, plan.streamk, grid);
-  a3d_timing_record rec;
-  if (plan.ring) {                                          // lds_dma 3: igemm_ring_kernel
-    const RingTile& t = kRingCfgs[plan.ring - 1];
-    rec = timing_record(mode, plan.prec, t.bm, t.bn, 0, 8, 64, avec, bvec, 3, p.M, p.N, p.K);
-  } else if (plan.prec != A3D_PREC_F32) {
-    rec = timing_record(mode, plan.prec, 128, plan.bf16_bn, 4, 8, plan.prec == A3D_PREC_BF16X3 ? 32 : 64, avec, bvec, 0, p.M, p.N, p.K);
-  } else {
-    const TileCfg& t = kCfgs[plan.cfg];
-    rec = timing_record(mode, plan.prec, t.bm, t.bn, t.waves_m, t.nwaves, t.bk, avec, bvec,
-                        is_glds_cfg(plan.cfg) && avec == 4 && bvec == 4, p.M, p.N, p.K);
-  }
-  rec.splitk = plan.splitk;
-  // a second output / a narrower output are written by the reduction stage of a classic split-K forward or bwd-data launch
-  // (or, the second output, by a copy launch behind an unsplit one): refuse the other combinations BEFORE anything is
-  // enqueued — a GEMM that has already stored N columns into rows of c_cols floats cannot be taken back
-  const bool reduce_vec4 = plan.splitk > 1 && mode == MODE_BWD_F && p.ldc == p.N && (p.slab % 4) == 0 && aligned16(final_c) && aligned16(ws);
-  if (plan.streamk > 0) {
-    A3D_CHECK_ARG(!p.out2 && !p.c_cols, "second output: not on stream-K launches");
-  } else if (plan.splitk > 1) {
-    if (mode == MODE_BWD_F) A3D_CHECK_ARG(!p.out2 && !p.c_cols, "a second output belongs to a forward or bwd-data launch");
-  } else {
-    A3D_CHECK_ARG(!p.c_cols || p.c_cols == p.N, "this launch has no reduction stage: the output cannot be narrower than the GEMM");
-    A3D_CHECK_ARG(!p.out2 || (p.sub_step == 1 && !p.pool), "second output: plain forward / bwd-data launches only");
-  }
-  rc = timed_launch(rec, st, [&] {
-    if (plan.ring) return launch_igemm_ring(mode, plan.ring - 1, p, grid, st);
-    if (plan.prec != A3D_PREC_F32) return launch_igemm_bf16(mode, plan.bf16_bn, plan.prec == A3D_PREC_BF16X3, p, grid, st);
-    if (mode == MODE_FWD) return launch_igemm_mode0(plan.cfg, avec, bvec, p, grid, st);
-    if (mode == MODE_BWD_D) return launch_igemm_mode1(plan.cfg, avec, bvec, p, grid, st);
-    return launch_igemm_mode2(plan.cfg, avec, bvec, p, grid, st);
-  });
-  if (rc != A3D_OK) return rc;
-  if (plan.streamk > 0) {
-    const unsigned tiles = (unsigned)(plan.tiles_m * plan.tiles_n);
-    if (mode == MODE_FWD) return launch_fixup_mode0(plan.cfg, p, tiles, grid, st);
-    if (mode == MODE_BWD_D) return launch_fixup_mode1(plan.cfg, p, tiles, grid, st);
-    return launch_fixup_mode2(plan.cfg, p, tiles, grid, st);
-  }
-  if (plan.splitk > 1) {
-    ReduceParams r{};
-    r.ws = static_cast<const float*>(ws); r.C = final_c; r.bias = p.bias; r.mask = p.mask; r.keep = p.keep;
-    r.mask_scale = p.mask_scale; r.M = p.M; r.N = p.N; r.ldc = p.ldc; r.splitk = plan.splitk; r.act = p.act;
-    r.mode = mode; r.slab = p.slab; r.mask_act = p.mask_act; r.c16 = p.c16;
-    r.vec4 = reduce_vec4;
-    r.sub_step = p.sub_step; r.sub_ph = p.sub_ph; r.sub_pw = p.sub_pw; r.outW = p.outW; r.outHW = p.outHW;
-    r.div_phw = p.div_phw; r.div_pw = p.div_pw;
-    r.dbias_ws = final_dbias ? p.dbias : nullptr;
-    r.dbias_out = final_dbias;
-    if (p.dbias_parts) { r.dbias_ws = p.dbias_parts; r.dbias_out = p.dbias_parts_out; r.dbias_splits = p.dbias_parts_n; }
-    if (r.vec4 && p.unpad_dst && p.unpad_rlp > 0 && p.N % 4 == 0 && aligned16(p.unpad_dst)) {
-      r.C = p.unpad_dst; r.row_rl = p.unpad_rl; r.row_rlp = p.unpad_rlp;
-      p.unpad_done = 1;
-    }
-    r.C2 = p.out2; r.ld2 = p.out2_ld; r.step2 = p.out2_step; r.off2 = p.out2_off; r.c2_16 = p.out2_bf16; r.cols2 = p.out2_cols;
-    r.c_cols = p.c_cols;
-    rc = launch_splitk_reduce(r, st);
-    return rc;
-  }
-  if (p.out2) {                                       // no reduction stage wrote it: one copy launch (what the caller saved otherwise)
-    const size_t total = (size_t)p.M * p.out2_cols;
-    clear_stale_error();
-    hipLaunchKernelGGL(second_output_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 2048)), dim3(256), 0, st,
-                       static_cast<const void*>(final_c), p.c16, p.M, p.ldc, p.out2, p.out2_ld, p.out2_step, p.out2_off, p.out2_bf16,
-                       p.out2_cols);
-    rc = check_launch("second_output");
-  }
-  return rc;
-}
-
-// a3d_second_output -> the host-only fields of IgemmParams
-static int take_second_output(IgemmParams& p, const a3d_second_output* o) {
-  if (!o || !o->ptr) return A3D_OK;
-  A3D_CHECK_ARG(o->ld > 0 && o->step > 0 && o->offset >= 0 && o->cols > 0 && o->cols <= p.N, "second output: bad geometry");
-  p.out2 = o->ptr; p.out2_ld = o->ld; p.out2_step = o->step; p.out2_off = o->offset; p.out2_bf16 = o->bf16 ? 1 : 0; p.out2_cols = o->cols;
-  return A3D_OK;
-}
+// The switches read here and in igemm_launch.hip (A3D_PLAN_LOG, A3D_DBG, A3D_FEWCH, ...) and the planner's (A3D_FORCE_*,
+// A3D_BF16_BN, A3D_RING*) all go through tune_int() (igemm_plan.h, capi.cc): the environment is consulted on every launch ONLY
+// in a process started with A3D_TUNING=1, as the sweep and fuzz tools do; otherwise nothing reads it, and plans are cached per
+// problem (plan_gemm).
 
 // ---- "window-run" form of few-channel VALID convolutions (Cin = 3: conv2d_0, fine/first) ----
 // For an unpadded conv with densely packed pixels a filter row (s, c) is ONE contiguous run of S*Cin floats of the
@@ -376,19 +28,22 @@ struct RunForm {
   int vec;      // 4 or 2
   int rl, rlp;  // run length S*Cin and its padded length
   int kp;       // R * rlp
+  int np;       // forward: a row of the padded filter, the k filters padded to 16 bytes
+  size_t bytes; // the padded filter (bwd-filter: its gradient) in the workspace
 };
 // bwd_filter: the filter-gradient GEMM may also take runs that start at any 4-byte address (DCNF's first conv: stride 1,
 // runs 12 bytes apart) as 8-byte buffer loads — the hardware only asks a multi-dword buffer load for dword alignment —
 // and runs whose padding reaches past the row's end: what a pad element multiplies ends up in a pad row of the padded
 // gradient, which is never stored (past the tensor's end the descriptor returns zeros).
-static bool run_form_ok(const a3d_conv_desc* d, const float* x, RunForm* rf, bool bwd_filter = false) {
+// x_off: x's address & 15 (a query: kOnGrid.x)
+static bool run_form_ok(const a3d_conv_desc* d, unsigned x_off, RunForm* rf, bool bwd_filter = false) {
   if (d->pad_t || d->pad_l || d->ldx != d->c || d->c % 4 == 0 || d->c > 4) return false;
   const int step = d->stride * d->c, row = d->w * d->c;
   int vec = 0;
   bool anywhere = false;
-  if (step % 4 == 0 && row % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) vec = 4;
-  else if (step % 2 == 0 && row % 2 == 0 && (reinterpret_cast<uintptr_t>(x) & 7) == 0) vec = 2;
-  else if (bwd_filter && d->precision == A3D_PREC_F32 && !d->storage && (reinterpret_cast<uintptr_t>(x) & 3) == 0) {
+  if (step % 4 == 0 && row % 4 == 0 && x_off == 0) vec = 4;
+  else if (step % 2 == 0 && row % 2 == 0 && (x_off & 7) == 0) vec = 2;
+  else if (bwd_filter && d->precision == A3D_PREC_F32 && !d->storage && (x_off & 3) == 0) {
     vec = 2;
     anywhere = true;
   }
@@ -405,6 +60,8 @@ static bool run_form_ok(const a3d_conv_desc* d, const float* x, RunForm* rf, boo
   rf->rl = d->s * d->c;
   rf->rlp = (rf->rl + vec - 1) / vec * vec;
   rf->kp = d->r * rf->rlp;
+  rf->np = (d->k + 3) / 4 * 4;
+  rf->bytes = ((size_t)rf->kp * rf->np * 4 + 255) / 256 * 256;
   // the padded run of the last output column stays inside its row; `anywhere`: the run itself does (no implicit padding
   // on the right / below: a SAME convolution with an even kernel has pad_t = pad_l = 0 and still pads), its padding may not
   if (anywhere) return (d->wo - 1) * step + rf->rl <= row && (d->ho - 1) * d->stride + d->r <= d->h;
@@ -429,8 +86,52 @@ __global__ __launch_bounds__(256) void unpad_filter_kernel(const float* wp, floa
     w[i] = wp[(size_t)(rr * rlp + q) * n + col];
   }
 }
-static size_t run_filter_bytes(const a3d_conv_desc* d, const RunForm& rf) {
-  return ((size_t)rf.kp * ((d->k + 3) / 4 * 4) * 4 + 255) / 256 * 256;      // forward: rows padded to 16 bytes
+
+// ---- what a candidate is told about a call's operands ----
+// A call is served by one of a fixed list of candidates: the GEMM over the tensors as stored, the same on the LDS-DMA kernel, the
+// window-run and bf16 image forms, conv3 / conv3b, fewch / fewch16, the stencil.  Each is written once, as a function of the
+// descriptor and of what is known of the operands, and answers whether it takes the call, the GEMM it plans and the workspace it
+// needs.  A launch asks the candidate it picks from its real pointers and checks ws_bytes against that answer; a *_ws_bytes query
+// has the descriptor alone and takes the maximum over the list, asking with kOnGrid: every operand on the 16-byte grid, no fused
+// pool, no prepared filter, a bias gradient wanted, and `known` false.  Where `known` is false the tests that need a pointer, a
+// pixel stride or the epilogue count as passed, and the GEMM is planned from the descriptor's channel counts alone (no hint, no
+// storage bit): every place that reads `o.known` is a query answer that a launch may exceed (tests/golden/plan_table.json pins them).
+struct Operands {
+  bool known = false;
+  unsigned x = 0, w = 0, y = 0;      // address & 15 of the image-side tensor (x, dx), the filter (w, dw) and the output-side one (y, dz)
+  unsigned aux = 0;                  // ... of the argmax rows (pooled forward) or the mask (bwd-data); 0 without one
+  int act = A3D_ACT_NONE, pool = 0, ld_out = 0;
+  bool argmax = false, prepared = false;
+  bool db = true;                    // bwd-filter: the bias gradient is wanted
+};
+static const Operands kOnGrid{};
+// ... of a launch: x / w / y as in Operands
+static Operands launch_operands(const void* x, const void* w, const void* y, const void* aux) {
+  auto off16 = [](const void* p) { return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15); };
+  Operands o;
+  o.known = true;
+  o.x = off16(x); o.w = off16(w); o.y = off16(y); o.aux = off16(aux);
+  return o;
+}
+
+enum GemmForm { kAsStored, kLdsDma, kRunForm, kBf16Image };
+struct Route {
+  bool ok = false;
+  RunForm rf{};           // kRunForm, kBf16Image
+  GemmProblem g{};
+  GemmPlan plan{};
+  size_t repack = 0;      // the repacked filter at the workspace's start; the plan's slabs follow it
+  size_t bytes = 0;       // all of it: repack + plan.ws_bytes + bias slabs or column-sum partials
+};
+static size_t upto(size_t need, const Route& r) { return r.ok ? std::max(need, r.bytes) : need; }
+
+static const int kAll16 = A3D_STORE_X_BF16 | A3D_STORE_W_BF16 | A3D_STORE_Y_BF16;
+static bool stored16(const a3d_conv_desc* d, int bits) { return (d->storage & bits) == bits; }
+// Forward / bwd-data: `both` operands bf16 tensors, whole 16-byte pieces inside one of at most 128 taps, the output (address & 15:
+// out_off) on the grid: the LDS-DMA kernel may take the launch
+static bool ring_ok(const a3d_conv_desc* d, const Operands& o, int both, unsigned out_off, int taps) {
+  if (d->precision != A3D_PREC_BF16 || !stored16(d, both) || d->c % 8 || d->k % 8) return false;
+  return !o.known || (d->ldx % 8 == 0 && d->ldy % 8 == 0 && taps <= 128 && !out_off);
 }
 
 // ---- descriptor checks / parameter assembly ----
@@ -482,9 +183,15 @@ static GemmProblem bwd_f_problem(const a3d_conv_desc* d) {
   return g;
 }
 
+// the problem as planned for bf16 operands: gathered in 16-byte pieces, and a bf16 output is not the LDS-DMA fp32 kernels'
+static void storage_vecs(GemmProblem& g, bool a16, bool b16, bool c16) {
+  if (c16) g.no_glds = 1;
+  if (a16) g.avec = 4;
+  if (b16) g.bvec = 4;
+}
 // a3d_conv_desc.storage -> which GEMM operands are bf16, with the checks a 16-byte bf16 gather needs
-static int apply_storage(IgemmParams& p, GemmProblem& g, int precision, bool a16, bool b16, bool c16, int a_c, int a_ld,
-                         int b_c, int b_ld, const void* a, const void* b, const void* c) {
+static int apply_storage(IgemmParams& p, int precision, bool a16, bool b16, bool c16, int a_c, int a_ld, int b_c, int b_ld,
+                         const void* a, const void* b, const void* c) {
   if (!a16 && !b16 && !c16) return A3D_OK;
   // a bf16 OUTPUT alone is also served by the fp32 kernels (the 3-channel layers of config 5 keep fp32 arithmetic)
   A3D_CHECK_ARG(precision == A3D_PREC_BF16 || (precision == A3D_PREC_F32 && !a16 && !b16),
@@ -494,9 +201,6 @@ static int apply_storage(IgemmParams& p, GemmProblem& g, int precision, bool a16
   A3D_CHECK_ARG(!b16 || ((b_c < 0 || b_c % 8 == 0) && b_ld % 8 == 0 && aligned16(b)), "bf16 operand: channels / stride must be multiples of 8, base 16-byte aligned");
   A3D_CHECK_ARG(!c16 || aligned16(c), "bf16 output: base must be 16-byte aligned");
   p.a16 = a16; p.b16 = b16; p.c16 = c16;
-  if (c16) g.no_glds = 1;
-  if (a16) g.avec = 4;
-  if (b16) g.bvec = 4;
   return A3D_OK;
 }
 
@@ -546,96 +250,45 @@ static void fill_pool(IgemmParams& p, const a3d_conv_desc* d, uint8_t* argmax, i
   p.ldc = ld_out;
 }
 
-}  // namespace a3d
-
-using namespace a3d;
-
-extern "C" {
-
-#ifdef A3D_STAMPS
-// diagnostic build only: copies the last launch's [grid][8 waves][8] phase sums to the host; returns the grid size
-int a3d_debug_stamps(unsigned long long* out, size_t cap_bytes) {
-  (void)hipDeviceSynchronize();
-  if (g_stamps && out) (void)hipMemcpy(out, g_stamps, std::min(cap_bytes, kStampBytes), hipMemcpyDeviceToHost);
-  return (int)g_stamp_grid;
-}
-#endif
-
-int a3d_timing_enable(int on) {
-  std::lock_guard<std::mutex> lk(g_timing_mu);
-  g_timing_on = on != 0;
-  return A3D_OK;
+// GEMM rows of a forward: output pixels or, with the 2x2 max pool in the epilogue, pool windows x 4
+static int fwd_rows(const a3d_conv_desc* d, int pool) {
+  return pool ? d->n * (d->ho / 2) * (d->wo / 2) * 4 : d->n * d->ho * d->wo;
 }
 
-int a3d_timing_select(const a3d_timing_record* like) {
-  std::lock_guard<std::mutex> lk(g_timing_mu);
-  g_timing_only = like != nullptr;
-  if (like) g_timing_like = *like;
-  return A3D_OK;
+// ---- the few-channel kernels as the timing list sees them (a3d_timing_*); m: fwd_rows ----
+// lds_dma 2: conv3_fwd_kernel (filter repack included in ms)
+static a3d_timing_record conv3_record(const a3d_conv_desc* d, int m) {
+  return timing_record(MODE_FWD, A3D_PREC_F32, 64, d->k > 64 ? 96 : 64, 1, 1, 8, 4, 4, 2, m, d->k, d->r * d->s * d->c);
 }
-
-int a3d_timing_collect(a3d_timing_record* out, int cap) {
-  std::vector<TimingSlot> slots;
-  {
-    std::lock_guard<std::mutex> lk(g_timing_mu);
-    slots.swap(g_timing);
-  }
-  int n = 0;
-  for (TimingSlot& s : slots) {
-    (void)hipEventSynchronize(s.stop);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, s.start, s.stop);
-    s.rec.ms = ms;
-    if (out && n < cap) out[n++] = s.rec;
-    (void)hipEventDestroy(s.start);
-    (void)hipEventDestroy(s.stop);
-  }
-  return n;
+// conv3b_fwd_kernel; k, flops: algorithmic, the image's three real channels
+static a3d_timing_record conv3b_record(const a3d_conv_desc* d, int m) {
+  return timing_record(MODE_FWD, A3D_PREC_BF16, 64, d->k > 64 ? 96 : 64, 1, 1, 16, 4, 4, 2, m, d->k, d->r * d->s * 3);
 }
-
-static size_t bf16_image_filter_bytes(const a3d_conv_desc* d);
-
-size_t a3d_conv2d_fwd_ws_bytes(const a3d_conv_desc* d) {
-  if (check_desc(d) != A3D_OK) return 0;
-  if (stencil1_applicable(d)) return 0;
-  // (a maximum over the paths a launch may take: which one it is also depends on the operands' alignment)
-  size_t need = plan_gemm(fwd_problem(d), d->precision).ws_bytes;
-  {                                              // ... the LDS-DMA kernel's plan among them (its split-K slabs: dense layers)
-    const int both = A3D_STORE_X_BF16 | A3D_STORE_W_BF16;
-    GemmProblem g = fwd_problem(d);
-    g.ring_ok = d->precision == A3D_PREC_BF16 && (d->storage & both) == both && d->c % 8 == 0 && d->k % 8 == 0;
-    g.avec = g.bvec = 4;
-    if (g.ring_ok) need = std::max(need, plan_gemm(g, d->precision).ws_bytes);
-  }
-  if (conv3_applicable(d, nullptr)) need = std::max(need, conv3_ws_bytes(d));
-  RunForm rf;
-  if (run_form_ok(d, nullptr, &rf)) {
-    GemmProblem g = fwd_problem(d);
-    g.K = rf.kp; g.avec = rf.vec;
-    need = std::max(need, run_filter_bytes(d, rf) + plan_gemm(g, d->precision).ws_bytes);
-  }
-  if (d->storage & A3D_STORE_X_BF16 && d->c == 4 && d->ldx == 4) {      // bf16 image form (same test minus the pointer)
-    GemmProblem g = fwd_problem(d);
-    g.K = d->r * ((d->s * 2 + 3) / 4 * 4 * 2); g.avec = 4; g.bvec = 4; g.no_glds = 1;
-    need = std::max(need, bf16_image_filter_bytes(d) + plan_gemm(g, d->precision).ws_bytes);
-    need = std::max(need, conv3b_filter_bytes(d));
-  }
-  return need;
+// lds_dma 4: fewch_bwdf_kernel, ms includes the slab reduction
+static a3d_timing_record fewch_record(const a3d_conv_desc* d) {
+  return timing_record(MODE_BWD_F, A3D_PREC_F32, 128, (d->k + 31) / 32 * 32, 4, 4, 2, 1, 1, 4, d->r * d->s * d->c, d->k, d->n * d->ho * d->wo);
+}
+// ... fewch16_bwdf_kernel
+static a3d_timing_record fewch16_record(const a3d_conv_desc* d) {
+  return timing_record(MODE_BWD_F, A3D_PREC_BF16, 128, (d->k + 31) / 32 * 32, 4, 4, 16, 1, 1, 4, d->r * d->s * d->c, d->k, d->n * d->ho * d->wo);
 }
 
 // ---- window-run form over a bf16 image of 8-byte pixels (4 channels; a3d_pad_channels_bf16) ----
 // Seen through its float view a pixel is 2 floats, so at an even stride the runs of a filter row start 16 bytes apart and
 // the bf16 kernel gathers them with its 16-byte loads: K = (r, run of s*4 bf16 padded to a multiple of 8), the filter
-// [r][s][4][k] float32 is repacked per call as bf16 [r][run][k padded to 8] (pad rows / columns zero).
-static bool bf16_image_form_ok(const a3d_conv_desc* d, const void* x) {
-  if (!(d->storage & A3D_STORE_X_BF16) || (d->storage & A3D_STORE_W_BF16) || d->precision != A3D_PREC_BF16) return false;
-  if (d->c != 4 || d->ldx != 4 || d->pad_t || d->pad_l || d->stride % 2 || (d->w * 2) % 4 || !aligned16(x)) return false;
-  const int rlv = (d->s * 2 + 3) / 4 * 4;                       // padded run in view floats
-  return (d->wo - 1) * d->stride * 2 + rlv <= d->w * 2;        // the last column's padded run stays inside its row
-}
-static size_t bf16_image_filter_bytes(const a3d_conv_desc* d) {
-  const int rlp = (d->s * 2 + 3) / 4 * 4 * 2, np = (d->k + 7) / 8 * 8;      // bf16 elements
-  return ((size_t)d->r * rlp * np * 2 + 255) / 256 * 256;
+// [r][s][4][k] float32 is repacked per call as bf16 [r][run][k padded to 8] (pad rows / columns zero).  rf: in bf16 elements.
+static bool bf16_image_form_ok(const a3d_conv_desc* d, const Operands& o, RunForm* rf) {
+  rf->vec = 4;
+  rf->rl = d->s * 4;
+  rf->rlp = (d->s * 2 + 3) / 4 * 4 * 2;
+  rf->kp = d->r * rf->rlp;
+  rf->np = (d->k + 7) / 8 * 8;
+  rf->bytes = ((size_t)rf->kp * rf->np * 2 + 255) / 256 * 256;
+  if (!(d->storage & A3D_STORE_X_BF16) || d->c != 4 || d->ldx != 4) return false;
+  if (!o.known) return true;
+  if ((d->storage & A3D_STORE_W_BF16) || d->precision != A3D_PREC_BF16) return false;
+  if (d->pad_t || d->pad_l || d->stride % 2 || (d->w * 2) % 4 || o.x) return false;
+  return (d->wo - 1) * d->stride * 2 + rf->rlp / 2 <= d->w * 2;      // (view floats) the last column's padded run stays inside its row
 }
 // filter [r][rl][n] float32 -> bf16 [r][rlp][np], pad rows / columns zero
 __global__ __launch_bounds__(256) void pad_filter_bf16_kernel(const float* w, __bf16* wp, int r, int rl, int rlp, int n, int np) {
@@ -646,46 +299,66 @@ __global__ __launch_bounds__(256) void pad_filter_bf16_kernel(const float* w, __
     wp[i] = (__bf16)((q < rl && col < n) ? w[(size_t)(rr * rl + q) * n + col] : 0.f);
   }
 }
-static int pad_filter_bf16(const a3d_conv_desc* d, const float* w, __bf16* wp, hipStream_t st) {
-  const int rl = d->s * 4, rlp = (d->s * 2 + 3) / 4 * 4 * 2, np = (d->k + 7) / 8 * 8;      // bf16 elements
+// the filter padded for the window-run form (float32) or for the bf16 image form (bf16) into wp
+static int pad_filter(const a3d_conv_desc* d, const RunForm& rf, bool bf16, const float* w, void* wp, hipStream_t st) {
+  const dim3 grid((rf.kp * rf.np + 255) / 256), block(256);
   clear_stale_error();
-  hipLaunchKernelGGL(pad_filter_bf16_kernel, dim3((d->r * rlp * np + 255) / 256), dim3(256), 0, st, w, wp, d->r, rl, rlp,
-                     d->k, np);
-  return check_launch("pad_filter_bf16");
+  if (bf16)
+    hipLaunchKernelGGL(pad_filter_bf16_kernel, grid, block, 0, st, w, static_cast<__bf16*>(wp), d->r, rf.rl, rf.rlp, d->k, rf.np);
+  else
+    hipLaunchKernelGGL(pad_filter_kernel, grid, block, 0, st, w, static_cast<float*>(wp), d->r, rf.rl, rf.rlp, d->k, rf.np);
+  return check_launch(bf16 ? "pad_filter_bf16" : "pad_filter");
 }
-static int conv_fwd_bf16_image(const a3d_conv_desc* d, const float* x, const float* w, const float* bias, float* y, int act,
-                               int pool, int ld_out, uint8_t* argmax, void* ws, size_t ws_bytes, hipStream_t st) {
-  const int rlp = (d->s * 2 + 3) / 4 * 4 * 2, np = (d->k + 7) / 8 * 8;      // bf16 elements
-  GemmProblem g = fwd_problem(d);
-  g.K = d->r * rlp; g.avec = 4; g.bvec = 4; g.no_glds = 1;
-  if (pool) {
-    g.M = d->n * (d->ho / 2) * (d->wo / 2) * 4;
-    g.plain = 1;
+
+// Does this form take the forward?  (kLdsDma, pooled: the pooled map's pixel stride and the argmax rows in whole 16-byte pieces too)
+static bool fwd_form_ok(const a3d_conv_desc* d, const Operands& o, GemmForm form, RunForm* rf) {
+  if (form == kRunForm) return run_form_ok(d, o.x, rf);
+  if (form == kBf16Image) return bf16_image_form_ok(d, o, rf);
+  if (form == kAsStored || !ring_ok(d, o, A3D_STORE_X_BF16 | A3D_STORE_W_BF16, o.y, d->r * d->s)) return form == kAsStored;
+  return !o.known || (o.act != A3D_ACT_SIGMOID && (!o.pool || ((d->storage & A3D_STORE_Y_BF16) && o.ld_out % 8 == 0 &&
+                                                               (!o.argmax || (d->k % 16 == 0 && !o.aux)))));
+}
+// The forward as a GEMM: over the tensors as stored, the same offered to the LDS-DMA kernel, or in the window-run / bf16 image
+// form (K = (r, padded run), the filter padded into the workspace)
+static Route fwd_gemm(const a3d_conv_desc* d, const Operands& o, GemmForm form) {
+  Route r;
+  if (!(r.ok = fwd_form_ok(d, o, form, &r.rf))) return r;
+  GemmProblem& g = r.g;
+  g = fwd_problem(d);
+  g.M = fwd_rows(d, o.pool); g.plain = o.pool ? 1 : 0;
+  if (o.x) g.avec = 1;
+  if (o.w) g.bvec = 1;
+  if (form == kRunForm || form == kBf16Image) {
+    g.K = r.rf.kp; g.avec = r.rf.vec;
+    if (!o.prepared) r.repack = r.rf.bytes;      // (prepared: w already is the padded filter, a3d_conv2d_fwd_prepare_filter)
   }
-  const bool prepared = (d->hints & A3D_HINT_W_PREPARED) != 0;      // w is already the padded bf16 filter (a3d_conv2d_fwd_prepare_filter)
-  const size_t ws_used = prepared ? 0 : bf16_image_filter_bytes(d);
-  GemmPlan plan = plan_gemm(g, d->precision);
-  if ((!ws && ws_used + plan.ws_bytes > 0) || ws_used + plan.ws_bytes > ws_bytes)
-    return set_error(A3D_EWORKSPACE, "conv2d_fwd: need %zu workspace bytes", ws_used + plan.ws_bytes);
-  A3D_CHECK_ARG(plan.prec == A3D_PREC_BF16 && aligned16(y), "conv2d_fwd: bf16 image form needs the bf16 kernel");
-  const __bf16* wp = reinterpret_cast<const __bf16*>(w);
-  if (!prepared) {
-    int rc = pad_filter_bf16(d, w, static_cast<__bf16*>(ws), st);
-    if (rc != A3D_OK) return rc;
-    wp = static_cast<const __bf16*>(ws);
-  } else {
-    A3D_CHECK_ARG(aligned16(w), "conv2d_fwd: a prepared filter is 16-byte aligned");
+  if (form == kBf16Image) { g.bvec = 4; g.no_glds = 1; }
+  if (form == kLdsDma) { g.ring_ok = 1; g.avec = g.bvec = 4; }
+  if (o.known) {
+    if (d->hints & A3D_HINT_SHARE_CU) g.no_glds = 1;      // the register-staged kernels take the hint (launch_one)
+    if (form == kRunForm) g.bvec = 4;                     // the padded copy is 256-byte aligned, its rows whole 16-byte pieces
+    storage_vecs(g, d->storage & A3D_STORE_X_BF16, d->storage & A3D_STORE_W_BF16, d->storage & A3D_STORE_Y_BF16);
   }
-  IgemmParams p;
-  fill_common(p, g);
-  p.a16 = 1; p.b16 = 1; p.c16 = (d->storage & A3D_STORE_Y_BF16) ? 1 : 0;
-  p.A = x; p.B = reinterpret_cast<const float*>(wp); p.C = y; p.bias = bias; p.act = act;
-  p.npix = g.M; p.nrsc = g.K;
-  fill_gather(p, d, d->ldx, 1, rlp);            // (bf16_image_form_ok: ldx = 4, no padding)
-  p.ldb = np; p.ldc = d->ldy;
-  if (pool) fill_pool(p, d, argmax, ld_out);
-  fill_staging(p, MODE_FWD, (unsigned long long)d->n * d->h * d->w * 4, (unsigned long long)g.K * np, d->r, 1);
-  return launch_igemm(MODE_FWD, plan, 4, 4, p, static_cast<char*>(ws) + ws_used, st);
+  r.plan = plan_gemm(g, d->precision);
+  r.bytes = r.repack + r.plan.ws_bytes;
+  return r;
+}
+
+}  // namespace a3d
+
+using namespace a3d;
+
+extern "C" {
+
+size_t a3d_conv2d_fwd_ws_bytes(const a3d_conv_desc* d) {
+  if (check_desc(d) != A3D_OK || stencil1_applicable(d)) return 0;
+  // (a maximum over the paths a launch may take: which one it is also depends on the operands' alignment)
+  size_t need = 0;
+  for (GemmForm form : {kAsStored, kLdsDma, kRunForm, kBf16Image}) need = upto(need, fwd_gemm(d, kOnGrid, form));
+  RunForm rf;
+  if (bf16_image_form_ok(d, kOnGrid, &rf)) need = std::max(need, conv3b_filter_bytes(d));
+  if (conv3_applicable(d, kOnGrid.x)) need = std::max(need, conv3_ws_bytes(d));
+  return need;
 }
 
 // conv2d forward; pool != 0: y is the 2x2 / stride-2 max pool of the activated conv output, [n, ho/2, wo/2, k] with
@@ -695,14 +368,19 @@ static int conv_fwd_impl(const a3d_conv_desc* d, const float* x, const float* w,
                          const a3d_second_output* out2 = nullptr) {
   int rc = check_desc(d);
   if (rc != A3D_OK) return rc;
-  A3D_CHECK_ARG(!(out2 && out2->ptr) || (!pool && !stencil1_applicable(d) && !bf16_image_form_ok(d, x) && !conv3_applicable(d, x)),
+  if (!ws) ws_bytes = 0;
+  Operands o = launch_operands(x, w, y, argmax);
+  o.act = act; o.pool = pool; o.ld_out = ld_out; o.argmax = argmax != nullptr;
+  o.prepared = (d->hints & A3D_HINT_W_PREPARED) != 0;
+  RunForm rf;
+  const bool image = fwd_form_ok(d, o, kBf16Image, &rf);
+  A3D_CHECK_ARG(!(out2 && out2->ptr) || (!pool && !stencil1_applicable(d) && !image && !conv3_applicable(d, o.x)),
                 "conv2d_fwd_ex2: a second output on the implicit-GEMM forwards only (no fused pool, no few-channel / one-filter kernels)");
   A3D_CHECK_ARG(x && w && y, "conv2d_fwd: null tensor");
   A3D_CHECK_ARG(act == A3D_ACT_NONE || act == A3D_ACT_RELU || act == A3D_ACT_SIGMOID, "conv2d_fwd: bad act");
   if (pool) {
-    const int all16 = A3D_STORE_X_BF16 | A3D_STORE_W_BF16 | A3D_STORE_Y_BF16;
-    A3D_CHECK_ARG(d->precision == A3D_PREC_F32 || bf16_image_form_ok(d, x) ||
-                      (d->precision == A3D_PREC_BF16 && ((d->storage & all16) == all16 || d->storage == A3D_STORE_Y_BF16)),
+    A3D_CHECK_ARG(d->precision == A3D_PREC_F32 || image ||
+                      (d->precision == A3D_PREC_BF16 && (stored16(d, kAll16) || d->storage == A3D_STORE_Y_BF16)),
                   "conv2d_pool_fwd: fp32, the bf16 image form (4-channel bf16 image, a3d_pad_channels_bf16), or bf16 arithmetic on "
                   "bf16 x, w and y (LDS-DMA kernel)");
     A3D_CHECK_ARG(d->ho >= 2 && d->wo >= 2 && ld_out >= d->k, "conv2d_pool_fwd: output smaller than one pool window");
@@ -712,84 +390,54 @@ static int conv_fwd_impl(const a3d_conv_desc* d, const float* x, const float* w,
     return stencil1_fwd(d, x, w, bias, y, act, static_cast<hipStream_t>(stream));
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int m_out = pool ? d->n * (d->ho / 2) * (d->wo / 2) * 4 : d->n * d->ho * d->wo;      // GEMM rows: pixels, or pool windows x 4
-  const bool prepared = (d->hints & A3D_HINT_W_PREPARED) != 0;
-  if (bf16_image_form_ok(d, x)) {
-    if (!conv3b_applicable(d)) return conv_fwd_bf16_image(d, x, w, bias, y, act, pool, ld_out, argmax, ws, ws_bytes, st);
-    // straight from L2 on the bf16 matrix cores (conv3.hip, conv3b_fwd_kernel); k, flops: algorithmic, the image's three real channels
-    return timed_launch(timing_record(MODE_FWD, A3D_PREC_BF16, 64, d->k > 64 ? 96 : 64, 1, 1, 16, 4, 4, 2, m_out, d->k, d->r * d->s * 3), st,
-                        [&] { return conv3b_fwd(d, x, w, bias, y, act, pool, ld_out, argmax, ws, ws_bytes, st, prepared); });
-  }
-  if (conv3_applicable(d, x))                    // few-channel layers: operands straight from L2 (conv3.hip)
-    // lds_dma 2: conv3_fwd_kernel (filter repack included in ms)
-    return timed_launch(timing_record(MODE_FWD, A3D_PREC_F32, 64, d->k > 64 ? 96 : 64, 1, 1, 8, 4, 4, 2, m_out, d->k, d->r * d->s * d->c), st,
-                        [&] { return conv3_fwd(d, x, w, bias, y, act, pool, ld_out, argmax, ws, ws_bytes, st, prepared); });
-  GemmProblem g = fwd_problem(d);
-  if (pool) {
-    g.M = m_out;
-    g.plain = 1;
-  }
-  if (!aligned16(x)) g.avec = 1;
-  if (!aligned16(w)) g.bvec = 1;
-  if (d->hints & A3D_HINT_SHARE_CU) g.no_glds = 1;      // the register-staged kernels take the hint (launch_one)
-  RunForm rf{};
-  const bool run = run_form_ok(d, x, &rf) && (prepared || (ws && ws_bytes >= run_filter_bytes(d, rf)));
+  if (image && conv3b_applicable(d))             // straight from L2 on the bf16 matrix cores (conv3.hip, conv3b_fwd_kernel)
+    return timed_launch(conv3b_record(d, fwd_rows(d, pool)), st,
+                        [&] { return conv3b_fwd(d, x, w, bias, y, act, pool, ld_out, argmax, ws, ws_bytes, st, o.prepared); });
+  if (!image && conv3_applicable(d, o.x))        // few-channel layers: operands straight from L2 (conv3.hip)
+    return timed_launch(conv3_record(d, fwd_rows(d, pool)), st,
+                        [&] { return conv3_fwd(d, x, w, bias, y, act, pool, ld_out, argmax, ws, ws_bytes, st, o.prepared); });
+  // the window-run form if the workspace holds its padded filter; else the tensors as stored, on the LDS-DMA kernel where that may be
+  const bool run = !image && fwd_form_ok(d, o, kRunForm, &rf) && (o.prepared || rf.bytes <= ws_bytes), padded = run || image;
+  const Route r = fwd_gemm(d, o, image ? kBf16Image : run ? kRunForm : fwd_form_ok(d, o, kLdsDma, &rf) ? kLdsDma : kAsStored);
   // (the prepared layout was chosen for a 16-byte aligned x — fwd_filter_form — and this launch reads it with THAT row padding)
-  A3D_CHECK_ARG(!prepared || (run && aligned16(w) && aligned16(x)),
+  A3D_CHECK_ARG(!o.prepared || (padded && !o.w && !o.x),
                 "conv2d_fwd: A3D_HINT_W_PREPARED on a launch that reads the filter as stored, or with x off the 16-byte grid");
-  size_t ws_used = 0;
-  const float* filter = w;
-  int run_ldb = d->k;
-  if (run) {                                   // window-run form: K = (r, padded run), filter padded into the workspace
-    g.K = rf.kp; g.avec = rf.vec;
-    const int np = (d->storage & A3D_STORE_W_BF16) ? d->k : (d->k + 3) / 4 * 4;
-    if (!prepared) {                           // (prepared: w already is the padded filter, a3d_conv2d_fwd_prepare_filter)
-      ws_used = run_filter_bytes(d, rf);
-      float* wp = static_cast<float*>(ws);
-      clear_stale_error();
-      hipLaunchKernelGGL(pad_filter_kernel, dim3((rf.kp * np + 255) / 256), dim3(256), 0, st, w, wp, d->r, rf.rl,
-                         rf.rlp, d->k, np);
-      rc = check_launch("pad_filter");
-      if (rc != A3D_OK) return rc;
-      filter = wp;
-    }
-    run_ldb = np;
-    g.bvec = (np % 4 == 0) ? 4 : 1;             // the padded copy is 256-byte aligned
-  }
   IgemmParams p;
-  fill_common(p, g);
-  {
-    const int sb = d->storage;
-    const int all16 = A3D_STORE_X_BF16 | A3D_STORE_W_BF16 | A3D_STORE_Y_BF16;
-    A3D_CHECK_ARG(!sb || ((!pool || sb == A3D_STORE_Y_BF16 || (sb == all16 && d->precision == A3D_PREC_BF16)) &&
+  fill_common(p, r.g);
+  const int sb = d->storage;
+  if (image) {
+    p.a16 = 1; p.b16 = 1; p.c16 = (sb & A3D_STORE_Y_BF16) ? 1 : 0;
+  } else {
+    A3D_CHECK_ARG(!sb || ((!pool || sb == A3D_STORE_Y_BF16 || (sb == kAll16 && d->precision == A3D_PREC_BF16)) &&
                           !(run && (sb & A3D_STORE_W_BF16))),
                   "conv2d_fwd: the fused pool takes float32 inputs (its output may be bf16) or bf16 x, w and y; 3-channel filters stay float32");
-    rc = apply_storage(p, g, d->precision, sb & A3D_STORE_X_BF16, sb & A3D_STORE_W_BF16, sb & A3D_STORE_Y_BF16, d->c,
-                       d->ldx, d->k, d->k, x, w, y);
+    rc = apply_storage(p, d->precision, sb & A3D_STORE_X_BF16, sb & A3D_STORE_W_BF16, sb & A3D_STORE_Y_BF16, d->c, d->ldx, d->k, d->k,
+                       x, w, y);
     if (rc != A3D_OK) return rc;
-    // both operands bf16 tensors, whole 16-byte pieces inside one tap: the LDS-DMA kernel may take the launch
-    // (pooled: the pooled map's pixel stride and the argmax rows in whole 16-byte pieces too)
-    g.ring_ok = p.a16 && p.b16 && !run && d->precision == A3D_PREC_BF16 && d->c % 8 == 0 && d->ldx % 8 == 0 &&
-                d->k % 8 == 0 && d->ldy % 8 == 0 && d->r * d->s <= 128 && aligned16(y) && act != A3D_ACT_SIGMOID &&
-                (!pool || (p.c16 && ld_out % 8 == 0 && (!argmax || (d->k % 16 == 0 && aligned16(argmax)))));
+    A3D_CHECK_ARG(!(pool && (p.a16 || p.b16)) || r.plan.ring,
+                  "conv2d_pool_fwd: on bf16 inputs the fused pool is the LDS-DMA kernel's (channels and strides in whole 16-byte pieces, k %% 16 == 0)");
   }
-  GemmPlan plan = plan_gemm(g, d->precision);
-  A3D_CHECK_ARG(!(pool && (p.a16 || p.b16)) || plan.ring,
-                "conv2d_pool_fwd: on bf16 inputs the fused pool is the LDS-DMA kernel's (channels and strides in whole 16-byte pieces, k %% 16 == 0)");
-  if (ws_used + plan.ws_bytes > ws_bytes)
-    return set_error(A3D_EWORKSPACE, "conv2d_fwd: need %zu workspace bytes", ws_used + plan.ws_bytes);
-  A3D_CHECK_ARG(!(p.a16 || p.b16) || plan.prec == A3D_PREC_BF16, "conv2d_fwd: bf16 operands need vectorisable tensors");
-  A3D_CHECK_ARG(!p.c16 || plan.prec == A3D_PREC_BF16 || !is_glds_cfg(plan.cfg), "conv2d_fwd: no bf16 output from the LDS-DMA kernels");
+  if (r.bytes > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_fwd: need %zu workspace bytes", r.bytes);
+  A3D_CHECK_ARG(!image || (r.plan.prec == A3D_PREC_BF16 && !o.y), "conv2d_fwd: bf16 image form needs the bf16 kernel");
+  A3D_CHECK_ARG(!(p.a16 || p.b16) || r.plan.prec == A3D_PREC_BF16, "conv2d_fwd: bf16 operands need vectorisable tensors");
+  A3D_CHECK_ARG(!p.c16 || r.plan.prec == A3D_PREC_BF16 || !is_glds_cfg(r.plan.cfg), "conv2d_fwd: no bf16 output from the LDS-DMA kernels");
+  const float* filter = w;
+  if (padded && !o.prepared) {
+    rc = pad_filter(d, r.rf, image, w, ws, st);
+    if (rc != A3D_OK) return rc;
+    filter = static_cast<const float*>(ws);
+  }
+  const int ldb = padded ? r.rf.np : d->k;
   p.A = x; p.B = filter; p.C = y; p.bias = bias; p.act = act;
   p.share = (d->hints & A3D_HINT_SHARE_CU) ? 1 : 0;
-  p.npix = g.M; p.nrsc = g.K;
-  fill_gather(p, d, d->ldx, run ? 1 : d->s, run ? rf.rlp : d->c);
-  p.ldb = run_ldb; p.ldc = d->ldy;
+  p.npix = r.g.M; p.nrsc = r.g.K;
+  fill_gather(p, d, d->ldx, padded ? 1 : d->s, padded ? r.rf.rlp : d->c);
+  p.ldb = ldb; p.ldc = d->ldy;
   if (pool) fill_pool(p, d, argmax, ld_out);
-  fill_staging(p, MODE_FWD, (unsigned long long)d->n * d->h * d->w * d->ldx, (unsigned long long)g.K * run_ldb, d->r, run ? 1 : d->s);
+  fill_staging(p, MODE_FWD, (unsigned long long)d->n * d->h * d->w * d->ldx, (unsigned long long)r.g.K * ldb, d->r, padded ? 1 : d->s);
   rc = take_second_output(p, out2);
   if (rc != A3D_OK) return rc;
-  return launch_igemm(MODE_FWD, plan, g.avec, g.bvec, p, static_cast<char*>(ws) + ws_used, st);
+  return launch_igemm(MODE_FWD, r.plan, r.g.avec, r.g.bvec, p, static_cast<char*>(ws) + r.repack, st);
 }
 
 int a3d_conv2d_fwd(const a3d_conv_desc* d, const float* x, const float* w, const float* bias, float* y, int act,
@@ -800,18 +448,19 @@ int a3d_conv2d_fwd(const a3d_conv_desc* d, const float* x, const float* w, const
 // Which per-call repack of the filter does this forward do?  0 none, 1 bf16 image form, 2 conv3's [K/4][N][4], 3 window-run padding
 static int fwd_filter_form(const a3d_conv_desc* d, RunForm* rf) {
   if (check_desc(d) != A3D_OK || stencil1_applicable(d)) return 0;
-  if (bf16_image_form_ok(d, nullptr)) return 1;
-  if (conv3_applicable(d, nullptr)) return 2;
-  if (run_form_ok(d, nullptr, rf)) return 3;
+  const Operands o = launch_operands(nullptr, nullptr, nullptr, nullptr);      // the layout a launch with every operand on the 16-byte grid reads
+  if (bf16_image_form_ok(d, o, rf)) return 1;
+  if (conv3_applicable(d, o.x)) return 2;
+  if (run_form_ok(d, o.x, rf)) return 3;
   return 0;
 }
 
 size_t a3d_conv2d_fwd_prepared_filter_bytes(const a3d_conv_desc* d) {
   RunForm rf{};
   switch (fwd_filter_form(d, &rf)) {
-    case 1: return conv3b_applicable(d) ? conv3b_filter_bytes(d) : bf16_image_filter_bytes(d);
+    case 1: return conv3b_applicable(d) ? conv3b_filter_bytes(d) : rf.bytes;
     case 2: return conv3_ws_bytes(d);
-    case 3: return run_filter_bytes(d, rf);
+    case 3: return rf.bytes;
     default: return 0;
   }
 }
@@ -826,15 +475,9 @@ int a3d_conv2d_fwd_prepare_filter(const a3d_conv_desc* d, const float* w, void* 
   hipStream_t st = static_cast<hipStream_t>(stream);
   RunForm rf{};
   switch (fwd_filter_form(d, &rf)) {
-    case 1: return conv3b_applicable(d) ? conv3b_pack(d, w, prepared, st) : pad_filter_bf16(d, w, static_cast<__bf16*>(prepared), st);
+    case 1: return conv3b_applicable(d) ? conv3b_pack(d, w, prepared, st) : pad_filter(d, rf, true, w, prepared, st);
     case 2: return conv3_pack(d, w, static_cast<float*>(prepared), st);
-    default: {
-      const int np = (d->storage & A3D_STORE_W_BF16) ? d->k : (d->k + 3) / 4 * 4;
-      clear_stale_error();
-      hipLaunchKernelGGL(pad_filter_kernel, dim3((rf.kp * np + 255) / 256), dim3(256), 0, st, w, static_cast<float*>(prepared), d->r,
-                         rf.rl, rf.rlp, d->k, np);
-      return check_launch("pad_filter");
-    }
+    default: return pad_filter(d, rf, false, w, prepared, st);
   }
 }
 
@@ -850,11 +493,12 @@ int a3d_conv2d_pool_fwd(const a3d_conv_desc* d, const float* x, const float* w, 
 
 // One parity class (ph, pw) of a strided bwd-data as a stride-1 problem; false if the class has no pixels.
 struct BwdDClass {
-  int hc, wc, r0, s0, rp, sp, off_y, off_x;
+  int ph, pw, hc, wc, r0, s0, rp, sp, off_y, off_x;
   GemmProblem g;
 };
 static bool bwd_d_class(const a3d_conv_desc* d, int ph, int pw, BwdDClass* c) {
   const int st = d->stride;
+  c->ph = ph; c->pw = pw;
   c->hc = (d->h - ph + st - 1) / st;
   c->wc = (d->w - pw + st - 1) / st;
   if (c->hc <= 0 || c->wc <= 0) return false;
@@ -869,25 +513,57 @@ static bool bwd_d_class(const a3d_conv_desc* d, int ph, int pw, BwdDClass* c) {
   c->g.K = c->rp * c->sp * d->k;          // 0: no tap reaches this class, the launch only writes zeros
   return true;
 }
+// the classes that have pixels (a stride-1 conv is its one class); returns their number
+static int bwd_d_classes(const a3d_conv_desc* d, BwdDClass (&cls)[16]) {
+  int n = 0;
+  for (int ph = 0; ph < d->stride; ++ph)
+    for (int pw = 0; pw < d->stride; ++pw)
+      if (bwd_d_class(d, ph, pw, &cls[n])) ++n;
+  return n;
+}
+
+// One class as a GEMM over the tensors as stored, or (stride 1, the mask on the 16-byte grid too) the same offered to the LDS-DMA
+// kernel; tiles: the plan is this one, nothing is searched
+static Route bwd_d_gemm(const a3d_conv_desc* d, const BwdDClass& c, const Operands& o, GemmForm form, const GemmPlan* tiles = nullptr) {
+  Route r;
+  r.ok = form == kAsStored || (d->stride == 1 && !o.aux && ring_ok(d, o, A3D_STORE_Y_BF16 | A3D_STORE_W_BF16, o.x, c.rp * c.sp));
+  if (!r.ok) return r;
+  r.g = c.g;
+  if (o.y) r.g.avec = 1;
+  if (o.w) r.g.bvec = 1;
+  if (form == kLdsDma) { r.g.ring_ok = 1; r.g.avec = r.g.bvec = 4; }
+  if (o.known) storage_vecs(r.g, d->storage & A3D_STORE_Y_BF16, d->storage & A3D_STORE_W_BF16, d->storage & A3D_STORE_X_BF16);
+  r.plan = tiles ? *tiles : plan_gemm(r.g, d->precision);
+  r.bytes = r.plan.ws_bytes;
+  return r;
+}
 
 size_t a3d_conv2d_bwd_data_ws_bytes(const a3d_conv_desc* d) {
   if (check_desc(d) != A3D_OK) return 0;
-  if (d->stride == 1) {
-    size_t need = plan_gemm(bwd_d_problem(d), d->precision).ws_bytes;
-    const int both = A3D_STORE_Y_BF16 | A3D_STORE_W_BF16;
-    GemmProblem g = bwd_d_problem(d);
-    g.ring_ok = d->precision == A3D_PREC_BF16 && (d->storage & both) == both && d->c % 8 == 0 && d->k % 8 == 0;
-    g.avec = g.bvec = 4;
-    if (g.ring_ok) need = std::max(need, plan_gemm(g, d->precision).ws_bytes);
-    return need;
-  }
+  BwdDClass cls[16];
+  const int ncls = bwd_d_classes(d, cls);
   size_t need = 0;
-  for (int ph = 0; ph < d->stride; ++ph)
-    for (int pw = 0; pw < d->stride; ++pw) {
-      BwdDClass c;
-      if (bwd_d_class(d, ph, pw, &c)) need = std::max(need, plan_gemm(c.g, d->precision).ws_bytes);
-    }
+  for (int i = 0; i < ncls; ++i)
+    for (GemmForm form : {kAsStored, kLdsDma}) need = upto(need, bwd_d_gemm(d, cls[i], kOnGrid, form));
   return need;
+}
+
+// The parameters of one class's launch: the class is a stride-1 problem over dz
+static void fill_bwd_d_class(IgemmParams& p, const a3d_conv_desc* d, const BwdDClass& c, const float* dz, const float* w, float* dx,
+                             const float* relu_mask) {
+  p.A = dz; p.B = w; p.C = dx; p.mask = relu_mask;
+  p.npix = p.M; p.nrsc = p.K;
+  p.H = d->ho; p.W = d->wo; p.ld = d->ldy; p.pHW = d->ho * d->wo;
+  p.stride = 1; p.lstride = 0; p.pad_t = c.off_y; p.pad_l = c.off_x;
+  p.S = std::max(c.sp, 1); p.Cg = d->k; p.Cn = d->c;
+  p.div_phw = make_fastdiv(c.hc * c.wc); p.div_pw = make_fastdiv(c.wc);
+  p.div_c = make_fastdiv(d->k); p.div_s = make_fastdiv(std::max(c.sp, 1));
+  p.div_c_half = make_fastdiv(std::max(1, d->k / 2));
+  p.ldb = 0; p.ldc = d->ldx;
+  p.sub_step = d->stride; p.sub_ph = c.ph; p.sub_pw = c.pw; p.tap_r0 = c.r0; p.tap_s0 = c.s0; p.S_full = d->s;
+  p.outW = d->w; p.outHW = d->h * d->w;
+  fill_staging(p, MODE_BWD_D, (unsigned long long)d->n * d->ho * d->wo * d->ldy, (unsigned long long)d->r * d->s * d->c * d->k, c.rp,
+               c.sp);
 }
 
 int a3d_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w, float* dx, const float* relu_mask,
@@ -895,111 +571,96 @@ int a3d_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w,
   int rc = check_desc(d);
   if (rc != A3D_OK) return rc;
   A3D_CHECK_ARG(dz && w && dx, "conv2d_bwd_data: null tensor");
-  const bool vec_ok_a = aligned16(dz), vec_ok_b = aligned16(w);
+  if (!ws) ws_bytes = 0;
+  const Operands o = launch_operands(dx, w, dz, relu_mask);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  // stride 2, fp32: the (up to) four classes as ONE launch of 64x64 tiles when that alone fills the chip
-  IgemmMulti multi;
-  int n_multi = 0, multi_avec = 4, multi_bvec = 4;
-  unsigned multi_grid = 0;
-  long multi_tiles = 0;
-  double multi_flops = 0;
-  const bool try_multi = d->stride == 2 && d->precision == A3D_PREC_F32 && !d->storage && tune_int("A3D_FORCE_CFG", -1) < 0;
+  BwdDClass cls[16];
+  const int ncls = bwd_d_classes(d, cls);
+  // stride 2, fp32: the (up to) four classes as ONE launch of 64x64 tiles when that alone fills the chip; under 256 tiles that
+  // is too little work without split-K: one launch per class
+  long tiles64 = 0;
+  for (int i = 0; i < ncls; ++i) tiles64 += (long)((cls[i].g.M + 63) / 64) * ((cls[i].g.N + 63) / 64);
+  const bool multi32 = d->stride == 2 && d->precision == A3D_PREC_F32 && !d->storage && tune_int("A3D_FORCE_CFG", -1) < 0 && tiles64 >= 256;
   // ... and on bf16-stored tensors (BASELINE config 5's conv2d_4): one launch of the bf16 kernel's 128-row tiles
-  const int all16 = A3D_STORE_X_BF16 | A3D_STORE_W_BF16 | A3D_STORE_Y_BF16;
-  const bool try_multi16 = d->stride == 2 && d->precision == A3D_PREC_BF16 && (d->storage & all16) == all16 && vec_ok_a &&
-                           vec_ok_b && tune_int("A3D_FORCE_SPLITK", 0) <= 0;
-  int multi16_bn = 0;
-  for (int ph = 0; ph < d->stride; ++ph) {
-    for (int pw = 0; pw < d->stride; ++pw) {
-      BwdDClass c;
-      if (!bwd_d_class(d, ph, pw, &c)) continue;
-      GemmProblem g = c.g;
-      if (!vec_ok_a) g.avec = 1;
-      if (!vec_ok_b) g.bvec = 1;
-      IgemmParams p;
-      fill_common(p, g);
-      rc = apply_storage(p, g, d->precision, d->storage & A3D_STORE_Y_BF16, d->storage & A3D_STORE_W_BF16,
-                         d->storage & A3D_STORE_X_BF16, d->k, d->ldy, d->k, d->k, dz, w, dx);
-      if (rc != A3D_OK) return rc;
-      A3D_CHECK_ARG(!p.c16 || !relu_mask || aligned16(relu_mask), "conv2d_bwd_data: bf16 mask must be 16-byte aligned");
-      g.ring_ok = d->stride == 1 && p.a16 && p.b16 && d->precision == A3D_PREC_BF16 && d->k % 8 == 0 && d->ldy % 8 == 0 &&
-                  d->c % 8 == 0 && d->ldx % 8 == 0 && aligned16(dx) && (!relu_mask || aligned16(relu_mask)) && c.rp * c.sp <= 128;
-      GemmPlan plan = plan_gemm(g, d->precision);
-      A3D_CHECK_ARG(!d->storage || plan.prec == A3D_PREC_BF16, "conv2d_bwd_data: bf16 storage needs vectorisable operands");
-      if (try_multi) {                                   // 64x64 tiles, no split-K
-        plan = GemmPlan{};
-        plan.cfg = 4; plan.splitk = 1; plan.ktiles_per_split = std::max(1, (g.K + 31) / 32);
-        plan.tiles_m = (g.M + 63) / 64; plan.tiles_n = (g.N + 63) / 64;
-      }
-      const bool multi16 = try_multi16 && plan.prec == A3D_PREC_BF16;
-      if (multi16) {                                     // the bf16 kernel's tiles, no split-K
-        multi16_bn = plan.bf16_bn;
-        plan.splitk = 1; plan.ktiles_per_split = std::max(1, (g.K + 63) / 64); plan.ws_bytes = 0;
-      }
-      if (plan.ws_bytes > ws_bytes)
-        return set_error(A3D_EWORKSPACE, "conv2d_bwd_data: need %zu workspace bytes", plan.ws_bytes);
-      p.M = g.M; p.N = g.N; p.K = g.K;
-      p.A = dz; p.B = w; p.C = dx; p.mask = relu_mask;
-      p.npix = g.M; p.nrsc = g.K;
-      p.H = d->ho; p.W = d->wo; p.ld = d->ldy; p.pHW = d->ho * d->wo;
-      p.stride = 1; p.lstride = 0; p.pad_t = c.off_y; p.pad_l = c.off_x;      // the class is a stride-1 problem
-      p.S = std::max(c.sp, 1); p.Cg = d->k; p.Cn = d->c;
-      p.div_phw = make_fastdiv(c.hc * c.wc); p.div_pw = make_fastdiv(c.wc);
-      p.div_c = make_fastdiv(d->k); p.div_s = make_fastdiv(std::max(c.sp, 1));
-      p.div_c_half = make_fastdiv(std::max(1, d->k / 2));
-      p.ldb = 0; p.ldc = d->ldx;
-      p.sub_step = d->stride; p.sub_ph = ph; p.sub_pw = pw; p.tap_r0 = c.r0; p.tap_s0 = c.s0; p.S_full = d->s;
-      p.outW = d->w; p.outHW = d->h * d->w;
-      fill_staging(p, MODE_BWD_D, (unsigned long long)d->n * d->ho * d->wo * d->ldy,
-                   (unsigned long long)d->r * d->s * d->c * d->k, c.rp, c.sp);
-      if (try_multi || multi16) {
-        p.splitk = 1; p.ktiles_per_split = plan.ktiles_per_split; p.tiles_m = plan.tiles_m; p.tiles_n = plan.tiles_n;
-        p.slab = (size_t)p.M * p.N;
-        multi.p[n_multi++] = p;
-        multi_avec = std::min(multi_avec, g.avec); multi_bvec = std::min(multi_bvec, g.bvec);
-        multi_grid = std::max(multi_grid, (unsigned)((long)plan.tiles_m * plan.tiles_n));
-        multi_tiles += (long)plan.tiles_m * plan.tiles_n;
-        multi_flops += 2.0 * p.M * p.N * p.K;
-        continue;
-      }
-      rc = launch_igemm(MODE_BWD_D, plan, g.avec, g.bvec, p, ws, st);
-      if (rc != A3D_OK) return rc;
+  const bool multi16 = d->stride == 2 && d->precision == A3D_PREC_BF16 && stored16(d, kAll16) && !o.y && !o.w &&
+                       tune_int("A3D_FORCE_SPLITK", 0) <= 0;
+  IgemmMulti multi;
+  int avec = 4, bvec = 4, multi16_bn = 0;
+  unsigned multi_grid = 0;
+  double multi_flops = 0;                    // the classes' own, summed: a class runs only the taps that reach it
+  for (int i = 0; i < ncls; ++i) {
+    const BwdDClass& c = cls[i];
+    GemmPlan tiles64{};                      // multi32: 64x64 tiles, no split-K, no workspace
+    tiles64.cfg = 4; tiles64.splitk = 1; tiles64.ktiles_per_split = std::max(1, (c.g.K + 31) / 32);
+    tiles64.tiles_m = (c.g.M + 63) / 64; tiles64.tiles_n = (c.g.N + 63) / 64;
+    Route r = bwd_d_gemm(d, c, o, kLdsDma);
+    if (!r.ok) r = bwd_d_gemm(d, c, o, kAsStored, multi32 ? &tiles64 : nullptr);
+    IgemmParams p;
+    fill_common(p, r.g);
+    rc = apply_storage(p, d->precision, d->storage & A3D_STORE_Y_BF16, d->storage & A3D_STORE_W_BF16, d->storage & A3D_STORE_X_BF16,
+                       d->k, d->ldy, d->k, d->k, dz, w, dx);
+    if (rc != A3D_OK) return rc;
+    A3D_CHECK_ARG(!p.c16 || !o.aux, "conv2d_bwd_data: bf16 mask must be 16-byte aligned");
+    A3D_CHECK_ARG(!d->storage || r.plan.prec == A3D_PREC_BF16, "conv2d_bwd_data: bf16 storage needs vectorisable operands");
+    if (multi16) {                           // the bf16 kernel's tiles, no split-K, no workspace
+      multi16_bn = r.plan.bf16_bn;
+      r.plan.splitk = 1; r.plan.ktiles_per_split = std::max(1, (r.g.K + 63) / 64);
+    } else if (r.bytes > ws_bytes) {
+      return set_error(A3D_EWORKSPACE, "conv2d_bwd_data: need %zu workspace bytes", r.bytes);
     }
-  }
-  if (try_multi16 && n_multi > 0) {
-    a3d_timing_record rec = timing_record(MODE_BWD_D, A3D_PREC_BF16, 128, multi16_bn, 4, 8, 64, 4, 4, 0, d->n * d->h * d->w, d->c,
-                                          d->r * d->s * d->k);
-    rec.flops = multi_flops;                 // the classes' own, summed: a class runs only the taps that reach it
-    return timed_launch(rec, st, [&] { return launch_igemm_bf16_multi_bwd_d(multi16_bn, multi, multi_grid, (unsigned)n_multi, st); });
-  }
-  if (try_multi && n_multi > 0) {
-    if (multi_tiles < 256) {                 // too little work for 64x64 tiles without split-K: one launch per class
-      for (int i = 0; i < n_multi; ++i) {
-        IgemmParams& p = multi.p[i];
-        GemmProblem g = bwd_d_problem(d);
-        g.M = p.M; g.K = p.K; g.avec = multi_avec; g.bvec = multi_bvec;
-        GemmPlan plan = plan_gemm(g, d->precision);
-        if (plan.ws_bytes > ws_bytes)
-          return set_error(A3D_EWORKSPACE, "conv2d_bwd_data: need %zu workspace bytes", plan.ws_bytes);
-        rc = launch_igemm(MODE_BWD_D, plan, g.avec, g.bvec, p, ws, st);
-        if (rc != A3D_OK) return rc;
-      }
-      return A3D_OK;
+    fill_bwd_d_class(p, d, c, dz, w, dx, relu_mask);
+    if (!multi32 && !multi16) {
+      rc = launch_igemm(MODE_BWD_D, r.plan, r.g.avec, r.g.bvec, p, ws, st);
+      if (rc != A3D_OK) return rc;
+      continue;
     }
-    a3d_timing_record rec = timing_record(MODE_BWD_D, A3D_PREC_F32, 64, 64, 2, 4, 32, multi_avec, multi_bvec, 0, d->n * d->h * d->w,
-                                          d->c, d->r * d->s * d->k);
-    rec.flops = multi_flops;
-    return timed_launch(rec, st, [&] { return launch_igemm_multi_bwd_d(multi_avec, multi_bvec, multi, multi_grid, (unsigned)n_multi, st); });
+    p.splitk = 1; p.ktiles_per_split = r.plan.ktiles_per_split; p.tiles_m = r.plan.tiles_m; p.tiles_n = r.plan.tiles_n;
+    p.slab = (size_t)p.M * p.N;
+    multi.p[i] = p;
+    avec = std::min(avec, r.g.avec); bvec = std::min(bvec, r.g.bvec);
+    multi_grid = std::max(multi_grid, (unsigned)((long)r.plan.tiles_m * r.plan.tiles_n));
+    multi_flops += 2.0 * p.M * p.N * p.K;
   }
-  return A3D_OK;
+  if (!multi32 && !multi16) return A3D_OK;
+  a3d_timing_record rec = multi16 ? timing_record(MODE_BWD_D, A3D_PREC_BF16, 128, multi16_bn, 4, 8, 64, 4, 4, 0, d->n * d->h * d->w, d->c,
+                                                  d->r * d->s * d->k)
+                                  : timing_record(MODE_BWD_D, A3D_PREC_F32, 64, 64, 2, 4, 32, avec, bvec, 0, d->n * d->h * d->w, d->c,
+                                                  d->r * d->s * d->k);
+  rec.flops = multi_flops;
+  return timed_launch(rec, st, [&] {
+    return multi16 ? launch_igemm_bf16_multi_bwd_d(multi16_bn, multi, multi_grid, (unsigned)ncls, st)
+                   : launch_igemm_multi_bwd_d(avec, bvec, multi, multi_grid, (unsigned)ncls, st);
+  });
 }
 
 // bf16 x and bf16 dz, whole 16-byte pieces inside one filter tap, 31-bit byte offsets into x: the LDS-DMA kernel may take the
 // filter gradient (BiasAddGrad then comes from colsum_bf16)
-static bool bwd_f_ring_ok(const a3d_conv_desc* d) {
-  const int both = A3D_STORE_X_BF16 | A3D_STORE_Y_BF16;
-  return d->precision == A3D_PREC_BF16 && (d->storage & both) == both && d->c % 8 == 0 && d->ldx % 8 == 0 && d->k % 8 == 0 &&
-         d->ldy % 8 == 0 && (double)d->n * d->h * d->w * d->ldx * 2.0 < 2147483647.0 && colsum_bf16_ok(d->k) && d->ldy == d->k;
+static bool bwd_f_ring_ok(const a3d_conv_desc* d, const Operands& o) {
+  return d->precision == A3D_PREC_BF16 && stored16(d, A3D_STORE_X_BF16 | A3D_STORE_Y_BF16) && d->c % 8 == 0 && d->ldx % 8 == 0 &&
+         d->k % 8 == 0 && d->ldy % 8 == 0 && (double)d->n * d->h * d->w * d->ldx * 2.0 < 2147483647.0 && colsum_bf16_ok(d->k) &&
+         d->ldy == d->k && !o.w;
+}
+// The filter gradient as a GEMM: over the tensors as stored, the same offered to the LDS-DMA kernel, or in the window-run form
+// (the gradient of the PADDED filter into the workspace, unpadded afterwards)
+static Route bwd_f_gemm(const a3d_conv_desc* d, const Operands& o, GemmForm form) {
+  Route r;
+  r.ok = form == kRunForm ? run_form_ok(d, o.x, &r.rf, true) : form == kLdsDma ? bwd_f_ring_ok(d, o) : true;
+  if (!r.ok) return r;
+  GemmProblem& g = r.g;
+  g = bwd_f_problem(d);
+  if (o.x) g.avec = 1;
+  if (o.y) g.bvec = 1;
+  if (form == kRunForm) {
+    g.M = r.rf.kp; g.avec = r.rf.vec;
+    r.repack = r.rf.bytes;
+  }
+  if (o.known) storage_vecs(g, d->storage & A3D_STORE_X_BF16, d->storage & A3D_STORE_Y_BF16, false);
+  g.ring_ok = form == kLdsDma;
+  r.plan = plan_gemm(g, d->precision);
+  // BiasAddGrad: column sums of dz fused into the GEMM, one slab row per split; beside the LDS-DMA kernel, colsum_bf16's partials
+  if (r.plan.ring) r.bytes = r.plan.ws_bytes + (o.db ? colsum_bf16_ws_bytes(d->k) : 0);
+  else r.bytes = r.repack + r.plan.ws_bytes + (r.plan.splitk > 1 && o.db ? (size_t)r.plan.splitk * g.N * 4 : 0);
+  return r;
 }
 
 int a3d_conv2d_bwd_both_supported(const a3d_conv_desc* d) {
@@ -1032,12 +693,9 @@ static bool fewch_wanted(const a3d_conv_desc* d, bool pooled) {
   return !d->storage && fewch_bwdf_applicable(d, pooled) && tune_int("A3D_FEWCH", 1) != 0;
 }
 
-// the launch as the timing list sees it (a3d_timing_*): lds_dma 4 = fewch_bwdf_kernel, ms includes the slab reduction
 static int fewch_timed(const a3d_conv_desc* d, const float* x, int src, const void* dz, int ldz, const void* pooled_act,
                        const uint8_t* argmax, int ld_arg, float* dw, float* db, void* ws, hipStream_t st) {
-  return timed_launch(timing_record(MODE_BWD_F, A3D_PREC_F32, 128, (d->k + 31) / 32 * 32, 4, 4, 2, 1, 1, 4, d->r * d->s * d->c, d->k,
-                                    d->n * d->ho * d->wo),
-                      st, [&] { return fewch_bwd_filter(d, x, src, dz, ldz, pooled_act, argmax, ld_arg, dw, db, ws, st); });
+  return timed_launch(fewch_record(d), st, [&] { return fewch_bwd_filter(d, x, src, dz, ldz, pooled_act, argmax, ld_arg, dw, db, ws, st); });
 }
 
 // config 5: bf16 arithmetic on the fp32 image and bf16 pooled tensors (fewch16.hip); A3D_FEWCH16=0 (tuning processes): refused
@@ -1045,11 +703,13 @@ static bool fewch16_wanted(const a3d_conv_desc* d, bool pooled) {
   return !d->storage && fewch16_bwdf_applicable(d, pooled) && tune_int("A3D_FEWCH16", 1) != 0;
 }
 
+// the pooled filter gradient in fp32 arithmetic (float32 or bf16 pooled tensors)
+static bool fewch_pooled_ok(const a3d_conv_desc* d) { return !d->storage && fewch_bwdf_applicable(d, true); }
+
 size_t a3d_conv2d_bwd_filter_pooled_ws_bytes(const a3d_conv_desc* d) {
-  if (check_desc(d) != A3D_OK || d->storage) return 0;
+  if (check_desc(d) != A3D_OK) return 0;
   if (fewch16_wanted(d, true)) return fewch16_bwdf_ws_bytes(d, true);
-  if (!fewch_bwdf_applicable(d, true)) return 0;
-  return fewch_bwdf_ws_bytes(d, true);
+  return fewch_pooled_ok(d) ? fewch_bwdf_ws_bytes(d, true) : 0;
 }
 
 int a3d_conv2d_bwd_filter_pooled(const a3d_conv_desc* d, const float* x, const void* dpool, int ld_dpool, const void* pooled,
@@ -1066,11 +726,10 @@ int a3d_conv2d_bwd_filter_pooled(const a3d_conv_desc* d, const float* x, const v
     A3D_CHECK_ARG(fewch_extents_ok(d, true, ld_dpool, 2, ld_argmax), "conv2d_bwd_filter_pooled: pooled tensors of 2 GiB or more");
     if (fewch16_bwdf_ws_bytes(d, true) > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd_filter_pooled: workspace too small");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return timed_launch(timing_record(MODE_BWD_F, A3D_PREC_BF16, 128, (d->k + 31) / 32 * 32, 4, 4, 16, 1, 1, 4, d->r * d->s * d->c, d->k,
-                                      d->n * d->ho * d->wo),
-                        st, [&] { return fewch16_bwd_filter(d, x, true, dpool, ld_dpool, pooled, argmax, ld_argmax, dw, db, ws, st); });
+    return timed_launch(fewch16_record(d), st,
+                        [&] { return fewch16_bwd_filter(d, x, true, dpool, ld_dpool, pooled, argmax, ld_argmax, dw, db, ws, st); });
   }
-  A3D_CHECK_ARG(!d->storage && fewch_bwdf_applicable(d, true),
+  A3D_CHECK_ARG(fewch_pooled_ok(d),
                 "conv2d_bwd_filter_pooled: an unpadded conv of <= 4 densely packed float32 input channels and 33..96 filters (fp32 "
                 "arithmetic; or bf16 arithmetic with bf16 pooled tensors)");
   A3D_CHECK_ARG(ld_dpool >= d->k && ld_argmax >= d->k, "conv2d_bwd_filter_pooled: pixel strides below the filter count");
@@ -1086,23 +745,10 @@ int a3d_conv2d_bwd_filter_pooled(const a3d_conv_desc* d, const float* x, const v
 size_t a3d_conv2d_bwd_filter_ws_bytes(const a3d_conv_desc* d) {
   if (check_desc(d) != A3D_OK) return 0;
   if (stencil1_applicable(d)) return stencil1_bwdf_ws_bytes(d);
-  const size_t few = fewch_wanted(d, false) ? fewch_bwdf_ws_bytes(d, false) : 0;      // (an unaligned x falls back to the plans below)
-  GemmProblem g0 = bwd_f_problem(d);
-  GemmPlan plan = plan_gemm(g0, d->precision);       // the plan without the LDS-DMA kernel: a launch may fall back to it (a dw
-  size_t need = plan.ws_bytes + (plan.splitk > 1 ? (size_t)plan.splitk * d->k * 4 : 0);      // off the 16-byte grid: ADVICE r4)
-  if (bwd_f_ring_ok(d)) {
-    g0.ring_ok = 1;
-    GemmPlan pr = plan_gemm(g0, d->precision);
-    if (pr.ring) need = std::max(need, pr.ws_bytes + colsum_bf16_ws_bytes(d->k));
-  }
-  RunForm rf;
-  if (run_form_ok(d, nullptr, &rf, true)) {
-    GemmProblem g = bwd_f_problem(d);
-    g.M = rf.kp; g.avec = rf.vec;
-    GemmPlan pr = plan_gemm(g, d->precision);
-    need = std::max(need, run_filter_bytes(d, rf) + pr.ws_bytes + (pr.splitk > 1 ? (size_t)pr.splitk * d->k * 4 : 0));
-  }
-  return std::max(need, few);
+  size_t need = fewch_wanted(d, false) ? fewch_bwdf_ws_bytes(d, false) : 0;      // (an unaligned x falls back to the plans below)
+  // kAsStored: the plan without the LDS-DMA kernel, a launch may fall back to it (a dw off the 16-byte grid: ADVICE r4)
+  for (GemmForm form : {kAsStored, kLdsDma, kRunForm}) need = upto(need, bwd_f_gemm(d, kOnGrid, form));
+  return need;
 }
 
 int a3d_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* dz, float* dw, float* db, void* ws,
@@ -1110,6 +756,7 @@ int a3d_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* d
   int rc = check_desc(d);
   if (rc != A3D_OK) return rc;
   A3D_CHECK_ARG(x && dz && dw, "conv2d_bwd_filter: null tensor");
+  if (!ws) ws_bytes = 0;
   if (stencil1_applicable(d)) {
     A3D_CHECK_ARG(!d->storage, "conv2d_bwd_filter: single-output-channel convs take float32 tensors");
     if (stencil1_bwdf_ws_bytes(d) > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd_filter: workspace too small");
@@ -1119,47 +766,39 @@ int a3d_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* d
     if (fewch_bwdf_ws_bytes(d, false) > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd_filter: workspace too small");
     return fewch_timed(d, x, 0, dz, d->ldy, nullptr, nullptr, 0, dw, db, ws, static_cast<hipStream_t>(stream));
   }
-  GemmProblem g = bwd_f_problem(d);
-  if (!aligned16(x)) g.avec = 1;
-  if (!aligned16(dz)) g.bvec = 1;
-  RunForm rf{};
-  const bool run = run_form_ok(d, x, &rf, true) && ws && ws_bytes >= run_filter_bytes(d, rf);
-  size_t ws_used = 0;
-  float* out = dw;
-  if (run) {                                   // window-run form: gradient of the PADDED filter, unpadded afterwards
-    g.M = rf.kp; g.avec = rf.vec;
-    ws_used = run_filter_bytes(d, rf);
-    out = static_cast<float*>(ws);
-  }
+  Operands o = launch_operands(x, dw, dz, nullptr);
+  o.db = db != nullptr;
+  // the window-run form if the workspace holds the padded gradient; else the tensors as stored, on the LDS-DMA kernel where that may be
+  RunForm rf;
+  const bool run = run_form_ok(d, o.x, &rf, true) && rf.bytes <= ws_bytes;
+  const Route r = bwd_f_gemm(d, o, run ? kRunForm : bwd_f_ring_ok(d, o) ? kLdsDma : kAsStored);
+  const GemmPlan& plan = r.plan;
+  float* out = run ? static_cast<float*>(ws) : dw;
   IgemmParams p;
-  fill_common(p, g);
-  rc = apply_storage(p, g, d->precision, d->storage & A3D_STORE_X_BF16, d->storage & A3D_STORE_Y_BF16, false, d->c, d->ldx,
-                     -1, d->ldy, x, dz, dw);
+  fill_common(p, r.g);
+  rc = apply_storage(p, d->precision, d->storage & A3D_STORE_X_BF16, d->storage & A3D_STORE_Y_BF16, false, d->c, d->ldx, -1, d->ldy,
+                     x, dz, dw);
   if (rc != A3D_OK) return rc;
-  g.ring_ok = !run && p.a16 && p.b16 && bwd_f_ring_ok(d) && aligned16(dw);
-  GemmPlan plan = plan_gemm(g, d->precision);
   A3D_CHECK_ARG(!d->storage || plan.prec == A3D_PREC_BF16, "conv2d_bwd_filter: bf16 storage needs vectorisable operands");
-  size_t need = ws_used + plan.ws_bytes + (plan.splitk > 1 && db ? (size_t)plan.splitk * g.N * 4 : 0);
-  if (plan.ring) need = plan.ws_bytes + (db ? colsum_bf16_ws_bytes(d->k) : 0);
-  if (need > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd_filter: need %zu workspace bytes", need);
+  if (r.bytes > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd_filter: need %zu workspace bytes", r.bytes);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (plan.ring && db) {                           // the LDS-DMA kernel never holds dz in registers: BiasAddGrad on the side
     // a split launch ends in a reduction kernel anyway: that one adds the partial sums (one launch fewer per layer)
     float* parts = reinterpret_cast<float*>(static_cast<char*>(ws) + plan.ws_bytes);
     int nparts = 0;
-    rc = colsum_bf16(dz, g.K, d->k, d->ldy, plan.splitk > 1 ? nullptr : db, parts, &nparts, st);
+    rc = colsum_bf16(dz, r.g.K, d->k, d->ldy, plan.splitk > 1 ? nullptr : db, parts, &nparts, st);
     if (rc != A3D_OK) return rc;
     if (plan.splitk > 1) { p.dbias_parts = parts; p.dbias_parts_out = db; p.dbias_parts_n = nparts; }
     db = nullptr;
   }
   p.A = x; p.B = dz; p.C = out; p.dbias = db;     // BiasAddGrad = column sums of dz, fused into the same kernel
-  p.npix = g.K; p.nrsc = g.M;
+  p.npix = r.g.K; p.nrsc = r.g.M;
   fill_gather(p, d, d->ldx, run ? 1 : d->s, run ? rf.rlp : d->c);
   p.ldb = d->ldy; p.ldc = d->k;
   fill_staging(p, MODE_BWD_F, (unsigned long long)d->n * d->h * d->w * d->ldx, (unsigned long long)d->n * d->ho * d->wo * d->ldy, d->r,
                run ? 1 : d->s);
   if (run) { p.unpad_dst = dw; p.unpad_rl = rf.rl; p.unpad_rlp = rf.rlp; }
-  rc = launch_igemm(MODE_BWD_F, plan, g.avec, g.bvec, p, static_cast<char*>(ws) + ws_used, st);
+  rc = launch_igemm(MODE_BWD_F, plan, r.g.avec, r.g.bvec, p, static_cast<char*>(ws) + r.repack, st);
   if (rc != A3D_OK || !run || p.unpad_done) return rc;       // the split-K reduction stored the unpadded filter itself
   clear_stale_error();
   hipLaunchKernelGGL(unpad_filter_kernel, dim3((d->r * rf.rl * d->k + 255) / 256), dim3(256), 0, st, out, dw, d->r,
@@ -1211,8 +850,9 @@ int a3d_dense_fwd_ex2(int m, int k, int n, const float* x, const float* w, const
   if (!aligned16(w)) g.bvec = 1;
   IgemmParams p;
   fill_common(p, g);
-  rc = apply_storage(p, g, precision, storage & A3D_STORE_X_BF16, storage & A3D_STORE_W_BF16, false, k, k, n, n, x, w, y);
+  rc = apply_storage(p, precision, storage & A3D_STORE_X_BF16, storage & A3D_STORE_W_BF16, false, k, k, n, n, x, w, y);
   if (rc != A3D_OK) return rc;
+  storage_vecs(g, p.a16, p.b16, p.c16);
   g.ring_ok = p.a16 && p.b16 && precision == A3D_PREC_BF16 && k % 8 == 0 && n % 8 == 0 && aligned16(y) && act != A3D_ACT_SIGMOID;
   g.need_reduce = ncols_y != n;                  // rows narrower than the GEMM are stored by the split-K reduction: plan one
   GemmPlan plan = plan_gemm(g, precision);
@@ -1260,9 +900,10 @@ int a3d_dense_bwd_data_ex2(int m, int k, int n, const float* dz, const float* w,
   if (!aligned16(w)) g.bvec = 1;
   IgemmParams p;
   fill_common(p, g);
-  rc = apply_storage(p, g, precision, storage & A3D_STORE_Y_BF16, storage & A3D_STORE_W_BF16, storage & A3D_STORE_X_BF16, n, n, n, n,
-                     dz, w, dx);
+  rc = apply_storage(p, precision, storage & A3D_STORE_Y_BF16, storage & A3D_STORE_W_BF16, storage & A3D_STORE_X_BF16, n, n, n, n, dz, w,
+                     dx);
   if (rc != A3D_OK) return rc;
+  storage_vecs(g, p.a16, p.b16, p.c16);
   g.ring_ok = p.a16 && p.b16 && precision == A3D_PREC_BF16 && k % 8 == 0 && n % 8 == 0 && aligned16(dx) &&
               (!mask || (aligned16(mask) && mask_act == A3D_ACT_RELU));
   GemmPlan plan = plan_gemm(g, precision);

@@ -1,5 +1,5 @@
 // igemm_plan.cc — the tile / split-K planner of the implicit-GEMM kernels: which kernel and tile a GEMM problem runs on,
-// how its K axis is split, and the workspace that takes.  Host code only; the launches are igemm_host.hip's.
+// how its K axis is split, and the workspace that takes.  Host code only; the launches are igemm_launch.hip's.
 #include <algorithm>
 #include <array>
 #include <map>
