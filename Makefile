@@ -69,7 +69,8 @@ SCRIPT := python3 -O -m torch.distributed.run --nnodes=1 --nproc-per-node ${GPUS
 endif
 
 # flags that are not the reference's go through TRAIN_ARGS, e.g. TRAIN_ARGS="--beta2 0.999 --augment eigen", or for depth
-# maps with holes (raw Kinect frames, Make3D) TRAIN_ARGS="--min-depth 0 --max-depth 0.99"
+# maps with holes (raw Kinect frames, Make3D) TRAIN_ARGS="--min-depth 0 --max-depth 0.99", or for MODEL=dcnf
+# TRAIN_ARGS="--train-pairwise --pairwise-texture" (the pairwise weights learn, over three similarities)
 TRAIN_ARGS ?=
 .PHONY: train
 train: ${DATA_DIR}

@@ -148,6 +148,12 @@ PAIR_SIGNATURES = {
     'a3dp_sgd_apply_floor': (c_int, [c_size_t, _P, _P, c_float, c_float, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_texture.h declares (NON-REFERENCE extension, prefix a3dt_)
+TEXTURE_SIGNATURES = {
+    'a3dt_superpixel_lbp_hist': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P]),
+    'a3dt_pair_similarity3': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, c_int, _P, _P, c_float, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -163,7 +169,8 @@ def load():
     # the runtime copy torch initialises: two HIP runtimes in one process cannot both own the device.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(PAIR_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(PAIR_SIGNATURES.items())
+                              + list(TEXTURE_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -56,6 +56,10 @@ def main(argv=None):
         logger.error(f'--train-pairwise learns the pairwise weights of the CRF of --model dcnf (Liu et al. 2015): '
                      f'{args.model or "(no model)"} has no such layer.')
         return 2
+    if args.pairwise_texture and not hasattr(getattr(models, args.model, None), 'pairwise_texture'):
+        logger.error(f'--pairwise-texture adds the texture similarity to the pairwise part of the CRF of --model dcnf '
+                     f'(Liu et al. 2015): {args.model or "(no model)"} has no such part.')
+        return 2
     if args.min_depth is not None or args.max_depth is not None:
         lo = 0. if args.min_depth is None else args.min_depth
         hi = float('inf') if args.max_depth is None else args.max_depth
@@ -121,6 +125,8 @@ def setup_model(args, rank=0, world=1):
                                  float('inf') if args.max_depth is None else args.max_depth)
     if hasattr(model, 'train_pairwise'):                                 # main() has refused the models that have none
         model.train_pairwise = bool(args.train_pairwise)
+    if hasattr(model, 'pairwise_texture'):
+        model.pairwise_texture = bool(args.pairwise_texture)
     inputs, targets = data.inputs(args.datadir, args.dataset, args.batchsize, rank=rank, world=world,
                                   seed=args.seed + rank)
     return model(inputs, targets)
@@ -167,10 +173,14 @@ class Session:
         latest = latest_checkpoint(self.dir) if self.dir else None
         if latest:
             self.log.info(f'Restoring {latest}')
-            if tfckpt.is_bundle(latest):                      # a checkpoint written by TensorFlow (or --tf-checkpoints)
-                rep.load_tf_variables(tfckpt.read_bundle(latest))
-            else:
-                rep.load_state_dict(torch.load(latest, map_location=rep.device))
+            try:
+                if tfckpt.is_bundle(latest):                  # a checkpoint written by TensorFlow (or --tf-checkpoints)
+                    rep.load_tf_variables(tfckpt.read_bundle(latest))
+                else:
+                    rep.load_state_dict(torch.load(latest, map_location=rep.device))
+            except ValueError:                                # refused (dcnf: a [2,1] / [3,1] pairwise kernel across
+                self.op.pipeline.close()                      # --pairwise-texture): __exit__ will not run
+                raise
         if self.world > 1:                                    # non-chief replicas take the chief's state
             import torch.distributed as dist
             rep.broadcast_state(dist, 0)
@@ -343,7 +353,7 @@ def latest_checkpoint(ckptdir):
 
 def parse_args(argv=None):
     """The reference's flags verbatim (src/ann3depth.py:221-254), plus --beta2 / --augment / --min-depth / --max-depth /
-    --train-pairwise / --seed / --trace-every / --profiler."""
+    --train-pairwise / --pairwise-texture / --seed / --trace-every / --profiler."""
     parser = argparse.ArgumentParser()
     parser.add_argument('dataset', default='nyu', type=str, help='The dataset to use.')
     parser.add_argument('--model', '-m', default='', type=str, help='Enter a model name.')
@@ -377,6 +387,11 @@ def parse_args(argv=None):
                         help='NON-REFERENCE: learn the pairwise dense layer of the CRF (dcnf only). The reference leaves it at '
                              'its initial draw (TF 1.3 has no gradient for scatter_nd_update); with this flag the loss is also '
                              'differentiated through the CRF matrix and the layer descends at 0.1, kept >= 0 (Liu et al. 2015).')
+    parser.add_argument('--pairwise-texture', action='store_true',
+                        help='NON-REFERENCE: a third pairwise similarity for the CRF (dcnf only), texture disparity over '
+                             'local-binary-pattern histograms of the superpixels (Liu et al. 2015); the pairwise kernel is '
+                             '[3,1], and a checkpoint with a [2,1] kernel is refused. Meant to go with --train-pairwise: '
+                             'without it the layer keeps its initial draw, as the reference\'s does.')
     parser.add_argument('--seed', default=0, type=int, help='Shuffle-queue seed.')
     parser.add_argument('--tf-checkpoints', action='store_true',
                         help='Also write every checkpoint as a TensorFlow V2 bundle (model.ckpt-N.index/.data-*).')

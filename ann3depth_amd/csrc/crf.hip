@@ -6,11 +6,13 @@
 // assumption).  All of it is tiny next to the unary conv stack; the kernels are written for clarity, not speed.
 // NON-REFERENCE (include/a3d_pairwise.h, --train-pairwise): the same loss kernel can also carry the identity through its
 // LU and write d loss / d r, the gradient TF 1.3 lacks; pair_dense_bwd_kernel takes it to the pairwise dense layer and
-// sgd_floor_kernel keeps that layer's weights >= 0 (Liu et al. 2015, eq. 9-14).
+// sgd_floor_kernel keeps that layer's weights >= 0 (Liu et al. 2015, eq. 9-14).  include/a3d_texture.h
+// (--pairwise-texture) adds the paper's third similarity, texture disparity over local-binary-pattern histograms.
 #include <algorithm>
 
 #include "a3d_internal.h"
 #include "a3d_pairwise.h"
+#include "a3d_texture.h"
 
 namespace a3d {
 
@@ -69,13 +71,54 @@ __global__ __launch_bounds__(256) void superpixel_hist_kernel(const float* __res
   hist[((size_t)b * rows * cols + p) * 256 + threadIdx.x] = (float)bins[threadIdx.x];
 }
 
-// similarity() of both feature kinds for one (image, pair) + the pairwise dense layer (2 -> 1).  A pair with an index
-// outside [0, nsp) gets NaN similarities and a NaN r in every image; the other pairs do not notice.
+// NON-REFERENCE (include/a3d_texture.h, --pairwise-texture): local-binary-pattern histogram of every superpixel, the
+// texture observation of Liu et al. 2015.  One block per (image, superpixel).  The (sp + 2)^2 grey values of the block
+// and its one-pixel halo are staged in LDS once: the halo comes from the IMAGE (the neighbouring superpixels) and is
+// clamped at the image border, where a clamped neighbour can be the pixel itself.  Bit k of a pixel's code is set iff
+// neighbour k >= centre (false with a NaN on either side, true for -0 >= +0); the code is the bin.  Integer LDS
+// atomics: the counts do not depend on the order.  Every global index is clamped into the image, every tile index is
+// below (sp + 2)^2 <= kLbpTile.
+constexpr int kMaxTextureSp = A3DT_MAX_SP;
+constexpr int kLbpTile = (kMaxTextureSp + 2) * (kMaxTextureSp + 2);      // 3025 floats = 12100 bytes of LDS
+__global__ __launch_bounds__(256) void superpixel_lbp_hist_kernel(const float* __restrict__ x, float* __restrict__ hist,
+                                                                  int h, int w, int sp) {
+  __shared__ float tile[kLbpTile];
+  __shared__ int bins[256];
+  const int cols = w / sp, rows = h / sp;
+  const int p = blockIdx.x % (rows * cols), b = blockIdx.x / (rows * cols);
+  const int y0 = (p / cols) * sp - 1, x0 = (p % cols) * sp - 1;      // the tile's corner in the image, halo included
+  const int tw = sp + 2;
+  bins[threadIdx.x] = 0;
+  for (int i = threadIdx.x; i < tw * tw; i += 256) {
+    const int yy = min(max(y0 + i / tw, 0), h - 1), xx = min(max(x0 + i % tw, 0), w - 1);
+    const float* px = x + (((size_t)b * h + yy) * w + xx) * 3;
+    tile[i] = (px[0] + px[1] + px[2]) / 3.f;                          // pair_similarity_kernel's grey value
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < sp * sp; i += 256) {
+    const float* c = tile + (i / sp + 1) * tw + i % sp + 1;
+    const float g = c[0];
+    const int code = (c[-tw - 1] >= g ? 1 : 0) | (c[-tw] >= g ? 2 : 0) | (c[-tw + 1] >= g ? 4 : 0) | (c[1] >= g ? 8 : 0) |
+                     (c[tw + 1] >= g ? 16 : 0) | (c[tw] >= g ? 32 : 0) | (c[tw - 1] >= g ? 64 : 0) | (c[-1] >= g ? 128 : 0);
+    atomicAdd(&bins[code], 1);
+  }
+  __syncthreads();
+  hist[((size_t)b * rows * cols + p) * 256 + threadIdx.x] = (float)bins[threadIdx.x];
+}
+
+// similarity() of the feature kinds for one (image, pair) + the pairwise dense layer (K -> 1).  K = 2: colour and
+// colour histogram, the reference's (a3d_pair_similarity).  K = 3 (a3dt_pair_similarity3, NON-REFERENCE) adds the texture
+// similarity from the LBP histograms `lbp`, the distance of the two frequency histograms; the first two similarities
+// come from the same operations in the same order in both.  A pair with an index outside [0, nsp) gets NaN
+// similarities and a NaN r in every image; the other pairs do not notice.
+template <int K>
 __global__ __launch_bounds__(256) void pair_similarity_kernel(const float* __restrict__ x, const float* __restrict__ hist,
+                                                              const float* __restrict__ lbp,
                                                               const int* __restrict__ left, const int* __restrict__ right,
                                                               const float* __restrict__ dw, const float* __restrict__ db,
                                                               float* __restrict__ sims, float* __restrict__ r, int h,
                                                               int w, int sp, int npairs, float gamma) {
+  static_assert(K == 2 || K == 3, "two or three similarities per pair");
   __shared__ float red[4];
   const int cols = w / sp, nsp = (h / sp) * cols;
   const int q = blockIdx.x % npairs, b = blockIdx.x / npairs;
@@ -83,7 +126,8 @@ __global__ __launch_bounds__(256) void pair_similarity_kernel(const float* __res
   if (pl < 0 || pl >= nsp || pr < 0 || pr >= nsp) {       // the whole block: nothing is indexed with a bad superpixel
     if (threadIdx.x == 0) {
       const size_t o = (size_t)b * npairs + q;
-      sims[2 * o] = sims[2 * o + 1] = r[o] = __builtin_nanf("");
+      for (int j = 0; j < K; ++j) sims[K * o + j] = __builtin_nanf("");
+      r[o] = __builtin_nanf("");
     }
     return;
   }
@@ -101,12 +145,23 @@ __global__ __launch_bounds__(256) void pair_similarity_kernel(const float* __res
   const float* hr = hist + ((size_t)b * nsp + pr) * 256;
   const float dh = hl[threadIdx.x] - hr[threadIdx.x];
   const float sh = block_sum_256(dh * dh, red);
+  float st = 0.f;
+  if (K == 3) {                                           // integer counts, S_t < 2^24: exact in any order
+    const float dt = lbp[((size_t)b * nsp + pl) * 256 + threadIdx.x] - lbp[((size_t)b * nsp + pr) * 256 + threadIdx.x];
+    st = block_sum_256(dt * dt, red);
+  }
   if (threadIdx.x == 0) {
     const float cdiff = expf(-gamma * sqrtf(sc)), hdiff = expf(-gamma * sqrtf(sh));
     const size_t o = (size_t)b * npairs + q;
-    sims[2 * o] = cdiff;
-    sims[2 * o + 1] = hdiff;
-    r[o] = cdiff * dw[0] + hdiff * dw[1] + db[0];
+    sims[K * o] = cdiff;
+    sims[K * o + 1] = hdiff;
+    if (K == 2) {
+      r[o] = cdiff * dw[0] + hdiff * dw[1] + db[0];
+    } else {
+      const float tdiff = expf(-gamma * (sqrtf(st) / (float)(sp * sp)));
+      sims[K * o + 2] = tdiff;
+      r[o] = ((cdiff * dw[0] + hdiff * dw[1]) + tdiff * dw[2]) + db[0];
+    }
   }
 }
 
@@ -422,9 +477,30 @@ int a3d_pair_similarity(int n, int h, int w, const float* x, int sp, const float
   A3D_CHECK_ARG(n > 0 && sp > 0 && h % sp == 0 && w % sp == 0 && npairs > 0 && x && hist && left && right && dense_w &&
                     dense_b && sims && r, "pair_similarity: bad arguments");
   clear_stale_error();
-  hipLaunchKernelGGL(pair_similarity_kernel, dim3(n * npairs), dim3(256), 0, static_cast<hipStream_t>(stream), x, hist,
-                     left, right, dense_w, dense_b, sims, r, h, w, sp, npairs, gamma);
+  hipLaunchKernelGGL(pair_similarity_kernel<2>, dim3(n * npairs), dim3(256), 0, static_cast<hipStream_t>(stream), x, hist,
+                     nullptr, left, right, dense_w, dense_b, sims, r, h, w, sp, npairs, gamma);
   return check_launch("pair_similarity");
+}
+
+int a3dt_superpixel_lbp_hist(int n, int h, int w, const float* x, int sp, float* hist, void* stream) {
+  A3D_CHECK_ARG(n > 0 && h > 0 && w > 0 && sp > 0 && sp <= kMaxTextureSp && h % sp == 0 && w % sp == 0 && x && hist,
+                "superpixel_lbp_hist: bad arguments (superpixel edge at most %d)", kMaxTextureSp);
+  clear_stale_error();
+  hipLaunchKernelGGL(superpixel_lbp_hist_kernel, dim3(n * (h / sp) * (w / sp)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), x, hist, h, w, sp);
+  return check_launch("superpixel_lbp_hist");
+}
+
+int a3dt_pair_similarity3(int n, int h, int w, const float* x, int sp, const float* hist, const float* lbp_hist,
+                          const int32_t* left, const int32_t* right, int npairs, const float* dense_w,
+                          const float* dense_b, float gamma, float* sims, float* r, void* stream) {
+  A3D_CHECK_ARG(n > 0 && h > 0 && w > 0 && sp > 0 && sp <= kMaxTextureSp && h % sp == 0 && w % sp == 0 && npairs > 0 &&
+                    x && hist && lbp_hist && left && right && dense_w && dense_b && sims && r,
+                "pair_similarity3: bad arguments (superpixel edge at most %d)", kMaxTextureSp);
+  clear_stale_error();
+  hipLaunchKernelGGL(pair_similarity_kernel<3>, dim3(n * npairs), dim3(256), 0, static_cast<hipStream_t>(stream), x, hist,
+                     lbp_hist, left, right, dense_w, dense_b, sims, r, h, w, sp, npairs, gamma);
+  return check_launch("pair_similarity3");
 }
 
 // a3d_crf_loss (dr == nullptr) and a3dp_crf_loss_grad: the same two launches, the first one in its other instantiation

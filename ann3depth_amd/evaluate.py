@@ -229,17 +229,29 @@ def main(argv=None):
         return 2
     if not torch.cuda.is_available():
         raise RuntimeError('ann3depth_amd needs an MI355X: evaluation has no CPU fallback')
-    from .models import DCNFReplica, MSDNReplica
+    from .models import DCNF_PAIR_PREFIX, DCNFReplica, MSDNReplica
     dev = torch.device('cuda', torch.cuda.current_device())
+    _say(f'restoring {ckpt}')
+    bundle = tfckpt.is_bundle(ckpt)                  # as ann3depth.Session.__enter__ restores
+    state = tfckpt.read_bundle(ckpt) if bundle else torch.load(ckpt, map_location=dev)
+    texture = False
     if args.model == 'dcnf':
-        replica = DCNFReplica(args.batchsize, device=dev, precision=args.precision)
+        # the checkpoint says how many similarities its pairwise layer weighs: 2, or 3 with --pairwise-texture
+        name = DCNF_PAIR_PREFIX + 'kernel'
+        shape = tuple(np.shape(state[name])) if name in state else None
+        if shape not in ((2, 1), (3, 1)):
+            _say(f'{ckpt}: {name} has shape {None if shape is None else list(shape)}; a dcnf checkpoint holds a [2, 1] '
+                 f'kernel, or a [3, 1] one when it was trained with --pairwise-texture.')
+            inputs.pipeline.close()
+            return 2
+        texture = shape == (3, 1)
+        replica = DCNFReplica(args.batchsize, device=dev, precision=args.precision, pairwise_texture=texture)
     else:
         replica = MSDNReplica(args.batchsize, device=dev, precision=args.precision, keep_dense_grads=False)
-    _say(f'restoring {ckpt}')
-    if tfckpt.is_bundle(ckpt):                       # as ann3depth.Session.__enter__ restores
-        replica.load_tf_variables(tfckpt.read_bundle(ckpt))
+    if bundle:
+        replica.load_tf_variables(state)
     else:
-        replica.load_state_dict(torch.load(ckpt, map_location=dev))
+        replica.load_state_dict(state)
     step = replica.global_step
     pipeline = inputs.pipeline
     evaluator = DCNFEvaluator if args.model == 'dcnf' else Evaluator
@@ -260,6 +272,8 @@ def main(argv=None):
            'resolution': args.resolution, 'precision': args.precision,
            'min_depth': args.min_depth, 'max_depth': args.max_depth, 'clamp_lo': args.clamp_lo, 'clamp_hi': args.clamp_hi,
            **res}
+    if texture:
+        out['pairwise_texture'] = True
     if args.predictions:
         np.save(args.predictions, torch.cat(ev.predictions).cpu().numpy() if ev.predictions else
                 np.zeros((0,) + ev.prediction_shape, np.float32))

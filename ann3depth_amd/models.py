@@ -1249,15 +1249,24 @@ class DCNFReplica:
     dz bits), ops.pair_dense_bwd takes it to the layer's kernel and bias, and the `pairwise` group descends at its
     learning rate under the projection onto kernel, bias >= 0 (ops.sgd_apply_floor), which construction applies once
     to the initial values.  The unary group's step is the bits it would be without the flag, given the same pairwise
-    values.  Off (the default), no launch and no buffer of the step differs from the reference form."""
+    values.  Off (the default), no launch and no buffer of the step differs from the reference form.
+
+    pairwise_texture (NON-REFERENCE, --pairwise-texture): the paper's third pairwise observation, texture disparity over
+    local-binary-pattern histograms (include/a3d_texture.h).  The dense layer's kernel is [3,1] under the same variable
+    name, drawn from the same stream; the forward launches ops.superpixel_lbp_hist and ops.pair_similarity3 in place of
+    ops.pair_similarity.  Meant to go with train_pairwise (the backward reads K from sims); without it the layer keeps
+    its draw.  A [2,1] kernel is refused at restore, as a [3,1] one is without the argument.  Off (the default),
+    construction and every launch are what they are without it."""
     uses_dropout = False
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, global_step=0, reducer=None,
-                 precision='fp32', train_pairwise=False):
+                 precision='fp32', train_pairwise=False, pairwise_texture=False):
         self.B = batchsize
         self.device = dev = torch.device(device)
         self.reducer = reducer
         self.train_pairwise = bool(train_pairwise)
+        self.pairwise_texture = bool(pairwise_texture)
+        self.nsims = 3 if self.pairwise_texture else 2
         self.global_step = global_step
         self.unary = DCNFUnary(batchsize, dev, params=params, seed=seed, precision=precision)
         self.rows, self.cols = DCNF_IMG_H // DCNF_SP, DCNF_IMG_W // DCNF_SP
@@ -1266,14 +1275,15 @@ class DCNFReplica:
         left, right = dcnf_pair_indices(self.rows, self.cols)
         self.left = torch.tensor(left, dtype=torch.int32, device=dev)
         self.right = torch.tensor(right, dtype=torch.int32, device=dev)
-        pshapes = collections.OrderedDict([(DCNF_PAIR_PREFIX + 'kernel', (2, 1)), (DCNF_PAIR_PREFIX + 'bias', (1,))])
+        pshapes = collections.OrderedDict([(DCNF_PAIR_PREFIX + 'kernel', (self.nsims, 1)), (DCNF_PAIR_PREFIX + 'bias', (1,))])
         self.pair_group = ParamGroup('pairwise', 0.1, pshapes, dev, slots=False)
         if params is None or DCNF_PAIR_PREFIX + 'kernel' not in params:
             rng = np.random.default_rng(seed + 1)
-            pw = {DCNF_PAIR_PREFIX + 'kernel': glorot_uniform(rng, (2, 1)),
+            pw = {DCNF_PAIR_PREFIX + 'kernel': glorot_uniform(rng, (self.nsims, 1)),
                   DCNF_PAIR_PREFIX + 'bias': np.zeros((1,), np.float32)}
         else:
             pw = params
+            self._check_pair_kernel(np.shape(pw[DCNF_PAIR_PREFIX + 'kernel']), 'params')
         for n in pshapes:
             self.pair_group.view(self.pair_group.var, n).copy_(
                 torch.from_numpy(np.ascontiguousarray(pw[n], np.float32)))
@@ -1282,6 +1292,8 @@ class DCNFReplica:
         self.groups = collections.OrderedDict([('unary', self.unary.group), ('pairwise', self.pair_group)])
         self.depths240 = torch.empty((batchsize, DCNF_IMG_H, DCNF_IMG_W, 1), device=dev)
         self.hist = torch.empty((batchsize, self.nsp, 256), device=dev)
+        if self.pairwise_texture:
+            self.lbp = torch.empty((batchsize, self.nsp, 256), device=dev)
         self.y = torch.empty((batchsize, self.nsp, 1), device=dev)
         self.output = torch.empty((batchsize, DCNF_IMG_H, DCNF_IMG_W, 1), device=dev)
         self.sims = self.r = self.loss = self.loss_per_image = self.dz = self.dr = None
@@ -1294,6 +1306,26 @@ class DCNFReplica:
     def pair_grad(self, name):
         return self.pair_group.view(self.pair_group.grad, DCNF_PAIR_PREFIX + name)
 
+    def _check_pair_kernel(self, shape, what):
+        """The pairwise kernel about to be restored has this replica's number of similarities, or ValueError."""
+        want = (self.nsims, 1)
+        if tuple(shape) != want:
+            raise ValueError(f'{what}: {DCNF_PAIR_PREFIX}kernel has shape {list(shape)}, this replica\'s is {list(want)} '
+                             f'(pairwise_texture={self.pairwise_texture}: [3, 1] with --pairwise-texture, [2, 1] without)')
+
+    def _pairwise(self):
+        """The similarities of every pair and the pair weights r from the resized images (src/models.py:112-127)."""
+        x = self.unary.resized
+        ops.superpixel_hist(x, DCNF_SP, self.hist)                                        # :112-113
+        kernel, bias = self.pair_var('kernel'), self.pair_var('bias')
+        if self.pairwise_texture:
+            ops.superpixel_lbp_hist(x, DCNF_SP, self.lbp)
+            self.sims, self.r = ops.pair_similarity3(x, DCNF_SP, self.hist, self.lbp, self.left, self.right, kernel, bias,
+                                                     DCNF_GAMMA)
+        else:
+            self.sims, self.r = ops.pair_similarity(x, DCNF_SP, self.hist, self.left, self.right, kernel, bias,
+                                                    DCNF_GAMMA)                           # :115-127
+
     def forward(self, images, depths):
         """z, r and the loss; leaves d loss / d z in self.dz."""
         self.unary.forward(images)                                                        # src/models.py:180,183
@@ -1303,9 +1335,7 @@ class DCNFReplica:
         """Everything after the unary stack: target superpixels, pairwise r, CRF loss and d loss / d z."""
         u = self.unary
         ops.resize_bilinear_tf1(depths, self.depths240)                                   # src/models.py:181
-        ops.superpixel_hist(u.resized, DCNF_SP, self.hist)                                # :112-113
-        self.sims, self.r = ops.pair_similarity(u.resized, DCNF_SP, self.hist, self.left, self.right,
-                                                self.pair_var('kernel'), self.pair_var('bias'), DCNF_GAMMA)  # :115-127
+        self._pairwise()
         ops.superpixel_mean(self.depths240, DCNF_SP, self.y)                              # :131-132
         crf_args = (u.z.view(self.B, self.nsp), self.y.view(self.B, self.nsp), self.r, self.left, self.right, DCNF_EPSILON)
         if self.train_pairwise:                                                           # one launch, not two
@@ -1331,9 +1361,7 @@ class DCNFReplica:
         if n < B:
             u.resized[n:].zero_()
         u.forward_resized(record_argmax=False)
-        ops.superpixel_hist(u.resized, DCNF_SP, self.hist)
-        self.sims, self.r = ops.pair_similarity(u.resized, DCNF_SP, self.hist, self.left, self.right,
-                                                self.pair_var('kernel'), self.pair_var('bias'), DCNF_GAMMA)
+        self._pairwise()
         self.crf, self.status = ops.crf_map(u.z.view(B, self.nsp), self.r, self.left, self.right, self.crf, self.status)
         return u.z.view(B, self.rows, self.cols), self.crf.view(B, self.rows, self.cols)
 
@@ -1396,6 +1424,7 @@ class DCNFReplica:
         return sd
 
     def load_state_dict(self, sd):
+        self._check_pair_kernel(sd[DCNF_PAIR_PREFIX + 'kernel'].shape, 'load_state_dict')
         for g in self.groups.values():
             for n in g.offsets:
                 g.view(g.var, n).copy_(sd[n])
@@ -1404,6 +1433,7 @@ class DCNFReplica:
     def load_tf_variables(self, tensors):
         """Restore from a TensorFlow checkpoint's whole tensors (the reference's dcnf partitions its variables, which
         tfckpt.read_bundle refuses; a bundle written by this build loads)."""
+        self._check_pair_kernel(np.shape(tensors[DCNF_PAIR_PREFIX + 'kernel']), 'load_tf_variables')
         for g in self.groups.values():
             for n in g.offsets:
                 g.view(g.var, n).copy_(torch.from_numpy(np.ascontiguousarray(tensors[n], np.float32)))
@@ -1582,13 +1612,14 @@ class _DistributedConvolutionalNeuralFields:
     precision = 'fp32'
     beta2 = None         # accepted for symmetry with msdn; gradient descent has no beta
     train_pairwise = False   # NON-REFERENCE, --train-pairwise: the pairwise dense layer learns, >= 0 (see DCNFReplica)
+    pairwise_texture = False  # NON-REFERENCE, --pairwise-texture: LBP texture disparity as a third similarity (see DCNFReplica)
 
     def __call__(self, images, depths, train=True):
         assert images.pipeline is depths.pipeline, 'inputs and targets must come from the same data.inputs() call'
         self.train = train
         replica = DCNFReplica(images.pipeline.B, device=torch.device('cuda', torch.cuda.current_device()),
                               seed=self.seed, reducer=self.reducer, precision=self.precision,
-                              train_pairwise=self.train_pairwise and train)
+                              train_pairwise=self.train_pairwise and train, pairwise_texture=self.pairwise_texture)
         if self.reducer is not None:
             for g in replica.groups.values():
                 self.reducer.broadcast(g.var)

@@ -681,6 +681,64 @@ def pair_similarity(x, sp, hist, left, right, dense_w, dense_b, gamma=1.0):
     return sims, r
 
 
+TEXTURE_MAX_SP = 53      # A3DT_MAX_SP: the texture similarity's sum of squared count differences stays below 2^24
+
+
+def superpixel_lbp_hist(x, sp, out=None):
+    """NON-REFERENCE (a3dt_superpixel_lbp_hist): local-binary-pattern histogram of every superpixel, [n,h,w,3] float32 ->
+    [n,P,256] float32 integer counts (each superpixel's sum to sp * sp).  Neighbours are read from the image, across
+    superpixel borders, clamped at the image border; sp <= 53."""
+    if x.dim() != 4 or x.shape[3] != 3 or not 0 < sp <= TEXTURE_MAX_SP or x.shape[1] % sp or x.shape[2] % sp:
+        raise ValueError(f'superpixel_lbp_hist: x {tuple(x.shape)} is not [n, h, w, 3] with h, w multiples of sp = {sp} '
+                         f'<= {TEXTURE_MAX_SP}')
+    n, h, w, _ = x.shape
+    shape = (n, (h // sp) * (w // sp), 256)
+    if n == 0 or h == 0 or w == 0:
+        raise ValueError(f'superpixel_lbp_hist: x {tuple(x.shape)} is empty')
+    out = out if out is not None else torch.empty(shape, dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != shape:
+        raise ValueError(f'superpixel_lbp_hist: out {tuple(out.shape)} for x {tuple(x.shape)}, sp {sp} must be {shape}')
+    if x.dtype != torch.float32 or out.dtype != torch.float32:
+        raise TypeError('superpixel_lbp_hist: x, out float32')
+    if not (x.is_contiguous() and out.is_contiguous()):
+        raise ValueError('superpixel_lbp_hist: contiguous tensors only')
+    if out.device != x.device:
+        raise ValueError('superpixel_lbp_hist: all tensors on one device')
+    check(_lib.load().a3dt_superpixel_lbp_hist(n, h, w, _ptr(x), sp, _ptr(out), _stream()), 'a3dt_superpixel_lbp_hist')
+    return out
+
+
+def pair_similarity3(x, sp, hist, lbp_hist, left, right, dense_w, dense_b, gamma=1.0):
+    """NON-REFERENCE (a3dt_pair_similarity3): pair_similarity with the texture similarity of the LBP histograms as the
+    third: returns (sims [n,Q,3], r [n,Q]); sims[..., :2] are pair_similarity's bits.  x [n,h,w,3], hist and lbp_hist
+    [n,P,256] float32; left, right [Q] int32; dense_w 3 and dense_b 1 float32 values.  A pair with an index outside
+    [0, P) gets NaN."""
+    if x.dim() != 4 or x.shape[3] != 3 or not 0 < sp <= TEXTURE_MAX_SP or x.shape[1] % sp or x.shape[2] % sp:
+        raise ValueError(f'pair_similarity3: x {tuple(x.shape)} is not [n, h, w, 3] with h, w multiples of sp = {sp} '
+                         f'<= {TEXTURE_MAX_SP}')
+    n, h, w, _ = x.shape
+    q = left.numel()
+    hshape = (n, (h // sp) * (w // sp), 256)
+    if (n == 0 or h == 0 or w == 0 or q == 0 or right.numel() != q or tuple(hist.shape) != hshape
+            or tuple(lbp_hist.shape) != hshape or dense_w.numel() != 3 or dense_b.numel() != 1):
+        raise ValueError(f'pair_similarity3: x {tuple(x.shape)}, sp {sp}, hist {tuple(hist.shape)}, lbp_hist '
+                         f'{tuple(lbp_hist.shape)}, {q} / {right.numel()} pair indices, dense kernel '
+                         f'{tuple(dense_w.shape)}, bias {tuple(dense_b.shape)}')
+    if (any(t.dtype != torch.float32 for t in (x, hist, lbp_hist, dense_w, dense_b)) or left.dtype != torch.int32
+            or right.dtype != torch.int32):
+        raise TypeError('pair_similarity3: x, hist, lbp_hist, dense_w, dense_b float32; left, right int32')
+    if not all(t.is_contiguous() for t in (x, hist, lbp_hist, left, right, dense_w, dense_b)):
+        raise ValueError('pair_similarity3: contiguous tensors only')
+    if any(t.device != x.device for t in (hist, lbp_hist, left, right, dense_w, dense_b)):
+        raise ValueError('pair_similarity3: all tensors on one device')
+    sims = torch.empty((n, q, 3), dtype=torch.float32, device=x.device)
+    r = torch.empty((n, q), dtype=torch.float32, device=x.device)
+    check(_lib.load().a3dt_pair_similarity3(n, h, w, _ptr(x), sp, _ptr(hist), _ptr(lbp_hist), _ptr(left), _ptr(right), q,
+                                            _ptr(dense_w), _ptr(dense_b), gamma, _ptr(sims), _ptr(r), _stream()),
+          'a3dt_pair_similarity3')
+    return sims, r
+
+
 def crf_loss(z, y, r, left, right, eps=1e-7):
     """loss_part (src/models.py:129-177): returns (mean loss [1], per-image loss [n], d mean / d z [n,P]).  z, y [n,P],
     r [n,Q] float32; left, right [Q] int32.  A pair index outside [0, P) turns every loss and all of dz into NaN."""

@@ -2,7 +2,8 @@
 Times the forward (resize -> patches -> 5 conv / 3 pool / 3 dense), the unary backward from a synthetic dz, and the
 whole `models.dcnf` train step (+ pairwise part, CRF loss, gradient descent).  --train-pairwise: the step that also
 learns the pairwise dense layer (NON-REFERENCE); `crf_loss_ms` is the loss launch alone in the form the step uses.
-    python tools/bench_dcnf.py [batch] [--train-pairwise] > dcnf.json"""
+--pairwise-texture: the pairwise part with the LBP texture similarity as a third feature (NON-REFERENCE).
+    python tools/bench_dcnf.py [batch] [--train-pairwise] [--pairwise-texture] > dcnf.json"""
 import json
 import os
 import sys
@@ -14,12 +15,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ann3depth_amd import models, ops  # noqa: E402
 
 PAIRWISE = '--train-pairwise' in sys.argv[1:]
-argv = [a for a in sys.argv[1:] if a != '--train-pairwise']
+TEXTURE = '--pairwise-texture' in sys.argv[1:]
+argv = [a for a in sys.argv[1:] if a not in ('--train-pairwise', '--pairwise-texture')]
 B = int(argv[0]) if argv else 16
 rng = np.random.default_rng(1000)
 img = torch.from_numpy((rng.integers(0, 256, (B, 480, 640, 3)) / 255).astype(np.float32)).cuda()
 dep = torch.from_numpy(rng.random((B, 55, 74, 1)).astype(np.float32)).cuda()
-rep = models.DCNFReplica(B, train_pairwise=True) if PAIRWISE else models.DCNFReplica(B)
+if TEXTURE:
+    rep = models.DCNFReplica(B, train_pairwise=PAIRWISE, pairwise_texture=True)
+else:
+    rep = models.DCNFReplica(B, train_pairwise=True) if PAIRWISE else models.DCNFReplica(B)
 net = rep.unary
 dz = torch.randn((net.P, 1), device='cuda')
 
@@ -49,4 +54,5 @@ print(json.dumps({'workload': f'DCNF unary, batch {B} -> {net.P} patches 100x100
                   'backward_ms': round(t_bwd, 3), 'dtype': 'f32',
                   'train_step_ms': round(t_step, 3), 'train_step_images_per_s': round(B / t_step * 1e3, 1),
                   'pairwise_and_crf_loss_ms': round(t_crf, 3), 'crf_loss_ms': round(t_loss, 4), 'train_pairwise': PAIRWISE,
+                  'pairwise_texture': TEXTURE,
                   'fwd_bwd_images_per_s': round(B / (t_fwd + t_bwd) * 1e3, 1)}))
