@@ -680,7 +680,9 @@ __device__ __forceinline__ void store_tile_pool_buf(const IgemmParams& p, f32x16
 #pragma unroll
           for (int i = 0; i < 4; ++i) v[i] = 1.f / (1.f + (FASTEXP ? __expf(-v[i]) : expf(-v[i])));
         }
-        if (ROUND16) {      // the bf16-storage kernels compare what a separate conv would have stored: rounded values
+        // a bf16 pooled map — from the bf16 kernels (ROUND16) or, STORE_Y alone, from the float32 kernel (c16) — compares what a
+        // separate conv would have stored: rounded values (as conv3.hip's epilogue does)
+        if (ROUND16 || c16) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) v[i] = (float)(__bf16)v[i];
         }

@@ -2,7 +2,7 @@
 
 Run with A3D_TUNING=1 (the library then reads its A3D_FORCE_* / A3D_BF16_BN / A3D_RING_CFG switches per launch) and
 A3D_PLAN_LOG=1 (one `a3d plan:` line per implicit-GEMM launch on stderr).  Each reference (tests/exact_ops.py: integer
-operands, exact in float32 and bf16) is computed once; every launch writes into a NaN-filled allocation with guard rows, and
+operands, exact in float32 and bf16; in the rounded-store passes of the bf16 launches: sums a bf16 tensor holds as their RNE) is computed once; every launch writes into a NaN-filled allocation with guard rows, and
 the whole allocation must equal the reference.  The process reads its own stderr: a launch whose plan line does not show the
 pinned configuration (or its register-staged twin), the split factor after the planner's clamp to the k-tile count, or the
 stream-K grid is a MISMATCH too — a switch that silently does not apply would prove nothing.
@@ -76,13 +76,15 @@ def differs(big, rows, cols, ref):
 class Problem:
     """a conv case on the device, float32 or bf16 tensors, and one launch per direction"""
 
-    def __init__(self, case, stored):
+    def __init__(self, case, stored, rounded=False):
         self.case, self.stored = case, stored
-        self.cs = cs = E.conv_case(*case)
+        # rounded: operands up to 8, the bf16 y and dx hold RNE(exact sum) — conditions asserted by exact_ops.rounded_case
+        self.cs = cs = E.rounded_case(case, 'y', 'dx') if rounded else E.conv_case(*case)
+        assert stored or not rounded
         n, h, w, c, k, ks, st, pad = case
         tdt = BF if stored else torch.float32
         self.tdt = tdt
-        if stored:
+        if stored and not rounded:
             cs.bf16('y', 'dx')
         self.x, self.w, self.b, self.dz = dev(cs.x, tdt), dev(cs.w, tdt), dev(cs.b), dev(cs.dz, tdt)
         d = ops.conv_desc(n, h, w, c, k, ks, ks, st, pad, precision='bf16' if stored else 'fp32')
@@ -90,20 +92,26 @@ class Problem:
         self.d = {0: ops.with_storage(d, X | W | Y if stored else 0), 1: ops.with_storage(d, X | W | Y if stored else 0),
                   2: ops.with_storage(d, X | Y if stored else 0)}
 
-    def run(self, mode):
-        """-> None or a description of the first difference"""
+    def run(self, mode, second=None):
+        """-> None or a description of the first difference.  second: the type of a second output beside the forward's y (it
+        must hold what y holds: written by the split-K reduction in a split launch, by second_output_kernel in a whole one)"""
         cs = self.cs
         n, h, w, c, k, ks, st, pad = self.case
         if mode == 0:                                      # bias + ReLU in the epilogue / the reduction
             rows = n * cs.ho * cs.wo
             y = guarded(rows, k, self.tdt)
-            ops.conv2d_fwd(self.d[0], self.x, self.w, self.b, y[:rows].view(n, cs.ho, cs.wo, k), 'relu')
-            return differs(y, rows, k, np.maximum(cs.y, 0))
+            y2 = guarded(rows, k, second) if second is not None else None
+            ops.conv2d_fwd(self.d[0], self.x, self.w, self.b, y[:rows].view(n, cs.ho, cs.wo, k), 'relu',
+                           out2=ops.second_output(y2[:rows]) if second is not None else None)
+            ref = np.maximum(cs.y, 0)
+            ref = cs.stored('y', ref) if self.stored else ref
+            return differs(y, rows, k, ref) or (second is not None and differs(y2, rows, k, ref) or None)
         if mode == 1:                                      # with the ReluGrad of the layer below
             rows = n * h * w
             dx = guarded(rows, c, self.tdt)
             ops.conv2d_bwd_data(self.d[1], self.dz, self.w, dx[:rows].view(n, h, w, c), relu_mask=self.x)
-            return differs(dx, rows, c, cs.dx * (cs.x > 0))
+            ref = cs.dx * (cs.x > 0)
+            return differs(dx, rows, c, cs.stored('dx', ref) if self.stored else ref)
         dw, db = guarded(ks * ks * c, k), guarded(1, k)      # with the fused BiasAddGrad
         ops.conv2d_bwd_filter(self.d[2], self.x, self.dz, dw[:ks * ks * c].view(ks, ks, c, k), db[0])
         return differs(dw, ks * ks * c, k, cs.dw) or differs(db, 1, k, cs.db)
@@ -127,17 +135,17 @@ def main():
     failures, verified = [], 0
     problems = {}
 
-    def problem(case, stored):
-        if (case, stored) not in problems:
-            problems[case, stored] = Problem(case, stored)
-        return problems[case, stored]
+    def problem(case, stored, rounded=False):
+        if (case, stored, rounded) not in problems:
+            problems[case, stored, rounded] = Problem(case, stored, rounded)
+        return problems[case, stored, rounded]
 
-    def launch(prob, mode, env):
+    def launch(prob, mode, env, second=None):
         for v in SWITCHES:
             os.environ.pop(v, None)
         os.environ.update({k: str(v) for k, v in env.items()})
         log.new_plans()
-        diff, recs = timed(lib, lambda: prob.run(mode))
+        diff, recs = timed(lib, lambda: prob.run(mode, second))
         return diff, recs, log.new_plans()
 
     try:
@@ -158,10 +166,15 @@ def main():
                 failures.append(f'MISMATCH {what}: {diff}')
             else:
                 verified += 1
-        for case, mode, kind, value, split in E.forced_bf16_combos():
-            what = f'bf16 {case} mode {mode} {kind} {value} splitk {split}'
+        # identity stores, then the same pinned launches on sums the bf16 store rounds (once, after split-K slabs are added)
+        bf16_passes = [(combo, False) for combo in E.forced_bf16_combos()] + [(combo, True) for combo in E.forced_bf16_rounded_combos()]
+        for (case, mode, kind, value, split), rounded in bf16_passes:
+            what = f'bf16 {case} mode {mode} {kind} {value} splitk {split}' + (' rounded store' if rounded else '')
             env = {'A3D_BF16_BN': value, 'A3D_FORCE_SPLITK': split} if kind == 'bn' else {'A3D_RING_CFG': value}
-            diff, recs, plans = launch(problem(case, True), mode, env)
+            # the rounded forwards also write a second output: bf16 beside 64 columns and odd tiles, float32 beside the others, so
+            # both types are written by a split launch (factors 2, 3) and by a whole one
+            second = None if not (rounded and mode == 0) else BF if (value == 64 or value % 2 == 1) else torch.float32
+            diff, recs, plans = launch(problem(case, True, rounded), mode, env, second)
             ok = len(plans) == 1 and len(recs) == 1 and plans[0]['mode'] == mode and recs[0].prec == 2
             if ok and kind == 'bn':          # the plan line does not show the bf16 kernel's column width: the timing record does
                 ok = (plans[0]['kind'] == 'cfg' and recs[0].lds_dma == 0 and recs[0].bn == value

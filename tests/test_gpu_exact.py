@@ -79,7 +79,7 @@ def conv_fwd_exact(ops, cs, d, x, wt, b, family, tdt=torch.float32, what=''):
     rows = n * cs.ho * cs.wo
     for bias, act, ref in ((b, None, cs.y), (b, 'relu', np.maximum(cs.y, 0)), (None, None, cs.y - E.f64(cs.b))):
         if tdt == BF:
-            E.require_bf16(cs.what + ' y', ref)
+            ref = cs.stored('y', ref)                          # <= 256, or the RNE of a rounded-store case
         big = guarded(rows, d.ldy, tdt)
         recs = launched(lambda: ops.conv2d_fwd(d, x, wt, bias, big[:rows].view(n, cs.ho, cs.wo, d.ldy), act))
         expect(big, rows, k, ref, what=f'{what} forward {cs.shape} act {act}')
@@ -106,6 +106,8 @@ def conv_bwd_data_exact(ops, cs, d, dz, wt, xmask, family, tdt=torch.float32, wh
     rows = n * h * w
     for mask in (None, xmask):
         ref = cs.dx if mask is None else cs.dx * (cs.x > 0)
+        if tdt == BF:
+            ref = cs.stored('dx', ref)
         big = guarded(rows, c, tdt)
         recs = launched(lambda: ops.conv2d_bwd_data(d, dz, wt, big[:rows].view(n, h, w, c), relu_mask=mask))
         expect(big, rows, c, ref, what=f'{what} dx {cs.shape} mask {mask is not None}')
@@ -137,7 +139,8 @@ def conv_exact_bf16_tensors(ops, cs, fwd=None, bwd_d=None, bwd_f=None, one_launc
     if 2 in directions:
         conv_bwd_filter_exact(ops, cs, ops.with_storage(d, X | Y), x, dz, bwd_f, what='bf16 tensors')
     if 1 in directions:
-        cs.bf16('dx')
+        if not cs.rounds:
+            cs.bf16('dx')
         conv_bwd_data_exact(ops, cs, ops.with_storage(d, X | W | Y), dz, wt, x, bwd_d, tdt=BF, what='bf16 tensors', one_launch=one_launch)
 
 
@@ -263,7 +266,7 @@ def test_one_filter_stencils(ops, case, dx16):
 
 
 # ---- conv + ReLU + 2x2 pool in one launch, and maxpool2x2_bwd_idx from its bytes ----
-def pool_fwd_exact(ops, cs, d, x, wt, b, ld, family, tdt=torch.float32, acts=(('relu', True), (None, False))):
+def pool_fwd_exact(ops, cs, d, x, wt, b, ld, family, tdt=torch.float32, acts=(('relu', True), (None, False)), ties=10):
     """pooled values and argmax bytes against the first maximum of the exact reference; then the by-index MaxPoolGrad
     (+ ReluGrad) from the bytes and values the launch wrote -> (pooled allocation, argmax allocation) of the last run"""
     n, h, w, c, k, ks, st, pad = cs.shape
@@ -271,9 +274,12 @@ def pool_fwd_exact(ops, cs, d, x, wt, b, ld, family, tdt=torch.float32, acts=(('
     prow = n * ph * pw
     for act, with_bias in acts:
         y = np.maximum(cs.y, 0) if act else cs.y - E.f64(cs.b)
-        pooled, arg = E.pool_reference(y)
+        if tdt == BF and cs.rounds:      # the first maximum of the ROUNDED window: rounding creates ties (asserted in >= `ties` windows)
+            pooled, arg = E.rounded_pool(cs, y, ties)
+        else:
+            pooled, arg = E.pool_reference(y)
         if tdt == BF:
-            E.require_bf16(cs.what + ' pooled', pooled)
+            pooled = cs.stored('pooled', pooled)
         pbig, abig = guarded(prow, ld, tdt), guarded(prow, k, torch.uint8, 9)
         recs = launched(lambda: ops.conv2d_pool_fwd(d, x, wt, b if with_bias else None, pbig[:prow].view(n, ph, pw, ld), act,
                                                     abig[:prow].view(n, ph, pw, k)))
@@ -311,8 +317,11 @@ def test_fused_pool_fp32(ops, case):
 def test_fused_pool_bf16_image_form(ops, case):
     """a 3-channel image as bf16 pixels of 4 channels (a3d_pad_channels_bf16), bf16 output at a pitch of whole 16-byte pieces;
     the filter's 4th channel holds anything (its pixels are zero); per-call repack and prepared filter"""
-    cs = E.conv_case(*case).bf16('y')
-    n, h, w, c, k, ks, st, pad = case
+    bf16_image_form_exact(ops, E.conv_case(*case).bf16('y'))
+
+
+def bf16_image_form_exact(ops, cs, ties=10):
+    n, h, w, c, k, ks, st, pad = cs.shape
     x4 = torch.full((n, h, w, 4), NAN, device='cuda', dtype=BF)
     ops.pad_channels_bf16(dev(cs.x), x4)
     np.testing.assert_array_equal(x4.float().cpu().numpy(), np.concatenate([cs.x, np.zeros((n, h, w, 1), np.float32)], -1))
@@ -326,14 +335,17 @@ def test_fused_pool_bf16_image_form(ops, case):
     pf.refresh(w4)
     for dd, filt in ((d, w4), (pf.desc_prepared, pf.buf)):
         conv_fwd_exact(ops, cs, dd, x4, filt, b, family, tdt=BF, what='bf16 image')
-        pool_fwd_exact(ops, cs, dd, x4, filt, b, ldy, family, tdt=BF, acts=(('relu', True),))
+        pool_fwd_exact(ops, cs, dd, x4, filt, b, ldy, family, tdt=BF, acts=(('relu', True),), ties=ties)
 
 
 @pytest.mark.parametrize('case', E.POOL_FWD_BF16_STORED)
 def test_fused_pool_on_bf16_stored_operands(ops, case):
     """bf16 x, w and pooled map: the pooling epilogue of the LDS-DMA kernel, and a3d_maxpool2x2_bwd_idx_bf16s from its bytes"""
-    cs = E.conv_case(*case).bf16('y')
-    n, h, w, c, k, ks, st, pad = case
+    bf16_stored_pool_exact(ops, E.conv_case(*case).bf16('y'))
+
+
+def bf16_stored_pool_exact(ops, cs):
+    n, h, w, c, k, ks, st, pad = cs.shape
     d = ops.with_storage(ops.conv_desc(n, h, w, c, k, ks, ks, st, pad, precision='bf16'), ops.STORE_X | ops.STORE_W | ops.STORE_Y)
     pool_fwd_exact(ops, cs, d, dev(cs.x, BF), dev(cs.w, BF), dev(cs.b), k, RING, tdt=BF, acts=(('relu', True),))
 
