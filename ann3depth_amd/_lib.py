@@ -154,6 +154,12 @@ TEXTURE_SIGNATURES = {
     'a3dt_pair_similarity3': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, c_int, _P, _P, c_float, _P, _P, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_gradloss.h declares (NON-REFERENCE extension, prefix a3dg_)
+GRADLOSS_SIGNATURES = {
+    'a3dg_silog_grad_loss_fwd': (c_int, [c_int, c_int, c_int, _P, _P, c_int, c_float, _P, _P, _P]),
+    'a3dg_silog_grad_loss_bwd_ex': (c_int, [c_int, c_int, c_int, _P, _P, c_int, c_float, _P, _P, _P, c_int, _P]),
+}
+
 _lib = None
 
 
@@ -170,7 +176,7 @@ def load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(PAIR_SIGNATURES.items())
-                              + list(TEXTURE_SIGNATURES.items())):
+                              + list(TEXTURE_SIGNATURES.items()) + list(GRADLOSS_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

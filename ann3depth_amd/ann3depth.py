@@ -60,6 +60,13 @@ def main(argv=None):
         logger.error(f'--pairwise-texture adds the texture similarity to the pairwise part of the CRF of --model dcnf '
                      f'(Liu et al. 2015): {args.model or "(no model)"} has no such part.')
         return 2
+    if args.loss_gradient is not None and args.model != 'msdn':
+        logger.error(f'--loss-gradient weighs the gradient-matching term of Eigen & Fergus 2015 in the two losses of --model '
+                     f'msdn: {args.model or "(no model)"} has no loss over a pixel grid (dcnf regresses superpixel means).')
+        return 2
+    if args.loss_gradient is not None and not args.loss_gradient >= 0:
+        logger.error(f'--loss-gradient {args.loss_gradient}: the weight is a number >= 0.')
+        return 2
     if args.min_depth is not None or args.max_depth is not None:
         lo = 0. if args.min_depth is None else args.min_depth
         hi = float('inf') if args.max_depth is None else args.max_depth
@@ -123,6 +130,8 @@ def setup_model(args, rank=0, world=1):
         if args.min_depth is not None or args.max_depth is not None:
             model.valid_range = (0. if args.min_depth is None else args.min_depth,
                                  float('inf') if args.max_depth is None else args.max_depth)
+    if hasattr(model, 'grad_weight'):                                    # main() has refused the models that have none
+        model.grad_weight = float(args.loss_gradient or 0.0)
     if hasattr(model, 'train_pairwise'):                                 # main() has refused the models that have none
         model.train_pairwise = bool(args.train_pairwise)
     if hasattr(model, 'pairwise_texture'):
@@ -352,7 +361,7 @@ def latest_checkpoint(ckptdir):
 
 
 def parse_args(argv=None):
-    """The reference's flags verbatim (src/ann3depth.py:221-254), plus --beta2 / --augment / --min-depth / --max-depth /
+    """The reference's flags verbatim (src/ann3depth.py:221-254), plus --beta2 / --augment / --min-depth / --max-depth / --loss-gradient /
     --train-pairwise / --pairwise-texture / --seed / --trace-every / --profiler."""
     parser = argparse.ArgumentParser()
     parser.add_argument('dataset', default='nyu', type=str, help='The dataset to use.')
@@ -383,6 +392,11 @@ def parse_args(argv=None):
                              'min < t <= max; the others leave the resized target and both losses. Giving either flag turns '
                              'the mode on, the other defaults to 0 / +inf.')
     parser.add_argument('--max-depth', default=None, type=float, help='NON-REFERENCE: see --min-depth.')
+    parser.add_argument('--loss-gradient', default=None, type=float, metavar='W',
+                        help='NON-REFERENCE: add W times the gradient-matching term of Eigen & Fergus 2015 (eq. 4) to both '
+                             'losses (msdn only): the squared horizontal and vertical differences of the log-depth error over '
+                             'the 55 x 74 grid, over the pairs of valid pixels under --min-depth / --max-depth. W >= 0; 0 is '
+                             'the run without the flag.')
     parser.add_argument('--train-pairwise', action='store_true',
                         help='NON-REFERENCE: learn the pairwise dense layer of the CRF (dcnf only). The reference leaves it at '
                              'its initial draw (TF 1.3 has no gradient for scatter_nd_update); with this flag the loss is also '

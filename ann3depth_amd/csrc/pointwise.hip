@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "a3d_internal.h"
+#include "silog_common.h"
 #include "../../include/a3d_valid.h"
 
 namespace a3d {
@@ -16,17 +17,7 @@ using namespace a3d;
 
 namespace a3d {
 // ------------------------------------------------------------------ scale-invariant log loss
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ float masked_log(float v) {
-  float l = logf(__fadd_rn(v, 1e-8f));
-  return isnan(l) ? 0.f : l;     // tf.where(tf.is_nan(log), 0, log): -inf is kept
-}
-
+// (masked_log, the wavefront sums, kSilogParts and kSilogC: silog_common.h, shared with gradloss.hip)
 // kSilogParts blocks per sample (one sample is 4070 pixels at MSDN's size: with one block per sample 32 CUs each walked a
 // chain of load latencies and logarithms — 29 us on the step's critical path; now every CU holds one short piece).  Block
 // (b, part) leaves its partial sums in ws[2nb+1 + 2(b*parts+part) ..]; the block that finishes last (ticket in ws[0],
@@ -40,12 +31,6 @@ __device__ __forceinline__ float masked_log(float v) {
 // a third value per block and per sample, the number n of pixels that count, travels beside the two sums (K = 3 floats
 // where the plain kernel has 2), and the sample's term is (npix / n) (s2 - (0.5 / n) s1^2), 0 when n = 0.  Same parts, same
 // reductions, same last block: with no hole and npix = 4070 the constants are the plain kernel's and so are the bits.
-constexpr int kSilogParts = A3D_SILOG_PARTS;
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 template <bool MASKED>
 __global__ __launch_bounds__(256) void silog_fwd_kernel(const float* __restrict__ out, const float* __restrict__ tgt,
                                                         float* __restrict__ ws, float* __restrict__ loss, int npix, int nb,
@@ -171,8 +156,6 @@ __global__ __launch_bounds__(256) void silog_bwd_kernel(const float* __restrict_
 }  // namespace a3d
 
 extern "C" {
-
-static const float kSilogC = (float)(0.5 / (74 * 55));   // src/models.py:269, folded constant
 
 int a3d_silog_loss_fwd(int b, int npix, const float* out, const float* tgt, float* loss, float* ws, void* stream) {
   A3D_CHECK_ARG(b > 0 && npix > 0 && out && tgt && loss && ws, "silog_fwd: bad arguments");

@@ -126,14 +126,21 @@ class MSDNReplica:
     """One data-parallel replica of the MSDN training graph (src/models.py:203-367) on one GPU."""
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, global_step=0, beta2=1.0, reducer=None,
-                 precision='fp32', keep_dense_grads=True, overlap=True, valid_range=None):
+                 precision='fp32', keep_dense_grads=True, overlap=True, valid_range=None, grad_weight=0.0):
         """precision: arithmetic of the conv contractions — 'fp32' (exact, the parity default), 'bf16x3' (split
         operands on the bf16 matrix cores, ~1e-5) or 'bf16' (BASELINE config 5).  Tensors stay float32 in HBM; the
         Cin = 3 layers, the dense layers and everything element-wise always compute in fp32.
         overlap=False: everything on the current stream (the one-stream schedule the two-stream one must equal bit for bit).
         valid_range (NON-REFERENCE): (min_depth, max_depth) — the depth maps have holes.  The target is resized (or warped)
         validity-aware: an element whose taps are not all finite and in (min_depth, max_depth] becomes NaN, and both losses
-        run over the finite targets only (ops.silog_masked_loss_fwd).  None: the reference's step, launch for launch."""
+        run over the finite targets only (ops.silog_masked_loss_fwd).  None: the reference's step, launch for launch.
+        grad_weight (NON-REFERENCE): weight of the gradient-matching term of Eigen & Fergus 2015 (eq. 4) in both losses: the
+        squared horizontal and vertical differences of the log-depth error over the 55 x 74 grid, over the pairs of finite
+        targets under valid_range.  > 0: the four loss launches are ops.silog_grad_loss_fwd / _bwd.  0: today's launches."""
+        grad_weight = float(grad_weight)
+        if not grad_weight >= 0:
+            raise ValueError(f'grad_weight {grad_weight!r}: the weight of the gradient-matching term is a number >= 0')
+        self.grad_weight = grad_weight
         if valid_range is not None:
             lo, hi = (float(v) for v in valid_range)
             if not lo <= hi:
@@ -253,15 +260,23 @@ class MSDNReplica:
         self.f2 = buf(B, OUT_H, OUT_W, 64)
         self.fine = buf(B, OUT_H, OUT_W, 1)
         self.loss_coarse = buf(1); self.loss_fine = buf(1)
-        if valid_range is not None:       # the masked loss writes the valid fraction of the target behind the loss
+        if grad_weight > 0:               # total, valid fraction, silog part, gradient part (ops.silog_grad_loss_fwd)
+            self.loss_quad_c = buf(4); self.loss_quad_f = buf(4)
+            self.loss_pair_c = self.loss_quad_c[:2]; self.loss_pair_f = self.loss_quad_f[:2]
+            self.loss_coarse = self.loss_pair_c[:1]; self.loss_fine = self.loss_pair_f[:1]
+        elif valid_range is not None:     # the masked loss writes the valid fraction of the target behind the loss
             self.loss_pair_c = buf(2); self.loss_pair_f = buf(2)
             self.loss_coarse = self.loss_pair_c[:1]; self.loss_fine = self.loss_pair_f[:1]
+        # what a loss launch writes: 4, 2 or 1 floats, loss_coarse / loss_fine their first
+        self.loss_out_c, self.loss_out_f = ((self.loss_quad_c, self.loss_quad_f) if grad_weight > 0 else
+                                            (self.loss_pair_c, self.loss_pair_f) if valid_range is not None else
+                                            (self.loss_coarse, self.loss_fine))
         # window positions of the pool maxima (all MaxPoolGrad needs besides the pooled values, see forward())
         self.a0 = torch.empty((B, 27, 37, 96), dtype=torch.uint8, device=dev)
         self.a1 = torch.empty((B, 13, 18, 256), dtype=torch.uint8, device=dev)
         self.af1 = torch.empty((B, OUT_H, OUT_W, 63), dtype=torch.uint8, device=dev)
         self.pooled_fwd = None            # which network ran conv + pool fused in the last forward
-        silog_ws = ops.silog_ws if valid_range is None else ops.silog_masked_ws
+        silog_ws = ops.silog_grad_ws if grad_weight > 0 else ops.silog_ws if valid_range is None else ops.silog_masked_ws
         self.ws_c = silog_ws(B, dev); self.ws_f = silog_ws(B, dev)           # per-sample sums + arrival ticket + partials
         self.t_one = buf(B, 1, 1, 1) if valid_range is not None else None    # see ops.resize_bilinear_tf1_valid
         # gradients wrt pre-activations
@@ -620,6 +635,9 @@ class MSDNReplica:
                'optimizers/Phase': out['phase']}
         if self.valid_range is not None:                 # NON-REFERENCE: share of the target pixels that hold a depth
             rec['valid_fraction'] = float(self.loss_pair_c[1])
+        if self.grad_weight > 0:                         # NON-REFERENCE: the gradient-matching terms, before their weight
+            rec['loss/coarse_grad'] = float(self.loss_quad_c[3])
+            rec['loss/fine_grad'] = float(self.loss_quad_f[3])
         return rec
 
     def summary_images(self):
@@ -818,15 +836,9 @@ class MSDNReplica:
             self._conv('fine/second/conv2d', self.cat, self.f2)
             self._conv('fine/third', self.f2, self.fine)
             if depths is not None:
-                if self.valid_range is None:
-                    ops.silog_loss_fwd(self.fine, self.t, self.loss_fine, self.ws_f)
-                else:
-                    ops.silog_masked_loss_fwd(self.fine, self.t, self.loss_pair_f, self.ws_f)
+                self._loss_fwd(self.fine, self.loss_out_f, self.ws_f)
         if depths is not None:
-            if self.valid_range is None:
-                ops.silog_loss_fwd(self.coarse, self.t, self.loss_coarse, self.ws_c)
-            else:
-                ops.silog_masked_loss_fwd(self.coarse, self.t, self.loss_pair_c, self.ws_c)
+            self._loss_fwd(self.coarse, self.loss_out_c, self.ws_c)
         if join:
             self._join()
 
@@ -847,6 +859,23 @@ class MSDNReplica:
             self.x[n:].zero_()
         self.forward(images, None, None, join=True, phase=3)
         return self.coarse.view(B, OUT_H, OUT_W), self.fine.view(B, OUT_H, OUT_W)
+
+    def _loss_fwd(self, out, loss, ws):
+        """One launch: the loss of `out` against self.t into `loss`, the buffer that launch writes (loss_out_c / loss_out_f)."""
+        if self.grad_weight > 0:
+            ops.silog_grad_loss_fwd(out, self.t, OUT_H, OUT_W, self.valid_range is not None, self.grad_weight, loss, ws)
+        elif self.valid_range is None:
+            ops.silog_loss_fwd(out, self.t, loss, ws)
+        else:
+            ops.silog_masked_loss_fwd(out, self.t, loss, ws)
+
+    def _loss_bwd(self, out, ws, dout, dout16=None):
+        if self.grad_weight > 0:
+            ops.silog_grad_loss_bwd(out, self.t, OUT_H, OUT_W, self.valid_range is not None, self.grad_weight, ws, dout, dout16)
+        elif self.valid_range is None:
+            ops.silog_loss_bwd(out, self.t, ws, dout, dout16)
+        else:
+            ops.silog_masked_loss_bwd(out, self.t, ws, dout, dout16)
 
     def _sharded_in_flight(self):
         """The deferred dense bucket is a reduce-scatter feeding only the m slot: nothing in the forward needs it, it is due
@@ -876,9 +905,8 @@ class MSDNReplica:
     def backward_coarse(self, after_dense=None, after_conv2=None, after_dense1=None):
         B = self.B
         bf16_x = self.bf16s and self.dense_bf16_x
-        silog_bwd = ops.silog_loss_bwd if self.valid_range is None else ops.silog_masked_loss_bwd
-        silog_bwd(self.coarse, self.t, self.ws_c, self.dz1.view(B, OUT_H, OUT_W, 1),
-                  dout16=self.dz1_16 if bf16_x else None)        # (dz1 a second time as bf16 rows of 4072: dense_1's bwd-data)
+        self._loss_bwd(self.coarse, self.ws_c, self.dz1.view(B, OUT_H, OUT_W, 1),
+                       dout16=self.dz1_16 if bf16_x else None)   # (dz1 a second time as bf16 rows of 4072: dense_1's bwd-data)
         self.settle()              # a reduce-scatter of the previous step may still be reading the dense gradient buffer
         n = 'coarse/dense/dense_1'
         self._bwd_filter(n, self.drop, self.dz1)
@@ -951,8 +979,7 @@ class MSDNReplica:
     # ---- backward of loss_fine wrt fine/* : src/models.py:333-338 ----
     def backward_fine(self):
         self._join()                                                          # the fine forward ran on the side stream
-        silog_bwd = ops.silog_loss_bwd if self.valid_range is None else ops.silog_masked_loss_bwd
-        silog_bwd(self.fine, self.t, self.ws_f, self.dfine)
+        self._loss_bwd(self.fine, self.ws_f, self.dfine)
         n = 'fine/third'
         if ops.conv2d_bwd_both_supported(self.d[n]):
             # filter, bias and input gradient (+ fine/second's ReluGrad) in one pass over f2
@@ -1586,6 +1613,7 @@ class _MultiScaleDeepNetwork:
     precision = 'fp32'   # --precision: 'fp32' | 'bf16x3' | 'bf16' (see MSDNReplica)
     augment = None       # NON-REFERENCE, --augment eigen: an augment.Eigen2014 (train-time augmentation of the input batch)
     valid_range = None   # NON-REFERENCE, --min-depth / --max-depth: (min, max), the depth maps have holes (see MSDNReplica)
+    grad_weight = 0.0    # NON-REFERENCE, --loss-gradient: weight of the gradient-matching term in both losses (see MSDNReplica)
 
     def __call__(self, images, depths, train=True):
         assert images.pipeline is depths.pipeline, 'inputs and targets must come from the same data.inputs() call'
@@ -1593,7 +1621,7 @@ class _MultiScaleDeepNetwork:
         replica = MSDNReplica(images.pipeline.B, device=torch.device('cuda', torch.cuda.current_device()),
                               seed=self.seed, beta2=self.beta2, reducer=self.reducer, precision=self.precision,
                               keep_dense_grads=False,        # one GPU + the reference's optimizer: dW feeds ApplyAdam directly
-                              valid_range=self.valid_range)
+                              valid_range=self.valid_range, grad_weight=self.grad_weight)
         replica.uses_dropout = bool(train)                   # train=False: tf.layers.dropout(training=False), src/models.py:230
         if self.reducer is not None:                         # replicas start from rank 0's weights
             for g in replica.groups.values():

@@ -452,6 +452,43 @@ def silog_masked_loss_bwd(out, tgt, ws, dout, dout16=None):
     return dout
 
 
+def silog_grad_ws(b, device):
+    """Workspace of silog_grad_loss_fwd / _bwd for a batch of b (or any smaller one): A3DG_WS_FLOATS(b) zeros (the ticket,
+    its first word, must start at zero)."""
+    return torch.zeros(5 * b + 1 + 5 * b * SILOG_PARTS, device=device)
+
+
+def _grad_loss_args(who, out, h, w, grad_weight):
+    b = out.shape[0]
+    assert out.numel() == b * h * w, f'{who}: out holds {out.numel()} values, not {b} x {h} x {w}'
+    grad_weight = float(grad_weight)
+    if not grad_weight >= 0:
+        raise ValueError(f'{who}: grad_weight {grad_weight!r} must be a number >= 0')
+    return b, grad_weight
+
+
+def silog_grad_loss_fwd(out, tgt, h, w, masked, grad_weight, loss, ws):
+    """NON-REFERENCE: the scale-invariant loss plus grad_weight times the gradient-matching term of Eigen & Fergus 2015 over
+    the horizontal and vertical neighbour pairs of the h x w grid (a3dg_silog_grad_loss_fwd).  masked: only finite targets
+    count, as in silog_masked_loss_fwd.  loss: 4 floats — the total, the valid fraction, the silog part, the gradient part."""
+    b, grad_weight = _grad_loss_args('silog_grad_loss_fwd', out, h, w, grad_weight)
+    assert ws.numel() >= 5 * b + 1 + 5 * b * SILOG_PARTS, \
+        'silog workspace too small: allocate it with ops.silog_grad_ws(b, device)'
+    assert loss.numel() >= 4 and loss.is_contiguous(), 'silog_grad_loss_fwd writes four floats'
+    check(_lib.load().a3dg_silog_grad_loss_fwd(b, h, w, _ptr(out), _ptr(tgt), int(bool(masked)), grad_weight, _ptr(loss),
+                                               _ptr(ws), _stream()), 'a3dg_silog_grad_loss_fwd')
+    return loss
+
+
+def silog_grad_loss_bwd(out, tgt, h, w, masked, grad_weight, ws, dout, dout16=None):
+    """dout16 as silog_loss_bwd's.  masked and grad_weight as in the forward call that filled ws."""
+    b, grad_weight = _grad_loss_args('silog_grad_loss_bwd', out, h, w, grad_weight)
+    check(_lib.load().a3dg_silog_grad_loss_bwd_ex(b, h, w, _ptr(out), _ptr(tgt), int(bool(masked)), grad_weight, _ptr(ws),
+                                                  _ptr(dout), _ptr(dout16), 0 if dout16 is None else dout16.shape[-1],
+                                                  _stream()), 'a3dg_silog_grad_loss_bwd_ex')
+    return dout
+
+
 METRIC_COLUMNS = ('n', 'abs_rel', 'sq_rel', 'sq', 'log', 'log_sq', 'log10', 'delta1', 'delta2', 'delta3', 'nonfinite')
 # A3D_METRIC_* (include/a3d.h): the per-image sums of a3d_depth_metrics, in this column order
 
