@@ -811,7 +811,9 @@ extern "C" int a3d_dense_bwd_filter_adam_tf1_ex(int m, int k, int n, const float
                 "dense_bwd_filter_adam: only the reference's frozen optimizer (beta2 == 1); otherwise call "
                 "a3d_dense_bwd_filter and a3d_adam_apply_tf1");
   clear_stale_error();
-  const uintptr_t slots = reinterpret_cast<uintptr_t>(m_w) | reinterpret_cast<uintptr_t>(dz);
+  // every tensor the kernels touch in CW-wide pieces: dz, the m slot, and var / v (written where a non-finite g or m poisons them)
+  const uintptr_t slots = reinterpret_cast<uintptr_t>(m_w) | reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(var_w) |
+                          reinterpret_cast<uintptr_t>(v_w);
   const dim3 rows_grid((n + 511) / 512, (k + 31) / 32);
   // stream form: two blocks per CU, each walking down its share of the row groups; 512 columns per block for batches of
   // at most 32 rows, 256 for up to 64

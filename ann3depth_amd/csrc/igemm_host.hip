@@ -95,7 +95,8 @@ __global__ __launch_bounds__(256) void unpad_filter_kernel(const float* wp, floa
 // has the descriptor alone and takes the maximum over the list, asking with kOnGrid: every operand on the 16-byte grid, no fused
 // pool, no prepared filter, a bias gradient wanted, and `known` false.  Where `known` is false the tests that need a pointer, a
 // pixel stride or the epilogue count as passed, and the GEMM is planned from the descriptor's channel counts alone (no hint, no
-// storage bit): every place that reads `o.known` is a query answer that a launch may exceed (tests/golden/plan_table.json pins them).
+// storage bit): every place that reads `o.known` is a query answer that a launch may exceed (tests/golden/plan_table.json pins them);
+// an operand off the grid is not one of them (fit_workspace).
 struct Operands {
   bool known = false;
   unsigned x = 0, w = 0, y = 0;      // address & 15 of the image-side tensor (x, dx), the filter (w, dw) and the output-side one (y, dz)
@@ -124,6 +125,16 @@ struct Route {
   size_t bytes = 0;       // all of it: repack + plan.ws_bytes + bias slabs or column-sum partials
 };
 static size_t upto(size_t need, const Route& r) { return r.ok ? std::max(need, r.bytes) : need; }
+// A query plans with kOnGrid; an operand off the 16-byte grid plans another GEMM (scalar gathers: another tile, another split, no
+// LDS-DMA twin), whose slabs may outgrow the query's answer.  include/a3d.h promises that the query's bytes are enough wherever
+// the operands lie: such a launch plans its split within the bytes it was given (per_split: the bias gradient's row of a split).
+static void fit_workspace(Route& r, const Operands& o, size_t ws_bytes, size_t per_split = 0) {
+  if (r.bytes <= ws_bytes || !(o.x | o.w | o.y | o.aux) || r.repack > ws_bytes) return;
+  r.plan = plan_within(r.g, r.plan, ws_bytes - r.repack, per_split);
+  r.bytes = r.repack + r.plan.ws_bytes + (r.plan.splitk > 1 ? (size_t)r.plan.splitk * per_split : 0);
+}
+// `ws` is read and written in 16-byte pieces (the padded and packed filter copies at its start, the vectorised split-K reduction)
+#define A3D_CHECK_WS(ws, who) A3D_CHECK_ARG(aligned16(ws), who ": ws must be 16-byte aligned")
 
 static const int kAll16 = A3D_STORE_X_BF16 | A3D_STORE_W_BF16 | A3D_STORE_Y_BF16;
 static bool stored16(const a3d_conv_desc* d, int bits) { return (d->storage & bits) == bits; }
@@ -190,16 +201,17 @@ static void storage_vecs(GemmProblem& g, bool a16, bool b16, bool c16) {
   if (b16) g.bvec = 4;
 }
 // a3d_conv_desc.storage -> which GEMM operands are bf16, with the checks a 16-byte bf16 gather needs
+// an / bn / cn: the operands' names in the entry point's argument list, for the message
 static int apply_storage(IgemmParams& p, int precision, bool a16, bool b16, bool c16, int a_c, int a_ld, int b_c, int b_ld,
-                         const void* a, const void* b, const void* c) {
+                         const void* a, const void* b, const void* c, const char* an, const char* bn, const char* cn) {
   if (!a16 && !b16 && !c16) return A3D_OK;
   // a bf16 OUTPUT alone is also served by the fp32 kernels (the 3-channel layers of config 5 keep fp32 arithmetic)
   A3D_CHECK_ARG(precision == A3D_PREC_BF16 || (precision == A3D_PREC_F32 && !a16 && !b16),
                 "bf16 operands need precision A3D_PREC_BF16");
-  A3D_CHECK_ARG(!a16 || (a_c % 8 == 0 && a_ld % 8 == 0 && aligned16(a)), "bf16 operand: channels / stride must be multiples of 8, base 16-byte aligned");
+  A3D_CHECK_ARG(!a16 || (a_c % 8 == 0 && a_ld % 8 == 0 && aligned16(a)), "bf16 %s: channels / stride must be multiples of 8, base 16-byte aligned", an);
   // b_c < 0: a row-major [rows][b_ld] operand read in whole 16-byte chunks (its pad columns must be readable zeros)
-  A3D_CHECK_ARG(!b16 || ((b_c < 0 || b_c % 8 == 0) && b_ld % 8 == 0 && aligned16(b)), "bf16 operand: channels / stride must be multiples of 8, base 16-byte aligned");
-  A3D_CHECK_ARG(!c16 || aligned16(c), "bf16 output: base must be 16-byte aligned");
+  A3D_CHECK_ARG(!b16 || ((b_c < 0 || b_c % 8 == 0) && b_ld % 8 == 0 && aligned16(b)), "bf16 %s: channels / stride must be multiples of 8, base 16-byte aligned", bn);
+  A3D_CHECK_ARG(!c16 || aligned16(c), "bf16 %s: base must be 16-byte aligned", cn);
   p.a16 = a16; p.b16 = b16; p.c16 = c16;
   return A3D_OK;
 }
@@ -336,7 +348,7 @@ static Route fwd_gemm(const a3d_conv_desc* d, const Operands& o, GemmForm form) 
   if (form == kLdsDma) { g.ring_ok = 1; g.avec = g.bvec = 4; }
   if (o.known) {
     if (d->hints & A3D_HINT_SHARE_CU) g.no_glds = 1;      // the register-staged kernels take the hint (launch_one)
-    if (form == kRunForm) g.bvec = 4;                     // the padded copy is 256-byte aligned, its rows whole 16-byte pieces
+    if (form == kRunForm) g.bvec = 4;                     // the padded copy starts the workspace (16-byte aligned: A3D_CHECK_WS), its rows are whole 16-byte pieces
     storage_vecs(g, d->storage & A3D_STORE_X_BF16, d->storage & A3D_STORE_W_BF16, d->storage & A3D_STORE_Y_BF16);
   }
   r.plan = plan_gemm(g, d->precision);
@@ -377,6 +389,7 @@ static int conv_fwd_impl(const a3d_conv_desc* d, const float* x, const float* w,
   A3D_CHECK_ARG(!(out2 && out2->ptr) || (!pool && !stencil1_applicable(d) && !image && !conv3_applicable(d, o.x)),
                 "conv2d_fwd_ex2: a second output on the implicit-GEMM forwards only (no fused pool, no few-channel / one-filter kernels)");
   A3D_CHECK_ARG(x && w && y, "conv2d_fwd: null tensor");
+  A3D_CHECK_WS(ws, "conv2d_fwd");
   A3D_CHECK_ARG(act == A3D_ACT_NONE || act == A3D_ACT_RELU || act == A3D_ACT_SIGMOID, "conv2d_fwd: bad act");
   if (pool) {
     A3D_CHECK_ARG(d->precision == A3D_PREC_F32 || image ||
@@ -398,7 +411,8 @@ static int conv_fwd_impl(const a3d_conv_desc* d, const float* x, const float* w,
                         [&] { return conv3_fwd(d, x, w, bias, y, act, pool, ld_out, argmax, ws, ws_bytes, st, o.prepared); });
   // the window-run form if the workspace holds its padded filter; else the tensors as stored, on the LDS-DMA kernel where that may be
   const bool run = !image && fwd_form_ok(d, o, kRunForm, &rf) && (o.prepared || rf.bytes <= ws_bytes), padded = run || image;
-  const Route r = fwd_gemm(d, o, image ? kBf16Image : run ? kRunForm : fwd_form_ok(d, o, kLdsDma, &rf) ? kLdsDma : kAsStored);
+  Route r = fwd_gemm(d, o, image ? kBf16Image : run ? kRunForm : fwd_form_ok(d, o, kLdsDma, &rf) ? kLdsDma : kAsStored);
+  fit_workspace(r, o, ws_bytes);
   // (the prepared layout was chosen for a 16-byte aligned x — fwd_filter_form — and this launch reads it with THAT row padding)
   A3D_CHECK_ARG(!o.prepared || (padded && !o.w && !o.x),
                 "conv2d_fwd: A3D_HINT_W_PREPARED on a launch that reads the filter as stored, or with x off the 16-byte grid");
@@ -412,7 +426,7 @@ static int conv_fwd_impl(const a3d_conv_desc* d, const float* x, const float* w,
                           !(run && (sb & A3D_STORE_W_BF16))),
                   "conv2d_fwd: the fused pool takes float32 inputs (its output may be bf16) or bf16 x, w and y; 3-channel filters stay float32");
     rc = apply_storage(p, d->precision, sb & A3D_STORE_X_BF16, sb & A3D_STORE_W_BF16, sb & A3D_STORE_Y_BF16, d->c, d->ldx, d->k, d->k,
-                       x, w, y);
+                       x, w, y, "x", "w", "y");
     if (rc != A3D_OK) return rc;
     A3D_CHECK_ARG(!(pool && (p.a16 || p.b16)) || r.plan.ring,
                   "conv2d_pool_fwd: on bf16 inputs the fused pool is the LDS-DMA kernel's (channels and strides in whole 16-byte pieces, k %% 16 == 0)");
@@ -571,6 +585,7 @@ int a3d_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w,
   int rc = check_desc(d);
   if (rc != A3D_OK) return rc;
   A3D_CHECK_ARG(dz && w && dx, "conv2d_bwd_data: null tensor");
+  A3D_CHECK_WS(ws, "conv2d_bwd_data");
   if (!ws) ws_bytes = 0;
   const Operands o = launch_operands(dx, w, dz, relu_mask);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -598,15 +613,16 @@ int a3d_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w,
     IgemmParams p;
     fill_common(p, r.g);
     rc = apply_storage(p, d->precision, d->storage & A3D_STORE_Y_BF16, d->storage & A3D_STORE_W_BF16, d->storage & A3D_STORE_X_BF16,
-                       d->k, d->ldy, d->k, d->k, dz, w, dx);
+                       d->k, d->ldy, d->k, d->k, dz, w, dx, "dz", "w", "dx");
     if (rc != A3D_OK) return rc;
     A3D_CHECK_ARG(!p.c16 || !o.aux, "conv2d_bwd_data: bf16 mask must be 16-byte aligned");
     A3D_CHECK_ARG(!d->storage || r.plan.prec == A3D_PREC_BF16, "conv2d_bwd_data: bf16 storage needs vectorisable operands");
     if (multi16) {                           // the bf16 kernel's tiles, no split-K, no workspace
       multi16_bn = r.plan.bf16_bn;
       r.plan.splitk = 1; r.plan.ktiles_per_split = std::max(1, (r.g.K + 63) / 64);
-    } else if (r.bytes > ws_bytes) {
-      return set_error(A3D_EWORKSPACE, "conv2d_bwd_data: need %zu workspace bytes", r.bytes);
+    } else if (!multi32) {
+      fit_workspace(r, o, ws_bytes);
+      if (r.bytes > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd_data: need %zu workspace bytes", r.bytes);
     }
     fill_bwd_d_class(p, d, c, dz, w, dx, relu_mask);
     if (!multi32 && !multi16) {
@@ -718,6 +734,7 @@ int a3d_conv2d_bwd_filter_pooled(const a3d_conv_desc* d, const float* x, const v
   int rc = check_desc(d);
   if (rc != A3D_OK) return rc;
   A3D_CHECK_ARG(x && dpool && argmax && dw, "conv2d_bwd_filter_pooled: null tensor");
+  A3D_CHECK_WS(ws, "conv2d_bwd_filter_pooled");
   if (fewch16_wanted(d, true)) {                    // bf16 arithmetic: float32 image, bf16 pooled tensors
     A3D_CHECK_ARG(pooled_bf16 && ld_dpool >= d->k && ld_argmax >= d->k && ld_dpool % 4 == 0 &&
                       (reinterpret_cast<uintptr_t>(dpool) & 7) == 0 && (reinterpret_cast<uintptr_t>(pooled) & 7) == 0 &&
@@ -756,6 +773,7 @@ int a3d_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* d
   int rc = check_desc(d);
   if (rc != A3D_OK) return rc;
   A3D_CHECK_ARG(x && dz && dw, "conv2d_bwd_filter: null tensor");
+  A3D_CHECK_WS(ws, "conv2d_bwd_filter");
   if (!ws) ws_bytes = 0;
   if (stencil1_applicable(d)) {
     A3D_CHECK_ARG(!d->storage, "conv2d_bwd_filter: single-output-channel convs take float32 tensors");
@@ -771,13 +789,14 @@ int a3d_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* d
   // the window-run form if the workspace holds the padded gradient; else the tensors as stored, on the LDS-DMA kernel where that may be
   RunForm rf;
   const bool run = run_form_ok(d, o.x, &rf, true) && rf.bytes <= ws_bytes;
-  const Route r = bwd_f_gemm(d, o, run ? kRunForm : bwd_f_ring_ok(d, o) ? kLdsDma : kAsStored);
+  Route r = bwd_f_gemm(d, o, run ? kRunForm : bwd_f_ring_ok(d, o) ? kLdsDma : kAsStored);
+  fit_workspace(r, o, ws_bytes, o.db ? (size_t)r.g.N * 4 : 0);
   const GemmPlan& plan = r.plan;
   float* out = run ? static_cast<float*>(ws) : dw;
   IgemmParams p;
   fill_common(p, r.g);
   rc = apply_storage(p, d->precision, d->storage & A3D_STORE_X_BF16, d->storage & A3D_STORE_Y_BF16, false, d->c, d->ldx, -1, d->ldy,
-                     x, dz, dw);
+                     x, dz, dw, "x", "dz", "dw");
   if (rc != A3D_OK) return rc;
   A3D_CHECK_ARG(!d->storage || plan.prec == A3D_PREC_BF16, "conv2d_bwd_filter: bf16 storage needs vectorisable operands");
   if (r.bytes > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd_filter: need %zu workspace bytes", r.bytes);
@@ -842,6 +861,7 @@ int a3d_dense_fwd_ex2(int m, int k, int n, const float* x, const float* w, const
   int rc = check_desc(&d);
   if (rc != A3D_OK) return rc;
   A3D_CHECK_ARG(x && w && y, "dense_fwd: null tensor");
+  A3D_CHECK_WS(ws, "dense_fwd");
   if (precision == A3D_PREC_F32 && !storage && dense_stream_applicable(m, k, n) && aligned16(x) && !out2 && ldy == n && ncols_y == n &&
       !tune_int("A3D_NO_DENSE_KERNELS", 0))
     return dense_fwd_stream(m, k, n, x, w, bias, y, act, drop_keep, 2.f, ws, ws_bytes, static_cast<hipStream_t>(stream));
@@ -850,12 +870,14 @@ int a3d_dense_fwd_ex2(int m, int k, int n, const float* x, const float* w, const
   if (!aligned16(w)) g.bvec = 1;
   IgemmParams p;
   fill_common(p, g);
-  rc = apply_storage(p, precision, storage & A3D_STORE_X_BF16, storage & A3D_STORE_W_BF16, false, k, k, n, n, x, w, y);
+  rc = apply_storage(p, precision, storage & A3D_STORE_X_BF16, storage & A3D_STORE_W_BF16, false, k, k, n, n, x, w, y, "x", "w", "y");
   if (rc != A3D_OK) return rc;
+  A3D_CHECK_ARG(!p.a16 || aligned16(y), "dense_fwd: beside a bf16 x, y must be 16-byte aligned (the LDS-DMA kernel alone reads a bf16 x)");
   storage_vecs(g, p.a16, p.b16, p.c16);
   g.ring_ok = p.a16 && p.b16 && precision == A3D_PREC_BF16 && k % 8 == 0 && n % 8 == 0 && aligned16(y) && act != A3D_ACT_SIGMOID;
   g.need_reduce = ncols_y != n;                  // rows narrower than the GEMM are stored by the split-K reduction: plan one
   GemmPlan plan = plan_gemm(g, precision);
+  if (!aligned16(x) || !aligned16(w) || !aligned16(y)) plan = plan_within(g, plan, ws ? ws_bytes : 0, 0);      // (fit_workspace)
   A3D_CHECK_ARG(!storage || plan.prec == A3D_PREC_BF16, "dense_fwd: bf16 weights need vectorisable operands");
   A3D_CHECK_ARG(!p.a16 || plan.ring, "dense_fwd: a bf16 x is taken by the LDS-DMA kernel only (bf16 weights, k and n multiples of 8)");
   if (plan.ws_bytes > ws_bytes) return set_error(A3D_EWORKSPACE, "dense_fwd: need %zu workspace bytes", plan.ws_bytes);
@@ -895,18 +917,21 @@ int a3d_dense_bwd_data_ex2(int m, int k, int n, const float* dz, const float* w,
   int rc = check_desc(&d);
   if (rc != A3D_OK) return rc;
   A3D_CHECK_ARG(dz && w && dx, "dense_bwd_data: null tensor");
+  A3D_CHECK_WS(ws, "dense_bwd_data");
   GemmProblem g = bwd_d_problem(&d);
   if (!aligned16(dz)) g.avec = 1;
   if (!aligned16(w)) g.bvec = 1;
   IgemmParams p;
   fill_common(p, g);
   rc = apply_storage(p, precision, storage & A3D_STORE_Y_BF16, storage & A3D_STORE_W_BF16, storage & A3D_STORE_X_BF16, n, n, n, n, dz, w,
-                     dx);
+                     dx, "dz", "w", "dx");
   if (rc != A3D_OK) return rc;
+  A3D_CHECK_ARG(!p.c16 || aligned16(mask), "dense_bwd_data: bf16 mask must be 16-byte aligned");
   storage_vecs(g, p.a16, p.b16, p.c16);
   g.ring_ok = p.a16 && p.b16 && precision == A3D_PREC_BF16 && k % 8 == 0 && n % 8 == 0 && aligned16(dx) &&
               (!mask || (aligned16(mask) && mask_act == A3D_ACT_RELU));
   GemmPlan plan = plan_gemm(g, precision);
+  if (!aligned16(dz) || !aligned16(w) || !aligned16(dx) || !aligned16(mask)) plan = plan_within(g, plan, ws ? ws_bytes : 0, 0);      // (fit_workspace)
   A3D_CHECK_ARG(!storage || plan.prec == A3D_PREC_BF16, "dense_bwd_data: bf16 weights need vectorisable operands");
   A3D_CHECK_ARG(!(p.a16 || p.c16) || plan.ring, "dense_bwd_data: bf16 dz / dx are taken by the LDS-DMA kernel only (bf16 weights, k and n multiples of 8, ReLU mask)");
   if (plan.ws_bytes > ws_bytes) return set_error(A3D_EWORKSPACE, "dense_bwd_data: need %zu workspace bytes", plan.ws_bytes);
@@ -930,6 +955,7 @@ size_t a3d_dense_bwd_filter_ws_bytes(int m, int k, int n) {
 int a3d_dense_bwd_filter(int m, int k, int n, const float* x, const float* dz, float* dw, float* db, void* ws,
                          size_t ws_bytes, void* stream) {
   A3D_CHECK_ARG(m > 0 && k > 0 && n > 0, "dense_bwd_filter: bad dims");
+  A3D_CHECK_WS(ws, "dense_bwd_filter");
   if (dense_dw_applicable(m, k, n) && (long)k * n >= (1L << 16) && !tune_int("A3D_NO_DENSE_KERNELS", 0)) {      // small batch: stream dw once (dense.hip)
     A3D_CHECK_ARG(x && dz && dw, "dense_bwd_filter: null tensor");
     return dense_dw_launch(m, k, n, x, dz, dw, db, static_cast<hipStream_t>(stream));

@@ -261,4 +261,20 @@ GemmPlan plan_gemm(const GemmProblem& g, int precision) {
   return plan;
 }
 
+// A launch whose operands lie off the 16-byte grid plans another GEMM than its *_ws_bytes query did (scalar gathers: another tile,
+// another split): it keeps the query's promise by splitting no deeper than the bytes it was given allow.  The LDS-DMA plans
+// (bf16 tensors, always on the grid) and a plan that must end in a reduction (need_reduce) are left as they are.
+GemmPlan plan_within(const GemmProblem& g, GemmPlan pl, size_t avail, size_t per_split) {
+  const size_t need = pl.ws_bytes + (pl.splitk > 1 ? (size_t)pl.splitk * per_split : 0);
+  if (need <= avail || pl.ring) return pl;
+  const int bk = pl.prec == A3D_PREC_F32 ? kCfgs[pl.cfg].bk : (pl.prec == A3D_PREC_BF16X3 ? 32 : 64);
+  const int nk = std::max(1, (g.K + bk - 1) / bk);
+  const size_t each = slab_bytes(g, 1) + per_split;
+  const int splitk = g.plain ? 1 : (int)std::min<size_t>(avail / each, (size_t)(pl.streamk > 0 ? std::min(nk, 256) : pl.splitk));
+  if (g.need_reduce && splitk < 2) return pl;
+  pl.streamk = 0;
+  finish_split(pl, g, nk, std::max(1, splitk));
+  return pl;
+}
+
 }  // namespace a3d

@@ -36,5 +36,8 @@ struct GemmProblem {
 };
 
 GemmPlan plan_gemm(const GemmProblem& g, int precision = 0);
+// `pl` if its slabs (and `per_split` more bytes per split: the bias gradient's row) fit into `avail` workspace bytes, else the same
+// tile with the deepest split-K that does, down to the unsplit launch, which needs none
+GemmPlan plan_within(const GemmProblem& g, GemmPlan pl, size_t avail, size_t per_split);
 
 }  // namespace a3d

@@ -77,6 +77,22 @@ typedef struct a3d_conv_desc {
 #define A3D_STORE_W_BF16 2
 #define A3D_STORE_Y_BF16 4
 
+/* Alignment of the conv / dense entry points' operands, stated once.
+ *   - A float32 tensor, a bias, and a uint8 row (argmax, drop_keep) may start at any multiple of its element size.  The kernels
+ *     are chosen per call by where the operands lie (16-byte gathers, 8-byte window runs, the LDS-DMA and few-channel kernels
+ *     need the 16-byte grid and give way to scalar gathers off it): the result is the same, only the speed differs.
+ *   - The entry points that say otherwise, and refuse with A3D_EINVAL before anything is enqueued:
+ *       bf16 tensors (A3D_STORE_*, the _ex forms' bf16 x / w / dz / dx / mask): base 16-byte aligned;
+ *       a3d_dense_fwd_ex / _ex2 with a bf16 x: the float32 y 16-byte aligned too (the LDS-DMA kernel alone reads a bf16 x);
+ *       a3d_conv2d_bwd_both: x, w and a float32 dx on a channel pair (8 bytes), a bf16 dx on 4 bytes, ws on 4 bytes;
+ *       a3d_conv2d_bwd_filter_pooled: x 16-byte aligned, dpool and pooled on whole 4-channel groups (float32: 16 bytes, bf16: 8);
+ *       the prepared filter of a3d_conv2d_fwd_prepare_filter: 16-byte aligned, and x of the launch that reads it as well.
+ *   - A3D_PREC_BF16 / A3D_PREC_BF16X3 arithmetic on float32 tensors needs channel counts (c and k, and the pixel strides) in
+ *     multiples of 4 and both gathered operands on the 16-byte grid; otherwise the launch runs in fp32 arithmetic, which is never
+ *     less exact than what was asked (a3d_timing_record.prec names the arithmetic a launch ran in).
+ *   - `ws`, where it is not NULL, must be 16-byte aligned (a3d_conv2d_bwd_both: 4-byte).  A workspace of the bytes the matching
+ *     *_ws_bytes query returns is enough wherever the operands lie: a launch whose off-grid operands would plan a deeper split
+ *     than the query's plans its split within the bytes it is given. */
 #define A3D_PREC_F32 0     /* exact fp32 on the fp32 matrix cores (default; what parity is stated for) */
 #define A3D_PREC_BF16X3 1  /* fp32 operands split into bf16 hi+lo, 3 bf16 MFMAs per product: ~1e-5 relative */
 #define A3D_PREC_BF16 2    /* operands rounded to bf16, fp32 accumulate (BASELINE config 5's arithmetic; storage: a3d_conv_desc.storage) */

@@ -590,3 +590,122 @@ def forced_bf16_rounded_combos():
 
 def forced_count():
     return len(forced_f32_combos()) + len(forced_bf16_combos()) + len(forced_bf16_rounded_combos())
+
+
+# ---- operands off the 16-byte grid (test_gpu_exact_offgrid.py) ----
+# include/a3d.h lets a float32 tensor, a bias or an argmax row start at any multiple of its element size; the front end routes by
+# address & 15 of every operand.  Byte offsets past a 256-byte boundary, by element type:
+OFFGRID_BYTES = {'f32': (4, 8, 12), 'bf16': (2, 4, 8), 'u8': (1, 4, 8)}
+OFFGRID_ALONE = 4                                       # sweep 1: each pointer operand alone (every type has this offset)
+OFFGRID_IMAGE = 8                                       # sweep 2: the image-side operand alone: 8-byte runs, b64 staging
+OFFGRID_TOGETHER = {'f32': 12, 'bf16': 2, 'u8': 1}      # sweep 3: all operands at once, each at the offset of its type not used above
+OFFGRID_WS = (16, 4)                                    # sweep 4: the workspace off the 256-byte grid, and off the 16-byte one
+ELEMENT_BYTES = {'f32': 4, 'bf16': 2, 'u8': 1}
+
+# entry (a key of the test's launchers) -> (the C entry point, its pointer operands in argument order, the image-side operand).
+# An operand's element type is 'f32' unless the launch's `types` names another.
+OFFGRID_ENTRIES = {
+    'conv2d_fwd': ('a3d_conv2d_fwd', ('x', 'w', 'bias', 'y'), 'x'),                       # bias + ReLU
+    'conv2d_pool_fwd': ('a3d_conv2d_pool_fwd', ('x', 'w', 'bias', 'y', 'argmax'), 'x'),
+    'conv2d_bwd_data': ('a3d_conv2d_bwd_data', ('dz', 'w', 'dx'), 'dx'),
+    'conv2d_bwd_data_mask': ('a3d_conv2d_bwd_data', ('dz', 'w', 'dx', 'mask'), 'dx'),
+    'conv2d_bwd_filter': ('a3d_conv2d_bwd_filter', ('x', 'dz', 'dw'), 'x'),
+    'conv2d_bwd_filter_db': ('a3d_conv2d_bwd_filter', ('x', 'dz', 'dw', 'db'), 'x'),
+    'conv2d_bwd_filter_pooled': ('a3d_conv2d_bwd_filter_pooled', ('x', 'dpool', 'pooled', 'argmax', 'dw', 'db'), 'x'),
+    'conv2d_bwd_both': ('a3d_conv2d_bwd_both', ('x', 'dz', 'w', 'dw', 'db', 'dx'), 'x'),
+    'dense_fwd': ('a3d_dense_fwd', ('x', 'w', 'bias', 'y', 'drop_keep'), 'x'),
+    'dense_bwd_data': ('a3d_dense_bwd_data', ('dz', 'w', 'dx', 'mask'), 'dx'),
+    'dense_bwd_filter': ('a3d_dense_bwd_filter', ('x', 'dz', 'dw', 'db'), 'x'),
+    'dense_bwd_filter_adam_tf1': ('a3d_dense_bwd_filter_adam_tf1', ('var_w', 'm_w', 'v_w', 'dz', 'x'), None),
+    'dense_fwd_ex': ('a3d_dense_fwd_ex', ('x', 'w', 'bias', 'y', 'drop_keep'), 'x'),
+    'dense_bwd_data_ex': ('a3d_dense_bwd_data_ex', ('dz', 'w', 'dx', 'mask'), 'dx'),
+}
+U8_OPERANDS = ('argmax', 'drop_keep')
+
+# the smallest shapes that still reach each route, all from the tables above
+OFFGRID_GENERIC = [(1, 9, 11, 16, 4, 3, 1, 'SAME'), (3, 13, 18, 32, 200, 3, 1, 'SAME')]      # generic fp32 GEMM, vec4-capable
+OFFGRID_GLDS_FROM = GENERIC                    # ... and the smallest of these whose on-grid forward is LDS-DMA staged (found on the GPU)
+OFFGRID_STRIDED = [STRIDED_ONE_LAUNCH[0]]
+OFFGRID_FEW_CHANNEL = [FEW_CHANNEL[1], FEW_CHANNEL[3], FEW_CHANNEL[2], FEW_CHANNEL[4]]      # conv3, window runs, fewch
+OFFGRID_POOL = [(2, 40, 52, 3, 63, 9, 2, 'VALID')] + [g[:6] + (1, 'SAME') for g in (GUARD[3], GUARD[2])]
+OFFGRID_POOLED_BWDF = [POOLED_BWDF[1]]
+OFFGRID_BOTH = [BOTH[0], BOTH[5], BOTH[2]]     # 64 channels SAME, 64 channels VALID, the 40-channel VALID case
+OFFGRID_BOTH_FWD = [BOTH[0], BOTH[5]]
+OFFGRID_BOTH_BWD_F = [BOTH[0]]
+OFFGRID_BF16_STORED = [RING_FWD[0]]            # (2, 13, 18, 64, 200, 3, 1, 'SAME')
+OFFGRID_BF16_ARITH = [OFFGRID_GENERIC[1]]      # bf16 / bf16x3 arithmetic on float32 tensors, E.wide_variants operands
+OFFGRID_DENSE = [DENSE[0], DENSE[1], DENSE[6]]
+OFFGRID_DENSE_ADAM = [(32, 384, 520), DENSE_STREAM_BF16[0]]
+OFFGRID_DENSE_BF16 = [DENSE_BF16[0]]
+assert OFFGRID_POOL[0][:7] == POOLED_BWDF[1][:7] and OFFGRID_BF16_STORED[0] == (2, 13, 18, 64, 200, 3, 1, 'SAME')
+assert all(c in GENERIC + [g[:6] + (1, 'SAME') for g in GUARD] for c in OFFGRID_GENERIC) and OFFGRID_STRIDED[0][6] == 2
+
+
+def operand_type(name, types=None):
+    return (types or {}).get(name, 'u8' if name in U8_OPERANDS else 'f32')
+
+
+def offgrid_sweep(entry, types=None, ws=True):
+    """[(label, {operand: byte offset}, workspace byte offset)] of one entry point: each operand alone at +4 bytes, the image-side
+    operand alone at +8, all operands together (float32 +12, bf16 +2, uint8 +1), then the workspace at +16 and +4 under on-grid
+    operands.  The first element is the on-grid launch the others are compared with."""
+    _, operands, image = OFFGRID_ENTRIES[entry]
+    for o in operands:
+        assert OFFGRID_ALONE in OFFGRID_BYTES[operand_type(o, types)] and OFFGRID_IMAGE in OFFGRID_BYTES[operand_type(o, types)]
+    out = [('on-grid', {}, 0)]
+    out += [(f'{o}+{OFFGRID_ALONE}', {o: OFFGRID_ALONE}, 0) for o in operands]
+    if image is not None:
+        out.append((f'{image}+{OFFGRID_IMAGE}', {image: OFFGRID_IMAGE}, 0))
+        out.append(('all', {o: OFFGRID_TOGETHER[operand_type(o, types)] for o in operands}, 0))
+    if ws:
+        out += [(f'ws+{b}', {}, b) for b in OFFGRID_WS]
+    for _, offs, _ in out:
+        for o, b in offs.items():
+            t = operand_type(o, types)
+            assert b in OFFGRID_BYTES[t] and b % ELEMENT_BYTES[t] == 0 and b % 16 != 0
+    return out
+
+
+def offgrid_offsets_used():
+    """every byte offset of OFFGRID_BYTES is used by some sweep"""
+    used = {t: {OFFGRID_ALONE, OFFGRID_IMAGE, OFFGRID_TOGETHER[t]} for t in OFFGRID_BYTES}
+    return all(used[t] == set(OFFGRID_BYTES[t]) for t in OFFGRID_BYTES)
+
+
+# What include/a3d.h says an entry point refuses: (C entry point, operand) -> the alignment in bytes its text asks of that operand
+# (float32 unless the key names the bf16 form).  Written from the header's alignment paragraph, not from the code: a launch whose
+# operand breaks one of these must return A3D_EINVAL before anything is enqueued, every other placement must be accepted.
+REFUSED = {
+    # "`ws` ... 16-byte aligned", every entry point with a workspace argument but the one below
+    **{(e, 'ws'): 16 for e in ('a3d_conv2d_fwd', 'a3d_conv2d_pool_fwd', 'a3d_conv2d_bwd_data', 'a3d_conv2d_bwd_filter',
+                               'a3d_conv2d_bwd_filter_pooled', 'a3d_dense_fwd', 'a3d_dense_bwd_data', 'a3d_dense_bwd_filter',
+                               'a3d_dense_fwd_ex', 'a3d_dense_bwd_data_ex')},
+    # a3d_conv2d_bwd_both: x, w and a float32 dx on a channel pair (8 bytes), a bf16 dx on a pair of its own (4), ws on 4
+    ('a3d_conv2d_bwd_both', 'x'): 8, ('a3d_conv2d_bwd_both', 'w'): 8, ('a3d_conv2d_bwd_both', 'dx'): 8,
+    ('a3d_conv2d_bwd_both', 'dx:bf16'): 4, ('a3d_conv2d_bwd_both', 'ws'): 4,
+    # a3d_conv2d_bwd_filter_pooled: x in 16-byte pieces; dpool / pooled in whole 4-channel groups: 16 bytes float32, 8 bytes bf16
+    ('a3d_conv2d_bwd_filter_pooled', 'x'): 16, ('a3d_conv2d_bwd_filter_pooled', 'dpool'): 16,
+    ('a3d_conv2d_bwd_filter_pooled', 'pooled'): 16, ('a3d_conv2d_bwd_filter_pooled', 'dpool:bf16'): 8,
+    ('a3d_conv2d_bwd_filter_pooled', 'pooled:bf16'): 8,
+    # bf16 tensors (A3D_STORE_*): base 16-byte aligned, whichever entry point reads or writes them
+    **{(e, o + ':bf16'): 16 for e, ops in (('a3d_conv2d_fwd', ('x', 'w', 'y')), ('a3d_conv2d_bwd_data', ('dz', 'w', 'dx', 'mask')),
+                                            ('a3d_conv2d_bwd_filter', ('x', 'dz')), ('a3d_dense_fwd_ex', ('x', 'w')),
+                                            ('a3d_dense_bwd_data_ex', ('dz', 'w', 'dx', 'mask'))) for o in ops},
+    # a3d_dense_fwd_ex on a bf16 x: the float32 y is written in 16-byte pieces by the LDS-DMA kernel, the only one that reads a bf16 x
+    ('a3d_dense_fwd_ex', 'y'): 16,
+}
+
+
+def refused_operands(entry, offsets, ws_off, types=None):
+    """the operands of this placement that include/a3d.h lets the entry point refuse (REFUSED), in argument order"""
+    cname, operands, _ = OFFGRID_ENTRIES[entry]
+    bad = []
+    for o in operands:
+        t = operand_type(o, types)
+        need = REFUSED.get((cname, o if t in ('f32', 'u8') else f'{o}:{t}'))
+        if need and offsets.get(o, 0) % need:
+            bad.append(o)
+    need = REFUSED.get((cname, 'ws'))
+    if need and ws_off % need:
+        bad.append('ws')
+    return bad

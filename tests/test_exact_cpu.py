@@ -301,3 +301,72 @@ def test_one_wrong_element_passes_relative_l2_and_fails_equality(case, tol, bf16
         assert rel_l2(mutant, cs.y) < tol                       # the suite's present criterion accepts it
         with pytest.raises(AssertionError):
             np.testing.assert_array_equal(mutant, cs.y)         # element-by-element equality does not
+
+
+# ---- operands off the 16-byte grid (test_gpu_exact_offgrid.py) ----
+@pytest.mark.parametrize('case', E.OFFGRID_GENERIC + E.OFFGRID_STRIDED + E.OFFGRID_FEW_CHANNEL + E.OFFGRID_POOL)
+def test_offgrid_conv_cases_are_exact_in_float32(case):
+    cs = E.conv_case(*case)
+    assert max(cs.headroom) < E.F32_EXACT
+    E.require_integers(cs.what, np.maximum(cs.y, 0))
+
+
+def test_offgrid_cases_of_the_other_routes():
+    for case in E.OFFGRID_POOLED_BWDF:
+        E.pooled_bwdf_case(*case)
+    for case in E.OFFGRID_BOTH + E.OFFGRID_BOTH_FWD + E.OFFGRID_BOTH_BWD_F:
+        E.both_case(*case)
+    for case in E.OFFGRID_BF16_STORED:
+        assert E.stores_bf16(case)
+        E.conv_case(*case).bf16('y', 'dx')
+    for case in E.OFFGRID_DENSE + E.OFFGRID_DENSE_ADAM:
+        E.dense_case(*case)
+    for case in E.OFFGRID_DENSE_BF16:
+        E.dense_case(*case).bf16()
+
+
+@pytest.mark.parametrize('case', E.OFFGRID_BF16_ARITH)
+def test_offgrid_wide_cases_tell_the_three_arithmetics_apart(case):
+    """an off-grid float32 operand turns a bf16 / bf16x3 request into fp32 arithmetic: with one operand wide, the bf16 reference
+    differs from the unrounded one in the outputs that read it, so the record's `prec` decides which one the output must equal"""
+    assert case[3] % 4 == 0 and case[4] % 4 == 0
+    for name, cs in E.wide_variants(case):
+        E.require_wide(f'{cs.what} {name}', getattr(cs, name))
+        assert max(cs.headroom) < E.F32_EXACT
+        reads = {'x': ('y', 'dw'), 'w': ('y', 'dx'), 'dz': ('dw', 'dx')}[name]
+        for out in reads:
+            assert (getattr(cs.arith_bf16, out) != getattr(cs, out)).mean() > 0.4
+            np.testing.assert_array_equal(getattr(cs.arith_bf16x3, out), getattr(cs, out))
+
+
+def test_offgrid_sweeps_and_the_refusal_table():
+    import os
+    import re
+    assert E.offgrid_offsets_used()
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'a3d.h')).read()
+    declared = set(re.findall(r'\b(a3d_\w+)\s*\(', header))
+    for cname, operands, image in E.OFFGRID_ENTRIES.values():
+        assert cname in declared and (image is None or image in operands)
+    for (cname, operand), align in E.REFUSED.items():
+        assert cname in declared, f'REFUSED names {cname}, which include/a3d.h does not declare'
+        assert align in (4, 8, 16)
+        name = operand.split(':')[0]
+        assert name == 'ws' or any(c == cname and name in ops for c, ops, _ in E.OFFGRID_ENTRIES.values()), (cname, operand)
+    # the header states the contract the table is written from
+    for phrase in ('Alignment', 'any multiple of', '16-byte'):
+        assert phrase in header
+    for entry, (cname, operands, image) in E.OFFGRID_ENTRIES.items():
+        sweep = E.offgrid_sweep(entry)
+        assert sweep[0] == ('on-grid', {}, 0)
+        alone = [offs for _, offs, _ in sweep if len(offs) == 1 and list(offs.values()) == [E.OFFGRID_ALONE]]
+        assert [list(o)[0] for o in alone] == list(operands)
+        assert [w for _, _, w in sweep if w] == list(E.OFFGRID_WS)
+        if image is not None:
+            assert ({image: E.OFFGRID_IMAGE} in [offs for _, offs, _ in sweep]) and any(len(offs) == len(operands) for _, offs, _ in sweep)
+    # a float32 operand anywhere is refused only where the table says so
+    assert E.refused_operands('conv2d_fwd', {'x': 4, 'w': 12, 'y': 8}, 16) == []
+    assert E.refused_operands('conv2d_fwd', {}, 4) == ['ws']
+    assert E.refused_operands('conv2d_fwd', {'x': 4, 'bias': 4}, 0, {'x': 'bf16', 'w': 'bf16', 'y': 'bf16'}) == ['x']
+    assert E.refused_operands('conv2d_bwd_both', {'x': 8, 'dx': 4}, 4) == ['dx']
+    assert E.refused_operands('conv2d_bwd_both', {'x': 4, 'dx': 4}, 0, {'dx': 'bf16'}) == ['x']
+    assert E.refused_operands('conv2d_bwd_filter_pooled', {'dpool': 8, 'pooled': 4, 'argmax': 1}, 0, {'dpool': 'bf16', 'pooled': 'bf16'}) == ['pooled']

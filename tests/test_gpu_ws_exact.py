@@ -7,7 +7,8 @@ NULL, 0), q being the query's answer, and must return 0, leave the 4096 tail byt
 through ops.* on the roomy workspace (same plan, same bits).
 
 The cases are the smallest shapes at which each candidate of the front end (csrc/igemm_host.hip) needs a workspace below that
-floor; operands are torch's own, 256-byte aligned.  Stream-K plans need more than 1 MiB: the other tests already run them
+floor; operands are torch's own, 256-byte aligned (tests/test_gpu_exact_offgrid.py repeats the promise with every operand off
+the 16-byte grid).  Stream-K plans need more than 1 MiB: the other tests already run them
 on exactly q."""
 import ctypes
 
