@@ -160,6 +160,12 @@ GRADLOSS_SIGNATURES = {
     'a3dg_silog_grad_loss_bwd_ex': (c_int, [c_int, c_int, c_int, _P, _P, c_int, c_float, _P, _P, _P, c_int, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_crf_valid.h declares (NON-REFERENCE extension, prefix a3dv_)
+CRF_VALID_SIGNATURES = {
+    'a3dv_superpixel_mean_valid': (c_int, [c_int, c_int, c_int, _P, c_int, c_int, _P, _P, _P]),
+    'a3dv_crf_loss_observed': (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -176,7 +182,8 @@ def load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(PAIR_SIGNATURES.items())
-                              + list(TEXTURE_SIGNATURES.items()) + list(GRADLOSS_SIGNATURES.items())):
+                              + list(TEXTURE_SIGNATURES.items()) + list(GRADLOSS_SIGNATURES.items())
+                              + list(CRF_VALID_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -47,10 +47,15 @@ def main(argv=None):
                      f'{args.model or "(no model)"} is not trained with it (dcnf computes its pairwise features from the '
                      f'resized image, and the paper behind it does not augment this way).')
         return 2
-    if (args.min_depth is not None or args.max_depth is not None) and args.model != 'msdn':
-        logger.error(f'--min-depth / --max-depth mask the holes of a depth map out of the msdn target and loss: '
-                     f'{args.model or "(no model)"} is not trained with them (dcnf regresses superpixel means, a mean over '
-                     f'a superpixel with holes is a different question).')
+    if (args.min_depth is not None or args.max_depth is not None) and not hasattr(getattr(models, args.model, None),
+                                                                                  'valid_range'):
+        logger.error(f'--min-depth / --max-depth keep the holes of a depth map out of the targets of msdn and dcnf: '
+                     f'{args.model or "(no model)"} is not trained with them.')
+        return 2
+    if args.model == 'dcnf' and (args.min_depth is None) != (args.max_depth is None):
+        logger.error('--model dcnf takes --min-depth and --max-depth together: its targets are means over 1600 pixels, the '
+                     'data sets it is reported on have holes at both ends of the range (no return and the range cap), and '
+                     'the kind a one-sided range lets through would be averaged into every superpixel it touches.')
         return 2
     if args.train_pairwise and not hasattr(getattr(models, args.model, None), 'train_pairwise'):
         logger.error(f'--train-pairwise learns the pairwise weights of the CRF of --model dcnf (Liu et al. 2015): '
@@ -387,10 +392,12 @@ def parse_args(argv=None):
                         help='NON-REFERENCE: train-time augmentation of the input batch on the GPU (msdn only). eigen: scale, '
                              'rotation, translation, flip and colour of Eigen et al. 2014, section 3.4.')
     parser.add_argument('--min-depth', default=None, type=float,
-                        help='NON-REFERENCE: the depth maps have holes (msdn only). A target pixel counts iff its stored depth t '
+                        help='NON-REFERENCE: the depth maps have holes (msdn, dcnf). A target pixel counts iff its stored depth t '
                              '(the float after the loader\'s +0.5: k/255 for converter-written records) is finite and '
-                             'min < t <= max; the others leave the resized target and both losses. Giving either flag turns '
-                             'the mode on, the other defaults to 0 / +inf.')
+                             'min < t <= max; the others leave the resized target and, for msdn, both losses; dcnf takes a '
+                             'superpixel as a target only if at least half of it counts, and trains on the likelihood of those '
+                             'superpixels alone. msdn: giving either flag turns the mode on, the other defaults to 0 / +inf; dcnf '
+                             'wants both. Still msdn only: --augment and --loss-gradient.')
     parser.add_argument('--max-depth', default=None, type=float, help='NON-REFERENCE: see --min-depth.')
     parser.add_argument('--loss-gradient', default=None, type=float, metavar='W',
                         help='NON-REFERENCE: add W times the gradient-matching term of Eigen & Fergus 2015 (eq. 4) to both '

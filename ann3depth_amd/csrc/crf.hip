@@ -8,9 +8,12 @@
 // LU and write d loss / d r, the gradient TF 1.3 lacks; pair_dense_bwd_kernel takes it to the pairwise dense layer and
 // sgd_floor_kernel keeps that layer's weights >= 0 (Liu et al. 2015, eq. 9-14).  include/a3d_texture.h
 // (--pairwise-texture) adds the paper's third similarity, texture disparity over local-binary-pattern histograms.
+// include/a3d_crf_valid.h (--model dcnf on depth maps with holes): the superpixel mean over the measured pixels and the
+// likelihood of the observed superpixels alone, the others integrated out (crf_observed_kernel).
 #include <algorithm>
 
 #include "a3d_internal.h"
+#include "a3d_crf_valid.h"
 #include "a3d_pairwise.h"
 #include "a3d_texture.h"
 
@@ -426,6 +429,250 @@ __global__ __launch_bounds__(64) void crf_map_kernel(const float* __restrict__ z
   if (lane == 0 && status) status[b] = bad ? 1 : 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// NON-REFERENCE (include/a3d_crf_valid.h, --model dcnf with --min-depth / --max-depth): depth maps with holes.
+
+// superpixel_mean_kernel over the finite pixels of a one-channel map: the same threads add the same pixels in the same
+// order, a hole adds nothing; c counts the pixels that were added.
+__global__ __launch_bounds__(256) void superpixel_mean_valid_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                                    int* __restrict__ count, int h, int w, int sp,
+                                                                    int min_count) {
+  __shared__ float red[4];
+  __shared__ int redc[4];
+  const int cols = w / sp, rows = h / sp;
+  const int p = blockIdx.x % (rows * cols), b = blockIdx.x / (rows * cols);
+  const int pr = p / cols, pc = p % cols;
+  float s = 0.f;
+  int c = 0;
+  for (int i = threadIdx.x; i < sp * sp; i += 256) {
+    const int yy = pr * sp + i / sp, xx = pc * sp + i % sp;
+    const float v = x[((size_t)b * h + yy) * w + xx];
+    if (isfinite(v)) { s += v; ++c; }
+  }
+  s = block_sum_256(s, red);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+  if ((threadIdx.x & 63) == 0) redc[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    c = redc[0] + redc[1] + redc[2] + redc[3];
+    const size_t o = (size_t)b * rows * cols + p;
+    out[o] = c >= max(1, min_count) ? s / (float)c : __builtin_nanf("");
+    if (count) count[o] = c;
+  }
+}
+
+// Elimination of the nn x nn system in the leading columns of U, carried over the columns 0 .. last, one lane per row: the
+// loss kernel's loop and pivot rule (crf_map_kernel's reading of a NaN: taken as the pivot at once).  *logdet = the sum
+// of the logs of the pivots.  True iff every pivot, after its exchange, is finite and > 0 and the number of exchanges is
+// even.  Nothing stops at a bad pivot: the values turn into NaN or inf, no index depends on them.  nn = 0: true, 0.
+template <int W>
+__device__ bool eliminate_positive(float (*U)[W], int nn, int last, int lane, float* logdet) {
+  bool ok = true;
+  float ld = 0.f;
+  int swaps = 0;
+  for (int k = 0; k < nn; ++k) {
+    float best = -1.f;
+    if (lane >= k && lane < nn) {
+      best = fabsf(U[lane][k]);
+      if (!(best == best)) best = INFINITY;
+    }
+    int arg = lane;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float ob = __shfl_xor(best, off, 64);
+      const int oa = __shfl_xor(arg, off, 64);
+      if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+    }
+    if (arg != k) {                             // arg is a row in [k, nn): lane k always offers a value >= 0
+      for (int j = lane; j <= last; j += 64) { const float t = U[k][j]; U[k][j] = U[arg][j]; U[arg][j] = t; }
+      ++swaps;
+    }
+    __syncthreads();
+    const float piv = U[k][k];
+    ok = ok && piv > 0.f && piv < INFINITY;
+    ld += logf(piv);
+    if (lane > k && lane < nn) {
+      const float f = U[lane][k] / piv;
+      for (int j = k; j <= last; ++j) U[lane][j] -= f * U[k][j];
+    }
+    __syncthreads();
+  }
+  *logdet = ld;
+  return ok && !(swaps & 1);
+}
+
+// Back substitution after eliminate_positive: x = the solution of column nn (lane 0, serial, as the loss kernel), and with
+// `inverse` the nn columns behind it in place, one lane per column.
+template <int W>
+__device__ void back_substitute(float (*U)[W], int nn, int lane, bool inverse, float* x) {
+  if (lane == 0) {
+    for (int i = nn - 1; i >= 0; --i) {
+      float s = U[i][nn];
+      for (int j = i + 1; j < nn; ++j) s -= U[i][j] * x[j];
+      x[i] = s / U[i][i];
+    }
+  }
+  if (inverse && lane < nn) {
+    const int c = nn + 1 + lane;
+    for (int i = nn - 1; i >= 0; --i) {
+      float s = U[i][c];
+      for (int j = i + 1; j < nn; ++j) s -= U[i][j] * U[j][c];
+      U[i][c] = s / U[i][i];
+    }
+  }
+  __syncthreads();
+}
+
+// One wavefront per image: the negative log-likelihood of the superpixels whose target y is finite (O, m of them; M the
+// others), L = q^T A q + (log det A_MM - log det A) / 2 + m log(pi) / 2 with q = yhat - A^-1 z, yhat = y on O and the
+// conditional mean A_MM^-1 (z_M - A_MO y_O) on M; dz = -2 q / batch; kPairGrad: dr too (include/a3d_crf_valid.h has the
+// derivation).  Two eliminations, one after the other in the same tile U: [A | z | I] and, the missing rows and columns
+// of A moved together in their order, [A_MM | z_M - A_MO y_O | I] (the identity columns only under kPairGrad).  A stays in
+// its own tile for the second system and for q^T A q.
+// LDS: A 64 x 65 floats (16640 bytes), U 64 x 131 (33536; 64 x 67 = 17152 without dr), seven arrays of 64 words and a flag
+// (1796): 51972 bytes under kPairGrad, 35588 without.  Both row strides are odd: lanes that walk a column, one row each,
+// and lanes that walk along a row hit different banks.
+// y is read once, to tell finite from not; an entry that is not finite is never used again.  dr holds S_k(A^-1) of every
+// pair between the two eliminations (each lane reads back only what it wrote itself).
+// Every index into A, U and the arrays is a lane, a pair index checked against [0, n), a rank below the number of missing
+// superpixels, or a column <= 2 n.
+constexpr float kHalfLogPi = 0.57236494292470009f;
+template <bool kPairGrad>
+__global__ __launch_bounds__(64) void crf_observed_kernel(const float* __restrict__ z, const float* __restrict__ y,
+                                                          const float* __restrict__ r, const int* __restrict__ left,
+                                                          const int* __restrict__ right, float* __restrict__ loss_img,
+                                                          float* __restrict__ dz, float* dr, int* __restrict__ nobs,
+                                                          int* __restrict__ status, int n, int npairs, float inv_batch) {
+  constexpr int W = kPairGrad ? 2 * kMaxSp + 3 : kMaxSp + 3;
+  __shared__ float A[kMaxSp][kMaxSp + 1];
+  __shared__ float U[kMaxSp][W];
+  __shared__ float zs[kMaxSp], yh[kMaxSp], mu[kMaxSp], xm[kMaxSp], qv[kMaxSp];
+  __shared__ int mrank[kMaxSp], midx[kMaxSp];
+  __shared__ int bad_index;
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const float nanf_ = __builtin_nanf("");
+  for (int i = lane; i < n * n; i += 64) A[i / n][i % n] = 0.f;
+  __syncthreads();
+  if (lane == 0) {                              // scatter the pair weights in pair order: R[l][r] = R[r][l] = r_q
+    int skipped = 0;
+    for (int q = 0; q < npairs; ++q) {
+      const int l = left[q], rr = right[q];
+      if (l < 0 || l >= n || rr < 0 || rr >= n) { skipped = 1; continue; }     // skipped, never indexed with
+      const float v = r[(size_t)b * npairs + q];
+      A[l][rr] = v;
+      A[rr][l] = v;
+    }
+    bad_index = skipped;
+  }
+  __syncthreads();
+  const bool bad = bad_index != 0;
+  const float zi = lane < n ? z[(size_t)b * n + lane] : 0.f;
+  const float yraw = lane < n ? y[(size_t)b * n + lane] : 0.f;
+  const bool obs = lane < n && isfinite(yraw);
+  const bool mis = lane < n && !obs;
+  const float yi = obs ? yraw : 0.f;            // from here on an unobserved target is not looked at
+  const unsigned long long mis_mask = __ballot(mis);
+  const int m = __popcll(__ballot(obs)), km = __popcll(mis_mask);
+  if (bad || m == 0) {                          // the whole wavefront: the index lists are the batch's, m is the image's
+    const float v = bad ? nanf_ : 0.f;
+    if (lane == 0) {
+      loss_img[b] = v;
+      nobs[b] = m;
+      status[b] = bad ? 1 : 0;
+    }
+    if (lane < n) dz[(size_t)b * n + lane] = v;
+    if (kPairGrad)
+      for (int q = lane; q < npairs; q += 64) dr[(size_t)b * npairs + q] = v;
+    return;
+  }
+  const int rank = __popcll(mis_mask & ((1ull << lane) - 1ull));
+  if (lane < n) {
+    zs[lane] = zi;
+    yh[lane] = yi;
+    mrank[lane] = mis ? rank : -1;
+    if (mis) midx[rank] = lane;
+    float rs = 0.f;                             // A = I + diag(row sums of R) - R, the loss kernel's arithmetic
+    for (int j = 0; j < n; ++j) rs += A[lane][j];
+    for (int j = 0; j < n; ++j) A[lane][j] = (j == lane ? 1.f + rs : 0.f) - A[lane][j];
+    for (int j = 0; j < n; ++j) U[lane][j] = A[lane][j];
+    U[lane][n] = zi;
+    if (kPairGrad)
+      for (int j = 0; j < n; ++j) U[lane][n + 1 + j] = j == lane ? 1.f : 0.f;
+  }
+  __syncthreads();
+  float ld_a, ld_m;
+  const bool ok_a = eliminate_positive<W>(U, n, kPairGrad ? 2 * n : n, lane, &ld_a);
+  back_substitute<W>(U, n, lane, kPairGrad, mu);                        // mu = A^-1 z; A^-1 behind column n
+  if (kPairGrad) {
+    for (int q = lane; q < npairs; q += 64) {
+      const int l = left[q], rr = right[q];                             // not bad: inside [0, n)
+      dr[(size_t)b * npairs + q] = ((U[l][n + 1 + l] + U[rr][n + 1 + rr]) - U[l][n + 1 + rr]) - U[rr][n + 1 + l];
+    }
+    __syncthreads();                                                    // A^-1 has been read: U is free
+  }
+  if (lane < km) {                              // row `lane` of the second system: missing superpixel i = midx[lane]
+    const int i = midx[lane];
+    for (int c = 0; c < km; ++c) U[lane][c] = A[i][midx[c]];
+    float s = 0.f;
+    for (int j = 0; j < n; ++j) s += A[i][j] * yh[j];                   // yh = 0 on M: A_MO y_O
+    U[lane][km] = zs[i] - s;
+    if (kPairGrad)
+      for (int c = 0; c < km; ++c) U[lane][km + 1 + c] = c == lane ? 1.f : 0.f;
+  }
+  __syncthreads();
+  const bool ok_m = eliminate_positive<W>(U, km, kPairGrad ? 2 * km : km, lane, &ld_m);
+  back_substitute<W>(U, km, lane, kPairGrad, xm);                       // xm = yhat_M; A_MM^-1 behind column km
+  float qi = 0.f;
+  if (lane < n) {
+    qi = (obs ? yi : xm[rank]) - mu[lane];
+    qv[lane] = qi;
+  }
+  __syncthreads();
+  float aq = 0.f;
+  if (lane < n)
+    for (int j = 0; j < n; ++j) aq += A[lane][j] * qv[j];
+  const float qAq = wave_sum_f(qi * aq);
+  const float loss = (qAq + 0.5f * (ld_m - ld_a)) + (float)m * kHalfLogPi;
+  const bool nan_row = !(ok_a && ok_m && isfinite(loss));
+  if (lane == 0) {
+    loss_img[b] = nan_row ? nanf_ : loss;
+    nobs[b] = m;
+    status[b] = nan_row ? 1 : 0;
+  }
+  if (lane < n) dz[(size_t)b * n + lane] = nan_row ? nanf_ : (-2.f * qi) * inv_batch;
+  if (kPairGrad) {
+    __syncthreads();                            // A has been read (every lane its own row): the last writers move there
+    if (lane == 0)
+      for (int q = 0; q < npairs; ++q) {
+        const int l = left[q], rr = right[q];
+        A[l][rr] = A[rr][l] = __int_as_float(q);
+      }
+    __syncthreads();
+    for (int q = lane; q < npairs; q += 64) {
+      float v = nanf_;
+      if (!nan_row) {
+        const int l = left[q], rr = right[q];
+        v = 0.f;
+        if (__float_as_int(A[l][rr]) == q) {                            // else a later pair overwrote both cells
+          const float s_a = dr[(size_t)b * npairs + q];
+          const int gl = mrank[l], gr = mrank[rr];
+          float s_m = 0.f;                                              // S_k of A_MM^-1 padded with zeros
+          if (gl >= 0 && gr >= 0)
+            s_m = ((U[gl][km + 1 + gl] + U[gr][km + 1 + gr]) - U[gl][km + 1 + gr]) - U[gr][km + 1 + gl];
+          else if (gl >= 0)
+            s_m = U[gl][km + 1 + gl];
+          else if (gr >= 0)
+            s_m = U[gr][km + 1 + gr];
+          const float vq = qv[l] - qv[rr], vm = mu[l] - mu[rr];
+          v = (((2.f * vq) * vm + vq * vq) - 0.5f * (s_a - s_m)) * inv_batch;
+        }
+      }
+      dr[(size_t)b * npairs + q] = v;
+    }
+  }
+}
+
 __global__ __launch_bounds__(64) void mean_kernel(const float* __restrict__ v, int n, float* __restrict__ out) {
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += 64) s += v[i];
@@ -553,6 +800,32 @@ int a3d_crf_map(int n, int nsp, const float* z, const float* r, const int32_t* l
   hipLaunchKernelGGL(crf_map_kernel, dim3(n), dim3(64), 0, static_cast<hipStream_t>(stream), z, r, left, right, y,
                      status, nsp, npairs);
   return check_launch("crf_map");
+}
+
+int a3dv_superpixel_mean_valid(int n, int h, int w, const float* x, int sp, int min_count, float* y, int32_t* count,
+                               void* stream) {
+  A3D_CHECK_ARG(n > 0 && sp > 0 && h > 0 && w > 0 && h % sp == 0 && w % sp == 0 && min_count >= 0 && x && y,
+                "superpixel_mean_valid: bad arguments");
+  clear_stale_error();
+  hipLaunchKernelGGL(superpixel_mean_valid_kernel, dim3(n * (h / sp) * (w / sp)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), x, y, count, h, w, sp, min_count);
+  return check_launch("superpixel_mean_valid");
+}
+
+int a3dv_crf_loss_observed(int n, int nsp, const float* z, const float* y, const float* r, const int32_t* left,
+                           const int32_t* right, int npairs, float* loss_per_image, float* loss_mean, float* dz, float* dr,
+                           int32_t* nobs, int32_t* status, void* stream) {
+  A3D_CHECK_ARG(n > 0 && nsp > 0 && nsp <= kMaxSp && npairs > 0 && z && y && r && left && right && loss_per_image &&
+                    loss_mean && dz && nobs && status, "crf_loss_observed: bad arguments (at most %d superpixels)", kMaxSp);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  clear_stale_error();
+  hipLaunchKernelGGL(dr ? crf_observed_kernel<true> : crf_observed_kernel<false>, dim3(n), dim3(64), 0, st, z, y, r, left,
+                     right, loss_per_image, dz, dr, nobs, status, nsp, npairs, 1.0f / (float)n);
+  int rc = check_launch("crf_loss_observed");
+  if (rc != A3D_OK) return rc;
+  clear_stale_error();
+  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(64), 0, st, loss_per_image, n, loss_mean);
+  return check_launch("crf_loss_observed_mean");
 }
 
 int a3d_sgd_apply(size_t count, float* var, const float* g, float lr, void* stream) {

@@ -171,9 +171,14 @@ class DCNFEvaluator:
     outputs = OUTPUTS['dcnf']
 
     def __init__(self, replica, resolution='grid', min_depth=0., max_depth=float('inf'), clamp_lo=1e-3,
-                 clamp_hi=float('inf'), keep_predictions=False):
+                 clamp_hi=float('inf'), keep_predictions=False, observed_nll=False):
+        """observed_nll (NON-REFERENCE): also the training objective of a run with --min-depth / --max-depth, the
+        likelihood of the superpixels that (min_depth, max_depth] leaves observed (DCNFReplica.nll(valid_range=...)); it
+        runs last in a batch, after the metrics have read the plainly resized targets."""
         self.rep, self.resolution = replica, resolution
         self.kw = dict(min_depth=min_depth, max_depth=max_depth, clamp_lo=clamp_lo, clamp_hi=clamp_hi)
+        self.observed = (float(min_depth), float(max_depth)) if observed_nll else None
+        self.onll, self.nobs = [], []
         self.rows = {o: [] for o in self.outputs}
         self.nll, self.status = [], []
         self.counts = []
@@ -191,6 +196,9 @@ class DCNFEvaluator:
         self.counts.append(n)
         if self.predictions is not None:
             self.predictions.append(crf[:n].clone())
+        if self.observed is not None:
+            self.onll.append(rep.nll(depths, n, valid_range=self.observed))
+            self.nobs.append(rep.nobs.sum().reshape(1))
 
     def results(self):
         torch.cuda.synchronize()
@@ -199,6 +207,10 @@ class DCNFEvaluator:
         per_batch = torch.cat(self.nll).double().cpu().numpy()
         out['crf_nll'] = float((per_batch * n).sum() / n.sum())
         out['singular_systems'] = int(torch.cat(self.status).sum().item())
+        if self.observed is not None:
+            per_batch = torch.cat(self.onll).double().cpu().numpy()
+            out['observed_nll'] = float((per_batch * n).sum() / n.sum())
+            out['observed_fraction'] = float(torch.cat(self.nobs).sum().item() / (n.sum() * self.rep.nsp))
         return out
 
 
@@ -213,6 +225,9 @@ def main(argv=None):
     args = parse_args(argv)
     if args.model not in OUTPUTS:
         _say(f'unknown model {args.model!r}; msdn and dcnf can be evaluated.')
+        return 2
+    if args.observed_nll and args.model != 'dcnf':
+        _say('--observed-nll is the held-out objective of a dcnf run trained with --min-depth / --max-depth.')
         return 2
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         _say('evaluation runs in one process on one GPU; start it without a distributed launcher.')
@@ -255,8 +270,9 @@ def main(argv=None):
     step = replica.global_step
     pipeline = inputs.pipeline
     evaluator = DCNFEvaluator if args.model == 'dcnf' else Evaluator
+    extra = {'observed_nll': True} if args.observed_nll else {}
     ev = evaluator(replica, args.resolution, args.min_depth, args.max_depth, args.clamp_lo, args.clamp_hi,
-                   keep_predictions=bool(args.predictions))
+                   keep_predictions=bool(args.predictions), **extra)
     op = EvalOp(pipeline, args.batchsize, dev)
     try:
         while True:
@@ -284,6 +300,8 @@ def main(argv=None):
     scalars = {f'eval/{o}/{k}': float(v) for o in ev.outputs for k, v in res[o].items()}
     if 'crf_nll' in res:
         scalars['eval/crf_nll'] = res['crf_nll']
+    if 'observed_nll' in res:
+        scalars['eval/observed_nll'] = res['observed_nll']
     events.add_scalars(step, scalars)
     events.close()
     print(json.dumps(out), flush=True)
@@ -311,6 +329,10 @@ def parse_args(argv=None):
     p.add_argument('--max-depth', default=float('inf'), type=float, help='Valid targets are <= this.')
     p.add_argument('--clamp-lo', default=1e-3, type=float, help='Predictions are clamped to at least this.')
     p.add_argument('--clamp-hi', default=float('inf'), type=float, help='Predictions are clamped to at most this.')
+    p.add_argument('--observed-nll', action='store_true',
+                   help='NON-REFERENCE, dcnf: also report observed_nll, the objective of a run trained with --min-depth / '
+                        '--max-depth (the likelihood of the superpixels those two thresholds leave observed), and the share '
+                        'of superpixels it counted.')
     p.add_argument('--predictions', default='', type=str,
                    help='Write the fine (msdn, [N,55,74]) or crf (dcnf, [N,6,8]) predictions to this .npy.')
     return p.parse_args(argv)

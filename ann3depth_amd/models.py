@@ -1283,11 +1283,31 @@ class DCNFReplica:
     name, drawn from the same stream; the forward launches ops.superpixel_lbp_hist and ops.pair_similarity3 in place of
     ops.pair_similarity.  Meant to go with train_pairwise (the backward reads K from sims); without it the layer keeps
     its draw.  A [2,1] kernel is refused at restore, as a [3,1] one is without the argument.  Off (the default),
-    construction and every launch are what they are without it."""
+    construction and every launch are what they are without it.
+
+    valid_range (NON-REFERENCE, --min-depth / --max-depth): (min_depth, max_depth) — the depth maps have holes
+    (include/a3d_crf_valid.h).  The target is resized validity-aware (ops.resize_bilinear_tf1_valid: NaN where a tap is
+    not finite or not in (min_depth, max_depth]), a superpixel's target is the mean of its measured pixels
+    (ops.superpixel_mean_valid), and the objective is the field's negative log-likelihood of the observed superpixels
+    alone, the others integrated out (ops.crf_loss_observed: no epsilons; with every superpixel observed it is the
+    reference's loss without its three).  Its dz goes into the unary backward, its dr, under train_pairwise, into the
+    pairwise layer's.  min_valid: a superpixel is a target only if at least ceil(min_valid * 40 * 40) of its pixels were
+    measured.  The default, 0.5, is a choice, not a derivation: a mean over the measured minority of a block that is
+    mostly sky or shadow describes its edge, not the superpixel.  None (the default): no launch, buffer or bit differs."""
     uses_dropout = False
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, global_step=0, reducer=None,
-                 precision='fp32', train_pairwise=False, pairwise_texture=False):
+                 precision='fp32', train_pairwise=False, pairwise_texture=False, valid_range=None, min_valid=0.5):
+        if valid_range is not None:
+            lo, hi = (float(v) for v in valid_range)
+            if not lo <= hi:
+                raise ValueError(f'valid_range {valid_range!r}: (min_depth, max_depth) with min_depth <= max_depth')
+            valid_range = (lo, hi)
+        if not 0 <= float(min_valid) <= 1:
+            raise ValueError(f'min_valid {min_valid!r}: the share of a superpixel that must be measured, 0 .. 1')
+        self.valid_range, self.min_valid = valid_range, float(min_valid)
+        self.min_count = int(math.ceil(self.min_valid * DCNF_SP * DCNF_SP))
+        self.t_one = self.count = self.nobs = None      # allocated by the first launch that has holes to look for
         self.B = batchsize
         self.device = dev = torch.device(device)
         self.reducer = reducer
@@ -1361,6 +1381,10 @@ class DCNFReplica:
     def forward_crf(self, depths):
         """Everything after the unary stack: target superpixels, pairwise r, CRF loss and d loss / d z."""
         u = self.unary
+        if self.valid_range is not None:
+            self._pairwise()
+            self.loss = self._observed(depths, self.B, self.valid_range, self.train_pairwise)
+            return self.loss
         ops.resize_bilinear_tf1(depths, self.depths240)                                   # src/models.py:181
         self._pairwise()
         ops.superpixel_mean(self.depths240, DCNF_SP, self.y)                              # :131-132
@@ -1370,6 +1394,21 @@ class DCNFReplica:
         else:
             self.loss, self.loss_per_image, self.dz = ops.crf_loss(*crf_args)             # :129-177
         return self.loss
+
+    def _observed(self, depths, n, valid_range, pair_grad):
+        """valid_range's objective on rows [0, n) from the z and r that stand in the buffers: the targets through the
+        validity-aware resize and superpixel mean, then the likelihood of the observed superpixels.  Leaves loss_per_image,
+        dz, dr (None without pair_grad), nobs and status of those rows; returns the mean [1]."""
+        if self.t_one is None:
+            self.t_one = torch.empty((self.B, 1, 1, 1), device=self.device)
+            self.count = torch.empty((self.B, self.nsp), dtype=torch.int32, device=self.device)
+        lo, hi = valid_range
+        y = self.y.view(self.B, self.nsp)
+        ops.resize_bilinear_tf1_valid(depths[:n], self.depths240[:n], lo, hi, scratch=self.t_one[:n])
+        ops.superpixel_mean_valid(self.depths240[:n], DCNF_SP, self.min_count, out=y[:n], count=self.count[:n])
+        mean, self.loss_per_image, self.dz, self.dr, self.nobs, self.status_observed = ops.crf_loss_observed(
+            self.unary.z.view(self.B, self.nsp)[:n], y[:n], self.r[:n], self.left, self.right, pair_grad=pair_grad)
+        return mean
 
     def predict(self, images, n=None):
         """The model's depths for a batch of images, without targets: (unary, crf), each [B, rows, cols] float32 (views
@@ -1392,12 +1431,17 @@ class DCNFReplica:
         self.crf, self.status = ops.crf_map(u.z.view(B, self.nsp), self.r, self.left, self.right, self.crf, self.status)
         return u.z.view(B, self.rows, self.cols), self.crf.view(B, self.rows, self.cols)
 
-    def nll(self, depths, n):
+    def nll(self, depths, n, valid_range=None):
         """The training objective (src/models.py:129-177) on rows [0, n) of the batch predict() just ran, from the z
-        and r it left: the mean of the n images' CRF negative log-likelihoods, [1] float32 on the device."""
+        and r it left: the mean of the n images' CRF negative log-likelihoods, [1] float32 on the device.  valid_range
+        (the replica's by default): the likelihood of the observed superpixels instead, as the train step computes it; the
+        numbers of observed superpixels are left in self.nobs."""
         n = int(n)
         if self.r is None or not 0 < n <= min(self.B, depths.shape[0]):
             raise ValueError(f'nll: n = {n} rows of {depths.shape[0]} depth maps, replica batch {self.B}, after predict()')
+        valid_range = self.valid_range if valid_range is None else valid_range
+        if valid_range is not None:
+            return self._observed(depths, n, valid_range, False)
         ops.resize_bilinear_tf1(depths[:n], self.depths240[:n])                           # src/models.py:181
         ops.superpixel_mean(self.depths240[:n], DCNF_SP, self.y[:n])                      # :131-132
         mean, _, _ = ops.crf_loss(self.unary.z.view(self.B, self.nsp)[:n], self.y.view(self.B, self.nsp)[:n],
@@ -1424,13 +1468,17 @@ class DCNFReplica:
         return {'mean_loss': self.loss}
 
     def summary_scalars(self, out):
-        return {'loss/mean_loss': float(out['mean_loss'])}                                # src/models.py:174
+        rec = {'loss/mean_loss': float(out['mean_loss'])}                                 # src/models.py:174
+        if self.valid_range is not None:                 # NON-REFERENCE: share of the superpixels that were targets
+            rec['loss/observed_fraction'] = float(self.nobs.sum()) / (self.B * self.nsp)
+        return rec
 
     def summary_images(self):
         """src/models.py:187-196; max_outputs=1."""
         ops.resize_bilinear_tf1(self.unary.z.view(self.B, self.rows, self.cols, 1), self.output)
+        target = self.depths240 if self.valid_range is None else torch.nan_to_num(self.depths240[:1], nan=0.0)   # a hole is 0
         return [('summaries/Output', self.output, 1), ('summaries/Input', self.unary.resized, 1),
-                ('summaries/Target', self.depths240, 1)]
+                ('summaries/Target', target, 1)]
 
     def broadcast_state(self, dist, src=0):
         for g in self.groups.values():
@@ -1641,13 +1689,16 @@ class _DistributedConvolutionalNeuralFields:
     beta2 = None         # accepted for symmetry with msdn; gradient descent has no beta
     train_pairwise = False   # NON-REFERENCE, --train-pairwise: the pairwise dense layer learns, >= 0 (see DCNFReplica)
     pairwise_texture = False  # NON-REFERENCE, --pairwise-texture: LBP texture disparity as a third similarity (see DCNFReplica)
+    valid_range = None   # NON-REFERENCE, --min-depth / --max-depth: (min, max), the depth maps have holes (see DCNFReplica)
+    min_valid = 0.5      # the share of a superpixel that must be measured for it to be a target (see DCNFReplica)
 
     def __call__(self, images, depths, train=True):
         assert images.pipeline is depths.pipeline, 'inputs and targets must come from the same data.inputs() call'
         self.train = train
         replica = DCNFReplica(images.pipeline.B, device=torch.device('cuda', torch.cuda.current_device()),
                               seed=self.seed, reducer=self.reducer, precision=self.precision,
-                              train_pairwise=self.train_pairwise and train, pairwise_texture=self.pairwise_texture)
+                              train_pairwise=self.train_pairwise and train, pairwise_texture=self.pairwise_texture,
+                              valid_range=self.valid_range, min_valid=self.min_valid)
         if self.reducer is not None:
             for g in replica.groups.values():
                 self.reducer.broadcast(g.var)

@@ -871,6 +871,64 @@ def crf_map(z, r, left, right, y=None, status=None):
     return y, status
 
 
+def superpixel_mean_valid(x, sp, min_count=0, out=None, count=None):
+    """NON-REFERENCE (a3dv_superpixel_mean_valid): superpixel_mean of a one-channel map with holes.  x [n,h,w,1] float32
+    with NaN (or an infinity) where nothing was measured -> (y [n,P] float32, count [n,P] int32): per superpixel the number
+    of finite pixels and their mean, NaN where fewer than max(1, min_count) are finite.  With every pixel finite y is
+    superpixel_mean's bits."""
+    if x.dim() != 4 or x.shape[3] != 1 or sp <= 0 or x.shape[1] % sp or x.shape[2] % sp or x.numel() == 0:
+        raise ValueError(f'superpixel_mean_valid: x {tuple(x.shape)} is not [n, h, w, 1] with h, w multiples of sp = {sp}')
+    if min_count < 0:
+        raise ValueError(f'superpixel_mean_valid: min_count {min_count}')
+    n, h, w, _ = x.shape
+    shape = (n, (h // sp) * (w // sp))
+    out = out if out is not None else torch.empty(shape, dtype=torch.float32, device=x.device)
+    count = count if count is not None else torch.empty(shape, dtype=torch.int32, device=x.device)
+    if out.numel() != shape[0] * shape[1] or count.numel() != out.numel():
+        raise ValueError(f'superpixel_mean_valid: out {tuple(out.shape)}, count {tuple(count.shape)} for {shape}')
+    if x.dtype != torch.float32 or out.dtype != torch.float32 or count.dtype != torch.int32:
+        raise TypeError('superpixel_mean_valid: x, out float32; count int32')
+    if not all(t.is_contiguous() for t in (x, out, count)):
+        raise ValueError('superpixel_mean_valid: contiguous tensors only')
+    if out.device != x.device or count.device != x.device:
+        raise ValueError('superpixel_mean_valid: all tensors on one device')
+    check(_lib.load().a3dv_superpixel_mean_valid(n, h, w, _ptr(x), sp, int(min_count), _ptr(out), _ptr(count), _stream()),
+          'a3dv_superpixel_mean_valid')
+    return out, count
+
+
+def crf_loss_observed(z, y, r, left, right, pair_grad=True):
+    """NON-REFERENCE (a3dv_crf_loss_observed): the CRF's negative log-likelihood of the superpixels whose target is finite,
+    the others integrated out: returns (mean [1], per-image [n], d mean / d z [n,P], d mean / d r [n,Q] or None without
+    pair_grad, nobs [n] int32, status [n] int32).  z, y [n,P] (y NaN where there is no target), r [n,Q] float32; left,
+    right [Q] int32.  An image without a target has loss 0 and zero gradients; one whose A is not positive is NaN with
+    status 1; a pair index outside [0, P) turns all of it into NaN."""
+    if z.dim() != 2 or r.dim() != 2:
+        raise ValueError(f'crf_loss_observed: z {tuple(z.shape)} and r {tuple(r.shape)} must be [n, P] and [n, Q]')
+    n, nsp = z.shape[0], z.shape[1]
+    if (n == 0 or tuple(y.shape) != (n, nsp) or r.shape[0] != n or left.numel() == 0 or r.shape[1] != left.numel()
+            or left.numel() != right.numel()):
+        raise ValueError(f'crf_loss_observed: z {tuple(z.shape)}, y {tuple(y.shape)}, r {tuple(r.shape)}, {left.numel()} / '
+                         f'{right.numel()} pair indices')
+    if (z.dtype != torch.float32 or y.dtype != torch.float32 or r.dtype != torch.float32 or left.dtype != torch.int32
+            or right.dtype != torch.int32):
+        raise TypeError('crf_loss_observed: z, y, r float32; left, right int32')
+    if not all(t.is_contiguous() for t in (z, y, r, left, right)):
+        raise ValueError('crf_loss_observed: contiguous tensors only')
+    if any(t.device != z.device for t in (y, r, left, right)):
+        raise ValueError('crf_loss_observed: all tensors on one device')
+    per = torch.empty((n,), dtype=torch.float32, device=z.device)
+    mean = torch.empty((1,), dtype=torch.float32, device=z.device)
+    dz = torch.empty((n, nsp), dtype=torch.float32, device=z.device)
+    dr = torch.empty_like(r) if pair_grad else None
+    nobs = torch.empty((n,), dtype=torch.int32, device=z.device)
+    status = torch.empty((n,), dtype=torch.int32, device=z.device)
+    check(_lib.load().a3dv_crf_loss_observed(n, nsp, _ptr(z), _ptr(y), _ptr(r), _ptr(left), _ptr(right), left.numel(),
+                                             _ptr(per), _ptr(mean), _ptr(dz), _ptr(dr) if pair_grad else None, _ptr(nobs),
+                                             _ptr(status), _stream()), 'a3dv_crf_loss_observed')
+    return mean, per, dz, dr, nobs, status
+
+
 def dropout_keep_mask(keep, seed, step, rate=0.5):
     """Fill the uint8 tensor `keep` with the Bernoulli(1-rate) keep mask of training step `step`."""
     check(_lib.load().a3d_dropout_keep_mask(keep.numel(), seed, step, rate, _ptr(keep), _stream()),

@@ -3,7 +3,10 @@ Times the forward (resize -> patches -> 5 conv / 3 pool / 3 dense), the unary ba
 whole `models.dcnf` train step (+ pairwise part, CRF loss, gradient descent).  --train-pairwise: the step that also
 learns the pairwise dense layer (NON-REFERENCE); `crf_loss_ms` is the loss launch alone in the form the step uses.
 --pairwise-texture: the pairwise part with the LBP texture similarity as a third feature (NON-REFERENCE).
-    python tools/bench_dcnf.py [batch] [--train-pairwise] [--pairwise-texture] > dcnf.json"""
+--holes: the step on depth maps with holes (NON-REFERENCE, DCNFReplica(valid_range=(0, 0.99))): the synthetic depth gets a
+band at the range cap over its upper third and scattered zeros, so that whole superpixels, and some in part, are not
+targets; `crf_loss_ms` is then ops.crf_loss_observed.
+    python tools/bench_dcnf.py [batch] [--train-pairwise] [--pairwise-texture] [--holes] > dcnf.json"""
 import json
 import os
 import sys
@@ -16,17 +19,27 @@ from ann3depth_amd import models, ops  # noqa: E402
 
 PAIRWISE = '--train-pairwise' in sys.argv[1:]
 TEXTURE = '--pairwise-texture' in sys.argv[1:]
-argv = [a for a in sys.argv[1:] if a not in ('--train-pairwise', '--pairwise-texture')]
+HOLES = '--holes' in sys.argv[1:]
+argv = [a for a in sys.argv[1:] if a not in ('--train-pairwise', '--pairwise-texture', '--holes')]
 B = int(argv[0]) if argv else 16
 rng = np.random.default_rng(1000)
 img = torch.from_numpy((rng.integers(0, 256, (B, 480, 640, 3)) / 255).astype(np.float32)).cuda()
-dep = torch.from_numpy(rng.random((B, 55, 74, 1)).astype(np.float32)).cuda()
-if TEXTURE:
+dep = rng.random((B, 55, 74, 1)).astype(np.float32)
+if HOLES:
+    dep = 0.05 + 0.9 * dep
+    dep[:, :22] = 1.0                                         # the range cap: two rows of superpixels and part of a third
+    dep[rng.random(dep.shape) < 0.08] = 0.0                   # no return
+dep = torch.from_numpy(dep).cuda()
+if HOLES:
+    rep = models.DCNFReplica(B, train_pairwise=PAIRWISE, pairwise_texture=TEXTURE, valid_range=(0.0, 0.99))
+elif TEXTURE:
     rep = models.DCNFReplica(B, train_pairwise=PAIRWISE, pairwise_texture=True)
 else:
     rep = models.DCNFReplica(B, train_pairwise=True) if PAIRWISE else models.DCNFReplica(B)
 net = rep.unary
 dz = torch.randn((net.P, 1), device='cuda')
+# the objective of the untouched network, before the timed steps move it (at the reference's rate 0.1 they move it far)
+first_loss = float(rep.forward(img, dep)) if HOLES else None
 
 
 def timeit(fn, reps=10):
@@ -46,13 +59,22 @@ t_bwd = timeit(lambda: net.backward(dz))
 t_step = timeit(lambda: rep.step(img, dep))
 t_crf = timeit(lambda: rep.forward_crf(dep))
 loss_args = (net.z.view(B, rep.nsp), rep.y.view(B, rep.nsp), rep.r, rep.left, rep.right, models.DCNF_EPSILON)
-t_loss = timeit(lambda: (ops.crf_loss_grad if PAIRWISE else ops.crf_loss)(*loss_args), reps=50)
+if HOLES:
+    t_loss = timeit(lambda: ops.crf_loss_observed(*loss_args[:5], pair_grad=PAIRWISE), reps=50)
+else:
+    t_loss = timeit(lambda: (ops.crf_loss_grad if PAIRWISE else ops.crf_loss)(*loss_args), reps=50)
 gflop_patch = 2.672          # forward GFLOP per patch
 fwd_tf = gflop_patch * net.P / t_fwd           # GFLOP / ms = TFLOP/s
+extra = {}
+if HOLES:
+    torch.cuda.synchronize()
+    nobs = rep.nobs.cpu().numpy()
+    extra = {'holes': True, 'observed_fraction': round(float(nobs.sum()) / (B * rep.nsp), 4),
+             'observed_superpixels_min_max': [int(nobs.min()), int(nobs.max())], 'loss_before_the_steps': round(first_loss, 4)}
 print(json.dumps({'workload': f'DCNF unary, batch {B} -> {net.P} patches 100x100x3', 'forward_ms': round(t_fwd, 3),
                   'forward_images_per_s': round(B / t_fwd * 1e3, 1), 'forward_tflops': round(fwd_tf, 1),
                   'backward_ms': round(t_bwd, 3), 'dtype': 'f32',
                   'train_step_ms': round(t_step, 3), 'train_step_images_per_s': round(B / t_step * 1e3, 1),
                   'pairwise_and_crf_loss_ms': round(t_crf, 3), 'crf_loss_ms': round(t_loss, 4), 'train_pairwise': PAIRWISE,
                   'pairwise_texture': TEXTURE,
-                  'fwd_bwd_images_per_s': round(B / (t_fwd + t_bwd) * 1e3, 1)}))
+                  'fwd_bwd_images_per_s': round(B / (t_fwd + t_bwd) * 1e3, 1), **extra}))
