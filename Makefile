@@ -70,7 +70,8 @@ endif
 
 # flags that are not the reference's go through TRAIN_ARGS, e.g. TRAIN_ARGS="--beta2 0.999 --augment eigen", or for depth
 # maps with holes (raw Kinect frames, Make3D) TRAIN_ARGS="--min-depth 0 --max-depth 0.99", or for MODEL=dcnf
-# TRAIN_ARGS="--train-pairwise --pairwise-texture" (the pairwise weights learn, over three similarities)
+# TRAIN_ARGS="--train-pairwise --pairwise-texture" (the pairwise weights learn, over three similarities) or
+# TRAIN_ARGS="--unary fcsp" (the unary convs once over the whole image, superpixel pooling before the dense head)
 TRAIN_ARGS ?=
 .PHONY: train
 train: ${DATA_DIR}

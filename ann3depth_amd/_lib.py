@@ -166,6 +166,12 @@ CRF_VALID_SIGNATURES = {
     'a3dv_crf_loss_observed': (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_fcsp.h declares (NON-REFERENCE extension, prefix a3df_)
+FCSP_SIGNATURES = {
+    'a3df_superpixel_pool_fwd': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P]),
+    'a3df_superpixel_pool_bwd': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P]),
+}
+
 _lib = None
 
 
@@ -183,7 +189,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(PAIR_SIGNATURES.items())
                               + list(TEXTURE_SIGNATURES.items()) + list(GRADLOSS_SIGNATURES.items())
-                              + list(CRF_VALID_SIGNATURES.items())):
+                              + list(CRF_VALID_SIGNATURES.items()) + list(FCSP_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

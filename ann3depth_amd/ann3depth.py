@@ -8,6 +8,11 @@ checkpoint saver/restorer, TraceHook).  The parameter-server path (`--job-name p
 replaced by synchronous RCCL data parallelism: launch one process per GPU with
 ``python -m torch.distributed.run --nproc-per-node N -m ann3depth_amd.ann3depth ...``; the old cluster flags are
 accepted and ignored.
+
+Flags that are not the reference's: --beta2, --precision, --augment, --min-depth / --max-depth, --loss-gradient,
+--train-pairwise, --pairwise-texture, --unary {patch,fcsp} (dcnf: the unary part over 48 patches per image, the
+reference's, or once over the whole image with superpixel pooling before the dense head), --seed, --tf-checkpoints,
+--trace-every, --profiler.
 """
 import argparse
 import json
@@ -64,6 +69,10 @@ def main(argv=None):
     if args.pairwise_texture and not hasattr(getattr(models, args.model, None), 'pairwise_texture'):
         logger.error(f'--pairwise-texture adds the texture similarity to the pairwise part of the CRF of --model dcnf '
                      f'(Liu et al. 2015): {args.model or "(no model)"} has no such part.')
+        return 2
+    if args.unary != 'patch' and not hasattr(getattr(models, args.model, None), 'unary'):
+        logger.error(f'--unary {args.unary} chooses the form of the unary part of --model dcnf (Liu et al. 2015, DCNF-FCSP): '
+                     f'{args.model or "(no model)"} has no such part.')
         return 2
     if args.loss_gradient is not None and args.model != 'msdn':
         logger.error(f'--loss-gradient weighs the gradient-matching term of Eigen & Fergus 2015 in the two losses of --model '
@@ -141,6 +150,8 @@ def setup_model(args, rank=0, world=1):
         model.train_pairwise = bool(args.train_pairwise)
     if hasattr(model, 'pairwise_texture'):
         model.pairwise_texture = bool(args.pairwise_texture)
+    if hasattr(model, 'unary'):
+        model.unary = args.unary
     inputs, targets = data.inputs(args.datadir, args.dataset, args.batchsize, rank=rank, world=world,
                                   seed=args.seed + rank)
     return model(inputs, targets)
@@ -193,7 +204,7 @@ class Session:
                 else:
                     rep.load_state_dict(torch.load(latest, map_location=rep.device))
             except ValueError:                                # refused (dcnf: a [2,1] / [3,1] pairwise kernel across
-                self.op.pipeline.close()                      # --pairwise-texture): __exit__ will not run
+                self.op.pipeline.close()                      # --pairwise-texture, a dense/kernel across --unary): no __exit__
                 raise
         if self.world > 1:                                    # non-chief replicas take the chief's state
             import torch.distributed as dist
@@ -367,7 +378,7 @@ def latest_checkpoint(ckptdir):
 
 def parse_args(argv=None):
     """The reference's flags verbatim (src/ann3depth.py:221-254), plus --beta2 / --augment / --min-depth / --max-depth / --loss-gradient /
-    --train-pairwise / --pairwise-texture / --seed / --trace-every / --profiler."""
+    --train-pairwise / --pairwise-texture / --unary / --seed / --trace-every / --profiler."""
     parser = argparse.ArgumentParser()
     parser.add_argument('dataset', default='nyu', type=str, help='The dataset to use.')
     parser.add_argument('--model', '-m', default='', type=str, help='Enter a model name.')
@@ -413,6 +424,11 @@ def parse_args(argv=None):
                              'local-binary-pattern histograms of the superpixels (Liu et al. 2015); the pairwise kernel is '
                              '[3,1], and a checkpoint with a [2,1] kernel is refused. Meant to go with --train-pairwise: '
                              'without it the layer keeps its initial draw, as the reference\'s does.')
+    parser.add_argument('--unary', default='patch', choices=['patch', 'fcsp'],
+                        help='NON-REFERENCE unless patch: the form of the unary part (dcnf only). patch: the reference\'s, the '
+                             'conv stack over 48 overlapping 100 x 100 patches per image. fcsp: the convs once over the whole '
+                             'image, the last feature map averaged inside every superpixel, then the dense head (Liu et al. '
+                             '2015, DCNF-FCSP); dense/kernel is [256,128], and a checkpoint of the other form is refused.')
     parser.add_argument('--seed', default=0, type=int, help='Shuffle-queue seed.')
     parser.add_argument('--tf-checkpoints', action='store_true',
                         help='Also write every checkpoint as a TensorFlow V2 bundle (model.ckpt-N.index/.data-*).')

@@ -244,12 +244,12 @@ def main(argv=None):
         return 2
     if not torch.cuda.is_available():
         raise RuntimeError('ann3depth_amd needs an MI355X: evaluation has no CPU fallback')
-    from .models import DCNF_PAIR_PREFIX, DCNFReplica, MSDNReplica
+    from .models import DCNF_PAIR_PREFIX, DCNF_PREFIX, DCNFReplica, MSDNReplica
     dev = torch.device('cuda', torch.cuda.current_device())
     _say(f'restoring {ckpt}')
     bundle = tfckpt.is_bundle(ckpt)                  # as ann3depth.Session.__enter__ restores
     state = tfckpt.read_bundle(ckpt) if bundle else torch.load(ckpt, map_location=dev)
-    texture = False
+    texture, unary = False, 'patch'
     if args.model == 'dcnf':
         # the checkpoint says how many similarities its pairwise layer weighs: 2, or 3 with --pairwise-texture
         name = DCNF_PAIR_PREFIX + 'kernel'
@@ -260,7 +260,10 @@ def main(argv=None):
             inputs.pipeline.close()
             return 2
         texture = shape == (3, 1)
-        replica = DCNFReplica(args.batchsize, device=dev, precision=args.precision, pairwise_texture=texture)
+        # ... and which form its unary part has: dense/kernel is [256, 128] with --unary fcsp, [12544, 128] without
+        dense = DCNF_PREFIX + 'dense/kernel'
+        unary = 'fcsp' if dense in state and tuple(np.shape(state[dense])) == (256, 128) else 'patch'
+        replica = DCNFReplica(args.batchsize, device=dev, precision=args.precision, pairwise_texture=texture, unary=unary)
     else:
         replica = MSDNReplica(args.batchsize, device=dev, precision=args.precision, keep_dense_grads=False)
     if bundle:
@@ -290,6 +293,8 @@ def main(argv=None):
            **res}
     if texture:
         out['pairwise_texture'] = True
+    if unary != 'patch':
+        out['unary_form'] = unary          # ('unary' holds the metrics of the unary output)
     if args.predictions:
         np.save(args.predictions, torch.cat(ev.predictions).cpu().numpy() if ev.predictions else
                 np.zeros((0,) + ev.prediction_shape, np.float32))

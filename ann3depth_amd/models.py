@@ -1161,7 +1161,11 @@ class DCNFUnary:
         """The stack over self.resized as it stands.  record_argmax=False (DCNFReplica.predict): the fused conv + pool
         does not write the pool positions, which only a backward reads."""
         ops.extract_patches(self.resized, DCNF_PATCH, DCNF_SP, self.act['x'])   # :50-59
-        t = self.act['x']
+        t = self._forward_convs(self.act['x'], record_argmax)
+        self._forward_denses(t.view(self.P, -1))
+        return self.z.view(self.B, self.rows * self.cols, 1)
+
+    def _forward_convs(self, t, record_argmax):
         for n, _, _, _ in DCNF_CONVS:
             if self.fuse_pool and n in DCNF_POOL_AFTER:
                 t = ops.conv2d_pool_fwd(self.desc[n], t, self.var(n + '/kernel'), self.var(n + '/bias'),
@@ -1172,11 +1176,12 @@ class DCNFUnary:
             if n in DCNF_POOL_AFTER:
                 ops.maxpool2x2_fwd(t, self.act[n + '/pool'])
                 t = self.act[n + '/pool']
-        t = t.view(self.P, -1)
+        return t
+
+    def _forward_denses(self, t):
         for n, _, _, act in DCNF_DENSES:
             ops.dense_fwd(t, self.var(n + '/kernel'), self.var(n + '/bias'), self.act[n], act)
             t = self.act[n]
-        return self.z.view(self.B, self.rows * self.cols, 1)
 
     def activations(self):
         """name -> numpy array of every activation; a pre-pool activation that the fused conv + pool never wrote comes
@@ -1184,15 +1189,20 @@ class DCNFUnary:
         out = {k: v.cpu().numpy() for k, v in self.act.items()}
         for n, arg in self.argmax.items():
             pooled = self.act[n + '/pool']
-            hw, c = self.conv_hw[n], pooled.shape[-1]
-            full = torch.zeros((self.P, hw, hw, c), device=self.device)
-            ph = pooled.shape[1]
-            win = full[:, :2 * ph, :2 * ph, :].reshape(self.P, ph, 2, ph, 2, c)
+            (hh, ww), c = self._conv_hw(n), pooled.shape[-1]
+            N, ph, pw = pooled.shape[:3]
+            full = torch.zeros((N, hh, ww, c), device=self.device)
+            win = full[:, :2 * ph, :2 * pw, :].reshape(N, ph, 2, pw, 2, c)
             a = arg.long()
             for pos in range(4):
                 win[:, :, pos >> 1, :, pos & 1, :] = torch.where(a == pos, pooled, torch.zeros_like(pooled))
             out[n] = full.cpu().numpy()
         return out
+
+    def _conv_hw(self, n):
+        """(height, width) of conv n's output."""
+        hw = self.conv_hw[n]
+        return hw if isinstance(hw, tuple) else (hw, hw)
 
     def _dbuf(self, key, like):
         if key not in self.dact:
@@ -1204,6 +1214,16 @@ class DCNFUnary:
         P = self.P
         a = self.act
         flat = a['conv2d_4/pool'].view(P, -1)
+        d0 = self._backward_denses(flat, dz)
+        dflat = self._dbuf('flat', a['conv2d_4/pool'])
+        ops.dense_bwd_data(d0, self.var('dense/kernel'), dflat.view(P, -1))
+        self._backward_convs(dflat)
+
+    def _backward_denses(self, flat, dz):
+        """The three dense layers' gradients from dz, flat [P, in] being the first one's input; returns the gradient of
+        the first layer's pre-activation, which the caller takes on to flat's own gradient."""
+        P = self.P
+        a = self.act
         d2 = dz.reshape(P, 1).contiguous()
         # dense_2 (linear)
         ops.dense_bwd_filter(a['dense_1'], d2, self.grad('dense_2/kernel'), self.grad('dense_2/bias'))
@@ -1213,9 +1233,12 @@ class DCNFUnary:
         d0 = self._dbuf('dense', a['dense'])
         ops.dense_bwd_data(d1, self.var('dense_1/kernel'), d0, mask=a['dense'], scale=1.0)     # ReluGrad fused
         ops.dense_bwd_filter(flat, d0, self.grad('dense/kernel'), self.grad('dense/bias'))
-        dflat = self._dbuf('flat', a['conv2d_4/pool'])
-        ops.dense_bwd_data(d0, self.var('dense/kernel'), dflat.view(P, -1))
-        d = dflat
+        return d0
+
+    def _backward_convs(self, d):
+        """The five convs' gradients from d, the gradient of conv2d_4/pool."""
+        a = self.act
+        N = a['x'].shape[0]
         inputs = {'conv2d': 'x', 'conv2d_1': 'conv2d/pool', 'conv2d_2': 'conv2d_1/pool', 'conv2d_3': 'conv2d_2',
                   'conv2d_4': 'conv2d_3'}
         for n, _, _, _ in reversed(DCNF_CONVS):
@@ -1227,9 +1250,9 @@ class DCNFUnary:
                                              self.grad(n + '/kernel'), self.grad(n + '/bias'))
                 continue
             if n in DCNF_POOL_AFTER and self.fuse_pool:
-                hw, co = self.conv_hw[n], a[n + '/pool'].shape[-1]
+                (hh, ww), co = self._conv_hw(n), a[n + '/pool'].shape[-1]
                 if n not in self.dact:
-                    self.dact[n] = torch.empty((P, hw, hw, co), device=self.device)
+                    self.dact[n] = torch.empty((N, hh, ww, co), device=self.device)
                 dzc = self.dact[n]
                 ops.maxpool2x2_bwd_idx(self.argmax[n], a[n + '/pool'], d.view(a[n + '/pool'].shape), dzc, relu_mask=True)
             elif n in DCNF_POOL_AFTER:
@@ -1245,6 +1268,150 @@ class DCNFUnary:
                 ops.conv2d_bwd_data(self.desc[n], dzc, self.var(n + '/kernel'), dx,
                                     relu_mask=x if prev_is_plain_relu else None)
                 d = dx
+
+
+def fcsp_receptive():
+    """(c0, jump) of the last pooled map of the unary conv stack over a whole image, in pixel indices: cell i sees the
+    image through a window centred on c0 + i * jump.  Walked from DCNF_CONVS / DCNF_POOL_AFTER (VALID, stride 1; 2x2
+    pools): a k x k conv moves the first centre by (k - 1) / 2 cells of its input, a pool by half a cell and doubles the
+    jump.  Returned as (twice c0, jump), both integers: (49, 8) for the reference's stack, c0 = 24.5."""
+    c0x2, jump = 0, 1
+    for n, _, _, k in DCNF_CONVS:
+        c0x2 += (k - 1) * jump
+        if n in DCNF_POOL_AFTER:
+            c0x2 += jump
+            jump *= 2
+    return c0x2, jump
+
+
+def fcsp_maps(H, W, h, w, align='centre'):
+    """The pixel-to-cell tables of superpixel pooling (ops.FcspMap): (ymap [H], xmap [W]) int32.
+    'centre': a pixel belongs to the cell whose receptive-field centre is nearest,
+    clamp(floor((2 y - 2 c0 + jump) / (2 jump)), 0, h - 1) in integers (fcsp_receptive); the model's choice.
+    'nearest': min(y * h // H, h - 1), nearest-neighbour upsampling of the map to the image, the paper's; for a padded
+    network the two coincide, for the reference's VALID convs 'nearest' is off by whole cells."""
+    if align == 'centre':
+        c0x2, jump = fcsp_receptive()
+
+        def table(size, cells):
+            y = np.arange(size, dtype=np.int64)
+            return np.clip((2 * y - c0x2 + jump) // (2 * jump), 0, cells - 1).astype(np.int32)
+    elif align == 'nearest':
+        def table(size, cells):
+            y = np.arange(size, dtype=np.int64)
+            return np.minimum(y * cells // size, cells - 1).astype(np.int32)
+    else:
+        raise ValueError(f"fcsp_maps: align {align!r} is neither 'centre' nor 'nearest'")
+    if min(H, W, h, w) <= 0:
+        raise ValueError(f'fcsp_maps: image {H} x {W}, map {h} x {w}')
+    return table(H, h), table(W, w)
+
+
+class DCNFUnaryFCSP(DCNFUnary):
+    """NON-REFERENCE (--unary fcsp): the unary part as Liu et al. 2015 build it in DCNF-FCSP.  The reference's five convs
+    (the same names, shapes, VALID padding, ReLU and pools) run ONCE over the whole resized image instead of over 48
+    overlapping patches; the last pooled map ([B,24,34,256] at 240x320) is averaged inside every superpixel
+    (ops.superpixel_pool_fwd, include/a3d_fcsp.h: each pixel belongs to the cell whose receptive-field centre is nearest,
+    fcsp_maps) and the [B * S, 256] rows go through the reference's three dense layers.  Only dense/kernel changes shape,
+    [256,128] for [12544,128]; the parameters come from the same stream in the same order, so at equal seed the conv
+    kernels are DCNFUnary's bits.  Offers what DCNFReplica uses of DCNFUnary; P is the number of dense rows, B * S.
+    image_hw, sp, fuse_pool: for tests (DCNFReplica runs at 240x320, 40, fused)."""
+
+    def __init__(self, batchsize, device='cuda', params=None, seed=3000, precision='fp32',
+                 image_hw=(DCNF_IMG_H, DCNF_IMG_W), sp=DCNF_SP, fuse_pool=None):
+        H, W = (int(v) for v in image_hw)
+        sp = int(sp)
+        if sp <= 0 or H <= 0 or W <= 0 or H % sp or W % sp:
+            raise ValueError(f'DCNFUnaryFCSP: image {H} x {W} is not cut into superpixels of edge {sp}')
+        self.B = batchsize
+        self.device = dev = torch.device(device)
+        self.H, self.W, self.sp = H, W, sp
+        self.rows, self.cols = H // sp, W // sp
+        self.S = S = self.rows * self.cols
+        self.P = P = batchsize * S
+        shapes = collections.OrderedDict()
+        for n, ci, co, k in DCNF_CONVS:
+            shapes[DCNF_PREFIX + n + '/kernel'] = (k, k, ci, co)
+            shapes[DCNF_PREFIX + n + '/bias'] = (co,)
+        feat = DCNF_CONVS[-1][2]
+        for n, i, o, _ in DCNF_DENSES:
+            shapes[DCNF_PREFIX + n + '/kernel'] = (feat if n == 'dense' else i, o)
+            shapes[DCNF_PREFIX + n + '/bias'] = (o,)
+        self.shapes = shapes
+        self.group = ParamGroup('unary', 0.1, shapes, dev, slots=False)    # GradientDescentOptimizer(0.1), src/models.py:198
+        if params is None:
+            rng = np.random.default_rng(seed)
+            params = {n: (glorot_uniform(rng, s) if n.endswith('/kernel') else np.zeros(s, np.float32))
+                      for n, s in shapes.items()}
+        for n, s in shapes.items():
+            if tuple(np.shape(params[n])) != tuple(s):
+                raise ValueError(f'DCNFUnaryFCSP: {n} has shape {list(np.shape(params[n]))}, this form\'s is {list(s)}')
+            self.group.view(self.group.var, n).copy_(torch.from_numpy(np.ascontiguousarray(params[n], np.float32)))
+
+        def buf(*shape):
+            return torch.empty(shape, device=dev)
+        self.resized = buf(batchsize, H, W, 3)
+        self.act = collections.OrderedDict()
+        self.dact = {}
+        self.desc = {}
+        # as DCNFUnary: conv + ReLU + max pool in one kernel (fp32); fuse_pool=False keeps the pre-pool maps, for tests
+        self.fuse_pool = precision == 'fp32' if fuse_pool is None else bool(fuse_pool) and precision == 'fp32'
+        self.argmax, self.conv_hw = {}, {}
+        self.act['x'] = self.resized
+        h, w = H, W
+        for n, ci, co, k in DCNF_CONVS:
+            if h < k or w < k:
+                raise ValueError(f'DCNFUnaryFCSP: image {H} x {W} is too small for {n}')
+            self.desc[n] = ops.conv_desc(batchsize, h, w, ci, co, k, k, 1, 'VALID', precision=precision)
+            h, w = h - k + 1, w - k + 1
+            self.conv_hw[n] = (h, w)
+            if not (self.fuse_pool and n in DCNF_POOL_AFTER):
+                self.act[n] = buf(batchsize, h, w, co)
+            if n in DCNF_POOL_AFTER:
+                h, w = h // 2, w // 2                     # an odd last row / column is dropped, as the pool's ABI states
+                if h == 0 or w == 0:
+                    raise ValueError(f'DCNFUnaryFCSP: image {H} x {W} is too small for {n}\'s pool')
+                self.act[n + '/pool'] = buf(batchsize, h, w, co)
+                if self.fuse_pool:
+                    self.argmax[n] = torch.empty((batchsize, h, w, co), dtype=torch.uint8, device=dev)
+        self.map_hw = (h, w)
+        self.map = ops.FcspMap(*fcsp_maps(H, W, h, w, 'centre'), h, w, sp, device=dev)
+        self.act['pooled'] = buf(P, feat)
+        for n, i, o, _ in DCNF_DENSES:
+            self.act[n] = buf(P, o)
+        self.z = self.act['dense_2']
+        self.few_pooled = (self.fuse_pool and dev.type == 'cuda'
+                           and ops.conv2d_bwd_filter_pooled_supported(self.desc['conv2d']))
+
+    def forward_resized(self, record_argmax=True):
+        """The stack over self.resized as it stands (see DCNFUnary.forward_resized)."""
+        t = self._forward_convs(self.resized, record_argmax)
+        ops.superpixel_pool_fwd(t, self.map, self.act['pooled'].view(self.B, self.S, -1))
+        self._forward_denses(self.act['pooled'])
+        return self.z.view(self.B, self.S, 1)
+
+    def backward(self, dz):
+        """Gradients of sum(z * dz) wrt every unary variable, into the flat gradient buffer."""
+        a = self.act
+        d0 = self._backward_denses(a['pooled'], dz)
+        dpooled = self._dbuf('pooled', a['pooled'])
+        ops.dense_bwd_data(d0, self.var('dense/kernel'), dpooled)
+        dflat = self._dbuf('flat', a['conv2d_4/pool'])
+        ops.superpixel_pool_bwd(dpooled.view(self.B, self.S, -1), self.map, dflat)     # writes every element
+        self._backward_convs(dflat)
+
+    def load_convs_from(self, state):
+        """Warm start from a checkpoint of the patch form (or of this one): copies the five convs' kernels and biases
+        from a name -> tensor / array mapping and leaves the dense head as it is.  Returns the names copied."""
+        names = [DCNF_PREFIX + n + suffix for n, _, _, _ in DCNF_CONVS for suffix in ('/kernel', '/bias')]
+        for n in names:
+            if n not in state or tuple(np.shape(state[n])) != tuple(self.shapes[n]):
+                raise ValueError(f'load_convs_from: {n} is missing or not of shape {list(self.shapes[n])}')
+        for n in names:
+            v = state[n]
+            v = v.detach() if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v, np.float32))
+            self.group.view(self.group.var, n).copy_(v)
+        return names
 
 
 DCNF_GAMMA, DCNF_EPSILON = 1.0, 1e-7    # src/models.py:17-18
@@ -1293,11 +1460,21 @@ class DCNFReplica:
     reference's loss without its three).  Its dz goes into the unary backward, its dr, under train_pairwise, into the
     pairwise layer's.  min_valid: a superpixel is a target only if at least ceil(min_valid * 40 * 40) of its pixels were
     measured.  The default, 0.5, is a choice, not a derivation: a mean over the measured minority of a block that is
-    mostly sky or shadow describes its edge, not the superpixel.  None (the default): no launch, buffer or bit differs."""
+    mostly sky or shadow describes its edge, not the superpixel.  None (the default): no launch, buffer or bit differs.
+
+    unary (NON-REFERENCE, --unary fcsp): 'fcsp' takes z from DCNFUnaryFCSP, the convs once over the whole image and
+    superpixel pooling before the dense head (Liu et al. 2015, DCNF-FCSP), in place of the 48 patches per image.  The rest
+    of the step reads only z and the resized image and is the same code.  dense/kernel is [256,128] in that form and
+    [12544,128] in the other; a restore across the two is refused.  'patch' (the default): no launch, buffer or bit
+    differs."""
     uses_dropout = False
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, global_step=0, reducer=None,
-                 precision='fp32', train_pairwise=False, pairwise_texture=False, valid_range=None, min_valid=0.5):
+                 precision='fp32', train_pairwise=False, pairwise_texture=False, valid_range=None, min_valid=0.5,
+                 unary='patch'):
+        if unary not in ('patch', 'fcsp'):
+            raise ValueError(f"unary {unary!r}: 'patch' or 'fcsp'")
+        self.unary_form = unary
         if valid_range is not None:
             lo, hi = (float(v) for v in valid_range)
             if not lo <= hi:
@@ -1315,7 +1492,10 @@ class DCNFReplica:
         self.pairwise_texture = bool(pairwise_texture)
         self.nsims = 3 if self.pairwise_texture else 2
         self.global_step = global_step
-        self.unary = DCNFUnary(batchsize, dev, params=params, seed=seed, precision=precision)
+        if params is not None:
+            self._check_unary_kernel(np.shape(params[DCNF_PREFIX + 'dense/kernel']), 'params')
+        self.unary = (DCNFUnaryFCSP if unary == 'fcsp' else DCNFUnary)(batchsize, dev, params=params, seed=seed,
+                                                                       precision=precision)
         self.rows, self.cols = DCNF_IMG_H // DCNF_SP, DCNF_IMG_W // DCNF_SP
         assert (self.rows, self.cols) == (self.unary.rows, self.unary.cols)
         self.nsp = self.rows * self.cols
@@ -1359,6 +1539,13 @@ class DCNFReplica:
         if tuple(shape) != want:
             raise ValueError(f'{what}: {DCNF_PAIR_PREFIX}kernel has shape {list(shape)}, this replica\'s is {list(want)} '
                              f'(pairwise_texture={self.pairwise_texture}: [3, 1] with --pairwise-texture, [2, 1] without)')
+
+    def _check_unary_kernel(self, shape, what):
+        """The unary dense/kernel about to be restored is of this replica's form, or ValueError."""
+        want = (DCNF_CONVS[-1][2] if self.unary_form == 'fcsp' else DCNF_DENSES[0][1], DCNF_DENSES[0][2])
+        if tuple(shape) != want:
+            raise ValueError(f'{what}: {DCNF_PREFIX}dense/kernel has shape {list(shape)}, this replica\'s is {list(want)} '
+                             f'(unary={self.unary_form!r}: [256, 128] with --unary fcsp, [12544, 128] with --unary patch)')
 
     def _pairwise(self):
         """The similarities of every pair and the pair weights r from the resized images (src/models.py:112-127)."""
@@ -1500,6 +1687,7 @@ class DCNFReplica:
 
     def load_state_dict(self, sd):
         self._check_pair_kernel(sd[DCNF_PAIR_PREFIX + 'kernel'].shape, 'load_state_dict')
+        self._check_unary_kernel(sd[DCNF_PREFIX + 'dense/kernel'].shape, 'load_state_dict')
         for g in self.groups.values():
             for n in g.offsets:
                 g.view(g.var, n).copy_(sd[n])
@@ -1509,6 +1697,7 @@ class DCNFReplica:
         """Restore from a TensorFlow checkpoint's whole tensors (the reference's dcnf partitions its variables, which
         tfckpt.read_bundle refuses; a bundle written by this build loads)."""
         self._check_pair_kernel(np.shape(tensors[DCNF_PAIR_PREFIX + 'kernel']), 'load_tf_variables')
+        self._check_unary_kernel(np.shape(tensors[DCNF_PREFIX + 'dense/kernel']), 'load_tf_variables')
         for g in self.groups.values():
             for n in g.offsets:
                 g.view(g.var, n).copy_(torch.from_numpy(np.ascontiguousarray(tensors[n], np.float32)))
@@ -1691,6 +1880,7 @@ class _DistributedConvolutionalNeuralFields:
     pairwise_texture = False  # NON-REFERENCE, --pairwise-texture: LBP texture disparity as a third similarity (see DCNFReplica)
     valid_range = None   # NON-REFERENCE, --min-depth / --max-depth: (min, max), the depth maps have holes (see DCNFReplica)
     min_valid = 0.5      # the share of a superpixel that must be measured for it to be a target (see DCNFReplica)
+    unary = 'patch'      # NON-REFERENCE, --unary fcsp: convs once over the image + superpixel pooling (see DCNFReplica)
 
     def __call__(self, images, depths, train=True):
         assert images.pipeline is depths.pipeline, 'inputs and targets must come from the same data.inputs() call'
@@ -1698,7 +1888,7 @@ class _DistributedConvolutionalNeuralFields:
         replica = DCNFReplica(images.pipeline.B, device=torch.device('cuda', torch.cuda.current_device()),
                               seed=self.seed, reducer=self.reducer, precision=self.precision,
                               train_pairwise=self.train_pairwise and train, pairwise_texture=self.pairwise_texture,
-                              valid_range=self.valid_range, min_valid=self.min_valid)
+                              valid_range=self.valid_range, min_valid=self.min_valid, unary=self.unary)
         if self.reducer is not None:
             for g in replica.groups.values():
                 self.reducer.broadcast(g.var)

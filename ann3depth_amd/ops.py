@@ -929,6 +929,87 @@ def crf_loss_observed(z, y, r, left, right, pair_grad=True):
     return mean, per, dz, dr, nobs, status
 
 
+FCSP_MAX_SP = 64         # A3DF_MAX_SP: one lane of a wave per window pixel, 2 KiB of LDS for a block's counts
+
+
+class FcspMap:
+    """NON-REFERENCE (include/a3d_fcsp.h): the validated pixel-to-cell tables of superpixel pooling on the device.  ymap [H],
+    xmap [W] (host integer sequences): image row y belongs to feature row ymap[y] of a [h, w] map, column x to xmap[x];
+    superpixels of edge sp.  Holds ymap, xmap (int32 device tensors) and H, W, h, w, sp.  ValueError for tables of the wrong
+    length (H, W positive multiples of sp, 0 < sp <= 64), out of range, or decreasing."""
+
+    def __init__(self, ymap, xmap, h, w, sp, device='cuda', H=None, W=None):
+        import numpy as np
+        ya, xa = np.asarray(ymap), np.asarray(xmap)
+        h, w, sp = int(h), int(w), int(sp)
+        if not 0 < sp <= FCSP_MAX_SP or h <= 0 or w <= 0:
+            raise ValueError(f'FcspMap: h {h}, w {w}, sp {sp}: a positive map and a superpixel edge in 1 .. {FCSP_MAX_SP}')
+        for name, a, want in (('ymap', ya, H), ('xmap', xa, W)):
+            if a.ndim != 1 or a.size == 0 or a.size % sp or a.dtype.kind not in 'iu' or (want is not None and a.size != want):
+                raise ValueError(f'FcspMap: {name} of shape {a.shape}, {a.dtype} is not one integer per image '
+                                 f'{"row" if name == "ymap" else "column"}'
+                                 + (f' ({want})' if want is not None else '') + f', a positive multiple of sp = {sp}')
+        for name, a, lim in (('ymap', ya, h), ('xmap', xa, w)):
+            if a.min() < 0 or a.max() >= lim:
+                raise ValueError(f'FcspMap: {name} has entries outside [0, {lim})')
+            if (np.diff(a.astype(np.int64)) < 0).any():
+                raise ValueError(f'FcspMap: {name} decreases')
+        self.H, self.W, self.h, self.w, self.sp = int(ya.size), int(xa.size), h, w, sp
+        self.S = (self.H // sp) * (self.W // sp)
+        self.ymap = torch.from_numpy(np.ascontiguousarray(ya, np.int32)).to(device)
+        self.xmap = torch.from_numpy(np.ascontiguousarray(xa, np.int32)).to(device)
+
+
+def _fcsp_args(who, feat, tables, pooled, channels):
+    """(n, h, w, C, ld, H, W, sp, ymap, xmap, S, ldp) of a pooling call.  feat [n,h,w,ld], pooled [n,S,ldp] or None (then
+    [n,S,C] is the shape to allocate); tables: an FcspMap, or (ymap, xmap, sp) device tables taken as they are."""
+    if isinstance(tables, FcspMap):
+        ymap, xmap, sp = tables.ymap, tables.xmap, tables.sp
+        if feat.dim() == 4 and tuple(feat.shape[1:3]) != (tables.h, tables.w):
+            raise ValueError(f'{who}: a map of {tuple(feat.shape[1:3])} cells, tables made for {(tables.h, tables.w)}')
+    else:
+        ymap, xmap, sp = tables
+    if feat.dim() != 4 or feat.numel() == 0:
+        raise ValueError(f'{who}: feature map {tuple(feat.shape)} is not a non-empty [n, h, w, ld]')
+    n, h, w, ld = feat.shape
+    C = ld if channels is None else int(channels)
+    H, W = ymap.numel(), xmap.numel()
+    if not 0 < sp <= FCSP_MAX_SP or H == 0 or W == 0 or H % sp or W % sp or not 0 < C <= ld:
+        raise ValueError(f'{who}: tables of {H} and {W} entries, sp {sp} (<= {FCSP_MAX_SP}), {C} channels of {ld}')
+    S = (H // sp) * (W // sp)
+    if pooled is not None and (pooled.dim() != 3 or tuple(pooled.shape[:2]) != (n, S) or pooled.shape[2] < C):
+        raise ValueError(f'{who}: pooled {tuple(pooled.shape)} for {n} images, {S} superpixels, {C} channels')
+    ts = [t for t in (feat, pooled) if t is not None]
+    if any(t.dtype != torch.float32 for t in ts) or ymap.dtype != torch.int32 or xmap.dtype != torch.int32:
+        raise TypeError(f'{who}: feature map and pooled rows float32; tables int32')
+    if not all(t.is_contiguous() for t in ts + [ymap, xmap]):
+        raise ValueError(f'{who}: contiguous tensors only')
+    if any(t.device != feat.device for t in ts + [ymap, xmap]):
+        raise ValueError(f'{who}: all tensors on one device')
+    return n, h, w, C, ld, H, W, sp, ymap, xmap, S, (C if pooled is None else pooled.shape[2])
+
+
+def superpixel_pool_fwd(feat, tables, pooled=None, channels=None):
+    """NON-REFERENCE (a3df_superpixel_pool_fwd): the mean of the feature map, upsampled by the tables, over every
+    superpixel: feat [n,h,w,ld] float32 -> pooled [n,S,ldp]; only the first `channels` (default all) of a pixel are read and
+    written.  Cells are summed in ascending (i, j) with integer weights, zero weights skipped, one division by sp * sp."""
+    n, h, w, C, ld, H, W, sp, ymap, xmap, S, ldp = _fcsp_args('superpixel_pool_fwd', feat, tables, pooled, channels)
+    if pooled is None:
+        pooled = torch.empty((n, S, C), dtype=torch.float32, device=feat.device)
+    check(_lib.load().a3df_superpixel_pool_fwd(n, h, w, C, _ptr(feat), ld, H, W, sp, _ptr(ymap), _ptr(xmap), _ptr(pooled),
+                                               ldp, _stream()), 'a3df_superpixel_pool_fwd')
+    return pooled
+
+
+def superpixel_pool_bwd(dpooled, tables, dfeat, channels=None):
+    """NON-REFERENCE (a3df_superpixel_pool_bwd): the transpose, dpooled [n,S,ldp] -> dfeat [n,h,w,ld], a gather; every
+    element of dfeat[..., :channels] is written (+0 where no pixel maps to the cell)."""
+    n, h, w, C, ld, H, W, sp, ymap, xmap, S, ldp = _fcsp_args('superpixel_pool_bwd', dfeat, tables, dpooled, channels)
+    check(_lib.load().a3df_superpixel_pool_bwd(n, h, w, C, _ptr(dpooled), ldp, H, W, sp, _ptr(ymap), _ptr(xmap), _ptr(dfeat),
+                                               ld, _stream()), 'a3df_superpixel_pool_bwd')
+    return dfeat
+
+
 def dropout_keep_mask(keep, seed, step, rate=0.5):
     """Fill the uint8 tensor `keep` with the Bernoulli(1-rate) keep mask of training step `step`."""
     check(_lib.load().a3d_dropout_keep_mask(keep.numel(), seed, step, rate, _ptr(keep), _stream()),

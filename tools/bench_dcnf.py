@@ -6,7 +6,9 @@ learns the pairwise dense layer (NON-REFERENCE); `crf_loss_ms` is the loss launc
 --holes: the step on depth maps with holes (NON-REFERENCE, DCNFReplica(valid_range=(0, 0.99))): the synthetic depth gets a
 band at the range cap over its upper third and scattered zeros, so that whole superpixels, and some in part, are not
 targets; `crf_loss_ms` is then ops.crf_loss_observed.
-    python tools/bench_dcnf.py [batch] [--train-pairwise] [--pairwise-texture] [--holes] > dcnf.json"""
+--unary fcsp: the fully convolutional unary with superpixel pooling (NON-REFERENCE, DCNFReplica(unary='fcsp')): the convs
+once over the 240x320 image; `forward_tflops` then counts that form's own multiply-adds (conv_macs below).
+    python tools/bench_dcnf.py [batch] [--train-pairwise] [--pairwise-texture] [--holes] [--unary fcsp] > dcnf.json"""
 import json
 import os
 import sys
@@ -21,6 +23,11 @@ PAIRWISE = '--train-pairwise' in sys.argv[1:]
 TEXTURE = '--pairwise-texture' in sys.argv[1:]
 HOLES = '--holes' in sys.argv[1:]
 argv = [a for a in sys.argv[1:] if a not in ('--train-pairwise', '--pairwise-texture', '--holes')]
+UNARY = 'patch'
+if '--unary' in argv:
+    i = argv.index('--unary')
+    UNARY = argv[i + 1]
+    del argv[i:i + 2]
 B = int(argv[0]) if argv else 16
 rng = np.random.default_rng(1000)
 img = torch.from_numpy((rng.integers(0, 256, (B, 480, 640, 3)) / 255).astype(np.float32)).cuda()
@@ -30,7 +37,24 @@ if HOLES:
     dep[:, :22] = 1.0                                         # the range cap: two rows of superpixels and part of a third
     dep[rng.random(dep.shape) < 0.08] = 0.0                   # no return
 dep = torch.from_numpy(dep).cuda()
-if HOLES:
+
+
+def conv_macs(h, w, rows):
+    """Multiply-adds of the unary stack on one h x w input (VALID convs, 2x2 pools) with `rows` dense rows behind it."""
+    total = 0
+    for n, ci, co, k in models.DCNF_CONVS:
+        h, w = h - k + 1, w - k + 1
+        total += h * w * co * k * k * ci
+        if n in models.DCNF_POOL_AFTER:
+            h, w = h // 2, w // 2
+    first = h * w * co if rows == 1 else co                     # the patch form flattens its 7 x 7 x 256 map
+    return total + rows * (first * 128 + 128 * 16 + 16)
+
+
+if UNARY != 'patch':
+    rep = models.DCNFReplica(B, train_pairwise=PAIRWISE, pairwise_texture=TEXTURE, valid_range=(0.0, 0.99) if HOLES else None,
+                             unary=UNARY)
+elif HOLES:
     rep = models.DCNFReplica(B, train_pairwise=PAIRWISE, pairwise_texture=TEXTURE, valid_range=(0.0, 0.99))
 elif TEXTURE:
     rep = models.DCNFReplica(B, train_pairwise=PAIRWISE, pairwise_texture=True)
@@ -65,13 +89,20 @@ else:
     t_loss = timeit(lambda: (ops.crf_loss_grad if PAIRWISE else ops.crf_loss)(*loss_args), reps=50)
 gflop_patch = 2.672          # forward GFLOP per patch
 fwd_tf = gflop_patch * net.P / t_fwd           # GFLOP / ms = TFLOP/s
+workload = f'DCNF unary, batch {B} -> {net.P} patches 100x100x3'
 extra = {}
+if UNARY != 'patch':
+    gflop_image = 2e-9 * conv_macs(models.DCNF_IMG_H, models.DCNF_IMG_W, rep.nsp)
+    fwd_tf = gflop_image * B / t_fwd
+    workload = f'DCNF unary ({UNARY}), batch {B} -> {B} images 240x320x3, {net.P} superpixel rows'
+    extra = {'unary': UNARY, 'forward_gflop_per_image': round(gflop_image, 3),
+             'patch_form_gflop_per_image': round(2e-9 * 48 * conv_macs(100, 100, 1), 3)}
 if HOLES:
     torch.cuda.synchronize()
     nobs = rep.nobs.cpu().numpy()
-    extra = {'holes': True, 'observed_fraction': round(float(nobs.sum()) / (B * rep.nsp), 4),
+    extra = {**extra, 'holes': True, 'observed_fraction': round(float(nobs.sum()) / (B * rep.nsp), 4),
              'observed_superpixels_min_max': [int(nobs.min()), int(nobs.max())], 'loss_before_the_steps': round(first_loss, 4)}
-print(json.dumps({'workload': f'DCNF unary, batch {B} -> {net.P} patches 100x100x3', 'forward_ms': round(t_fwd, 3),
+print(json.dumps({'workload': workload, 'forward_ms': round(t_fwd, 3),
                   'forward_images_per_s': round(B / t_fwd * 1e3, 1), 'forward_tflops': round(fwd_tf, 1),
                   'backward_ms': round(t_bwd, 3), 'dtype': 'f32',
                   'train_step_ms': round(t_step, 3), 'train_step_images_per_s': round(B / t_step * 1e3, 1),
