@@ -72,6 +72,7 @@ endif
 # maps with holes (raw Kinect frames, Make3D) TRAIN_ARGS="--min-depth 0 --max-depth 0.99", or for MODEL=dcnf
 # TRAIN_ARGS="--train-pairwise --pairwise-texture" (the pairwise weights learn, over three similarities) or
 # TRAIN_ARGS="--unary fcsp" (the unary convs once over the whole image, superpixel pooling before the dense head)
+# or TRAIN_ARGS="--unary fcsp --superpixel 10" (a 24 x 32 depth map per image on the banded CRF; 20: 12 x 16)
 TRAIN_ARGS ?=
 .PHONY: train
 train: ${DATA_DIR}

@@ -172,6 +172,12 @@ FCSP_SIGNATURES = {
     'a3df_superpixel_pool_bwd': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_crf_band.h declares (NON-REFERENCE extension, prefix a3db_)
+CRF_BAND_SIGNATURES = {
+    'a3db_crf_band_nll': (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    'a3db_crf_band_map': (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -189,7 +195,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(PAIR_SIGNATURES.items())
                               + list(TEXTURE_SIGNATURES.items()) + list(GRADLOSS_SIGNATURES.items())
-                              + list(CRF_VALID_SIGNATURES.items()) + list(FCSP_SIGNATURES.items())):
+                              + list(CRF_VALID_SIGNATURES.items()) + list(FCSP_SIGNATURES.items())
+                              + list(CRF_BAND_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

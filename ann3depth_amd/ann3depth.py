@@ -10,7 +10,7 @@ replaced by synchronous RCCL data parallelism: launch one process per GPU with
 accepted and ignored.
 
 Flags that are not the reference's: --beta2, --precision, --augment, --min-depth / --max-depth, --loss-gradient,
---train-pairwise, --pairwise-texture, --unary {patch,fcsp} (dcnf: the unary part over 48 patches per image, the
+--train-pairwise, --pairwise-texture, --superpixel {40,20,10}, --unary {patch,fcsp} (dcnf: the unary part over 48 patches per image, the
 reference's, or once over the whole image with superpixel pooling before the dense head), --seed, --tf-checkpoints,
 --trace-every, --profiler.
 """
@@ -74,6 +74,17 @@ def main(argv=None):
         logger.error(f'--unary {args.unary} chooses the form of the unary part of --model dcnf (Liu et al. 2015, DCNF-FCSP): '
                      f'{args.model or "(no model)"} has no such part.')
         return 2
+    if args.superpixel != models.DCNF_SP:
+        if not hasattr(getattr(models, args.model, None), 'superpixel'):
+            logger.error(f'--superpixel {args.superpixel} sets the grid of the CRF of --model dcnf: '
+                         f'{args.model or "(no model)"} has no superpixels.')
+            return 2
+        try:
+            models.check_dcnf_superpixel(args.superpixel, args.unary,
+                                         None if args.min_depth is None and args.max_depth is None else (0, 0))
+        except ValueError as e:
+            logger.error(f'--superpixel {args.superpixel}: {e}.')
+            return 2
     if args.loss_gradient is not None and args.model != 'msdn':
         logger.error(f'--loss-gradient weighs the gradient-matching term of Eigen & Fergus 2015 in the two losses of --model '
                      f'msdn: {args.model or "(no model)"} has no loss over a pixel grid (dcnf regresses superpixel means).')
@@ -152,6 +163,8 @@ def setup_model(args, rank=0, world=1):
         model.pairwise_texture = bool(args.pairwise_texture)
     if hasattr(model, 'unary'):
         model.unary = args.unary
+    if hasattr(model, 'superpixel'):
+        model.superpixel = args.superpixel
     inputs, targets = data.inputs(args.datadir, args.dataset, args.batchsize, rank=rank, world=world,
                                   seed=args.seed + rank)
     return model(inputs, targets)
@@ -429,6 +442,12 @@ def parse_args(argv=None):
                              'conv stack over 48 overlapping 100 x 100 patches per image. fcsp: the convs once over the whole '
                              'image, the last feature map averaged inside every superpixel, then the dense head (Liu et al. '
                              '2015, DCNF-FCSP); dense/kernel is [256,128], and a checkpoint of the other form is refused.')
+    parser.add_argument('--superpixel', default=40, type=int, choices=[40, 20, 10],
+                        help='NON-REFERENCE unless 40: the edge of the superpixels (dcnf only). 40: the reference\'s 6 x 8 depth '
+                             'map per image. 20 and 10: 12 x 16 and 24 x 32, on the banded CRF likelihood (no epsilons; its '
+                             'value is not comparable with the loss at 40). They need --unary fcsp and do not go with '
+                             '--min-depth / --max-depth yet. No weight depends on the grid: a checkpoint trained at one '
+                             'evaluates at another.')
     parser.add_argument('--seed', default=0, type=int, help='Shuffle-queue seed.')
     parser.add_argument('--tf-checkpoints', action='store_true',
                         help='Also write every checkpoint as a TensorFlow V2 bundle (model.ckpt-N.index/.data-*).')

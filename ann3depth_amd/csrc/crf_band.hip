@@ -1,0 +1,301 @@
+// crf_band.hip — DCNF's CRF on fine superpixel grids (include/a3d_crf_band.h, NON-REFERENCE, --superpixel 20 / 10): the
+// negative log-likelihood L = e^T A e - 1/2 log det A + (nsp / 2) log pi, e = y - A^-1 z, its gradients wrt z and the pair
+// weights r, and the MAP depths A^-1 z, for up to 768 superpixels per image.  A = I + D - R of a row-major grid graph is
+// banded, half bandwidth `band` = the grid's columns.  One workgroup per image; the dense A is never formed.
+//
+// Band storage.  S[c][d], c < nsp, 0 <= d <= band, holds the lower triangle by columns: S[c][d] = A[c + d][c].  The
+// factorisation A = L D L^T (no pivoting) runs in place: step k reads column k and subtracts l_i a_j from S[k + j][i - j],
+// 1 <= j <= i <= band, so the storage holds a = L D until one parallel pass divides every column by its pivot.  The
+// forward solve L u = z rides along in the same steps.  mu comes from the column sweep of L^T mu = D^-1 u.  With dr the
+// Takahashi recurrence then overwrites the factor, last row first, with the entries of Z = A^-1 inside the band,
+// S[i][d] = Z[i][i + d]:  Z[i][j] = -sum_m L[i + m][i] Z[i + m][j] (j > i),  Z[i][i] = 1 / D_i - sum_m L[i + m][i] Z[i][i + m].
+// e^T A e = sum_i D_i ((L^T e)_i)^2 is taken from the factor before that: A itself is gone by then.
+//
+// Row stride.  The lanes walk S along a row (S[c][d], d the lane: dwords 1 apart) and along an anti-diagonal
+// (S[k - d][d] in the backward sweep, S[i + d][m - d] in the recurrence: dwords stride - 1 apart); nothing on the serial
+// chain walks a column.  So the stride is the even number band + 1 or band + 2, which makes stride - 1 odd: both walks
+// touch 32 different banks of the 64.  (crf.hip's tiles are walked by row and by column and have odd strides for the
+// same reason.)  Only the set-up pass that adds the row sums of R walks columns, two lanes to a bank, once.
+//
+// Threads.  kThreads = 256: four wavefronts.  Steps k and k + 1 of all three sweeps depend on each other, so every step ends
+// in a barrier, and a one-wavefront workgroup's barrier is free; but a step of the factorisation is up to 528 multiply-adds
+// whose LDS round trips one wavefront takes 16 deep and four take 4 deep, and that outweighs s_barrier: measured at batch
+// 16, 24 x 32, the launch without dr takes 0.94 ms with 64 threads and 0.42 ms with 256 (DESIGN.md §3.5 has both tables).
+// The code is written for any multiple of 64 (-DA3DB_THREADS=64 builds the other one).
+//
+// LDS (dynamic, sized from the call's nsp and band): nsp x stride floats of S and two vectors of nsp floats (z / u / mu and
+// y / e); static: 1056 bytes in the nll kernel (the recurrence's partial sums, the wavefronts' sums, two flags), 16 in the
+// map kernel.  Dynamic bytes:
+//   6 x 8   (band 8,  stride 10):  48 x 10 x 4 +  384 =   2 304 bytes
+//   12 x 16 (band 16, stride 18): 192 x 18 x 4 + 1536 =  15 360 bytes
+//   24 x 32 (band 32, stride 34): 768 x 34 x 4 + 6144 = 110 592 bytes      (the maxima; 160 KiB per CU: one workgroup)
+// Compiler's resource report for gfx950 (-Rpass-analysis=kernel-resource-usage): crf_band_kernel<false> (nll) 50 VGPRs,
+// crf_band_kernel<true> (map) 26 VGPRs, band_mean_kernel 7 VGPRs; scratch 0 bytes, no spills in all three.
+//
+// Every loop bound is a function of nsp, band, npairs and the thread alone; no trip count, branch or index depends on a
+// value of z, y or r.  A bad pivot turns values into NaN or inf and nothing else.  Indices into S: a column c < nsp with an
+// offset d <= band (c = k + j <= k + w, w = min(band, nsp - 1 - k); c = k - d >= 0 is tested); a pair's cell only after
+// both of its indices were checked against [0, nsp) and their distance against band.  No spin waits, nothing between
+// workgroups, no float atomics: the only atomic is an integer max in LDS that finds the last writer of a cell.
+#include "a3d_internal.h"
+#include "a3d_crf_band.h"
+
+#ifndef A3DB_THREADS
+#define A3DB_THREADS 256
+#endif
+
+namespace a3d {
+namespace {
+
+constexpr int kThreads = A3DB_THREADS;
+constexpr int kWaves = kThreads / 64;
+constexpr float kHalfLogPi = 0.57236494292470009f;
+static_assert(kThreads % 64 == 0 && kThreads >= 64 && kThreads <= 1024, "whole wavefronts");
+
+__host__ __device__ constexpr int band_stride(int band) { return (band + 2) & ~1; }
+
+// the sum over the workgroup in a fixed order: xor butterfly inside a wavefront, then the wavefronts in turn
+__device__ __forceinline__ float band_block_sum(float v, float* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if (kWaves == 1) return v;
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float s = red[0];
+  for (int i = 1; i < kWaves; ++i) s += red[i];
+  __syncthreads();
+  return s;
+}
+
+// kMap: mu and status alone (y, loss_img, dz, dr are not touched).
+template <bool kMap>
+__global__ __launch_bounds__(kThreads) void crf_band_kernel(const float* __restrict__ z, const float* __restrict__ y,
+                                                            const float* __restrict__ r, const int* __restrict__ left,
+                                                            const int* __restrict__ right, float* __restrict__ loss_img,
+                                                            float* __restrict__ dz, float* dr, float* __restrict__ mu,
+                                                            int* __restrict__ status, int n, int band, int npairs,
+                                                            float inv_batch) {
+  extern __shared__ __attribute__((aligned(16))) float band_smem[];
+  __shared__ float red[kWaves > 1 ? kWaves : 1];
+  __shared__ float part[kThreads];               // the recurrence's partial sums, [kThreads / 32][32]
+  __shared__ int flags[2];                       // [0]: a pair that cannot be used; [1]: a pivot or a value that is not accepted
+  const int stride = band_stride(band);
+  float* S = band_smem;                          // [n][stride]
+  int* Si = reinterpret_cast<int*>(band_smem);
+  float* zv = S + n * stride;                    // z, then u (L u = z), then D^-1 u, then mu
+  float* ev = zv + n;                            // y, then e = y - mu
+  const int b = blockIdx.x, t = threadIdx.x;
+  const float nanf_ = __builtin_nanf("");
+  const bool want_dr = !kMap && dr != nullptr;
+
+  for (int c = t; c < n * stride; c += kThreads) Si[c] = -1;
+  if (t < 2) flags[t] = 0;
+  __syncthreads();
+  for (int q = t; q < npairs; q += kThreads) {   // the last writer of every cell: the largest pair number
+    const int l = left[q], rr = right[q];
+    const int lo = min(l, rr), d = max(l, rr) - lo;
+    if (l < 0 || l >= n || rr < 0 || rr >= n || d > band) flags[0] = 1;      // skipped, never indexed with
+    else if (d > 0) atomicMax(&Si[lo * stride + d], q);
+  }
+  __syncthreads();
+  const bool bad = flags[0] != 0;                // the index lists are the batch's: every image ends as NaN
+  if (want_dr) {                                 // park "this pair owns its cell" in dr; each thread reads back its own
+    for (int q = t; q < npairs; q += kThreads) {
+      const int l = left[q], rr = right[q];
+      const int lo = min(l, rr), d = max(l, rr) - lo;
+      const bool usable = !(l < 0 || l >= n || rr < 0 || rr >= n || d > band) && d > 0;
+      dr[(size_t)b * npairs + q] = (usable && Si[lo * stride + d] == q) ? 1.f : 0.f;
+    }
+    __syncthreads();
+  }
+  for (int c = t; c < n * stride; c += kThreads) {      // -R below the diagonal (0 - r as crf.hip), +0 where no pair is
+    const int q = Si[c];
+    S[c] = q >= 0 ? 0.f - r[(size_t)b * npairs + q] : 0.f;
+  }
+  __syncthreads();
+  for (int i = t; i < n; i += kThreads) {        // A[i][i] = 1 + the row sum of R, columns in ascending order
+    float rs = 0.f;
+    for (int j = max(0, i - band); j < i; ++j) rs += S[j * stride + (i - j)];
+    const int w = min(band, n - 1 - i);
+    for (int d = 1; d <= w; ++d) rs += S[i * stride + d];
+    S[i * stride] = 1.f - rs;                    // rs = -(row sum): 1 + the row sum, bit for bit
+    zv[i] = z[(size_t)b * n + i];
+    if (!kMap) ev[i] = y[(size_t)b * n + i];
+  }
+  __syncthreads();
+
+  // L D L^T and L u = z.  Thread (i, g): row offset i = 1 .. 32, column offsets j = 1 + g, 1 + g + G, ... <= i.
+  {
+    const int i = (t & 31) + 1, g = t >> 5;
+    constexpr int G = kThreads / 32;
+    for (int k = 0; k < n; ++k) {
+      const int w = min(band, n - 1 - k);
+      const float* col = S + k * stride;
+      if (i <= w) {
+        const float li = col[i] / col[0];
+        for (int j = 1 + g; j <= i; j += G) S[(k + j) * stride + (i - j)] -= li * col[j];
+        if (g == 0) zv[k + i] -= li * zv[k];
+      }
+      __syncthreads();
+    }
+  }
+  // the pivots: accepted iff all are finite and > 0; log det; L = a / D; D^-1 u
+  float ld = 0.f;
+  bool ok = true;
+  for (int i = t; i < n; i += kThreads) {
+    const float p = S[i * stride];
+    ok = ok && p > 0.f && p < INFINITY;
+    ld += logf(p);
+    zv[i] = zv[i] / p;
+  }
+  for (int c = t; c < n * stride; c += kThreads) {
+    const int row = c / stride, d = c - row * stride;
+    if (d >= 1 && d <= band) S[c] = S[c] / S[row * stride];
+  }
+  if (!ok) flags[1] = 1;
+  ld = band_block_sum(ld, red);
+  __syncthreads();
+  // L^T mu = D^-1 u, column sweep: once mu_k stands, the rows above take their share
+  for (int k = n - 1; k > 0; --k) {
+    const int d = t + 1;
+    if (d <= band && k - d >= 0) zv[k - d] -= S[(k - d) * stride + d] * zv[k];
+    __syncthreads();
+  }
+  if (kMap) {
+    bool fin = true;
+    for (int i = t; i < n; i += kThreads) fin = fin && isfinite(zv[i]);
+    if (!fin) flags[1] = 1;
+    __syncthreads();
+    const bool nan_row = bad || flags[1] != 0;
+    for (int i = t; i < n; i += kThreads) mu[(size_t)b * n + i] = nan_row ? nanf_ : zv[i];
+    if (t == 0) status[b] = nan_row ? 1 : 0;
+    return;
+  }
+  for (int i = t; i < n; i += kThreads) ev[i] = ev[i] - zv[i];
+  __syncthreads();
+  float qf = 0.f;                                // e^T A e = sum_i D_i ((L^T e)_i)^2
+  for (int i = t; i < n; i += kThreads) {
+    const int w = min(band, n - 1 - i);
+    float s = ev[i];
+    for (int d = 1; d <= w; ++d) s += S[i * stride + d] * ev[i + d];
+    qf += S[i * stride] * (s * s);
+  }
+  qf = band_block_sum(qf, red);
+  const float loss = (qf - 0.5f * ld) + (float)n * kHalfLogPi;
+  const bool nan_row = bad || flags[1] != 0 || !isfinite(loss);
+  if (t == 0) {
+    loss_img[b] = nan_row ? nanf_ : loss;
+    status[b] = nan_row ? 1 : 0;
+  }
+  for (int i = t; i < n; i += kThreads) {
+    dz[(size_t)b * n + i] = nan_row ? nanf_ : (-2.f * ev[i]) * inv_batch;
+    if (mu) mu[(size_t)b * n + i] = nan_row ? nanf_ : zv[i];
+  }
+  if (!want_dr) return;
+  __syncthreads();
+  // Takahashi: row i of Z over the slot of column i of L.  Thread (d, g): the terms m = 1 + g, 1 + g + G, ... of the entry
+  // Z[i][i + d]; the G partial sums meet in LDS and the first 32 threads add them in the order of g.
+  for (int i = n - 1; i >= 0; --i) {
+    constexpr int G = kThreads / 32;
+    const int w = min(band, n - 1 - i), d = (t & 31) + 1, g = t >> 5;
+    const float* col = S + i * stride;
+    float acc = 0.f;
+    if (d <= w)
+      for (int m = 1 + g; m <= w; m += G) {
+        const float zz = m <= d ? S[(i + m) * stride + (d - m)] : S[(i + d) * stride + (m - d)];
+        acc += col[m] * zz;
+      }
+    part[t] = acc;
+    const float ld_ = (g == 0 && d <= w) ? col[d] : 0.f, dinv = 1.f / col[0];
+    __syncthreads();                             // column i of L has been read, the partial sums stand
+    if (g == 0) {                                // one half of the first wavefront; the other half adds zeros
+      float sum = part[t];
+      for (int k = 1; k < G; ++k) sum += part[k * 32 + t];
+      const float zij = 0.f - sum;
+      float s = ld_ * zij;
+#pragma unroll
+      for (int off = 16; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+      if (d <= w) S[i * stride + d] = zij;
+      if (t == 0) S[i * stride] = dinv - s;
+    }
+    __syncthreads();
+  }
+  for (int q = t; q < npairs; q += kThreads) {
+    const size_t o = (size_t)b * npairs + q;
+    const bool own = dr[o] != 0.f;
+    float v = nanf_;
+    if (!nan_row) {                              // not bad: an owner's l and rr are inside [0, n), 0 < |l - rr| <= band
+      v = 0.f;
+      if (own) {
+        const int l = left[q], rr = right[q];
+        const int lo = min(l, rr), d = max(l, rr) - lo;
+        const float zlr = S[lo * stride + d];
+        const float s_a = ((S[l * stride] + S[rr * stride]) - zlr) - zlr;
+        const float vq = ev[l] - ev[rr], vm = zv[l] - zv[rr];
+        v = (((2.f * vq) * vm + vq * vq) - 0.5f * s_a) * inv_batch;
+      }
+    }
+    dr[o] = v;
+  }
+}
+
+__global__ __launch_bounds__(64) void band_mean_kernel(const float* __restrict__ v, int n, float* __restrict__ out) {
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 64) s += v[i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  if (threadIdx.x == 0) out[0] = s / (float)n;
+}
+
+size_t band_lds_bytes(int nsp, int band) { return ((size_t)nsp * band_stride(band) + 2 * (size_t)nsp) * sizeof(float); }
+static_assert(((size_t)A3DB_MAX_SP * band_stride(A3DB_MAX_BAND) + 2 * (size_t)A3DB_MAX_SP) * sizeof(float) + 2048 <= 160 * 1024,
+              "the maxima fit one CU's LDS");
+
+template <bool kMap>
+int band_launch(int n, int nsp, int band, const float* z, const float* y, const float* r, const int32_t* left,
+                const int32_t* right, int npairs, float* loss_per_image, float* dz, float* dr, float* mu, int32_t* status,
+                hipStream_t st, const char* what) {
+  const size_t lds = band_lds_bytes(nsp, band);
+  // above 64 KiB of dynamic LDS: the attribute is per device and cheap, set on every call that needs it
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&crf_band_kernel<kMap>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)band_lds_bytes(A3DB_MAX_SP, A3DB_MAX_BAND)) != hipSuccess)
+    return set_error(A3D_ELAUNCH, "%s: hipFuncSetAttribute failed", what);
+  clear_stale_error();
+  hipLaunchKernelGGL(crf_band_kernel<kMap>, dim3(n), dim3(kThreads), lds, st, z, y, r, left, right, loss_per_image, dz, dr,
+                     mu, status, nsp, band, npairs, 1.0f / (float)n);
+  return check_launch(what);
+}
+
+}  // namespace
+}  // namespace a3d
+
+using namespace a3d;
+
+extern "C" {
+
+int a3db_crf_band_nll(int n, int nsp, int band, const float* z, const float* y, const float* r, const int32_t* left,
+                      const int32_t* right, int npairs, float* loss_per_image, float* loss_mean, float* dz, float* dr,
+                      float* mu, int32_t* status, void* stream) {
+  A3D_CHECK_ARG(n > 0 && nsp >= 1 && nsp <= A3DB_MAX_SP && band >= 1 && band <= A3DB_MAX_BAND && npairs > 0 && z && y && r &&
+                    left && right && loss_per_image && loss_mean && dz && status,
+                "crf_band_nll: bad arguments (1 .. %d superpixels, band 1 .. %d)", A3DB_MAX_SP, A3DB_MAX_BAND);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = band_launch<false>(n, nsp, band, z, y, r, left, right, npairs, loss_per_image, dz, dr, mu, status, st,
+                              "crf_band_nll");
+  if (rc != A3D_OK) return rc;
+  clear_stale_error();
+  hipLaunchKernelGGL(band_mean_kernel, dim3(1), dim3(64), 0, st, loss_per_image, n, loss_mean);
+  return check_launch("crf_band_nll_mean");
+}
+
+int a3db_crf_band_map(int n, int nsp, int band, const float* z, const float* r, const int32_t* left, const int32_t* right,
+                      int npairs, float* mu, int32_t* status, void* stream) {
+  A3D_CHECK_ARG(n > 0 && nsp >= 1 && nsp <= A3DB_MAX_SP && band >= 1 && band <= A3DB_MAX_BAND && npairs > 0 && z && r && left &&
+                    right && mu && status,
+                "crf_band_map: bad arguments (1 .. %d superpixels, band 1 .. %d)", A3DB_MAX_SP, A3DB_MAX_BAND);
+  return band_launch<true>(n, nsp, band, z, nullptr, r, left, right, npairs, nullptr, nullptr, nullptr, mu, status,
+                           static_cast<hipStream_t>(stream), "crf_band_map");
+}
+
+}  // extern "C"

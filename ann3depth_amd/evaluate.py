@@ -166,7 +166,7 @@ class Evaluator:
 
 class DCNFEvaluator:
     """DCNF's per-batch work: predict (unary z and the field's MAP depths), the objective on the same batch, which also
-    leaves the targets at 240 x 320, and the metric rows of both outputs; the 6 x 8 predictions are sampled at the
+    leaves the targets at 240 x 320, and the metric rows of both outputs; the replica's rows x cols predictions are sampled at the
     target's pixels inside a3d_depth_metrics."""
     outputs = OUTPUTS['dcnf']
 
@@ -229,6 +229,13 @@ def main(argv=None):
     if args.observed_nll and args.model != 'dcnf':
         _say('--observed-nll is the held-out objective of a dcnf run trained with --min-depth / --max-depth.')
         return 2
+    if args.superpixel != 40 and args.model != 'dcnf':
+        _say(f'--superpixel {args.superpixel} sets the grid of the CRF of --model dcnf: {args.model} has no superpixels.')
+        return 2
+    if args.superpixel != 40 and args.observed_nll:
+        _say(f'--superpixel {args.superpixel} cannot go with --observed-nll yet: the likelihood of the observed superpixels '
+             f'alone exists only for the dense 6 x 8 CRF (--superpixel 40).')
+        return 2
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         _say('evaluation runs in one process on one GPU; start it without a distributed launcher.')
         return 2
@@ -244,7 +251,7 @@ def main(argv=None):
         return 2
     if not torch.cuda.is_available():
         raise RuntimeError('ann3depth_amd needs an MI355X: evaluation has no CPU fallback')
-    from .models import DCNF_PAIR_PREFIX, DCNF_PREFIX, DCNFReplica, MSDNReplica
+    from .models import DCNF_PAIR_PREFIX, DCNF_PREFIX, DCNFReplica, MSDNReplica, check_dcnf_superpixel
     dev = torch.device('cuda', torch.cuda.current_device())
     _say(f'restoring {ckpt}')
     bundle = tfckpt.is_bundle(ckpt)                  # as ann3depth.Session.__enter__ restores
@@ -263,7 +270,14 @@ def main(argv=None):
         # ... and which form its unary part has: dense/kernel is [256, 128] with --unary fcsp, [12544, 128] without
         dense = DCNF_PREFIX + 'dense/kernel'
         unary = 'fcsp' if dense in state and tuple(np.shape(state[dense])) == (256, 128) else 'patch'
-        replica = DCNFReplica(args.batchsize, device=dev, precision=args.precision, pairwise_texture=texture, unary=unary)
+        try:
+            check_dcnf_superpixel(args.superpixel, unary, None)
+        except ValueError as e:
+            _say(f'{ckpt}: a checkpoint of the patch form; {e}.')
+            inputs.pipeline.close()
+            return 2
+        replica = DCNFReplica(args.batchsize, device=dev, precision=args.precision, pairwise_texture=texture, unary=unary,
+                              superpixel=args.superpixel)
     else:
         replica = MSDNReplica(args.batchsize, device=dev, precision=args.precision, keep_dense_grads=False)
     if bundle:
@@ -295,6 +309,8 @@ def main(argv=None):
         out['pairwise_texture'] = True
     if unary != 'patch':
         out['unary_form'] = unary          # ('unary' holds the metrics of the unary output)
+    if args.model == 'dcnf':
+        out['superpixel'] = args.superpixel
     if args.predictions:
         np.save(args.predictions, torch.cat(ev.predictions).cpu().numpy() if ev.predictions else
                 np.zeros((0,) + ev.prediction_shape, np.float32))
@@ -339,7 +355,13 @@ def parse_args(argv=None):
                         '--max-depth (the likelihood of the superpixels those two thresholds leave observed), and the share '
                         'of superpixels it counted.')
     p.add_argument('--predictions', default='', type=str,
-                   help='Write the fine (msdn, [N,55,74]) or crf (dcnf, [N,6,8]) predictions to this .npy.')
+                   help='Write the fine (msdn, [N,55,74]) or crf (dcnf, [N,6,8]; [N,12,16] or [N,24,32] with --superpixel 20 or '
+                        '10) predictions to this .npy.')
+    p.add_argument('--superpixel', default=40, type=int, choices=[40, 20, 10],
+                   help='NON-REFERENCE unless 40, dcnf: the edge of the superpixels the checkpoint is evaluated at (6 x 8, '
+                        '12 x 16 or 24 x 32 depths per image). Checkpoints hold no grid: one trained at 40 evaluates at 10 and '
+                        'the reverse. 20 and 10 need a checkpoint of --unary fcsp; crf_nll is then the banded likelihood, '
+                        'not comparable with the value at 40.')
     return p.parse_args(argv)
 
 

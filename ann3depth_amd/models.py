@@ -1418,6 +1418,26 @@ DCNF_GAMMA, DCNF_EPSILON = 1.0, 1e-7    # src/models.py:17-18
 DCNF_PAIR_PREFIX = 'pairwise/pairwise_layers/dense/'
 
 
+DCNF_SUPERPIXELS = (40, 20, 10)         # --superpixel: 6 x 8, 12 x 16, 24 x 32 superpixels on 240 x 320
+
+
+def check_dcnf_superpixel(superpixel, unary, valid_range):
+    """ValueError unless DCNFReplica can run at this superpixel edge with this unary form and these targets (the driver
+    and the evaluation call it before any GPU work)."""
+    if superpixel not in DCNF_SUPERPIXELS:
+        raise ValueError(f'superpixel {superpixel!r}: one of {DCNF_SUPERPIXELS} (--superpixel)')
+    if superpixel == DCNF_SP:
+        return
+    rows, cols = DCNF_IMG_H // superpixel, DCNF_IMG_W // superpixel
+    if unary != 'fcsp':
+        raise ValueError(f'superpixel {superpixel} needs --unary fcsp: the patch form would run {rows * cols} patches per '
+                         f'image')
+    if valid_range is not None:
+        raise ValueError(f'superpixel {superpixel} cannot go with --min-depth / --max-depth yet: the likelihood of the '
+                         f'observed superpixels alone exists only for the dense 6 x 8 CRF (--superpixel 40); on the banded '
+                         f'CRF it is a later change')
+
+
 def dcnf_pair_indices(rows, cols):
     """src/models.py:20-30: every interior superpixel on one colour of the checkerboard, paired with its four
     neighbours (up, down, left, right): two int lists (left, right)."""
@@ -1466,15 +1486,31 @@ class DCNFReplica:
     superpixel pooling before the dense head (Liu et al. 2015, DCNF-FCSP), in place of the 48 patches per image.  The rest
     of the step reads only z and the resized image and is the same code.  dense/kernel is [256,128] in that form and
     [12544,128] in the other; a restore across the two is refused.  'patch' (the default): no launch, buffer or bit
-    differs."""
+    differs.
+
+    superpixel (NON-REFERENCE, --superpixel): the edge of the square superpixels, 40 (the reference's 6 x 8 grid of 48),
+    20 (12 x 16 = 192) or 10 (24 x 32 = 768).  Every part of the step that reads a superpixel uses this replica's sp;
+    no weight depends on it, so a checkpoint trained at one grid loads and evaluates at another.  20 and 10 need
+    unary='fcsp' (the patch form would run 192 or 768 patches per image) and valid_range=None (the likelihood of the
+    observed superpixels on a band is not built yet).  At 20 and 10 the CRF is the banded one (include/a3d_crf_band.h):
+    forward_crf and nll launch ops.crf_band_nll (with dr iff train_pairwise), predict launches ops.crf_band_map, and
+    self.status keeps its meaning.  The objective there is the field's negative log-likelihood WITHOUT the reference's
+    three epsilons, e^T A e - log det A / 2 + S log(pi) / 2: the reference's form multiplies by pi^(S/2), which has no
+    float32 value from S = 156.  Its value is not comparable with the --superpixel 40 loss.  The likelihood exists only for
+    a positive definite A, so at 20 and 10 construction projects the pairwise kernel and bias onto >= 0 whether or not
+    they train (r >= 0 makes A strictly diagonally dominant, every pivot >= 1).  40 (the default): today's code path,
+    launches, buffers and bits."""
     uses_dropout = False
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, global_step=0, reducer=None,
                  precision='fp32', train_pairwise=False, pairwise_texture=False, valid_range=None, min_valid=0.5,
-                 unary='patch'):
+                 unary='patch', superpixel=DCNF_SP):
         if unary not in ('patch', 'fcsp'):
             raise ValueError(f"unary {unary!r}: 'patch' or 'fcsp'")
         self.unary_form = unary
+        check_dcnf_superpixel(superpixel, unary, valid_range)
+        self.sp = sp = int(superpixel)
+        self.banded = sp != DCNF_SP
         if valid_range is not None:
             lo, hi = (float(v) for v in valid_range)
             if not lo <= hi:
@@ -1483,7 +1519,7 @@ class DCNFReplica:
         if not 0 <= float(min_valid) <= 1:
             raise ValueError(f'min_valid {min_valid!r}: the share of a superpixel that must be measured, 0 .. 1')
         self.valid_range, self.min_valid = valid_range, float(min_valid)
-        self.min_count = int(math.ceil(self.min_valid * DCNF_SP * DCNF_SP))
+        self.min_count = int(math.ceil(self.min_valid * sp * sp))
         self.t_one = self.count = self.nobs = None      # allocated by the first launch that has holes to look for
         self.B = batchsize
         self.device = dev = torch.device(device)
@@ -1494,14 +1530,17 @@ class DCNFReplica:
         self.global_step = global_step
         if params is not None:
             self._check_unary_kernel(np.shape(params[DCNF_PREFIX + 'dense/kernel']), 'params')
-        self.unary = (DCNFUnaryFCSP if unary == 'fcsp' else DCNFUnary)(batchsize, dev, params=params, seed=seed,
-                                                                       precision=precision)
-        self.rows, self.cols = DCNF_IMG_H // DCNF_SP, DCNF_IMG_W // DCNF_SP
+        if unary == 'fcsp':
+            self.unary = DCNFUnaryFCSP(batchsize, dev, params=params, seed=seed, precision=precision, sp=sp)
+        else:
+            self.unary = DCNFUnary(batchsize, dev, params=params, seed=seed, precision=precision)
+        self.rows, self.cols = DCNF_IMG_H // sp, DCNF_IMG_W // sp
         assert (self.rows, self.cols) == (self.unary.rows, self.unary.cols)
         self.nsp = self.rows * self.cols
         left, right = dcnf_pair_indices(self.rows, self.cols)
         self.left = torch.tensor(left, dtype=torch.int32, device=dev)
         self.right = torch.tensor(right, dtype=torch.int32, device=dev)
+        self.band = ops.pair_band(left, right)
         pshapes = collections.OrderedDict([(DCNF_PAIR_PREFIX + 'kernel', (self.nsims, 1)), (DCNF_PAIR_PREFIX + 'bias', (1,))])
         self.pair_group = ParamGroup('pairwise', 0.1, pshapes, dev, slots=False)
         if params is None or DCNF_PAIR_PREFIX + 'kernel' not in params:
@@ -1514,7 +1553,7 @@ class DCNFReplica:
         for n in pshapes:
             self.pair_group.view(self.pair_group.var, n).copy_(
                 torch.from_numpy(np.ascontiguousarray(pw[n], np.float32)))
-        if self.train_pairwise:
+        if self.train_pairwise or self.banded:
             ops.sgd_apply_floor(self.pair_group.var, self.pair_group.grad, 0.0, 0.0)      # beta >= 0 from the start
         self.groups = collections.OrderedDict([('unary', self.unary.group), ('pairwise', self.pair_group)])
         self.depths240 = torch.empty((batchsize, DCNF_IMG_H, DCNF_IMG_W, 1), device=dev)
@@ -1550,14 +1589,14 @@ class DCNFReplica:
     def _pairwise(self):
         """The similarities of every pair and the pair weights r from the resized images (src/models.py:112-127)."""
         x = self.unary.resized
-        ops.superpixel_hist(x, DCNF_SP, self.hist)                                        # :112-113
+        ops.superpixel_hist(x, self.sp, self.hist)                                        # :112-113
         kernel, bias = self.pair_var('kernel'), self.pair_var('bias')
         if self.pairwise_texture:
-            ops.superpixel_lbp_hist(x, DCNF_SP, self.lbp)
-            self.sims, self.r = ops.pair_similarity3(x, DCNF_SP, self.hist, self.lbp, self.left, self.right, kernel, bias,
+            ops.superpixel_lbp_hist(x, self.sp, self.lbp)
+            self.sims, self.r = ops.pair_similarity3(x, self.sp, self.hist, self.lbp, self.left, self.right, kernel, bias,
                                                      DCNF_GAMMA)
         else:
-            self.sims, self.r = ops.pair_similarity(x, DCNF_SP, self.hist, self.left, self.right, kernel, bias,
+            self.sims, self.r = ops.pair_similarity(x, self.sp, self.hist, self.left, self.right, kernel, bias,
                                                     DCNF_GAMMA)                           # :115-127
 
     def forward(self, images, depths):
@@ -1574,13 +1613,25 @@ class DCNFReplica:
             return self.loss
         ops.resize_bilinear_tf1(depths, self.depths240)                                   # src/models.py:181
         self._pairwise()
-        ops.superpixel_mean(self.depths240, DCNF_SP, self.y)                              # :131-132
+        ops.superpixel_mean(self.depths240, self.sp, self.y)                              # :131-132
+        if self.banded:
+            self.loss, self.loss_per_image, self.dz, self.dr = self._banded(self.B, self.train_pairwise)
+            return self.loss
         crf_args = (u.z.view(self.B, self.nsp), self.y.view(self.B, self.nsp), self.r, self.left, self.right, DCNF_EPSILON)
         if self.train_pairwise:                                                           # one launch, not two
             self.loss, self.loss_per_image, self.dz, self.dr = ops.crf_loss_grad(*crf_args)
         else:
             self.loss, self.loss_per_image, self.dz = ops.crf_loss(*crf_args)             # :129-177
         return self.loss
+
+    def _banded(self, n, pair_grad):
+        """superpixel 20 / 10: the banded likelihood on rows [0, n) from the z, y and r that stand in the buffers: (mean [1],
+        per image, dz, dr or None without pair_grad); leaves the status of those rows in self.status."""
+        mean, per, dz, dr, _, status = ops.crf_band_nll(
+            self.unary.z.view(self.B, self.nsp)[:n], self.y.view(self.B, self.nsp)[:n], self.r[:n], self.left, self.right,
+            self.band, pair_grad=pair_grad)
+        self.status[:n].copy_(status)
+        return mean, per, dz, dr
 
     def _observed(self, depths, n, valid_range, pair_grad):
         """valid_range's objective on rows [0, n) from the z and r that stand in the buffers: the targets through the
@@ -1592,7 +1643,7 @@ class DCNFReplica:
         lo, hi = valid_range
         y = self.y.view(self.B, self.nsp)
         ops.resize_bilinear_tf1_valid(depths[:n], self.depths240[:n], lo, hi, scratch=self.t_one[:n])
-        ops.superpixel_mean_valid(self.depths240[:n], DCNF_SP, self.min_count, out=y[:n], count=self.count[:n])
+        ops.superpixel_mean_valid(self.depths240[:n], self.sp, self.min_count, out=y[:n], count=self.count[:n])
         mean, self.loss_per_image, self.dz, self.dr, self.nobs, self.status_observed = ops.crf_loss_observed(
             self.unary.z.view(self.B, self.nsp)[:n], y[:n], self.r[:n], self.left, self.right, pair_grad=pair_grad)
         return mean
@@ -1615,7 +1666,10 @@ class DCNFReplica:
             u.resized[n:].zero_()
         u.forward_resized(record_argmax=False)
         self._pairwise()
-        self.crf, self.status = ops.crf_map(u.z.view(B, self.nsp), self.r, self.left, self.right, self.crf, self.status)
+        if self.banded:
+            ops.crf_band_map(u.z.view(B, self.nsp), self.r, self.left, self.right, self.band, self.crf, self.status)
+        else:
+            self.crf, self.status = ops.crf_map(u.z.view(B, self.nsp), self.r, self.left, self.right, self.crf, self.status)
         return u.z.view(B, self.rows, self.cols), self.crf.view(B, self.rows, self.cols)
 
     def nll(self, depths, n, valid_range=None):
@@ -1628,9 +1682,13 @@ class DCNFReplica:
             raise ValueError(f'nll: n = {n} rows of {depths.shape[0]} depth maps, replica batch {self.B}, after predict()')
         valid_range = self.valid_range if valid_range is None else valid_range
         if valid_range is not None:
+            if self.banded:
+                raise ValueError(f'nll: superpixel {self.sp} has no likelihood of observed superpixels alone yet (valid_range)')
             return self._observed(depths, n, valid_range, False)
         ops.resize_bilinear_tf1(depths[:n], self.depths240[:n])                           # src/models.py:181
-        ops.superpixel_mean(self.depths240[:n], DCNF_SP, self.y[:n])                      # :131-132
+        ops.superpixel_mean(self.depths240[:n], self.sp, self.y[:n])                      # :131-132
+        if self.banded:
+            return self._banded(n, False)[0]
         mean, _, _ = ops.crf_loss(self.unary.z.view(self.B, self.nsp)[:n], self.y.view(self.B, self.nsp)[:n],
                                   self.r[:n], self.left, self.right, DCNF_EPSILON)
         return mean
@@ -1881,6 +1939,7 @@ class _DistributedConvolutionalNeuralFields:
     valid_range = None   # NON-REFERENCE, --min-depth / --max-depth: (min, max), the depth maps have holes (see DCNFReplica)
     min_valid = 0.5      # the share of a superpixel that must be measured for it to be a target (see DCNFReplica)
     unary = 'patch'      # NON-REFERENCE, --unary fcsp: convs once over the image + superpixel pooling (see DCNFReplica)
+    superpixel = DCNF_SP  # NON-REFERENCE, --superpixel 20 / 10: finer grids on the banded CRF (see DCNFReplica)
 
     def __call__(self, images, depths, train=True):
         assert images.pipeline is depths.pipeline, 'inputs and targets must come from the same data.inputs() call'
@@ -1888,7 +1947,8 @@ class _DistributedConvolutionalNeuralFields:
         replica = DCNFReplica(images.pipeline.B, device=torch.device('cuda', torch.cuda.current_device()),
                               seed=self.seed, reducer=self.reducer, precision=self.precision,
                               train_pairwise=self.train_pairwise and train, pairwise_texture=self.pairwise_texture,
-                              valid_range=self.valid_range, min_valid=self.min_valid, unary=self.unary)
+                              valid_range=self.valid_range, min_valid=self.min_valid, unary=self.unary,
+                              superpixel=self.superpixel)
         if self.reducer is not None:
             for g in replica.groups.values():
                 self.reducer.broadcast(g.var)

@@ -929,6 +929,70 @@ def crf_loss_observed(z, y, r, left, right, pair_grad=True):
     return mean, per, dz, dr, nobs, status
 
 
+BAND_MAX_SP, BAND_MAX_BAND = 768, 32         # A3DB_MAX_SP, A3DB_MAX_BAND
+
+
+def pair_band(left, right):
+    """max |l - r| over the pairs (host integer sequences of one length, not empty): the `band` of crf_band_nll and
+    crf_band_map, which cannot look at the device's lists."""
+    left, right = [int(v) for v in left], [int(v) for v in right]
+    if not left or len(left) != len(right):
+        raise ValueError(f'pair_band: {len(left)} / {len(right)} pair indices')
+    return max(abs(a - b) for a, b in zip(left, right))
+
+
+def _check_band(who, z, r, left, right, band, others):
+    if z.dim() != 2 or r.dim() != 2:
+        raise ValueError(f'{who}: z {tuple(z.shape)} and r {tuple(r.shape)} must be [n, P] and [n, Q]')
+    n, nsp = z.shape[0], z.shape[1]
+    if (n == 0 or r.shape[0] != n or left.numel() == 0 or r.shape[1] != left.numel() or left.numel() != right.numel()
+            or any(tuple(t.shape) != (n, nsp) for t in others)):
+        raise ValueError(f'{who}: z {tuple(z.shape)}, {[tuple(t.shape) for t in others]}, r {tuple(r.shape)}, '
+                         f'{left.numel()} / {right.numel()} pair indices')
+    if not 1 <= nsp <= BAND_MAX_SP or not 1 <= int(band) <= BAND_MAX_BAND:
+        raise ValueError(f'{who}: {nsp} superpixels (1 .. {BAND_MAX_SP}), band {band} (1 .. {BAND_MAX_BAND})')
+    if (any(t.dtype != torch.float32 for t in (z, r, *others)) or left.dtype != torch.int32 or right.dtype != torch.int32):
+        raise TypeError(f'{who}: z, y, r, mu float32; left, right int32')
+    if not all(t.is_contiguous() for t in (z, r, left, right, *others)):
+        raise ValueError(f'{who}: contiguous tensors only')
+    if any(t.device != z.device for t in (r, left, right, *others)):
+        raise ValueError(f'{who}: all tensors on one device')
+    return n, nsp
+
+
+def crf_band_nll(z, y, r, left, right, band, pair_grad=True, want_mu=False):
+    """NON-REFERENCE (a3db_crf_band_nll): the CRF's negative log-likelihood e^T A e - log det A / 2 + P log(pi) / 2 of a
+    banded A (every pair |l - r| <= band = pair_band(left, right)), up to 768 superpixels: returns (mean [1], per-image
+    [n], d mean / d z [n,P], d mean / d r [n,Q] or None without pair_grad, mu = A^-1 z [n,P] or None without want_mu,
+    status [n] int32).  z, y [n,P], r [n,Q] float32; left, right [Q] int32.  An image whose A is not positive is NaN with
+    status 1; a pair index outside [0, P) or farther apart than band turns all of it into NaN."""
+    n, nsp = _check_band('crf_band_nll', z, r, left, right, band, (y,))
+    per = torch.empty((n,), dtype=torch.float32, device=z.device)
+    mean = torch.empty((1,), dtype=torch.float32, device=z.device)
+    dz = torch.empty((n, nsp), dtype=torch.float32, device=z.device)
+    dr = torch.empty_like(r) if pair_grad else None
+    mu = torch.empty((n, nsp), dtype=torch.float32, device=z.device) if want_mu else None
+    status = torch.empty((n,), dtype=torch.int32, device=z.device)
+    check(_lib.load().a3db_crf_band_nll(n, nsp, int(band), _ptr(z), _ptr(y), _ptr(r), _ptr(left), _ptr(right), left.numel(),
+                                        _ptr(per), _ptr(mean), _ptr(dz), _ptr(dr) if pair_grad else None,
+                                        _ptr(mu) if want_mu else None, _ptr(status), _stream()), 'a3db_crf_band_nll')
+    return mean, per, dz, dr, mu, status
+
+
+def crf_band_map(z, r, left, right, band, mu=None, status=None):
+    """NON-REFERENCE (a3db_crf_band_map): the field's MAP depths mu = A^-1 z of a banded A, as crf_map for up to 768
+    superpixels: z [n,P], r [n,Q] -> (mu [n,P] float32, status [n] int32; 1 where A was not positive or the solution not
+    finite and the row of mu is NaN)."""
+    mu = mu if mu is not None else torch.empty_like(z)
+    n, nsp = _check_band('crf_band_map', z, r, left, right, band, (mu,))
+    status = status if status is not None else torch.empty((n,), dtype=torch.int32, device=z.device)
+    if status.dtype != torch.int32 or status.numel() != n or not status.is_contiguous() or status.device != z.device:
+        raise ValueError(f'crf_band_map: status {tuple(status.shape)} {status.dtype} for {n} images')
+    check(_lib.load().a3db_crf_band_map(n, nsp, int(band), _ptr(z), _ptr(r), _ptr(left), _ptr(right), left.numel(), _ptr(mu),
+                                        _ptr(status), _stream()), 'a3db_crf_band_map')
+    return mu, status
+
+
 FCSP_MAX_SP = 64         # A3DF_MAX_SP: one lane of a wave per window pixel, 2 KiB of LDS for a block's counts
 
 

@@ -8,7 +8,12 @@ band at the range cap over its upper third and scattered zeros, so that whole su
 targets; `crf_loss_ms` is then ops.crf_loss_observed.
 --unary fcsp: the fully convolutional unary with superpixel pooling (NON-REFERENCE, DCNFReplica(unary='fcsp')): the convs
 once over the 240x320 image; `forward_tflops` then counts that form's own multiply-adds (conv_macs below).
-    python tools/bench_dcnf.py [batch] [--train-pairwise] [--pairwise-texture] [--holes] [--unary fcsp] > dcnf.json"""
+--superpixel N (with --unary fcsp; NON-REFERENCE, DCNFReplica(superpixel=N)): the step on the 12 x 16 (N = 20) or 24 x 32
+(N = 10) grid, whose CRF is the banded one (include/a3d_crf_band.h); `crf_loss_ms` is then ops.crf_band_nll in the form the
+step uses, and `band` holds the band launches alone (nll with dr, nll without, map), their dynamic LDS bytes, the
+workgroups per CU that leaves room for, and the share of the step the step's own launch takes.  --superpixel 40 is the
+run without the flag.
+    python tools/bench_dcnf.py [batch] [--train-pairwise] [--pairwise-texture] [--holes] [--unary fcsp] [--superpixel N] > dcnf.json"""
 import json
 import os
 import sys
@@ -27,6 +32,11 @@ UNARY = 'patch'
 if '--unary' in argv:
     i = argv.index('--unary')
     UNARY = argv[i + 1]
+    del argv[i:i + 2]
+SUPERPIXEL = 40
+if '--superpixel' in argv:
+    i = argv.index('--superpixel')
+    SUPERPIXEL = int(argv[i + 1])
     del argv[i:i + 2]
 B = int(argv[0]) if argv else 16
 rng = np.random.default_rng(1000)
@@ -51,7 +61,10 @@ def conv_macs(h, w, rows):
     return total + rows * (first * 128 + 128 * 16 + 16)
 
 
-if UNARY != 'patch':
+if SUPERPIXEL != 40:
+    rep = models.DCNFReplica(B, train_pairwise=PAIRWISE, pairwise_texture=TEXTURE, valid_range=(0.0, 0.99) if HOLES else None,
+                             unary=UNARY, superpixel=SUPERPIXEL)
+elif UNARY != 'patch':
     rep = models.DCNFReplica(B, train_pairwise=PAIRWISE, pairwise_texture=TEXTURE, valid_range=(0.0, 0.99) if HOLES else None,
                              unary=UNARY)
 elif HOLES:
@@ -83,7 +96,19 @@ t_bwd = timeit(lambda: net.backward(dz))
 t_step = timeit(lambda: rep.step(img, dep))
 t_crf = timeit(lambda: rep.forward_crf(dep))
 loss_args = (net.z.view(B, rep.nsp), rep.y.view(B, rep.nsp), rep.r, rep.left, rep.right, models.DCNF_EPSILON)
-if HOLES:
+band = None
+if SUPERPIXEL != 40:
+    bz, by = loss_args[0].clone(), loss_args[1].clone()
+    t_loss = timeit(lambda: ops.crf_band_nll(bz, by, rep.r, rep.left, rep.right, rep.band, pair_grad=PAIRWISE), reps=50)
+    t_dr = timeit(lambda: ops.crf_band_nll(bz, by, rep.r, rep.left, rep.right, rep.band, pair_grad=True), reps=50)
+    t_nodr = timeit(lambda: ops.crf_band_nll(bz, by, rep.r, rep.left, rep.right, rep.band, pair_grad=False), reps=50)
+    t_map = timeit(lambda: ops.crf_band_map(bz, rep.r, rep.left, rep.right, rep.band, rep.crf, rep.status), reps=50)
+    lds = (rep.nsp * ((rep.band + 2) & ~1) + 2 * rep.nsp) * 4            # band_lds_bytes of csrc/crf_band.hip
+    band = {'grid': [rep.rows, rep.cols], 'superpixels': rep.nsp, 'band': rep.band, 'pairs': int(rep.left.numel()),
+            'nll_with_dr_ms': round(t_dr, 4), 'nll_without_dr_ms': round(t_nodr, 4), 'map_ms': round(t_map, 4),
+            'lds_bytes_per_workgroup': lds, 'workgroups_per_cu_by_lds': min(160 * 1024 // lds, 32), 'workgroups': B,
+            'threads_per_workgroup': 256, 'share_of_step': round(t_loss / t_step, 4)}
+elif HOLES:
     t_loss = timeit(lambda: ops.crf_loss_observed(*loss_args[:5], pair_grad=PAIRWISE), reps=50)
 else:
     t_loss = timeit(lambda: (ops.crf_loss_grad if PAIRWISE else ops.crf_loss)(*loss_args), reps=50)
@@ -97,6 +122,8 @@ if UNARY != 'patch':
     workload = f'DCNF unary ({UNARY}), batch {B} -> {B} images 240x320x3, {net.P} superpixel rows'
     extra = {'unary': UNARY, 'forward_gflop_per_image': round(gflop_image, 3),
              'patch_form_gflop_per_image': round(2e-9 * 48 * conv_macs(100, 100, 1), 3)}
+if band is not None:
+    extra = {**extra, 'superpixel': SUPERPIXEL, 'band': band}
 if HOLES:
     torch.cuda.synchronize()
     nobs = rep.nobs.cpu().numpy()
