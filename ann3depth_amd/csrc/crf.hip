@@ -4,6 +4,8 @@
 // and, for evaluation, the field's MAP depths A^-1 z (crf_map_kernel), which the reference never forms.
 // A is a constant for the gradient: TF 1.3 registers no gradient for scatter_nd_update (oracle/dcnf.py states the
 // assumption).  All of it is tiny next to the unary conv stack; the kernels are written for clarity, not speed.
+// The three one-wavefront kernels over the system (loss, MAP, observed likelihood) share their steps, the device functions
+// in front of crf_loss_kernel; crf_common.h holds what crf_band.hip uses as well.
 // NON-REFERENCE (include/a3d_pairwise.h, --train-pairwise): the same loss kernel can also carry the identity through its
 // LU and write d loss / d r, the gradient TF 1.3 lacks; pair_dense_bwd_kernel takes it to the pairwise dense layer and
 // sgd_floor_kernel keeps that layer's weights >= 0 (Liu et al. 2015, eq. 9-14).  include/a3d_texture.h
@@ -16,14 +18,9 @@
 #include "a3d_crf_valid.h"
 #include "a3d_pairwise.h"
 #include "a3d_texture.h"
+#include "crf_common.h"
 
 namespace a3d {
-
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
   v = wave_sum_f(v);
@@ -168,20 +165,164 @@ __global__ __launch_bounds__(256) void pair_similarity_kernel(const float* __res
   }
 }
 
-// One wavefront per image.  A = I + D - R from the pair weights, LU with partial pivoting on [A | z] in LDS:
-// det(A) = +-prod(pivots), w = A^-1 z by back substitution; then energy, partition function, loss, d loss / d z.
-// A pair index outside [0, n) is skipped, not used, and turns every image's loss and dz into NaN (as crf_map_kernel).
+// ---------------------------------------------------------------------------------------------------------------------
+// The dense CRF: one wavefront per image, the n x n system A = I + D - R (n <= kMaxSp) in LDS tiles of row width W.  The
+// steps that crf_loss_kernel, crf_map_kernel and crf_observed_kernel share follow, each written once.  A tile that lanes
+// walk both down a column, one row each, and along a row has an odd row stride, so the two walks hit different banks.
+constexpr int kMaxSp = 64;
+
+// v[q] (without v: q itself, as bits) into T[l][r] and T[r][l] in pair order: a later pair overwrites an earlier one, a self
+// pair lands on the diagonal.  True, in every lane, iff a pair has an index outside [0, n): then nothing is scattered and
+// nothing indexed with, for every output of every image is NaN whatever T holds.  The lanes look at all pairs first, so
+// that lane 0's serial loop has no branch that waits for a load.  The caller's barrier comes before T is read.
+template <int W>
+__device__ bool scatter_pairs(float (*T)[W], const float* __restrict__ v, const int* __restrict__ left,
+                              const int* __restrict__ right, int n, int npairs, int lane) {
+  bool outside = false;
+  for (int q = lane; q < npairs; q += 64) {
+    const int l = left[q], rr = right[q];
+    outside = outside || l < 0 || l >= n || rr < 0 || rr >= n;
+  }
+  if (__any(outside)) return true;
+  if (lane == 0)
+    for (int q = 0; q < npairs; ++q) {
+      const int l = left[q], rr = right[q];
+      const float val = v ? v[q] : __int_as_float(q);
+      T[l][rr] = val;
+      T[rr][l] = val;
+    }
+  return false;
+}
+
+// A = I + diag(row sums of R) - R in the n x n corner of T, R scattered from the image's pair weights r: the row sum over
+// ascending columns, 1 + it on the diagonal, 0 - R beside it.  Lane i ends with row i; the caller's barrier comes before
+// anyone reads another row.  Returns scatter_pairs' flag: the index lists are the batch's, so it is every image's.
+template <int W>
+__device__ bool pair_matrix(float (*T)[W], const float* __restrict__ r, const int* __restrict__ left,
+                            const int* __restrict__ right, int n, int npairs, int lane) {
+  for (int i = lane; i < n * n; i += 64) T[i / n][i % n] = 0.f;
+  __syncthreads();
+  const bool bad = scatter_pairs(T, r, left, right, n, npairs, lane);
+  __syncthreads();
+  if (lane < n) {
+    float rs = 0.f;
+    for (int j = 0; j < n; ++j) rs += T[lane][j];
+    for (int j = 0; j < n; ++j) T[lane][j] = (j == lane ? 1.f + rs : 0.f) - T[lane][j];
+  }
+  return bad;
+}
+
+// Row `lane` of an nn x nn system in U gets its right-hand side in column nn and, with `inverse`, its row of the identity
+// in the nn columns behind that: [. | rhs | I].
+template <int W>
+__device__ void augment(float (*U)[W], int nn, int lane, float rhs, bool inverse) {
+  if (lane >= nn) return;
+  U[lane][nn] = rhs;
+  if (inverse)
+    for (int j = 0; j < nn; ++j) U[lane][nn + 1 + j] = j == lane ? 1.f : 0.f;
+}
+
+// Step k's pivot: of rows k .. nn - 1 the one with the largest magnitude in column k, the lowest of equals, a NaN before all
+// (np.argmax's rule, tests/crf_loss_ref.loss32).  It is exchanged with row k over columns 0 .. last; true iff rows moved.
+// Every lane ends with the same row: lane k always offers a value >= 0, the lanes outside [k, nn) offer -1.
+// Left as a NaN, a candidate would compare false with everything: its lane would keep its own row, the others would
+// agree on a row without it, and the lanes would exchange different rows, each in its own columns.  crf_loss_kernel once
+// did; the rule changes none of its results, because with a NaN in column k on or below the diagonal every output of the
+// image was NaN then as it is now.  If it is U[k][k], lane k, which moves column k, keeps row k: the pivot is NaN, and so
+// is det in every lane.  If it is U[i][k], i > k, no other lane can settle on row i, so it stays where it is, row i's
+// multiplier is NaN, and row i is NaN over columns k .. last whatever was exchanged; that repeats at every later step
+// until k = i, the first case.  A NaN det makes fac, Z, u, the loss and every dz NaN, and dr through nan_row.
+template <int W>
+__device__ bool pivot_exchange(float (*U)[W], int k, int nn, int last, int lane) {
+  float best = -1.f;
+  if (lane >= k && lane < nn) {
+    best = fabsf(U[lane][k]);
+    if (!(best == best)) best = INFINITY;
+  }
+  int arg = lane;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ob = __shfl_xor(best, off, 64);
+    const int oa = __shfl_xor(arg, off, 64);
+    if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+  }
+  if (arg != k)
+    for (int j = lane; j <= last; j += 64) { const float t = U[k][j]; U[k][j] = U[arg][j]; U[arg][j] = t; }
+  __syncthreads();
+  return arg != k;
+}
+
+// What an elimination says about its pivots.  The function is inlined: a caller pays for the fields it reads.
+struct Pivots {
+  float det;         // their product, its sign turned at every exchange (the exchange first, then the pivot)
+  float logdet;      // the sum of their logarithms
+  bool positive;     // every one, after its exchange, finite and > 0, and the number of exchanges even
+};
+
+// LU with partial pivoting of the nn x nn system in the leading columns of U, carried over the columns 0 .. last, one lane
+// per row.  Nothing stops at a bad pivot: the values turn into NaN or inf, no index depends on them.  nn = 0: {1, 0, true}.
+template <int W>
+__device__ __forceinline__ Pivots eliminate(float (*U)[W], int nn, int last, int lane) {
+  Pivots p = {1.f, 0.f, true};
+  bool even = true;
+  for (int k = 0; k < nn; ++k) {
+    if (pivot_exchange(U, k, nn, last, lane)) {
+      p.det = -p.det;
+      even = !even;
+    }
+    const float piv = U[k][k];
+    p.det *= piv;
+    p.positive = p.positive && piv > 0.f && piv < INFINITY;
+    p.logdet += logf(piv);
+    if (lane > k && lane < nn) {
+      const float f = U[lane][k] / piv;
+      for (int j = k; j <= last; ++j) U[lane][j] -= f * U[k][j];
+    }
+    __syncthreads();
+  }
+  p.positive = p.positive && even;
+  return p;
+}
+
+// Back substitution after eliminate: x = the solution of column nn (lane 0, serial: 48 x 48 is small), and with `inverse`
+// the nn columns behind it in place, one lane per column.
+template <int W>
+__device__ void back_substitute(float (*U)[W], int nn, int lane, bool inverse, float* x) {
+  if (lane == 0) {
+    for (int i = nn - 1; i >= 0; --i) {
+      float s = U[i][nn];
+      for (int j = i + 1; j < nn; ++j) s -= U[i][j] * x[j];
+      x[i] = s / U[i][i];
+    }
+  }
+  if (inverse && lane < nn) {
+    const int c = nn + 1 + lane;
+    for (int i = nn - 1; i >= 0; --i) {
+      float s = U[i][c];
+      for (int j = i + 1; j < nn; ++j) s -= U[i][j] * U[j][c];
+      U[i][c] = s / U[i][i];
+    }
+  }
+  __syncthreads();
+}
+
+// S = Z[l][l] + Z[r][r] - Z[l][r] - Z[r][l] of the inverse Z that back_substitute left behind column nn, added left to right
+template <int W>
+__device__ float pair_spread(float (*U)[W], int nn, int l, int rr) {
+  const int c = nn + 1;
+  return ((U[l][c + l] + U[rr][c + rr]) - U[l][c + rr]) - U[rr][c + l];
+}
+
+// The reference's loss (src/models.py:129-177): det(A) = +-prod(pivots) and w = A^-1 z from the LU of [A | z]; then energy,
+// partition function, loss, d loss / d z, with the reference's epsilons.  A pair index outside [0, n) turns every image's
+// loss and dz into NaN.
 //
 // kPairGrad (a3dp_crf_loss_grad) also writes dr = d mean loss / d r [batch, npairs], A no longer a constant.  With
-// dA / dr_q = (e_l - e_r)(e_l - e_r)^T:  dE_q = (y_l - y_r)^2,  dg_q = -(w_l - w_r)^2,  d det = det S_q with
-// S_q = A^-1[l][l] + A^-1[r][r] - A^-1[l][r] - A^-1[r][l], hence dfac_q = -fac / (sqrt(det) + eps) (sqrt(det) / 2) S_q.
-// A^-1 comes from the same elimination: U is [A | z | I], the row exchanges and row operations run over all 2n + 1
-// columns, and the n extra columns are back-substituted with one lane per column.  Every operation that feeds the loss
-// and dz is the one the other instantiation performs, in its order: both write the same bits.  The row stride of U is
-// odd there, so lanes that walk a column, one row each, and lanes that walk along a row hit different banks.
-// A pair whose two cells a later pair overwrote has no part in A: its dr is +0.  The scatter notes the last writer of
-// every cell (where the identity will stand, and once A has been read, in A's place).
-constexpr int kMaxSp = 64;
+// dA / dr_q = (e_l - e_r)(e_l - e_r)^T:  dE_q = (y_l - y_r)^2,  dg_q = -(w_l - w_r)^2,  d det = det S_q with S_q =
+// pair_spread of A^-1, hence dfac_q = -fac / (sqrt(det) + eps) (sqrt(det) / 2) S_q.  A^-1 comes from the same elimination:
+// U is [A | z | I].  Every operation that feeds the loss and dz is the one the other instantiation performs, in its order:
+// both write the same bits.  A pair whose two cells a later pair overwrote has no part in A: its dr is +0; once A has
+// been read, the tile holds the last writer of every cell instead.
 template <bool kPairGrad>
 __global__ __launch_bounds__(64) void crf_loss_kernel(const float* __restrict__ z, const float* __restrict__ y,
                                                       const float* __restrict__ r, const int* __restrict__ left,
@@ -191,34 +332,13 @@ __global__ __launch_bounds__(64) void crf_loss_kernel(const float* __restrict__ 
   __shared__ float A[kMaxSp][kMaxSp + 1];
   __shared__ float U[kMaxSp][kPairGrad ? 2 * kMaxSp + 3 : kMaxSp + 2];      // working copy: [A | z] or [A | z | I]
   __shared__ float wv[kMaxSp];
-  __shared__ int bad_index;
   const int b = blockIdx.x, lane = threadIdx.x;
-  const int last = kPairGrad ? 2 * n : n;      // the last column of U in use; column n holds the right-hand side
-  for (int i = lane; i < n * n; i += 64) A[i / n][i % n] = 0.f;
-  __syncthreads();
-  if (lane == 0) {                              // scatter the pair weights in pair order: R[l][r] = R[r][l] = r_q
-    int skipped = 0;
-    for (int q = 0; q < npairs; ++q) {
-      const int l = left[q], rr = right[q];
-      if (l < 0 || l >= n || rr < 0 || rr >= n) { skipped = 1; continue; }     // skipped, never indexed with
-      const float v = r[(size_t)b * npairs + q];
-      A[l][rr] = v;
-      A[rr][l] = v;
-      if (kPairGrad) U[l][n + 1 + rr] = U[rr][n + 1 + l] = __int_as_float(q);      // the last writer of both cells
-    }
-    bad_index = skipped;
-  }
-  __syncthreads();
-  const bool bad = bad_index != 0;              // the index lists are the batch's: every image ends as NaN
-  const float zi = lane < n ? z[(size_t)b * n + lane] : 0.f;
+  const float zi = lane < n ? z[(size_t)b * n + lane] : 0.f;      // on their way while the matrix is built
   const float yi = lane < n ? y[(size_t)b * n + lane] : 0.f;
-  if (lane < n) {                               // A = I + diag(row sums of R) - R
-    float rs = 0.f;
-    for (int j = 0; j < n; ++j) rs += A[lane][j];
-    for (int j = 0; j < n; ++j) A[lane][j] = (j == lane ? 1.f + rs : 0.f) - A[lane][j];
+  const bool bad = pair_matrix(A, r + (size_t)b * npairs, left, right, n, npairs, lane);
+  if (lane < n)
     for (int j = 0; j < n; ++j) U[lane][j] = A[lane][j];
-    U[lane][n] = zi;
-  }
+  augment(U, n, lane, zi, kPairGrad);
   __syncthreads();
   // energy = y^T A y - 2 z^T y + z^T z
   float ay = 0.f;
@@ -226,52 +346,13 @@ __global__ __launch_bounds__(64) void crf_loss_kernel(const float* __restrict__ 
     for (int j = 0; j < n; ++j) ay += A[lane][j] * y[(size_t)b * n + j];
   const float yAy = wave_sum_f(yi * ay), zy = wave_sum_f(zi * yi), zz = wave_sum_f(zi * zi), zsum = wave_sum_f(zi);
   const float energy = yAy - 2.f * zy + zz;
-  if (kPairGrad && lane < n)                    // A has been read (every lane its own row): the writers move there
-    for (int j = 0; j < n; ++j) {
-      A[lane][j] = U[lane][n + 1 + j];
-      U[lane][n + 1 + j] = j == lane ? 1.f : 0.f;
-    }
-  if (kPairGrad) __syncthreads();
-  // LU, one lane per row
-  float det = 1.f;
-  for (int k = 0; k < n; ++k) {
-    float best = (lane >= k && lane < n) ? fabsf(U[lane][k]) : -1.f;
-    int arg = lane;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ob = __shfl_xor(best, off, 64);
-      const int oa = __shfl_xor(arg, off, 64);
-      if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-    }
-    if (arg != k) {
-      for (int j = lane; j <= last; j += 64) { const float t = U[k][j]; U[k][j] = U[arg][j]; U[arg][j] = t; }
-      det = -det;
-    }
+  if (kPairGrad) {                              // A has been read: the last writer of every cell takes its place
     __syncthreads();
-    const float piv = U[k][k];
-    det *= piv;
-    if (lane > k && lane < n) {
-      const float f = U[lane][k] / piv;
-      for (int j = k; j <= last; ++j) U[lane][j] -= f * U[k][j];
-    }
+    scatter_pairs(A, nullptr, left, right, n, npairs, lane);
     __syncthreads();
   }
-  if (lane == 0) {                              // back substitution (48 x 48: serial is fine)
-    for (int i = n - 1; i >= 0; --i) {
-      float s = U[i][n];
-      for (int j = i + 1; j < n; ++j) s -= U[i][j] * wv[j];
-      wv[i] = s / U[i][i];
-    }
-  }
-  if (kPairGrad && lane < n) {                  // lane c: column c of A^-1, in place
-    const int c = n + 1 + lane;
-    for (int i = n - 1; i >= 0; --i) {
-      float s = U[i][c];
-      for (int j = i + 1; j < n; ++j) s -= U[i][j] * U[j][c];
-      U[i][c] = s / U[i][i];
-    }
-  }
-  __syncthreads();
+  const float det = eliminate(U, n, kPairGrad ? 2 * n : n, lane).det;
+  back_substitute(U, n, lane, kPairGrad, wv);   // wv = A^-1 z; A^-1 behind column n
   const float wi = lane < n ? wv[lane] : 0.f;
   // g = z^T (A^-1 + eps) z - z^T z ;  inverseA = inv(A) + eps adds eps to EVERY element (src/models.py:165)
   const float zw = wave_sum_f(zi * wi);
@@ -299,8 +380,7 @@ __global__ __launch_bounds__(64) void crf_loss_kernel(const float* __restrict__ 
         v = 0.f;
         if (__float_as_int(A[l][rr]) == q) {                  // else a later pair overwrote both cells
           const float dy = y[(size_t)b * n + l] - y[(size_t)b * n + rr], dw = wv[l] - wv[rr];
-          const float S = U[l][n + 1 + l] + U[rr][n + 1 + rr] - U[l][n + 1 + rr] - U[rr][n + 1 + l];
-          const float dE = dy * dy, dg = -(dw * dw), dfac = dfac_s * S;
+          const float dE = dy * dy, dg = -(dw * dw), dfac = dfac_s * pair_spread(U, n, l, rr);
           const float du = u * (-dE) - (u / Z) * (dfac * ex + fac * ex * dg);
           v = (-du / (u + eps)) * inv_batch;
         }
@@ -339,64 +419,26 @@ __global__ __launch_bounds__(256) void pair_dense_bwd_kernel(const float* __rest
   if (threadIdx.x == 0) db[0] = accb;
 }
 
-// MAP depths of the same field: y = A^-1 z.  One wavefront per image, [A | z] in LDS (row stride kMaxSp + 1 dwords: odd,
-// so the 32 lanes of an LDS access group hit 32 banks whether they read a column, one row each, or along one row).  LU
-// with the loss kernel's pivot rule; a row is eliminated with one lane per column, and only the rows whose multiplier
-// is not zero are visited: A is sparse (a superpixel has at most four neighbours, fill-in stays inside the band).
+// MAP depths of the same field: y = A^-1 z from [A | z] in one tile.  The shared pivot search and exchange; but a row is
+// eliminated with one lane per column, and only the rows whose multiplier is not zero are visited: A is sparse (a
+// superpixel has at most four neighbours, fill-in stays inside the band).
 // Then a column sweep by the whole wavefront: lane j keeps the right-hand side of row j in a register, and once y[i]
 // is known every lane above subtracts its U[j][i] * y[i] (zero coefficients skipped too: r = 0 returns z's bits).
 // A pivot that is zero or not finite or a non-finite component of the solution turns the image's whole row of y into NaN
-// and its status into 1; nothing traps, other images are not touched.  A pair index outside [0, n) is skipped, not
-// used, and does the same to every image (the index lists are the batch's).
+// and its status into 1; nothing traps, other images are not touched.  A pair index outside [0, n) does the same to
+// every image.
 __global__ __launch_bounds__(64) void crf_map_kernel(const float* __restrict__ z, const float* __restrict__ r,
                                                      const int* __restrict__ left, const int* __restrict__ right,
                                                      float* __restrict__ y, int* __restrict__ status, int n,
                                                      int npairs) {
   __shared__ float U[kMaxSp][kMaxSp + 1];       // column n holds the right-hand side
   const int b = blockIdx.x, lane = threadIdx.x;
-  for (int i = lane; i < n * n; i += 64) U[i / n][i % n] = 0.f;
+  const float zi = lane < n ? z[(size_t)b * n + lane] : 0.f;      // on its way while the matrix is built
+  bool bad = pair_matrix(U, r + (size_t)b * npairs, left, right, n, npairs, lane);
+  augment(U, n, lane, zi, false);
   __syncthreads();
-  bool bad = false;
-  for (int base = 0; base < npairs; base += 64) {       // R[l][r] = R[r][l] = r_q in pair order: a later pair overwrites
-    const int q = base + lane;
-    const bool have = q < npairs;
-    const int lq = have ? left[q] : 0, rq = have ? right[q] : 0;
-    const float vq = have ? r[(size_t)b * npairs + q] : 0.f;
-    const int cnt = min(64, npairs - base);
-    for (int t = 0; t < cnt; ++t) {
-      const int l = __shfl(lq, t, 64), rr = __shfl(rq, t, 64);
-      const float v = __shfl(vq, t, 64);
-      if (l < 0 || l >= n || rr < 0 || rr >= n) { bad = true; continue; }
-      if (lane == 0) {
-        U[l][rr] = v;
-        U[rr][l] = v;
-      }
-    }
-  }
-  __syncthreads();
-  if (lane < n) {                               // A = I + diag(row sums of R) - R, the loss kernel's arithmetic
-    float rs = 0.f;
-    for (int j = 0; j < n; ++j) rs += U[lane][j];
-    for (int j = 0; j < n; ++j) U[lane][j] = (j == lane ? 1.f + rs : 0.f) - U[lane][j];
-    U[lane][n] = z[(size_t)b * n + lane];
-  }
-  __syncthreads();
-  for (int k = 0; k < n && !bad; ++k) {         // `bad` and `arg` are the same in every lane: no divergent barrier
-    float best = -1.f;
-    if (lane >= k && lane < n) {
-      best = fabsf(U[lane][k]);
-      if (!(best == best)) best = INFINITY;     // a NaN is taken as the pivot at once, and ends the image below
-    }
-    int arg = lane;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ob = __shfl_xor(best, off, 64);
-      const int oa = __shfl_xor(arg, off, 64);
-      if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-    }
-    if (arg != k)
-      for (int j = lane; j <= n; j += 64) { const float t = U[k][j]; U[k][j] = U[arg][j]; U[arg][j] = t; }
-    __syncthreads();
+  for (int k = 0; k < n && !bad; ++k) {         // `bad` is the same in every lane: no divergent barrier
+    pivot_exchange(U, k, n, n, lane);           // a NaN is taken as the pivot at once, and ends the image below
     const float piv = U[k][k];
     if (piv == 0.f || !isfinite(piv)) { bad = true; break; }
     const bool below = lane > k && lane < n;
@@ -462,113 +504,33 @@ __global__ __launch_bounds__(256) void superpixel_mean_valid_kernel(const float*
   }
 }
 
-// Elimination of the nn x nn system in the leading columns of U, carried over the columns 0 .. last, one lane per row: the
-// loss kernel's loop and pivot rule (crf_map_kernel's reading of a NaN: taken as the pivot at once).  *logdet = the sum
-// of the logs of the pivots.  True iff every pivot, after its exchange, is finite and > 0 and the number of exchanges is
-// even.  Nothing stops at a bad pivot: the values turn into NaN or inf, no index depends on them.  nn = 0: true, 0.
-template <int W>
-__device__ bool eliminate_positive(float (*U)[W], int nn, int last, int lane, float* logdet) {
-  bool ok = true;
-  float ld = 0.f;
-  int swaps = 0;
-  for (int k = 0; k < nn; ++k) {
-    float best = -1.f;
-    if (lane >= k && lane < nn) {
-      best = fabsf(U[lane][k]);
-      if (!(best == best)) best = INFINITY;
-    }
-    int arg = lane;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ob = __shfl_xor(best, off, 64);
-      const int oa = __shfl_xor(arg, off, 64);
-      if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-    }
-    if (arg != k) {                             // arg is a row in [k, nn): lane k always offers a value >= 0
-      for (int j = lane; j <= last; j += 64) { const float t = U[k][j]; U[k][j] = U[arg][j]; U[arg][j] = t; }
-      ++swaps;
-    }
-    __syncthreads();
-    const float piv = U[k][k];
-    ok = ok && piv > 0.f && piv < INFINITY;
-    ld += logf(piv);
-    if (lane > k && lane < nn) {
-      const float f = U[lane][k] / piv;
-      for (int j = k; j <= last; ++j) U[lane][j] -= f * U[k][j];
-    }
-    __syncthreads();
-  }
-  *logdet = ld;
-  return ok && !(swaps & 1);
-}
-
-// Back substitution after eliminate_positive: x = the solution of column nn (lane 0, serial, as the loss kernel), and with
-// `inverse` the nn columns behind it in place, one lane per column.
-template <int W>
-__device__ void back_substitute(float (*U)[W], int nn, int lane, bool inverse, float* x) {
-  if (lane == 0) {
-    for (int i = nn - 1; i >= 0; --i) {
-      float s = U[i][nn];
-      for (int j = i + 1; j < nn; ++j) s -= U[i][j] * x[j];
-      x[i] = s / U[i][i];
-    }
-  }
-  if (inverse && lane < nn) {
-    const int c = nn + 1 + lane;
-    for (int i = nn - 1; i >= 0; --i) {
-      float s = U[i][c];
-      for (int j = i + 1; j < nn; ++j) s -= U[i][j] * U[j][c];
-      U[i][c] = s / U[i][i];
-    }
-  }
-  __syncthreads();
-}
-
 // One wavefront per image: the negative log-likelihood of the superpixels whose target y is finite (O, m of them; M the
 // others), L = q^T A q + (log det A_MM - log det A) / 2 + m log(pi) / 2 with q = yhat - A^-1 z, yhat = y on O and the
 // conditional mean A_MM^-1 (z_M - A_MO y_O) on M; dz = -2 q / batch; kPairGrad: dr too (include/a3d_crf_valid.h has the
 // derivation).  Two eliminations, one after the other in the same tile U: [A | z | I] and, the missing rows and columns
 // of A moved together in their order, [A_MM | z_M - A_MO y_O | I] (the identity columns only under kPairGrad).  A stays in
-// its own tile for the second system and for q^T A q.
-// LDS: A 64 x 65 floats (16640 bytes), U 64 x 131 (33536; 64 x 67 = 17152 without dr), seven arrays of 64 words and a flag
-// (1796): 51972 bytes under kPairGrad, 35588 without.  Both row strides are odd: lanes that walk a column, one row each,
-// and lanes that walk along a row hit different banks.
+// its own tile for the second system and for q^T A q, and holds the last writer of every cell after that.
+// LDS: A 64 x 65 floats (16640 bytes), U 64 x 131 (33536; 64 x 67 = 17152 without dr), seven arrays of 64 words (1792):
+// 51968 bytes under kPairGrad, 35584 without.
 // y is read once, to tell finite from not; an entry that is not finite is never used again.  dr holds S_k(A^-1) of every
 // pair between the two eliminations (each lane reads back only what it wrote itself).
 // Every index into A, U and the arrays is a lane, a pair index checked against [0, n), a rank below the number of missing
 // superpixels, or a column <= 2 n.
-constexpr float kHalfLogPi = 0.57236494292470009f;
 template <bool kPairGrad>
 __global__ __launch_bounds__(64) void crf_observed_kernel(const float* __restrict__ z, const float* __restrict__ y,
                                                           const float* __restrict__ r, const int* __restrict__ left,
                                                           const int* __restrict__ right, float* __restrict__ loss_img,
                                                           float* __restrict__ dz, float* dr, int* __restrict__ nobs,
                                                           int* __restrict__ status, int n, int npairs, float inv_batch) {
-  constexpr int W = kPairGrad ? 2 * kMaxSp + 3 : kMaxSp + 3;
   __shared__ float A[kMaxSp][kMaxSp + 1];
-  __shared__ float U[kMaxSp][W];
+  __shared__ float U[kMaxSp][kPairGrad ? 2 * kMaxSp + 3 : kMaxSp + 3];
   __shared__ float zs[kMaxSp], yh[kMaxSp], mu[kMaxSp], xm[kMaxSp], qv[kMaxSp];
   __shared__ int mrank[kMaxSp], midx[kMaxSp];
-  __shared__ int bad_index;
   const int b = blockIdx.x, lane = threadIdx.x;
   const float nanf_ = __builtin_nanf("");
-  for (int i = lane; i < n * n; i += 64) A[i / n][i % n] = 0.f;
-  __syncthreads();
-  if (lane == 0) {                              // scatter the pair weights in pair order: R[l][r] = R[r][l] = r_q
-    int skipped = 0;
-    for (int q = 0; q < npairs; ++q) {
-      const int l = left[q], rr = right[q];
-      if (l < 0 || l >= n || rr < 0 || rr >= n) { skipped = 1; continue; }     // skipped, never indexed with
-      const float v = r[(size_t)b * npairs + q];
-      A[l][rr] = v;
-      A[rr][l] = v;
-    }
-    bad_index = skipped;
-  }
-  __syncthreads();
-  const bool bad = bad_index != 0;
-  const float zi = lane < n ? z[(size_t)b * n + lane] : 0.f;
+  const float zi = lane < n ? z[(size_t)b * n + lane] : 0.f;      // on their way while the matrix is built
   const float yraw = lane < n ? y[(size_t)b * n + lane] : 0.f;
+  const bool bad = pair_matrix(A, r + (size_t)b * npairs, left, right, n, npairs, lane);
   const bool obs = lane < n && isfinite(yraw);
   const bool mis = lane < n && !obs;
   const float yi = obs ? yraw : 0.f;            // from here on an unobserved target is not looked at
@@ -592,37 +554,29 @@ __global__ __launch_bounds__(64) void crf_observed_kernel(const float* __restric
     yh[lane] = yi;
     mrank[lane] = mis ? rank : -1;
     if (mis) midx[rank] = lane;
-    float rs = 0.f;                             // A = I + diag(row sums of R) - R, the loss kernel's arithmetic
-    for (int j = 0; j < n; ++j) rs += A[lane][j];
-    for (int j = 0; j < n; ++j) A[lane][j] = (j == lane ? 1.f + rs : 0.f) - A[lane][j];
     for (int j = 0; j < n; ++j) U[lane][j] = A[lane][j];
-    U[lane][n] = zi;
-    if (kPairGrad)
-      for (int j = 0; j < n; ++j) U[lane][n + 1 + j] = j == lane ? 1.f : 0.f;
   }
+  augment(U, n, lane, zi, kPairGrad);
   __syncthreads();
-  float ld_a, ld_m;
-  const bool ok_a = eliminate_positive<W>(U, n, kPairGrad ? 2 * n : n, lane, &ld_a);
-  back_substitute<W>(U, n, lane, kPairGrad, mu);                        // mu = A^-1 z; A^-1 behind column n
+  const Pivots pa = eliminate(U, n, kPairGrad ? 2 * n : n, lane);
+  back_substitute(U, n, lane, kPairGrad, mu);                           // mu = A^-1 z; A^-1 behind column n
   if (kPairGrad) {
-    for (int q = lane; q < npairs; q += 64) {
-      const int l = left[q], rr = right[q];                             // not bad: inside [0, n)
-      dr[(size_t)b * npairs + q] = ((U[l][n + 1 + l] + U[rr][n + 1 + rr]) - U[l][n + 1 + rr]) - U[rr][n + 1 + l];
-    }
+    for (int q = lane; q < npairs; q += 64)                             // not bad: the pairs are inside [0, n)
+      dr[(size_t)b * npairs + q] = pair_spread(U, n, left[q], right[q]);
     __syncthreads();                                                    // A^-1 has been read: U is free
   }
+  float rhs_m = 0.f;
   if (lane < km) {                              // row `lane` of the second system: missing superpixel i = midx[lane]
     const int i = midx[lane];
     for (int c = 0; c < km; ++c) U[lane][c] = A[i][midx[c]];
     float s = 0.f;
     for (int j = 0; j < n; ++j) s += A[i][j] * yh[j];                   // yh = 0 on M: A_MO y_O
-    U[lane][km] = zs[i] - s;
-    if (kPairGrad)
-      for (int c = 0; c < km; ++c) U[lane][km + 1 + c] = c == lane ? 1.f : 0.f;
+    rhs_m = zs[i] - s;
   }
+  augment(U, km, lane, rhs_m, kPairGrad);
   __syncthreads();
-  const bool ok_m = eliminate_positive<W>(U, km, kPairGrad ? 2 * km : km, lane, &ld_m);
-  back_substitute<W>(U, km, lane, kPairGrad, xm);                       // xm = yhat_M; A_MM^-1 behind column km
+  const Pivots pm = eliminate(U, km, kPairGrad ? 2 * km : km, lane);
+  back_substitute(U, km, lane, kPairGrad, xm);                          // xm = yhat_M; A_MM^-1 behind column km
   float qi = 0.f;
   if (lane < n) {
     qi = (obs ? yi : xm[rank]) - mu[lane];
@@ -633,8 +587,8 @@ __global__ __launch_bounds__(64) void crf_observed_kernel(const float* __restric
   if (lane < n)
     for (int j = 0; j < n; ++j) aq += A[lane][j] * qv[j];
   const float qAq = wave_sum_f(qi * aq);
-  const float loss = (qAq + 0.5f * (ld_m - ld_a)) + (float)m * kHalfLogPi;
-  const bool nan_row = !(ok_a && ok_m && isfinite(loss));
+  const float loss = (qAq + 0.5f * (pm.logdet - pa.logdet)) + (float)m * kHalfLogPi;
+  const bool nan_row = !(pa.positive && pm.positive && isfinite(loss));
   if (lane == 0) {
     loss_img[b] = nan_row ? nanf_ : loss;
     nobs[b] = m;
@@ -642,12 +596,8 @@ __global__ __launch_bounds__(64) void crf_observed_kernel(const float* __restric
   }
   if (lane < n) dz[(size_t)b * n + lane] = nan_row ? nanf_ : (-2.f * qi) * inv_batch;
   if (kPairGrad) {
-    __syncthreads();                            // A has been read (every lane its own row): the last writers move there
-    if (lane == 0)
-      for (int q = 0; q < npairs; ++q) {
-        const int l = left[q], rr = right[q];
-        A[l][rr] = A[rr][l] = __int_as_float(q);
-      }
+    __syncthreads();                            // A has been read: the last writer of every cell takes its place
+    scatter_pairs(A, nullptr, left, right, n, npairs, lane);
     __syncthreads();
     for (int q = lane; q < npairs; q += 64) {
       float v = nanf_;
@@ -659,7 +609,7 @@ __global__ __launch_bounds__(64) void crf_observed_kernel(const float* __restric
           const int gl = mrank[l], gr = mrank[rr];
           float s_m = 0.f;                                              // S_k of A_MM^-1 padded with zeros
           if (gl >= 0 && gr >= 0)
-            s_m = ((U[gl][km + 1 + gl] + U[gr][km + 1 + gr]) - U[gl][km + 1 + gr]) - U[gr][km + 1 + gl];
+            s_m = pair_spread(U, km, gl, gr);
           else if (gl >= 0)
             s_m = U[gl][km + 1 + gl];
           else if (gr >= 0)
@@ -671,13 +621,6 @@ __global__ __launch_bounds__(64) void crf_observed_kernel(const float* __restric
       dr[(size_t)b * npairs + q] = v;
     }
   }
-}
-
-__global__ __launch_bounds__(64) void mean_kernel(const float* __restrict__ v, int n, float* __restrict__ out) {
-  float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += 64) s += v[i];
-  s = wave_sum_f(s);
-  if (threadIdx.x == 0) out[0] = s / (float)n;
 }
 
 // tf.train.GradientDescentOptimizer(lr) (src/models.py:198): var -= lr * g

@@ -30,7 +30,7 @@
 //   12 x 16 (band 16, stride 18): 192 x 18 x 4 + 1536 =  15 360 bytes
 //   24 x 32 (band 32, stride 34): 768 x 34 x 4 + 6144 = 110 592 bytes      (the maxima; 160 KiB per CU: one workgroup)
 // Compiler's resource report for gfx950 (-Rpass-analysis=kernel-resource-usage): crf_band_kernel<false> (nll) 50 VGPRs,
-// crf_band_kernel<true> (map) 26 VGPRs, band_mean_kernel 7 VGPRs; scratch 0 bytes, no spills in all three.
+// crf_band_kernel<true> (map) 26 VGPRs, mean_kernel (crf_common.h) 7 VGPRs; scratch 0 bytes, no spills in all three.
 //
 // Every loop bound is a function of nsp, band, npairs and the thread alone; no trip count, branch or index depends on a
 // value of z, y or r.  A bad pivot turns values into NaN or inf and nothing else.  Indices into S: a column c < nsp with an
@@ -39,6 +39,7 @@
 // workgroups, no float atomics: the only atomic is an integer max in LDS that finds the last writer of a cell.
 #include "a3d_internal.h"
 #include "a3d_crf_band.h"
+#include "crf_common.h"
 
 #ifndef A3DB_THREADS
 #define A3DB_THREADS 256
@@ -49,15 +50,13 @@ namespace {
 
 constexpr int kThreads = A3DB_THREADS;
 constexpr int kWaves = kThreads / 64;
-constexpr float kHalfLogPi = 0.57236494292470009f;
 static_assert(kThreads % 64 == 0 && kThreads >= 64 && kThreads <= 1024, "whole wavefronts");
 
 __host__ __device__ constexpr int band_stride(int band) { return (band + 2) & ~1; }
 
 // the sum over the workgroup in a fixed order: xor butterfly inside a wavefront, then the wavefronts in turn
 __device__ __forceinline__ float band_block_sum(float v, float* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  v = wave_sum_f(v);
   if (kWaves == 1) return v;
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -239,14 +238,6 @@ __global__ __launch_bounds__(kThreads) void crf_band_kernel(const float* __restr
   }
 }
 
-__global__ __launch_bounds__(64) void band_mean_kernel(const float* __restrict__ v, int n, float* __restrict__ out) {
-  float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += 64) s += v[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-  if (threadIdx.x == 0) out[0] = s / (float)n;
-}
-
 size_t band_lds_bytes(int nsp, int band) { return ((size_t)nsp * band_stride(band) + 2 * (size_t)nsp) * sizeof(float); }
 static_assert(((size_t)A3DB_MAX_SP * band_stride(A3DB_MAX_BAND) + 2 * (size_t)A3DB_MAX_SP) * sizeof(float) + 2048 <= 160 * 1024,
               "the maxima fit one CU's LDS");
@@ -285,7 +276,7 @@ int a3db_crf_band_nll(int n, int nsp, int band, const float* z, const float* y, 
                               "crf_band_nll");
   if (rc != A3D_OK) return rc;
   clear_stale_error();
-  hipLaunchKernelGGL(band_mean_kernel, dim3(1), dim3(64), 0, st, loss_per_image, n, loss_mean);
+  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(64), 0, st, loss_per_image, n, loss_mean);
   return check_launch("crf_band_nll_mean");
 }
 

@@ -1606,47 +1606,43 @@ class DCNFReplica:
 
     def forward_crf(self, depths):
         """Everything after the unary stack: target superpixels, pairwise r, CRF loss and d loss / d z."""
-        u = self.unary
-        if self.valid_range is not None:
-            self._pairwise()
-            self.loss = self._observed(depths, self.B, self.valid_range, self.train_pairwise)
-            return self.loss
-        ops.resize_bilinear_tf1(depths, self.depths240)                                   # src/models.py:181
+        self._targets(depths, self.B, self.valid_range)
         self._pairwise()
-        ops.superpixel_mean(self.depths240, self.sp, self.y)                              # :131-132
-        if self.banded:
-            self.loss, self.loss_per_image, self.dz, self.dr = self._banded(self.B, self.train_pairwise)
-            return self.loss
-        crf_args = (u.z.view(self.B, self.nsp), self.y.view(self.B, self.nsp), self.r, self.left, self.right, DCNF_EPSILON)
-        if self.train_pairwise:                                                           # one launch, not two
-            self.loss, self.loss_per_image, self.dz, self.dr = ops.crf_loss_grad(*crf_args)
-        else:
-            self.loss, self.loss_per_image, self.dz = ops.crf_loss(*crf_args)             # :129-177
+        self.loss, self.loss_per_image, self.dz, self.dr = self._objective(self.B, self.valid_range, self.train_pairwise)
         return self.loss
 
-    def _banded(self, n, pair_grad):
-        """superpixel 20 / 10: the banded likelihood on rows [0, n) from the z, y and r that stand in the buffers: (mean [1],
-        per image, dz, dr or None without pair_grad); leaves the status of those rows in self.status."""
-        mean, per, dz, dr, _, status = ops.crf_band_nll(
-            self.unary.z.view(self.B, self.nsp)[:n], self.y.view(self.B, self.nsp)[:n], self.r[:n], self.left, self.right,
-            self.band, pair_grad=pair_grad)
-        self.status[:n].copy_(status)
-        return mean, per, dz, dr
-
-    def _observed(self, depths, n, valid_range, pair_grad):
-        """valid_range's objective on rows [0, n) from the z and r that stand in the buffers: the targets through the
-        validity-aware resize and superpixel mean, then the likelihood of the observed superpixels.  Leaves loss_per_image,
-        dz, dr (None without pair_grad), nobs and status of those rows; returns the mean [1]."""
+    def _targets(self, depths, n, valid_range):
+        """The target superpixels of rows [0, n) into self.y: the means over the resized depth maps' blocks
+        (src/models.py:181,131-132); with valid_range through the validity-aware resize and mean, NaN where a superpixel
+        is no target, the numbers of measured pixels in self.count."""
+        if valid_range is None:
+            ops.resize_bilinear_tf1(depths[:n], self.depths240[:n])
+            ops.superpixel_mean(self.depths240[:n], self.sp, self.y[:n])
+            return
         if self.t_one is None:
             self.t_one = torch.empty((self.B, 1, 1, 1), device=self.device)
             self.count = torch.empty((self.B, self.nsp), dtype=torch.int32, device=self.device)
         lo, hi = valid_range
-        y = self.y.view(self.B, self.nsp)
         ops.resize_bilinear_tf1_valid(depths[:n], self.depths240[:n], lo, hi, scratch=self.t_one[:n])
-        ops.superpixel_mean_valid(self.depths240[:n], self.sp, self.min_count, out=y[:n], count=self.count[:n])
-        mean, self.loss_per_image, self.dz, self.dr, self.nobs, self.status_observed = ops.crf_loss_observed(
-            self.unary.z.view(self.B, self.nsp)[:n], y[:n], self.r[:n], self.left, self.right, pair_grad=pair_grad)
-        return mean
+        ops.superpixel_mean_valid(self.depths240[:n], self.sp, self.min_count, out=self.y.view(self.B, self.nsp)[:n],
+                                  count=self.count[:n])
+
+    def _objective(self, n, valid_range, pair_grad):
+        """The objective on rows [0, n) of the z, y and r that stand in the buffers, in one launch: (mean [1], per image,
+        dz, dr or None without pair_grad).  With valid_range the likelihood of the observed superpixels, which leaves
+        self.nobs and self.status_observed; on the banded CRF its likelihood, which leaves those rows of self.status;
+        else the reference's loss (src/models.py:129-177)."""
+        args = (self.unary.z.view(self.B, self.nsp)[:n], self.y.view(self.B, self.nsp)[:n], self.r[:n], self.left, self.right)
+        if valid_range is not None:
+            mean, per, dz, dr, self.nobs, self.status_observed = ops.crf_loss_observed(*args, pair_grad=pair_grad)
+        elif self.banded:
+            mean, per, dz, dr, _, status = ops.crf_band_nll(*args, self.band, pair_grad=pair_grad)
+            self.status[:n].copy_(status)
+        elif pair_grad:
+            mean, per, dz, dr = ops.crf_loss_grad(*args, DCNF_EPSILON)
+        else:
+            (mean, per, dz), dr = ops.crf_loss(*args, DCNF_EPSILON), None
+        return mean, per, dz, dr
 
     def predict(self, images, n=None):
         """The model's depths for a batch of images, without targets: (unary, crf), each [B, rows, cols] float32 (views
@@ -1681,17 +1677,10 @@ class DCNFReplica:
         if self.r is None or not 0 < n <= min(self.B, depths.shape[0]):
             raise ValueError(f'nll: n = {n} rows of {depths.shape[0]} depth maps, replica batch {self.B}, after predict()')
         valid_range = self.valid_range if valid_range is None else valid_range
-        if valid_range is not None:
-            if self.banded:
-                raise ValueError(f'nll: superpixel {self.sp} has no likelihood of observed superpixels alone yet (valid_range)')
-            return self._observed(depths, n, valid_range, False)
-        ops.resize_bilinear_tf1(depths[:n], self.depths240[:n])                           # src/models.py:181
-        ops.superpixel_mean(self.depths240[:n], self.sp, self.y[:n])                      # :131-132
-        if self.banded:
-            return self._banded(n, False)[0]
-        mean, _, _ = ops.crf_loss(self.unary.z.view(self.B, self.nsp)[:n], self.y.view(self.B, self.nsp)[:n],
-                                  self.r[:n], self.left, self.right, DCNF_EPSILON)
-        return mean
+        if valid_range is not None and self.banded:
+            raise ValueError(f'nll: superpixel {self.sp} has no likelihood of observed superpixels alone yet (valid_range)')
+        self._targets(depths, n, valid_range)
+        return self._objective(n, valid_range, False)[0]
 
     def step(self, images, depths, keep_mask=None):
         self.forward(images, depths)

@@ -684,38 +684,33 @@ def superpixel_mean(x, sp, out=None):
     return out
 
 
+def _check_operands(who, f32, i32, names):
+    """TypeError unless the tensors of f32 are float32 and those of i32 int32; ValueError unless all are contiguous and on
+    one device."""
+    if any(t.dtype != torch.float32 for t in f32) or any(t.dtype != torch.int32 for t in i32):
+        raise TypeError(f'{who}: {names}')
+    if not all(t.is_contiguous() for t in (*f32, *i32)):
+        raise ValueError(f'{who}: contiguous tensors only')
+    if any(t.device != f32[0].device for t in (*f32, *i32)):
+        raise ValueError(f'{who}: all tensors on one device')
+
+
+def _check_superpixels(who, x, sp, channels, max_sp=None):
+    """(n, h, w, P) of a non-empty image batch x [n, h, w, channels] cut into P superpixels of edge sp, or ValueError."""
+    if (x.dim() != 4 or x.shape[3] != channels or sp <= 0 or (max_sp is not None and sp > max_sp) or x.shape[1] % sp
+            or x.shape[2] % sp or x.numel() == 0):
+        raise ValueError(f'{who}: x {tuple(x.shape)} is not a non-empty [n, h, w, {channels}] with h, w multiples of '
+                         f'sp = {sp}' + (f' <= {max_sp}' if max_sp is not None else ''))
+    n, h, w, _ = x.shape
+    return n, h, w, (h // sp) * (w // sp)
+
+
 def superpixel_hist(x, sp, out=None):
     """color_histogram of every superpixel (src/models.py:95-100): [n,h,w,3] -> [n,P,256]."""
-    n, h, w, c = x.shape
-    assert c == 3
-    out = out if out is not None else torch.empty((n, (h // sp) * (w // sp), 256), dtype=torch.float32, device=x.device)
+    n, h, w, nsp = _check_superpixels('superpixel_hist', x, sp, 3)
+    out = out if out is not None else torch.empty((n, nsp, 256), dtype=torch.float32, device=x.device)
     check(_lib.load().a3d_superpixel_hist(n, h, w, _ptr(x), sp, _ptr(out), _stream()), 'a3d_superpixel_hist')
     return out
-
-
-def pair_similarity(x, sp, hist, left, right, dense_w, dense_b, gamma=1.0):
-    """pairwise_part (src/models.py:108-127): returns (sims [n,Q,2], r [n,Q]).  x [n,h,w,3], hist [n,P,256] float32;
-    left, right [Q] int32; dense_w 2 and dense_b 1 float32 values.  A pair with an index outside [0, P) gets NaN."""
-    if x.dim() != 4 or x.shape[3] != 3 or sp <= 0 or x.shape[1] % sp or x.shape[2] % sp:
-        raise ValueError(f'pair_similarity: x {tuple(x.shape)} is not [n, h, w, 3] with h, w multiples of sp = {sp}')
-    n, h, w, _ = x.shape
-    q = left.numel()
-    if (n == 0 or q == 0 or right.numel() != q or tuple(hist.shape) != (n, (h // sp) * (w // sp), 256)
-            or dense_w.numel() != 2 or dense_b.numel() != 1):
-        raise ValueError(f'pair_similarity: x {tuple(x.shape)}, sp {sp}, hist {tuple(hist.shape)}, {q} / '
-                         f'{right.numel()} pair indices, dense kernel {tuple(dense_w.shape)}, bias {tuple(dense_b.shape)}')
-    if (any(t.dtype != torch.float32 for t in (x, hist, dense_w, dense_b)) or left.dtype != torch.int32
-            or right.dtype != torch.int32):
-        raise TypeError('pair_similarity: x, hist, dense_w, dense_b float32; left, right int32')
-    if not all(t.is_contiguous() for t in (x, hist, left, right, dense_w, dense_b)):
-        raise ValueError('pair_similarity: contiguous tensors only')
-    if any(t.device != x.device for t in (hist, left, right, dense_w, dense_b)):
-        raise ValueError('pair_similarity: all tensors on one device')
-    sims = torch.empty((n, q, 2), dtype=torch.float32, device=x.device)
-    r = torch.empty((n, q), dtype=torch.float32, device=x.device)
-    check(_lib.load().a3d_pair_similarity(n, h, w, _ptr(x), sp, _ptr(hist), _ptr(left), _ptr(right), q, _ptr(dense_w),
-                                          _ptr(dense_b), gamma, _ptr(sims), _ptr(r), _stream()), 'a3d_pair_similarity')
-    return sims, r
 
 
 TEXTURE_MAX_SP = 53      # A3DT_MAX_SP: the texture similarity's sum of squared count differences stays below 2^24
@@ -725,24 +720,41 @@ def superpixel_lbp_hist(x, sp, out=None):
     """NON-REFERENCE (a3dt_superpixel_lbp_hist): local-binary-pattern histogram of every superpixel, [n,h,w,3] float32 ->
     [n,P,256] float32 integer counts (each superpixel's sum to sp * sp).  Neighbours are read from the image, across
     superpixel borders, clamped at the image border; sp <= 53."""
-    if x.dim() != 4 or x.shape[3] != 3 or not 0 < sp <= TEXTURE_MAX_SP or x.shape[1] % sp or x.shape[2] % sp:
-        raise ValueError(f'superpixel_lbp_hist: x {tuple(x.shape)} is not [n, h, w, 3] with h, w multiples of sp = {sp} '
-                         f'<= {TEXTURE_MAX_SP}')
-    n, h, w, _ = x.shape
-    shape = (n, (h // sp) * (w // sp), 256)
-    if n == 0 or h == 0 or w == 0:
-        raise ValueError(f'superpixel_lbp_hist: x {tuple(x.shape)} is empty')
-    out = out if out is not None else torch.empty(shape, dtype=torch.float32, device=x.device)
-    if tuple(out.shape) != shape:
-        raise ValueError(f'superpixel_lbp_hist: out {tuple(out.shape)} for x {tuple(x.shape)}, sp {sp} must be {shape}')
-    if x.dtype != torch.float32 or out.dtype != torch.float32:
-        raise TypeError('superpixel_lbp_hist: x, out float32')
-    if not (x.is_contiguous() and out.is_contiguous()):
-        raise ValueError('superpixel_lbp_hist: contiguous tensors only')
-    if out.device != x.device:
-        raise ValueError('superpixel_lbp_hist: all tensors on one device')
+    n, h, w, nsp = _check_superpixels('superpixel_lbp_hist', x, sp, 3, TEXTURE_MAX_SP)
+    out = out if out is not None else torch.empty((n, nsp, 256), dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != (n, nsp, 256):
+        raise ValueError(f'superpixel_lbp_hist: out {tuple(out.shape)} for x {tuple(x.shape)}, sp {sp} must be '
+                         f'{(n, nsp, 256)}')
+    _check_operands('superpixel_lbp_hist', (x, out), (), 'x, out float32')
     check(_lib.load().a3dt_superpixel_lbp_hist(n, h, w, _ptr(x), sp, _ptr(out), _stream()), 'a3dt_superpixel_lbp_hist')
     return out
+
+
+def _pair_similarity(who, x, sp, hists, left, right, dense_w, dense_b, gamma, max_sp=None):
+    """pair_similarity (hists: the colour histograms) and pair_similarity3 (and the LBP histograms): one similarity from
+    the image and one from each of hists, all [n,P,256]."""
+    n, h, w, nsp = _check_superpixels(who, x, sp, 3, max_sp)
+    q, k = left.numel(), 1 + len(hists)
+    if (q == 0 or right.numel() != q or any(tuple(t.shape) != (n, nsp, 256) for t in hists) or dense_w.numel() != k
+            or dense_b.numel() != 1):
+        raise ValueError(f'{who}: x {tuple(x.shape)}, sp {sp}, histograms {[tuple(t.shape) for t in hists]}, {q} / '
+                         f'{right.numel()} pair indices, dense kernel {tuple(dense_w.shape)}, bias {tuple(dense_b.shape)}')
+    _check_operands(who, (x, *hists, dense_w, dense_b), (left, right),
+                    'x, hist, lbp_hist, dense_w, dense_b float32; left, right int32')
+    sims = torch.empty((n, q, k), dtype=torch.float32, device=x.device)
+    r = torch.empty((n, q), dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    fn, name = (lib.a3d_pair_similarity, 'a3d_pair_similarity') if k == 2 else (lib.a3dt_pair_similarity3,
+                                                                                'a3dt_pair_similarity3')
+    check(fn(n, h, w, _ptr(x), sp, *(_ptr(t) for t in hists), _ptr(left), _ptr(right), q, _ptr(dense_w), _ptr(dense_b),
+             gamma, _ptr(sims), _ptr(r), _stream()), name)
+    return sims, r
+
+
+def pair_similarity(x, sp, hist, left, right, dense_w, dense_b, gamma=1.0):
+    """pairwise_part (src/models.py:108-127): returns (sims [n,Q,2], r [n,Q]).  x [n,h,w,3], hist [n,P,256] float32;
+    left, right [Q] int32; dense_w 2 and dense_b 1 float32 values.  A pair with an index outside [0, P) gets NaN."""
+    return _pair_similarity('pair_similarity', x, sp, (hist,), left, right, dense_w, dense_b, gamma)
 
 
 def pair_similarity3(x, sp, hist, lbp_hist, left, right, dense_w, dense_b, gamma=1.0):
@@ -750,82 +762,54 @@ def pair_similarity3(x, sp, hist, lbp_hist, left, right, dense_w, dense_b, gamma
     third: returns (sims [n,Q,3], r [n,Q]); sims[..., :2] are pair_similarity's bits.  x [n,h,w,3], hist and lbp_hist
     [n,P,256] float32; left, right [Q] int32; dense_w 3 and dense_b 1 float32 values.  A pair with an index outside
     [0, P) gets NaN."""
-    if x.dim() != 4 or x.shape[3] != 3 or not 0 < sp <= TEXTURE_MAX_SP or x.shape[1] % sp or x.shape[2] % sp:
-        raise ValueError(f'pair_similarity3: x {tuple(x.shape)} is not [n, h, w, 3] with h, w multiples of sp = {sp} '
-                         f'<= {TEXTURE_MAX_SP}')
-    n, h, w, _ = x.shape
-    q = left.numel()
-    hshape = (n, (h // sp) * (w // sp), 256)
-    if (n == 0 or h == 0 or w == 0 or q == 0 or right.numel() != q or tuple(hist.shape) != hshape
-            or tuple(lbp_hist.shape) != hshape or dense_w.numel() != 3 or dense_b.numel() != 1):
-        raise ValueError(f'pair_similarity3: x {tuple(x.shape)}, sp {sp}, hist {tuple(hist.shape)}, lbp_hist '
-                         f'{tuple(lbp_hist.shape)}, {q} / {right.numel()} pair indices, dense kernel '
-                         f'{tuple(dense_w.shape)}, bias {tuple(dense_b.shape)}')
-    if (any(t.dtype != torch.float32 for t in (x, hist, lbp_hist, dense_w, dense_b)) or left.dtype != torch.int32
-            or right.dtype != torch.int32):
-        raise TypeError('pair_similarity3: x, hist, lbp_hist, dense_w, dense_b float32; left, right int32')
-    if not all(t.is_contiguous() for t in (x, hist, lbp_hist, left, right, dense_w, dense_b)):
-        raise ValueError('pair_similarity3: contiguous tensors only')
-    if any(t.device != x.device for t in (hist, lbp_hist, left, right, dense_w, dense_b)):
-        raise ValueError('pair_similarity3: all tensors on one device')
-    sims = torch.empty((n, q, 3), dtype=torch.float32, device=x.device)
-    r = torch.empty((n, q), dtype=torch.float32, device=x.device)
-    check(_lib.load().a3dt_pair_similarity3(n, h, w, _ptr(x), sp, _ptr(hist), _ptr(lbp_hist), _ptr(left), _ptr(right), q,
-                                            _ptr(dense_w), _ptr(dense_b), gamma, _ptr(sims), _ptr(r), _stream()),
-          'a3dt_pair_similarity3')
-    return sims, r
+    return _pair_similarity('pair_similarity3', x, sp, (hist, lbp_hist), left, right, dense_w, dense_b, gamma,
+                            TEXTURE_MAX_SP)
+
+
+def _check_crf(who, z, r, left, right, others):
+    """(n, P) of a CRF call, or ValueError / TypeError: z [n,P], r [n,Q] and every tensor of `others` [n,P] float32; left,
+    right [Q] int32, Q > 0; all contiguous and on one device."""
+    if z.dim() != 2 or r.dim() != 2:
+        raise ValueError(f'{who}: z {tuple(z.shape)} and r {tuple(r.shape)} must be [n, P] and [n, Q]')
+    n, nsp = z.shape[0], z.shape[1]
+    if (n == 0 or r.shape[0] != n or left.numel() == 0 or r.shape[1] != left.numel() or left.numel() != right.numel()
+            or any(tuple(t.shape) != (n, nsp) for t in others)):
+        raise ValueError(f'{who}: z {tuple(z.shape)}, {[tuple(t.shape) for t in others]}, r {tuple(r.shape)}, '
+                         f'{left.numel()} / {right.numel()} pair indices')
+    _check_operands(who, (z, r, *others), (left, right), 'z, y, r, mu float32; left, right int32')
+    return n, nsp
+
+
+def _crf_outputs(z, r, pair_grad):
+    """What every CRF objective writes: (per-image [n], mean [1], dz [n,P], dr [n,Q] or None without pair_grad)."""
+    n, nsp = z.shape
+    return (torch.empty((n,), dtype=torch.float32, device=z.device), torch.empty((1,), dtype=torch.float32, device=z.device),
+            torch.empty((n, nsp), dtype=torch.float32, device=z.device), torch.empty_like(r) if pair_grad else None)
+
+
+def _crf_loss(who, z, y, r, left, right, eps, pair_grad):
+    n, nsp = _check_crf(who, z, r, left, right, (y,))
+    per, mean, dz, dr = _crf_outputs(z, r, pair_grad)
+    lib = _lib.load()
+    args = (n, nsp, _ptr(z), _ptr(y), _ptr(r), _ptr(left), _ptr(right), left.numel(), eps, _ptr(per), _ptr(mean), _ptr(dz))
+    if pair_grad:
+        check(lib.a3dp_crf_loss_grad(*args, _ptr(dr), _stream()), 'a3dp_crf_loss_grad')
+        return mean, per, dz, dr
+    check(lib.a3d_crf_loss(*args, _stream()), 'a3d_crf_loss')
+    return mean, per, dz
 
 
 def crf_loss(z, y, r, left, right, eps=1e-7):
     """loss_part (src/models.py:129-177): returns (mean loss [1], per-image loss [n], d mean / d z [n,P]).  z, y [n,P],
     r [n,Q] float32; left, right [Q] int32.  A pair index outside [0, P) turns every loss and all of dz into NaN."""
-    if z.dim() != 2 or r.dim() != 2:
-        raise ValueError(f'crf_loss: z {tuple(z.shape)} and r {tuple(r.shape)} must be [n, P] and [n, Q]')
-    n, nsp = z.shape[0], z.shape[1]
-    if (n == 0 or tuple(y.shape) != (n, nsp) or r.shape[0] != n or left.numel() == 0 or r.shape[1] != left.numel()
-            or left.numel() != right.numel()):
-        raise ValueError(f'crf_loss: z {tuple(z.shape)}, y {tuple(y.shape)}, r {tuple(r.shape)}, {left.numel()} / '
-                         f'{right.numel()} pair indices')
-    if (z.dtype != torch.float32 or y.dtype != torch.float32 or r.dtype != torch.float32 or left.dtype != torch.int32
-            or right.dtype != torch.int32):
-        raise TypeError('crf_loss: z, y, r float32; left, right int32')
-    if not all(t.is_contiguous() for t in (z, y, r, left, right)):
-        raise ValueError('crf_loss: contiguous tensors only')
-    if any(t.device != z.device for t in (y, r, left, right)):
-        raise ValueError('crf_loss: all tensors on one device')
-    per = torch.empty((n,), dtype=torch.float32, device=z.device)
-    mean = torch.empty((1,), dtype=torch.float32, device=z.device)
-    dz = torch.empty((n, nsp), dtype=torch.float32, device=z.device)
-    check(_lib.load().a3d_crf_loss(n, nsp, _ptr(z), _ptr(y), _ptr(r), _ptr(left), _ptr(right), left.numel(), eps,
-                                   _ptr(per), _ptr(mean), _ptr(dz), _stream()), 'a3d_crf_loss')
-    return mean, per, dz
+    return _crf_loss('crf_loss', z, y, r, left, right, eps, False)
 
 
 def crf_loss_grad(z, y, r, left, right, eps=1e-7):
     """NON-REFERENCE (a3dp_crf_loss_grad): crf_loss with the CRF matrix no longer a constant: returns (mean loss [1],
     per-image loss [n], d mean / d z [n,P], d mean / d r [n,Q]), the first three the bits crf_loss returns.  A pair index
     outside [0, P) turns all of it into NaN; a pair that a later pair overwrote has a gradient of +0."""
-    if z.dim() != 2 or r.dim() != 2:
-        raise ValueError(f'crf_loss_grad: z {tuple(z.shape)} and r {tuple(r.shape)} must be [n, P] and [n, Q]')
-    n, nsp = z.shape[0], z.shape[1]
-    if (n == 0 or tuple(y.shape) != (n, nsp) or r.shape[0] != n or left.numel() == 0 or r.shape[1] != left.numel()
-            or left.numel() != right.numel()):
-        raise ValueError(f'crf_loss_grad: z {tuple(z.shape)}, y {tuple(y.shape)}, r {tuple(r.shape)}, {left.numel()} / '
-                         f'{right.numel()} pair indices')
-    if (z.dtype != torch.float32 or y.dtype != torch.float32 or r.dtype != torch.float32 or left.dtype != torch.int32
-            or right.dtype != torch.int32):
-        raise TypeError('crf_loss_grad: z, y, r float32; left, right int32')
-    if not all(t.is_contiguous() for t in (z, y, r, left, right)):
-        raise ValueError('crf_loss_grad: contiguous tensors only')
-    if any(t.device != z.device for t in (y, r, left, right)):
-        raise ValueError('crf_loss_grad: all tensors on one device')
-    per = torch.empty((n,), dtype=torch.float32, device=z.device)
-    mean = torch.empty((1,), dtype=torch.float32, device=z.device)
-    dz = torch.empty((n, nsp), dtype=torch.float32, device=z.device)
-    dr = torch.empty_like(r)
-    check(_lib.load().a3dp_crf_loss_grad(n, nsp, _ptr(z), _ptr(y), _ptr(r), _ptr(left), _ptr(right), left.numel(), eps,
-                                         _ptr(per), _ptr(mean), _ptr(dz), _ptr(dr), _stream()), 'a3dp_crf_loss_grad')
-    return mean, per, dz, dr
+    return _crf_loss('crf_loss_grad', z, y, r, left, right, eps, True)
 
 
 def pair_dense_bwd(sims, dr, dw, db):
@@ -837,12 +821,7 @@ def pair_dense_bwd(sims, dr, dw, db):
     k = sims.shape[2]
     if not 1 <= k <= 8 or dw.numel() != k or db.numel() != 1:
         raise ValueError(f'pair_dense_bwd: {k} similarities per pair (1 .. 8), dw {tuple(dw.shape)}, db {tuple(db.shape)}')
-    if any(t.dtype != torch.float32 for t in (sims, dr, dw, db)):
-        raise TypeError('pair_dense_bwd: sims, dr, dw, db float32')
-    if not all(t.is_contiguous() for t in (sims, dr, dw, db)):
-        raise ValueError('pair_dense_bwd: contiguous tensors only')
-    if any(t.device != sims.device for t in (dr, dw, db)):
-        raise ValueError('pair_dense_bwd: all tensors on one device')
+    _check_operands('pair_dense_bwd', (sims, dr, dw, db), (), 'sims, dr, dw, db float32')
     check(_lib.load().a3dp_pair_dense_bwd(dr.shape[0], dr.shape[1], k, _ptr(sims), _ptr(dr), _ptr(dw), _ptr(db), _stream()),
           'a3dp_pair_dense_bwd')
     return dw, db
@@ -851,21 +830,13 @@ def pair_dense_bwd(sims, dr, dw, db):
 def crf_map(z, r, left, right, y=None, status=None):
     """The field's MAP depths y = A^-1 z, A = I + D - R from the pair weights r (a3d_crf_map): z [n,P], r [n,Q] ->
     (y [n,P] float32, status [n] int32; 1 where the image's system was singular or not finite and its row of y is NaN)."""
-    n, nsp = z.shape[0], z.shape[1]
-    if r.shape[0] != n or r[0].numel() != left.numel() or left.numel() != right.numel():
-        raise ValueError(f'crf_map: z {tuple(z.shape)}, r {tuple(r.shape)}, {left.numel()} / {right.numel()} pair indices')
-    if z.dtype != torch.float32 or r.dtype != torch.float32 or left.dtype != torch.int32 or right.dtype != torch.int32:
-        raise TypeError('crf_map: z, r float32; left, right int32')
-    y = y if y is not None else torch.empty((n, nsp), dtype=torch.float32, device=z.device)
+    y = y if y is not None else torch.empty_like(z)
+    n, nsp = _check_crf('crf_map', z, r, left, right, (y,))
     status = status if status is not None else torch.empty((n,), dtype=torch.int32, device=z.device)
-    if y.dtype != torch.float32 or status.dtype != torch.int32:
+    if status.dtype != torch.int32:
         raise TypeError('crf_map: y float32, status int32')
-    if tuple(y.shape) != (n, nsp) or status.numel() != n:
-        raise ValueError(f'crf_map: y {tuple(y.shape)} / status {tuple(status.shape)} for {n} images of {nsp} superpixels')
-    if not all(t.is_contiguous() for t in (z, r, left, right, y, status)):
-        raise ValueError('crf_map: contiguous tensors only')
-    if any(t.device != z.device for t in (r, left, right, y, status)):
-        raise ValueError('crf_map: all tensors on one device')
+    if status.numel() != n or not status.is_contiguous() or status.device != z.device:
+        raise ValueError(f'crf_map: status {tuple(status.shape)} on {status.device} for {n} images on {z.device}')
     check(_lib.load().a3d_crf_map(n, nsp, _ptr(z), _ptr(r), _ptr(left), _ptr(right), left.numel(), _ptr(y), _ptr(status),
                                   _stream()), 'a3d_crf_map')
     return y, status
@@ -876,22 +847,14 @@ def superpixel_mean_valid(x, sp, min_count=0, out=None, count=None):
     with NaN (or an infinity) where nothing was measured -> (y [n,P] float32, count [n,P] int32): per superpixel the number
     of finite pixels and their mean, NaN where fewer than max(1, min_count) are finite.  With every pixel finite y is
     superpixel_mean's bits."""
-    if x.dim() != 4 or x.shape[3] != 1 or sp <= 0 or x.shape[1] % sp or x.shape[2] % sp or x.numel() == 0:
-        raise ValueError(f'superpixel_mean_valid: x {tuple(x.shape)} is not [n, h, w, 1] with h, w multiples of sp = {sp}')
+    n, h, w, nsp = _check_superpixels('superpixel_mean_valid', x, sp, 1)
     if min_count < 0:
         raise ValueError(f'superpixel_mean_valid: min_count {min_count}')
-    n, h, w, _ = x.shape
-    shape = (n, (h // sp) * (w // sp))
-    out = out if out is not None else torch.empty(shape, dtype=torch.float32, device=x.device)
-    count = count if count is not None else torch.empty(shape, dtype=torch.int32, device=x.device)
-    if out.numel() != shape[0] * shape[1] or count.numel() != out.numel():
-        raise ValueError(f'superpixel_mean_valid: out {tuple(out.shape)}, count {tuple(count.shape)} for {shape}')
-    if x.dtype != torch.float32 or out.dtype != torch.float32 or count.dtype != torch.int32:
-        raise TypeError('superpixel_mean_valid: x, out float32; count int32')
-    if not all(t.is_contiguous() for t in (x, out, count)):
-        raise ValueError('superpixel_mean_valid: contiguous tensors only')
-    if out.device != x.device or count.device != x.device:
-        raise ValueError('superpixel_mean_valid: all tensors on one device')
+    out = out if out is not None else torch.empty((n, nsp), dtype=torch.float32, device=x.device)
+    count = count if count is not None else torch.empty((n, nsp), dtype=torch.int32, device=x.device)
+    if out.numel() != n * nsp or count.numel() != out.numel():
+        raise ValueError(f'superpixel_mean_valid: out {tuple(out.shape)}, count {tuple(count.shape)} for {(n, nsp)}')
+    _check_operands('superpixel_mean_valid', (x, out), (count,), 'x, out float32; count int32')
     check(_lib.load().a3dv_superpixel_mean_valid(n, h, w, _ptr(x), sp, int(min_count), _ptr(out), _ptr(count), _stream()),
           'a3dv_superpixel_mean_valid')
     return out, count
@@ -903,29 +866,13 @@ def crf_loss_observed(z, y, r, left, right, pair_grad=True):
     pair_grad, nobs [n] int32, status [n] int32).  z, y [n,P] (y NaN where there is no target), r [n,Q] float32; left,
     right [Q] int32.  An image without a target has loss 0 and zero gradients; one whose A is not positive is NaN with
     status 1; a pair index outside [0, P) turns all of it into NaN."""
-    if z.dim() != 2 or r.dim() != 2:
-        raise ValueError(f'crf_loss_observed: z {tuple(z.shape)} and r {tuple(r.shape)} must be [n, P] and [n, Q]')
-    n, nsp = z.shape[0], z.shape[1]
-    if (n == 0 or tuple(y.shape) != (n, nsp) or r.shape[0] != n or left.numel() == 0 or r.shape[1] != left.numel()
-            or left.numel() != right.numel()):
-        raise ValueError(f'crf_loss_observed: z {tuple(z.shape)}, y {tuple(y.shape)}, r {tuple(r.shape)}, {left.numel()} / '
-                         f'{right.numel()} pair indices')
-    if (z.dtype != torch.float32 or y.dtype != torch.float32 or r.dtype != torch.float32 or left.dtype != torch.int32
-            or right.dtype != torch.int32):
-        raise TypeError('crf_loss_observed: z, y, r float32; left, right int32')
-    if not all(t.is_contiguous() for t in (z, y, r, left, right)):
-        raise ValueError('crf_loss_observed: contiguous tensors only')
-    if any(t.device != z.device for t in (y, r, left, right)):
-        raise ValueError('crf_loss_observed: all tensors on one device')
-    per = torch.empty((n,), dtype=torch.float32, device=z.device)
-    mean = torch.empty((1,), dtype=torch.float32, device=z.device)
-    dz = torch.empty((n, nsp), dtype=torch.float32, device=z.device)
-    dr = torch.empty_like(r) if pair_grad else None
+    n, nsp = _check_crf('crf_loss_observed', z, r, left, right, (y,))
+    per, mean, dz, dr = _crf_outputs(z, r, pair_grad)
     nobs = torch.empty((n,), dtype=torch.int32, device=z.device)
     status = torch.empty((n,), dtype=torch.int32, device=z.device)
     check(_lib.load().a3dv_crf_loss_observed(n, nsp, _ptr(z), _ptr(y), _ptr(r), _ptr(left), _ptr(right), left.numel(),
-                                             _ptr(per), _ptr(mean), _ptr(dz), _ptr(dr) if pair_grad else None, _ptr(nobs),
-                                             _ptr(status), _stream()), 'a3dv_crf_loss_observed')
+                                             _ptr(per), _ptr(mean), _ptr(dz), _ptr(dr), _ptr(nobs), _ptr(status),
+                                             _stream()), 'a3dv_crf_loss_observed')
     return mean, per, dz, dr, nobs, status
 
 
@@ -942,21 +889,10 @@ def pair_band(left, right):
 
 
 def _check_band(who, z, r, left, right, band, others):
-    if z.dim() != 2 or r.dim() != 2:
-        raise ValueError(f'{who}: z {tuple(z.shape)} and r {tuple(r.shape)} must be [n, P] and [n, Q]')
-    n, nsp = z.shape[0], z.shape[1]
-    if (n == 0 or r.shape[0] != n or left.numel() == 0 or r.shape[1] != left.numel() or left.numel() != right.numel()
-            or any(tuple(t.shape) != (n, nsp) for t in others)):
-        raise ValueError(f'{who}: z {tuple(z.shape)}, {[tuple(t.shape) for t in others]}, r {tuple(r.shape)}, '
-                         f'{left.numel()} / {right.numel()} pair indices')
+    """_check_crf, then the banded kernels' limits."""
+    n, nsp = _check_crf(who, z, r, left, right, others)
     if not 1 <= nsp <= BAND_MAX_SP or not 1 <= int(band) <= BAND_MAX_BAND:
         raise ValueError(f'{who}: {nsp} superpixels (1 .. {BAND_MAX_SP}), band {band} (1 .. {BAND_MAX_BAND})')
-    if (any(t.dtype != torch.float32 for t in (z, r, *others)) or left.dtype != torch.int32 or right.dtype != torch.int32):
-        raise TypeError(f'{who}: z, y, r, mu float32; left, right int32')
-    if not all(t.is_contiguous() for t in (z, r, left, right, *others)):
-        raise ValueError(f'{who}: contiguous tensors only')
-    if any(t.device != z.device for t in (r, left, right, *others)):
-        raise ValueError(f'{who}: all tensors on one device')
     return n, nsp
 
 
@@ -967,15 +903,12 @@ def crf_band_nll(z, y, r, left, right, band, pair_grad=True, want_mu=False):
     status [n] int32).  z, y [n,P], r [n,Q] float32; left, right [Q] int32.  An image whose A is not positive is NaN with
     status 1; a pair index outside [0, P) or farther apart than band turns all of it into NaN."""
     n, nsp = _check_band('crf_band_nll', z, r, left, right, band, (y,))
-    per = torch.empty((n,), dtype=torch.float32, device=z.device)
-    mean = torch.empty((1,), dtype=torch.float32, device=z.device)
-    dz = torch.empty((n, nsp), dtype=torch.float32, device=z.device)
-    dr = torch.empty_like(r) if pair_grad else None
+    per, mean, dz, dr = _crf_outputs(z, r, pair_grad)
     mu = torch.empty((n, nsp), dtype=torch.float32, device=z.device) if want_mu else None
     status = torch.empty((n,), dtype=torch.int32, device=z.device)
     check(_lib.load().a3db_crf_band_nll(n, nsp, int(band), _ptr(z), _ptr(y), _ptr(r), _ptr(left), _ptr(right), left.numel(),
-                                        _ptr(per), _ptr(mean), _ptr(dz), _ptr(dr) if pair_grad else None,
-                                        _ptr(mu) if want_mu else None, _ptr(status), _stream()), 'a3db_crf_band_nll')
+                                        _ptr(per), _ptr(mean), _ptr(dz), _ptr(dr), _ptr(mu), _ptr(status), _stream()),
+          'a3db_crf_band_nll')
     return mean, per, dz, dr, mu, status
 
 

@@ -185,7 +185,7 @@ def autograd64(z, y, r, left, right):
 
 # ------------------------------------------------------------------------------------------------ float32
 def _eliminate32(Um, nn):
-    """eliminate_positive of crf.hip on Um [B, nn, cols] float32 in place -> (logdet [B], ok [B])."""
+    """eliminate of crf.hip on Um [B, nn, cols] float32 in place -> its (logdet [B], positive [B])."""
     B = Um.shape[0]
     idx = np.arange(B)
     ld, ok, swaps = np.zeros(B, F), np.ones(B, bool), np.zeros(B, np.int64)
