@@ -178,6 +178,12 @@ CRF_BAND_SIGNATURES = {
     'a3db_crf_band_map': (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_wino.h declares (prefix a3dw_)
+WINO_SIGNATURES = {
+    'a3dw_conv2d_bwd_data_prepared_filter_bytes': (c_size_t, [_D]),
+    'a3dw_conv2d_bwd_data_prepare_filter': (c_int, [_D, _P, _P, c_size_t, _P]),
+}
+
 _lib = None
 
 
@@ -196,7 +202,7 @@ def load():
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(PAIR_SIGNATURES.items())
                               + list(TEXTURE_SIGNATURES.items()) + list(GRADLOSS_SIGNATURES.items())
                               + list(CRF_VALID_SIGNATURES.items()) + list(FCSP_SIGNATURES.items())
-                              + list(CRF_BAND_SIGNATURES.items())):
+                              + list(CRF_BAND_SIGNATURES.items()) + list(WINO_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

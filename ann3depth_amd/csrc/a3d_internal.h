@@ -121,4 +121,20 @@ int conv3b_pack(const a3d_conv_desc* d, const float* w, void* wp, hipStream_t st
 int conv3b_fwd(const a3d_conv_desc* d, const void* x, const float* w, const float* bias, void* y, int act, int pool, int ld_out,
                uint8_t* argmax, void* ws, size_t ws_bytes, hipStream_t st, bool prepared);
 
+// ---- Winograd F(2x2,3x3) route of A3D_PREC_F32_WINOGRAD (wino.hip); bwd: the bwd-data form of the descriptor ----
+struct WinoGeom {
+  int oh, ow, th, tw;                    // the output grid (bwd: dx's) and its 2x2 tiles
+  size_t T;                              // n * th * tw
+  int K, N, Kp, Np;                      // channels contracted / produced, and padded to whole 16-byte pieces
+  size_t v_bytes, m_bytes, u_bytes;      // V [16][T][Kp], M [16][T][Np], U [16][Kp][Np]
+};
+WinoGeom wino_geom(const a3d_conv_desc* d, bool bwd);
+bool wino_applicable(const a3d_conv_desc* d);
+int wino_filter(const a3d_conv_desc* d, bool bwd, const float* w, float* U, hipStream_t st);
+int wino_input(const a3d_conv_desc* d, bool bwd, const float* src, float* V, hipStream_t st);
+int wino_output(const a3d_conv_desc* d, bool bwd, const float* M, float* out, const float* bias, const float* mask, int act,
+                hipStream_t st);
+a3d_timing_record wino_record(int mode, const WinoGeom& g);
+int wino_gemm(IgemmParams& p, const WinoGeom& g, hipStream_t st);      // p: one product; the sixteen differ in A, B and C
+
 }  // namespace a3d

@@ -802,6 +802,7 @@ extern "C" int a3d_dense_bwd_filter_adam_tf1_ex(int m, int k, int n, const float
                                                 float* v_w, float* var_b, float* m_b, float* v_b, float lr, float beta1,
                                                 float beta2, float beta1_power, float beta2_power, float grad_scale,
                                                 int precision, void* stream) {
+  if (precision == A3D_PREC_F32_WINOGRAD) precision = A3D_PREC_F32;      // no 3x3 window in a dense layer: runs as A3D_PREC_F32
   A3D_CHECK_ARG(precision == A3D_PREC_F32 || precision == A3D_PREC_BF16, "dense_bwd_filter_adam: precision %d (float32 or bf16)", precision);
   A3D_CHECK_ARG(m > 0 && k > 0 && n > 0 && x && dz && var_w && m_w && v_w, "dense_bwd_filter_adam: bad arguments");
   A3D_CHECK_ARG((var_b && m_b && v_b) || (!var_b && !m_b && !v_b), "dense_bwd_filter_adam: bias slots come as a set");

@@ -3,6 +3,7 @@
 // that takes, and the kernel's parameters.  The plans: igemm_plan.cc; the launches: igemm_launch.hip.
 #include <algorithm>
 
+#include "../../include/a3d_wino.h"
 #include "a3d_internal.h"
 #include "igemm.h"
 #include "igemm_cfgs.h"
@@ -161,13 +162,23 @@ static int check_desc(const a3d_conv_desc* d) {
   A3D_CHECK_ARG((d->ho - 1) * d->stride - d->pad_t < d->h && (d->wo - 1) * d->stride - d->pad_l < d->w,
                 "conv: output size inconsistent with input");
   A3D_CHECK_ARG(d->ldx >= d->c && d->ldy >= d->k, "conv: pixel strides smaller than channel counts");
-  A3D_CHECK_ARG(d->precision >= A3D_PREC_F32 && d->precision <= A3D_PREC_BF16, "conv: unknown precision %d", d->precision);
+  A3D_CHECK_ARG(d->precision >= A3D_PREC_F32 && d->precision <= A3D_PREC_F32_WINOGRAD, "conv: unknown precision %d", d->precision);
   const double lim = 2147483647.0;
   A3D_CHECK_ARG((double)d->n * d->h * d->w * d->ldx < lim && (double)d->n * d->ho * d->wo * d->ldy < lim &&
                     (double)d->r * d->s * d->c * d->k < lim,
                 "conv: tensor too large for 31-bit indexing");
   return A3D_OK;
 }
+
+// A3D_PREC_F32_WINOGRAD on a call the Winograd route (wino.hip) does not take runs exactly as A3D_PREC_F32 does: from this
+// line on `d` is the descriptor with that value
+#define A3D_AS_F32(d)                                          \
+  a3d_conv_desc d##_f32;                                       \
+  if ((d) && (d)->precision == A3D_PREC_F32_WINOGRAD) {        \
+    d##_f32 = *(d);                                            \
+    d##_f32.precision = A3D_PREC_F32;                          \
+    (d) = &d##_f32;                                            \
+  }
 
 static GemmProblem fwd_problem(const a3d_conv_desc* d) {
   GemmProblem g;
@@ -362,8 +373,54 @@ using namespace a3d;
 
 extern "C" {
 
+// The Winograd route's workspace: [U unless prepared][V][M]
+static size_t wino_bytes(const a3d_conv_desc* d, bool bwd, bool prepared) {
+  const WinoGeom g = wino_geom(d, bwd);
+  return (prepared ? 0 : g.u_bytes) + g.v_bytes + g.m_bytes;
+}
+// forward (dz = x, dx = y, bias + act) or bwd-data (mask) of a descriptor wino_applicable() accepted; `w`: the filter, or its
+// transform when prepared
+static int wino_conv(const a3d_conv_desc* d, bool bwd, const float* src, const float* w, float* out, const float* bias, const float* mask,
+                     int act, bool prepared, void* ws, size_t ws_bytes, hipStream_t st) {
+  const WinoGeom g = wino_geom(d, bwd);
+  const size_t need = wino_bytes(d, bwd, prepared);
+  if (!ws || need > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d (Winograd): need %zu workspace bytes", need);
+  A3D_CHECK_ARG(!prepared || aligned16(w), "conv2d (Winograd): the prepared filter must be 16-byte aligned");
+  char* base = static_cast<char*>(ws);
+  const float* U = w;
+  int rc;
+  if (!prepared) {
+    rc = wino_filter(d, bwd, w, reinterpret_cast<float*>(base), st);
+    if (rc != A3D_OK) return rc;
+    U = reinterpret_cast<const float*>(base);
+    base += g.u_bytes;
+  }
+  float* V = reinterpret_cast<float*>(base);
+  float* M = reinterpret_cast<float*>(base + g.v_bytes);
+  rc = wino_input(d, bwd, src, V, st);
+  if (rc != A3D_OK) return rc;
+  // one product: T rows of Kp gathered channels (a 1x1 conv over T one-pixel images) against U[xi] [Kp][Np]
+  a3d_conv_desc e{};
+  e.n = (int)g.T; e.h = e.w = e.ho = e.wo = 1; e.c = g.Kp; e.k = g.Np; e.r = e.s = 1; e.stride = 1; e.ldx = g.Kp; e.ldy = g.Np;
+  GemmProblem gp = fwd_problem(&e);
+  IgemmParams p;
+  fill_common(p, gp);
+  p.A = V; p.B = U; p.C = M;
+  p.npix = gp.M; p.nrsc = gp.K;
+  fill_gather(p, &e, g.Kp, 1, g.Kp);
+  p.ldb = g.Np; p.ldc = g.Np;
+  fill_staging(p, MODE_FWD, (unsigned long long)g.T * g.Kp, (unsigned long long)g.Kp * g.Np, 1, 1);
+  rc = timed_launch(wino_record(bwd ? MODE_BWD_D : MODE_FWD, g), st, [&] { return wino_gemm(p, g, st); });
+  if (rc != A3D_OK) return rc;
+  return wino_output(d, bwd, M, out, bias, mask, act, st);
+}
+
 size_t a3d_conv2d_fwd_ws_bytes(const a3d_conv_desc* d) {
-  if (check_desc(d) != A3D_OK || stencil1_applicable(d)) return 0;
+  if (check_desc(d) != A3D_OK) return 0;
+  const size_t wino = wino_applicable(d) ? wino_bytes(d, false, (d->hints & A3D_HINT_W_PREPARED) != 0) : 0;
+  A3D_AS_F32(d);
+  if (stencil1_applicable(d)) return 0;
+  if (wino) return std::max(wino, a3d_conv2d_fwd_ws_bytes(d));      // (the _ex2 form with a second output runs direct)
   // (a maximum over the paths a launch may take: which one it is also depends on the operands' alignment)
   size_t need = 0;
   for (GemmForm form : {kAsStored, kLdsDma, kRunForm, kBf16Image}) need = upto(need, fwd_gemm(d, kOnGrid, form));
@@ -381,6 +438,17 @@ static int conv_fwd_impl(const a3d_conv_desc* d, const float* x, const float* w,
   int rc = check_desc(d);
   if (rc != A3D_OK) return rc;
   if (!ws) ws_bytes = 0;
+  if (wino_applicable(d) && !pool && !(out2 && out2->ptr)) {
+    A3D_CHECK_ARG(x && w && y, "conv2d_fwd: null tensor");
+    A3D_CHECK_WS(ws, "conv2d_fwd");
+    A3D_CHECK_ARG(act == A3D_ACT_NONE || act == A3D_ACT_RELU || act == A3D_ACT_SIGMOID, "conv2d_fwd: bad act");
+    return wino_conv(d, false, x, w, y, bias, nullptr, act, (d->hints & A3D_HINT_W_PREPARED) != 0, ws, ws_bytes,
+                     static_cast<hipStream_t>(stream));
+  }
+  // the prepared filter of an 'fp32w' descriptor is the Winograd transform: the direct forwards (fused pool, second output) cannot read it
+  A3D_CHECK_ARG(!(wino_applicable(d) && (d->hints & A3D_HINT_W_PREPARED)),
+                "conv2d_fwd: A3D_HINT_W_PREPARED with A3D_PREC_F32_WINOGRAD is for the plain forward only (no fused pool, no second output)");
+  A3D_AS_F32(d);
   Operands o = launch_operands(x, w, y, argmax);
   o.act = act; o.pool = pool; o.ld_out = ld_out; o.argmax = argmax != nullptr;
   o.prepared = (d->hints & A3D_HINT_W_PREPARED) != 0;
@@ -470,6 +538,8 @@ static int fwd_filter_form(const a3d_conv_desc* d, RunForm* rf) {
 }
 
 size_t a3d_conv2d_fwd_prepared_filter_bytes(const a3d_conv_desc* d) {
+  if (check_desc(d) == A3D_OK && wino_applicable(d)) return wino_geom(d, false).u_bytes;      // the transformed filter U
+  A3D_AS_F32(d);
   RunForm rf{};
   switch (fwd_filter_form(d, &rf)) {
     case 1: return conv3b_applicable(d) ? conv3b_filter_bytes(d) : rf.bytes;
@@ -487,6 +557,8 @@ int a3d_conv2d_fwd_prepare_filter(const a3d_conv_desc* d, const float* w, void* 
   A3D_CHECK_ARG(need > 0, "conv2d_fwd_prepare_filter: this forward reads the filter as stored");
   if (prepared_bytes < need) return set_error(A3D_EWORKSPACE, "conv2d_fwd_prepare_filter: need %zu bytes", need);
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (wino_applicable(d)) return wino_filter(d, false, w, static_cast<float*>(prepared), st);
+  A3D_AS_F32(d);
   RunForm rf{};
   switch (fwd_filter_form(d, &rf)) {
     case 1: return conv3b_applicable(d) ? conv3b_pack(d, w, prepared, st) : pad_filter(d, rf, true, w, prepared, st);
@@ -554,6 +626,8 @@ static Route bwd_d_gemm(const a3d_conv_desc* d, const BwdDClass& c, const Operan
 
 size_t a3d_conv2d_bwd_data_ws_bytes(const a3d_conv_desc* d) {
   if (check_desc(d) != A3D_OK) return 0;
+  if (wino_applicable(d)) return wino_bytes(d, true, (d->hints & A3D_HINT_W_PREPARED) != 0);
+  A3D_AS_F32(d);
   BwdDClass cls[16];
   const int ncls = bwd_d_classes(d, cls);
   size_t need = 0;
@@ -587,6 +661,10 @@ int a3d_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w,
   A3D_CHECK_ARG(dz && w && dx, "conv2d_bwd_data: null tensor");
   A3D_CHECK_WS(ws, "conv2d_bwd_data");
   if (!ws) ws_bytes = 0;
+  if (wino_applicable(d))
+    return wino_conv(d, true, dz, w, dx, nullptr, relu_mask, A3D_ACT_NONE, (d->hints & A3D_HINT_W_PREPARED) != 0, ws, ws_bytes,
+                     static_cast<hipStream_t>(stream));
+  A3D_AS_F32(d);
   const Operands o = launch_operands(dx, w, dz, relu_mask);
   hipStream_t st = static_cast<hipStream_t>(stream);
   BwdDClass cls[16];
@@ -649,6 +727,20 @@ int a3d_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w,
   });
 }
 
+size_t a3dw_conv2d_bwd_data_prepared_filter_bytes(const a3d_conv_desc* d) {
+  return check_desc(d) == A3D_OK && wino_applicable(d) ? wino_geom(d, true).u_bytes : 0;
+}
+
+int a3dw_conv2d_bwd_data_prepare_filter(const a3d_conv_desc* d, const float* w, void* prepared, size_t prepared_bytes, void* stream) {
+  int rc = check_desc(d);
+  if (rc != A3D_OK) return rc;
+  A3D_CHECK_ARG(w && prepared && aligned16(prepared), "conv2d_bwd_data_prepare_filter: null or misaligned buffer");
+  const size_t need = a3dw_conv2d_bwd_data_prepared_filter_bytes(d);
+  A3D_CHECK_ARG(need > 0, "conv2d_bwd_data_prepare_filter: this bwd-data reads the filter as stored");
+  if (prepared_bytes < need) return set_error(A3D_EWORKSPACE, "conv2d_bwd_data_prepare_filter: need %zu bytes", need);
+  return wino_filter(d, true, w, static_cast<float*>(prepared), static_cast<hipStream_t>(stream));
+}
+
 // bf16 x and bf16 dz, whole 16-byte pieces inside one filter tap, 31-bit byte offsets into x: the LDS-DMA kernel may take the
 // filter gradient (BiasAddGrad then comes from colsum_bf16)
 static bool bwd_f_ring_ok(const a3d_conv_desc* d, const Operands& o) {
@@ -680,6 +772,7 @@ static Route bwd_f_gemm(const a3d_conv_desc* d, const Operands& o, GemmForm form
 }
 
 int a3d_conv2d_bwd_both_supported(const a3d_conv_desc* d) {
+  A3D_AS_F32(d);
   return check_desc(d) == A3D_OK && !d->storage && stencil1_bwd_both_applicable(d);
 }
 
@@ -690,6 +783,7 @@ size_t a3d_conv2d_bwd_both_ws_bytes(const a3d_conv_desc* d) {
 int a3d_conv2d_bwd_both(const a3d_conv_desc* d, const float* x, const float* dz, const float* w, float* dw, float* db,
                         void* dx, int lddx, int dx_bf16, int relu_mask, uint32_t* state, void* ws, size_t ws_bytes,
                         void* stream) {
+  A3D_AS_F32(d);
   int rc = check_desc(d);
   if (rc != A3D_OK) return rc;
   A3D_CHECK_ARG(x && dz && w && dw && dx && state, "conv2d_bwd_both: null tensor");
@@ -723,6 +817,7 @@ static bool fewch16_wanted(const a3d_conv_desc* d, bool pooled) {
 static bool fewch_pooled_ok(const a3d_conv_desc* d) { return !d->storage && fewch_bwdf_applicable(d, true); }
 
 size_t a3d_conv2d_bwd_filter_pooled_ws_bytes(const a3d_conv_desc* d) {
+  A3D_AS_F32(d);
   if (check_desc(d) != A3D_OK) return 0;
   if (fewch16_wanted(d, true)) return fewch16_bwdf_ws_bytes(d, true);
   return fewch_pooled_ok(d) ? fewch_bwdf_ws_bytes(d, true) : 0;
@@ -731,6 +826,7 @@ size_t a3d_conv2d_bwd_filter_pooled_ws_bytes(const a3d_conv_desc* d) {
 int a3d_conv2d_bwd_filter_pooled(const a3d_conv_desc* d, const float* x, const void* dpool, int ld_dpool, const void* pooled,
                                  const uint8_t* argmax, int ld_argmax, int pooled_bf16, float* dw, float* db, void* ws,
                                  size_t ws_bytes, void* stream) {
+  A3D_AS_F32(d);
   int rc = check_desc(d);
   if (rc != A3D_OK) return rc;
   A3D_CHECK_ARG(x && dpool && argmax && dw, "conv2d_bwd_filter_pooled: null tensor");
@@ -760,6 +856,7 @@ int a3d_conv2d_bwd_filter_pooled(const a3d_conv_desc* d, const float* x, const v
 }
 
 size_t a3d_conv2d_bwd_filter_ws_bytes(const a3d_conv_desc* d) {
+  A3D_AS_F32(d);
   if (check_desc(d) != A3D_OK) return 0;
   if (stencil1_applicable(d)) return stencil1_bwdf_ws_bytes(d);
   size_t need = fewch_wanted(d, false) ? fewch_bwdf_ws_bytes(d, false) : 0;      // (an unaligned x falls back to the plans below)
@@ -770,6 +867,7 @@ size_t a3d_conv2d_bwd_filter_ws_bytes(const a3d_conv_desc* d) {
 
 int a3d_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* dz, float* dw, float* db, void* ws,
                           size_t ws_bytes, void* stream) {
+  A3D_AS_F32(d);
   int rc = check_desc(d);
   if (rc != A3D_OK) return rc;
   A3D_CHECK_ARG(x && dz && dw, "conv2d_bwd_filter: null tensor");
@@ -856,6 +954,7 @@ int a3d_dense_fwd_ex2(int m, int k, int n, const float* x, const float* w, const
   A3D_CHECK_ARG(m > 0 && k > 0 && n > 0, "dense_fwd: bad dims");
   A3D_CHECK_ARG(ncols_y > 0 && ncols_y <= n && ldy >= ncols_y, "dense_fwd: y rows of %d columns at pitch %d from a GEMM of %d", ncols_y, ldy, n);
   A3D_CHECK_ARG((storage & ~(A3D_STORE_W_BF16 | A3D_STORE_X_BF16)) == 0, "dense_fwd: the weights and x may be bf16, y is float32");
+  if (precision == A3D_PREC_F32_WINOGRAD) precision = A3D_PREC_F32;      // no 3x3 window in a dense layer: runs as A3D_PREC_F32
   a3d_conv_desc d = dense_desc(m, k, n);
   d.precision = precision;
   int rc = check_desc(&d);
@@ -911,6 +1010,7 @@ int a3d_dense_bwd_data_ex2(int m, int k, int n, const float* dz, const float* w,
                            void* stream) {
   A3D_CHECK_ARG(m > 0 && k > 0 && n > 0, "dense_bwd_data: bad dims");
   // storage bits as a3d_conv2d_bwd_data's: Y = dz, W = w, X = dx and the mask
+  if (precision == A3D_PREC_F32_WINOGRAD) precision = A3D_PREC_F32;      // as a3d_dense_fwd_ex2
   A3D_CHECK_ARG(precision >= A3D_PREC_F32 && precision <= A3D_PREC_BF16, "dense_bwd_data: unknown precision %d", precision);
   A3D_CHECK_ARG(!mask || mask_act == A3D_ACT_RELU || mask_act == A3D_ACT_SIGMOID, "dense_bwd_data: bad mask_act");
   a3d_conv_desc d = dense_desc(m, k, n);

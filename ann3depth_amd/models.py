@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib, augment as augment_, ops
+from ._lib import ConvDesc
 
 NET_H, NET_W = 228, 304          # src/models.py:282
 OUT_H, OUT_W = 55, 74            # src/models.py:283
@@ -320,6 +321,15 @@ class MSDNReplica:
             'fine/second/conv2d': D(B, OUT_H, OUT_W, 64, 64, 5, 5, 1, 'SAME'),
             'fine/third': D(B, OUT_H, OUT_W, 64, 1, 5, 5, 1, 'SAME'),
         }
+        # fp32: the two stride-1 3x3 layers' bwd-data through Winograd F(2x2,3x3) ('fp32w', csrc/wino.hip) from WINO_MIN_TILES
+        # 2x2 tiles up; their forwards and filter gradients, and every layer below that, stay on the direct kernels
+        self.d_wino = {}
+        if precision == 'fp32' and dev.type == 'cuda':
+            for n in self.WINO_LAYERS:
+                d = self.d[n]
+                if d.n * -(-d.ho // 2) * -(-d.wo // 2) >= self.WINO_MIN_TILES:
+                    e = self.d_wino[n] = ConvDesc.from_buffer_copy(d)
+                    e.precision = ops.PREC['fp32w']
         # conv -> ReLU -> pool blocks on the 3-channel image: filter gradient straight from the POOLED map's gradient (MaxPoolGrad
         # by index + ReluGrad while the kernel stages its operand): dc0 / df1 (50 / 131 MB at B = 32) are never written or read.
         # fp32 arithmetic on the fp32 image in every precision mode but 'bf16s'.
@@ -378,6 +388,17 @@ class MSDNReplica:
                 pass
 
     SHARE_CU = ('fine/first/conv2d', 'fine/second/conv2d')     # forwards hinted A3D_HINT_SHARE_CU beside the side stream
+    # Winograd for the bwd-data of conv2d_2 / conv2d_3 (precision 'fp32' only).  Per launch, both routes timed at B = 8, 16, 32
+    # on one MI355X (tools/bench_layers.py, profiles/wino_bench_layers.txt): both bwd-data launches win at each — 504 tiles
+    # (B = 8) by 5-22 %, 2016 (B = 32) by 35-36 % — and nothing smaller was measured, so the threshold is the smallest count that
+    # was.  Above 252: the pinned plans and records of B <= 4 (tests/golden/plan_log.json, test_make_train_drop_in) are the
+    # direct kernels'.  The FORWARDS win as well (39-41 % at B = 32) and stay direct all the same: Winograd moves the coarse map
+    # by 8e-7 rel-L2, and the scale-invariant log loss of an untrained network has outputs so close to zero that one of them
+    # moves by 1.6 % with it; its 1/y gradient moves as much, an output that crosses zero is switched by the masked log, and the
+    # Adam m slots after 25 steps differ from the direct forward's by more than their own norm.  bwd-data changes the conv
+    # gradients by 7e-7 rel-L2 and nothing else (profiles/wino_outputs_vs_parent.txt).
+    WINO_LAYERS = ('coarse/conv/conv2d_2', 'coarse/conv/conv2d_3')
+    WINO_MIN_TILES = 504
 
     def _desc(self, name, which):
         """The layer's conv descriptor for 'fwd' | 'bwd_d' | 'bwd_f', with that call's storage bits."""
@@ -399,13 +420,14 @@ class MSDNReplica:
             return self.wcopy[name]
         return self._v(name + '/kernel')
 
-    def _prepared(self, key, desc, w):
-        """(descriptor, filter) for a few-channel forward: the prepared copy and the descriptor that says so, where the launch has one."""
+    def _prepared(self, key, desc, w, which='fwd'):
+        """(descriptor, filter) for a few-channel forward or a Winograd bwd-data: the prepared copy and the descriptor that says
+        so, where the launch has one."""
         if self.device.type != 'cuda':
             return desc, w
         pf = self._prep.get(key)
         if pf is None:
-            pf = self._prep[key] = ops.PreparedFilter(desc, self.device)
+            pf = self._prep[key] = ops.PreparedFilter(desc, self.device, which)
             pf.source = w
             if pf.ok:
                 pf.refresh(w)
@@ -887,7 +909,10 @@ class MSDNReplica:
         return not self.keep_dense_grads and self.groups['CoarseDense'].frozen()
 
     def _bwd_data(self, name, dz, dx, relu_mask=None):
-        ops.conv2d_bwd_data(self._desc(name, 'bwd_d'), dz, self._w(name, 'bwd_d'), dx, relu_mask=relu_mask)
+        d, w = self._desc(name, 'bwd_d'), self._w(name, 'bwd_d')
+        if name in self.d_wino:
+            d, w = self._prepared((name, 'bwd_d', 'fp32w'), self.d_wino[name], w, 'bwd_d')
+        ops.conv2d_bwd_data(d, dz, w, dx, relu_mask=relu_mask)
 
     def _bwd_filter(self, name, x, dz):
         if name in self.d:

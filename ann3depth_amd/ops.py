@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import ConvDesc, check
 
 ACT = {None: 0, 'relu': 1, 'sigmoid': 2}
-PREC = {'fp32': 0, 'f32': 0, 'bf16x3': 1, 'bf16': 2}
+PREC = {'fp32': 0, 'f32': 0, 'bf16x3': 1, 'bf16': 2, 'fp32w': 3}      # 'fp32w': A3D_PREC_F32_WINOGRAD
 
 
 def _ptr(t):
@@ -75,11 +75,13 @@ HINT_W_PREPARED = 2
 class PreparedFilter:
     """The filter of a few-channel forward in the layout its kernel reads (a3d_conv2d_fwd_prepare_filter), kept beside the
     stored filter so that the repack runs when the weights change instead of on every call.  desc: the descriptor the forward
-    uses WITHOUT the hint; .desc_prepared is the same descriptor with A3D_HINT_W_PREPARED, .buf the prepared copy."""
+    uses WITHOUT the hint; .desc_prepared is the same descriptor with A3D_HINT_W_PREPARED, .buf the prepared copy.
+    which='bwd_d': the filter a3d_conv2d_bwd_data reads (precision 'fp32w': the transform of the flipped taps)."""
 
-    def __init__(self, desc, device):
+    def __init__(self, desc, device, which='fwd'):
         lib = _lib.load()
-        nbytes = lib.a3d_conv2d_fwd_prepared_filter_bytes(ctypes.byref(desc))
+        self.stem = {'fwd': 'a3d_conv2d_fwd', 'bwd_d': 'a3dw_conv2d_bwd_data'}[which]
+        nbytes = getattr(lib, self.stem + '_prepared_filter_bytes')(ctypes.byref(desc))
         self.ok = nbytes > 0
         self.desc = desc
         if self.ok:
@@ -88,13 +90,14 @@ class PreparedFilter:
             self.desc_prepared.hints = desc.hints | HINT_W_PREPARED
 
     def refresh(self, w):
-        check(_lib.load().a3d_conv2d_fwd_prepare_filter(ctypes.byref(self.desc), _ptr(w), _ptr(self.buf), self.buf.numel(), _stream()),
-              'a3d_conv2d_fwd_prepare_filter')
+        name = self.stem + '_prepare_filter'
+        check(getattr(_lib.load(), name)(ctypes.byref(self.desc), _ptr(w), _ptr(self.buf), self.buf.numel(), _stream()), name)
 
 
 def conv_desc(n, h, w, c, k, r, s, stride, padding, ldx=None, ldy=None, precision='fp32', storage=0, hints=0):
     """Descriptor of tf.layers.conv2d(x[n,h,w,c], k, (r,s), (stride,stride), padding).  precision selects the
-    arithmetic of the contraction: 'fp32' (exact, default), 'bf16x3' (split operands) or 'bf16'."""
+    arithmetic of the contraction: 'fp32' (exact, default), 'bf16x3' (split operands), 'bf16', or 'fp32w' (fp32 through
+    Winograd F(2x2,3x3) where the layer is a stride-1 3x3 one, 'fp32' elsewhere)."""
     padding = padding.upper()
     if padding == 'SAME':
         ho, pt = same_pad(h, r, stride)

@@ -64,7 +64,11 @@ typedef struct a3d_conv_desc {
 /* `w` of this FORWARD call is the filter as a3d_conv2d_fwd_prepare_filter laid it out for this descriptor (the few-channel
  * layers repack or pad their filter — [K/4][N][4], zero rows for the window runs' pad positions, a bf16 copy for the image
  * form — which otherwise happens on every call, 5 us per launch for weights that the reference's optimizer never moves:
- * src/models.py:309).  The caller refreshes the prepared copy whenever the weights change.  Same results bit for bit. */
+ * src/models.py:309).  The caller refreshes the prepared copy whenever the weights change.  Same results bit for bit.
+ * Under A3D_PREC_F32_WINOGRAD the prepared filter is the Winograd transform, and a3d_conv2d_bwd_data honours the hint too, with
+ * the copy a3dw_conv2d_bwd_data_prepare_filter (include/a3d_wino.h) made.  That copy of the forward is for the plain
+ * a3d_conv2d_fwd alone: a3d_conv2d_pool_fwd and a3d_conv2d_fwd_ex2 with a second output run direct and refuse the hint on such
+ * a descriptor (A3D_EINVAL). */
 #define A3D_HINT_W_PREPARED 2
 
 /* BASELINE config 5 ("bf16 activations + bf16 weight copies, fp32 master and accumulate"): tensors marked here are bf16 in
@@ -96,6 +100,17 @@ typedef struct a3d_conv_desc {
 #define A3D_PREC_F32 0     /* exact fp32 on the fp32 matrix cores (default; what parity is stated for) */
 #define A3D_PREC_BF16X3 1  /* fp32 operands split into bf16 hi+lo, 3 bf16 MFMAs per product: ~1e-5 relative */
 #define A3D_PREC_BF16 2    /* operands rounded to bf16, fp32 accumulate (BASELINE config 5's arithmetic; storage: a3d_conv_desc.storage) */
+/* fp32 tensors on the fp32 matrix cores through Winograd F(2x2,3x3): 2.25x fewer multiplies, other last bits than A3D_PREC_F32
+ * (the same error against float64 on the layers it was built for: DESIGN.md 3.1).  An arithmetic, not a hint.  Honoured by
+ * a3d_conv2d_fwd and a3d_conv2d_bwd_data when r = s = 3, stride = 1, pad_t and pad_l each 0 or 1 and storage = 0 — whatever
+ * the batch; every other call (a3d_conv2d_pool_fwd, the _ex2 form with a second output, bwd-filter, other kernel sizes and
+ * strides, the dense _ex forms) runs exactly as with A3D_PREC_F32, which is never less exact than what was asked.  One stated
+ * deviation: a non-finite input reaches every output whose 2x2 tile's 4x4 window holds it, not only the outputs whose own 3x3
+ * window does.  Sums are taken in a fixed order: the same bits on every run.  Workspace (the *_ws_bytes queries): the
+ * transformed input and the sixteen products, 16 * tiles * (c + k) floats with tiles = n * ceil(ho/2) * ceil(wo/2) (bwd-data:
+ * of h and w), plus the transformed filter, 16 * c * k floats, unless the call passes a prepared one (A3D_HINT_W_PREPARED:
+ * a3d_conv2d_fwd_prepare_filter for the forward, a3dw_conv2d_bwd_data_prepare_filter of include/a3d_wino.h for bwd-data). */
+#define A3D_PREC_F32_WINOGRAD 3
 
 const char* a3d_version(void);
 int a3d_last_error(char* buf, size_t len);

@@ -1,6 +1,9 @@
 """Times every MSDN layer x direction (B = 32 unless B=..) with the planner's own choice, the way MSDNReplica.step calls
-them (conv + pool fused where the step fuses them).  One line per op: us, TFLOP/s.  A/B two builds of the library on one
-GPU box:  A3D_LIB=tools/ab/liba3d_old.so python tools/bench_layers.py ; python tools/bench_layers.py"""
+them (conv + pool fused where the step fuses them).  One line per op: us, TFLOP/s.  The stride-1 3x3 layers get two more rows,
+fwd/wino and bwd_d/wino: the same call through the Winograd route (precision 'fp32w', prepared filters, all its launches; TF
+counts the direct convolution's FLOPs, so the rows compare as times) — what MSDNReplica.WINO_MIN_TILES is chosen from (the
+step uses the bwd-data rows: DESIGN 3.1k); they are not part of the total.  A/B two builds of the library on one GPU box:
+    A3D_LIB=tools/ab/liba3d_old.so python tools/bench_layers.py ; python tools/bench_layers.py"""
 import json
 import os
 import sys
@@ -55,14 +58,21 @@ def main():
         modes['bwd_f'] = lambda: ops.conv2d_bwd_filter(d, x, dz, dw, db)
         if c > 3:
             modes['bwd_d'] = lambda: ops.conv2d_bwd_data(d, dz, wt, dx, relu_mask=x)
+        if ks == 3 and st == 1:
+            dw_ = ops.conv_desc(B, h, w, c, k, ks, ks, st, pad, precision='fp32w')
+            pf, pb = ops.PreparedFilter(dw_, x.device), ops.PreparedFilter(dw_, x.device, 'bwd_d')
+            pf.refresh(wt)
+            pb.refresh(wt)
+            modes['fwd/wino'] = lambda: ops.conv2d_fwd(pf.desc_prepared, x, pf.buf, bias, y, 'relu')
+            modes['bwd_d/wino'] = lambda: ops.conv2d_bwd_data(pb.desc_prepared, dz, pb.buf, dx, relu_mask=x)
         # conv + pool in one launch enumerates whole pool windows only: the last odd row / column is never computed
         flops_pooled = 2.0 * B * (d.ho // 2) * (d.wo // 2) * 4 * k * ks * ks * c
         for mode, fn in modes.items():
             t = timeit(fn)
-            tot += t
+            tot += 0.0 if mode.endswith('/wino') else t
             f = flops_pooled if mode == 'fwd+pool' else flops      # the FLOPs of the GEMM the launch computes
             rows.append({'layer': name, 'mode': mode, 'us': round(t, 1), 'tflops': round(f / t / 1e6, 1)})
-            print(f'{name:9s} {mode:9s} {f / 1e9:6.2f} GF {t:8.1f} us {f / t / 1e6:6.1f} TF', flush=True)
+            print(f'{name:9s} {mode:10s} {f / 1e9:6.2f} GF {t:8.1f} us {f / t / 1e6:6.1f} TF', flush=True)
     print(f'total {tot:.1f} us   lib={os.environ.get("A3D_LIB", "in-tree")}')
     out = os.environ.get('OUT')
     if out:
