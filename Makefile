@@ -87,6 +87,20 @@ evaluate:
 	python3 -O -m ann3depth_amd.evaluate --ckptdir=${CKPT_DIR} --datadir=${DATA_DIR} --model=${MODEL} --id=${RUNID} \
 		--batchsize=${BATCHSIZE} ${EVAL_ARGS} ${DATASET}
 
+# depth maps for image files from the newest checkpoint of ${CKPT_DIR}/${MODEL}_${RUNID} (ann3depth_amd/predict.py):
+#   make predict MODEL=msdn RUNID=r1 IMAGES="a.png b.png" OUT=depths
+# writes ${OUT}/<stem>-depth.npy and ${OUT}/<stem>-depth.png at each image's own size, brought there by joint bilateral
+# upsampling under the image; more flags through PREDICT_ARGS, e.g. PREDICT_ARGS="--upsample bilinear", or for MODEL=dcnf
+# PREDICT_ARGS="--superpixel 10 --radius 2 --sigma-range 0.1"; the same filter scores a split with
+# EVAL_ARGS="--upsample joint"
+IMAGES ?=
+OUT ?= predictions
+PREDICT_ARGS ?=
+.PHONY: predict
+predict:
+	python3 -O -m ann3depth_amd.predict --ckptdir=${CKPT_DIR} --model=${MODEL} --id=${RUNID} --batchsize=${BATCHSIZE} \
+		--out=${OUT} ${PREDICT_ARGS} ${IMAGES}
+
 # raw downloads -> PNG pairs of one size (the reference's `make preprocess`, Makefile:118-121), without h5py / scipy.misc;
 # NYU only (tools/data_preprocessor.py)
 .PHONY: preprocess

@@ -15,6 +15,11 @@ the 6 x 8 superpixel grid and sampled at the target's pixels inside the metrics 
 the DCNF step resizes its targets to.  The objective is reported once, as ``crf_nll``; ``singular_systems`` counts the
 images whose system had no solution (their crf row is NaN and shows up under ``nonfinite``).
 
+``--upsample joint`` (NON-REFERENCE; ``--radius``, ``--sigma-space``, ``--sigma-range``) adds a third output, ``fine_joint``
+or ``crf_joint``: the same prediction brought to the record image's size by joint bilateral upsampling under the batch's
+images (ops.joint_bilateral_upsample, include/a3d_upsample.h), judged against the same target.  The default,
+``none``, launches nothing more and adds no key.
+
 Output: one JSON line on stdout, ``<ckptdir>/<model>_<id>/eval-<global_step>.json`` and TensorBoard scalars
 ``eval/<output>/<metric>`` (and ``eval/crf_nll``) at the checkpoint's global step.  Exit code 2 when there is nothing to
 evaluate (no checkpoint, no test split) or the request is unsupported (an unknown model, more than one process).
@@ -123,15 +128,20 @@ class Evaluator:
     outputs = OUTPUTS['msdn']
 
     def __init__(self, replica, resolution='grid', min_depth=0., max_depth=float('inf'), clamp_lo=1e-3,
-                 clamp_hi=float('inf'), keep_predictions=False):
+                 clamp_hi=float('inf'), keep_predictions=False, upsample=None):
+        """upsample (NON-REFERENCE, --upsample joint): an ops.JointUpsampler; a third output `fine_joint`, the fine map
+        brought to the record image's size under the batch's images, is judged against the same target."""
         from .models import OUT_H, OUT_W
         self.rep, self.resolution = replica, resolution
+        self.upsample = upsample
+        if upsample is not None:
+            self.outputs = self.outputs + ('fine_joint',)
         self.kw = dict(min_depth=min_depth, max_depth=max_depth, clamp_lo=clamp_lo, clamp_hi=clamp_hi)
         dev = replica.device
         self.t = torch.empty((replica.B, OUT_H, OUT_W), device=dev)
         self.silog_ws = {}              # per batch size (a3d_silog_loss_fwd's per-sample sums and partials)
         self.rows = {o: [] for o in self.outputs}
-        self.losses = {o: [] for o in self.outputs}
+        self.losses = {o: [] for o in OUTPUTS['msdn']}
         self.counts = []
         self.predictions = [] if keep_predictions else None
         self.prediction_shape = (OUT_H, OUT_W)
@@ -140,7 +150,7 @@ class Evaluator:
         coarse, fine = self.rep.predict(images, n)
         ops.resize_bilinear_tf1(depths[:n], self.t[:n].view(n, self.t.shape[1], self.t.shape[2], 1))
         target = self.t[:n] if self.resolution == 'grid' else depths[:n]
-        for name, out in zip(self.outputs, (coarse, fine)):
+        for name, out in zip(OUTPUTS['msdn'], (coarse, fine)):
             self.rows[name].append(ops.depth_metrics(out[:n], target, **self.kw))
             loss = torch.empty(1, device=out.device)
             ws = self.silog_ws.get(n)
@@ -148,6 +158,8 @@ class Evaluator:
                 ws = self.silog_ws[n] = ops.silog_ws(n, out.device)
             ops.silog_loss_fwd(out[:n], self.t[:n], loss, ws)                    # the mean over these n images
             self.losses[name].append(loss)
+        if self.upsample is not None:
+            self.rows['fine_joint'].append(ops.depth_metrics(self.upsample(fine[:n], images[:n]), target, **self.kw))
         self.counts.append(n)
         if self.predictions is not None:
             self.predictions.append(fine[:n].clone())
@@ -158,8 +170,9 @@ class Evaluator:
         n = np.asarray(self.counts, np.float64)
         for name in self.outputs:
             res = ops.summarize_depth_metrics(torch.cat(self.rows[name]))
-            per_batch = torch.cat(self.losses[name]).double().cpu().numpy()
-            res['silog'] = float((per_batch * n).sum() / n.sum())
+            if name in self.losses:
+                per_batch = torch.cat(self.losses[name]).double().cpu().numpy()
+                res['silog'] = float((per_batch * n).sum() / n.sum())
             out[name] = res
         return out
 
@@ -171,11 +184,16 @@ class DCNFEvaluator:
     outputs = OUTPUTS['dcnf']
 
     def __init__(self, replica, resolution='grid', min_depth=0., max_depth=float('inf'), clamp_lo=1e-3,
-                 clamp_hi=float('inf'), keep_predictions=False, observed_nll=False):
+                 clamp_hi=float('inf'), keep_predictions=False, observed_nll=False, upsample=None):
         """observed_nll (NON-REFERENCE): also the training objective of a run with --min-depth / --max-depth, the
         likelihood of the superpixels that (min_depth, max_depth] leaves observed (DCNFReplica.nll(valid_range=...)); it
-        runs last in a batch, after the metrics have read the plainly resized targets."""
+        runs last in a batch, after the metrics have read the plainly resized targets.
+        upsample (NON-REFERENCE, --upsample joint): an ops.JointUpsampler; a third output `crf_joint`, the MAP depths
+        brought to the record image's size under the batch's images, is judged against the same target."""
         self.rep, self.resolution = replica, resolution
+        self.upsample = upsample
+        if upsample is not None:
+            self.outputs = self.outputs + ('crf_joint',)
         self.kw = dict(min_depth=min_depth, max_depth=max_depth, clamp_lo=clamp_lo, clamp_hi=clamp_hi)
         self.observed = (float(min_depth), float(max_depth)) if observed_nll else None
         self.onll, self.nobs = [], []
@@ -190,8 +208,10 @@ class DCNFEvaluator:
         unary, crf = rep.predict(images, n)
         self.nll.append(rep.nll(depths, n))                                      # the mean over these n images
         target = rep.depths240[:n] if self.resolution == 'grid' else depths[:n]
-        for name, out in zip(self.outputs, (unary, crf)):
+        for name, out in zip(OUTPUTS['dcnf'], (unary, crf)):
             self.rows[name].append(ops.depth_metrics(out[:n], target, **self.kw))
+        if self.upsample is not None:
+            self.rows['crf_joint'].append(ops.depth_metrics(self.upsample(crf[:n], images[:n]), target, **self.kw))
         self.status.append(rep.status[:n].clone())
         self.counts.append(n)
         if self.predictions is not None:
@@ -221,6 +241,54 @@ def find_checkpoint(args, run_dir):
     return latest_checkpoint(run_dir)
 
 
+def current_gpu(what):
+    if not torch.cuda.is_available():
+        raise RuntimeError(f'ann3depth_amd needs an MI355X: {what} has no CPU fallback')
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def restore_replica(args, ckpt, say, dev=None):
+    """The replica of args.model (msdn, dcnf) at args.batchsize / args.precision / args.superpixel with the weights of
+    checkpoint `ckpt` (a .pt file or a TF bundle prefix), as ann3depth.Session.__enter__ restores: (replica, texture,
+    unary), the last two what a dcnf checkpoint says about its own form.  None, after say(why), for a checkpoint this
+    model and --superpixel cannot use.  dev: the GPU to restore to; None (the prediction driver) reads the checkpoint on
+    the host and asks for the current GPU only once nothing is left to refuse."""
+    from .models import DCNF_PAIR_PREFIX, DCNF_PREFIX, DCNFReplica, MSDNReplica, check_dcnf_superpixel
+    say(f'restoring {ckpt}')
+    bundle = tfckpt.is_bundle(ckpt)                  # as ann3depth.Session.__enter__ restores
+    state = tfckpt.read_bundle(ckpt) if bundle else torch.load(ckpt, map_location='cpu' if dev is None else dev)
+    texture, unary = False, 'patch'
+    if args.model == 'dcnf':
+        # the checkpoint says how many similarities its pairwise layer weighs: 2, or 3 with --pairwise-texture
+        name = DCNF_PAIR_PREFIX + 'kernel'
+        shape = tuple(np.shape(state[name])) if name in state else None
+        if shape not in ((2, 1), (3, 1)):
+            say(f'{ckpt}: {name} has shape {None if shape is None else list(shape)}; a dcnf checkpoint holds a [2, 1] '
+                f'kernel, or a [3, 1] one when it was trained with --pairwise-texture.')
+            return None
+        texture = shape == (3, 1)
+        # ... and which form its unary part has: dense/kernel is [256, 128] with --unary fcsp, [12544, 128] without
+        dense = DCNF_PREFIX + 'dense/kernel'
+        unary = 'fcsp' if dense in state and tuple(np.shape(state[dense])) == (256, 128) else 'patch'
+        try:
+            check_dcnf_superpixel(args.superpixel, unary, None)
+        except ValueError as e:
+            say(f'{ckpt}: a checkpoint of the patch form; {e}.')
+            return None
+    if dev is None:
+        dev = current_gpu('prediction')
+    if args.model == 'dcnf':
+        replica = DCNFReplica(args.batchsize, device=dev, precision=args.precision, pairwise_texture=texture, unary=unary,
+                              superpixel=args.superpixel)
+    else:
+        replica = MSDNReplica(args.batchsize, device=dev, precision=args.precision, keep_dense_grads=False)
+    if bundle:
+        replica.load_tf_variables(state)
+    else:
+        replica.load_state_dict(state)
+    return replica, texture, unary
+
+
 def main(argv=None):
     args = parse_args(argv)
     if args.model not in OUTPUTS:
@@ -236,6 +304,15 @@ def main(argv=None):
         _say(f'--superpixel {args.superpixel} cannot go with --observed-nll yet: the likelihood of the observed superpixels '
              f'alone exists only for the dense 6 x 8 CRF (--superpixel 40).')
         return 2
+    upsample = None
+    if args.upsample == 'joint':
+        try:
+            upsample = ops.JointUpsampler('block' if args.model == 'dcnf' else 'corner',
+                                          args.superpixel if args.model == 'dcnf' else None, args.radius, args.sigma_space,
+                                          args.sigma_range)
+        except ValueError as e:
+            _say(f'--upsample joint: {e}.')
+            return 2
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         _say('evaluation runs in one process on one GPU; start it without a distributed launcher.')
         return 2
@@ -249,45 +326,18 @@ def main(argv=None):
     except FileNotFoundError as e:
         _say(f'no test split: {e} is missing.')
         return 2
-    if not torch.cuda.is_available():
-        raise RuntimeError('ann3depth_amd needs an MI355X: evaluation has no CPU fallback')
-    from .models import DCNF_PAIR_PREFIX, DCNF_PREFIX, DCNFReplica, MSDNReplica, check_dcnf_superpixel
-    dev = torch.device('cuda', torch.cuda.current_device())
-    _say(f'restoring {ckpt}')
-    bundle = tfckpt.is_bundle(ckpt)                  # as ann3depth.Session.__enter__ restores
-    state = tfckpt.read_bundle(ckpt) if bundle else torch.load(ckpt, map_location=dev)
-    texture, unary = False, 'patch'
-    if args.model == 'dcnf':
-        # the checkpoint says how many similarities its pairwise layer weighs: 2, or 3 with --pairwise-texture
-        name = DCNF_PAIR_PREFIX + 'kernel'
-        shape = tuple(np.shape(state[name])) if name in state else None
-        if shape not in ((2, 1), (3, 1)):
-            _say(f'{ckpt}: {name} has shape {None if shape is None else list(shape)}; a dcnf checkpoint holds a [2, 1] '
-                 f'kernel, or a [3, 1] one when it was trained with --pairwise-texture.')
-            inputs.pipeline.close()
-            return 2
-        texture = shape == (3, 1)
-        # ... and which form its unary part has: dense/kernel is [256, 128] with --unary fcsp, [12544, 128] without
-        dense = DCNF_PREFIX + 'dense/kernel'
-        unary = 'fcsp' if dense in state and tuple(np.shape(state[dense])) == (256, 128) else 'patch'
-        try:
-            check_dcnf_superpixel(args.superpixel, unary, None)
-        except ValueError as e:
-            _say(f'{ckpt}: a checkpoint of the patch form; {e}.')
-            inputs.pipeline.close()
-            return 2
-        replica = DCNFReplica(args.batchsize, device=dev, precision=args.precision, pairwise_texture=texture, unary=unary,
-                              superpixel=args.superpixel)
-    else:
-        replica = MSDNReplica(args.batchsize, device=dev, precision=args.precision, keep_dense_grads=False)
-    if bundle:
-        replica.load_tf_variables(state)
-    else:
-        replica.load_state_dict(state)
+    dev = current_gpu('evaluation')
+    restored = restore_replica(args, ckpt, _say, dev)
+    if restored is None:
+        inputs.pipeline.close()
+        return 2
+    replica, texture, unary = restored
     step = replica.global_step
     pipeline = inputs.pipeline
     evaluator = DCNFEvaluator if args.model == 'dcnf' else Evaluator
     extra = {'observed_nll': True} if args.observed_nll else {}
+    if upsample is not None:
+        extra['upsample'] = upsample
     ev = evaluator(replica, args.resolution, args.min_depth, args.max_depth, args.clamp_lo, args.clamp_hi,
                    keep_predictions=bool(args.predictions), **extra)
     op = EvalOp(pipeline, args.batchsize, dev)
@@ -311,6 +361,9 @@ def main(argv=None):
         out['unary_form'] = unary          # ('unary' holds the metrics of the unary output)
     if args.model == 'dcnf':
         out['superpixel'] = args.superpixel
+    if upsample is not None:
+        out.update(upsample='joint', radius=upsample.radius, sigma_space=upsample.sigma_space,
+                   sigma_range=upsample.sigma_range)
     if args.predictions:
         np.save(args.predictions, torch.cat(ev.predictions).cpu().numpy() if ev.predictions else
                 np.zeros((0,) + ev.prediction_shape, np.float32))
@@ -362,7 +415,23 @@ def parse_args(argv=None):
                         '12 x 16 or 24 x 32 depths per image). Checkpoints hold no grid: one trained at 40 evaluates at 10 and '
                         'the reverse. 20 and 10 need a checkpoint of --unary fcsp; crf_nll is then the banded likelihood, '
                         'not comparable with the value at 40.')
+    add_upsample_args(p, ['none', 'joint'], 'none',
+                      'NON-REFERENCE: joint also judges a third output, fine_joint (msdn) or crf_joint (dcnf): the prediction '
+                      'brought to the record image\'s size by joint bilateral upsampling under the image '
+                      '(ops.joint_bilateral_upsample), against the same target as the other outputs.')
     return p.parse_args(argv)
+
+
+def add_upsample_args(p, choices, default, text):
+    """--upsample and the three parameters of the joint bilateral filter, shared with the prediction driver."""
+    p.add_argument('--upsample', default=default, choices=choices, help=text)
+    p.add_argument('--radius', default=ops.UPSAMPLE_RADIUS, type=int,
+                   help=f'--upsample joint: cells around a pixel that count, 1 .. {ops.UPSAMPLE_MAX_RADIUS} (a window of '
+                        f'(2 radius + 1)^2).')
+    p.add_argument('--sigma-space', default=ops.UPSAMPLE_SIGMA_SPACE, type=float,
+                   help='--upsample joint: width of the distance weight, in cells of the prediction.')
+    p.add_argument('--sigma-range', default=ops.UPSAMPLE_SIGMA_RANGE, type=float,
+                   help='--upsample joint: width of the colour weight, in units of the [0, 1] colour range; inf: distance only.')
 
 
 if __name__ == '__main__':

@@ -1010,6 +1010,139 @@ def superpixel_pool_bwd(dpooled, tables, dfeat, channels=None):
     return dfeat
 
 
+UPSAMPLE_MAX_RADIUS = 4      # A3DU_MAX_RADIUS: 81 cells per output pixel
+UPSAMPLE_GRID = (240, 320)   # the grid DCNF's superpixels are cut from (models.DCNF_IMG_H, DCNF_IMG_W)
+
+
+def upsample_tables(gh, gw, H, W, kind, sp=None):
+    """The four host tables of a3du_joint_bilateral_upsample for a gh x gw prediction and an H x W image: (cy [H], cx [W]
+    float32, ay [gh], ax [gw] int32), computed in float64 and cast.  Both kinds relate two sizes as resize_bilinear_tf1
+    does: pixel u of a size S sits at pixel u * H / S of a size H (no half-pixel shift).
+
+    kind='corner' (msdn): the targets were made by that resize, so cell i stands for relative position i / gh:
+        cy[y] = y * gh / H,  ay[i] = clamp(floor(i * H / gh + 1/2), 0, H - 1).
+    kind='block' (dcnf): cell R is the mean of rows [R sp, (R + 1) sp) of the 240 x 320 grid; with u = y * 240 / H
+        cy[y] = (u + 1/2) / sp - 1/2,  ay[R] = clamp(floor((R + 1/2) * sp * H / 240), 0, H - 1),
+    the image row in the middle of the rows [R sp H / 240, (R + 1) sp H / 240) the block covers, the later of the two
+    when the middle falls between rows (H = 240: 20, 60, ..; H = 480: 40, 120, ..).  Carrying the grid's middle row
+    (R + 1/2) sp - 1/2 through the legacy mapping instead gives the earlier one there (39, 119, .. at H = 480); both are
+    half a pixel from the middle.  The same along x with 320."""
+    import numpy as np
+    gh, gw, H, W = int(gh), int(gw), int(H), int(W)
+    if min(gh, gw, H, W) <= 0:
+        raise ValueError(f'upsample_tables: a {gh} x {gw} grid and a {H} x {W} image must be positive')
+    if kind == 'corner':
+        if sp is not None:
+            raise ValueError(f"upsample_tables: sp = {sp!r} goes with kind='block'")
+        c = [np.arange(S, dtype=np.float64) * g / S for g, S in ((gh, H), (gw, W))]
+        a = [np.floor(np.arange(g, dtype=np.float64) * S / g + 0.5) for g, S in ((gh, H), (gw, W))]
+    elif kind == 'block':
+        G = UPSAMPLE_GRID
+        if sp is None or int(sp) <= 0 or G[0] % int(sp) or G[1] % int(sp) or (gh, gw) != (G[0] // int(sp), G[1] // int(sp)):
+            raise ValueError(f"upsample_tables: kind='block' is a {G[0]} x {G[1]} grid cut into superpixels of edge sp; "
+                             f'sp = {sp!r} does not give {gh} x {gw} cells')
+        sp = int(sp)
+        c = [(np.arange(S, dtype=np.float64) * g / S + 0.5) / sp - 0.5 for g, S in zip(G, (H, W))]
+        a = [np.floor((np.arange(n, dtype=np.float64) + 0.5) * sp * S / g) for n, g, S in zip((gh, gw), G, (H, W))]
+    else:
+        raise ValueError(f"upsample_tables: kind {kind!r}: 'corner' or 'block'")
+    ay, ax = (np.clip(t, 0, S - 1).astype(np.int32) for t, S in zip(a, (H, W)))
+    return c[0].astype(np.float32), c[1].astype(np.float32), ay, ax
+
+
+class UpsampleMap:
+    """NON-REFERENCE (include/a3d_upsample.h): the tables of joint_bilateral_upsample on the device, built once per pair of
+    sizes (upsample_tables).  Holds cy, cx (float32), ay, ax (int32) and gh, gw, H, W, kind, sp.  device='cpu' builds them
+    without a GPU (for inspection; the launch refuses them)."""
+
+    def __init__(self, gh, gw, H, W, kind, sp=None, device='cuda'):
+        cy, cx, ay, ax = upsample_tables(gh, gw, H, W, kind, sp)
+        self.gh, self.gw, self.H, self.W, self.kind, self.sp = int(gh), int(gw), int(H), int(W), kind, sp
+        self.cy, self.cx, self.ay, self.ax = (torch.from_numpy(t).to(device) for t in (cy, cx, ay, ax))
+
+
+# The defaults are choices, not derivations: sigma_space is in cells (1: the neighbouring cell weighs e^-1/2), sigma_range
+# in colour units of [0, 1] (0.1: a step of a quarter of the range in one channel is worth e^-3).  Whether they are good
+# on NYU has not been shown: no run on a data set stands behind them.
+UPSAMPLE_RADIUS, UPSAMPLE_SIGMA_SPACE, UPSAMPLE_SIGMA_RANGE = 2, 1.0, 0.1
+
+
+def upsample_params(radius, sigma_space, sigma_range):
+    """(R, inv2ss, inv2sr) as a3du_joint_bilateral_upsample takes them, or ValueError: an integer radius in 1 .. 4; sigmas
+    > 0, inf allowed (inv = 0: that term is off), whose 1 / (2 sigma^2) is finite in float32."""
+    import numpy as np
+    if int(radius) != radius or not 1 <= int(radius) <= UPSAMPLE_MAX_RADIUS:
+        raise ValueError(f'joint_bilateral_upsample: radius {radius!r} is not an integer in 1 .. {UPSAMPLE_MAX_RADIUS}')
+    inv = []
+    for name, s in (('sigma_space', sigma_space), ('sigma_range', sigma_range)):
+        s = float(s)
+        if not s > 0:
+            raise ValueError(f'joint_bilateral_upsample: {name} {s!r} must be > 0 (inf switches the term off)')
+        with np.errstate(over='ignore'):
+            v = float(np.float32(0.0 if s == float('inf') else 1.0 / (2.0 * s * s)))
+        if not v < float('inf'):
+            raise ValueError(f'joint_bilateral_upsample: 1 / (2 {name}^2) with {name} = {s!r} is not finite in float32')
+        inv.append(v)
+    return int(radius), inv[0], inv[1]
+
+
+def joint_bilateral_upsample(depth, guide, tables, radius=UPSAMPLE_RADIUS, sigma_space=UPSAMPLE_SIGMA_SPACE,
+                             sigma_range=UPSAMPLE_SIGMA_RANGE, out=None):
+    """NON-REFERENCE (a3du_joint_bilateral_upsample): depth [n, gh, gw] float32 -> out [n, H, W] float32 under guide
+    [n, H, W, 3], float32 or the uint8 pixel values k (read as fl(k / 255)); tables: an UpsampleMap of these sizes.  Every
+    output pixel is the weighted mean of the finite cells within `radius` of it, w = exp(-dist^2 / (2 sigma_space^2)
+    - |colour difference|^2 / (2 sigma_range^2)), clamped to their range; NaN where no cell counts.  sigma_range=inf:
+    distance only.  Stream-ordered, no synchronisation."""
+    who = 'joint_bilateral_upsample'
+    R, inv2ss, inv2sr = upsample_params(radius, sigma_space, sigma_range)
+    if not isinstance(tables, UpsampleMap):
+        raise TypeError(f'{who}: tables must be an ops.UpsampleMap')
+    if depth.dim() != 3 or guide.dim() != 4 or depth.numel() == 0 or guide.shape[3] != 3 or guide.shape[0] != depth.shape[0]:
+        raise ValueError(f'{who}: depth {tuple(depth.shape)} and guide {tuple(guide.shape)} must be a non-empty [n, gh, gw] '
+                         f'and [n, H, W, 3]')
+    n = depth.shape[0]
+    if tuple(depth.shape[1:]) != (tables.gh, tables.gw) or tuple(guide.shape[1:3]) != (tables.H, tables.W):
+        raise ValueError(f'{who}: depth {tuple(depth.shape)}, guide {tuple(guide.shape)}; tables made for '
+                         f'{(tables.gh, tables.gw)} -> {(tables.H, tables.W)}')
+    if out is not None and tuple(out.shape) != (n, tables.H, tables.W):
+        raise ValueError(f'{who}: out {tuple(out.shape)} must be {(n, tables.H, tables.W)}')
+    if depth.dtype != torch.float32 or guide.dtype not in (torch.float32, torch.uint8) or (
+            out is not None and out.dtype != torch.float32):
+        raise TypeError(f'{who}: depth and out float32; guide float32 or uint8')
+    ts = [t for t in (depth, guide, out, tables.cy, tables.cx, tables.ay, tables.ax) if t is not None]
+    if not all(t.is_contiguous() for t in ts):
+        raise ValueError(f'{who}: contiguous tensors only')
+    if not depth.is_cuda or any(t.device != depth.device for t in ts):
+        raise ValueError(f'{who}: all tensors on one GPU; ' + ', '.join(sorted({str(t.device) for t in ts})))
+    if out is None:
+        out = torch.empty((n, tables.H, tables.W), dtype=torch.float32, device=depth.device)
+    check(_lib.load().a3du_joint_bilateral_upsample(n, tables.gh, tables.gw, _ptr(depth), tables.H, tables.W, _ptr(guide),
+                                                    int(guide.dtype == torch.uint8), _ptr(tables.cy), _ptr(tables.cx),
+                                                    _ptr(tables.ay), _ptr(tables.ax), R, inv2ss, inv2sr, _ptr(out), _stream()),
+          'a3du_joint_bilateral_upsample')
+    return out
+
+
+class JointUpsampler:
+    """joint_bilateral_upsample with fixed parameters for predictions of one model, whatever sizes come: kind / sp as
+    upsample_tables takes them (msdn: 'corner'; dcnf: 'block' and the replica's superpixel edge); the tables of every
+    pair of sizes are built once and kept.  ValueError at construction for parameters the launch would refuse."""
+
+    def __init__(self, kind, sp=None, radius=UPSAMPLE_RADIUS, sigma_space=UPSAMPLE_SIGMA_SPACE,
+                 sigma_range=UPSAMPLE_SIGMA_RANGE):
+        upsample_params(radius, sigma_space, sigma_range)
+        self.kind, self.sp = kind, sp
+        self.radius, self.sigma_space, self.sigma_range = int(radius), float(sigma_space), float(sigma_range)
+        self.tables = {}
+
+    def __call__(self, depth, guide, out=None):
+        key = (tuple(depth.shape[1:3]), tuple(guide.shape[1:3]), depth.device)
+        tables = self.tables.get(key)
+        if tables is None:
+            tables = self.tables[key] = UpsampleMap(*key[0], *key[1], self.kind, self.sp, device=depth.device)
+        return joint_bilateral_upsample(depth, guide, tables, self.radius, self.sigma_space, self.sigma_range, out)
+
+
 def dropout_keep_mask(keep, seed, step, rate=0.5):
     """Fill the uint8 tensor `keep` with the Bernoulli(1-rate) keep mask of training step `step`."""
     check(_lib.load().a3d_dropout_keep_mask(keep.numel(), seed, step, rate, _ptr(keep), _stream()),
