@@ -190,6 +190,11 @@ UPSAMPLE_SIGNATURES = {
                                               c_float, _P, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_posterior.h declares (NON-REFERENCE extension, prefix a3dc_)
+POSTERIOR_SIGNATURES = {
+    'a3dc_crf_band_posterior': (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -209,7 +214,7 @@ def load():
                               + list(TEXTURE_SIGNATURES.items()) + list(GRADLOSS_SIGNATURES.items())
                               + list(CRF_VALID_SIGNATURES.items()) + list(FCSP_SIGNATURES.items())
                               + list(CRF_BAND_SIGNATURES.items()) + list(WINO_SIGNATURES.items())
-                              + list(UPSAMPLE_SIGNATURES.items())):
+                              + list(UPSAMPLE_SIGNATURES.items()) + list(POSTERIOR_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -20,6 +20,16 @@ or ``crf_joint``: the same prediction brought to the record image's size by join
 images (ops.joint_bilateral_upsample, include/a3d_upsample.h), judged against the same target.  The default,
 ``none``, launches nothing more and adds no key.
 
+``--condition KEEP --condition-seed S`` (NON-REFERENCE, dcnf, ``--resolution grid``, 0 < KEEP < 1) judges depth completion
+(include/a3d_posterior.h, DCNFReplica.posterior).  Per record a host generator seeded by (S, the record's index in the
+file) keeps each target superpixel with probability KEEP; the field is conditioned on the kept ones, and two outputs are
+judged over the pixels of the other superpixels only (the kept superpixels' pixels of a copy of the target are set to
+min_depth, which the metrics' validity test ``min_depth < t`` refuses): ``crf_cond``, the completed map, and
+``crf_hidden``, the unconditioned MAP depths on the same pixels.  Also ``condition_z2``, the mean over the hidden
+superpixels of (y - mean)^2 / var in float64 on the host, which is 1 for a calibrated field (var is the conditional
+variance of y itself), ``hidden_fraction`` (hidden / measured superpixels, images whose system was rejected left out) and
+``rejected_systems``.  Without the flag nothing more is launched and the report has no new key.
+
 Output: one JSON line on stdout, ``<ckptdir>/<model>_<id>/eval-<global_step>.json`` and TensorBoard scalars
 ``eval/<output>/<metric>`` (and ``eval/crf_nll``) at the checkpoint's global step.  Exit code 2 when there is nothing to
 evaluate (no checkpoint, no test split) or the request is unsupported (an unknown model, more than one process).
@@ -184,16 +194,22 @@ class DCNFEvaluator:
     outputs = OUTPUTS['dcnf']
 
     def __init__(self, replica, resolution='grid', min_depth=0., max_depth=float('inf'), clamp_lo=1e-3,
-                 clamp_hi=float('inf'), keep_predictions=False, observed_nll=False, upsample=None):
+                 clamp_hi=float('inf'), keep_predictions=False, observed_nll=False, upsample=None, condition=None):
         """observed_nll (NON-REFERENCE): also the training objective of a run with --min-depth / --max-depth, the
         likelihood of the superpixels that (min_depth, max_depth] leaves observed (DCNFReplica.nll(valid_range=...)); it
         runs last in a batch, after the metrics have read the plainly resized targets.
         upsample (NON-REFERENCE, --upsample joint): an ops.JointUpsampler; a third output `crf_joint`, the MAP depths
-        brought to the record image's size under the batch's images, is judged against the same target."""
+        brought to the record image's size under the batch's images, is judged against the same target.
+        condition (NON-REFERENCE, --condition KEEP --condition-seed S): (keep, seed); two more outputs, `crf_cond` and
+        `crf_hidden`, judged over the pixels of the superpixels hidden from the field; it runs last in a batch."""
         self.rep, self.resolution = replica, resolution
         self.upsample = upsample
         if upsample is not None:
             self.outputs = self.outputs + ('crf_joint',)
+        self.condition = condition
+        if condition is not None:
+            self.outputs = self.outputs + ('crf_cond', 'crf_hidden')
+            self.z2_sum, self.z2_n, self.measured, self.rejected = 0.0, 0, 0, 0
         self.kw = dict(min_depth=min_depth, max_depth=max_depth, clamp_lo=clamp_lo, clamp_hi=clamp_hi)
         self.observed = (float(min_depth), float(max_depth)) if observed_nll else None
         self.onll, self.nobs = [], []
@@ -219,6 +235,30 @@ class DCNFEvaluator:
         if self.observed is not None:
             self.onll.append(rep.nll(depths, n, valid_range=self.observed))
             self.nobs.append(rep.nobs.sum().reshape(1))
+        if self.condition is not None:
+            self._condition(crf, depths, n, int(sum(self.counts)) - n)
+
+    def _condition(self, crf, depths, n, first):
+        """Hide target superpixels from the field, complete them, judge the completion and the MAP on their pixels."""
+        rep = self.rep
+        keep_p, seed = self.condition
+        keep = np.stack([np.random.default_rng([int(seed), first + k]).random(rep.nsp) < keep_p for k in range(n)])
+        keep_d = torch.from_numpy(keep).to(rep.device)
+        mean, var = rep.posterior(None, depths, n, (self.kw['min_depth'], self.kw['max_depth']), keep=keep_d)
+        sp = rep.sp
+        kept_pixels = keep_d.view(n, rep.rows, rep.cols).repeat_interleave(sp, 1).repeat_interleave(sp, 2)
+        target = rep.depths240[:n].clone()                       # the validity-aware resize: NaN where nothing was measured
+        target.view(n, target.shape[1], target.shape[2])[kept_pixels] = self.kw['min_depth']
+        self.rows['crf_cond'].append(ops.depth_metrics(mean[:n], target, **self.kw))
+        self.rows['crf_hidden'].append(ops.depth_metrics(crf[:n], target, **self.kw))
+        y = rep.y.view(rep.B, rep.nsp)[:n].double().cpu().numpy()
+        m, v = (t[:n].reshape(n, rep.nsp).double().cpu().numpy() for t in (mean, var))
+        bad = rep.status[:n].cpu().numpy() != 0
+        hidden = np.isfinite(y) & ~keep & ~bad[:, None]
+        self.rejected += int(bad.sum())
+        self.measured += int((np.isfinite(y) & ~bad[:, None]).sum())
+        self.z2_n += int(hidden.sum())
+        self.z2_sum += float((((y - m) ** 2)[hidden] / v[hidden]).sum())
 
     def results(self):
         torch.cuda.synchronize()
@@ -231,6 +271,10 @@ class DCNFEvaluator:
             per_batch = torch.cat(self.onll).double().cpu().numpy()
             out['observed_nll'] = float((per_batch * n).sum() / n.sum())
             out['observed_fraction'] = float(torch.cat(self.nobs).sum().item() / (n.sum() * self.rep.nsp))
+        if self.condition is not None:
+            out['condition_z2'] = self.z2_sum / self.z2_n if self.z2_n else float('nan')
+            out['hidden_fraction'] = self.z2_n / self.measured if self.measured else float('nan')
+            out['rejected_systems'] = self.rejected
         return out
 
 
@@ -304,6 +348,14 @@ def main(argv=None):
         _say(f'--superpixel {args.superpixel} cannot go with --observed-nll yet: the likelihood of the observed superpixels '
              f'alone exists only for the dense 6 x 8 CRF (--superpixel 40).')
         return 2
+    if args.condition is not None:
+        if args.model != 'dcnf':
+            _say('--condition hides superpixels from the CRF of --model dcnf; msdn has no field to condition.')
+            return 2
+        if args.resolution != 'grid' or not 0 < args.condition < 1:
+            _say(f'--condition {args.condition} needs --resolution grid (the superpixels tile the 240 x 320 target) and '
+                 f'0 < KEEP < 1.')
+            return 2
     upsample = None
     if args.upsample == 'joint':
         try:
@@ -338,6 +390,8 @@ def main(argv=None):
     extra = {'observed_nll': True} if args.observed_nll else {}
     if upsample is not None:
         extra['upsample'] = upsample
+    if args.condition is not None:
+        extra['condition'] = (args.condition, args.condition_seed)
     ev = evaluator(replica, args.resolution, args.min_depth, args.max_depth, args.clamp_lo, args.clamp_hi,
                    keep_predictions=bool(args.predictions), **extra)
     op = EvalOp(pipeline, args.batchsize, dev)
@@ -364,6 +418,8 @@ def main(argv=None):
     if upsample is not None:
         out.update(upsample='joint', radius=upsample.radius, sigma_space=upsample.sigma_space,
                    sigma_range=upsample.sigma_range)
+    if args.condition is not None:
+        out.update(condition=args.condition, condition_seed=args.condition_seed)
     if args.predictions:
         np.save(args.predictions, torch.cat(ev.predictions).cpu().numpy() if ev.predictions else
                 np.zeros((0,) + ev.prediction_shape, np.float32))
@@ -372,6 +428,8 @@ def main(argv=None):
         json.dump(out, f, indent=1)
     events = summary.EventFileWriter(run_dir)
     scalars = {f'eval/{o}/{k}': float(v) for o in ev.outputs for k, v in res[o].items()}
+    if 'condition_z2' in res:
+        scalars['eval/condition_z2'] = res['condition_z2']
     if 'crf_nll' in res:
         scalars['eval/crf_nll'] = res['crf_nll']
     if 'observed_nll' in res:
@@ -415,6 +473,12 @@ def parse_args(argv=None):
                         '12 x 16 or 24 x 32 depths per image). Checkpoints hold no grid: one trained at 40 evaluates at 10 and '
                         'the reverse. 20 and 10 need a checkpoint of --unary fcsp; crf_nll is then the banded likelihood, '
                         'not comparable with the value at 40.')
+    p.add_argument('--condition', default=None, type=float, metavar='KEEP',
+                   help='NON-REFERENCE, dcnf, --resolution grid: judge depth completion. Each target superpixel is kept with '
+                        'probability KEEP (0 < KEEP < 1), the field is conditioned on the kept ones, and crf_cond (completed) '
+                        'and crf_hidden (the plain MAP) are judged on the pixels of the hidden ones.')
+    p.add_argument('--condition-seed', default=0, type=int,
+                   help='--condition: the masks are drawn on the host from (this seed, the record\'s index).')
     add_upsample_args(p, ['none', 'joint'], 'none',
                       'NON-REFERENCE: joint also judges a third output, fine_joint (msdn) or crf_joint (dcnf): the prediction '
                       'brought to the record image\'s size by joint bilateral upsampling under the image '

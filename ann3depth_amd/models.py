@@ -1669,6 +1669,20 @@ class DCNFReplica:
             (mean, per, dz), dr = ops.crf_loss(*args, DCNF_EPSILON), None
         return mean, per, dz, dr
 
+    def _predict_forward(self, images, n, who):
+        """predict()'s network part: z of rows [0, n) of images (default all) and of zero images in rows n .. B, and the
+        pair weights in self.r.  Returns n."""
+        B, u = self.B, self.unary
+        n = images.shape[0] if n is None else int(n)
+        if not 0 < n <= min(B, images.shape[0]):
+            raise ValueError(f'{who}: n = {n} rows of a batch of {images.shape[0]} images, replica batch {B}')
+        ops.resize_bilinear_tf1(images[:n], u.resized[:n])                                # src/models.py:180
+        if n < B:
+            u.resized[n:].zero_()
+        u.forward_resized(record_argmax=False)
+        self._pairwise()
+        return n
+
     def predict(self, images, n=None):
         """The model's depths for a batch of images, without targets: (unary, crf), each [B, rows, cols] float32 (views
         of this replica's buffers, valid until its next forward).  unary is z, what the reference draws as `Output`
@@ -1679,19 +1693,66 @@ class DCNFReplica:
         self.status where the system was singular (that row of crf is NaN).  Weights, gradients and global_step are
         left as they are."""
         B, u = self.B, self.unary
-        n = images.shape[0] if n is None else int(n)
-        if not 0 < n <= min(B, images.shape[0]):
-            raise ValueError(f'predict: n = {n} rows of a batch of {images.shape[0]} images, replica batch {B}')
-        ops.resize_bilinear_tf1(images[:n], u.resized[:n])                                # src/models.py:180
-        if n < B:
-            u.resized[n:].zero_()
-        u.forward_resized(record_argmax=False)
-        self._pairwise()
+        self._predict_forward(images, n, 'predict')
         if self.banded:
             ops.crf_band_map(u.z.view(B, self.nsp), self.r, self.left, self.right, self.band, self.crf, self.status)
         else:
             self.crf, self.status = ops.crf_map(u.z.view(B, self.nsp), self.r, self.left, self.right, self.crf, self.status)
         return u.z.view(B, self.rows, self.cols), self.crf.view(B, self.rows, self.cols)
+
+    def posterior(self, images, depths=None, n=None, valid_range=None, want_var=True, keep=None):
+        """NON-REFERENCE (include/a3d_posterior.h): the field as a distribution at prediction -> (mean, var), each
+        [B, rows, cols] float32 (var None without want_var; valid until the next call).  Runs predict()'s forward and pair
+        weights (images None: the z and r that predict() or posterior() just left, n given), then ops.crf_band_posterior,
+        at all three grids (6 x 8 is a band of 8) and for both unary forms.  Without
+        depths mean is the MAP estimate (predict()'s crf on the banded grids, bit for bit) and var the field's marginal
+        variance A^-1_ii / 2.  With depths [m, H, W, 1] the field is conditioned on the superpixels they measure: the
+        targets of _targets(depths, n, valid_range), which needs valid_range = (min_depth, max_depth); mean is the target on
+        a measured superpixel and the conditional mean elsewhere, var 0 and the conditional variance.  Leaves the numbers of
+        measured superpixels in self.nobs and, per image, 1 in self.status where the system was not positive definite (NaN
+        rows; at superpixel 40 the pair weights are not projected onto >= 0, and an indefinite A is no distribution).  Rows
+        n .. B are those of a zero image without depths.  keep ([n, nsp] bool on the device, with depths): only the targets
+        it marks are conditioned on, the others are hidden from the field; self.y keeps every target (NaN where the depth
+        map measures none).  Training state, self.valid_range included, is left as it is."""
+        B = self.B
+        if images is None and (self.r is None or n is None):
+            raise ValueError('posterior: images None reuses the last predict(): call it first and pass n')
+        n = images.shape[0] if n is None else int(n)
+        m = B if images is None else images.shape[0]
+        y = None
+        if depths is not None:
+            if valid_range is None:
+                raise ValueError('posterior: depths need valid_range = (min_depth, max_depth), which says what a hole is')
+            lo, hi = (float(v) for v in valid_range)
+            if not lo <= hi:
+                raise ValueError(f'valid_range {valid_range!r}: (min_depth, max_depth) with min_depth <= max_depth')
+            if not 0 < n <= min(B, m, depths.shape[0]):
+                raise ValueError(f'posterior: n = {n} rows of {m} images and {depths.shape[0]} depth maps, '
+                                 f'replica batch {B}')
+        elif valid_range is not None or keep is not None:
+            raise ValueError('posterior: valid_range or keep without depths')
+        if keep is not None and (keep.dtype != torch.bool or tuple(keep.shape) != (n, self.nsp)):
+            raise ValueError(f'posterior: keep {tuple(keep.shape)} {keep.dtype} must be bool {(n, self.nsp)}')
+        if images is not None:
+            self._predict_forward(images, n, 'posterior')
+        elif not 0 < n <= B:
+            raise ValueError(f'posterior: n = {n}, replica batch {B}')
+        if depths is not None:
+            self._targets(depths, n, (lo, hi))
+            y = self.y.view(B, self.nsp)
+            if n < B:
+                y[n:].fill_(float('nan'))
+            if keep is not None:
+                y = y.clone()
+                y[:n].masked_fill_(~keep, float('nan'))
+        if getattr(self, 'post_mean', None) is None:
+            self.post_mean = torch.empty((B, self.nsp), device=self.device)
+            self.post_var = torch.empty((B, self.nsp), device=self.device)
+        mean, var, self.nobs, status = ops.crf_band_posterior(
+            self.unary.z.view(B, self.nsp), y, self.r, self.left, self.right, self.band, want_var=want_var,
+            mean=self.post_mean, var=self.post_var if want_var else None)
+        self.status.copy_(status)
+        return mean.view(B, self.rows, self.cols), None if var is None else var.view(B, self.rows, self.cols)
 
     def nll(self, depths, n, valid_range=None):
         """The training objective (src/models.py:129-177) on rows [0, n) of the batch predict() just ran, from the z

@@ -929,7 +929,31 @@ def crf_band_map(z, r, left, right, band, mu=None, status=None):
     return mu, status
 
 
-FCSP_MAX_SP = 64         # A3DF_MAX_SP: one lane of a wave per window pixel, 2 KiB of LDS for a block's counts
+def crf_band_posterior(z, y, r, left, right, band, want_var=True, mean=None, var=None):
+    """NON-REFERENCE (a3dc_crf_band_posterior): the field's mean and variance per superpixel given the superpixels whose y
+    is finite (y None: none is), A banded as for crf_band_nll: returns (mean [n,P], var [n,P] or None without want_var,
+    nobs [n] int32, status [n] int32).  z, y [n,P], r [n,Q] float32; left, right [Q] int32.  On an observed superpixel mean
+    is y's bits and var +0; on the others the conditional mean A_MM^-1 (z_M - A_MO y_O) and 1/2 diag A_MM^-1.  With nothing
+    observed mean is crf_band_map's mu bit for bit.  An image whose system is not positive is NaN with status 1; a pair
+    index outside [0, P) or farther apart than band turns all of it into NaN.  mean, var: buffers to write into."""
+    mean = mean if mean is not None else torch.empty_like(z)
+    if var is not None and not want_var:
+        raise ValueError('crf_band_posterior: a var buffer without want_var')
+    if want_var and var is None:
+        var = torch.empty_like(z)
+    others = tuple(t for t in (y, mean, var) if t is not None)
+    if any(not isinstance(t, torch.Tensor) for t in others):
+        raise TypeError('crf_band_posterior: y, mean, var are tensors (y may be None)')
+    n, nsp = _check_band('crf_band_posterior', z, r, left, right, band, others)
+    nobs = torch.empty((n,), dtype=torch.int32, device=z.device)
+    status = torch.empty((n,), dtype=torch.int32, device=z.device)
+    check(_lib.load().a3dc_crf_band_posterior(n, nsp, int(band), _ptr(z), _ptr(y), _ptr(r), _ptr(left), _ptr(right),
+                                              left.numel(), _ptr(mean), _ptr(var), _ptr(nobs), _ptr(status), _stream()),
+          'a3dc_crf_band_posterior')
+    return mean, var, nobs, status
+
+
+FCSP_MAX_SP = 64       # A3DF_MAX_SP: one lane of a wave per window pixel, 2 KiB of LDS for a block's counts
 
 
 class FcspMap:

@@ -2,7 +2,7 @@
 
     python -m ann3depth_amd.predict --model msdn|dcnf [--id r1 | --checkpoint PATH] [--superpixel 40|20|10]
         [--precision ...] [--batchsize B] [--upsample joint|bilinear|none] [--radius R --sigma-space S --sigma-range S]
-        --out DIR IMAGE.png ...
+        [--uncertainty] [--depths DIR --min-depth LO --max-depth HI] --out DIR IMAGE.png ...
 
 Each image is read with png.imread (8-bit RGB; grey is replicated to three channels, alpha is dropped), consecutive
 images of one size run together in batches of up to B through the replica's predict() on their uint8 pixels, and the
@@ -16,7 +16,20 @@ over its finite pixels with the rounding tools/data_preprocessor.py uses for dep
 is not finite becomes 0).  One JSON line on stdout names the files, their sizes and the count of non-finite pixels, and
 for dcnf `singular_systems`.  Exit code 2, before a GPU is touched, when there is nothing to do (no checkpoint, no image,
 an unreadable image) or the request is unsupported (an unknown model, more than one process, a --superpixel the
-checkpoint's form cannot run)."""
+checkpoint's form cannot run).
+
+dcnf is a probabilistic model, y ~ N(mu, A^-1 / 2) over the superpixels (NON-REFERENCE, include/a3d_posterior.h,
+DCNFReplica.posterior); msdn has no distribution, so both flags are refused for it:
+  --uncertainty   also writes <out>/<stem>-sigma.npy and .png: the field's standard deviation per superpixel, sqrt(var),
+                  brought to the output size exactly as the depth map is (under --upsample joint by the same upsampler).
+                  The depth files are the bytes they are without the flag.
+  --depths DIR    depth completion: DIR/<stem>.npy, float32 [H, W] of any size, is a measured depth map with holes, a
+                  pixel a hole where it is not finite or outside (--min-depth, --max-depth].  The field is conditioned on
+                  the superpixels the file measures (at least half of their pixels, the replica's min_valid): they come
+                  back as their block means, the others as the conditional mean, and sigma is 0 and the conditional
+                  standard deviation.  A missing file, or one of another rank or dtype, exits 2 before any GPU work.
+With either flag the JSON line gains `uncertainty`, `conditioned`, `observed_fraction` (the share of superpixels a file
+measured; 0 without --depths) and `rejected_systems` (images whose system was not positive definite: NaN maps)."""
 import argparse
 import json
 import os
@@ -62,15 +75,26 @@ def depth_png(depth):
     return img
 
 
-def batches(images, B):
-    """Runs of consecutive images of one size, at most B long: lists of indices."""
+def batches(images, B, also=None):
+    """Runs of consecutive images of one size, at most B long: lists of indices.  also: a second list of arrays (the
+    measured depth maps) whose sizes must agree within a run too."""
+    def key(i):
+        return (images[i].shape, None if also is None else also[i].shape)
     out = []
-    for i, img in enumerate(images):
-        if out and len(out[-1]) < B and images[out[-1][0]].shape == img.shape:
+    for i in range(len(images)):
+        if out and len(out[-1]) < B and key(out[-1][0]) == key(i):
             out[-1].append(i)
         else:
             out.append([i])
     return out
+
+
+def read_depth(path):
+    """A measured depth map: float32 [H, W], holes as they are.  ValueError for anything else."""
+    a = np.load(path, allow_pickle=False)
+    if a.dtype != np.float32 or a.ndim != 2 or a.size == 0:
+        raise ValueError(f'not a float32 [H, W] array ({a.dtype}, shape {a.shape})')
+    return np.ascontiguousarray(a)
 
 
 def main(argv=None):
@@ -83,6 +107,14 @@ def main(argv=None):
         return 2
     if args.batchsize <= 0:
         _say(f'--batchsize {args.batchsize} must be positive.')
+        return 2
+    posterior = args.uncertainty or bool(args.depths)
+    if posterior and args.model != 'dcnf':
+        _say(f'--uncertainty and --depths read the distribution of the CRF of --model dcnf, y ~ N(mu, A^-1 / 2): '
+             f'{args.model} is a regression without one.')
+        return 2
+    if args.depths and not (args.min_depth < args.max_depth):
+        _say(f'--depths needs --min-depth < --max-depth (a pixel is measured inside ({args.min_depth}, {args.max_depth}]).')
         return 2
     upsample = None
     if args.upsample == 'joint':
@@ -115,34 +147,66 @@ def main(argv=None):
     if len(set(stems)) != len(stems):
         _say(f'two images share a file stem and would be written to one place: {sorted(s for s in set(stems) if stems.count(s) > 1)}')
         return 2
+    measured = None
+    if args.depths:
+        measured = []
+        for stem in stems:
+            path = os.path.join(args.depths, stem + '.npy')
+            try:
+                measured.append(read_depth(path))
+            except Exception as e:                    # a missing file, a pickle, a text file, another rank or dtype
+                _say(f'--depths: cannot use {path}: {e}')
+                return 2
     restored = restore_replica(args, ckpt, _say)
     if restored is None:
         return 2
     replica = restored[0]
     dev = replica.device
     os.makedirs(args.out, exist_ok=True)
-    files, singular = [], 0
-    for idx in batches(images, args.batchsize):
+    files, singular, rejected, observed = [], 0, 0, 0
+
+    def to_size(grid, pixels, n):
+        """[B, gh, gw] on the model's grid -> the n maps at the output size, as --upsample says."""
+        H, W = pixels.shape[1:3]
+        if upsample is not None:
+            return upsample(grid[:n], pixels)
+        if args.upsample == 'bilinear':
+            return ops.resize_bilinear_tf1(grid[:n].reshape(n, grid.shape[1], grid.shape[2], 1),
+                                           torch.empty((n, H, W, 1), device=dev)).view(n, H, W)
+        return grid[:n]
+
+    for idx in batches(images, args.batchsize, measured):
         n = len(idx)
         pixels = torch.from_numpy(np.stack([images[i] for i in idx])).to(dev)
         pred = replica.predict(pixels, n)[1]                       # fine (msdn) or crf (dcnf), [B, gh, gw]
         if args.model == 'dcnf':
             singular += int(replica.status[:n].sum().item())
         H, W = pixels.shape[1:3]
-        if upsample is not None:
-            full = upsample(pred[:n], pixels)
-        elif args.upsample == 'bilinear':
-            full = ops.resize_bilinear_tf1(pred[:n].reshape(n, pred.shape[1], pred.shape[2], 1),
-                                           torch.empty((n, H, W, 1), device=dev)).view(n, H, W)
-        else:
-            full = pred[:n]
-        full = full.cpu().numpy()
+        sigma = None
+        if posterior:                                  # from the z and r predict() left
+            holes = None
+            if measured is not None:
+                holes = torch.from_numpy(np.stack([measured[i] for i in idx])[..., None]).to(dev)
+            mean, var = replica.posterior(None, holes, n, (args.min_depth, args.max_depth) if holes is not None else None,
+                                          want_var=args.uncertainty)
+            rejected += int(replica.status[:n].sum().item())
+            observed += int(replica.nobs[:n].sum().item())
+            if holes is not None:
+                pred = mean                                # without --depths the depth map stays predict()'s, byte for byte
+            if var is not None:
+                sigma = to_size(torch.sqrt(var), pixels, n).cpu().numpy()
+        full = to_size(pred, pixels, n).cpu().numpy()
         for k, i in enumerate(idx):
             base = os.path.join(args.out, stems[i] + '-depth')
             np.save(base + '.npy', full[k])
             png.imsave(base + '.png', depth_png(full[k]))
             files.append({'image': args.images[i], 'image_size': [int(H), int(W)], 'npy': base + '.npy', 'png': base + '.png',
                           'size': [int(v) for v in full[k].shape], 'nonfinite': int((~np.isfinite(full[k])).sum())})
+            if sigma is not None:
+                base = os.path.join(args.out, stems[i] + '-sigma')
+                np.save(base + '.npy', sigma[k])
+                png.imsave(base + '.png', depth_png(sigma[k]))
+                files[-1].update(sigma_npy=base + '.npy', sigma_png=base + '.png')
     out = {'checkpoint': ckpt, 'global_step': replica.global_step, 'model': args.model, 'precision': args.precision,
            'output': OUTPUTS[args.model][1], 'upsample': args.upsample, 'files': files,
            'nonfinite': int(sum(f['nonfinite'] for f in files))}
@@ -150,6 +214,11 @@ def main(argv=None):
         out.update(radius=upsample.radius, sigma_space=upsample.sigma_space, sigma_range=upsample.sigma_range)
     if args.model == 'dcnf':
         out.update(superpixel=args.superpixel, singular_systems=singular)
+    if posterior:
+        out.update(uncertainty=bool(args.uncertainty), conditioned=measured is not None,
+                   observed_fraction=observed / float(len(images) * replica.nsp), rejected_systems=rejected)
+        if measured is not None:
+            out.update(min_depth=args.min_depth, max_depth=args.max_depth)
     print(json.dumps(out), flush=True)
     return 0
 
@@ -169,6 +238,14 @@ def parse_args(argv=None):
     p.add_argument('--superpixel', default=40, type=int, choices=[40, 20, 10],
                    help='NON-REFERENCE unless 40, dcnf: the edge of the superpixels (6 x 8, 12 x 16 or 24 x 32 depths per image '
                         'before upsampling); 20 and 10 need a checkpoint of --unary fcsp.')
+    p.add_argument('--uncertainty', action='store_true',
+                   help='NON-REFERENCE, dcnf: also write <stem>-sigma.npy / .png, the standard deviation of the CRF\'s field per '
+                        'superpixel, brought to the output size as the depth map is.')
+    p.add_argument('--depths', default='', type=str,
+                   help='NON-REFERENCE, dcnf: depth completion. DIR/<stem>.npy (float32 [H, W], any size) is a measured depth '
+                        'map with holes; the field is conditioned on the superpixels it measures.')
+    p.add_argument('--min-depth', default=0., type=float, help='--depths: a pixel is measured if its value is > this ...')
+    p.add_argument('--max-depth', default=float('inf'), type=float, help='... and <= this, and finite.')
     add_upsample_args(p, ['joint', 'bilinear', 'none'], 'joint',
                       'How the prediction reaches the image\'s size: joint (NON-REFERENCE: joint bilateral upsampling under '
                       'the image), bilinear (the legacy resize), none (it stays on the model\'s grid).')
