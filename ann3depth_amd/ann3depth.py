@@ -212,10 +212,7 @@ class Session:
         if latest:
             self.log.info(f'Restoring {latest}')
             try:
-                if tfckpt.is_bundle(latest):                  # a checkpoint written by TensorFlow (or --tf-checkpoints)
-                    rep.load_tf_variables(tfckpt.read_bundle(latest))
-                else:
-                    rep.load_state_dict(torch.load(latest, map_location=rep.device))
+                load_checkpoint(rep, *read_checkpoint(latest, rep.device))
             except ValueError:                                # refused (dcnf: a [2,1] / [3,1] pairwise kernel across
                 self.op.pipeline.close()                      # --pairwise-texture, a dense/kernel across --unary): no __exit__
                 raise
@@ -241,15 +238,14 @@ class Session:
         the next step; whether a rank's reader FAILED (CRC mismatch, malformed record: raised on every rank, never
         mistaken for a clean end of input); whether the chief wants a checkpoint now."""
         rep = train_op.replica
-        end = getattr(train_op, 'end', None)
-        due = end is not None and end[0] <= train_op.k
-        dry = due and isinstance(end[1], data.OutOfRangeError)
-        failed = due and not dry
+        due = train_op.feed.due()
+        dry = isinstance(due, data.OutOfRangeError)
+        failed = due is not None and not dry
         stop, err, save = rep.reducer.agree_all([self.sig.signal_received or (1 if dry else 0), int(failed),
                                                  int(want_save)])
         if err:
             if failed:
-                raise end[1]
+                raise due
             raise RuntimeError('the input pipeline of another replica failed; stopping with it')
         if stop:
             self.stop = True
@@ -387,6 +383,22 @@ def latest_checkpoint(ckptdir):
     if name and (os.path.exists(path) or tfckpt.is_bundle(path)):    # ours (.pt file) or TensorFlow's (bundle prefix)
         return path
     return None
+
+
+def read_checkpoint(path, map_location):
+    """The state a checkpoint holds -> (state, bundle): a TF bundle prefix (written by TensorFlow or --tf-checkpoints) is
+    read into name -> ndarray on the host, anything else is a .pt file of name -> tensor, loaded to map_location."""
+    if tfckpt.is_bundle(path):
+        return tfckpt.read_bundle(path), True
+    return torch.load(path, map_location=map_location), False
+
+
+def load_checkpoint(replica, state, bundle):
+    """Put what read_checkpoint returned into a replica."""
+    if bundle:
+        replica.load_tf_variables(state)
+    else:
+        replica.load_state_dict(state)
 
 
 def parse_args(argv=None):

@@ -35,7 +35,6 @@ Output: one JSON line on stdout, ``<ckptdir>/<model>_<id>/eval-<global_step>.jso
 evaluate (no checkpoint, no test split) or the request is unsupported (an unknown model, more than one process).
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -43,8 +42,9 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, data, ops, summary, tfckpt
-from .ann3depth import latest_checkpoint
+from . import data, ops, summary, tfckpt
+from .ann3depth import latest_checkpoint, load_checkpoint, read_checkpoint
+from .feed import DeviceFeed
 
 OUTPUTS = {'msdn': ('coarse', 'fine'), 'dcnf': ('unary', 'crf')}
 
@@ -54,86 +54,53 @@ def _say(msg):
 
 
 class EvalOp:
-    """The test split's batches on the device, in file order.  Like models.TrainOp: the staging pool is pinned memory,
-    a batch is DMA'd on a copy stream into one of two device buffers, and batch k+1 is in flight while batch k computes.
-    run(fn) calls fn(images, depths, n) on the current stream with batch k's device tensors (B rows, the first n of them
-    this batch's records; each uint8 when every record of the batch staged that feature as pixel values) and returns
-    what fn returns; OutOfRangeError after the last batch."""
+    """The test split's batches on the device, in file order, through a feed.DeviceFeed.  run(fn) calls
+    fn(images, depths, n) on the current stream with batch k's device tensors (B rows, the first n of them this batch's
+    records; each uint8 when every record of the batch staged that feature as pixel values) and returns what fn returns;
+    OutOfRangeError after the last batch."""
 
     def __init__(self, pipeline, batchsize, device):
         self.pipeline, self.B = pipeline, batchsize
-        pipeline.allocate(lambda shape: torch.empty(shape, dtype=torch.float32).pin_memory().numpy(),
-                          lambda shape: torch.empty(shape, dtype=torch.uint8).pin_memory().numpy())
-        self.pool = (torch.from_numpy(pipeline.images), torch.from_numpy(pipeline.depths))
-        self.pool_u8 = None
-        if pipeline.images_u8 is not None:
-            self.pool_u8 = (torch.from_numpy(pipeline.images_u8), torch.from_numpy(pipeline.depths_u8))
-        self.dev = [tuple(torch.empty((batchsize,) + tuple(p.shape[1:]), device=device) for p in self.pool)
-                    for _ in range(2)]
-        self.dev_u8 = [tuple(torch.empty((batchsize,) + tuple(p.shape[1:]), device=device, dtype=torch.uint8)
-                             for p in self.pool) for _ in range(2)] if self.pool_u8 is not None else None
-        self.cur = [None, None]
-        self.copy_stream = torch.cuda.Stream(device=device)
-        self.copied = [None, None]
-        self.consumed = [None, None]
-        self.held = [[], []]
-        self.k = 0
-        self.end = None
-        self._prefetch(0)
-        self._prefetch(1)
-
-    def _prefetch(self, j):
-        if self.end is not None:
-            return
-        i = j & 1
-        try:
-            slots = self.pipeline.dequeue()
-        except BaseException as e:          # raised when batch j would have been consumed
-            self.end = (j, e)
-            return
-        if self.consumed[i] is not None:
-            self.copy_stream.wait_event(self.consumed[i])
-        pl = self.pipeline
-        cur = []
-        kinds = int(np.bitwise_and.reduce(pl.kind[slots])) if self.pool_u8 is not None else 0
-        for which in (0, 1):
-            as_u8 = bool(kinds & (1 << which))
-            if not as_u8 and self.pool_u8 is not None:
-                for s in slots:
-                    pl.materialise(s, which)
-            cur.append((self.dev_u8 if as_u8 else self.dev)[i][which])
-        ids = (ctypes.c_int32 * len(slots))(*slots)
-        with torch.cuda.stream(self.copy_stream):
-            for which in (0, 1):
-                src = (self.pool_u8 if cur[which].dtype == torch.uint8 else self.pool)[which]
-                ops.check(_lib.load().a3d_h2d_gather(cur[which].data_ptr(), src.data_ptr(), ids, len(slots), len(src),
-                                                     src[0].numel() * src.element_size(), self.copy_stream.cuda_stream),
-                          'a3d_h2d_gather')
-            ev = torch.cuda.Event()
-            ev.record(self.copy_stream)
-        self.cur[i] = tuple(cur)
-        self.copied[i] = ev
-        self.held[i] = slots
+        self.feed = DeviceFeed(pipeline, batchsize, device)
+        self.feed.start()
 
     def run(self, fn):
-        i = self.k & 1
-        if self.end is not None and self.end[0] == self.k:
-            raise self.end[1]
-        cur = torch.cuda.current_stream()
-        cur.wait_event(self.copied[i])
-        out = fn(self.cur[i][0], self.cur[i][1], len(self.held[i]))
-        ev = torch.cuda.Event()
-        ev.record(cur)
-        self.consumed[i] = ev
-        self.copied[i].synchronize()
-        self.pipeline.release(self.held[i])
-        self.held[i] = []
-        self.k += 1
-        self._prefetch(self.k + 1)
+        images, depths, n, _ = self.feed.take()
+        out = fn(images, depths, n)
+        self.feed.give_back()
         return out
 
 
-class Evaluator:
+class MetricRows:
+    """What the evaluators of both models keep: the metric rows of every output per batch, the batch sizes and, when
+    asked for, the predictions."""
+
+    def __init__(self, replica, resolution, more_outputs, prediction_shape, min_depth, max_depth, clamp_lo, clamp_hi,
+                 keep_predictions):
+        self.rep, self.resolution = replica, resolution
+        self.outputs = self.outputs + more_outputs
+        self.kw = dict(min_depth=min_depth, max_depth=max_depth, clamp_lo=clamp_lo, clamp_hi=clamp_hi)
+        self.rows = {o: [] for o in self.outputs}
+        self.counts = []
+        self.predictions = [] if keep_predictions else None
+        self.prediction_shape = prediction_shape
+
+    def judge(self, name, out, n, target):
+        """Append the metric rows of out[:n] against target under output `name`."""
+        self.rows[name].append(ops.depth_metrics(out[:n], target, **self.kw))
+
+    def mean(self, per_batch):
+        """The mean over the records of per-batch means ([1] device tensors, one per batch)."""
+        n = np.asarray(self.counts, np.float64)
+        per_batch = torch.cat(per_batch).double().cpu().numpy()
+        return float((per_batch * n).sum() / n.sum())
+
+    def results(self):
+        torch.cuda.synchronize()
+        return {name: ops.summarize_depth_metrics(torch.cat(self.rows[name])) for name in self.outputs}
+
+
+class Evaluator(MetricRows):
     """MSDN's per-batch work: predict, targets on the grid (the training step's resize), metric rows, the objective."""
     outputs = OUTPUTS['msdn']
 
@@ -142,26 +109,19 @@ class Evaluator:
         """upsample (NON-REFERENCE, --upsample joint): an ops.JointUpsampler; a third output `fine_joint`, the fine map
         brought to the record image's size under the batch's images, is judged against the same target."""
         from .models import OUT_H, OUT_W
-        self.rep, self.resolution = replica, resolution
+        super().__init__(replica, resolution, ('fine_joint',) if upsample is not None else (), (OUT_H, OUT_W), min_depth,
+                         max_depth, clamp_lo, clamp_hi, keep_predictions)
         self.upsample = upsample
-        if upsample is not None:
-            self.outputs = self.outputs + ('fine_joint',)
-        self.kw = dict(min_depth=min_depth, max_depth=max_depth, clamp_lo=clamp_lo, clamp_hi=clamp_hi)
-        dev = replica.device
-        self.t = torch.empty((replica.B, OUT_H, OUT_W), device=dev)
+        self.t = torch.empty((replica.B, OUT_H, OUT_W), device=replica.device)
         self.silog_ws = {}              # per batch size (a3d_silog_loss_fwd's per-sample sums and partials)
-        self.rows = {o: [] for o in self.outputs}
         self.losses = {o: [] for o in OUTPUTS['msdn']}
-        self.counts = []
-        self.predictions = [] if keep_predictions else None
-        self.prediction_shape = (OUT_H, OUT_W)
 
     def __call__(self, images, depths, n):
         coarse, fine = self.rep.predict(images, n)
         ops.resize_bilinear_tf1(depths[:n], self.t[:n].view(n, self.t.shape[1], self.t.shape[2], 1))
         target = self.t[:n] if self.resolution == 'grid' else depths[:n]
         for name, out in zip(OUTPUTS['msdn'], (coarse, fine)):
-            self.rows[name].append(ops.depth_metrics(out[:n], target, **self.kw))
+            self.judge(name, out, n, target)
             loss = torch.empty(1, device=out.device)
             ws = self.silog_ws.get(n)
             if ws is None:
@@ -169,25 +129,19 @@ class Evaluator:
             ops.silog_loss_fwd(out[:n], self.t[:n], loss, ws)                    # the mean over these n images
             self.losses[name].append(loss)
         if self.upsample is not None:
-            self.rows['fine_joint'].append(ops.depth_metrics(self.upsample(fine[:n], images[:n]), target, **self.kw))
+            self.judge('fine_joint', self.upsample(fine[:n], images[:n]), n, target)
         self.counts.append(n)
         if self.predictions is not None:
             self.predictions.append(fine[:n].clone())
 
     def results(self):
-        torch.cuda.synchronize()
-        out = {}
-        n = np.asarray(self.counts, np.float64)
-        for name in self.outputs:
-            res = ops.summarize_depth_metrics(torch.cat(self.rows[name]))
-            if name in self.losses:
-                per_batch = torch.cat(self.losses[name]).double().cpu().numpy()
-                res['silog'] = float((per_batch * n).sum() / n.sum())
-            out[name] = res
+        out = super().results()
+        for name, losses in self.losses.items():
+            out[name]['silog'] = self.mean(losses)
         return out
 
 
-class DCNFEvaluator:
+class DCNFEvaluator(MetricRows):
     """DCNF's per-batch work: predict (unary z and the field's MAP depths), the objective on the same batch, which also
     leaves the targets at 240 x 320, and the metric rows of both outputs; the replica's rows x cols predictions are sampled at the
     target's pixels inside a3d_depth_metrics."""
@@ -202,22 +156,15 @@ class DCNFEvaluator:
         brought to the record image's size under the batch's images, is judged against the same target.
         condition (NON-REFERENCE, --condition KEEP --condition-seed S): (keep, seed); two more outputs, `crf_cond` and
         `crf_hidden`, judged over the pixels of the superpixels hidden from the field; it runs last in a batch."""
-        self.rep, self.resolution = replica, resolution
-        self.upsample = upsample
-        if upsample is not None:
-            self.outputs = self.outputs + ('crf_joint',)
-        self.condition = condition
+        super().__init__(replica, resolution, (('crf_joint',) if upsample is not None else ()) +
+                         (('crf_cond', 'crf_hidden') if condition is not None else ()), (replica.rows, replica.cols),
+                         min_depth, max_depth, clamp_lo, clamp_hi, keep_predictions)
+        self.upsample, self.condition = upsample, condition
         if condition is not None:
-            self.outputs = self.outputs + ('crf_cond', 'crf_hidden')
             self.z2_sum, self.z2_n, self.measured, self.rejected = 0.0, 0, 0, 0
-        self.kw = dict(min_depth=min_depth, max_depth=max_depth, clamp_lo=clamp_lo, clamp_hi=clamp_hi)
         self.observed = (float(min_depth), float(max_depth)) if observed_nll else None
         self.onll, self.nobs = [], []
-        self.rows = {o: [] for o in self.outputs}
         self.nll, self.status = [], []
-        self.counts = []
-        self.predictions = [] if keep_predictions else None
-        self.prediction_shape = (replica.rows, replica.cols)
 
     def __call__(self, images, depths, n):
         rep = self.rep
@@ -225,9 +172,9 @@ class DCNFEvaluator:
         self.nll.append(rep.nll(depths, n))                                      # the mean over these n images
         target = rep.depths240[:n] if self.resolution == 'grid' else depths[:n]
         for name, out in zip(OUTPUTS['dcnf'], (unary, crf)):
-            self.rows[name].append(ops.depth_metrics(out[:n], target, **self.kw))
+            self.judge(name, out, n, target)
         if self.upsample is not None:
-            self.rows['crf_joint'].append(ops.depth_metrics(self.upsample(crf[:n], images[:n]), target, **self.kw))
+            self.judge('crf_joint', self.upsample(crf[:n], images[:n]), n, target)
         self.status.append(rep.status[:n].clone())
         self.counts.append(n)
         if self.predictions is not None:
@@ -249,8 +196,8 @@ class DCNFEvaluator:
         kept_pixels = keep_d.view(n, rep.rows, rep.cols).repeat_interleave(sp, 1).repeat_interleave(sp, 2)
         target = rep.depths240[:n].clone()                       # the validity-aware resize: NaN where nothing was measured
         target.view(n, target.shape[1], target.shape[2])[kept_pixels] = self.kw['min_depth']
-        self.rows['crf_cond'].append(ops.depth_metrics(mean[:n], target, **self.kw))
-        self.rows['crf_hidden'].append(ops.depth_metrics(crf[:n], target, **self.kw))
+        self.judge('crf_cond', mean, n, target)
+        self.judge('crf_hidden', crf, n, target)
         y = rep.y.view(rep.B, rep.nsp)[:n].double().cpu().numpy()
         m, v = (t[:n].reshape(n, rep.nsp).double().cpu().numpy() for t in (mean, var))
         bad = rep.status[:n].cpu().numpy() != 0
@@ -261,16 +208,12 @@ class DCNFEvaluator:
         self.z2_sum += float((((y - m) ** 2)[hidden] / v[hidden]).sum())
 
     def results(self):
-        torch.cuda.synchronize()
-        n = np.asarray(self.counts, np.float64)
-        out = {name: ops.summarize_depth_metrics(torch.cat(self.rows[name])) for name in self.outputs}
-        per_batch = torch.cat(self.nll).double().cpu().numpy()
-        out['crf_nll'] = float((per_batch * n).sum() / n.sum())
+        out = super().results()
+        out['crf_nll'] = self.mean(self.nll)
         out['singular_systems'] = int(torch.cat(self.status).sum().item())
         if self.observed is not None:
-            per_batch = torch.cat(self.onll).double().cpu().numpy()
-            out['observed_nll'] = float((per_batch * n).sum() / n.sum())
-            out['observed_fraction'] = float(torch.cat(self.nobs).sum().item() / (n.sum() * self.rep.nsp))
+            out['observed_nll'] = self.mean(self.onll)
+            out['observed_fraction'] = float(torch.cat(self.nobs).sum().item() / (sum(self.counts) * self.rep.nsp))
         if self.condition is not None:
             out['condition_z2'] = self.z2_sum / self.z2_n if self.z2_n else float('nan')
             out['hidden_fraction'] = self.z2_n / self.measured if self.measured else float('nan')
@@ -293,14 +236,13 @@ def current_gpu(what):
 
 def restore_replica(args, ckpt, say, dev=None):
     """The replica of args.model (msdn, dcnf) at args.batchsize / args.precision / args.superpixel with the weights of
-    checkpoint `ckpt` (a .pt file or a TF bundle prefix), as ann3depth.Session.__enter__ restores: (replica, texture,
+    checkpoint `ckpt` (a .pt file or a TF bundle prefix; ann3depth.read_checkpoint, load_checkpoint): (replica, texture,
     unary), the last two what a dcnf checkpoint says about its own form.  None, after say(why), for a checkpoint this
     model and --superpixel cannot use.  dev: the GPU to restore to; None (the prediction driver) reads the checkpoint on
     the host and asks for the current GPU only once nothing is left to refuse."""
     from .models import DCNF_PAIR_PREFIX, DCNF_PREFIX, DCNFReplica, MSDNReplica, check_dcnf_superpixel
     say(f'restoring {ckpt}')
-    bundle = tfckpt.is_bundle(ckpt)                  # as ann3depth.Session.__enter__ restores
-    state = tfckpt.read_bundle(ckpt) if bundle else torch.load(ckpt, map_location='cpu' if dev is None else dev)
+    state, bundle = read_checkpoint(ckpt, 'cpu' if dev is None else dev)
     texture, unary = False, 'patch'
     if args.model == 'dcnf':
         # the checkpoint says how many similarities its pairwise layer weighs: 2, or 3 with --pairwise-texture
@@ -326,23 +268,57 @@ def restore_replica(args, ckpt, say, dev=None):
                               superpixel=args.superpixel)
     else:
         replica = MSDNReplica(args.batchsize, device=dev, precision=args.precision, keep_dense_grads=False)
-    if bundle:
-        replica.load_tf_variables(state)
-    else:
-        replica.load_state_dict(state)
+    load_checkpoint(replica, state, bundle)
     return replica, texture, unary
+
+
+def refuse_model(args, say, can, own=lambda: None):
+    """The opening of both inference drivers' main(), first half: 2 after say(why) for an unknown model, for what own()
+    refuses (the driver's own refusal that comes next in its order; it says why itself) and for --superpixel without dcnf."""
+    if args.model not in OUTPUTS:
+        say(f'unknown model {args.model!r}; msdn and dcnf {can}.')
+        return 2
+    if own():
+        return 2
+    if args.superpixel != 40 and args.model != 'dcnf':
+        say(f'--superpixel {args.superpixel} sets the grid of the CRF of --model dcnf: {args.model} has no superpixels.')
+        return 2
+
+
+def open_checkpoint(args, say, noun, refusing, own=lambda: None):
+    """... second half, after the driver's own flags: (upsample, run_dir, ckpt), the ops.JointUpsampler of --upsample joint
+    or None, <ckptdir>/<model>_<id> and the checkpoint to restore; or 2 after say(why), own() as in refuse_model."""
+    upsample = None
+    if args.upsample == 'joint':
+        try:
+            upsample = ops.JointUpsampler('block' if args.model == 'dcnf' else 'corner',
+                                          args.superpixel if args.model == 'dcnf' else None, args.radius, args.sigma_space,
+                                          args.sigma_range)
+        except ValueError as e:
+            say(f'--upsample joint: {e}.')
+            return 2
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        say(f'{noun} runs in one process on one GPU; start it without a distributed launcher.')
+        return 2
+    if own():
+        return 2
+    run_dir = os.path.join(args.ckptdir, args.model + ('' if not args.id else f'_{args.id}'))
+    ckpt = find_checkpoint(args, run_dir)
+    if not ckpt:
+        say(f'no checkpoint found ({args.checkpoint or run_dir}); refusing to {refusing}.')
+        return 2
+    return upsample, run_dir, ckpt
 
 
 def main(argv=None):
     args = parse_args(argv)
-    if args.model not in OUTPUTS:
-        _say(f'unknown model {args.model!r}; msdn and dcnf can be evaluated.')
-        return 2
-    if args.observed_nll and args.model != 'dcnf':
-        _say('--observed-nll is the held-out objective of a dcnf run trained with --min-depth / --max-depth.')
-        return 2
-    if args.superpixel != 40 and args.model != 'dcnf':
-        _say(f'--superpixel {args.superpixel} sets the grid of the CRF of --model dcnf: {args.model} has no superpixels.')
+
+    def observed_nll_without_dcnf():
+        if args.observed_nll and args.model != 'dcnf':
+            _say('--observed-nll is the held-out objective of a dcnf run trained with --min-depth / --max-depth.')
+            return 2
+
+    if refuse_model(args, _say, 'can be evaluated', observed_nll_without_dcnf):
         return 2
     if args.superpixel != 40 and args.observed_nll:
         _say(f'--superpixel {args.superpixel} cannot go with --observed-nll yet: the likelihood of the observed superpixels '
@@ -356,23 +332,10 @@ def main(argv=None):
             _say(f'--condition {args.condition} needs --resolution grid (the superpixels tile the 240 x 320 target) and '
                  f'0 < KEEP < 1.')
             return 2
-    upsample = None
-    if args.upsample == 'joint':
-        try:
-            upsample = ops.JointUpsampler('block' if args.model == 'dcnf' else 'corner',
-                                          args.superpixel if args.model == 'dcnf' else None, args.radius, args.sigma_space,
-                                          args.sigma_range)
-        except ValueError as e:
-            _say(f'--upsample joint: {e}.')
-            return 2
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        _say('evaluation runs in one process on one GPU; start it without a distributed launcher.')
+    opened = open_checkpoint(args, _say, 'evaluation', 'evaluate untrained weights')
+    if opened == 2:
         return 2
-    run_dir = os.path.join(args.ckptdir, args.model + ('' if not args.id else f'_{args.id}'))
-    ckpt = find_checkpoint(args, run_dir)
-    if not ckpt:
-        _say(f'no checkpoint found ({args.checkpoint or run_dir}); refusing to evaluate untrained weights.')
-        return 2
+    upsample, run_dir, ckpt = opened
     try:
         inputs, _ = data.inputs(args.datadir, args.dataset, args.batchsize, train_or_test='test', shuffle=False)
     except FileNotFoundError as e:
@@ -445,15 +408,9 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(
         description='Evaluate an MSDN or DCNF checkpoint on <datadir>/<dataset>/test.tfrecords.')
     p.add_argument('dataset', default='nyu', type=str, help='The dataset to use.')
-    p.add_argument('--model', '-m', default='msdn', type=str, help='Model name (msdn, dcnf).')
-    p.add_argument('--batchsize', '-b', default=32, type=int, help='Batchsize')
-    p.add_argument('--ckptdir', '-p', default='checkpoints', help='Checkpoint directory')
-    p.add_argument('--id', default='', type=str, help='Checkpoint path suffix.')
+    add_shared_args(p, 'model', 'batchsize', 'ckptdir', 'id')
     p.add_argument('--datadir', '-d', default='data', type=str, help='The data directory containing the datasets.')
-    p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16x3', 'bf16', 'bf16s'],
-                   help='Arithmetic of the conv contractions, as in training.')
-    p.add_argument('--checkpoint', default='', type=str,
-                   help='A .pt file or TF bundle prefix instead of the newest checkpoint of <ckptdir>/<model>_<id>.')
+    add_shared_args(p, 'precision', 'checkpoint')
     p.add_argument('--resolution', default='grid', choices=['grid', 'record'],
                    help='grid: targets resized as the training step does (msdn 55x74, dcnf 240x320); record: the depth '
                         'map as stored.  A prediction on another grid than the target is resampled at its pixels.')
@@ -468,11 +425,11 @@ def parse_args(argv=None):
     p.add_argument('--predictions', default='', type=str,
                    help='Write the fine (msdn, [N,55,74]) or crf (dcnf, [N,6,8]; [N,12,16] or [N,24,32] with --superpixel 20 or '
                         '10) predictions to this .npy.')
-    p.add_argument('--superpixel', default=40, type=int, choices=[40, 20, 10],
-                   help='NON-REFERENCE unless 40, dcnf: the edge of the superpixels the checkpoint is evaluated at (6 x 8, '
-                        '12 x 16 or 24 x 32 depths per image). Checkpoints hold no grid: one trained at 40 evaluates at 10 and '
-                        'the reverse. 20 and 10 need a checkpoint of --unary fcsp; crf_nll is then the banded likelihood, '
-                        'not comparable with the value at 40.')
+    add_shared_args(p, 'superpixel',
+                    superpixel='NON-REFERENCE unless 40, dcnf: the edge of the superpixels the checkpoint is evaluated at (6 x 8, '
+                               '12 x 16 or 24 x 32 depths per image). Checkpoints hold no grid: one trained at 40 evaluates at 10 '
+                               'and the reverse. 20 and 10 need a checkpoint of --unary fcsp; crf_nll is then the banded '
+                               'likelihood, not comparable with the value at 40.')
     p.add_argument('--condition', default=None, type=float, metavar='KEEP',
                    help='NON-REFERENCE, dcnf, --resolution grid: judge depth completion. Each target superpixel is kept with '
                         'probability KEEP (0 < KEEP < 1), the field is conditioned on the kept ones, and crf_cond (completed) '
@@ -484,6 +441,25 @@ def parse_args(argv=None):
                       'brought to the record image\'s size by joint bilateral upsampling under the image '
                       '(ops.joint_bilateral_upsample), against the same target as the other outputs.')
     return p.parse_args(argv)
+
+
+def add_shared_args(p, *names, **text):
+    """The flags both inference drivers take, in the order `names` gives them (each driver's --help interleaves its own
+    flags); text: the help strings that differ between the two, by flag name."""
+    shared = {
+        'model': (('--model', '-m'), dict(default='msdn', type=str, help='Model name (msdn, dcnf).')),
+        'batchsize': (('--batchsize', '-b'), dict(default=32, type=int, help='Batchsize')),
+        'ckptdir': (('--ckptdir', '-p'), dict(default='checkpoints', help='Checkpoint directory')),
+        'id': (('--id',), dict(default='', type=str, help='Checkpoint path suffix.')),
+        'checkpoint': (('--checkpoint',), dict(default='', type=str, help='A .pt file or TF bundle prefix instead of the newest '
+                                                                         'checkpoint of <ckptdir>/<model>_<id>.')),
+        'precision': (('--precision',), dict(default='fp32', choices=['fp32', 'bf16x3', 'bf16', 'bf16s'],
+                                             help='Arithmetic of the conv contractions, as in training.')),
+        'superpixel': (('--superpixel',), dict(default=40, type=int, choices=[40, 20, 10])),
+    }
+    for name in names:
+        flags, kw = shared[name]
+        p.add_argument(*flags, **dict(kw, **({'help': text[name]} if name in text else {})))
 
 
 def add_upsample_args(p, choices, default, text):

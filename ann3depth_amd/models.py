@@ -18,6 +18,7 @@ import torch
 
 from . import _lib, augment as augment_, ops
 from ._lib import ConvDesc
+from .feed import DeviceFeed
 
 NET_H, NET_W = 228, 304          # src/models.py:282
 OUT_H, OUT_W = 55, 74            # src/models.py:283
@@ -123,7 +124,43 @@ class ParamGroup:
         ops.sgd_apply(self.var, self.grad, self.lr * grad_scale)
 
 
-class MSDNReplica:
+def check_valid_range(valid_range):
+    """None, or (min_depth, max_depth) as two floats; ValueError unless they are two numbers in that order."""
+    if valid_range is None:
+        return None
+    lo, hi = (float(v) for v in valid_range)
+    if not lo <= hi:
+        raise ValueError(f'valid_range {valid_range!r}: (min_depth, max_depth) with min_depth <= max_depth')
+    return lo, hi
+
+
+def check_rows(who, n, B, what, *have, ready=True, tail=''):
+    """A replica at batch B reads rows [0, n) of `what` (a description of tensors holding `have` rows each): ValueError
+    unless 0 < n <= B and every tensor has them (and, for a call that reuses an earlier one's results, they are ready)."""
+    if not (ready and 0 < n <= min(B, *have)):
+        raise ValueError(f'{who}: n = {n} rows of {what}, replica batch {B}{tail}')
+
+
+class Replica:
+    """What the two models' replicas do alike beyond their interface (state_dict() and self.global_step are each one's own)."""
+
+    def tf_variables(self):
+        """name -> ndarray in TensorFlow's naming, for tfckpt.write_bundle."""
+        out = {}
+        for k, v in self.state_dict().items():
+            a = v.detach().cpu().numpy()
+            out[k] = a.astype(np.int64) if k == 'global_step' else a.astype(np.float32)
+        return out
+
+    def _broadcast_step(self, dist, src, more=()):
+        """One collective: global_step, and the host scalars `more`, from rank src as float64; returns the latter."""
+        st = torch.tensor([self.global_step, *more], dtype=torch.float64, device=self.device)
+        dist.broadcast(st, src)
+        self.global_step = int(st[0].item())
+        return [x.item() for x in st[1:]]
+
+
+class MSDNReplica(Replica):
     """One data-parallel replica of the MSDN training graph (src/models.py:203-367) on one GPU."""
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, global_step=0, beta2=1.0, reducer=None,
@@ -142,12 +179,7 @@ class MSDNReplica:
         if not grad_weight >= 0:
             raise ValueError(f'grad_weight {grad_weight!r}: the weight of the gradient-matching term is a number >= 0')
         self.grad_weight = grad_weight
-        if valid_range is not None:
-            lo, hi = (float(v) for v in valid_range)
-            if not lo <= hi:
-                raise ValueError(f'valid_range {valid_range!r}: (min_depth, max_depth) with min_depth <= max_depth')
-            valid_range = (lo, hi)
-        self.valid_range = valid_range
+        self.valid_range = check_valid_range(valid_range)
         # keep_dense_grads=False (the training driver and bench.py on one GPU): under the reference's frozen optimizer the
         # gradient of the two dense kernels (268 MB) goes straight from the matrix cores into ApplyAdam's m slot
         # (ops.dense_bwd_filter_adam_tf1) and is never written; grad('coarse/dense/...') is then stale.  A data-parallel
@@ -643,14 +675,6 @@ class MSDNReplica:
                         power = power * np.float32(beta)
                     setattr(g, attr, power)
 
-    def tf_variables(self):
-        """name -> ndarray in TensorFlow's naming, for tfckpt.write_bundle."""
-        out = {}
-        for k, v in self.state_dict().items():
-            a = v.detach().cpu().numpy()
-            out[k] = a.astype(np.int64) if k == 'global_step' else a.astype(np.float32)
-        return out
-
     def summary_scalars(self, out):
         """Tags as the reference's name scopes 'loss' (src/models.py:288) and 'optimizers' (:347)."""
         rec = {'loss/coarse_loss': float(out['coarse_loss']), 'loss/fine_loss': float(out['fine_loss']),
@@ -674,13 +698,10 @@ class MSDNReplica:
         for g in self.groups.values():
             for buf in (g.var, g.m, g.v):
                 dist.broadcast(buf, src)
-        st = torch.tensor([self.global_step] + [float(x) for g in self.groups.values()
-                                                for x in (g.beta1_power, g.beta2_power)],
-                          dtype=torch.float64, device=self.device)
-        dist.broadcast(st, src)
-        self.global_step = int(st[0].item())
+        powers = self._broadcast_step(dist, src, [float(x) for g in self.groups.values()
+                                                  for x in (g.beta1_power, g.beta2_power)])
         for i, g in enumerate(self.groups.values()):
-            g.beta1_power, g.beta2_power = np.float32(st[1 + 2 * i].item()), np.float32(st[2 + 2 * i].item())
+            g.beta1_power, g.beta2_power = np.float32(powers[2 * i]), np.float32(powers[2 * i + 1])
         if self.wcopy:
             self.refresh_weight_copies()
         self._refresh_prepared()
@@ -874,8 +895,7 @@ class MSDNReplica:
         joined before returning."""
         B = self.B
         n = images.shape[0] if n is None else int(n)
-        if not 0 < n <= min(B, images.shape[0]):
-            raise ValueError(f'predict: n = {n} rows of a batch of {images.shape[0]} images, replica batch {B}')
+        check_rows('predict', n, B, f'a batch of {images.shape[0]} images', images.shape[0])
         ops.resize_bilinear_tf1(images[:n], self.x[:n])
         if n < B:
             self.x[n:].zero_()
@@ -1476,7 +1496,7 @@ def dcnf_pair_indices(rows, cols):
     return left, right
 
 
-class DCNFReplica:
+class DCNFReplica(Replica):
     """The whole DCNF train step (src/models.py:179-200): resize to 240x320, unary z over 48 patches, pairwise r over 48
     superpixel pairs, CRF negative log-likelihood, gradient descent (0.1) on what receives a gradient.
 
@@ -1536,11 +1556,7 @@ class DCNFReplica:
         check_dcnf_superpixel(superpixel, unary, valid_range)
         self.sp = sp = int(superpixel)
         self.banded = sp != DCNF_SP
-        if valid_range is not None:
-            lo, hi = (float(v) for v in valid_range)
-            if not lo <= hi:
-                raise ValueError(f'valid_range {valid_range!r}: (min_depth, max_depth) with min_depth <= max_depth')
-            valid_range = (lo, hi)
+        valid_range = check_valid_range(valid_range)
         if not 0 <= float(min_valid) <= 1:
             raise ValueError(f'min_valid {min_valid!r}: the share of a superpixel that must be measured, 0 .. 1')
         self.valid_range, self.min_valid = valid_range, float(min_valid)
@@ -1674,9 +1690,8 @@ class DCNFReplica:
         pair weights in self.r.  Returns n."""
         B, u = self.B, self.unary
         n = images.shape[0] if n is None else int(n)
-        if not 0 < n <= min(B, images.shape[0]):
-            raise ValueError(f'{who}: n = {n} rows of a batch of {images.shape[0]} images, replica batch {B}')
-        ops.resize_bilinear_tf1(images[:n], u.resized[:n])                                # src/models.py:180
+        check_rows(who, n, B, f'a batch of {images.shape[0]} images', images.shape[0])
+        ops.resize_bilinear_tf1(images[:n], u.resized[:n])                               # src/models.py:180
         if n < B:
             u.resized[n:].zero_()
         u.forward_resized(record_argmax=False)
@@ -1723,12 +1738,8 @@ class DCNFReplica:
         if depths is not None:
             if valid_range is None:
                 raise ValueError('posterior: depths need valid_range = (min_depth, max_depth), which says what a hole is')
-            lo, hi = (float(v) for v in valid_range)
-            if not lo <= hi:
-                raise ValueError(f'valid_range {valid_range!r}: (min_depth, max_depth) with min_depth <= max_depth')
-            if not 0 < n <= min(B, m, depths.shape[0]):
-                raise ValueError(f'posterior: n = {n} rows of {m} images and {depths.shape[0]} depth maps, '
-                                 f'replica batch {B}')
+            valid_range = check_valid_range(valid_range)
+            check_rows('posterior', n, B, f'{m} images and {depths.shape[0]} depth maps', m, depths.shape[0])
         elif valid_range is not None or keep is not None:
             raise ValueError('posterior: valid_range or keep without depths')
         if keep is not None and (keep.dtype != torch.bool or tuple(keep.shape) != (n, self.nsp)):
@@ -1738,7 +1749,7 @@ class DCNFReplica:
         elif not 0 < n <= B:
             raise ValueError(f'posterior: n = {n}, replica batch {B}')
         if depths is not None:
-            self._targets(depths, n, (lo, hi))
+            self._targets(depths, n, valid_range)
             y = self.y.view(B, self.nsp)
             if n < B:
                 y[n:].fill_(float('nan'))
@@ -1760,8 +1771,8 @@ class DCNFReplica:
         (the replica's by default): the likelihood of the observed superpixels instead, as the train step computes it; the
         numbers of observed superpixels are left in self.nobs."""
         n = int(n)
-        if self.r is None or not 0 < n <= min(self.B, depths.shape[0]):
-            raise ValueError(f'nll: n = {n} rows of {depths.shape[0]} depth maps, replica batch {self.B}, after predict()')
+        check_rows('nll', n, self.B, f'{depths.shape[0]} depth maps', depths.shape[0], ready=self.r is not None,
+                   tail=', after predict()')
         valid_range = self.valid_range if valid_range is None else valid_range
         if valid_range is not None and self.banded:
             raise ValueError(f'nll: superpixel {self.sp} has no likelihood of observed superpixels alone yet (valid_range)')
@@ -1803,9 +1814,7 @@ class DCNFReplica:
     def broadcast_state(self, dist, src=0):
         for g in self.groups.values():
             dist.broadcast(g.var, src)
-        st = torch.tensor([self.global_step], dtype=torch.float64, device=self.device)
-        dist.broadcast(st, src)
-        self.global_step = int(st[0].item())
+        self._broadcast_step(dist, src)
 
     def gather_state(self):
         """Nothing is sharded here (the driver calls this on every replica before a checkpoint)."""
@@ -1837,13 +1846,6 @@ class DCNFReplica:
         if 'global_step' in tensors:
             self.global_step = int(np.asarray(tensors['global_step']).reshape(-1)[0])
 
-    def tf_variables(self):
-        out = {}
-        for k, v in self.state_dict().items():
-            a = v.detach().cpu().numpy()
-            out[k] = a.astype(np.int64) if k == 'global_step' else a.astype(np.float32)
-        return out
-
 
 # =====================================================================================================
 # plugin surface: models.msdn / models.dcnf  (src/models.py:370-371)
@@ -1851,9 +1853,7 @@ class DCNFReplica:
 class TrainOp:
     """What `model(inputs, targets)` returns: run() is one `session.run(train_op)`.
 
-    Input side: the shuffle queue's staging pool is pinned memory; a dequeued batch is B slot numbers, DMA'd to HBM
-    on a side stream into one of two device batch buffers.  Batch k+1 is in flight while step k computes, so host
-    decode, PCIe transfer and the training step overlap.
+    Input side: a feed.DeviceFeed over the shuffle queue; batch k+1 is in flight while step k computes.
 
     augment (NON-REFERENCE, an augment.Eigen2014): every batch is warped as it is resized.  Its table is drawn beside the
     batch's DMA for the global step that will consume it, from (seed, rank, step) alone, and travels under the same event."""
@@ -1863,111 +1863,45 @@ class TrainOp:
         self.augment, self.rank = augment, rank
         dev = replica.device
         self.keep = torch.empty((replica.B, 4096), dtype=torch.uint8, device=dev) if replica.uses_dropout else None
-        pipeline.allocate(lambda shape: torch.empty(shape, dtype=torch.float32).pin_memory().numpy(),
-                          lambda shape: torch.empty(shape, dtype=torch.uint8).pin_memory().numpy())
-        self.pool = (torch.from_numpy(pipeline.images), torch.from_numpy(pipeline.depths))      # pinned views
-        # converter-written records are staged as uint8 pixel values (data.py): their own pinned pool and device buffers;
-        # the resize kernel rebuilds the loader's float32 from them bit for bit
-        self.pool_u8 = None
-        if pipeline.images_u8 is not None:
-            self.pool_u8 = (torch.from_numpy(pipeline.images_u8), torch.from_numpy(pipeline.depths_u8))
-        self.dev = [tuple(torch.empty((replica.B,) + tuple(p.shape[1:]), device=dev) for p in self.pool)
-                    for _ in range(2)]
-        self.dev_u8 = [tuple(torch.empty((replica.B,) + tuple(p.shape[1:]), device=dev, dtype=torch.uint8) for p in self.pool)
-                       for _ in range(2)] if self.pool_u8 is not None else None
-        self.cur = [None, None]             # the (images, depths) tensors batch i was copied into: uint8 or float32 each
-        self.copy_stream = torch.cuda.Stream(device=dev)
-        self.copied = [None, None]          # event: the DMA into buffer i finished
-        self.consumed = [None, None]        # event: the step that read buffer i finished
-        self.held = [[], []]                # pool slots buffer i was filled from
-        self.k = 0                          # batches consumed
-        self.end = None                     # (batch index, exception) once the pipeline ran dry
+        self.feed = DeviceFeed(pipeline, replica.B, dev)
         self.last = None
         if augment is not None:
-            if tuple(self.pool[0].shape[1:3]) != tuple(self.pool[1].shape[1:3]):
+            self.hw = tuple(self.feed.pool[0].shape[1:3])
+            if self.hw != tuple(self.feed.pool[1].shape[1:3]):
                 raise ValueError(f'augmentation warps the image and its depth map with one map: they must be stored at the '
-                                 f'same size, not {tuple(self.pool[0].shape[1:3])} and {tuple(self.pool[1].shape[1:3])}')
+                                 f'same size, not {self.hw} and {tuple(self.feed.pool[1].shape[1:3])}')
             self.table_host = [torch.empty((replica.B, augment_.STRIDE), dtype=torch.float32).pin_memory() for _ in range(2)]
             self.table_dev = [torch.empty((replica.B, augment_.STRIDE), device=dev) for _ in range(2)]
             self.table_step = [None, None]  # the global step table i was drawn for
-        self._prefetch(0)
-        self._prefetch(1)
+        self.feed.start(self._draw)
 
-    def _prefetch(self, j):
-        """Dequeue batch j and start its DMA into device buffer j & 1 on the copy stream."""
-        if self.end is not None:
-            return
-        i = j & 1
-        try:
-            slots = self.pipeline.dequeue()
-        except BaseException as e:          # raised to the caller when batch j would have been consumed
-            self.end = (j, e)
-            return
-        if self.consumed[i] is not None:
-            self.copy_stream.wait_event(self.consumed[i])
-        pl = self.pipeline
-        cur = []
-        kinds = int(np.bitwise_and.reduce(pl.kind[slots])) if self.pool_u8 is not None else 0
-        for which in (0, 1):                # images, depths: uint8 when EVERY record of the batch staged that feature so
-            as_u8 = bool(kinds & (1 << which))
-            if not as_u8 and self.pool_u8 is not None:
-                for s in slots:
-                    pl.materialise(s, which)                    # (a mixed batch: the uint8 records are expanded on the host)
-            cur.append((self.dev_u8 if as_u8 else self.dev)[i][which])
-        ids = (ctypes.c_int32 * len(slots))(*slots)
-        with torch.cuda.stream(self.copy_stream):
-            for which in (0, 1):
-                src = (self.pool_u8 if cur[which].dtype == torch.uint8 else self.pool)[which]
-                ops.check(_lib.load().a3d_h2d_gather(cur[which].data_ptr(), src.data_ptr(), ids, len(slots), len(src),
-                                                     src[0].numel() * src.element_size(), self.copy_stream.cuda_stream),
-                          'a3d_h2d_gather')                     # B copies from ONE call (no per-record host-language work)
-            if self.augment is not None:
-                self._table(i, self.replica.global_step + j - self.k)
-            ev = torch.cuda.Event()
-            ev.record(self.copy_stream)
-        self.cur[i] = tuple(cur)
-        self.copied[i] = ev
-        self.held[i] = slots
+    def _draw(self, i, j):
+        """The feed's hook: batch j, just copied into buffer i, will be consumed j - k steps from now."""
+        if self.augment is not None:
+            self._table(i, self.replica.global_step + j - self.feed.k)
 
     def _table(self, i, step):
         """Draw the table of global step `step` into pinned buffer i and start its copy (the current stream is the copy
-        stream; the earlier copy out of that buffer has finished: run() waited for `copied` before releasing the slots)."""
-        h, w = self.pool[0].shape[1:3]
+        stream; the earlier copy out of that buffer has finished: the feed waited for `copied` before releasing the slots)."""
+        h, w = self.hw
         augment_.table(self.augment, self.seed, self.rank, step, self.replica.B, h, w, out=self.table_host[i].numpy())
         self.table_dev[i].copy_(self.table_host[i], non_blocking=True)
         self.table_step[i] = step
 
     def run(self):
-        r = self.replica
-        i = self.k & 1
-        if self.end is not None and self.end[0] == self.k:
-            raise self.end[1]
-        cur = torch.cuda.current_stream()
-        warp = None
-        if self.augment is not None:
-            if self.table_step[i] != r.global_step:
-                # the batch was prefetched before a checkpoint moved global_step (the first two steps of a resumed run)
-                self.copied[i].synchronize()
-                with torch.cuda.stream(self.copy_stream):
-                    self._table(i, r.global_step)
-                    self.copied[i] = torch.cuda.Event()
-                    self.copied[i].record(self.copy_stream)
-            warp = self.table_dev[i]
-        cur.wait_event(self.copied[i])
+        r, feed = self.replica, self.feed
+        i = feed.k & 1
+        if self.augment is not None and feed.due() is None and self.table_step[i] != r.global_step:
+            # the batch was prefetched before a checkpoint moved global_step (the first two steps of a resumed run)
+            feed.redo(i, lambda: self._table(i, r.global_step))
+        images, depths, _, i = feed.take()
         if self.keep is not None:
             ops.dropout_keep_mask(self.keep, self.seed, r.global_step)
-        if warp is None:
-            self.last = r.step(self.cur[i][0], self.cur[i][1], self.keep)
+        if self.augment is None:
+            self.last = r.step(images, depths, self.keep)
         else:
-            self.last = r.step(self.cur[i][0], self.cur[i][1], self.keep, warp=warp)
-        ev = torch.cuda.Event()
-        ev.record(cur)
-        self.consumed[i] = ev
-        self.copied[i].synchronize()        # issued a whole step ago: the staging slots can go back to the readers
-        self.pipeline.release(self.held[i])
-        self.held[i] = []
-        self.k += 1
-        self._prefetch(self.k + 1)          # into the buffer this step just read; the DMA waits for `consumed`
+            self.last = r.step(images, depths, self.keep, warp=self.table_dev[i])
+        feed.give_back(self._draw)
         return self.last
 
     @property

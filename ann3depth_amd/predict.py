@@ -39,7 +39,7 @@ import numpy as np
 import torch
 
 from . import imresize, ops, png
-from .evaluate import OUTPUTS, add_upsample_args, find_checkpoint, restore_replica
+from .evaluate import OUTPUTS, add_shared_args, add_upsample_args, open_checkpoint, refuse_model, restore_replica
 
 
 def _say(msg):
@@ -99,11 +99,7 @@ def read_depth(path):
 
 def main(argv=None):
     args = parse_args(argv)
-    if args.model not in OUTPUTS:
-        _say(f'unknown model {args.model!r}; msdn and dcnf can predict.')
-        return 2
-    if args.superpixel != 40 and args.model != 'dcnf':
-        _say(f'--superpixel {args.superpixel} sets the grid of the CRF of --model dcnf: {args.model} has no superpixels.')
+    if refuse_model(args, _say, 'can predict'):
         return 2
     if args.batchsize <= 0:
         _say(f'--batchsize {args.batchsize} must be positive.')
@@ -116,26 +112,16 @@ def main(argv=None):
     if args.depths and not (args.min_depth < args.max_depth):
         _say(f'--depths needs --min-depth < --max-depth (a pixel is measured inside ({args.min_depth}, {args.max_depth}]).')
         return 2
-    upsample = None
-    if args.upsample == 'joint':
-        try:
-            upsample = ops.JointUpsampler('block' if args.model == 'dcnf' else 'corner',
-                                          args.superpixel if args.model == 'dcnf' else None, args.radius, args.sigma_space,
-                                          args.sigma_range)
-        except ValueError as e:
-            _say(f'--upsample joint: {e}.')
+
+    def no_images():
+        if not args.images:
+            _say('no images given.')
             return 2
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        _say('prediction runs in one process on one GPU; start it without a distributed launcher.')
+
+    opened = open_checkpoint(args, _say, 'prediction', 'predict with untrained weights', no_images)
+    if opened == 2:
         return 2
-    if not args.images:
-        _say('no images given.')
-        return 2
-    run_dir = os.path.join(args.ckptdir, args.model + ('' if not args.id else f'_{args.id}'))
-    ckpt = find_checkpoint(args, run_dir)
-    if not ckpt:
-        _say(f'no checkpoint found ({args.checkpoint or run_dir}); refusing to predict with untrained weights.')
-        return 2
+    upsample, _, ckpt = opened
     images = []
     for path in args.images:
         try:
@@ -227,17 +213,10 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(description='Depth maps for image files from an MSDN or DCNF checkpoint.')
     p.add_argument('images', nargs='*', type=str, help='8-bit PNG files (RGB or grey; alpha is dropped).')
     p.add_argument('--out', '-o', required=True, type=str, help='Directory for <stem>-depth.npy and <stem>-depth.png.')
-    p.add_argument('--model', '-m', default='msdn', type=str, help='Model name (msdn, dcnf).')
-    p.add_argument('--batchsize', '-b', default=32, type=int, help='Images of one size that run together.')
-    p.add_argument('--ckptdir', '-p', default='checkpoints', help='Checkpoint directory')
-    p.add_argument('--id', default='', type=str, help='Checkpoint path suffix.')
-    p.add_argument('--checkpoint', default='', type=str,
-                   help='A .pt file or TF bundle prefix instead of the newest checkpoint of <ckptdir>/<model>_<id>.')
-    p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16x3', 'bf16', 'bf16s'],
-                   help='Arithmetic of the conv contractions, as in training.')
-    p.add_argument('--superpixel', default=40, type=int, choices=[40, 20, 10],
-                   help='NON-REFERENCE unless 40, dcnf: the edge of the superpixels (6 x 8, 12 x 16 or 24 x 32 depths per image '
-                        'before upsampling); 20 and 10 need a checkpoint of --unary fcsp.')
+    add_shared_args(p, 'model', 'batchsize', 'ckptdir', 'id', 'checkpoint', 'precision', 'superpixel',
+                    batchsize='Images of one size that run together.',
+                    superpixel='NON-REFERENCE unless 40, dcnf: the edge of the superpixels (6 x 8, 12 x 16 or 24 x 32 depths per '
+                               'image before upsampling); 20 and 10 need a checkpoint of --unary fcsp.')
     p.add_argument('--uncertainty', action='store_true',
                    help='NON-REFERENCE, dcnf: also write <stem>-sigma.npy / .png, the standard deviation of the CRF\'s field per '
                         'superpixel, brought to the output size as the depth map is.')

@@ -113,10 +113,12 @@ def main(out_path):
     # reader FAILURE on one rank is raised on both (it used to look like a clean end of input), the chief's
     # checkpoint request reaches everybody
     import types
-    from ann3depth_amd import ann3depth, data
+    from ann3depth_amd import ann3depth, data, feed
     def session(end):
         rep = types.SimpleNamespace(reducer=red, global_step=0)
-        op = types.SimpleNamespace(replica=rep, end=end, k=0)
+        f = object.__new__(feed.DeviceFeed)                   # a feed without pipeline or GPU: only what due() reads
+        f.end, f.k = end, 0
+        op = types.SimpleNamespace(replica=rep, feed=f)
         sess = ann3depth.Session(op, None, last_step=10, stop_at_signal=types.SimpleNamespace(signal_received=0),
                                  save_checkpoint_secs=0, save_summaries_steps=0, trace_every=0, logger=None, world=world)
         return sess, op

@@ -47,9 +47,9 @@ def test_train_op_matches_oracle_on_a_dequeued_batch(tmp_path, monkeypatch, u8_r
     write_shard(str(tmp_path))
     inputs, targets = data.inputs(str(tmp_path), 'nyu', 4, seed=3)
     op = models.msdn(inputs, targets)
-    op.copied[0].synchronize()                       # batch 0 has landed in device buffer 0 (prefetched)
-    assert (op.cur[0][0].dtype == torch.uint8) == u8_records and (op.cur[0][1].dtype == torch.uint8) == u8_records
-    img, dep = (t.cpu().numpy() for t in op.cur[0])
+    op.feed.copied[0].synchronize()                       # batch 0 has landed in device buffer 0 (prefetched)
+    assert (op.feed.cur[0][0].dtype == torch.uint8) == u8_records and (op.feed.cur[0][1].dtype == torch.uint8) == u8_records
+    img, dep = (t.cpu().numpy() for t in op.feed.cur[0])
     if u8_records:
         img, dep = data.expand_u8(img), data.expand_u8(dep)          # the loader's float32, from the pixel values
     out = op.run()                                   # consumes it; the buffer is refilled with batch 2 afterwards
@@ -90,9 +90,9 @@ def test_mixed_batches_fall_back_to_float32_per_feature(tmp_path):
     op = models.msdn(inputs, targets)
     kinds = set()
     for _ in range(6):                               # all 24 records
-        i = op.k & 1
-        op.copied[i].synchronize()
-        img_t, dep_t = op.cur[i]
+        i = op.feed.k & 1
+        op.feed.copied[i].synchronize()
+        img_t, dep_t = op.feed.cur[i]
         assert dep_t.dtype == torch.float32
         img = img_t.cpu().numpy()
         tags = [int(t) for t in (img[:, 0, 0, 0] if img.dtype == np.uint8 else np.rint(img[:, 0, 0, 0] * 255))]

@@ -65,7 +65,7 @@ for label, env, aug in (('uint8_records', '0', None), ('float32_records', '1', N
         op.run()
     torch.cuda.synchronize()
     out[f'train_loop_images_per_s_{label}'] = round(B * steps / (time.perf_counter() - t0), 1)
-    out[f'staged_as_{label}'] = str(op.cur[0][0].dtype)
+    out[f'staged_as_{label}'] = str(op.feed.cur[0][0].dtype)
     op.pipeline.close()
     del op
 os.environ.pop('A3D_NO_U8_RECORDS')
