@@ -184,6 +184,12 @@ WINO_SIGNATURES = {
     'a3dw_conv2d_bwd_data_prepare_filter': (c_int, [_D, _P, _P, c_size_t, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_wino_grad.h declares (prefix a3dwg_)
+WINO_GRAD_SIGNATURES = {
+    'a3dwg_conv2d_bwd_filter_ws_bytes': (c_size_t, [_D]),
+    'a3dwg_conv2d_bwd_filter': (c_int, [_D, _P, _P, _P, _P, _P, c_size_t, _P]),
+}
+
 # name -> (restype, argtypes); every symbol include/a3d_upsample.h declares (NON-REFERENCE extension, prefix a3du_)
 UPSAMPLE_SIGNATURES = {
     'a3du_joint_bilateral_upsample': (c_int, [c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, _P, _P, _P, _P, c_int, c_float,
@@ -214,7 +220,8 @@ def load():
                               + list(TEXTURE_SIGNATURES.items()) + list(GRADLOSS_SIGNATURES.items())
                               + list(CRF_VALID_SIGNATURES.items()) + list(FCSP_SIGNATURES.items())
                               + list(CRF_BAND_SIGNATURES.items()) + list(WINO_SIGNATURES.items())
-                              + list(UPSAMPLE_SIGNATURES.items()) + list(POSTERIOR_SIGNATURES.items())):
+                              + list(UPSAMPLE_SIGNATURES.items()) + list(POSTERIOR_SIGNATURES.items())
+                              + list(WINO_GRAD_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -137,4 +137,20 @@ int wino_output(const a3d_conv_desc* d, bool bwd, const float* M, float* out, co
 a3d_timing_record wino_record(int mode, const WinoGeom& g);
 int wino_gemm(IgemmParams& p, const WinoGeom& g, hipStream_t st);      // p: one product; the sixteen differ in A, B and C
 
+// ---- the same identity for the filter gradient (include/a3d_wino_grad.h; wino.hip) ----
+struct WinoGradGeom {
+  size_t T;                              // 2x2 tiles of dz: the forward's
+  int Cp, Kp;                            // c and k padded to whole 16-byte pieces
+  int splits;                            // wino_grad_splits(c, k, T)
+  size_t v_bytes, z_bytes;               // V [16][T][Cp], Z [16][T][Kp]
+  size_t slab_bytes, bias_bytes;         // raw sums [16][splits][Cp][Kp], bias partials [splits][Kp]
+};
+int wino_grad_splits(int C, int K, size_t T);
+WinoGradGeom wino_grad_geom(const a3d_conv_desc* d);
+bool wino_grad_applicable(const a3d_conv_desc* d);      // precision F32 or F32_WINOGRAD: the entry point names the arithmetic
+int wino_dz(const a3d_conv_desc* d, const float* dz, float* Z, hipStream_t st);
+int wino_dw(const a3d_conv_desc* d, const WinoGradGeom& g, const float* slabs, const float* bparts, float* dw, float* db, hipStream_t st);
+a3d_timing_record wino_grad_record(const a3d_conv_desc* d, const WinoGradGeom& g);
+int wino_grad_gemm(IgemmParams& p, const WinoGradGeom& g, hipStream_t st);      // p: one product, splits and tiles filled in here
+
 }  // namespace a3d

@@ -4,6 +4,7 @@
 #include <algorithm>
 
 #include "../../include/a3d_wino.h"
+#include "../../include/a3d_wino_grad.h"
 #include "a3d_internal.h"
 #include "igemm.h"
 #include "igemm_cfgs.h"
@@ -921,6 +922,49 @@ int a3d_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* d
   hipLaunchKernelGGL(unpad_filter_kernel, dim3((d->r * rf.rl * d->k + 255) / 256), dim3(256), 0, st, out, dw, d->r,
                      rf.rl, rf.rlp, d->k);
   return check_launch("unpad_filter");
+}
+
+// ---- include/a3d_wino_grad.h: the filter gradient through Winograd F(2x2,3x3); workspace [V][Z][slabs][bias partials] ----
+static bool wino_grad_takes(const a3d_conv_desc* d) { return check_desc(d) == A3D_OK && wino_grad_applicable(d); }
+
+size_t a3dwg_conv2d_bwd_filter_ws_bytes(const a3d_conv_desc* d) {
+  if (!wino_grad_takes(d)) return a3d_conv2d_bwd_filter_ws_bytes(d);
+  const WinoGradGeom g = wino_grad_geom(d);
+  return g.v_bytes + g.z_bytes + g.slab_bytes + g.bias_bytes;
+}
+
+int a3dwg_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* dz, float* dw, float* db, void* ws,
+                            size_t ws_bytes, void* stream) {
+  if (!wino_grad_takes(d)) return a3d_conv2d_bwd_filter(d, x, dz, dw, db, ws, ws_bytes, stream);
+  A3D_CHECK_ARG(x && dz && dw, "conv2d_bwd_filter (Winograd): null tensor");
+  A3D_CHECK_WS(ws, "conv2d_bwd_filter (Winograd)");
+  const WinoGradGeom g = wino_grad_geom(d);
+  const size_t need = g.v_bytes + g.z_bytes + g.slab_bytes + g.bias_bytes;
+  if (!ws || need > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd_filter (Winograd): need %zu workspace bytes", need);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(ws);
+  float* V = reinterpret_cast<float*>(base);
+  float* Z = reinterpret_cast<float*>(base + g.v_bytes);
+  float* slabs = reinterpret_cast<float*>(base + g.v_bytes + g.z_bytes);
+  float* bparts = reinterpret_cast<float*>(base + g.v_bytes + g.z_bytes + g.slab_bytes);
+  int rc = wino_input(d, false, x, V, st);
+  if (rc != A3D_OK) return rc;
+  rc = wino_dz(d, dz, Z, st);
+  if (rc != A3D_OK) return rc;
+  // one product: the filter gradient of a 1x1 conv over T one-pixel images of Cp channels, Kp filters
+  a3d_conv_desc e{};
+  e.n = (int)g.T; e.h = e.w = e.ho = e.wo = 1; e.c = g.Cp; e.k = g.Kp; e.r = e.s = 1; e.stride = 1; e.ldx = g.Cp; e.ldy = g.Kp;
+  GemmProblem gp = bwd_f_problem(&e);
+  IgemmParams p;
+  fill_common(p, gp);
+  p.A = V; p.B = Z; p.C = slabs; p.dbias = db ? bparts : nullptr;
+  p.npix = gp.K; p.nrsc = gp.M;
+  fill_gather(p, &e, g.Cp, 1, g.Cp);
+  p.ldb = g.Kp; p.ldc = g.Kp;
+  fill_staging(p, MODE_BWD_F, (unsigned long long)g.T * g.Cp, (unsigned long long)g.T * g.Kp, 1, 1);
+  rc = timed_launch(wino_grad_record(d, g), st, [&] { return wino_grad_gemm(p, g, st); });
+  if (rc != A3D_OK) return rc;
+  return wino_dw(d, g, slabs, bparts, dw, db, st);
 }
 
 // ---- dense = 1x1 conv over a 1x1 image ----

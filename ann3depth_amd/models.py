@@ -354,7 +354,7 @@ class MSDNReplica(Replica):
             'fine/third': D(B, OUT_H, OUT_W, 64, 1, 5, 5, 1, 'SAME'),
         }
         # fp32: the two stride-1 3x3 layers' bwd-data through Winograd F(2x2,3x3) ('fp32w', csrc/wino.hip) from WINO_MIN_TILES
-        # 2x2 tiles up; their forwards and filter gradients, and every layer below that, stay on the direct kernels
+        # 2x2 tiles up; their forwards, and every layer below that, stay on the direct kernels
         self.d_wino = {}
         if precision == 'fp32' and dev.type == 'cuda':
             for n in self.WINO_LAYERS:
@@ -362,6 +362,13 @@ class MSDNReplica(Replica):
                 if d.n * -(-d.ho // 2) * -(-d.wo // 2) >= self.WINO_MIN_TILES:
                     e = self.d_wino[n] = ConvDesc.from_buffer_copy(d)
                     e.precision = ops.PREC['fp32w']
+        # ... and their filter gradients through the same identity (include/a3d_wino_grad.h) from WINO_GRAD_MIN_TILES tiles up
+        self.wino_grad = set()
+        if precision == 'fp32' and dev.type == 'cuda':
+            for n in self.WINO_GRAD_LAYERS:
+                d = self.d[n]
+                if d.n * -(-d.ho // 2) * -(-d.wo // 2) >= self.WINO_GRAD_MIN_TILES:
+                    self.wino_grad.add(n)
         # conv -> ReLU -> pool blocks on the 3-channel image: filter gradient straight from the POOLED map's gradient (MaxPoolGrad
         # by index + ReluGrad while the kernel stages its operand): dc0 / df1 (50 / 131 MB at B = 32) are never written or read.
         # fp32 arithmetic on the fp32 image in every precision mode but 'bf16s'.
@@ -431,6 +438,14 @@ class MSDNReplica(Replica):
     # gradients by 7e-7 rel-L2 and nothing else (profiles/wino_outputs_vs_parent.txt).
     WINO_LAYERS = ('coarse/conv/conv2d_2', 'coarse/conv/conv2d_3')
     WINO_MIN_TILES = 504
+    # The filter gradients of the same layers through the same identity (ops.conv2d_bwd_filter_wino; precision 'fp32' only).
+    # tools/bench_layers.py at B = 8, 16, 32 (profiles/wino_grad_bench_layers.txt), conv2d_2 / conv2d_3, direct -> route:
+    # 51.8 / 64.0 -> 45.9 / 51.3 us, 79.9 / 99.9 -> 60.5 / 73.9, 135.8 / 172.8 -> 95.1 / 124.0: both win at each, so the
+    # threshold is again the smallest count measured, and B <= 4 stays direct (the pinned plans and records).  Inside the step
+    # at B = 32 both win too: 2.691-2.703 -> 2.614-2.629 ms.  A filter gradient feeds only its layer's Adam m
+    # slot: nothing but CoarseConv's m moves, by 3.8e-7 rel-L2 (profiles/wino_grad_outputs_vs_parent.txt).
+    WINO_GRAD_LAYERS = WINO_LAYERS
+    WINO_GRAD_MIN_TILES = 504
 
     def _desc(self, name, which):
         """The layer's conv descriptor for 'fwd' | 'bwd_d' | 'bwd_f', with that call's storage bits."""
@@ -936,7 +951,8 @@ class MSDNReplica(Replica):
 
     def _bwd_filter(self, name, x, dz):
         if name in self.d:
-            ops.conv2d_bwd_filter(self._desc(name, 'bwd_f'), x, dz, self._g(name + '/kernel'), self._g(name + '/bias'))
+            call = ops.conv2d_bwd_filter_wino if name in self.wino_grad else ops.conv2d_bwd_filter
+            call(self._desc(name, 'bwd_f'), x, dz, self._g(name + '/kernel'), self._g(name + '/bias'))
         elif self._fused_dense_adam():
             g = self.groups[self.group_of[name + '/kernel']]
             kw = [g.view(buf, name + '/kernel') for buf in (g.var, g.m, g.v)]

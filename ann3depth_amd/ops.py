@@ -190,6 +190,16 @@ def conv2d_bwd_filter(d, x, dz, dw, db=None):
     return dw, db
 
 
+def conv2d_bwd_filter_wino(d, x, dz, dw, db=None):
+    """The filter and bias gradient through Winograd F(2x2,3x3) in fp32 (include/a3d_wino_grad.h) where d is a stride-1 3x3
+    layer of float32 tensors; for any other descriptor the library runs conv2d_bwd_filter's kernels."""
+    lib = _lib.load()
+    ws, n = _ws().get(lib.a3dwg_conv2d_bwd_filter_ws_bytes(ctypes.byref(d)), x.device)
+    check(lib.a3dwg_conv2d_bwd_filter(ctypes.byref(d), _ptr(x), _ptr(dz), _ptr(dw), _ptr(db), ws, n, _stream()),
+          'a3dwg_conv2d_bwd_filter')
+    return dw, db
+
+
 def conv2d_bwd_filter_pooled_supported(d):
     return _lib.load().a3d_conv2d_bwd_filter_pooled_ws_bytes(ctypes.byref(d)) > 0
 

@@ -1,8 +1,9 @@
 """Times every MSDN layer x direction (B = 32 unless B=..) with the planner's own choice, the way MSDNReplica.step calls
-them (conv + pool fused where the step fuses them).  One line per op: us, TFLOP/s.  The stride-1 3x3 layers get two more rows,
-fwd/wino and bwd_d/wino: the same call through the Winograd route (precision 'fp32w', prepared filters, all its launches; TF
-counts the direct convolution's FLOPs, so the rows compare as times) — what MSDNReplica.WINO_MIN_TILES is chosen from (the
-step uses the bwd-data rows: DESIGN 3.1k); they are not part of the total.  A/B two builds of the library on one GPU box:
+them (conv + pool fused where the step fuses them).  One line per op: us, TFLOP/s.  The stride-1 3x3 layers get three more rows,
+fwd/wino, bwd_d/wino and bwd_f/wino: the same call through the Winograd route (precision 'fp32w' with prepared filters; the
+filter gradient through ops.conv2d_bwd_filter_wino: both transforms, the products and the final transform; TF counts the direct
+convolution's FLOPs, so the rows compare as times) — what MSDNReplica.WINO_MIN_TILES and WINO_GRAD_MIN_TILES are chosen from (the
+step uses the bwd-data and bwd-filter rows: DESIGN 3.1k); they are not part of the total.  A/B two builds of the library on one GPU box:
     A3D_LIB=tools/ab/liba3d_old.so python tools/bench_layers.py ; python tools/bench_layers.py"""
 import json
 import os
@@ -65,6 +66,7 @@ def main():
             pb.refresh(wt)
             modes['fwd/wino'] = lambda: ops.conv2d_fwd(pf.desc_prepared, x, pf.buf, bias, y, 'relu')
             modes['bwd_d/wino'] = lambda: ops.conv2d_bwd_data(pb.desc_prepared, dz, pb.buf, dx, relu_mask=x)
+            modes['bwd_f/wino'] = lambda: ops.conv2d_bwd_filter_wino(d, x, dz, dw, db)
         # conv + pool in one launch enumerates whole pool windows only: the last odd row / column is never computed
         flops_pooled = 2.0 * B * (d.ho // 2) * (d.wo // 2) * 4 * k * ks * ks * c
         for mode, fn in modes.items():
