@@ -73,6 +73,7 @@ endif
 # TRAIN_ARGS="--train-pairwise --pairwise-texture" (the pairwise weights learn, over three similarities) or
 # TRAIN_ARGS="--unary fcsp" (the unary convs once over the whole image, superpixel pooling before the dense head)
 # or TRAIN_ARGS="--unary fcsp --superpixel 10" (a 24 x 32 depth map per image on the banded CRF; 20: 12 x 16)
+# or TRAIN_ARGS="--unary fcsp --segmentation slic" (SLIC superpixels of the image instead of square blocks; any --superpixel)
 TRAIN_ARGS ?=
 .PHONY: train
 train: ${DATA_DIR}

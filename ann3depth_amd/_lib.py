@@ -201,6 +201,18 @@ POSTERIOR_SIGNATURES = {
     'a3dc_crf_band_posterior': (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_slic.h declares (NON-REFERENCE extension, prefix a3ds_)
+SLIC_SIGNATURES = {
+    'a3ds_label_mean': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P]),
+    'a3ds_label_hist': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, _P]),
+    'a3ds_slic_update': (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P]),
+    'a3ds_slic_assign': (c_int, [c_int, c_int, c_int, _P, c_int, _P, c_float, _P, _P]),
+    'a3ds_slic_segment': (c_int, [c_int, c_int, c_int, _P, c_int, c_int, c_float, _P, _P, _P, _P]),
+    'a3ds_pair_similarity': (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, c_float, _P, _P, _P]),
+    'a3ds_label_pool_fwd': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P]),
+    'a3ds_label_pool_bwd': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P]),
+}
+
 _lib = None
 
 
@@ -221,7 +233,7 @@ def load():
                               + list(CRF_VALID_SIGNATURES.items()) + list(FCSP_SIGNATURES.items())
                               + list(CRF_BAND_SIGNATURES.items()) + list(WINO_SIGNATURES.items())
                               + list(UPSAMPLE_SIGNATURES.items()) + list(POSTERIOR_SIGNATURES.items())
-                              + list(WINO_GRAD_SIGNATURES.items())):
+                              + list(WINO_GRAD_SIGNATURES.items()) + list(SLIC_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

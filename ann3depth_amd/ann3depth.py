@@ -85,6 +85,18 @@ def main(argv=None):
         except ValueError as e:
             logger.error(f'--superpixel {args.superpixel}: {e}.')
             return 2
+    if args.segmentation != 'grid':
+        if not hasattr(getattr(models, args.model, None), 'segmentation'):
+            logger.error(f'--segmentation {args.segmentation} chooses the superpixels of the CRF of --model dcnf: '
+                         f'{args.model or "(no model)"} has no superpixels.')
+            return 2
+        try:
+            models.check_dcnf_segmentation(args.segmentation, args.unary, args.pairwise_texture,
+                                           None if args.min_depth is None and args.max_depth is None else (0, 0),
+                                           args.slic_iters, args.slic_compactness)
+        except ValueError as e:
+            logger.error(f'{e}.')
+            return 2
     if args.loss_gradient is not None and args.model != 'msdn':
         logger.error(f'--loss-gradient weighs the gradient-matching term of Eigen & Fergus 2015 in the two losses of --model '
                      f'msdn: {args.model or "(no model)"} has no loss over a pixel grid (dcnf regresses superpixel means).')
@@ -165,6 +177,9 @@ def setup_model(args, rank=0, world=1):
         model.unary = args.unary
     if hasattr(model, 'superpixel'):
         model.superpixel = args.superpixel
+    if hasattr(model, 'segmentation'):                                   # main() has refused the models that have none
+        model.segmentation, model.slic_iters, model.slic_compactness = (args.segmentation, args.slic_iters,
+                                                                        args.slic_compactness)
     inputs, targets = data.inputs(args.datadir, args.dataset, args.batchsize, rank=rank, world=world,
                                   seed=args.seed + rank)
     return model(inputs, targets)
@@ -401,6 +416,28 @@ def load_checkpoint(replica, state, bundle):
         replica.load_state_dict(state)
 
 
+def add_segmentation_args(parser, listed=True):
+    """--segmentation, --slic-iters, --slic-compactness: the same three flags on the training, evaluation and prediction
+    drivers (evaluate.add_shared_args).  listed=False keeps them out of --help: the two inference drivers' help texts are
+    recorded word for word (tests/golden/*_help.txt), so there the flags are described in the module docstrings and in
+    INTEGRATION.md instead; they parse and default the same either way."""
+    def text(t):
+        return t if listed else argparse.SUPPRESS
+    parser.add_argument('--segmentation', default='grid', choices=list(models.DCNF_SEGMENTATIONS),
+                        help=text('NON-REFERENCE unless grid: what a superpixel is (dcnf only). grid: the square blocks of '
+                             '--superpixel. slic: SLIC superpixels of the resized image, each pixel joining one of the 3 x 3 '
+                             'clusters around its block, so the pair graph and the CRF stay the grid\'s (Liu et al. 2015 define '
+                             'DCNF over such an over-segmentation); targets, colour statistics and the pooled features are taken '
+                             'over the labels, and the two similarities are the paper\'s (mean colours, frequency histograms). '
+                             'Needs --unary fcsp; not with --pairwise-texture or --min-depth / --max-depth yet. No weight '
+                             'depends on it: a checkpoint trained on one segmentation evaluates on the other.'))
+    parser.add_argument('--slic-iters', default=models.DCNF_SLIC_ITERS, type=int,
+                        help=text('--segmentation slic: assignment / update rounds after the grid start (0: the grid).'))
+    parser.add_argument('--slic-compactness', default=models.DCNF_SLIC_COMPACTNESS, type=float,
+                        help=text('--segmentation slic: the colour distance, in units of the [0, 1] RGB range, that one '
+                                  'superpixel edge of distance weighs as much as; larger keeps the superpixels squarer.'))
+
+
 def parse_args(argv=None):
     """The reference's flags verbatim (src/ann3depth.py:221-254), plus --beta2 / --augment / --min-depth / --max-depth / --loss-gradient /
     --train-pairwise / --pairwise-texture / --unary / --seed / --trace-every / --profiler."""
@@ -460,6 +497,7 @@ def parse_args(argv=None):
                              'value is not comparable with the loss at 40). They need --unary fcsp and do not go with '
                              '--min-depth / --max-depth yet. No weight depends on the grid: a checkpoint trained at one '
                              'evaluates at another.')
+    add_segmentation_args(parser)
     parser.add_argument('--seed', default=0, type=int, help='Shuffle-queue seed.')
     parser.add_argument('--tf-checkpoints', action='store_true',
                         help='Also write every checkpoint as a TensorFlow V2 bundle (model.ckpt-N.index/.data-*).')

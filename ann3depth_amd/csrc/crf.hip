@@ -60,12 +60,7 @@ __global__ __launch_bounds__(256) void superpixel_hist_kernel(const float* __res
   __syncthreads();
   for (int i = threadIdx.x; i < sp * sp; i += 256) {
     const int yy = pr * sp + i / sp, xx = pc * sp + i % sp;
-    const float* px = x + (((size_t)b * h + yy) * w + xx) * 3;
-    const float v = __fadd_rn(__fadd_rn(__fmul_rn(px[0], 16777216.f), __fmul_rn(px[1], 65536.f)), __fmul_rn(px[2], 256.f));
-    const float scaled = __fdiv_rn(v, 16777216.f);
-    int idx = (int)floorf(__fmul_rn(256.f, scaled));
-    idx = min(max(idx, 0), 255);
-    atomicAdd(&bins[idx], 1);
+    atomicAdd(&bins[colour_bin(x + (((size_t)b * h + yy) * w + xx) * 3)], 1);
   }
   __syncthreads();
   hist[((size_t)b * rows * cols + p) * 256 + threadIdx.x] = (float)bins[threadIdx.x];

@@ -8,31 +8,13 @@
 // with -ffp-contract=off; the operations are spelled with the __f*_rn intrinsics all the same.
 #include "a3d_internal.h"
 #include "../../include/a3d_fcsp.h"
+#include "pool_lanes.h"
 
 namespace a3d {
 namespace {
 
 constexpr int kMaxSp = A3DF_MAX_SP;
 constexpr int kChunk = 64;      // superpixel rows / columns whose counts the backward holds at a time
-
-template <int VEC>
-__device__ inline void load(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-  } else {
-    v[0] = *p;
-  }
-}
-
-template <int VEC>
-__device__ inline void store(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    *p = v[0];
-  }
-}
 
 // One block per (image, superpixel) and per blockDim.x * VEC channels (gridDim.y).  Per axis the block reduces the
 // window's sp table entries to the ascending list of its distinct in-range cells and their counts; arbitrary tables
@@ -181,10 +163,6 @@ int pool_args(const char* who, int n, int h, int w, int C, const void* a, const 
                 "%s: more than 2^31 - 1 cells or superpixels", who);
   A3D_CHECK_ARG(C <= (1 << 22), "%s: C = %d above 2^22", who, C);
   return A3D_OK;
-}
-
-bool vec4_ok(int C, int ld, int ldp, const void* a, const void* b) {
-  return C % 4 == 0 && ld % 4 == 0 && ldp % 4 == 0 && aligned16(a) && aligned16(b);
 }
 
 }  // namespace

@@ -30,6 +30,13 @@ superpixels of (y - mean)^2 / var in float64 on the host, which is 1 for a calib
 variance of y itself), ``hidden_fraction`` (hidden / measured superpixels, images whose system was rejected left out) and
 ``rejected_systems``.  Without the flag nothing more is launched and the report has no new key.
 
+``--segmentation slic [--slic-iters N --slic-compactness M]`` (NON-REFERENCE, dcnf, a checkpoint of ``--unary fcsp``;
+include/a3d_slic.h, DCNFReplica(segmentation='slic'); the training driver's three flags, not listed by ``--help``) runs the
+field over SLIC superpixels of the resized image instead of square blocks, at any ``--superpixel``; no weight depends on
+it.  ``unary`` and ``crf`` are painted onto 240 x 320 by the labels (DCNFReplica.depth_map) before the metrics kernel reads
+them, and the report gains ``segmentation``, ``slic_iters``, ``slic_compactness``.  Refused with it, before any GPU work:
+``--upsample joint``, ``--observed-nll``, ``--condition``.  Without the flag (``grid``) nothing differs.
+
 Output: one JSON line on stdout, ``<ckptdir>/<model>_<id>/eval-<global_step>.json`` and TensorBoard scalars
 ``eval/<output>/<metric>`` (and ``eval/crf_nll``) at the checkpoint's global step.  Exit code 2 when there is nothing to
 evaluate (no checkpoint, no test split) or the request is unsupported (an unknown model, more than one process).
@@ -43,7 +50,7 @@ import numpy as np
 import torch
 
 from . import data, ops, summary, tfckpt
-from .ann3depth import latest_checkpoint, load_checkpoint, read_checkpoint
+from .ann3depth import add_segmentation_args, latest_checkpoint, load_checkpoint, read_checkpoint
 from .feed import DeviceFeed
 
 OUTPUTS = {'msdn': ('coarse', 'fine'), 'dcnf': ('unary', 'crf')}
@@ -172,7 +179,7 @@ class DCNFEvaluator(MetricRows):
         self.nll.append(rep.nll(depths, n))                                      # the mean over these n images
         target = rep.depths240[:n] if self.resolution == 'grid' else depths[:n]
         for name, out in zip(OUTPUTS['dcnf'], (unary, crf)):
-            self.judge(name, out, n, target)
+            self.judge(name, rep.depth_map(out) if rep.slic else out, n, target)     # a label map has no grid to sample
         if self.upsample is not None:
             self.judge('crf_joint', self.upsample(crf[:n], images[:n]), n, target)
         self.status.append(rep.status[:n].clone())
@@ -240,7 +247,8 @@ def restore_replica(args, ckpt, say, dev=None):
     unary), the last two what a dcnf checkpoint says about its own form.  None, after say(why), for a checkpoint this
     model and --superpixel cannot use.  dev: the GPU to restore to; None (the prediction driver) reads the checkpoint on
     the host and asks for the current GPU only once nothing is left to refuse."""
-    from .models import DCNF_PAIR_PREFIX, DCNF_PREFIX, DCNFReplica, MSDNReplica, check_dcnf_superpixel
+    from .models import (DCNF_PAIR_PREFIX, DCNF_PREFIX, DCNFReplica, MSDNReplica, check_dcnf_segmentation,
+                         check_dcnf_superpixel)
     say(f'restoring {ckpt}')
     state, bundle = read_checkpoint(ckpt, 'cpu' if dev is None else dev)
     texture, unary = False, 'patch'
@@ -261,11 +269,17 @@ def restore_replica(args, ckpt, say, dev=None):
         except ValueError as e:
             say(f'{ckpt}: a checkpoint of the patch form; {e}.')
             return None
+        try:
+            check_dcnf_segmentation(args.segmentation, unary, texture, None, args.slic_iters, args.slic_compactness)
+        except ValueError as e:
+            say(f'{ckpt}: a checkpoint of --unary {unary}{" --pairwise-texture" if texture else ""}; {e}.')
+            return None
     if dev is None:
         dev = current_gpu('prediction')
     if args.model == 'dcnf':
         replica = DCNFReplica(args.batchsize, device=dev, precision=args.precision, pairwise_texture=texture, unary=unary,
-                              superpixel=args.superpixel)
+                              superpixel=args.superpixel, segmentation=args.segmentation, slic_iters=args.slic_iters,
+                              slic_compactness=args.slic_compactness)
     else:
         replica = MSDNReplica(args.batchsize, device=dev, precision=args.precision, keep_dense_grads=False)
     load_checkpoint(replica, state, bundle)
@@ -282,6 +296,25 @@ def refuse_model(args, say, can, own=lambda: None):
         return 2
     if args.superpixel != 40 and args.model != 'dcnf':
         say(f'--superpixel {args.superpixel} sets the grid of the CRF of --model dcnf: {args.model} has no superpixels.')
+        return 2
+    if args.segmentation != 'grid' and args.model != 'dcnf':
+        say(f'--segmentation {args.segmentation} chooses the superpixels of the CRF of --model dcnf: {args.model} has no '
+            f'superpixels.')
+        return 2
+
+
+def refuse_under_slic(args, say, flags):
+    """2 after say(why) when --segmentation slic meets one of `flags`, (flag text, given?) pairs of what a driver cannot do
+    on a label map yet, or --slic-iters / --slic-compactness outside their range; before any GPU work."""
+    if args.segmentation != 'slic':
+        return None
+    for flag, given in flags:
+        if given:
+            say(f'--segmentation slic cannot go with {flag} yet: it reads the square blocks of the grid, and its form on a '
+                f'label map is a later change.')
+            return 2
+    if args.slic_iters < 0 or not 0 <= args.slic_compactness < float('inf'):
+        say(f'--slic-iters {args.slic_iters} must be >= 0 and --slic-compactness {args.slic_compactness} finite and >= 0.')
         return 2
 
 
@@ -323,6 +356,9 @@ def main(argv=None):
     if args.superpixel != 40 and args.observed_nll:
         _say(f'--superpixel {args.superpixel} cannot go with --observed-nll yet: the likelihood of the observed superpixels '
              f'alone exists only for the dense 6 x 8 CRF (--superpixel 40).')
+        return 2
+    if refuse_under_slic(args, _say, (('--upsample joint', args.upsample == 'joint'), ('--observed-nll', args.observed_nll),
+                                      ('--condition', args.condition is not None))):
         return 2
     if args.condition is not None:
         if args.model != 'dcnf':
@@ -378,6 +414,8 @@ def main(argv=None):
         out['unary_form'] = unary          # ('unary' holds the metrics of the unary output)
     if args.model == 'dcnf':
         out['superpixel'] = args.superpixel
+    if args.segmentation != 'grid':
+        out.update(segmentation=args.segmentation, slic_iters=args.slic_iters, slic_compactness=args.slic_compactness)
     if upsample is not None:
         out.update(upsample='joint', radius=upsample.radius, sigma_space=upsample.sigma_space,
                    sigma_range=upsample.sigma_range)
@@ -436,6 +474,7 @@ def parse_args(argv=None):
                         'and crf_hidden (the plain MAP) are judged on the pixels of the hidden ones.')
     p.add_argument('--condition-seed', default=0, type=int,
                    help='--condition: the masks are drawn on the host from (this seed, the record\'s index).')
+    add_shared_args(p, 'segmentation')
     add_upsample_args(p, ['none', 'joint'], 'none',
                       'NON-REFERENCE: joint also judges a third output, fine_joint (msdn) or crf_joint (dcnf): the prediction '
                       'brought to the record image\'s size by joint bilateral upsampling under the image '
@@ -458,6 +497,9 @@ def add_shared_args(p, *names, **text):
         'superpixel': (('--superpixel',), dict(default=40, type=int, choices=[40, 20, 10])),
     }
     for name in names:
+        if name == 'segmentation':                  # --segmentation, --slic-iters, --slic-compactness: the training driver's
+            add_segmentation_args(p, listed=False)
+            continue
         flags, kw = shared[name]
         p.add_argument(*flags, **dict(kw, **({'help': text[name]} if name in text else {})))
 

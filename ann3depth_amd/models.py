@@ -1376,7 +1376,10 @@ class DCNFUnaryFCSP(DCNFUnary):
     fcsp_maps) and the [B * S, 256] rows go through the reference's three dense layers.  Only dense/kernel changes shape,
     [256,128] for [12544,128]; the parameters come from the same stream in the same order, so at equal seed the conv
     kernels are DCNFUnary's bits.  Offers what DCNFReplica uses of DCNFUnary; P is the number of dense rows, B * S.
-    image_hw, sp, fuse_pool: for tests (DCNFReplica runs at 240x320, 40, fused)."""
+    image_hw, sp, fuse_pool: for tests (DCNFReplica runs at 240x320, 40, fused).
+    labels, label_count (None by default): a label map [B,H,W] and counts [B,S] int32 that DCNFReplica(segmentation='slic')
+    attaches; the pooling and its transpose then run over the superpixels of that map (ops.label_pool_fwd / _bwd,
+    include/a3d_slic.h) and read what the two tensors hold at the time of the launch."""
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, precision='fp32',
                  image_hw=(DCNF_IMG_H, DCNF_IMG_W), sp=DCNF_SP, fuse_pool=None):
@@ -1437,6 +1440,7 @@ class DCNFUnaryFCSP(DCNFUnary):
                     self.argmax[n] = torch.empty((batchsize, h, w, co), dtype=torch.uint8, device=dev)
         self.map_hw = (h, w)
         self.map = ops.FcspMap(*fcsp_maps(H, W, h, w, 'centre'), h, w, sp, device=dev)
+        self.labels = self.label_count = None       # DCNFReplica(segmentation='slic') attaches its label map and counts
         self.act['pooled'] = buf(P, feat)
         for n, i, o, _ in DCNF_DENSES:
             self.act[n] = buf(P, o)
@@ -1447,7 +1451,11 @@ class DCNFUnaryFCSP(DCNFUnary):
     def forward_resized(self, record_argmax=True):
         """The stack over self.resized as it stands (see DCNFUnary.forward_resized)."""
         t = self._forward_convs(self.resized, record_argmax)
-        ops.superpixel_pool_fwd(t, self.map, self.act['pooled'].view(self.B, self.S, -1))
+        pooled = self.act['pooled'].view(self.B, self.S, -1)
+        if self.labels is None:
+            ops.superpixel_pool_fwd(t, self.map, pooled)
+        else:
+            ops.label_pool_fwd(t, self.map, self.labels, self.label_count, pooled)
         self._forward_denses(self.act['pooled'])
         return self.z.view(self.B, self.S, 1)
 
@@ -1458,7 +1466,10 @@ class DCNFUnaryFCSP(DCNFUnary):
         dpooled = self._dbuf('pooled', a['pooled'])
         ops.dense_bwd_data(d0, self.var('dense/kernel'), dpooled)
         dflat = self._dbuf('flat', a['conv2d_4/pool'])
-        ops.superpixel_pool_bwd(dpooled.view(self.B, self.S, -1), self.map, dflat)     # writes every element
+        if self.labels is None:
+            ops.superpixel_pool_bwd(dpooled.view(self.B, self.S, -1), self.map, dflat)     # writes every element
+        else:
+            ops.label_pool_bwd(dpooled.view(self.B, self.S, -1), self.map, self.labels, self.label_count, dflat)
         self._backward_convs(dflat)
 
     def load_convs_from(self, state):
@@ -1497,6 +1508,33 @@ def check_dcnf_superpixel(superpixel, unary, valid_range):
         raise ValueError(f'superpixel {superpixel} cannot go with --min-depth / --max-depth yet: the likelihood of the '
                          f'observed superpixels alone exists only for the dense 6 x 8 CRF (--superpixel 40); on the banded '
                          f'CRF it is a later change')
+
+
+DCNF_SEGMENTATIONS = ('grid', 'slic')    # --segmentation
+DCNF_SLIC_ITERS, DCNF_SLIC_COMPACTNESS = 5, 0.1
+
+
+def check_dcnf_segmentation(segmentation, unary, pairwise_texture, valid_range, slic_iters=DCNF_SLIC_ITERS,
+                            slic_compactness=DCNF_SLIC_COMPACTNESS):
+    """ValueError unless DCNFReplica can run on this segmentation with this unary form, these similarities and these
+    targets (the drivers call it before any GPU work)."""
+    if segmentation not in DCNF_SEGMENTATIONS:
+        raise ValueError(f'segmentation {segmentation!r}: one of {DCNF_SEGMENTATIONS} (--segmentation)')
+    if segmentation == 'grid':
+        return
+    if unary != 'fcsp':
+        raise ValueError('--segmentation slic needs --unary fcsp: a patch is a square around a grid block, not a '
+                         'superpixel of a label map')
+    if pairwise_texture:
+        raise ValueError('--segmentation slic cannot go with --pairwise-texture yet: the LBP histogram over the pixels of a '
+                         'label map is a later change')
+    if valid_range is not None:
+        raise ValueError('--segmentation slic cannot go with --min-depth / --max-depth yet: the mean over the measured '
+                         'pixels of a label map is a later change')
+    if int(slic_iters) != slic_iters or slic_iters < 0:
+        raise ValueError(f'--slic-iters {slic_iters!r}: a non-negative integer')
+    if not 0 <= float(slic_compactness) < float('inf'):
+        raise ValueError(f'--slic-compactness {slic_compactness!r}: a finite number >= 0')
 
 
 def dcnf_pair_indices(rows, cols):
@@ -1560,15 +1598,36 @@ class DCNFReplica(Replica):
     float32 value from S = 156.  Its value is not comparable with the --superpixel 40 loss.  The likelihood exists only for
     a positive definite A, so at 20 and 10 construction projects the pairwise kernel and bias onto >= 0 whether or not
     they train (r >= 0 makes A strictly diagonally dominant, every pivot >= 1).  40 (the default): today's code path,
-    launches, buffers and bits."""
+    launches, buffers and bits.
+
+    segmentation (NON-REFERENCE, --segmentation slic): 'slic' runs the field over SLIC superpixels of the resized image
+    instead of square blocks (include/a3d_slic.h), the over-segmentation Liu et al. 2015 define DCNF on.  A pixel may only
+    join one of the 3 x 3 clusters around its home block, so superpixel (R, C) stays within the blocks (R +- 1, C +- 1)
+    and the pair graph, the CRF kernels and the band are the grid's, at all three --superpixel values.  Right after the
+    resize, step, forward, predict and nll segment unary.resized (ops.slic_segment -> self.labels [B,240,320] int32,
+    self.centres, self.label_count); the unary pools its last map over the labels (ops.label_pool_fwd / _bwd), y is
+    ops.label_mean of the resized depth map, and r comes from the paper's similarities, the distance of the mean colours
+    and of the frequency histograms, both in (0, 1] (ops.label_mean, ops.label_hist, ops.label_pair_similarity); the
+    reference's grid similarities compare two blocks pixel by pixel and have no meaning for two shapes.  Everything else
+    (pairs, loss, MAP, train_pairwise, descent, reducer, checkpoints, variable names and shapes) is the same code, and no
+    weight depends on the segmentation: a checkpoint trained on one evaluates on the other.  predict() still returns
+    [B, rows, cols]; depth_map() paints such values onto the pixels.  slic_iters = 5 and slic_compactness = 0.1 (in units
+    of the [0, 1] RGB range) are choices, not derivations: few iterations move most of what will move, and 0.1 lets an edge
+    of a tenth of the colour range outweigh a block's width.  RGB, not CIELAB, and no connectivity post-pass: the
+    statistics do not need connected superpixels.  Needs unary='fcsp', no pairwise_texture, no valid_range; posterior()
+    is refused.  'grid' (the default): no launch, buffer, bit, message or refusal differs."""
     uses_dropout = False
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, global_step=0, reducer=None,
                  precision='fp32', train_pairwise=False, pairwise_texture=False, valid_range=None, min_valid=0.5,
-                 unary='patch', superpixel=DCNF_SP):
+                 unary='patch', superpixel=DCNF_SP, segmentation='grid', slic_iters=DCNF_SLIC_ITERS,
+                 slic_compactness=DCNF_SLIC_COMPACTNESS):
         if unary not in ('patch', 'fcsp'):
             raise ValueError(f"unary {unary!r}: 'patch' or 'fcsp'")
         self.unary_form = unary
+        check_dcnf_segmentation(segmentation, unary, pairwise_texture, valid_range, slic_iters, slic_compactness)
+        self.slic = segmentation == 'slic'
+        self.segmentation, self.slic_iters, self.slic_compactness = segmentation, int(slic_iters), float(slic_compactness)
         check_dcnf_superpixel(superpixel, unary, valid_range)
         self.sp = sp = int(superpixel)
         self.banded = sp != DCNF_SP
@@ -1622,6 +1681,14 @@ class DCNFReplica(Replica):
         self.sims = self.r = self.loss = self.loss_per_image = self.dz = self.dr = None
         self.crf = torch.empty((batchsize, self.nsp), device=dev)                          # predict(): the MAP depths
         self.status = torch.empty((batchsize,), dtype=torch.int32, device=dev)
+        self.labels = None
+        if self.slic:
+            self.labels = torch.empty((batchsize, DCNF_IMG_H, DCNF_IMG_W), dtype=torch.int32, device=dev)
+            self.centres = torch.empty((batchsize, self.nsp, 5), device=dev)
+            self.label_count = torch.empty((batchsize, self.nsp), dtype=torch.int32, device=dev)
+            self.mean3 = torch.empty((batchsize, self.nsp, 3), device=dev)
+            self.count3 = torch.empty((batchsize, self.nsp), dtype=torch.int32, device=dev)
+            self.unary.labels, self.unary.label_count = self.labels, self.label_count
 
     def pair_var(self, name):
         return self.pair_group.view(self.pair_group.var, DCNF_PAIR_PREFIX + name)
@@ -1646,6 +1713,12 @@ class DCNFReplica(Replica):
     def _pairwise(self):
         """The similarities of every pair and the pair weights r from the resized images (src/models.py:112-127)."""
         x = self.unary.resized
+        if self.slic:
+            ops.label_mean(x, self.sp, self.labels, self.mean3, self.count3)
+            ops.label_hist(x, self.sp, self.labels, self.hist)
+            self.sims, self.r = ops.label_pair_similarity(self.mean3, self.hist, self.label_count, self.left, self.right,
+                                                          self.pair_var('kernel'), self.pair_var('bias'), DCNF_GAMMA)
+            return
         ops.superpixel_hist(x, self.sp, self.hist)                                        # :112-113
         kernel, bias = self.pair_var('kernel'), self.pair_var('bias')
         if self.pairwise_texture:
@@ -1658,8 +1731,27 @@ class DCNFReplica(Replica):
 
     def forward(self, images, depths):
         """z, r and the loss; leaves d loss / d z in self.dz."""
-        self.unary.forward(images)                                                        # src/models.py:180,183
+        if self.slic:
+            ops.resize_bilinear_tf1(images, self.unary.resized)                           # unary.forward's first launch
+            self._segment()
+            self.unary.forward_resized()
+        else:
+            self.unary.forward(images)                                                    # src/models.py:180,183
         return self.forward_crf(depths)
+
+    def _segment(self):
+        """SLIC superpixels of unary.resized as it stands, into self.labels, self.centres and self.label_count."""
+        ops.slic_segment(self.unary.resized, self.sp, self.slic_iters, self.slic_compactness, self.labels, self.centres,
+                         self.label_count)
+
+    def depth_map(self, values):
+        """Per-superpixel values [B, rows, cols] (or [B, nsp]) painted onto the pixels -> [B, 240, 320]: every pixel gets
+        the value of its superpixel, by the labels of the last forward under segmentation='slic', by the blocks otherwise."""
+        values = values.reshape(self.B, self.nsp)
+        if self.slic:
+            return ops.paint_labels(values, self.labels)
+        return values.view(self.B, self.rows, 1, self.cols, 1).expand(-1, -1, self.sp, -1, self.sp).reshape(
+            self.B, DCNF_IMG_H, DCNF_IMG_W)
 
     def forward_crf(self, depths):
         """Everything after the unary stack: target superpixels, pairwise r, CRF loss and d loss / d z."""
@@ -1674,7 +1766,10 @@ class DCNFReplica(Replica):
         is no target, the numbers of measured pixels in self.count."""
         if valid_range is None:
             ops.resize_bilinear_tf1(depths[:n], self.depths240[:n])
-            ops.superpixel_mean(self.depths240[:n], self.sp, self.y[:n])
+            if self.slic:
+                ops.label_mean(self.depths240[:n], self.sp, self.labels[:n], self.y[:n], self.count3[:n])
+            else:
+                ops.superpixel_mean(self.depths240[:n], self.sp, self.y[:n])
             return
         if self.t_one is None:
             self.t_one = torch.empty((self.B, 1, 1, 1), device=self.device)
@@ -1710,6 +1805,8 @@ class DCNFReplica(Replica):
         ops.resize_bilinear_tf1(images[:n], u.resized[:n])                               # src/models.py:180
         if n < B:
             u.resized[n:].zero_()
+        if self.slic:
+            self._segment()
         u.forward_resized(record_argmax=False)
         self._pairwise()
         return n
@@ -1746,6 +1843,9 @@ class DCNFReplica(Replica):
         it marks are conditioned on, the others are hidden from the field; self.y keeps every target (NaN where the depth
         map measures none).  Training state, self.valid_range included, is left as it is."""
         B = self.B
+        if self.slic:
+            raise ValueError("posterior: not with segmentation='slic' yet (--segmentation slic): conditioning on the "
+                             'measured pixels of a label map is a later change')
         if images is None and (self.r is None or n is None):
             raise ValueError('posterior: images None reuses the last predict(): call it first and pass n')
         n = images.shape[0] if n is None else int(n)
@@ -1790,6 +1890,8 @@ class DCNFReplica(Replica):
         check_rows('nll', n, self.B, f'{depths.shape[0]} depth maps', depths.shape[0], ready=self.r is not None,
                    tail=', after predict()')
         valid_range = self.valid_range if valid_range is None else valid_range
+        if valid_range is not None and self.slic:
+            raise ValueError("nll: segmentation='slic' has no mean over the measured pixels of a label map yet (valid_range)")
         if valid_range is not None and self.banded:
             raise ValueError(f'nll: superpixel {self.sp} has no likelihood of observed superpixels alone yet (valid_range)')
         self._targets(depths, n, valid_range)
@@ -1965,6 +2067,8 @@ class _DistributedConvolutionalNeuralFields:
     min_valid = 0.5      # the share of a superpixel that must be measured for it to be a target (see DCNFReplica)
     unary = 'patch'      # NON-REFERENCE, --unary fcsp: convs once over the image + superpixel pooling (see DCNFReplica)
     superpixel = DCNF_SP  # NON-REFERENCE, --superpixel 20 / 10: finer grids on the banded CRF (see DCNFReplica)
+    segmentation = 'grid'  # NON-REFERENCE, --segmentation slic: SLIC superpixels in place of square blocks (see DCNFReplica)
+    slic_iters, slic_compactness = DCNF_SLIC_ITERS, DCNF_SLIC_COMPACTNESS
 
     def __call__(self, images, depths, train=True):
         assert images.pipeline is depths.pipeline, 'inputs and targets must come from the same data.inputs() call'
@@ -1973,7 +2077,8 @@ class _DistributedConvolutionalNeuralFields:
                               seed=self.seed, reducer=self.reducer, precision=self.precision,
                               train_pairwise=self.train_pairwise and train, pairwise_texture=self.pairwise_texture,
                               valid_range=self.valid_range, min_valid=self.min_valid, unary=self.unary,
-                              superpixel=self.superpixel)
+                              superpixel=self.superpixel, segmentation=self.segmentation, slic_iters=self.slic_iters,
+                              slic_compactness=self.slic_compactness)
         if self.reducer is not None:
             for g in replica.groups.values():
                 self.reducer.broadcast(g.var)

@@ -1044,6 +1044,176 @@ def superpixel_pool_bwd(dpooled, tables, dfeat, channels=None):
     return dfeat
 
 
+SLIC_MAX_SP = 64               # A3DS_MAX_SP
+SLIC_MAX_CELLS = 4096          # A3DS_MAX_CELLS: the label pooling's forward keeps one count per cell of the map in LDS
+SLIC_MAX_SUPERPIXELS = 768     # A3DS_MAX_SUPERPIXELS: its backward one per superpixel of an image
+
+
+def _slic_image(who, x, sp, channels, labels=None, coords=False):
+    """(n, H, W, S) of a label call on a non-empty image batch x [n,H,W,channels] float32 with labels [n,H,W] int32 (when
+    given), or ValueError / TypeError.  channels: an int, or None for 1 .. 4.  coords: the call forms coordinate means."""
+    sp = int(sp)
+    ok = x.dim() == 4 and x.numel() > 0 and 0 < sp <= SLIC_MAX_SP and x.shape[1] % sp == 0 and x.shape[2] % sp == 0
+    if not ok or (x.shape[3] != channels if channels is not None else not 1 <= x.shape[3] <= 4):
+        raise ValueError(f'{who}: x {tuple(x.shape)} is not a non-empty [n, H, W, {channels or "1 .. 4"}] with H, W multiples '
+                         f'of sp = {sp} <= {SLIC_MAX_SP}')
+    n, H, W, _ = x.shape
+    if coords and 9 * sp * sp * max(H, W) >= 1 << 24:
+        raise ValueError(f'{who}: 9 sp^2 max(H, W) = {9 * sp * sp * max(H, W)} reaches 2^24 (H {H}, W {W}, sp {sp}): the '
+                         f'coordinate sums would not be exact in float32')
+    if labels is not None and tuple(labels.shape) != (n, H, W):
+        raise ValueError(f'{who}: labels {tuple(labels.shape)} for x {tuple(x.shape)} must be {(n, H, W)}')
+    return n, H, W, (H // sp) * (W // sp)
+
+
+def _slic_out(who, name, t, shape, dtype, device):
+    """The output tensor `t`, allocated when None, or ValueError unless it has the shape."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f'{who}: {name} {tuple(t.shape)} must be {tuple(shape)}')
+    return t
+
+
+def _slic_compactness(who, compactness):
+    compactness = float(compactness)
+    if not 0 <= compactness < float('inf'):
+        raise ValueError(f'{who}: compactness {compactness} is negative or not finite')
+    return compactness
+
+
+def label_mean(x, sp, labels, mean=None, count=None):
+    """NON-REFERENCE (a3ds_label_mean): x [n,H,W,c] float32 (c in 1 .. 4), labels [n,H,W] int32 -> (mean [n,S,c] float32,
+    count [n,S] int32) over the pixels that count for every superpixel (label s, and s among the pixel's 3 x 3 candidates);
+    NaN where count is 0."""
+    n, H, W, S = _slic_image('label_mean', x, sp, None, labels)
+    c = x.shape[3]
+    mean = _slic_out('label_mean', 'mean', mean, (n, S, c), torch.float32, x.device)
+    count = _slic_out('label_mean', 'count', count, (n, S), torch.int32, x.device)
+    _check_operands('label_mean', (x, mean), (labels, count), 'x, mean float32; labels, count int32')
+    check(_lib.load().a3ds_label_mean(n, H, W, c, _ptr(x), int(sp), _ptr(labels), _ptr(mean), _ptr(count), _stream()),
+          'a3ds_label_mean')
+    return mean, count
+
+
+def label_hist(x, sp, labels, out=None):
+    """NON-REFERENCE (a3ds_label_hist): superpixel_hist over the pixels that count for every superpixel of a label map:
+    x [n,H,W,3] float32, labels [n,H,W] int32 -> [n,S,256] float32 integer counts."""
+    n, H, W, S = _slic_image('label_hist', x, sp, 3, labels)
+    out = _slic_out('label_hist', 'out', out, (n, S, 256), torch.float32, x.device)
+    _check_operands('label_hist', (x, out), (labels,), 'x, out float32; labels int32')
+    check(_lib.load().a3ds_label_hist(n, H, W, _ptr(x), int(sp), _ptr(labels), _ptr(out), _stream()), 'a3ds_label_hist')
+    return out
+
+
+def slic_update(x, sp, labels, centres, count=None):
+    """NON-REFERENCE (a3ds_slic_update): the centres (ybar, xbar, c0, c1, c2) of a segmentation, written into centres
+    [n,S,5] (in/out: the row of a superpixel without pixels is left alone); returns (centres, count [n,S] int32)."""
+    n, H, W, S = _slic_image('slic_update', x, sp, 3, labels, coords=True)
+    centres = _slic_out('slic_update', 'centres', centres, (n, S, 5), torch.float32, x.device)
+    count = _slic_out('slic_update', 'count', count, (n, S), torch.int32, x.device)
+    _check_operands('slic_update', (x, centres), (labels, count), 'x, centres float32; labels, count int32')
+    check(_lib.load().a3ds_slic_update(n, H, W, _ptr(x), int(sp), _ptr(labels), _ptr(centres), _ptr(count), _stream()),
+          'a3ds_slic_update')
+    return centres, count
+
+
+def slic_assign(x, sp, centres, compactness, labels=None):
+    """NON-REFERENCE (a3ds_slic_assign): every pixel to the nearest of the up to nine centres around its home cell, in
+    colour plus (compactness / sp)^2 times position; ties to the lowest index, NaN distances skipped, the anchor pixel of
+    every cell kept.  x [n,H,W,3], centres [n,S,5] float32 -> labels [n,H,W] int32."""
+    n, H, W, S = _slic_image('slic_assign', x, sp, 3, labels, coords=True)
+    compactness = _slic_compactness('slic_assign', compactness)
+    if tuple(centres.shape) != (n, S, 5):
+        raise ValueError(f'slic_assign: centres {tuple(centres.shape)} must be {(n, S, 5)}')
+    labels = _slic_out('slic_assign', 'labels', labels, (n, H, W), torch.int32, x.device)
+    _check_operands('slic_assign', (x, centres), (labels,), 'x, centres float32; labels int32')
+    check(_lib.load().a3ds_slic_assign(n, H, W, _ptr(x), int(sp), _ptr(centres), compactness, _ptr(labels), _stream()),
+          'a3ds_slic_assign')
+    return labels
+
+
+def slic_segment(x, sp, iters=5, compactness=0.1, labels=None, centres=None, count=None):
+    """NON-REFERENCE (a3ds_slic_segment): grid labels, slic_update, then iters x (slic_assign, slic_update): x [n,H,W,3]
+    float32 -> (labels [n,H,W] int32, centres [n,S,5] float32, count [n,S] int32).  iters = 0 gives the grid."""
+    n, H, W, S = _slic_image('slic_segment', x, sp, 3, labels, coords=True)
+    compactness = _slic_compactness('slic_segment', compactness)
+    if int(iters) != iters or iters < 0:
+        raise ValueError(f'slic_segment: iters {iters} is not a non-negative integer')
+    labels = _slic_out('slic_segment', 'labels', labels, (n, H, W), torch.int32, x.device)
+    centres = _slic_out('slic_segment', 'centres', centres, (n, S, 5), torch.float32, x.device)
+    count = _slic_out('slic_segment', 'count', count, (n, S), torch.int32, x.device)
+    _check_operands('slic_segment', (x, centres), (labels, count), 'x, centres float32; labels, count int32')
+    check(_lib.load().a3ds_slic_segment(n, H, W, _ptr(x), int(sp), int(iters), compactness, _ptr(labels), _ptr(centres),
+                                        _ptr(count), _stream()), 'a3ds_slic_segment')
+    return labels, centres, count
+
+
+def label_pair_similarity(mean3, hist, count, left, right, dense_w, dense_b, gamma=1.0):
+    """NON-REFERENCE (a3ds_pair_similarity): the paper's colour and histogram similarities from label statistics, and the
+    pairwise dense layer: mean3 [n,S,3], hist [n,S,256] float32, count [n,S] int32, left, right [Q] int32, dense_w 2 and
+    dense_b 1 float32 values -> (sims [n,Q,2], r [n,Q]).  A pair with an index outside [0, S) gets NaN."""
+    who = 'label_pair_similarity'
+    q = left.numel()
+    if (mean3.dim() != 3 or mean3.shape[2] != 3 or mean3.numel() == 0 or tuple(hist.shape) != (*mean3.shape[:2], 256)
+            or tuple(count.shape) != tuple(mean3.shape[:2]) or q == 0 or right.numel() != q or dense_w.numel() != 2
+            or dense_b.numel() != 1):
+        raise ValueError(f'{who}: mean3 {tuple(mean3.shape)}, hist {tuple(hist.shape)}, count {tuple(count.shape)}, {q} / '
+                         f'{right.numel()} pair indices, dense kernel {tuple(dense_w.shape)}, bias {tuple(dense_b.shape)}')
+    _check_operands(who, (mean3, hist, dense_w, dense_b), (count, left, right),
+                    'mean3, hist, dense_w, dense_b float32; count, left, right int32')
+    n, S, _ = mean3.shape
+    sims = torch.empty((n, q, 2), dtype=torch.float32, device=mean3.device)
+    r = torch.empty((n, q), dtype=torch.float32, device=mean3.device)
+    check(_lib.load().a3ds_pair_similarity(n, S, _ptr(mean3), _ptr(hist), _ptr(count), _ptr(left), _ptr(right), q,
+                                           _ptr(dense_w), _ptr(dense_b), gamma, _ptr(sims), _ptr(r), _stream()),
+          'a3ds_pair_similarity')
+    return sims, r
+
+
+def _label_pool_args(who, feat, tables, labels, count, pooled, channels):
+    """_fcsp_args plus the label map and counts of a3ds_label_pool_*: labels [n,H,W], count [n,S] int32."""
+    args = _fcsp_args(who, feat, tables, pooled, channels)
+    n, h, w, _, _, H, W, _, _, _, S, _ = args
+    if h * w > SLIC_MAX_CELLS or S > SLIC_MAX_SUPERPIXELS:
+        raise ValueError(f'{who}: a map of {h * w} cells (at most {SLIC_MAX_CELLS}), {S} superpixels (at most '
+                         f'{SLIC_MAX_SUPERPIXELS})')
+    if tuple(labels.shape) != (n, H, W) or tuple(count.shape) != (n, S):
+        raise ValueError(f'{who}: labels {tuple(labels.shape)}, count {tuple(count.shape)} must be {(n, H, W)}, {(n, S)}')
+    _check_operands(who, (feat,), (labels, count), 'labels, count int32')
+    return args
+
+
+def label_pool_fwd(feat, tables, labels, count, pooled=None, channels=None):
+    """NON-REFERENCE (a3ds_label_pool_fwd): superpixel_pool_fwd over the superpixels of a label map: the mean of the
+    upsampled feature map over the pixels that count for each, divided by count [n,S]; +0 where count is 0."""
+    n, h, w, C, ld, H, W, sp, ymap, xmap, S, ldp = _label_pool_args('label_pool_fwd', feat, tables, labels, count, pooled,
+                                                                    channels)
+    if pooled is None:
+        pooled = torch.empty((n, S, C), dtype=torch.float32, device=feat.device)
+    check(_lib.load().a3ds_label_pool_fwd(n, h, w, C, _ptr(feat), ld, H, W, sp, _ptr(ymap), _ptr(xmap), _ptr(labels),
+                                          _ptr(count), _ptr(pooled), ldp, _stream()), 'a3ds_label_pool_fwd')
+    return pooled
+
+
+def label_pool_bwd(dpooled, tables, labels, count, dfeat, channels=None):
+    """NON-REFERENCE (a3ds_label_pool_bwd): the exact transpose, dpooled [n,S,ldp] -> dfeat [n,h,w,ld]; every element of
+    dfeat[..., :channels] is written."""
+    n, h, w, C, ld, H, W, sp, ymap, xmap, S, ldp = _label_pool_args('label_pool_bwd', dfeat, tables, labels, count, dpooled,
+                                                                    channels)
+    check(_lib.load().a3ds_label_pool_bwd(n, h, w, C, _ptr(dpooled), ldp, H, W, sp, _ptr(ymap), _ptr(xmap), _ptr(labels),
+                                          _ptr(count), _ptr(dfeat), ld, _stream()), 'a3ds_label_pool_bwd')
+    return dfeat
+
+
+def paint_labels(values, labels):
+    """values [n,S] -> [n,H,W]: every pixel gets the value of its label (labels [n,H,W] int32, all in [0, S): a
+    segmentation of slic_segment).  Plumbing, a torch.gather; not on the training path."""
+    if values.dim() != 2 or labels.dim() != 3 or labels.shape[0] != values.shape[0]:
+        raise ValueError(f'paint_labels: values {tuple(values.shape)}, labels {tuple(labels.shape)}')
+    return torch.gather(values, 1, labels.reshape(labels.shape[0], -1).long()).reshape(labels.shape)
+
+
 UPSAMPLE_MAX_RADIUS = 4      # A3DU_MAX_RADIUS: 81 cells per output pixel
 UPSAMPLE_GRID = (240, 320)   # the grid DCNF's superpixels are cut from (models.DCNF_IMG_H, DCNF_IMG_W)
 

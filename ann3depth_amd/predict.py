@@ -29,7 +29,14 @@ DCNFReplica.posterior); msdn has no distribution, so both flags are refused for 
                   back as their block means, the others as the conditional mean, and sigma is 0 and the conditional
                   standard deviation.  A missing file, or one of another rank or dtype, exits 2 before any GPU work.
 With either flag the JSON line gains `uncertainty`, `conditioned`, `observed_fraction` (the share of superpixels a file
-measured; 0 without --depths) and `rejected_systems` (images whose system was not positive definite: NaN maps)."""
+measured; 0 without --depths) and `rejected_systems` (images whose system was not positive definite: NaN maps).
+
+--segmentation slic [--slic-iters N --slic-compactness M] (NON-REFERENCE, dcnf, a checkpoint of --unary fcsp;
+include/a3d_slic.h; the training driver's three flags, not listed by --help): the field runs over SLIC superpixels of the
+resized image instead of square blocks.  The crf output is painted onto 240 x 320 by the labels, then --upsample bilinear
+resizes that map to the image's size and --upsample none writes it as it is; the JSON line gains `segmentation`,
+`slic_iters`, `slic_compactness`.  Refused with it, before any GPU work: --upsample joint (the default: name bilinear or
+none), --uncertainty, --depths."""
 import argparse
 import json
 import os
@@ -39,7 +46,8 @@ import numpy as np
 import torch
 
 from . import imresize, ops, png
-from .evaluate import OUTPUTS, add_shared_args, add_upsample_args, open_checkpoint, refuse_model, restore_replica
+from .evaluate import (OUTPUTS, add_shared_args, add_upsample_args, open_checkpoint, refuse_model, refuse_under_slic,
+                       restore_replica)
 
 
 def _say(msg):
@@ -104,6 +112,9 @@ def main(argv=None):
     if args.batchsize <= 0:
         _say(f'--batchsize {args.batchsize} must be positive.')
         return 2
+    if refuse_under_slic(args, _say, (('--upsample joint', args.upsample == 'joint'), ('--uncertainty', args.uncertainty),
+                                      ('--depths', bool(args.depths)))):
+        return 2
     posterior = args.uncertainty or bool(args.depths)
     if posterior and args.model != 'dcnf':
         _say(f'--uncertainty and --depths read the distribution of the CRF of --model dcnf, y ~ N(mu, A^-1 / 2): '
@@ -167,6 +178,8 @@ def main(argv=None):
         pred = replica.predict(pixels, n)[1]                       # fine (msdn) or crf (dcnf), [B, gh, gw]
         if args.model == 'dcnf':
             singular += int(replica.status[:n].sum().item())
+            if replica.slic:
+                pred = replica.depth_map(pred)                     # painted by the labels: [B, 240, 320]
         H, W = pixels.shape[1:3]
         sigma = None
         if posterior:                                  # from the z and r predict() left
@@ -200,6 +213,8 @@ def main(argv=None):
         out.update(radius=upsample.radius, sigma_space=upsample.sigma_space, sigma_range=upsample.sigma_range)
     if args.model == 'dcnf':
         out.update(superpixel=args.superpixel, singular_systems=singular)
+        if args.segmentation != 'grid':
+            out.update(segmentation=args.segmentation, slic_iters=args.slic_iters, slic_compactness=args.slic_compactness)
     if posterior:
         out.update(uncertainty=bool(args.uncertainty), conditioned=measured is not None,
                    observed_fraction=observed / float(len(images) * replica.nsp), rejected_systems=rejected)
@@ -213,7 +228,7 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(description='Depth maps for image files from an MSDN or DCNF checkpoint.')
     p.add_argument('images', nargs='*', type=str, help='8-bit PNG files (RGB or grey; alpha is dropped).')
     p.add_argument('--out', '-o', required=True, type=str, help='Directory for <stem>-depth.npy and <stem>-depth.png.')
-    add_shared_args(p, 'model', 'batchsize', 'ckptdir', 'id', 'checkpoint', 'precision', 'superpixel',
+    add_shared_args(p, 'model', 'batchsize', 'ckptdir', 'id', 'checkpoint', 'precision', 'superpixel', 'segmentation',
                     batchsize='Images of one size that run together.',
                     superpixel='NON-REFERENCE unless 40, dcnf: the edge of the superpixels (6 x 8, 12 x 16 or 24 x 32 depths per '
                                'image before upsampling); 20 and 10 need a checkpoint of --unary fcsp.')

@@ -13,7 +13,12 @@ once over the 240x320 image; `forward_tflops` then counts that form's own multip
 step uses, and `band` holds the band launches alone (nll with dr, nll without, map), their dynamic LDS bytes, the
 workgroups per CU that leaves room for, and the share of the step the step's own launch takes.  --superpixel 40 is the
 run without the flag.
-    python tools/bench_dcnf.py [batch] [--train-pairwise] [--pairwise-texture] [--holes] [--unary fcsp] [--superpixel N] > dcnf.json"""
+--segmentation slic (with --unary fcsp; NON-REFERENCE, DCNFReplica(segmentation='slic')): the step on SLIC superpixels
+(include/a3d_slic.h); `slic` then holds each new launch alone: the segmentation (5 rounds), the label mean of the target and
+of the image, the label histogram, the pair similarities, the label pooling forward and backward.  --segmentation grid is
+the run without the flag.
+    python tools/bench_dcnf.py [batch] [--train-pairwise] [--pairwise-texture] [--holes] [--unary fcsp] [--superpixel N]
+                               [--segmentation slic] > dcnf.json"""
 import json
 import os
 import sys
@@ -38,6 +43,11 @@ if '--superpixel' in argv:
     i = argv.index('--superpixel')
     SUPERPIXEL = int(argv[i + 1])
     del argv[i:i + 2]
+SLIC = False
+if '--segmentation' in argv:
+    i = argv.index('--segmentation')
+    SLIC = argv[i + 1] == 'slic'
+    del argv[i:i + 2]
 B = int(argv[0]) if argv else 16
 rng = np.random.default_rng(1000)
 img = torch.from_numpy((rng.integers(0, 256, (B, 480, 640, 3)) / 255).astype(np.float32)).cuda()
@@ -61,7 +71,10 @@ def conv_macs(h, w, rows):
     return total + rows * (first * 128 + 128 * 16 + 16)
 
 
-if SUPERPIXEL != 40:
+if SLIC:
+    rep = models.DCNFReplica(B, train_pairwise=PAIRWISE, pairwise_texture=TEXTURE, valid_range=(0.0, 0.99) if HOLES else None,
+                             unary=UNARY, superpixel=SUPERPIXEL, segmentation='slic')
+elif SUPERPIXEL != 40:
     rep = models.DCNFReplica(B, train_pairwise=PAIRWISE, pairwise_texture=TEXTURE, valid_range=(0.0, 0.99) if HOLES else None,
                              unary=UNARY, superpixel=SUPERPIXEL)
 elif UNARY != 'patch':
@@ -76,7 +89,7 @@ else:
 net = rep.unary
 dz = torch.randn((net.P, 1), device='cuda')
 # the objective of the untouched network, before the timed steps move it (at the reference's rate 0.1 they move it far)
-first_loss = float(rep.forward(img, dep)) if HOLES else None
+first_loss = float(rep.forward(img, dep)) if HOLES or SLIC else None      # slic: also leaves the labels the unary pools over
 
 
 def timeit(fn, reps=10):
@@ -124,6 +137,23 @@ if UNARY != 'patch':
              'patch_form_gflop_per_image': round(2e-9 * 48 * conv_macs(100, 100, 1), 3)}
 if band is not None:
     extra = {**extra, 'superpixel': SUPERPIXEL, 'band': band}
+if SLIC:
+    x, sp, last = net.resized, rep.sp, net.act['conv2d_4/pool']
+    pooled, dpooled = net.act['pooled'].view(B, rep.nsp, -1), torch.randn((B, rep.nsp, 256), device='cuda')
+    dflat = torch.empty_like(last)
+    slic = {'segment_ms': timeit(lambda: rep._segment(), reps=50),
+            'label_mean_target_ms': timeit(lambda: ops.label_mean(rep.depths240, sp, rep.labels, rep.y, rep.count3), reps=50),
+            'label_mean_image_ms': timeit(lambda: ops.label_mean(x, sp, rep.labels, rep.mean3, rep.count3), reps=50),
+            'label_hist_ms': timeit(lambda: ops.label_hist(x, sp, rep.labels, rep.hist), reps=50),
+            'pair_similarity_ms': timeit(lambda: ops.label_pair_similarity(rep.mean3, rep.hist, rep.label_count, rep.left,
+                                                                          rep.right, rep.pair_var('kernel'),
+                                                                          rep.pair_var('bias'), models.DCNF_GAMMA), reps=50),
+            'label_pool_fwd_ms': timeit(lambda: ops.label_pool_fwd(last, net.map, rep.labels, rep.label_count, pooled), reps=50),
+            'label_pool_bwd_ms': timeit(lambda: ops.label_pool_bwd(dpooled, net.map, rep.labels, rep.label_count, dflat), reps=50)}
+    grid_labels = (torch.arange(240, device='cuda')[:, None] // sp * rep.cols + torch.arange(320, device='cuda')[None, :] // sp)
+    extra = {**extra, 'superpixel': SUPERPIXEL, 'segmentation': 'slic', 'slic_iters': rep.slic_iters,
+             'slic_compactness': rep.slic_compactness, 'slic': {k: round(v, 4) for k, v in slic.items()},
+             'pixels_off_their_block': round(float((rep.labels != grid_labels.int()).float().mean()), 4)}
 if HOLES:
     torch.cuda.synchronize()
     nobs = rep.nobs.cpu().numpy()
