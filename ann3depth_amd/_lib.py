@@ -190,6 +190,18 @@ WINO_GRAD_SIGNATURES = {
     'a3dwg_conv2d_bwd_filter': (c_int, [_D, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
+class WinoBwdPool(ctypes.Structure):
+    """a3dwb_pool (include/a3d_wino_bwd.h): the 2x2 max pool below a layer, as the fused forward recorded it."""
+    _fields_ = [('argmax', c_void_p), ('y', c_void_p), ('ldy', c_int), ('h2', c_int), ('w2', c_int)]
+
+
+# name -> (restype, argtypes); every symbol include/a3d_wino_bwd.h declares (prefix a3dwb_)
+WINO_BWD_SIGNATURES = {
+    'a3dwb_sizeof_pool': (c_size_t, []),
+    'a3dwb_conv2d_bwd_ws_bytes': (c_size_t, [_D, c_int, c_int]),
+    'a3dwb_conv2d_bwd': (c_int, [_D, _P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(WinoBwdPool), _P, c_size_t, _P]),
+}
+
 # name -> (restype, argtypes); every symbol include/a3d_upsample.h declares (NON-REFERENCE extension, prefix a3du_)
 UPSAMPLE_SIGNATURES = {
     'a3du_joint_bilateral_upsample': (c_int, [c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, _P, _P, _P, _P, c_int, c_float,
@@ -233,7 +245,8 @@ def load():
                               + list(CRF_VALID_SIGNATURES.items()) + list(FCSP_SIGNATURES.items())
                               + list(CRF_BAND_SIGNATURES.items()) + list(WINO_SIGNATURES.items())
                               + list(UPSAMPLE_SIGNATURES.items()) + list(POSTERIOR_SIGNATURES.items())
-                              + list(WINO_GRAD_SIGNATURES.items()) + list(SLIC_SIGNATURES.items())):
+                              + list(WINO_GRAD_SIGNATURES.items()) + list(SLIC_SIGNATURES.items())
+                              + list(WINO_BWD_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -243,6 +256,9 @@ def load():
     if lib.a3d_sizeof_conv_desc() != ctypes.sizeof(ConvDesc):
         raise A3dError(f'liba3d.so reads a {lib.a3d_sizeof_conv_desc()}-byte a3d_conv_desc, this binding passes '
                        f'{ctypes.sizeof(ConvDesc)} bytes: stale build?')
+    if lib.a3dwb_sizeof_pool() != ctypes.sizeof(WinoBwdPool):
+        raise A3dError(f'liba3d.so reads a {lib.a3dwb_sizeof_pool()}-byte a3dwb_pool, this binding passes '
+                       f'{ctypes.sizeof(WinoBwdPool)} bytes: stale build?')
     _lib = lib
     return lib
 

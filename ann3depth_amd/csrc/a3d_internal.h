@@ -153,4 +153,18 @@ int wino_dw(const a3d_conv_desc* d, const WinoGradGeom& g, const float* slabs, c
 a3d_timing_record wino_grad_record(const a3d_conv_desc* d, const WinoGradGeom& g);
 int wino_grad_gemm(IgemmParams& p, const WinoGradGeom& g, hipStream_t st);      // p: one product, splits and tiles filled in here
 
+// ---- both gradients of a layer as one chain of three launches (include/a3d_wino_bwd.h; wino.hip) ----
+struct WinoBwdPool {                     // a3dwb_pool
+  const uint8_t* argmax;
+  const float* y;
+  int ldy, h2, w2;
+};
+// V_x (forward grid), V_dz (bwd-data's grid) and Z (forward grid) in one launch
+int wino_bwd_transforms(const a3d_conv_desc* d, const float* x, const float* dz, float* Vx, float* Vdz, float* Z, hipStream_t st);
+// wino_grad_gemm(pf, gg) and wino_gemm(pd, g) as one grid, the filter gradient's blocks first
+int wino_bwd_gemm(IgemmParams& pf, const WinoGradGeom& gg, IgemmParams& pd, const WinoGeom& g, hipStream_t st);
+// wino_dw and bwd-data's wino_output (no bias, no activation) in one launch; pool: the output scattered into the unpooled dx
+int wino_bwd_finish(const a3d_conv_desc* d, const WinoGradGeom& gg, const float* slabs, const float* bparts, float* dw, float* db,
+                    const float* M, float* dx, const float* mask, const WinoBwdPool* pool, hipStream_t st);
+
 }  // namespace a3d

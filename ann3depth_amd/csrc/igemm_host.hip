@@ -5,6 +5,7 @@
 
 #include "../../include/a3d_wino.h"
 #include "../../include/a3d_wino_grad.h"
+#include "../../include/a3d_wino_bwd.h"
 #include "a3d_internal.h"
 #include "igemm.h"
 #include "igemm_cfgs.h"
@@ -379,6 +380,20 @@ static size_t wino_bytes(const a3d_conv_desc* d, bool bwd, bool prepared) {
   const WinoGeom g = wino_geom(d, bwd);
   return (prepared ? 0 : g.u_bytes) + g.v_bytes + g.m_bytes;
 }
+// one of the sixteen products: T rows of Kp gathered channels (a 1x1 conv over T one-pixel images) against U[xi] [Kp][Np]
+static IgemmParams wino_product(const WinoGeom& g, const float* V, const float* U, float* M) {
+  a3d_conv_desc e{};
+  e.n = (int)g.T; e.h = e.w = e.ho = e.wo = 1; e.c = g.Kp; e.k = g.Np; e.r = e.s = 1; e.stride = 1; e.ldx = g.Kp; e.ldy = g.Np;
+  GemmProblem gp = fwd_problem(&e);
+  IgemmParams p;
+  fill_common(p, gp);
+  p.A = V; p.B = U; p.C = M;
+  p.npix = gp.M; p.nrsc = gp.K;
+  fill_gather(p, &e, g.Kp, 1, g.Kp);
+  p.ldb = g.Np; p.ldc = g.Np;
+  fill_staging(p, MODE_FWD, (unsigned long long)g.T * g.Kp, (unsigned long long)g.Kp * g.Np, 1, 1);
+  return p;
+}
 // forward (dz = x, dx = y, bias + act) or bwd-data (mask) of a descriptor wino_applicable() accepted; `w`: the filter, or its
 // transform when prepared
 static int wino_conv(const a3d_conv_desc* d, bool bwd, const float* src, const float* w, float* out, const float* bias, const float* mask,
@@ -400,17 +415,7 @@ static int wino_conv(const a3d_conv_desc* d, bool bwd, const float* src, const f
   float* M = reinterpret_cast<float*>(base + g.v_bytes);
   rc = wino_input(d, bwd, src, V, st);
   if (rc != A3D_OK) return rc;
-  // one product: T rows of Kp gathered channels (a 1x1 conv over T one-pixel images) against U[xi] [Kp][Np]
-  a3d_conv_desc e{};
-  e.n = (int)g.T; e.h = e.w = e.ho = e.wo = 1; e.c = g.Kp; e.k = g.Np; e.r = e.s = 1; e.stride = 1; e.ldx = g.Kp; e.ldy = g.Np;
-  GemmProblem gp = fwd_problem(&e);
-  IgemmParams p;
-  fill_common(p, gp);
-  p.A = V; p.B = U; p.C = M;
-  p.npix = gp.M; p.nrsc = gp.K;
-  fill_gather(p, &e, g.Kp, 1, g.Kp);
-  p.ldb = g.Np; p.ldc = g.Np;
-  fill_staging(p, MODE_FWD, (unsigned long long)g.T * g.Kp, (unsigned long long)g.Kp * g.Np, 1, 1);
+  IgemmParams p = wino_product(g, V, U, M);
   rc = timed_launch(wino_record(bwd ? MODE_BWD_D : MODE_FWD, g), st, [&] { return wino_gemm(p, g, st); });
   if (rc != A3D_OK) return rc;
   return wino_output(d, bwd, M, out, bias, mask, act, st);
@@ -927,6 +932,21 @@ int a3d_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* d
 // ---- include/a3d_wino_grad.h: the filter gradient through Winograd F(2x2,3x3); workspace [V][Z][slabs][bias partials] ----
 static bool wino_grad_takes(const a3d_conv_desc* d) { return check_desc(d) == A3D_OK && wino_grad_applicable(d); }
 
+// one of the sixteen sums over tiles: the filter gradient of a 1x1 conv over T one-pixel images of Cp channels, Kp filters
+static IgemmParams wino_grad_product(const WinoGradGeom& g, const float* V, const float* Z, float* slabs, float* bparts) {
+  a3d_conv_desc e{};
+  e.n = (int)g.T; e.h = e.w = e.ho = e.wo = 1; e.c = g.Cp; e.k = g.Kp; e.r = e.s = 1; e.stride = 1; e.ldx = g.Cp; e.ldy = g.Kp;
+  GemmProblem gp = bwd_f_problem(&e);
+  IgemmParams p;
+  fill_common(p, gp);
+  p.A = V; p.B = Z; p.C = slabs; p.dbias = bparts;
+  p.npix = gp.K; p.nrsc = gp.M;
+  fill_gather(p, &e, g.Cp, 1, g.Cp);
+  p.ldb = g.Kp; p.ldc = g.Kp;
+  fill_staging(p, MODE_BWD_F, (unsigned long long)g.T * g.Cp, (unsigned long long)g.T * g.Kp, 1, 1);
+  return p;
+}
+
 size_t a3dwg_conv2d_bwd_filter_ws_bytes(const a3d_conv_desc* d) {
   if (!wino_grad_takes(d)) return a3d_conv2d_bwd_filter_ws_bytes(d);
   const WinoGradGeom g = wino_grad_geom(d);
@@ -951,20 +971,91 @@ int a3dwg_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float*
   if (rc != A3D_OK) return rc;
   rc = wino_dz(d, dz, Z, st);
   if (rc != A3D_OK) return rc;
-  // one product: the filter gradient of a 1x1 conv over T one-pixel images of Cp channels, Kp filters
-  a3d_conv_desc e{};
-  e.n = (int)g.T; e.h = e.w = e.ho = e.wo = 1; e.c = g.Cp; e.k = g.Kp; e.r = e.s = 1; e.stride = 1; e.ldx = g.Cp; e.ldy = g.Kp;
-  GemmProblem gp = bwd_f_problem(&e);
-  IgemmParams p;
-  fill_common(p, gp);
-  p.A = V; p.B = Z; p.C = slabs; p.dbias = db ? bparts : nullptr;
-  p.npix = gp.K; p.nrsc = gp.M;
-  fill_gather(p, &e, g.Cp, 1, g.Cp);
-  p.ldb = g.Kp; p.ldc = g.Kp;
-  fill_staging(p, MODE_BWD_F, (unsigned long long)g.T * g.Cp, (unsigned long long)g.T * g.Kp, 1, 1);
+  IgemmParams p = wino_grad_product(g, V, Z, slabs, db ? bparts : nullptr);
   rc = timed_launch(wino_grad_record(d, g), st, [&] { return wino_grad_gemm(p, g, st); });
   if (rc != A3D_OK) return rc;
   return wino_dw(d, g, slabs, bparts, dw, db, st);
+}
+
+// ---- include/a3d_wino_bwd.h: both gradients as one chain; workspace [U unless prepared][V_dz][M][V_x][Z][slabs][bias partials] ----
+// Both routes take the descriptor, and the filter gradient's tile grid (over ho x wo) lies inside bwd-data's (over h x w), whose
+// items write Z
+static bool wino_bwd_takes(const a3d_conv_desc* d) {
+  if (!wino_grad_takes(d)) return false;
+  const WinoGeom gx = wino_geom(d, false), gd = wino_geom(d, true);
+  return gx.th <= gd.th && gx.tw <= gd.tw;
+}
+static a3d_conv_desc as_winograd(const a3d_conv_desc* d) {
+  a3d_conv_desc e = *d;
+  e.precision = A3D_PREC_F32_WINOGRAD;
+  return e;
+}
+
+size_t a3dwb_sizeof_pool(void) { return sizeof(a3dwb_pool); }
+
+size_t a3dwb_conv2d_bwd_ws_bytes(const a3d_conv_desc* d, int w_prepared, int pooled) {
+  (void)pooled;      // the pooled-size dx has no buffer
+  if (!wino_bwd_takes(d)) return std::max(a3dwg_conv2d_bwd_filter_ws_bytes(d), a3d_conv2d_bwd_data_ws_bytes(d));
+  const a3d_conv_desc e = as_winograd(d);
+  const WinoGradGeom g = wino_grad_geom(&e);
+  return wino_bytes(&e, true, w_prepared != 0) + g.v_bytes + g.z_bytes + g.slab_bytes + g.bias_bytes;
+}
+
+int a3dwb_conv2d_bwd(const a3d_conv_desc* d, const float* x, const float* dz, const float* w_or_U, float* dw, float* db, float* dx,
+                     const float* relu_mask, const a3dwb_pool* pool, void* ws, size_t ws_bytes, void* stream) {
+  static_assert(sizeof(WinoBwdPool) == sizeof(a3dwb_pool), "WinoBwdPool mirrors a3dwb_pool");
+  if (!wino_bwd_takes(d)) {
+    A3D_CHECK_ARG(!pool, "conv2d_bwd (Winograd): a pool only where the Winograd routes take the descriptor");
+    const int rc = a3dwg_conv2d_bwd_filter(d, x, dz, dw, db, ws, ws_bytes, stream);
+    return rc != A3D_OK ? rc : a3d_conv2d_bwd_data(d, dz, w_or_U, dx, relu_mask, ws, ws_bytes, stream);
+  }
+  A3D_CHECK_ARG(x && dz && w_or_U && dw && dx, "conv2d_bwd (Winograd): null tensor");
+  A3D_CHECK_WS(ws, "conv2d_bwd (Winograd)");
+  A3D_CHECK_ARG(!(pool && relu_mask), "conv2d_bwd (Winograd): relu_mask and pool exclude each other");
+  A3D_CHECK_ARG(!pool || (pool->argmax && pool->y && pool->ldy >= d->c && pool->h2 >= 2 && pool->w2 >= 2 && pool->h2 / 2 == d->h &&
+                          pool->w2 / 2 == d->w),
+                "conv2d_bwd (Winograd): the pool's halved extents must be the layer's input's");
+  const a3d_conv_desc e = as_winograd(d);
+  const bool prepared = (d->hints & A3D_HINT_W_PREPARED) != 0;
+  const WinoGeom g = wino_geom(&e, true);
+  const WinoGradGeom gg = wino_grad_geom(&e);
+  const size_t need = wino_bytes(&e, true, prepared) + gg.v_bytes + gg.z_bytes + gg.slab_bytes + gg.bias_bytes;
+  if (!ws || need > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd (Winograd): need %zu workspace bytes", need);
+  A3D_CHECK_ARG(!prepared || aligned16(w_or_U), "conv2d_bwd (Winograd): the prepared filter must be 16-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(ws);
+  const float* U = w_or_U;
+  int rc;
+  if (!prepared) {
+    rc = wino_filter(&e, true, w_or_U, reinterpret_cast<float*>(base), st);
+    if (rc != A3D_OK) return rc;
+    U = reinterpret_cast<const float*>(base);
+    base += g.u_bytes;
+  }
+  auto take = [&base](size_t bytes) {
+    float* p = reinterpret_cast<float*>(base);
+    base += bytes;
+    return p;
+  };
+  float *Vdz = take(g.v_bytes), *M = take(g.m_bytes);                                                        // bwd-data's
+  float *Vx = take(gg.v_bytes), *Z = take(gg.z_bytes), *slabs = take(gg.slab_bytes), *bparts = take(gg.bias_bytes);      // the filter gradient's
+  rc = wino_bwd_transforms(&e, x, dz, Vx, Vdz, Z, st);
+  if (rc != A3D_OK) return rc;
+  IgemmParams pf = wino_grad_product(gg, Vx, Z, slabs, db ? bparts : nullptr);
+  IgemmParams pd = wino_product(g, Vdz, U, M);
+  // a bracket measures one kernel: when either product's record is wanted the two run as the launches those records describe
+  const a3d_timing_record rf = wino_grad_record(&e, gg), rd = wino_record(MODE_BWD_D, g);
+  if (timing_wanted(rf) || timing_wanted(rd) || tune_int("A3D_WINO_BWD_PAIR", 1) == 0) {      // (A3D_TUNING=1: the A/B of the pairing)
+    rc = timed_launch(rf, st, [&] { return wino_grad_gemm(pf, gg, st); });
+    if (rc != A3D_OK) return rc;
+    rc = timed_launch(rd, st, [&] { return wino_gemm(pd, g, st); });
+  } else {
+    rc = wino_bwd_gemm(pf, gg, pd, g, st);
+  }
+  if (rc != A3D_OK) return rc;
+  WinoBwdPool wp{};
+  if (pool) wp = WinoBwdPool{pool->argmax, pool->y, pool->ldy, pool->h2, pool->w2};
+  return wino_bwd_finish(&e, gg, slabs, bparts, dw, db, M, dx, relu_mask, pool ? &wp : nullptr, st);
 }
 
 // ---- dense = 1x1 conv over a 1x1 image ----

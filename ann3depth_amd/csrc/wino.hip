@@ -5,6 +5,9 @@
 // Y = A^T M A with the epilogue (bias + activation, or the ReLU mask of bwd-data).  bwd-data is the same pipeline on dz with
 // padding 2 - pad and the filter's taps flipped and its channels swapped.  V, U and M are padded to whole 16-byte pieces of
 // channels (zeros), so the GEMM always gathers and stores vectors.  Every sum has a fixed order: no atomics.
+// Below them the filter gradient through the same identity (include/a3d_wino_grad.h) and, last, both gradients of a layer as one
+// chain of three launches (include/a3d_wino_bwd.h).  The per-item bodies are device functions, so that the chain's kernels run
+// the very statements of the kernels they merge.
 #include "a3d_internal.h"
 #include "igemm.h"
 #include "igemm_cfgs.h"
@@ -51,6 +54,51 @@ __global__ __launch_bounds__(256) void wino_filter_kernel(const float* w, float*
 
 // ---- input transform: x [n][h][w][ld] -> V [16][T][Cp]; one thread per (tile, 4 channels) ----
 // VEC: 16-byte loads (c % 4 == 0, ld % 4 == 0, x on the 16-byte grid); otherwise float by float, channels >= c zero
+
+// the 4x4 window of image `img` whose first pixel is (y0, x0), channels cq*4 .. cq*4+3; positions outside h x w read as zero
+template <bool VEC>
+__device__ __forceinline__ void wino_load_window(const float* __restrict__ x, f4 (&d)[4][4], size_t img, int y0, int x0, int h, int w, int c,
+                                                 int ld, int cq) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      f4 v = f4(0.f);
+      const int yy = y0 + a, xx = x0 + b;
+      if (yy >= 0 && yy < h && xx >= 0 && xx < w) {
+        const float* src = x + ((img * h + yy) * w + xx) * (size_t)ld + cq * 4;
+        if (VEC) {
+          v = *reinterpret_cast<const f4*>(src);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (cq * 4 + e < c) v[e] = src[e];
+        }
+      }
+      d[a][b] = v;
+    }
+}
+
+// B^T d B of one window into its sixteen planes of V
+__device__ __forceinline__ void wino_input_store(const f4 (&d)[4][4], float* __restrict__ V, size_t T, size_t t, int Cp, int cq) {
+  // B^T d: rows
+  f4 r[4][4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    r[0][b] = d[0][b] - d[2][b];
+    r[1][b] = d[1][b] + d[2][b];
+    r[2][b] = d[2][b] - d[1][b];
+    r[3][b] = d[1][b] - d[3][b];
+  }
+  // (B^T d) B: columns
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const f4 v[4] = {r[a][0] - r[a][2], r[a][1] + r[a][2], r[a][2] - r[a][1], r[a][1] - r[a][3]};
+#pragma unroll
+    for (int b = 0; b < 4; ++b) *reinterpret_cast<f4*>(V + ((size_t)(a * 4 + b) * T + t) * Cp + cq * 4) = v[b];
+  }
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict__ x, float* __restrict__ V, int h, int w, int c, int ld,
                                                          int th, int tw, int pad_t, int pad_l, int Cp, size_t T) {
@@ -61,48 +109,29 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict
     const size_t t = i / cqn;
     const int tj = (int)(t % tw), ti = (int)((t / tw) % th);
     const size_t img = t / ((size_t)tw * th);
-    const int y0 = 2 * ti - pad_t, x0 = 2 * tj - pad_l;
     f4 d[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        f4 v = f4(0.f);
-        const int yy = y0 + a, xx = x0 + b;
-        if (yy >= 0 && yy < h && xx >= 0 && xx < w) {
-          const float* src = x + ((img * h + yy) * w + xx) * (size_t)ld + cq * 4;
-          if (VEC) {
-            v = *reinterpret_cast<const f4*>(src);
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (cq * 4 + e < c) v[e] = src[e];
-          }
-        }
-        d[a][b] = v;
-      }
-    // B^T d: rows
-    f4 r[4][4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      r[0][b] = d[0][b] - d[2][b];
-      r[1][b] = d[1][b] + d[2][b];
-      r[2][b] = d[2][b] - d[1][b];
-      r[3][b] = d[1][b] - d[3][b];
-    }
-    // (B^T d) B: columns
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const f4 v[4] = {r[a][0] - r[a][2], r[a][1] + r[a][2], r[a][2] - r[a][1], r[a][1] - r[a][3]};
-#pragma unroll
-      for (int b = 0; b < 4; ++b) *reinterpret_cast<f4*>(V + ((size_t)(a * 4 + b) * T + t) * Cp + cq * 4) = v[b];
-    }
+    wino_load_window<VEC>(x, d, img, 2 * ti - pad_t, 2 * tj - pad_l, h, w, c, ld, cq);
+    wino_input_store(d, V, T, t, Cp, cq);
   }
 }
 
 // ---- output transform: M [16][T][Np] -> out [n][oh][ow][ld]; one thread per (tile, 4 columns) ----
 // Forward: + bias, activation.  bwd-data: *= (mask > 0), mask laid out as out.  Tile rows / columns beyond oh / ow and
 // columns >= ncols are never written.  VEC: 16-byte stores (ncols % 4 == 0, ld % 4 == 0, out and mask on the 16-byte grid).
+// A^T M of one tile's sixteen planes: the rows of the output transform
+__device__ __forceinline__ void wino_output_rows(const float* __restrict__ M, f4 (&r)[2][4], size_t T, size_t t, int Np, int cq) {
+  f4 m[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) m[a][b] = *reinterpret_cast<const f4*>(M + ((size_t)(a * 4 + b) * T + t) * Np + cq * 4);
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    r[0][b] = (m[0][b] + m[1][b]) + m[2][b];
+    r[1][b] = (m[1][b] - m[2][b]) - m[3][b];
+  }
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restrict__ M, float* __restrict__ out, const float* __restrict__ bias,
                                                           const float* __restrict__ mask, int act, int oh, int ow, int ncols, int ld,
@@ -114,17 +143,8 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restric
     const size_t t = i / cqn;
     const int tj = (int)(t % tw), ti = (int)((t / tw) % th);
     const size_t img = t / ((size_t)tw * th);
-    f4 m[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) m[a][b] = *reinterpret_cast<const f4*>(M + ((size_t)(a * 4 + b) * T + t) * Np + cq * 4);
     f4 r[2][4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      r[0][b] = (m[0][b] + m[1][b]) + m[2][b];
-      r[1][b] = (m[1][b] - m[2][b]) - m[3][b];
-    }
+    wino_output_rows(M, r, T, t, Np, cq);
     f4 bv = f4(0.f);
     if (bias) {
 #pragma unroll
@@ -239,6 +259,15 @@ a3d_timing_record wino_record(int mode, const WinoGeom& g) {
   return timing_record(mode, A3D_PREC_F32, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4, 0, (int)(16 * g.T), g.N, g.K);
 }
 
+// one product's tiles: no split
+static void wino_gemm_tiles(IgemmParams& p) {
+  p.splitk = 1;
+  p.ktiles_per_split = (p.K + kBK - 1) / kBK;
+  p.tiles_m = (p.M + kBM - 1) / kBM;
+  p.tiles_n = (p.N + kBN - 1) / kBN;
+  p.slab = (size_t)p.M * p.N;
+}
+
 int wino_gemm(IgemmParams& p, const WinoGeom& g, hipStream_t st) {
   using Cfg = IgemmCfg<MODE_FWD, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>;
   // the raised LDS limit is a per-DEVICE attribute of the kernel: one flag per device (a benign race at worst sets it twice)
@@ -251,11 +280,7 @@ int wino_gemm(IgemmParams& p, const WinoGeom& g, hipStream_t st) {
     if (e != hipSuccess) return set_error(A3D_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
     if (dev >= 0 && dev < 64) attr_done[dev] = true;
   }
-  p.splitk = 1;
-  p.ktiles_per_split = (p.K + kBK - 1) / kBK;
-  p.tiles_m = (p.M + kBM - 1) / kBM;
-  p.tiles_n = (p.N + kBN - 1) / kBN;
-  p.slab = (size_t)p.M * p.N;
+  wino_gemm_tiles(p);
   clear_stale_error();
   hipLaunchKernelGGL(wino_gemm_kernel, dim3((unsigned)(p.tiles_m * p.tiles_n), 16), dim3(Cfg::NT), Cfg::LDS_BYTES, st, p,
                      g.T * (size_t)g.Kp, (size_t)g.Kp * g.Np, g.T * (size_t)g.Np);
@@ -272,6 +297,21 @@ int wino_gemm(IgemmParams& p, const WinoGeom& g, hipStream_t st) {
 
 // ---- dz transform: dz [n][ho][wo][ld] -> Z [16][T][Kp]; one thread per (tile, 4 channels) ----
 // Positions beyond ho / wo read as zero; VEC as wino_input_kernel's, otherwise float by float with channels >= k zero
+
+// A dY A^T of one 2x2 tile into its sixteen planes of Z
+__device__ __forceinline__ void wino_dz_store(const f4 (&y)[2][2], float* __restrict__ Z, size_t T, size_t t, int Kp, int cq) {
+  // A dY: rows (A = [[1,0],[1,1],[1,-1],[0,-1]])
+  const f4 r[4][2] = {{y[0][0], y[0][1]}, {y[0][0] + y[1][0], y[0][1] + y[1][1]}, {y[0][0] - y[1][0], y[0][1] - y[1][1]},
+                      {-y[1][0], -y[1][1]}};
+  // (A dY) A^T: columns
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const f4 z[4] = {r[a][0], r[a][0] + r[a][1], r[a][0] - r[a][1], -r[a][1]};
+#pragma unroll
+    for (int b = 0; b < 4; ++b) *reinterpret_cast<f4*>(Z + ((size_t)(a * 4 + b) * T + t) * Kp + cq * 4) = z[b];
+  }
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(256) void wino_dz_kernel(const float* __restrict__ dz, float* __restrict__ Z, int ho, int wo, int k, int ld,
                                                       int th, int tw, int Kp, size_t T) {
@@ -301,63 +341,59 @@ __global__ __launch_bounds__(256) void wino_dz_kernel(const float* __restrict__ 
         }
         y[a][b] = v;
       }
-    // A dY: rows (A = [[1,0],[1,1],[1,-1],[0,-1]])
-    const f4 r[4][2] = {{y[0][0], y[0][1]}, {y[0][0] + y[1][0], y[0][1] + y[1][1]}, {y[0][0] - y[1][0], y[0][1] - y[1][1]},
-                        {-y[1][0], -y[1][1]}};
-    // (A dY) A^T: columns
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const f4 z[4] = {r[a][0], r[a][0] + r[a][1], r[a][0] - r[a][1], -r[a][1]};
-#pragma unroll
-      for (int b = 0; b < 4; ++b) *reinterpret_cast<f4*>(Z + ((size_t)(a * 4 + b) * T + t) * Kp + cq * 4) = z[b];
-    }
+    wino_dz_store(y, Z, T, t, Kp, cq);
   }
 }
 
 // ---- final transform: slabs [16][splits][Cp][Kp] -> dw [3][3][c][k] = G^T M G, M = the splits added in ascending order; one
 //      thread per (input channel, filter), which also adds the [splits][Kp] bias partials of its filter into db when it is the
 //      first channel's.  Columns >= k and rows >= c of the slabs are never read, nothing but dw and db is written ----
+__device__ __forceinline__ void wino_dw_item(size_t i, const float* __restrict__ slabs, const float* __restrict__ bparts, float* __restrict__ dw,
+                                             float* __restrict__ db, int c, int k, int Cp, int Kp, int splits) {
+  const size_t plane = (size_t)Cp * Kp;
+  const int col = (int)(i % k), row = (int)(i / k);
+  const size_t at = (size_t)row * Kp + col;
+  // split by split, the sixteen loads of a split in flight together: a thread's chain of 16 x splits dependent loads was
+  // the cost of this kernel (13.6 / 21.5 us for conv2d_3 / conv2d_2's 28 / 31 MB at 3 / 5 splits)
+  float m[4][4];
+#pragma unroll
+  for (int xi = 0; xi < 16; ++xi) m[xi / 4][xi % 4] = slabs[(size_t)xi * splits * plane + at];
+  for (int z = 1; z < splits; ++z) {
+    float v[16];
+#pragma unroll
+    for (int xi = 0; xi < 16; ++xi) v[xi] = slabs[((size_t)xi * splits + z) * plane + at];
+#pragma unroll
+    for (int xi = 0; xi < 16; ++xi) m[xi / 4][xi % 4] += v[xi];
+  }
+  // G^T M: rows (G^T = [[1,1/2,1/2,0],[0,1/2,-1/2,0],[0,1/2,1/2,1]])
+  float t[3][4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const float hs = (m[1][b] + m[2][b]) * 0.5f;
+    t[0][b] = m[0][b] + hs;
+    t[1][b] = (m[1][b] - m[2][b]) * 0.5f;
+    t[2][b] = hs + m[3][b];
+  }
+  // (G^T M) G: columns
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float hs = (t[a][1] + t[a][2]) * 0.5f;
+    const float g[3] = {t[a][0] + hs, (t[a][1] - t[a][2]) * 0.5f, hs + t[a][3]};
+#pragma unroll
+    for (int b = 0; b < 3; ++b) dw[((size_t)(a * 3 + b) * c + row) * k + col] = g[b];
+  }
+  if (db && row == 0) {
+    float s = bparts[col];
+    for (int z = 1; z < splits; ++z) s += bparts[(size_t)z * Kp + col];
+    db[col] = s;
+  }
+}
+
 __global__ __launch_bounds__(256) void wino_dw_kernel(const float* __restrict__ slabs, const float* __restrict__ bparts, float* __restrict__ dw,
                                                       float* __restrict__ db, int c, int k, int Cp, int Kp, int splits) {
-  const size_t total = (size_t)c * k, plane = (size_t)Cp * Kp;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int col = (int)(i % k), row = (int)(i / k);
-    const size_t at = (size_t)row * Kp + col;
-    // split by split, the sixteen loads of a split in flight together: a thread's chain of 16 x splits dependent loads was
-    // the cost of this kernel (13.6 / 21.5 us for conv2d_3 / conv2d_2's 28 / 31 MB at 3 / 5 splits)
-    float m[4][4];
-#pragma unroll
-    for (int xi = 0; xi < 16; ++xi) m[xi / 4][xi % 4] = slabs[(size_t)xi * splits * plane + at];
-    for (int z = 1; z < splits; ++z) {
-      float v[16];
-#pragma unroll
-      for (int xi = 0; xi < 16; ++xi) v[xi] = slabs[((size_t)xi * splits + z) * plane + at];
-#pragma unroll
-      for (int xi = 0; xi < 16; ++xi) m[xi / 4][xi % 4] += v[xi];
-    }
-    // G^T M: rows (G^T = [[1,1/2,1/2,0],[0,1/2,-1/2,0],[0,1/2,1/2,1]])
-    float t[3][4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const float hs = (m[1][b] + m[2][b]) * 0.5f;
-      t[0][b] = m[0][b] + hs;
-      t[1][b] = (m[1][b] - m[2][b]) * 0.5f;
-      t[2][b] = hs + m[3][b];
-    }
-    // (G^T M) G: columns
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float hs = (t[a][1] + t[a][2]) * 0.5f;
-      const float g[3] = {t[a][0] + hs, (t[a][1] - t[a][2]) * 0.5f, hs + t[a][3]};
-#pragma unroll
-      for (int b = 0; b < 3; ++b) dw[((size_t)(a * 3 + b) * c + row) * k + col] = g[b];
-    }
-    if (db && row == 0) {
-      float s = bparts[col];
-      for (int z = 1; z < splits; ++z) s += bparts[(size_t)z * Kp + col];
-      db[col] = s;
-    }
-  }
+  const size_t total = (size_t)c * k;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256)
+    wino_dw_item(i, slabs, bparts, dw, db, c, k, Cp, Kp, splits);
 }
 
 // ---- the sixteen sums over tiles: the bwd-filter body on problem blockIdx.y; the bias partials belong to plane (1,1) ----
@@ -439,6 +475,16 @@ a3d_timing_record wino_grad_record(const a3d_conv_desc* d, const WinoGradGeom& g
   return r;
 }
 
+// one product's tiles and the split of its T axis
+static void wino_grad_gemm_tiles(IgemmParams& p, const WinoGradGeom& g) {
+  const int nk = (p.K + kBK - 1) / kBK;
+  p.splitk = g.splits;
+  p.ktiles_per_split = (nk + g.splits - 1) / g.splits;
+  p.tiles_m = (p.M + kBM - 1) / kBM;
+  p.tiles_n = (p.N + kBN - 1) / kBN;
+  p.slab = (size_t)p.M * p.N;
+}
+
 int wino_grad_gemm(IgemmParams& p, const WinoGradGeom& g, hipStream_t st) {
   using Cfg = IgemmCfg<MODE_BWD_F, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>;
   static bool attr_done[64] = {};      // per device, as wino_gemm's
@@ -450,16 +496,259 @@ int wino_grad_gemm(IgemmParams& p, const WinoGradGeom& g, hipStream_t st) {
     if (e != hipSuccess) return set_error(A3D_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
     if (dev >= 0 && dev < 64) attr_done[dev] = true;
   }
-  const int nk = (p.K + kBK - 1) / kBK;
-  p.splitk = g.splits;
-  p.ktiles_per_split = (nk + g.splits - 1) / g.splits;
-  p.tiles_m = (p.M + kBM - 1) / kBM;
-  p.tiles_n = (p.N + kBN - 1) / kBN;
-  p.slab = (size_t)p.M * p.N;
+  wino_grad_gemm_tiles(p, g);
   clear_stale_error();
   hipLaunchKernelGGL(wino_grad_gemm_kernel, dim3((unsigned)(p.tiles_m * p.tiles_n * p.splitk), 16), dim3(Cfg::NT), Cfg::LDS_BYTES, st, p,
                      g.T * (size_t)g.Cp, g.T * (size_t)g.Kp, (size_t)g.splits * g.Cp * g.Kp);
   return check_launch("wino_grad_gemm");
+}
+
+// ==== both gradients of one layer as one chain (include/a3d_wino_bwd.h): the transforms, products and finishing transforms of
+//      the filter gradient above and of bwd-data, three launches in place of seven.  Every item runs the statements of the
+//      kernel it comes from (the helpers above), so dw, db and dx are the bits of the two routes run one after the other ====
+
+// ---- launch 1: V_x = B^T x B on the forward's tile grid; V_dz = B^T dz B on bwd-data's grid (padding 2 - pad) and, from the
+//      same sixteen loads, Z = A dY A^T of the 2x2 tile inside that window.  With pad 0 bwd-data's grid (over h x w) is larger
+//      than Z's (over ho x wo): the dz items walk the larger one and write Z where it has a tile ----
+struct WinoBwdXform {
+  const float *x, *dz;
+  float *Vx, *Vdz, *Z;
+  int h, w, c, ldx, xth, xtw, xpt, xpl, Cp;      // x [n][h][w][ldx], the forward's tiles (Z's too) and padding
+  int ho, wo, k, ldy, dth, dtw, dpt, dpl, Kp;    // dz [n][ho][wo][ldy], bwd-data's tiles and padding (1 or 2)
+  size_t Tx, Td, x_items;                        // tiles of the two grids; items [0, x_items) are x's
+};
+template <bool VEC>
+__global__ __launch_bounds__(256) void wino_bwd_transform_kernel(const WinoBwdXform q) {
+  const int cqx = q.Cp / 4, cqd = q.Kp / 4;
+  const size_t total = q.x_items + q.Td * (size_t)cqd;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    f4 d[4][4];
+    if (i < q.x_items) {
+      const int cq = (int)(i % cqx);
+      const size_t t = i / cqx;
+      const int tj = (int)(t % q.xtw), ti = (int)((t / q.xtw) % q.xth);
+      const size_t img = t / ((size_t)q.xtw * q.xth);
+      wino_load_window<VEC>(q.x, d, img, 2 * ti - q.xpt, 2 * tj - q.xpl, q.h, q.w, q.c, q.ldx, cq);
+      wino_input_store(d, q.Vx, q.Tx, t, q.Cp, cq);
+      continue;
+    }
+    const size_t j = i - q.x_items;
+    const int cq = (int)(j % cqd);
+    const size_t t = j / cqd;
+    const int tj = (int)(t % q.dtw), ti = (int)((t / q.dtw) % q.dth);
+    const size_t img = t / ((size_t)q.dtw * q.dth);
+    wino_load_window<VEC>(q.dz, d, img, 2 * ti - q.dpt, 2 * tj - q.dpl, q.ho, q.wo, q.k, q.ldy, cq);
+    wino_input_store(d, q.Vdz, q.Td, t, q.Kp, cq);
+    if (ti < q.xth && tj < q.xtw) {      // dz (2 ti + a, 2 tj + b) is window position (dpt + a, dpl + b)
+      f4 y[2][2];
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          const f4 lo = q.dpl == 1 ? d[1 + a][1 + b] : d[1 + a][2 + b], hi = q.dpl == 1 ? d[2 + a][1 + b] : d[2 + a][2 + b];
+          y[a][b] = q.dpt == 1 ? lo : hi;
+        }
+      wino_dz_store(y, q.Z, q.Tx, (img * q.xth + ti) * q.xtw + tj, q.Kp, cq);
+    }
+  }
+}
+
+int wino_bwd_transforms(const a3d_conv_desc* d, const float* x, const float* dz, float* Vx, float* Vdz, float* Z, hipStream_t st) {
+  const WinoGeom gx = wino_geom(d, false), gd = wino_geom(d, true);
+  WinoBwdXform q{};
+  q.x = x; q.dz = dz; q.Vx = Vx; q.Vdz = Vdz; q.Z = Z;
+  q.h = d->h; q.w = d->w; q.c = d->c; q.ldx = d->ldx; q.xth = gx.th; q.xtw = gx.tw; q.xpt = d->pad_t; q.xpl = d->pad_l; q.Cp = gx.Kp;
+  q.ho = d->ho; q.wo = d->wo; q.k = d->k; q.ldy = d->ldy; q.dth = gd.th; q.dtw = gd.tw; q.dpt = 2 - d->pad_t; q.dpl = 2 - d->pad_l;
+  q.Kp = gd.Kp;
+  q.Tx = gx.T; q.Td = gd.T; q.x_items = gx.T * (size_t)(gx.Kp / 4);
+  const bool vec = d->c % 4 == 0 && d->ldx % 4 == 0 && aligned16(x) && d->k % 4 == 0 && d->ldy % 4 == 0 && aligned16(dz);
+  const dim3 grid(grid_for(q.x_items + gd.T * (size_t)(gd.Kp / 4), 256, 1u << 20)), block(256);
+  clear_stale_error();
+  if (vec) hipLaunchKernelGGL(wino_bwd_transform_kernel<true>, grid, block, 0, st, q);
+  else hipLaunchKernelGGL(wino_bwd_transform_kernel<false>, grid, block, 0, st, q);
+  return check_launch("wino_bwd_transform");
+}
+
+// ---- launch 2: the two sets of sixteen products in one grid.  Blocks [0, 16 gf) are the filter gradient's (the longer K loop
+//      first), the rest bwd-data's; within a set the block order is that of the set's own launch (plane-major), and a block runs
+//      the body of that launch on the same parameters: same tiles, same splits, same sums ----
+struct WinoBatch {
+  size_t a, b, c;      // elements between two planes of the three operands
+};
+__global__ __launch_bounds__(64 * kNWaves, 2 * kNWaves / 4) void wino_bwd_gemm_kernel(const IgemmParams pf, const WinoBatch bf, const uint32_t gf,
+                                                                                       const IgemmParams pd, const WinoBatch bd, const uint32_t gd) {
+  if (blockIdx.x < 16 * gf) {
+    const uint32_t xi = blockIdx.x / gf;
+    IgemmParams q = pf;
+    q.A = pf.A + (size_t)xi * bf.a;
+    q.B = pf.B + (size_t)xi * bf.b;
+    q.C = pf.C + (size_t)xi * bf.c;
+    if (xi != kBiasPlane) q.dbias = nullptr;
+    igemm_body<MODE_BWD_F, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>(q, gf, blockIdx.x - xi * gf);
+  } else {
+    const uint32_t id = blockIdx.x - 16 * gf, xi = id / gd;
+    IgemmParams q = pd;
+    q.A = pd.A + (size_t)xi * bd.a;
+    q.B = pd.B + (size_t)xi * bd.b;
+    q.C = pd.C + (size_t)xi * bd.c;
+    igemm_body<MODE_FWD, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>(q, gd, id - xi * gd);
+  }
+}
+
+int wino_bwd_gemm(IgemmParams& pf, const WinoGradGeom& gg, IgemmParams& pd, const WinoGeom& g, hipStream_t st) {
+  constexpr size_t kLds = std::max(IgemmCfg<MODE_BWD_F, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>::LDS_BYTES,
+                                   IgemmCfg<MODE_FWD, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>::LDS_BYTES);
+  static bool attr_done[64] = {};      // per device, as wino_gemm's
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino_bwd_gemm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds);
+    if (e != hipSuccess) return set_error(A3D_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+    if (dev >= 0 && dev < 64) attr_done[dev] = true;
+  }
+  wino_grad_gemm_tiles(pf, gg);
+  wino_gemm_tiles(pd);
+  const uint32_t gf = (uint32_t)(pf.tiles_m * pf.tiles_n * pf.splitk), gd = (uint32_t)(pd.tiles_m * pd.tiles_n);
+  const WinoBatch bf{gg.T * (size_t)gg.Cp, gg.T * (size_t)gg.Kp, (size_t)gg.splits * gg.Cp * gg.Kp};
+  const WinoBatch bd{g.T * (size_t)g.Kp, (size_t)g.Kp * g.Np, g.T * (size_t)g.Np};
+  clear_stale_error();
+  hipLaunchKernelGGL(wino_bwd_gemm_kernel, dim3(16 * (gf + gd)), dim3(64 * kNWaves), kLds, st, pf, bf, gf, pd, bd, gd);
+  return check_launch("wino_bwd_gemm");
+}
+
+// ---- launch 3: wino_dw_kernel's items (the splits added in ascending order, G^T . G, db), then the output transform's:
+//      A^T M A, times (mask > 0) — or, POOL, scattered through a 2x2 max pool's recorded positions into the unpooled gradient
+//      [n][h2][w2][ncols]: what a3d_maxpool2x2_bwd_idx(relu_mask = 1) writes from the pooled-size dx, which is never stored,
+//      the zero last row / column of odd extents included ----
+struct WinoBwdFinish {
+  const float *slabs, *bparts;
+  float *dw, *db;
+  int c, k, Cp, Kp, splits;                                    // wino_dw_item's
+  const float* M;
+  float* dx;
+  const float* mask;
+  int oh, ow, ncols, ld, th, tw, Np;                           // bwd-data's output transform
+  size_t T, dw_items;                                          // items [0, dw_items) are dw's
+  const uint8_t* argmax;                                       // POOL: positions [n][oh][ow][ncols], pooled values y with
+  const float* py;                                             // pixel stride pldy, unpooled extents h2 x w2
+  int pldy, h2, w2;
+};
+template <bool VEC, bool POOL>
+__global__ __launch_bounds__(256) void wino_bwd_finish_kernel(const WinoBwdFinish q) {
+  const int cqn = q.Np / 4;
+  const size_t total = q.dw_items + q.T * (size_t)cqn;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    if (i < q.dw_items) {
+      wino_dw_item(i, q.slabs, q.bparts, q.dw, q.db, q.c, q.k, q.Cp, q.Kp, q.splits);
+      continue;
+    }
+    const size_t j = i - q.dw_items;
+    const int cq = (int)(j % cqn);
+    const size_t t = j / cqn;
+    const int tj = (int)(t % q.tw), ti = (int)((t / q.tw) % q.th);
+    const size_t img = t / ((size_t)q.tw * q.th);
+    f4 r[2][4];
+    wino_output_rows(q.M, r, q.T, t, q.Np, cq);
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const f4 y2[2] = {(r[a][0] + r[a][1]) + r[a][2], (r[a][1] - r[a][2]) - r[a][3]};
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int oy = 2 * ti + a, ox = 2 * tj + b;
+        if (oy >= q.oh || ox >= q.ow) continue;
+        const f4 v = y2[b] + f4(0.f);      // wino_output_kernel's "+ bias" without one (-0 becomes +0 there too)
+        const size_t win = (img * q.oh + oy) * q.ow + ox;
+        if (!POOL) {
+          const size_t o = win * (size_t)q.ld + cq * 4;
+          if (VEC) {
+            f4 u = v;
+            if (q.mask) {
+              const f4 y = *reinterpret_cast<const f4*>(q.mask + o);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) u[e] = apply_act_grad(v[e], y[e], EPI_RELU, 1.f);
+            }
+            *reinterpret_cast<f4*>(q.dx + o) = u;
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              if (cq * 4 + e < q.ncols) q.dx[o + e] = q.mask ? apply_act_grad(v[e], q.mask[o + e], EPI_RELU, 1.f) : v[e];
+          }
+          continue;
+        }
+        // the pool's window of pooled pixel (oy, ox): rows 2 oy, 2 oy + 1, columns 2 ox, 2 ox + 1 of dx; an odd extent's last
+        // row / column, which the pool dropped, is zeroed by the last pooled row / column's items
+        const size_t px = (size_t)q.ncols, row = (size_t)q.w2 * px;
+        const size_t base = ((img * q.h2 + 2 * oy) * q.w2 + 2 * ox) * px + cq * 4;
+        const bool cut_r = oy == q.oh - 1 && (q.h2 & 1), cut_c = ox == q.ow - 1 && (q.w2 & 1);
+        if (VEC) {
+          const uint32_t a4 = *reinterpret_cast<const uint32_t*>(q.argmax + win * px + cq * 4);
+          const f4 y4 = *reinterpret_cast<const f4*>(q.py + win * (size_t)q.pldy + cq * 4);
+          const f4 zero = f4(0.f);
+          f4 o[4] = {zero, zero, zero, zero};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const uint32_t arg = (a4 >> (8 * e)) & 0xffu;
+            const float g = !(y4[e] > 0.f) ? 0.f : v[e];
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) o[kk][e] = arg == (uint32_t)kk ? g : 0.f;
+          }
+          *reinterpret_cast<f4*>(q.dx + base) = o[0];
+          *reinterpret_cast<f4*>(q.dx + base + px) = o[1];
+          *reinterpret_cast<f4*>(q.dx + base + row) = o[2];
+          *reinterpret_cast<f4*>(q.dx + base + row + px) = o[3];
+          if (cut_c) {
+            *reinterpret_cast<f4*>(q.dx + base + 2 * px) = zero;
+            *reinterpret_cast<f4*>(q.dx + base + row + 2 * px) = zero;
+          }
+          if (cut_r) {
+            *reinterpret_cast<f4*>(q.dx + base + 2 * row) = zero;
+            *reinterpret_cast<f4*>(q.dx + base + 2 * row + px) = zero;
+            if (cut_c) *reinterpret_cast<f4*>(q.dx + base + 2 * row + 2 * px) = zero;
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if (cq * 4 + e >= q.ncols) continue;
+            const int arg = q.argmax[win * px + cq * 4 + e];
+            const float g = !(q.py[win * (size_t)q.pldy + cq * 4 + e] > 0.f) ? 0.f : v[e];
+            float* dst = q.dx + base + e;
+            dst[0] = arg == 0 ? g : 0.f;
+            dst[px] = arg == 1 ? g : 0.f;
+            dst[row] = arg == 2 ? g : 0.f;
+            dst[row + px] = arg == 3 ? g : 0.f;
+            if (cut_c) dst[2 * px] = dst[row + 2 * px] = 0.f;
+            if (cut_r) {
+              dst[2 * row] = dst[2 * row + px] = 0.f;
+              if (cut_c) dst[2 * row + 2 * px] = 0.f;
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
+int wino_bwd_finish(const a3d_conv_desc* d, const WinoGradGeom& gg, const float* slabs, const float* bparts, float* dw, float* db,
+                    const float* M, float* dx, const float* mask, const WinoBwdPool* pool, hipStream_t st) {
+  const WinoGeom g = wino_geom(d, true);
+  WinoBwdFinish q{};
+  q.slabs = slabs; q.bparts = bparts; q.dw = dw; q.db = db; q.c = d->c; q.k = d->k; q.Cp = gg.Cp; q.Kp = gg.Kp; q.splits = gg.splits;
+  q.M = M; q.dx = dx; q.mask = mask; q.oh = g.oh; q.ow = g.ow; q.ncols = g.N; q.ld = d->ldx; q.th = g.th; q.tw = g.tw; q.Np = g.Np;
+  q.T = g.T; q.dw_items = (size_t)d->c * d->k;
+  bool vec = g.N % 4 == 0 && aligned16(dx);
+  if (pool) {
+    q.argmax = pool->argmax; q.py = pool->y; q.pldy = pool->ldy; q.h2 = pool->h2; q.w2 = pool->w2;
+    vec = vec && pool->ldy % 4 == 0 && aligned16(pool->y) && (reinterpret_cast<uintptr_t>(pool->argmax) & 3) == 0;
+  } else {
+    vec = vec && d->ldx % 4 == 0 && aligned16(mask);
+  }
+  const dim3 grid(grid_for(q.dw_items + g.T * (size_t)(g.Np / 4), 256, 1u << 20)), block(256);
+  clear_stale_error();
+  if (pool && vec) hipLaunchKernelGGL((wino_bwd_finish_kernel<true, true>), grid, block, 0, st, q);
+  else if (pool) hipLaunchKernelGGL((wino_bwd_finish_kernel<false, true>), grid, block, 0, st, q);
+  else if (vec) hipLaunchKernelGGL((wino_bwd_finish_kernel<true, false>), grid, block, 0, st, q);
+  else hipLaunchKernelGGL((wino_bwd_finish_kernel<false, false>), grid, block, 0, st, q);
+  return check_launch("wino_bwd_finish");
 }
 
 }  // namespace a3d

@@ -446,6 +446,9 @@ class MSDNReplica(Replica):
     # slot: nothing but CoarseConv's m moves, by 3.8e-7 rel-L2 (profiles/wino_grad_outputs_vs_parent.txt).
     WINO_GRAD_LAYERS = WINO_LAYERS
     WINO_GRAD_MIN_TILES = 504
+    # Where both routes are on, the layer's two gradients run as one chain of three launches (include/a3d_wino_bwd.h) with the
+    # bits of the separate calls; conv2d_2's also carries conv2d_1's pool gradient.  False: the separate calls (the tests' yardstick).
+    WINO_BWD_CHAIN = True
 
     def _desc(self, name, which):
         """The layer's conv descriptor for 'fwd' | 'bwd_d' | 'bwd_f', with that call's storage bits."""
@@ -949,6 +952,14 @@ class MSDNReplica(Replica):
             d, w = self._prepared((name, 'bwd_d', 'fp32w'), self.d_wino[name], w, 'bwd_d')
         ops.conv2d_bwd_data(d, dz, w, dx, relu_mask=relu_mask)
 
+    def _wino_chain(self, name):
+        """Both Winograd routes are on for the layer: its two gradients run as one chain (ops.conv2d_bwd_wino)."""
+        return self.WINO_BWD_CHAIN and name in self.d_wino and name in self.wino_grad
+
+    def _bwd_wino(self, name, x, dz, dx, relu_mask=None, pool=None):
+        d, w = self._prepared((name, 'bwd_d', 'fp32w'), self.d_wino[name], self._w(name, 'bwd_d'), 'bwd_d')
+        ops.conv2d_bwd_wino(d, x, dz, w, self._g(name + '/kernel'), self._g(name + '/bias'), dx, relu_mask=relu_mask, pool=pool)
+
     def _bwd_filter(self, name, x, dz):
         if name in self.d:
             call = ops.conv2d_bwd_filter_wino if name in self.wino_grad else ops.conv2d_bwd_filter
@@ -1008,19 +1019,31 @@ class MSDNReplica(Replica):
         # (measured, round 3: the filter-gradient GEMMs on the side stream beside the bwd-data chain — to fill its tails and
         # launch gaps — make the step 2 % SLOWER, 3.20 vs 3.14 ms: two MFMA-bound grids only take CU slots from each other)
         dw = self._bwd_filter
-        n = 'coarse/conv/conv2d_3'
-        dw(n, self.c2, self.dc3)
-        self._bwd_data(n, self.dc3, self.dc2, relu_mask=self.c2)
-        n = 'coarse/conv/conv2d_2'
-        dw(n, self.p1, self.dc2)
-        if after_conv2 is not None:
-            after_conv2()          # gradients of conv2d_2..4 (the tail of the CoarseConv buffer) are complete
-        self._bwd_data(n, self.dc2, self.dp1)
         pooled = self.pooled_fwd == 1 or self.bf16s         # the forward recorded a0 / a1 instead of writing c0 / c1
-        if pooled:
-            ops.maxpool2x2_bwd_idx(self.a1, self.p1, self.dp1, self.dc1, relu_mask=True)
+        n = 'coarse/conv/conv2d_3'
+        if self._wino_chain(n):
+            self._bwd_wino(n, self.c2, self.dc3, self.dc2, relu_mask=self.c2)
         else:
-            ops.maxpool2x2_bwd(self.c1, self.dp1, self.dc1, relu_mask=True)
+            dw(n, self.c2, self.dc3)
+            self._bwd_data(n, self.dc3, self.dc2, relu_mask=self.c2)
+        n = 'coarse/conv/conv2d_2'
+        if self._wino_chain(n):
+            # one chain: dw, db and — where the fused forward recorded a1 — dc1 itself, the pool's gradient scattered by the
+            # output transform (dp1 is never written).  after_conv2 fires one product launch later than on the separate calls
+            self._bwd_wino(n, self.p1, self.dc2, self.dc1 if pooled else self.dp1, pool=(self.a1, self.p1) if pooled else None)
+            if after_conv2 is not None:
+                after_conv2()
+            if not pooled:
+                ops.maxpool2x2_bwd(self.c1, self.dp1, self.dc1, relu_mask=True)
+        else:
+            dw(n, self.p1, self.dc2)
+            if after_conv2 is not None:
+                after_conv2()          # gradients of conv2d_2..4 (the tail of the CoarseConv buffer) are complete
+            self._bwd_data(n, self.dc2, self.dp1)
+            if pooled:
+                ops.maxpool2x2_bwd_idx(self.a1, self.p1, self.dp1, self.dc1, relu_mask=True)
+            else:
+                ops.maxpool2x2_bwd(self.c1, self.dp1, self.dc1, relu_mask=True)
         n = 'coarse/conv/conv2d_1'
         dw(n, self.p0, self.dc1)
         self._bwd_data(n, self.dc1, self.dp0)

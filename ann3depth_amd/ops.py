@@ -200,6 +200,24 @@ def conv2d_bwd_filter_wino(d, x, dz, dw, db=None):
     return dw, db
 
 
+def conv2d_bwd_wino(d, x, dz, w, dw, db, dx, relu_mask=None, pool=None):
+    """Filter, bias and input gradient of a stride-1 3x3 layer of float32 tensors through Winograd F(2x2,3x3) as one chain of
+    three launches (include/a3d_wino_bwd.h): the bits of conv2d_bwd_filter_wino followed by conv2d_bwd_data under 'fp32w'.
+    w: the filter, or its prepared bwd-data transform when d.hints says so.  pool = (argmax, y_pooled): dx is then the UNPOOLED
+    gradient [n, h2, w2, c], what maxpool2x2_bwd_idx(relu_mask=True) writes from the layer's own dx.  For any other descriptor the
+    library runs the two calls."""
+    lib = _lib.load()
+    prepared = int(bool(d.hints & HINT_W_PREPARED))
+    ws, n = _ws().get(lib.a3dwb_conv2d_bwd_ws_bytes(ctypes.byref(d), prepared, int(pool is not None)), x.device)
+    pp = None
+    if pool is not None:
+        argmax, y = pool
+        pp = ctypes.byref(_lib.WinoBwdPool(_ptr(argmax), _ptr(y), y.shape[-1], dx.shape[1], dx.shape[2]))
+    check(lib.a3dwb_conv2d_bwd(ctypes.byref(d), _ptr(x), _ptr(dz), _ptr(w), _ptr(dw), _ptr(db), _ptr(dx), _ptr(relu_mask), pp,
+                               ws, n, _stream()), 'a3dwb_conv2d_bwd')
+    return dw, db, dx
+
+
 def conv2d_bwd_filter_pooled_supported(d):
     return _lib.load().a3d_conv2d_bwd_filter_pooled_ws_bytes(ctypes.byref(d)) > 0
 
