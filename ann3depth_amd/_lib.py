@@ -160,6 +160,12 @@ GRADLOSS_SIGNATURES = {
     'a3dg_silog_grad_loss_bwd_ex': (c_int, [c_int, c_int, c_int, _P, _P, c_int, c_float, _P, _P, _P, c_int, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_berhu.h declares (NON-REFERENCE extension, prefix a3dh_)
+BERHU_SIGNATURES = {
+    'a3dh_berhu_loss_fwd': (c_int, [c_int, c_int, _P, _P, c_int, c_float, _P, _P, _P]),
+    'a3dh_berhu_loss_bwd_ex': (c_int, [c_int, c_int, _P, _P, c_int, c_float, _P, _P, _P, c_int, _P]),
+}
+
 # name -> (restype, argtypes); every symbol include/a3d_crf_valid.h declares (NON-REFERENCE extension, prefix a3dv_)
 CRF_VALID_SIGNATURES = {
     'a3dv_superpixel_mean_valid': (c_int, [c_int, c_int, c_int, _P, c_int, c_int, _P, _P, _P]),
@@ -246,7 +252,7 @@ def load():
                               + list(CRF_BAND_SIGNATURES.items()) + list(WINO_SIGNATURES.items())
                               + list(UPSAMPLE_SIGNATURES.items()) + list(POSTERIOR_SIGNATURES.items())
                               + list(WINO_GRAD_SIGNATURES.items()) + list(SLIC_SIGNATURES.items())
-                              + list(WINO_BWD_SIGNATURES.items())):
+                              + list(WINO_BWD_SIGNATURES.items()) + list(BERHU_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

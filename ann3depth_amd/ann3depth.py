@@ -10,6 +10,7 @@ replaced by synchronous RCCL data parallelism: launch one process per GPU with
 accepted and ignored.
 
 Flags that are not the reference's: --beta2, --precision, --augment, --min-depth / --max-depth, --loss-gradient,
+--loss {silog,berhu}, --berhu-fraction,
 --train-pairwise, --pairwise-texture, --superpixel {40,20,10}, --unary {patch,fcsp} (dcnf: the unary part over 48 patches per image, the
 reference's, or once over the whole image with superpixel pooling before the dense head), --seed, --tf-checkpoints,
 --trace-every, --profiler.
@@ -104,6 +105,20 @@ def main(argv=None):
     if args.loss_gradient is not None and not args.loss_gradient >= 0:
         logger.error(f'--loss-gradient {args.loss_gradient}: the weight is a number >= 0.')
         return 2
+    if args.loss == 'berhu' and args.model != 'msdn':
+        logger.error(f'--loss berhu is the reverse Huber loss on the linear depths of --model msdn: {args.model or "(no model)"} '
+                     f'has no loss over a pixel grid (dcnf regresses superpixel means through a likelihood).')
+        return 2
+    if args.loss == 'berhu' and args.loss_gradient is not None:
+        logger.error('--loss berhu cannot go with --loss-gradient: the gradient-matching term is defined on differences of log '
+                     'depth and belongs to --loss silog.')
+        return 2
+    if args.berhu_fraction is not None and args.loss != 'berhu':
+        logger.error('--berhu-fraction sets the threshold of --loss berhu; --loss silog has none.')
+        return 2
+    if args.berhu_fraction is not None and not 0 < args.berhu_fraction <= 1:
+        logger.error(f'--berhu-fraction {args.berhu_fraction}: the threshold is a fraction in (0, 1] of the largest error.')
+        return 2
     if args.min_depth is not None or args.max_depth is not None:
         lo = 0. if args.min_depth is None else args.min_depth
         hi = float('inf') if args.max_depth is None else args.max_depth
@@ -169,6 +184,9 @@ def setup_model(args, rank=0, world=1):
                                  float('inf') if args.max_depth is None else args.max_depth)
     if hasattr(model, 'grad_weight'):                                    # main() has refused the models that have none
         model.grad_weight = float(args.loss_gradient or 0.0)
+    if hasattr(model, 'objective'):                                      # main() has refused the models that have none
+        model.objective = args.loss
+        model.berhu_fraction = 0.2 if args.berhu_fraction is None else float(args.berhu_fraction)
     if hasattr(model, 'train_pairwise'):                                 # main() has refused the models that have none
         model.train_pairwise = bool(args.train_pairwise)
     if hasattr(model, 'pairwise_texture'):
@@ -477,6 +495,14 @@ def parse_args(argv=None):
                              'losses (msdn only): the squared horizontal and vertical differences of the log-depth error over '
                              'the 55 x 74 grid, over the pairs of valid pixels under --min-depth / --max-depth. W >= 0; 0 is '
                              'the run without the flag.')
+    parser.add_argument('--loss', default='silog', choices=['silog', 'berhu'],
+                        help='NON-REFERENCE unless silog: the objective of both losses (msdn only). silog: the reference\'s '
+                             'scale-invariant log loss, under which an output at or below zero gets no gradient. berhu: the reverse '
+                             'Huber loss of Laina et al. 2016 on linear depth, L1 up to a threshold and quadratic beyond it, over '
+                             'the valid pixels under --min-depth / --max-depth; not with --loss-gradient.')
+    parser.add_argument('--berhu-fraction', default=None, type=float, metavar='F',
+                        help='NON-REFERENCE, --loss berhu: the threshold is F times the largest error of each sample (per sample, '
+                             'not per batch, so that a sample\'s gradient does not depend on its batch). 0 < F <= 1, default 0.2.')
     parser.add_argument('--train-pairwise', action='store_true',
                         help='NON-REFERENCE: learn the pairwise dense layer of the CRF (dcnf only). The reference leaves it at '
                              'its initial draw (TF 1.3 has no gradient for scatter_nd_update); with this flag the loss is also '

@@ -37,6 +37,12 @@ it.  ``unary`` and ``crf`` are painted onto 240 x 320 by the labels (DCNFReplica
 them, and the report gains ``segmentation``, ``slic_iters``, ``slic_compactness``.  Refused with it, before any GPU work:
 ``--upsample joint``, ``--observed-nll``, ``--condition``.  Without the flag (``grid``) nothing differs.
 
+``--loss berhu [--berhu-fraction F]`` (NON-REFERENCE, msdn; the training driver's two flags, not listed by ``--help``;
+include/a3d_berhu.h) adds ``berhu`` beside ``silog`` to ``coarse`` and ``fine``: the plain reverse Huber loss on the grid
+targets with the threshold F (default 0.2, 0 < F <= 1) times each image's largest error, averaged the way ``silog`` is, and the
+report gains ``loss`` and ``berhu_fraction``.  Checkpoints do not record the objective: any MSDN checkpoint can be asked.
+Without the flag nothing more is launched and the report has no new key.
+
 Output: one JSON line on stdout, ``<ckptdir>/<model>_<id>/eval-<global_step>.json`` and TensorBoard scalars
 ``eval/<output>/<metric>`` (and ``eval/crf_nll``) at the checkpoint's global step.  Exit code 2 when there is nothing to
 evaluate (no checkpoint, no test split) or the request is unsupported (an unknown model, more than one process).
@@ -112,9 +118,11 @@ class Evaluator(MetricRows):
     outputs = OUTPUTS['msdn']
 
     def __init__(self, replica, resolution='grid', min_depth=0., max_depth=float('inf'), clamp_lo=1e-3,
-                 clamp_hi=float('inf'), keep_predictions=False, upsample=None):
+                 clamp_hi=float('inf'), keep_predictions=False, upsample=None, berhu_fraction=None):
         """upsample (NON-REFERENCE, --upsample joint): an ops.JointUpsampler; a third output `fine_joint`, the fine map
-        brought to the record image's size under the batch's images, is judged against the same target."""
+        brought to the record image's size under the batch's images, is judged against the same target.
+        berhu_fraction (NON-REFERENCE, --loss berhu): also report `berhu`, the plain reverse Huber loss on the grid targets
+        with this threshold fraction, beside `silog`."""
         from .models import OUT_H, OUT_W
         super().__init__(replica, resolution, ('fine_joint',) if upsample is not None else (), (OUT_H, OUT_W), min_depth,
                          max_depth, clamp_lo, clamp_hi, keep_predictions)
@@ -122,6 +130,10 @@ class Evaluator(MetricRows):
         self.t = torch.empty((replica.B, OUT_H, OUT_W), device=replica.device)
         self.silog_ws = {}              # per batch size (a3d_silog_loss_fwd's per-sample sums and partials)
         self.losses = {o: [] for o in OUTPUTS['msdn']}
+        self.berhu_fraction = berhu_fraction
+        if berhu_fraction is not None:
+            self.berhu_ws = {}          # per batch size, as silog_ws
+            self.berhu = {o: [] for o in OUTPUTS['msdn']}
 
     def __call__(self, images, depths, n):
         coarse, fine = self.rep.predict(images, n)
@@ -135,6 +147,13 @@ class Evaluator(MetricRows):
                 ws = self.silog_ws[n] = ops.silog_ws(n, out.device)
             ops.silog_loss_fwd(out[:n], self.t[:n], loss, ws)                    # the mean over these n images
             self.losses[name].append(loss)
+            if self.berhu_fraction is not None:
+                quad = torch.empty(4, device=out.device)
+                ws = self.berhu_ws.get(n)
+                if ws is None:
+                    ws = self.berhu_ws[n] = ops.berhu_ws(n, out.device)
+                ops.berhu_loss_fwd(out[:n], self.t[:n], 0, self.berhu_fraction, quad, ws)
+                self.berhu[name].append(quad[:1])
         if self.upsample is not None:
             self.judge('fine_joint', self.upsample(fine[:n], images[:n]), n, target)
         self.counts.append(n)
@@ -145,6 +164,8 @@ class Evaluator(MetricRows):
         out = super().results()
         for name, losses in self.losses.items():
             out[name]['silog'] = self.mean(losses)
+            if self.berhu_fraction is not None:
+                out[name]['berhu'] = self.mean(self.berhu[name])
         return out
 
 
@@ -360,6 +381,13 @@ def main(argv=None):
     if refuse_under_slic(args, _say, (('--upsample joint', args.upsample == 'joint'), ('--observed-nll', args.observed_nll),
                                       ('--condition', args.condition is not None))):
         return 2
+    if (args.loss == 'berhu' or args.berhu_fraction is not None) and args.model != 'msdn':
+        _say(f'--loss berhu reports the reverse Huber loss of the two outputs of --model msdn: {args.model} has no loss over a '
+             f'pixel grid.')
+        return 2
+    if args.berhu_fraction is not None and (args.loss != 'berhu' or not 0 < args.berhu_fraction <= 1):
+        _say(f'--berhu-fraction {args.berhu_fraction} sets the threshold of --loss berhu, a fraction in (0, 1] of the largest error.')
+        return 2
     if args.condition is not None:
         if args.model != 'dcnf':
             _say('--condition hides superpixels from the CRF of --model dcnf; msdn has no field to condition.')
@@ -391,6 +419,8 @@ def main(argv=None):
         extra['upsample'] = upsample
     if args.condition is not None:
         extra['condition'] = (args.condition, args.condition_seed)
+    if args.loss == 'berhu':
+        extra['berhu_fraction'] = 0.2 if args.berhu_fraction is None else args.berhu_fraction
     ev = evaluator(replica, args.resolution, args.min_depth, args.max_depth, args.clamp_lo, args.clamp_hi,
                    keep_predictions=bool(args.predictions), **extra)
     op = EvalOp(pipeline, args.batchsize, dev)
@@ -421,6 +451,8 @@ def main(argv=None):
                    sigma_range=upsample.sigma_range)
     if args.condition is not None:
         out.update(condition=args.condition, condition_seed=args.condition_seed)
+    if args.loss == 'berhu':
+        out.update(loss='berhu', berhu_fraction=extra['berhu_fraction'])
     if args.predictions:
         np.save(args.predictions, torch.cat(ev.predictions).cpu().numpy() if ev.predictions else
                 np.zeros((0,) + ev.prediction_shape, np.float32))
@@ -474,6 +506,10 @@ def parse_args(argv=None):
                         'and crf_hidden (the plain MAP) are judged on the pixels of the hidden ones.')
     p.add_argument('--condition-seed', default=0, type=int,
                    help='--condition: the masks are drawn on the host from (this seed, the record\'s index).')
+    # NON-REFERENCE, msdn: --loss berhu [--berhu-fraction F] (see the module docstring).  Kept out of --help like --segmentation:
+    # this driver's help text is recorded word for word (tests/golden/evaluate_help.txt).
+    p.add_argument('--loss', default='silog', choices=['silog', 'berhu'], help=argparse.SUPPRESS)
+    p.add_argument('--berhu-fraction', default=None, type=float, metavar='F', help=argparse.SUPPRESS)
     add_shared_args(p, 'segmentation')
     add_upsample_args(p, ['none', 'joint'], 'none',
                       'NON-REFERENCE: joint also judges a third output, fine_joint (msdn) or crf_joint (dcnf): the prediction '

@@ -162,9 +162,11 @@ class Replica:
 
 class MSDNReplica(Replica):
     """One data-parallel replica of the MSDN training graph (src/models.py:203-367) on one GPU."""
+    objective = 'silog'       # the reference's loss; an instance built with objective='berhu' carries its own (see __init__)
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, global_step=0, beta2=1.0, reducer=None,
-                 precision='fp32', keep_dense_grads=True, overlap=True, valid_range=None, grad_weight=0.0):
+                 precision='fp32', keep_dense_grads=True, overlap=True, valid_range=None, grad_weight=0.0,
+                 objective='silog', berhu_fraction=0.2):
         """precision: arithmetic of the conv contractions — 'fp32' (exact, the parity default), 'bf16x3' (split
         operands on the bf16 matrix cores, ~1e-5) or 'bf16' (BASELINE config 5).  Tensors stay float32 in HBM; the
         Cin = 3 layers, the dense layers and everything element-wise always compute in fp32.
@@ -174,11 +176,25 @@ class MSDNReplica(Replica):
         run over the finite targets only (ops.silog_masked_loss_fwd).  None: the reference's step, launch for launch.
         grad_weight (NON-REFERENCE): weight of the gradient-matching term of Eigen & Fergus 2015 (eq. 4) in both losses: the
         squared horizontal and vertical differences of the log-depth error over the 55 x 74 grid, over the pairs of finite
-        targets under valid_range.  > 0: the four loss launches are ops.silog_grad_loss_fwd / _bwd.  0: today's launches."""
+        targets under valid_range.  > 0: the four loss launches are ops.silog_grad_loss_fwd / _bwd.  0: today's launches.
+        objective (NON-REFERENCE): 'silog', the reference's scale-invariant log loss, or 'berhu', the reverse Huber loss of
+        Laina et al. 2016 on linear depth (ops.berhu_loss_fwd / _bwd), which pulls on outputs at or below zero too; its
+        threshold is berhu_fraction, in (0, 1], times the largest error of each sample.  'silog': today's launches."""
+        if objective not in ('silog', 'berhu'):
+            raise ValueError(f"objective {objective!r}: 'silog' or 'berhu'")
+        berhu_fraction = float(berhu_fraction)
+        if not 0 < berhu_fraction <= 1:
+            raise ValueError(f'berhu_fraction {berhu_fraction!r}: the threshold is a fraction in (0, 1] of the largest error')
+        berhu = objective == 'berhu'
         grad_weight = float(grad_weight)
         if not grad_weight >= 0:
             raise ValueError(f'grad_weight {grad_weight!r}: the weight of the gradient-matching term is a number >= 0')
+        if berhu and grad_weight > 0:
+            raise ValueError(f"objective 'berhu' with grad_weight {grad_weight!r}: the gradient-matching term is defined on "
+                             f'log differences and belongs to the silog objective')
         self.grad_weight = grad_weight
+        if berhu:                         # under 'silog' the instance gains no attribute and no buffer
+            self.objective, self.berhu_fraction = objective, berhu_fraction
         self.valid_range = check_valid_range(valid_range)
         # keep_dense_grads=False (the training driver and bench.py on one GPU): under the reference's frozen optimizer the
         # gradient of the two dense kernels (268 MB) goes straight from the matrix cores into ApplyAdam's m slot
@@ -293,7 +309,11 @@ class MSDNReplica(Replica):
         self.f2 = buf(B, OUT_H, OUT_W, 64)
         self.fine = buf(B, OUT_H, OUT_W, 1)
         self.loss_coarse = buf(1); self.loss_fine = buf(1)
-        if grad_weight > 0:               # total, valid fraction, silog part, gradient part (ops.silog_grad_loss_fwd)
+        if berhu:                         # loss, valid fraction, mean threshold, quadratic share (ops.berhu_loss_fwd)
+            self.loss_berhu_c = buf(4); self.loss_berhu_f = buf(4)
+            self.loss_pair_c = self.loss_berhu_c[:2]; self.loss_pair_f = self.loss_berhu_f[:2]
+            self.loss_coarse = self.loss_pair_c[:1]; self.loss_fine = self.loss_pair_f[:1]
+        elif grad_weight > 0:             # total, valid fraction, silog part, gradient part (ops.silog_grad_loss_fwd)
             self.loss_quad_c = buf(4); self.loss_quad_f = buf(4)
             self.loss_pair_c = self.loss_quad_c[:2]; self.loss_pair_f = self.loss_quad_f[:2]
             self.loss_coarse = self.loss_pair_c[:1]; self.loss_fine = self.loss_pair_f[:1]
@@ -301,7 +321,8 @@ class MSDNReplica(Replica):
             self.loss_pair_c = buf(2); self.loss_pair_f = buf(2)
             self.loss_coarse = self.loss_pair_c[:1]; self.loss_fine = self.loss_pair_f[:1]
         # what a loss launch writes: 4, 2 or 1 floats, loss_coarse / loss_fine their first
-        self.loss_out_c, self.loss_out_f = ((self.loss_quad_c, self.loss_quad_f) if grad_weight > 0 else
+        self.loss_out_c, self.loss_out_f = ((self.loss_berhu_c, self.loss_berhu_f) if berhu else
+                                            (self.loss_quad_c, self.loss_quad_f) if grad_weight > 0 else
                                             (self.loss_pair_c, self.loss_pair_f) if valid_range is not None else
                                             (self.loss_coarse, self.loss_fine))
         # window positions of the pool maxima (all MaxPoolGrad needs besides the pooled values, see forward())
@@ -309,7 +330,8 @@ class MSDNReplica(Replica):
         self.a1 = torch.empty((B, 13, 18, 256), dtype=torch.uint8, device=dev)
         self.af1 = torch.empty((B, OUT_H, OUT_W, 63), dtype=torch.uint8, device=dev)
         self.pooled_fwd = None            # which network ran conv + pool fused in the last forward
-        silog_ws = ops.silog_grad_ws if grad_weight > 0 else ops.silog_ws if valid_range is None else ops.silog_masked_ws
+        silog_ws = (ops.berhu_ws if berhu else ops.silog_grad_ws if grad_weight > 0 else
+                    ops.silog_ws if valid_range is None else ops.silog_masked_ws)
         self.ws_c = silog_ws(B, dev); self.ws_f = silog_ws(B, dev)           # per-sample sums + arrival ticket + partials
         self.t_one = buf(B, 1, 1, 1) if valid_range is not None else None    # see ops.resize_bilinear_tf1_valid
         # gradients wrt pre-activations
@@ -702,6 +724,10 @@ class MSDNReplica(Replica):
         if self.grad_weight > 0:                         # NON-REFERENCE: the gradient-matching terms, before their weight
             rec['loss/coarse_grad'] = float(self.loss_quad_c[3])
             rec['loss/fine_grad'] = float(self.loss_quad_f[3])
+        if self.objective == 'berhu':                    # NON-REFERENCE: the mean threshold, the share of quadratic pixels
+            for name, quad in (('coarse', self.loss_berhu_c), ('fine', self.loss_berhu_f)):
+                rec[f'loss/{name}_threshold'] = float(quad[2])
+                rec[f'loss/{name}_quadratic'] = float(quad[3])
         return rec
 
     def summary_images(self):
@@ -922,7 +948,9 @@ class MSDNReplica(Replica):
 
     def _loss_fwd(self, out, loss, ws):
         """One launch: the loss of `out` against self.t into `loss`, the buffer that launch writes (loss_out_c / loss_out_f)."""
-        if self.grad_weight > 0:
+        if self.objective == 'berhu':
+            ops.berhu_loss_fwd(out, self.t, self.valid_range is not None, self.berhu_fraction, loss, ws)
+        elif self.grad_weight > 0:
             ops.silog_grad_loss_fwd(out, self.t, OUT_H, OUT_W, self.valid_range is not None, self.grad_weight, loss, ws)
         elif self.valid_range is None:
             ops.silog_loss_fwd(out, self.t, loss, ws)
@@ -930,7 +958,9 @@ class MSDNReplica(Replica):
             ops.silog_masked_loss_fwd(out, self.t, loss, ws)
 
     def _loss_bwd(self, out, ws, dout, dout16=None):
-        if self.grad_weight > 0:
+        if self.objective == 'berhu':
+            ops.berhu_loss_bwd(out, self.t, self.valid_range is not None, self.berhu_fraction, ws, dout, dout16)
+        elif self.grad_weight > 0:
             ops.silog_grad_loss_bwd(out, self.t, OUT_H, OUT_W, self.valid_range is not None, self.grad_weight, ws, dout, dout16)
         elif self.valid_range is None:
             ops.silog_loss_bwd(out, self.t, ws, dout, dout16)
@@ -2059,6 +2089,8 @@ class _MultiScaleDeepNetwork:
     augment = None       # NON-REFERENCE, --augment eigen: an augment.Eigen2014 (train-time augmentation of the input batch)
     valid_range = None   # NON-REFERENCE, --min-depth / --max-depth: (min, max), the depth maps have holes (see MSDNReplica)
     grad_weight = 0.0    # NON-REFERENCE, --loss-gradient: weight of the gradient-matching term in both losses (see MSDNReplica)
+    objective = 'silog'  # NON-REFERENCE, --loss berhu: the reverse Huber loss on linear depth (see MSDNReplica)
+    berhu_fraction = 0.2  # --berhu-fraction: its threshold, as a fraction of each sample's largest error
 
     def __call__(self, images, depths, train=True):
         assert images.pipeline is depths.pipeline, 'inputs and targets must come from the same data.inputs() call'
@@ -2066,7 +2098,8 @@ class _MultiScaleDeepNetwork:
         replica = MSDNReplica(images.pipeline.B, device=torch.device('cuda', torch.cuda.current_device()),
                               seed=self.seed, beta2=self.beta2, reducer=self.reducer, precision=self.precision,
                               keep_dense_grads=False,        # one GPU + the reference's optimizer: dW feeds ApplyAdam directly
-                              valid_range=self.valid_range, grad_weight=self.grad_weight)
+                              valid_range=self.valid_range, grad_weight=self.grad_weight, objective=self.objective,
+                              berhu_fraction=self.berhu_fraction)
         replica.uses_dropout = bool(train)                   # train=False: tf.layers.dropout(training=False), src/models.py:230
         if self.reducer is not None:                         # replicas start from rank 0's weights
             for g in replica.groups.values():

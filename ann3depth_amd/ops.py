@@ -520,6 +520,42 @@ def silog_grad_loss_bwd(out, tgt, h, w, masked, grad_weight, ws, dout, dout16=No
     return dout
 
 
+def berhu_ws(b, device):
+    """Workspace of berhu_loss_fwd / _bwd for a batch of b (or any smaller one): A3DH_WS_FLOATS(b) zeros (the ticket, its
+    first word, must start at zero)."""
+    return torch.zeros(3 * b + 1 + 3 * b * SILOG_PARTS, device=device)
+
+
+def _berhu_args(who, out, tgt, fraction):
+    b = out.shape[0]
+    assert out.numel() == tgt.numel(), f'{who}: out holds {out.numel()} values, tgt {tgt.numel()}'
+    fraction = float(fraction)
+    if not 0 < fraction <= 1:
+        raise ValueError(f'{who}: fraction {fraction!r} must lie in (0, 1]')
+    return b, out.numel() // b, fraction
+
+
+def berhu_loss_fwd(out, tgt, masked, fraction, loss, ws):
+    """NON-REFERENCE: the reverse Huber loss of Laina et al. 2016 on linear depth, with the threshold fraction x the largest
+    error of each sample (a3dh_berhu_loss_fwd, two launches).  masked: only finite targets count, as in silog_masked_loss_fwd.
+    loss: 4 floats — the loss, the valid fraction, the mean threshold, the share of the counting pixels that are quadratic."""
+    b, npix, fraction = _berhu_args('berhu_loss_fwd', out, tgt, fraction)
+    assert ws.numel() >= 3 * b + 1 + 3 * b * SILOG_PARTS, 'berhu workspace too small: allocate it with ops.berhu_ws(b, device)'
+    assert loss.numel() >= 4 and loss.is_contiguous(), 'berhu_loss_fwd writes four floats'
+    check(_lib.load().a3dh_berhu_loss_fwd(b, npix, _ptr(out), _ptr(tgt), int(bool(masked)), fraction, _ptr(loss), _ptr(ws),
+                                          _stream()), 'a3dh_berhu_loss_fwd')
+    return loss
+
+
+def berhu_loss_bwd(out, tgt, masked, fraction, ws, dout, dout16=None):
+    """dout16 as silog_loss_bwd's.  masked and fraction as in the forward call that filled ws."""
+    b, npix, fraction = _berhu_args('berhu_loss_bwd', out, tgt, fraction)
+    check(_lib.load().a3dh_berhu_loss_bwd_ex(b, npix, _ptr(out), _ptr(tgt), int(bool(masked)), fraction, _ptr(ws), _ptr(dout),
+                                             _ptr(dout16), 0 if dout16 is None else dout16.shape[-1], _stream()),
+          'a3dh_berhu_loss_bwd_ex')
+    return dout
+
+
 METRIC_COLUMNS = ('n', 'abs_rel', 'sq_rel', 'sq', 'log', 'log_sq', 'log10', 'delta1', 'delta2', 'delta3', 'nonfinite')
 # A3D_METRIC_* (include/a3d.h): the per-image sums of a3d_depth_metrics, in this column order
 
