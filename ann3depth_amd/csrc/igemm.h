@@ -330,7 +330,7 @@ struct Im2colTile {
         x >>= p.lstride;
       }
       ok = ok && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
-      const uint32_t off = (uint32_t)(pt.x + y * p.W + x) * (uint32_t)p.ld + (uint32_t)cd.c;   // < 2^31 (check_desc)
+      const uint32_t off = (uint32_t)(pt.x + y * p.W + x) * (uint32_t)p.ld + (uint32_t)cd.c;   // an ELEMENT index < 2^31 (check_desc); the pointer sum is 64-bit: right up to 8 GiB
       load_vec<VEC>(ok ? p.A + off : g_zero_line, regs[j]);
     }
   }
@@ -851,7 +851,8 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p, const uint32_t 
   constexpr int SGN = TRANSPOSED ? -1 : 1;
   const int pW = p.W, pld = p.ld;
 
-  // image of the tile's first pixel: descriptors are based there, so lane offsets stay far below 2^31
+  // image of the tile's first pixel: descriptors are based there (a 64-bit sum), so a lane's BYTE offset spans only the images the
+  // tile's rows reach: below 2^31 by check_desc's tile-span test, whatever the tensor's size (check_desc admits 2^31 ELEMENTS)
   auto image_of = [&](int pixel) -> uint32_t {
     const int px = pixel < p.npix ? pixel : p.npix - 1;
     return fdiv((uint32_t)px, p.div_phw);

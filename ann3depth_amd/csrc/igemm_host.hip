@@ -2,6 +2,7 @@
 // bf16 image and window-run forms with their filter repacks, fewch / fewch16, the LDS-DMA kernel or the generic GEMM), the workspace
 // that takes, and the kernel's parameters.  The plans: igemm_plan.cc; the launches: igemm_launch.hip.
 #include <algorithm>
+#include <cmath>
 
 #include "../../include/a3d_wino.h"
 #include "../../include/a3d_wino_grad.h"
@@ -169,6 +170,17 @@ static int check_desc(const a3d_conv_desc* d) {
   A3D_CHECK_ARG((double)d->n * d->h * d->w * d->ldx < lim && (double)d->n * d->ho * d->wo * d->ldy < lim &&
                     (double)d->r * d->s * d->c * d->k < lim,
                 "conv: tensor too large for 31-bit indexing");
+  // Those are ELEMENT counts: a tensor may hold up to 8 GiB.  The implicit-GEMM gathers address a tile's rows in BYTES from the
+  // image of the tile's first row (igemm.h, igemm_bf16.h, igemm_ring.h: int row-table entries), so the images that a tile of up
+  // to 256 rows can reach — one more than the rows cover — must lie within 2^31 bytes (4-byte elements assumed)
+  auto tile_span_ok = [&](double rows_per_image, double image_elems) {
+    const double images = std::min((double)d->n, std::floor(255.0 / rows_per_image) + 2.0);
+    return images * image_elems * 4.0 < lim;
+  };
+  A3D_CHECK_ARG(tile_span_ok((double)d->ho * d->wo, (double)d->h * d->w * d->ldx) &&                                   // forward, bwd-filter: x
+                    tile_span_ok(std::max(1.0, std::floor((double)d->h / d->stride) * std::floor((double)d->w / d->stride)),
+                                 (double)d->ho * d->wo * d->ldy),                                                      // bwd-data: dz, per class
+                "conv: single images too large for 31-bit byte offsets inside a tile");
   return A3D_OK;
 }
 
@@ -747,12 +759,13 @@ int a3dw_conv2d_bwd_data_prepare_filter(const a3d_conv_desc* d, const float* w, 
   return wino_filter(d, true, w, static_cast<float*>(prepared), static_cast<hipStream_t>(stream));
 }
 
-// bf16 x and bf16 dz, whole 16-byte pieces inside one filter tap, 31-bit byte offsets into x: the LDS-DMA kernel may take the
-// filter gradient (BiasAddGrad then comes from colsum_bf16)
+// bf16 x and bf16 dz, whole 16-byte pieces inside one filter tap, 31-bit byte offsets into x AND into dz (the kernel addresses
+// both from the tensor's first byte: a piece at 2^31 or beyond would read as zeros): the LDS-DMA kernel may take the filter
+// gradient (BiasAddGrad then comes from colsum_bf16)
 static bool bwd_f_ring_ok(const a3d_conv_desc* d, const Operands& o) {
   return d->precision == A3D_PREC_BF16 && stored16(d, A3D_STORE_X_BF16 | A3D_STORE_Y_BF16) && d->c % 8 == 0 && d->ldx % 8 == 0 &&
-         d->k % 8 == 0 && d->ldy % 8 == 0 && (double)d->n * d->h * d->w * d->ldx * 2.0 < 2147483647.0 && colsum_bf16_ok(d->k) &&
-         d->ldy == d->k && !o.w;
+         d->k % 8 == 0 && d->ldy % 8 == 0 && (double)d->n * d->h * d->w * d->ldx * 2.0 < 2147483647.0 &&
+         (double)d->n * d->ho * d->wo * d->ldy * 2.0 < 2147483647.0 && colsum_bf16_ok(d->k) && d->ldy == d->k && !o.w;
 }
 // The filter gradient as a GEMM: over the tensors as stored, the same offered to the LDS-DMA kernel, or in the window-run form
 // (the gradient of the PADDED filter into the workspace, unpadded afterwards)

@@ -280,7 +280,8 @@ __global__ __launch_bounds__(512, (RingCfg<MODE, BM, BN, WAVES_M>::MIN_WAVES)) v
       }
     } else if (pc < Cfg::A_NI + Cfg::B_NI) {
       const int j = pc - Cfg::A_NI;
-      // (b_voff = kOOB stays past the end under the additions: filter and slab offsets are below 2^31, checked on the host)
+      // (b_voff = kOOB stays past the end under the additions: filter offsets, and bwd-filter's offsets into the whole dz, are below 2^31:
+      // bwd_f_ring_ok on the host)
       if constexpr (Cfg::B_KC) bo[j] = (b_voff[j] + (uint32_t)tt.w + (uint32_t)p_ch * 2u) | (p_kvalid ? 0u : kOOB) | dbg_b;
       else bo[j] = (b_voff[j] + (uint32_t)p_kt * (uint32_t)(BK * p.ldb * 2)) | (p_kt < kt_end ? 0u : kOOB) | dbg_b;   // rows (bwd-filter: pixels) past the end: past the end
     } else {

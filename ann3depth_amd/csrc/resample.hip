@@ -187,9 +187,13 @@ static int launch_resample(ResampleArgs p, const char* who, bool warp, bool vali
   A3D_CHECK_ARG(!warp || p.table, "%s: no table", who);
   A3D_CHECK_ARG(!valid || p.lo <= p.hi, "%s: thresholds %g, %g (NaN, or min_depth > max_depth)", who, (double)p.lo, (double)p.hi);
   if (!two) p.t[1] = p.t[0];
-  long long blocks = std::min(p.n * std::max(a.oh, b.oh), 16384);       // resize: a block per output row
+  const long long lim = 0x7fffffffLL;         // the kernels' index arithmetic is 32-bit
+  // resize: output rows (n oh) and the elements of one source or output line are ints; image bases are 64-bit
+  A3D_CHECK_ARG((long long)p.n * std::max(a.oh, b.oh) <= lim && (long long)a.w * a.c <= lim && (long long)b.w * b.c <= lim &&
+                    (long long)a.ow * a.c <= lim && (long long)b.ow * b.c <= lim,
+                "%s: image too large", who);
+  long long blocks = std::min((long long)p.n * std::max(a.oh, b.oh), 16384LL);       // resize: a block per output row
   if (warp) {
-    const long long lim = 0x7fffffffLL;       // the kernel's index arithmetic is 32-bit
     A3D_CHECK_ARG((long long)a.h * a.w * std::max(a.c, b.c) <= lim && (long long)p.n * A3D_WARP_STRIDE <= lim,
                   "%s: image too large", who);
     auto tiles = [&](const ResizeOne& r) {

@@ -41,7 +41,11 @@ extern "C" {
 #define A3D_ACT_SIGMOID 2
 
 /* Geometry of one tf.layers.conv2d call (src/models.py:64-72,211-223,241-251).
- * pad_t/pad_l are TF's "before" paddings (SAME: pad_total//2; VALID: 0); ho/wo the output extent. */
+ * pad_t/pad_l are TF's "before" paddings (SAME: pad_total//2; VALID: 0); ho/wo the output extent.
+ * Sizes: each of n h w ldx, n ho wo ldy (the conv output, also where a call writes only its pooled map) and r s c k must be
+ * below 2^31 - 1 ELEMENTS, so a float32 tensor may hold up to 8 GiB; and the images that 256 consecutive output (bwd-data:
+ * input) pixels reach, plus one, must lie within 2^31 bytes.  Anything else is A3D_EINVAL before any launch; a kernel that
+ * cannot address an admitted size is never chosen for it. */
 typedef struct a3d_conv_desc {
   int32_t n, h, w, c;        /* input  [n,h,w,c]  */
   int32_t k, r, s;           /* filter [r,s,c,k]  */
