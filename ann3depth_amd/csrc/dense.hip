@@ -14,6 +14,7 @@
 // over m in ascending order, one fmaf per term — the order of the BiasAddGrad sum too.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 
 #include "a3d_internal.h"
@@ -735,6 +736,23 @@ __global__ __launch_bounds__(256) void dense_fwd_stream_kernel(const DenseStream
   }
 }
 
+// Tuning aid (A3D_TUNING=1 A3D_PLAN_LOG=1, the switch of igemm_launch.hip's `a3d plan:` line): one `a3d dense:` line per
+// launch of this file on stderr — entry point, m k n, the kernel with its template arguments, the grid, and what the
+// dispatch derived (forward: splits and span; the Adam stream kernels: row groups per block).  These launches carry no
+// timing record: the line is the only trace of which instantiation ran.
+static bool dense_route_log() {
+  static const bool on = tune_int("A3D_PLAN_LOG", 0) != 0;
+  return on;
+}
+static void log_dense_route(const char* entry, int m, int k, int n, const char* kernel, dim3 grid, const char* detail) {
+  char name[96];
+  size_t len = 0;
+  for (const char* c = kernel; *c && len + 1 < sizeof(name); ++c)      // "<2, 1, 2>" as the source spells it -> "<2,1,2>"
+    if (*c != ' ') name[len++] = *c;
+  name[len] = '\0';
+  fprintf(stderr, "a3d dense: %s m %d k %d n %d -> %s grid %ux%u%s\n", entry, m, k, n, name, grid.x, grid.y, detail);
+}
+
 static int pick_span(int extent, int groups, int quantum) {
   const int target = 512;                              // two resident blocks per CU
   const int want = std::max(1, target / std::max(1, groups));
@@ -760,6 +778,11 @@ int dense_fwd_stream(int m, int k, int n, const float* x, const float* w, const 
   p.out = p.splits > 1 ? static_cast<float*>(ws) : y;
   clear_stale_error();
   const dim3 grid((n + 127) / 128, p.splits);
+  if (dense_route_log()) {
+    char detail[64];
+    snprintf(detail, sizeof(detail), " splits %d span %d", p.splits, p.span);
+    log_dense_route("dense_fwd_stream", m, k, n, m <= 32 ? "dense_fwd_stream_kernel<1>" : "dense_fwd_stream_kernel<2>", grid, detail);
+  }
   if (m <= 32) hipLaunchKernelGGL(dense_fwd_stream_kernel<1>, grid, dim3(256), 0, st, p);
   else hipLaunchKernelGGL(dense_fwd_stream_kernel<2>, grid, dim3(256), 0, st, p);
   int rc = check_launch("dense_fwd_stream");
@@ -774,7 +797,9 @@ bool dense_dw_applicable(int m, int k, int n) { return m >= 1 && m <= 64 && k >=
 
 int dense_dw_launch(int m, int k, int n, const float* x, const float* dz, float* dw, float* db, hipStream_t st) {
   clear_stale_error();
-  hipLaunchKernelGGL((dense_dw_kernel<false, 4>), dim3((n + 127) / 128, (k + 127) / 128), dim3(256), 0, st, x, dz, dw, db,
+  const dim3 grid((n + 127) / 128, (k + 127) / 128);
+  if (dense_route_log()) log_dense_route("dense_dw_launch", m, k, n, "dense_dw_kernel<false, 4>", grid, "");
+  hipLaunchKernelGGL((dense_dw_kernel<false, 4>), grid, dim3(256), 0, st, x, dz, dw, db,
                      nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, m, k, n, 0.f, 1.f);
   return check_launch("dense_dw");
 }
@@ -828,27 +853,41 @@ extern "C" int a3d_dense_bwd_filter_adam_tf1_ex(int m, int k, int n, const float
   const dim3 stream_grid(colblocks, ((k + 31) / 32 + gpb - 1) / gpb);
   const bool stream_ok = m <= 64 && k % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && !no_stream;
   const hipStream_t hst = static_cast<hipStream_t>(stream);
-#define A3D_DW_STREAM(CWV, MBV, ...)                                                                                     \
-  hipLaunchKernelGGL((dense_dw_adam_stream_kernel<CWV, MBV, ##__VA_ARGS__>), stream_grid, dim3(256), 0, hst, x, dz, var_w, m_w, v_w, var_b, \
-                     m_b, v_b, m, k, n, 1.f - beta1, grad_scale, gpb)
+  const dim3 plain_grid((n + 127) / 128, (k + 127) / 128);
+  const char* kernel = nullptr;         // what launches, for the route line
+  const dim3* grid = nullptr;
+#define A3D_DW_STREAM(...)                                                                                                \
+  do {                                                                                                                    \
+    kernel = "dense_dw_adam_stream_kernel<" #__VA_ARGS__ ">", grid = &stream_grid;                                        \
+    hipLaunchKernelGGL((dense_dw_adam_stream_kernel<__VA_ARGS__>), stream_grid, dim3(256), 0, hst, x, dz, var_w, m_w, v_w, var_b, \
+                       m_b, v_b, m, k, n, 1.f - beta1, grad_scale, gpb);                                                  \
+  } while (0)
   // bf16 arithmetic (config 5): the bf16 matrix cores take the batch axis 16 rows per instruction — worth it above 32 rows
   const bool bf = precision == A3D_PREC_BF16 && m > 32 && stream_ok;
+  // (no <4, 1> / <2, 1> stream form: at m <= 32 and an even n on 8-byte slots the slim form is taken; an odd n or slots off
+  // the 8-byte grid leave the stream kernels altogether)
   if (bf && n % 4 == 0 && (slots & 15) == 0) A3D_DW_STREAM(4, 2, 1, true);
   else if (bf && n % 2 == 0 && (slots & 7) == 0) A3D_DW_STREAM(2, 2, 1, true);
   else if (stream_ok && slim && (slots & 7) == 0) A3D_DW_STREAM(2, 1, 2);
-  else if (stream_ok && m <= 32 && n % 4 == 0 && (slots & 15) == 0) A3D_DW_STREAM(4, 1);
-  else if (stream_ok && m <= 32 && n % 2 == 0 && (slots & 7) == 0) A3D_DW_STREAM(2, 1);
   else if (stream_ok && n % 2 == 0 && (slots & 7) == 0) A3D_DW_STREAM(2, 2);
 #undef A3D_DW_STREAM
-  else if (n % 4 == 0 && (slots & 15) == 0)
-    hipLaunchKernelGGL(dense_dw_adam_rows_kernel<4>, rows_grid, dim3(256), 0, static_cast<hipStream_t>(stream), x, dz, var_w,
+  else if (n % 4 == 0 && (slots & 15) == 0) {
+    kernel = "dense_dw_adam_rows_kernel<4>", grid = &rows_grid;
+    hipLaunchKernelGGL(dense_dw_adam_rows_kernel<4>, rows_grid, dim3(256), 0, hst, x, dz, var_w,
                        m_w, v_w, var_b, m_b, v_b, m, k, n, 1.f - beta1, grad_scale);
-  else if (n % 2 == 0 && (slots & 7) == 0)
-    hipLaunchKernelGGL(dense_dw_adam_rows_kernel<2>, rows_grid, dim3(256), 0, static_cast<hipStream_t>(stream), x, dz, var_w,
+  } else if (n % 2 == 0 && (slots & 7) == 0) {
+    kernel = "dense_dw_adam_rows_kernel<2>", grid = &rows_grid;
+    hipLaunchKernelGGL(dense_dw_adam_rows_kernel<2>, rows_grid, dim3(256), 0, hst, x, dz, var_w,
                        m_w, v_w, var_b, m_b, v_b, m, k, n, 1.f - beta1, grad_scale);
-  else
-    hipLaunchKernelGGL((dense_dw_kernel<true, 4>), dim3((n + 127) / 128, (k + 127) / 128), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), x, dz, nullptr, nullptr, var_w, m_w, v_w, var_b, m_b, v_b, m, k, n,
-                       1.f - beta1, grad_scale);
+  } else {
+    kernel = "dense_dw_kernel<true, 4>", grid = &plain_grid;
+    hipLaunchKernelGGL((dense_dw_kernel<true, 4>), plain_grid, dim3(256), 0, hst, x, dz, nullptr, nullptr, var_w, m_w, v_w,
+                       var_b, m_b, v_b, m, k, n, 1.f - beta1, grad_scale);
+  }
+  if (dense_route_log()) {
+    char detail[32] = "";
+    if (grid == &stream_grid) snprintf(detail, sizeof(detail), " gpb %d", gpb);
+    log_dense_route("a3d_dense_bwd_filter_adam_tf1_ex", m, k, n, kernel, *grid, detail);
+  }
   return check_launch("dense_dw_adam");
 }

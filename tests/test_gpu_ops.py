@@ -673,9 +673,11 @@ def test_adam_frozen_path_poison_semantics(ops):
     assert np.isnan(ref['w']).sum() == 5 and np.isnan(opt.v['w']).sum() == 5
 
 
-# the last two are large enough for the streaming kernel to walk several row groups per block (16- and 8-byte rows)
+# (64, 4488, 1030) and (32, 1028, 8450) are large enough for a block of the stream kernels to walk two row groups (<2, 2>: 141
+# groups x 5 column blocks > 512; the slim <2, 1, 2>: 33 x 34 > 1024); the two other 4488-row shapes run the slim form with one
+# group per block (141 x 7 < 1024).  tests/dense_cases.py holds the routes to the library's `a3d dense:` line.
 @pytest.mark.parametrize('m,k,n', [(32, 384, 520), (5, 130, 4070), (64, 512, 256), (1, 512, 257), (32, 4488, 1540),
-                                   (17, 4488, 1538), (64, 4488, 1030), (47, 1028, 772)])
+                                   (17, 4488, 1538), (64, 4488, 1030), (47, 1028, 772), (32, 1028, 8450)])
 def test_dense_bwd_filter_adam_fused_equals_two_passes(ops, m, k, n):
     """a3d_dense_bwd_filter_adam_tf1 (gradient never written) against a3d_dense_bwd_filter + a3d_adam_apply_tf1 and the
     oracle's ApplyAdam, over two steps, with non-finite gradients in both the kernel and the bias: m, v and var must agree
