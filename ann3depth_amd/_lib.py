@@ -166,6 +166,16 @@ BERHU_SIGNATURES = {
     'a3dh_berhu_loss_bwd_ex': (c_int, [c_int, c_int, _P, _P, c_int, c_float, _P, _P, _P, c_int, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_align.h declares (NON-REFERENCE extension, prefix a3da_)
+ALIGN_SIGNATURES = {
+    'a3da_depth_align_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'a3da_depth_align': (c_int, [c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, c_float, c_float, c_int, _P, _P, _P, _P,
+                                 c_size_t, _P]),
+    'a3da_depth_metrics_aligned': (c_int, [c_int, c_int, c_int, _P, c_int, c_int, _P, c_int, c_float, c_float, c_float, c_float,
+                                           _P, _P, _P, c_size_t, _P]),
+    'a3da_affine_apply': (c_int, [c_int, c_int, _P, _P, _P, _P]),
+}
+
 # name -> (restype, argtypes); every symbol include/a3d_crf_valid.h declares (NON-REFERENCE extension, prefix a3dv_)
 CRF_VALID_SIGNATURES = {
     'a3dv_superpixel_mean_valid': (c_int, [c_int, c_int, c_int, _P, c_int, c_int, _P, _P, _P]),
@@ -252,7 +262,8 @@ def load():
                               + list(CRF_BAND_SIGNATURES.items()) + list(WINO_SIGNATURES.items())
                               + list(UPSAMPLE_SIGNATURES.items()) + list(POSTERIOR_SIGNATURES.items())
                               + list(WINO_GRAD_SIGNATURES.items()) + list(SLIC_SIGNATURES.items())
-                              + list(WINO_BWD_SIGNATURES.items()) + list(BERHU_SIGNATURES.items())):
+                              + list(WINO_BWD_SIGNATURES.items()) + list(BERHU_SIGNATURES.items())
+                              + list(ALIGN_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -10,54 +10,33 @@
 // in ws[(b * parts + part) * 11 + col].  metrics_rows_kernel: one thread per (image, column) adds the parts in part order
 // into rows[b * 11 + col].  The launch boundary makes the partials visible; every sum is taken in a fixed order, so the
 // result is the same bits on every run.
+//
+// The walk, the target decode, the validity test and the sampler are metrics_common.h's, shared with align.hip.
+// a3da_depth_metrics_aligned (include/a3d_align.h) is the same kernel body with a per-image affine map of the prediction.
 #include <algorithm>
 #include <cmath>
 
-#include "a3d_internal.h"
+#include "../../include/a3d_align.h"
+#include "metrics_common.h"
 
 namespace a3d {
 
 namespace {
 
-constexpr int kCols = A3D_METRIC_COLS;
-constexpr int kThreads = 256;
-constexpr int kPixelsPerPart = 4096;      // 480 x 640 targets: 75 workgroups per image; 55 x 74: one
-constexpr int kMaxParts = 1024;
+using namespace pixels;
 
-struct MetricsArgs {
-  const float* pred;
-  const void* target;
-  double* ws;
-  int ph, pw, th, tw, npix, chunk, parts, u8;
-  float sy, sx;                           // legacy ResizeBilinear scales in / out (resize_one in resample.hip)
-  float min_depth, max_depth, clamp_lo, clamp_hi;
+constexpr int kCols = A3D_METRIC_COLS;
+
+struct MetricsArgs : PixelArgs {           // out: double [n][parts][kCols]
+  float clamp_lo, clamp_hi;
+  const float* coef;                      // [n, 2] (s, b) of a3da_depth_metrics_aligned; not read by the plain entry
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// The prediction at target pixel (oy, ox): the legacy align_corners=False mapping with resize_rows' operations, or the
-// pixel itself when the grids agree.
-__device__ __forceinline__ float sample_pred(const MetricsArgs& a, const float* p, int oy, int ox) {
-  if (a.ph == a.th && a.pw == a.tw) return p[oy * a.pw + ox];
-  const float fy = __fmul_rn((float)oy, a.sy);
-  const int y0 = (int)fy, y1 = min(y0 + 1, a.ph - 1);
-  const float ly = __fsub_rn(fy, (float)y0);
-  const float fx = __fmul_rn((float)ox, a.sx);
-  const int x0 = (int)fx, x1 = min(x0 + 1, a.pw - 1);
-  const float lx = __fsub_rn(fx, (float)x0);
-  const float tl = p[y0 * a.pw + x0], tr = p[y0 * a.pw + x1];
-  const float bl = p[y1 * a.pw + x0], br = p[y1 * a.pw + x1];
-  const float top = __fadd_rn(tl, __fmul_rn(__fsub_rn(tr, tl), lx));
-  const float bot = __fadd_rn(bl, __fmul_rn(__fsub_rn(br, bl), lx));
-  return __fadd_rn(top, __fmul_rn(__fsub_rn(bot, top), ly));
-}
-
-__device__ __forceinline__ void accumulate(const MetricsArgs& a, float p, float t, double (&s)[kCols]) {
-  if (!(isfinite(t) && t > a.min_depth && t <= a.max_depth)) return;
+// ALIGNED: the sampled prediction p becomes fl(fl(s p) + b) (include/a3d_align.h) before the finiteness test and the clamp.
+template <int ALIGNED>
+__device__ __forceinline__ void accumulate(const MetricsArgs& a, float p, float t, float cs, float cb, double (&s)[kCols]) {
+  if (!target_valid(a, t)) return;
+  if (ALIGNED) p = __fadd_rn(__fmul_rn(cs, p), cb);
   if (!isfinite(p)) {
     s[A3D_METRIC_NONFINITE] += 1.0;
     return;
@@ -80,51 +59,31 @@ __device__ __forceinline__ void accumulate(const MetricsArgs& a, float p, float 
   s[A3D_METRIC_DELTA3] += ratio < 1.953125f ? 1.0 : 0.0;
 }
 
-template <int U8>
+template <int U8, int ALIGNED>
 __global__ __launch_bounds__(kThreads) void metrics_part_kernel(const MetricsArgs a) {
   __shared__ float lut[256];
   __shared__ double red[kThreads / 64][kCols];
   if constexpr (U8 != 0) {
-    // the float the converter stored plus the loader's 0.5, as resize_kernel's table (fill_u8_lut, resample.hip)
-    lut[threadIdx.x] = __fadd_rn(__fsub_rn(__fdiv_rn((float)threadIdx.x, 255.f), 0.5f), 0.5f);
+    fill_u8_lut(lut);
     __syncthreads();
   }
   const int part = blockIdx.x, b = blockIdx.y;
-  const int lo = part * a.chunk, hi = min(a.npix, lo + a.chunk);
-  const float* p = a.pred + (size_t)b * a.ph * a.pw;
-  const size_t base = (size_t)b * a.npix;
-  // whole aligned groups of four when every image starts on a 16-byte (float) / 4-byte (uint8) boundary (chunk is a
-  // multiple of 4); a uniform choice per launch
-  const bool vec = (a.npix & 3) == 0 &&
-                   ((reinterpret_cast<uintptr_t>(a.target) & (U8 ? 3u : 15u)) == 0);
+  float cs = 1.f, cb = 0.f;
+  if constexpr (ALIGNED != 0) { cs = a.coef[2 * b]; cb = a.coef[2 * b + 1]; }
   double s[kCols];
 #pragma unroll
   for (int c = 0; c < kCols; ++c) s[c] = 0.0;
+  const int lo = part * a.chunk, hi = min(a.npix, lo + a.chunk);
+  const float* p = a.pred + (size_t)b * a.ph * a.pw;
+  const size_t base = (size_t)b * a.npix;
+  const bool vec = vector_targets<U8>(a);
   for (int i0 = lo + 4 * threadIdx.x; i0 < hi; i0 += 4 * kThreads) {
     float t[4];
-    if (U8) {
-      const uint8_t* tg = static_cast<const uint8_t*>(a.target) + base + i0;
-      if (vec) {
-        const uchar4 k = *reinterpret_cast<const uchar4*>(tg);
-        t[0] = lut[k.x]; t[1] = lut[k.y]; t[2] = lut[k.z]; t[3] = lut[k.w];
-      } else {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) t[u] = i0 + u < hi ? lut[tg[u]] : 0.f;
-      }
-    } else {
-      const float* tg = static_cast<const float*>(a.target) + base + i0;
-      if (vec) {
-        const float4 v = *reinterpret_cast<const float4*>(tg);
-        t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
-      } else {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) t[u] = i0 + u < hi ? tg[u] : 0.f;
-      }
-    }
+    load_targets4<U8>(a, lut, base, i0, hi, vec, t);
     int oy = i0 / a.tw, ox = i0 - oy * a.tw;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      if (i0 + u < hi) accumulate(a, sample_pred(a, p, oy, ox), t[u], s);
+      if (i0 + u < hi) accumulate<ALIGNED>(a, sample_pred(a, p, oy, ox), t[u], cs, cb, s);
       if (++ox == a.tw) { ox = 0; ++oy; }
     }
   }
@@ -137,7 +96,7 @@ __global__ __launch_bounds__(kThreads) void metrics_part_kernel(const MetricsArg
   __syncthreads();
   if (threadIdx.x < kCols) {
     const int c = threadIdx.x;
-    a.ws[((size_t)b * a.parts + part) * kCols + c] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
+    static_cast<double*>(a.out)[((size_t)b * a.parts + part) * kCols + c] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
   }
 }
 
@@ -152,10 +111,40 @@ __global__ __launch_bounds__(kThreads) void metrics_rows_kernel(const double* __
   rows[i] = acc;
 }
 
-int parts_for(int npix) { return std::min(kMaxParts, std::max(1, (npix + kPixelsPerPart - 1) / kPixelsPerPart)); }
-
-bool shape_ok(int n, int th, int tw) {
-  return n > 0 && n <= 65535 && th > 0 && tw > 0 && (int64_t)th * tw <= (int64_t)INT32_MAX - 4 * kThreads;   // (grid y)
+// Both entry points: coef NULL is the plain a3d_depth_metrics.
+int depth_metrics(const char* what, int n, int ph, int pw, const float* pred, int th, int tw, const void* target, int target_u8,
+                  float min_depth, float max_depth, float clamp_lo, float clamp_hi, const float* coef, double* rows, void* ws,
+                  size_t ws_bytes, void* stream) {
+  A3D_CHECK_ARG(shape_ok(n, th, tw) && pred_shape_ok(ph, pw) && pred && target && rows, "%s: bad arguments", what);
+  A3D_CHECK_ARG(!std::isnan(min_depth) && !std::isnan(max_depth) && !std::isnan(clamp_lo) && !std::isnan(clamp_hi) &&
+                    clamp_lo <= clamp_hi,
+                "%s: bad depth range or clamp", what);
+  const size_t need = a3d_depth_metrics_ws_bytes(n, th, tw);
+  if (!ws || ws_bytes < need)
+    return set_error(A3D_EWORKSPACE, "%s: need %zu workspace bytes, got %zu", what, need, ws ? ws_bytes : (size_t)0);
+  MetricsArgs a;
+  fill_pixel_args(a, ph, pw, pred, th, tw, target, target_u8, min_depth, max_depth);
+  a.out = ws; a.coef = coef;
+  a.clamp_lo = clamp_lo; a.clamp_hi = clamp_hi;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  clear_stale_error();
+  const dim3 grid(a.parts, n), block(kThreads);
+  if (coef) {
+    if (a.u8)
+      hipLaunchKernelGGL((metrics_part_kernel<1, 1>), grid, block, 0, st, a);
+    else
+      hipLaunchKernelGGL((metrics_part_kernel<0, 1>), grid, block, 0, st, a);
+  } else {
+    if (a.u8)
+      hipLaunchKernelGGL((metrics_part_kernel<1, 0>), grid, block, 0, st, a);
+    else
+      hipLaunchKernelGGL((metrics_part_kernel<0, 0>), grid, block, 0, st, a);
+  }
+  int rc = check_launch(what);
+  if (rc != A3D_OK) return rc;
+  hipLaunchKernelGGL(metrics_rows_kernel, dim3((n * kCols + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
+                     static_cast<const double*>(ws), rows, n, a.parts);
+  return check_launch("depth_metrics_rows");
 }
 
 }  // namespace
@@ -170,33 +159,16 @@ size_t a3d_depth_metrics_ws_bytes(int n, int th, int tw) {
 int a3d_depth_metrics(int n, int ph, int pw, const float* pred, int th, int tw, const void* target, int target_u8,
                       float min_depth, float max_depth, float clamp_lo, float clamp_hi, double* rows, void* ws,
                       size_t ws_bytes, void* stream) {
-  A3D_CHECK_ARG(shape_ok(n, th, tw) && ph > 0 && pw > 0 && (int64_t)ph * pw <= INT32_MAX && pred && target && rows,
-                "depth_metrics: bad arguments");
-  A3D_CHECK_ARG(!std::isnan(min_depth) && !std::isnan(max_depth) && !std::isnan(clamp_lo) && !std::isnan(clamp_hi) &&
-                    clamp_lo <= clamp_hi,
-                "depth_metrics: bad depth range or clamp");
-  const size_t need = a3d_depth_metrics_ws_bytes(n, th, tw);
-  if (!ws || ws_bytes < need)
-    return set_error(A3D_EWORKSPACE, "depth_metrics: need %zu workspace bytes, got %zu", need, ws ? ws_bytes : (size_t)0);
-  MetricsArgs a;
-  a.pred = pred; a.target = target; a.ws = static_cast<double*>(ws);
-  a.ph = ph; a.pw = pw; a.th = th; a.tw = tw; a.npix = th * tw;
-  a.parts = parts_for(a.npix);
-  a.chunk = ((a.npix + a.parts - 1) / a.parts + 3) & ~3;
-  a.u8 = target_u8 ? 1 : 0;
-  a.sy = (float)ph / (float)th; a.sx = (float)pw / (float)tw;
-  a.min_depth = min_depth; a.max_depth = max_depth; a.clamp_lo = clamp_lo; a.clamp_hi = clamp_hi;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  clear_stale_error();
-  if (a.u8)
-    hipLaunchKernelGGL(metrics_part_kernel<1>, dim3(a.parts, n), dim3(kThreads), 0, st, a);
-  else
-    hipLaunchKernelGGL(metrics_part_kernel<0>, dim3(a.parts, n), dim3(kThreads), 0, st, a);
-  int rc = check_launch("depth_metrics");
-  if (rc != A3D_OK) return rc;
-  hipLaunchKernelGGL(metrics_rows_kernel, dim3((n * kCols + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
-                     static_cast<const double*>(ws), rows, n, a.parts);
-  return check_launch("depth_metrics_rows");
+  return depth_metrics("depth_metrics", n, ph, pw, pred, th, tw, target, target_u8, min_depth, max_depth, clamp_lo, clamp_hi,
+                       nullptr, rows, ws, ws_bytes, stream);
+}
+
+int a3da_depth_metrics_aligned(int n, int ph, int pw, const float* pred, int th, int tw, const void* target, int target_u8,
+                               float min_depth, float max_depth, float clamp_lo, float clamp_hi, const float* coef,
+                               double* rows, void* ws, size_t ws_bytes, void* stream) {
+  A3D_CHECK_ARG(coef, "depth_metrics_aligned: NULL coef");
+  return depth_metrics("depth_metrics_aligned", n, ph, pw, pred, th, tw, target, target_u8, min_depth, max_depth, clamp_lo,
+                       clamp_hi, coef, rows, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

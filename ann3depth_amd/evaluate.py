@@ -43,6 +43,15 @@ targets with the threshold F (default 0.2, 0 < F <= 1) times each image's larges
 report gains ``loss`` and ``berhu_fraction``.  Checkpoints do not record the objective: any MSDN checkpoint can be asked.
 Without the flag nothing more is launched and the report has no new key.
 
+``--align median|scale|affine`` (NON-REFERENCE, both models; include/a3d_align.h, ops.depth_align; not listed by ``--help``):
+the depth maps the models train on are min-max scaled per image, so a checkpoint predicts depth up to an affine map per
+image.  Every output judged is judged a second time as ``<name>_aligned`` after a per-image scale (``median``: the ratio of
+the lower medians; ``scale``: least squares) or scale and shift (``affine``: least squares) fitted against the same target
+over the pixels the metrics count, under the same ``--min-depth`` / ``--max-depth``.  Each ``_aligned`` entry also carries
+``unaligned_images`` (images that could not be fitted and were judged as they are) and ``mean_scale`` / ``mean_shift`` over
+the others; the report gains ``align``.  ``--predictions`` keeps writing the unaligned maps.  The default, ``none``,
+launches nothing more and adds no key.
+
 Output: one JSON line on stdout, ``<ckptdir>/<model>_<id>/eval-<global_step>.json`` and TensorBoard scalars
 ``eval/<output>/<metric>`` (and ``eval/crf_nll``) at the checkpoint's global step.  Exit code 2 when there is nothing to
 evaluate (no checkpoint, no test split) or the request is unsupported (an unknown model, more than one process).
@@ -89,11 +98,16 @@ class MetricRows:
     asked for, the predictions."""
 
     def __init__(self, replica, resolution, more_outputs, prediction_shape, min_depth, max_depth, clamp_lo, clamp_hi,
-                 keep_predictions):
+                 keep_predictions, align=None):
+        """align (NON-REFERENCE, --align median|scale|affine): every output judged is judged a second time as
+        `<name>_aligned`, after the per-image scale and shift of ops.depth_align against the same target."""
         self.rep, self.resolution = replica, resolution
         self.outputs = self.outputs + more_outputs
         self.kw = dict(min_depth=min_depth, max_depth=max_depth, clamp_lo=clamp_lo, clamp_hi=clamp_hi)
-        self.rows = {o: [] for o in self.outputs}
+        self.align = align
+        self.aligned = tuple(o + '_aligned' for o in self.outputs) if align is not None else ()
+        self.rows = {o: [] for o in self.outputs + self.aligned}
+        self.fits = {o: [] for o in self.aligned}            # (coef, status) per batch
         self.counts = []
         self.predictions = [] if keep_predictions else None
         self.prediction_shape = prediction_shape
@@ -101,6 +115,11 @@ class MetricRows:
     def judge(self, name, out, n, target):
         """Append the metric rows of out[:n] against target under output `name`."""
         self.rows[name].append(ops.depth_metrics(out[:n], target, **self.kw))
+        if self.align is not None:
+            coef, _, status = ops.depth_align(out[:n], target, self.align, min_depth=self.kw['min_depth'],
+                                              max_depth=self.kw['max_depth'])
+            self.rows[name + '_aligned'].append(ops.depth_metrics(out[:n], target, coef=coef, **self.kw))
+            self.fits[name + '_aligned'].append((coef, status))
 
     def mean(self, per_batch):
         """The mean over the records of per-batch means ([1] device tensors, one per batch)."""
@@ -110,7 +129,14 @@ class MetricRows:
 
     def results(self):
         torch.cuda.synchronize()
-        return {name: ops.summarize_depth_metrics(torch.cat(self.rows[name])) for name in self.outputs}
+        out = {name: ops.summarize_depth_metrics(torch.cat(self.rows[name])) for name in self.outputs + self.aligned}
+        for name in self.aligned:
+            coef = torch.cat([c for c, _ in self.fits[name]]).double().cpu().numpy()
+            ok = torch.cat([s for _, s in self.fits[name]]).cpu().numpy() == 0
+            out[name].update(unaligned_images=int((~ok).sum()),
+                             mean_scale=float(coef[ok, 0].mean()) if ok.any() else float('nan'),
+                             mean_shift=float(coef[ok, 1].mean()) if ok.any() else float('nan'))
+        return out
 
 
 class Evaluator(MetricRows):
@@ -118,14 +144,14 @@ class Evaluator(MetricRows):
     outputs = OUTPUTS['msdn']
 
     def __init__(self, replica, resolution='grid', min_depth=0., max_depth=float('inf'), clamp_lo=1e-3,
-                 clamp_hi=float('inf'), keep_predictions=False, upsample=None, berhu_fraction=None):
+                 clamp_hi=float('inf'), keep_predictions=False, upsample=None, berhu_fraction=None, align=None):
         """upsample (NON-REFERENCE, --upsample joint): an ops.JointUpsampler; a third output `fine_joint`, the fine map
         brought to the record image's size under the batch's images, is judged against the same target.
         berhu_fraction (NON-REFERENCE, --loss berhu): also report `berhu`, the plain reverse Huber loss on the grid targets
         with this threshold fraction, beside `silog`."""
         from .models import OUT_H, OUT_W
         super().__init__(replica, resolution, ('fine_joint',) if upsample is not None else (), (OUT_H, OUT_W), min_depth,
-                         max_depth, clamp_lo, clamp_hi, keep_predictions)
+                         max_depth, clamp_lo, clamp_hi, keep_predictions, align)
         self.upsample = upsample
         self.t = torch.empty((replica.B, OUT_H, OUT_W), device=replica.device)
         self.silog_ws = {}              # per batch size (a3d_silog_loss_fwd's per-sample sums and partials)
@@ -176,7 +202,8 @@ class DCNFEvaluator(MetricRows):
     outputs = OUTPUTS['dcnf']
 
     def __init__(self, replica, resolution='grid', min_depth=0., max_depth=float('inf'), clamp_lo=1e-3,
-                 clamp_hi=float('inf'), keep_predictions=False, observed_nll=False, upsample=None, condition=None):
+                 clamp_hi=float('inf'), keep_predictions=False, observed_nll=False, upsample=None, condition=None,
+                 align=None):
         """observed_nll (NON-REFERENCE): also the training objective of a run with --min-depth / --max-depth, the
         likelihood of the superpixels that (min_depth, max_depth] leaves observed (DCNFReplica.nll(valid_range=...)); it
         runs last in a batch, after the metrics have read the plainly resized targets.
@@ -186,7 +213,7 @@ class DCNFEvaluator(MetricRows):
         `crf_hidden`, judged over the pixels of the superpixels hidden from the field; it runs last in a batch."""
         super().__init__(replica, resolution, (('crf_joint',) if upsample is not None else ()) +
                          (('crf_cond', 'crf_hidden') if condition is not None else ()), (replica.rows, replica.cols),
-                         min_depth, max_depth, clamp_lo, clamp_hi, keep_predictions)
+                         min_depth, max_depth, clamp_lo, clamp_hi, keep_predictions, align)
         self.upsample, self.condition = upsample, condition
         if condition is not None:
             self.z2_sum, self.z2_n, self.measured, self.rejected = 0.0, 0, 0, 0
@@ -421,6 +448,8 @@ def main(argv=None):
         extra['condition'] = (args.condition, args.condition_seed)
     if args.loss == 'berhu':
         extra['berhu_fraction'] = 0.2 if args.berhu_fraction is None else args.berhu_fraction
+    if args.align != 'none':
+        extra['align'] = args.align
     ev = evaluator(replica, args.resolution, args.min_depth, args.max_depth, args.clamp_lo, args.clamp_hi,
                    keep_predictions=bool(args.predictions), **extra)
     op = EvalOp(pipeline, args.batchsize, dev)
@@ -453,6 +482,8 @@ def main(argv=None):
         out.update(condition=args.condition, condition_seed=args.condition_seed)
     if args.loss == 'berhu':
         out.update(loss='berhu', berhu_fraction=extra['berhu_fraction'])
+    if args.align != 'none':
+        out['align'] = args.align
     if args.predictions:
         np.save(args.predictions, torch.cat(ev.predictions).cpu().numpy() if ev.predictions else
                 np.zeros((0,) + ev.prediction_shape, np.float32))
@@ -460,7 +491,7 @@ def main(argv=None):
     with open(os.path.join(run_dir, f'eval-{step}.json'), 'w') as f:
         json.dump(out, f, indent=1)
     events = summary.EventFileWriter(run_dir)
-    scalars = {f'eval/{o}/{k}': float(v) for o in ev.outputs for k, v in res[o].items()}
+    scalars = {f'eval/{o}/{k}': float(v) for o in ev.outputs + ev.aligned for k, v in res[o].items()}
     if 'condition_z2' in res:
         scalars['eval/condition_z2'] = res['condition_z2']
     if 'crf_nll' in res:
@@ -511,6 +542,8 @@ def parse_args(argv=None):
     p.add_argument('--loss', default='silog', choices=['silog', 'berhu'], help=argparse.SUPPRESS)
     p.add_argument('--berhu-fraction', default=None, type=float, metavar='F', help=argparse.SUPPRESS)
     add_shared_args(p, 'segmentation')
+    # NON-REFERENCE: --align (see the module docstring), kept out of --help for the same reason
+    p.add_argument('--align', default='none', choices=['none'] + list(ops.ALIGN_MODES), help=argparse.SUPPRESS)
     add_upsample_args(p, ['none', 'joint'], 'none',
                       'NON-REFERENCE: joint also judges a third output, fine_joint (msdn) or crf_joint (dcnf): the prediction '
                       'brought to the record image\'s size by joint bilateral upsampling under the image '

@@ -560,32 +560,91 @@ METRIC_COLUMNS = ('n', 'abs_rel', 'sq_rel', 'sq', 'log', 'log_sq', 'log10', 'del
 # A3D_METRIC_* (include/a3d.h): the per-image sums of a3d_depth_metrics, in this column order
 
 
-def depth_metrics(pred, target, *, min_depth=0., max_depth=float('inf'), clamp_lo=1e-3, clamp_hi=float('inf'), rows=None):
+def _depth_pair(what, pred, target):
+    """The argument checks depth_metrics and depth_align share: (n, ph, pw, th, tw)."""
+    n = pred.shape[0]
+    if target.shape[0] != n:
+        raise ValueError(f'{what}: {n} predictions, {target.shape[0]} targets')
+    if pred.dtype != torch.float32 or target.dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f'{what}: pred float32, target float32 or uint8')
+    if not (pred.is_contiguous() and target.is_contiguous()):
+        raise ValueError(f'{what}: contiguous tensors only')
+    ph, pw = pred.shape[1], pred.shape[2]
+    th, tw = target.shape[1], target.shape[2]
+    if pred[0].numel() != ph * pw or target[0].numel() != th * tw:
+        raise ValueError(f'{what}: one channel only')
+    return n, ph, pw, th, tw
+
+
+def _coef_ok(what, coef, n, device):
+    if coef.dtype != torch.float32 or not coef.is_contiguous() or tuple(coef.shape) != (n, 2) or coef.device != device:
+        raise ValueError(f'{what}: coef is float32 [{n}, 2], contiguous, on the tensors\' device')
+
+
+def depth_metrics(pred, target, *, min_depth=0., max_depth=float('inf'), clamp_lo=1e-3, clamp_hi=float('inf'), rows=None,
+                  coef=None):
     """Per-image error sums of Eigen et al. 2014, section 4: pred [n, ph, pw(, 1)] float32 on the model grid; target
     [n, th, tw(, 1)] float32 or the uint8 pixel values of a converter-written record.  A target of another size than the
     prediction is compared at its own pixels, the prediction sampled there as ResizeBilinear (align_corners=False) would
     resample it.  Returns float64 [n, 11] (`rows`, or a new tensor) with the columns of METRIC_COLUMNS; see
-    summarize_depth_metrics for the metrics.  Stream-ordered, no synchronisation."""
-    n = pred.shape[0]
-    if target.shape[0] != n:
-        raise ValueError(f'depth_metrics: {n} predictions, {target.shape[0]} targets')
-    if pred.dtype != torch.float32 or target.dtype not in (torch.float32, torch.uint8):
-        raise TypeError('depth_metrics: pred float32, target float32 or uint8')
-    if not (pred.is_contiguous() and target.is_contiguous()):
-        raise ValueError('depth_metrics: contiguous tensors only')
-    ph, pw = pred.shape[1], pred.shape[2]
-    th, tw = target.shape[1], target.shape[2]
-    if pred[0].numel() != ph * pw or target[0].numel() != th * tw:
-        raise ValueError('depth_metrics: one channel only')
+    summarize_depth_metrics for the metrics.  Stream-ordered, no synchronisation.
+    coef (NON-REFERENCE, include/a3d_align.h): float32 [n, 2] (s, b) per image, as depth_align returns them; the sampled
+    prediction p is judged as fl(fl(s p) + b).  None: the plain a3d_depth_metrics."""
+    n, ph, pw, th, tw = _depth_pair('depth_metrics', pred, target)
     if rows is None:
         rows = torch.empty((n, len(METRIC_COLUMNS)), dtype=torch.float64, device=pred.device)
     assert rows.dtype == torch.float64 and rows.is_contiguous() and rows.shape[0] >= n and rows.shape[1] == len(METRIC_COLUMNS)
     lib = _lib.load()
     need = lib.a3d_depth_metrics_ws_bytes(n, th, tw)
     ws, cap = _ws().get(need, pred.device)
-    check(lib.a3d_depth_metrics(n, ph, pw, _ptr(pred), th, tw, _ptr(target), int(target.dtype == torch.uint8), min_depth,
-                                max_depth, clamp_lo, clamp_hi, _ptr(rows), ws, cap, _stream()), 'a3d_depth_metrics')
+    if coef is None:
+        check(lib.a3d_depth_metrics(n, ph, pw, _ptr(pred), th, tw, _ptr(target), int(target.dtype == torch.uint8), min_depth,
+                                    max_depth, clamp_lo, clamp_hi, _ptr(rows), ws, cap, _stream()), 'a3d_depth_metrics')
+        return rows
+    _coef_ok('depth_metrics', coef, n, pred.device)
+    check(lib.a3da_depth_metrics_aligned(n, ph, pw, _ptr(pred), th, tw, _ptr(target), int(target.dtype == torch.uint8),
+                                         min_depth, max_depth, clamp_lo, clamp_hi, _ptr(coef), _ptr(rows), ws, cap, _stream()),
+          'a3da_depth_metrics_aligned')
     return rows
+
+
+ALIGN_MODES = ('median', 'scale', 'affine')      # A3DA_MEDIAN, A3DA_SCALE, A3DA_AFFINE (include/a3d_align.h), in this order
+
+
+def depth_align(pred, target, mode, *, min_depth=0., max_depth=float('inf')):
+    """NON-REFERENCE (include/a3d_align.h).  Per image, the scale and shift that align pred to target over the pixels
+    depth_metrics sums over (valid target, finite sampled prediction): mode 'median' (s = med t / med p, lower medians),
+    'scale' (least squares, b = 0) or 'affine' (least squares).  pred / target as depth_metrics takes them.  Returns
+    (coef float32 [n, 2], count int32 [n], status int32 [n]); an image that cannot be aligned has coef (1, 0) and status 1.
+    Stream-ordered, no synchronisation."""
+    if mode not in ALIGN_MODES:
+        raise ValueError(f'depth_align: mode {mode!r} is none of {ALIGN_MODES}')
+    n, ph, pw, th, tw = _depth_pair('depth_align', pred, target)
+    coef = torch.empty((n, 2), dtype=torch.float32, device=pred.device)
+    count = torch.empty(n, dtype=torch.int32, device=pred.device)
+    status = torch.empty(n, dtype=torch.int32, device=pred.device)
+    lib = _lib.load()
+    m = ALIGN_MODES.index(mode)
+    need = lib.a3da_depth_align_ws_bytes(n, th, tw, m)
+    ws, cap = _ws().get(need, pred.device)
+    check(lib.a3da_depth_align(n, ph, pw, _ptr(pred), th, tw, _ptr(target), int(target.dtype == torch.uint8), min_depth,
+                               max_depth, m, _ptr(coef), _ptr(count), _ptr(status), ws, cap, _stream()), 'a3da_depth_align')
+    return coef, count, status
+
+
+def affine_apply(x, coef, out=None):
+    """NON-REFERENCE (include/a3d_align.h): out[i] = fl(fl(s_i x[i]) + b_i) for x float32 [n, ...] and coef [n, 2] (s, b) per
+    image; out may be x (None: a new tensor).  Stream-ordered."""
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() < 2 or x[0].numel() == 0:
+        raise ValueError('affine_apply: x is float32 [n, ...], contiguous')
+    n = x.shape[0]
+    _coef_ok('affine_apply', coef, n, x.device)
+    if out is None:
+        out = torch.empty_like(x)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.shape != x.shape or out.device != x.device:
+        raise ValueError('affine_apply: out has x\'s shape, dtype and device')
+    check(_lib.load().a3da_affine_apply(n, x[0].numel(), _ptr(x), _ptr(coef), _ptr(out), _stream()), 'a3da_affine_apply')
+    return out
 
 
 def summarize_depth_metrics(rows):

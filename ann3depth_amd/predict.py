@@ -2,7 +2,7 @@
 
     python -m ann3depth_amd.predict --model msdn|dcnf [--id r1 | --checkpoint PATH] [--superpixel 40|20|10]
         [--precision ...] [--batchsize B] [--upsample joint|bilinear|none] [--radius R --sigma-space S --sigma-range S]
-        [--uncertainty] [--depths DIR --min-depth LO --max-depth HI] --out DIR IMAGE.png ...
+        [--uncertainty] [--depths DIR --min-depth LO --max-depth HI] [--align MODE --align-to DIR] --out DIR IMAGE.png ...
 
 Each image is read with png.imread (8-bit RGB; grey is replicated to three channels, alpha is dropped), consecutive
 images of one size run together in batches of up to B through the replica's predict() on their uint8 pixels, and the
@@ -36,7 +36,17 @@ include/a3d_slic.h; the training driver's three flags, not listed by --help): th
 resized image instead of square blocks.  The crf output is painted onto 240 x 320 by the labels, then --upsample bilinear
 resizes that map to the image's size and --upsample none writes it as it is; the JSON line gains `segmentation`,
 `slic_iters`, `slic_compactness`.  Refused with it, before any GPU work: --upsample joint (the default: name bilinear or
-none), --uncertainty, --depths."""
+none), --uncertainty, --depths.
+
+--align median|scale|affine --align-to DIR (NON-REFERENCE, both models, every --upsample; include/a3d_align.h; both flags
+or neither): the models predict in the training data's normalised units, depth up to an affine map per image.  DIR/<stem>.npy,
+float32 [H, W] of any size, holds a few measured depths (a sparse LiDAR or Kinect map; a pixel is measured where it is finite
+and inside (--min-depth, --max-depth]).  Each map at its output size is sampled at the measured map's pixels, the scale and
+shift of ops.depth_align are fitted over the measured ones, and the map is written as s * map + b (ops.affine_apply); a
+-sigma map is scaled by |s| alone.  Each entry of `files` gains `scale`, `shift`, `measured` (the pixels fitted on) and
+`aligned` (false: the fit was refused, e.g. nothing measured, and the map is written as it is); the JSON line gains `align`,
+`min_depth`, `max_depth`.  Exit code 2 before any GPU work: one flag without the other, --align-to with --depths (the
+conditioned field already uses the measurements), a missing or unusable file, --min-depth >= --max-depth."""
 import argparse
 import json
 import os
@@ -123,6 +133,15 @@ def main(argv=None):
     if args.depths and not (args.min_depth < args.max_depth):
         _say(f'--depths needs --min-depth < --max-depth (a pixel is measured inside ({args.min_depth}, {args.max_depth}]).')
         return 2
+    if (args.align != 'none') != bool(args.align_to):
+        _say('--align MODE and --align-to DIR go together: the mode of the fit, and the measured depth maps it is fitted to.')
+        return 2
+    if args.align_to and args.depths:
+        _say('--align-to cannot go with --depths: the conditioned field already uses the measurements.')
+        return 2
+    if args.align_to and not (args.min_depth < args.max_depth):
+        _say(f'--align-to needs --min-depth < --max-depth (a pixel is measured inside ({args.min_depth}, {args.max_depth}]).')
+        return 2
 
     def no_images():
         if not args.images:
@@ -154,6 +173,16 @@ def main(argv=None):
             except Exception as e:                    # a missing file, a pickle, a text file, another rank or dtype
                 _say(f'--depths: cannot use {path}: {e}')
                 return 2
+    fit_to = None
+    if args.align_to:
+        fit_to = []
+        for stem in stems:
+            path = os.path.join(args.align_to, stem + '.npy')
+            try:
+                fit_to.append(read_depth(path))
+            except Exception as e:
+                _say(f'--align-to: cannot use {path}: {e}')
+                return 2
     restored = restore_replica(args, ckpt, _say)
     if restored is None:
         return 2
@@ -172,7 +201,7 @@ def main(argv=None):
                                            torch.empty((n, H, W, 1), device=dev)).view(n, H, W)
         return grid[:n]
 
-    for idx in batches(images, args.batchsize, measured):
+    for idx in batches(images, args.batchsize, measured if fit_to is None else fit_to):
         n = len(idx)
         pixels = torch.from_numpy(np.stack([images[i] for i in idx])).to(dev)
         pred = replica.predict(pixels, n)[1]                       # fine (msdn) or crf (dcnf), [B, gh, gw]
@@ -193,14 +222,31 @@ def main(argv=None):
             if holes is not None:
                 pred = mean                                # without --depths the depth map stays predict()'s, byte for byte
             if var is not None:
-                sigma = to_size(torch.sqrt(var), pixels, n).cpu().numpy()
-        full = to_size(pred, pixels, n).cpu().numpy()
+                sigma = to_size(torch.sqrt(var), pixels, n)
+        full = to_size(pred, pixels, n)
+        fit = None
+        if fit_to is not None:                         # the maps at output size, sampled at the measured maps' pixels
+            coef, count, status = ops.depth_align(full, torch.from_numpy(np.stack([fit_to[i] for i in idx])).to(dev),
+                                                  args.align, min_depth=args.min_depth, max_depth=args.max_depth)
+            full = full.contiguous()
+            ops.affine_apply(full, coef, out=full)         # in place
+            if sigma is not None:
+                by_scale = torch.stack([coef[:, 0].abs(), torch.zeros_like(coef[:, 0])], 1).contiguous()
+                sigma = sigma.contiguous()
+                ops.affine_apply(sigma, by_scale, out=sigma)
+            fit = (coef.cpu().numpy(), count.cpu().numpy(), status.cpu().numpy())
+        full = full.cpu().numpy()
+        if sigma is not None:
+            sigma = sigma.cpu().numpy()
         for k, i in enumerate(idx):
             base = os.path.join(args.out, stems[i] + '-depth')
             np.save(base + '.npy', full[k])
             png.imsave(base + '.png', depth_png(full[k]))
             files.append({'image': args.images[i], 'image_size': [int(H), int(W)], 'npy': base + '.npy', 'png': base + '.png',
                           'size': [int(v) for v in full[k].shape], 'nonfinite': int((~np.isfinite(full[k])).sum())})
+            if fit is not None:
+                files[-1].update(scale=float(fit[0][k, 0]), shift=float(fit[0][k, 1]), measured=int(fit[1][k]),
+                                 aligned=bool(fit[2][k] == 0))
             if sigma is not None:
                 base = os.path.join(args.out, stems[i] + '-sigma')
                 np.save(base + '.npy', sigma[k])
@@ -220,6 +266,8 @@ def main(argv=None):
                    observed_fraction=observed / float(len(images) * replica.nsp), rejected_systems=rejected)
         if measured is not None:
             out.update(min_depth=args.min_depth, max_depth=args.max_depth)
+    if fit_to is not None:
+        out.update(align=args.align, min_depth=args.min_depth, max_depth=args.max_depth)
     print(json.dumps(out), flush=True)
     return 0
 
@@ -240,6 +288,10 @@ def parse_args(argv=None):
                         'map with holes; the field is conditioned on the superpixels it measures.')
     p.add_argument('--min-depth', default=0., type=float, help='--depths: a pixel is measured if its value is > this ...')
     p.add_argument('--max-depth', default=float('inf'), type=float, help='... and <= this, and finite.')
+    # NON-REFERENCE: --align MODE --align-to DIR (see the module docstring).  Kept out of --help: this driver's help text is
+    # recorded word for word (tests/golden/predict_help.txt).
+    p.add_argument('--align', default='none', choices=['none'] + list(ops.ALIGN_MODES), help=argparse.SUPPRESS)
+    p.add_argument('--align-to', default='', type=str, metavar='DIR', help=argparse.SUPPRESS)
     add_upsample_args(p, ['joint', 'bilinear', 'none'], 'joint',
                       'How the prediction reaches the image\'s size: joint (NON-REFERENCE: joint bilateral upsampling under '
                       'the image), bilinear (the legacy resize), none (it stays on the model\'s grid).')

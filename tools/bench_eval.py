@@ -5,7 +5,13 @@ metrics) on a synthetic converter-written test shard, as a fraction of the resid
 With `dcnf` as the second argument, the same for DCNF at batch 16 (BASELINE config 4's batch): DCNFReplica.predict, its
 parts that are not the unary stack (ops.crf_map alone, at 16 and 64 images, and the pairwise features), the objective,
 and the loop end to end.
-    python tools/bench_eval.py 320 dcnf > profiles/bench_eval_dcnf.json"""
+    python tools/bench_eval.py 320 dcnf > profiles/bench_eval_dcnf.json
+With `--align MODE` (median, scale, affine or all; include/a3d_align.h) instead: the align launches and
+a3da_depth_metrics_aligned beside a3d_depth_metrics on the same inputs, batch 32, targets 55 x 74 and 480 x 640, in rounds
+that alternate the calls; `--parent-lib PATH` adds the a3d_depth_metrics of another build of liba3d.so (the parent commit's)
+to every round and says whether this build's median lies inside that build's own spread.
+    python tools/bench_eval.py --align all --parent-lib ../parent/ann3depth_amd/liba3d.so > profiles/bench_eval_align.json"""
+import ctypes
 import json
 import os
 import sys
@@ -111,7 +117,76 @@ def main_dcnf(n_records):
     print(json.dumps(out))
 
 
+def main_align(mode, parent_path, rounds=9, iters=200):
+    from ann3depth_amd import _lib
+    B = 32
+    rng = np.random.default_rng(0)
+    lib = _lib.load()
+    parent = None
+    if parent_path:
+        parent = ctypes.CDLL(parent_path)
+        for name in ('a3d_depth_metrics_ws_bytes', 'a3d_depth_metrics'):
+            getattr(parent, name).restype, getattr(parent, name).argtypes = _lib.SIGNATURES[name]
+    modes = ops.ALIGN_MODES if mode == 'all' else (mode,)
+    pred = torch.from_numpy(rng.uniform(0.1, 9, (B, 55, 74)).astype(np.float32)).cuda()
+    cases = {'grid_f32': torch.from_numpy(rng.uniform(0.1, 9, (B, 55, 74)).astype(np.float32)).cuda(),
+             'record_u8': torch.from_numpy(rng.integers(0, 256, (B, 480, 640)).astype(np.uint8)).cuda(),
+             'record_f32': torch.from_numpy(rng.uniform(0.1, 9, (B, 480, 640)).astype(np.float32)).cuda()}
+    rows = {k: torch.zeros((B, len(ops.METRIC_COLUMNS)), dtype=torch.float64, device='cuda') for k in ('parent', 'plain', 'aligned')}
+    coef = torch.empty((B, 2), dtype=torch.float32, device='cuda')
+    count = torch.empty(B, dtype=torch.int32, device='cuda')
+    status = torch.empty(B, dtype=torch.int32, device='cuda')
+    ws = torch.empty(64 << 20, dtype=torch.uint8, device='cuda')
+    P, stream = ops._ptr, ops._stream
+    out = {'device': torch.cuda.get_device_name(0), 'batch': B, 'rounds': rounds, 'iters_per_round': iters,
+           'unit': 'microseconds per call, events around back-to-back calls; median [min, max] over the rounds',
+           'parent_lib': bool(parent)}
+
+    def stats(v):
+        return {'median': round(float(np.median(v)), 2), 'min': round(min(v), 2), 'max': round(max(v), 2)}
+
+    for name, tgt in cases.items():
+        th, tw = tgt.shape[1:]
+        head = (B, 55, 74, P(pred), th, tw, P(tgt), int(tgt.dtype == torch.uint8), 0.0, float('inf'))
+
+        def metrics(l, r):
+            return lambda: ops.check(l.a3d_depth_metrics(*head, 1e-3, float('inf'), P(r), P(ws), ws.numel(), stream()), 'metrics')
+
+        def aligned():
+            ops.check(lib.a3da_depth_metrics_aligned(*head, 1e-3, float('inf'), P(coef), P(rows['aligned']), P(ws), ws.numel(),
+                                                     stream()), 'aligned')
+
+        def align(m):
+            return lambda: ops.check(lib.a3da_depth_align(*head, m, P(coef), P(count), P(status), P(ws), ws.numel(), stream()),
+                                     'align')
+        calls = {'depth_metrics': metrics(lib, rows['plain']), 'depth_metrics_aligned': aligned}
+        if parent is not None:
+            calls = {'parent_depth_metrics': metrics(parent, rows['parent']), **calls}
+        calls.update({f'depth_align_{m}': align(ops.ALIGN_MODES.index(m)) for m in modes})
+        align(ops.ALIGN_MODES.index(modes[-1]))()                      # coefficients for the aligned launch
+        us = {k: [] for k in calls}
+        for _ in range(rounds):
+            for k, fn in calls.items():
+                us[k].append(timed(fn, iters=iters, warmup=10) * 1e3)
+        res = {k: stats(v) for k, v in us.items()}
+        if parent is not None:
+            torch.cuda.synchronize()
+            res['same_bits_as_parent'] = bool(torch.equal(rows['plain'].view(torch.int64), rows['parent'].view(torch.int64)))
+            lo, hi = res['parent_depth_metrics']['min'], res['parent_depth_metrics']['max']
+            res['plain_median_inside_parent_spread'] = bool(lo <= res['depth_metrics']['median'] <= hi)
+        for m in modes:
+            res[f'depth_align_{m}_over_depth_metrics'] = round(res[f'depth_align_{m}']['median'] / res['depth_metrics']['median'], 2)
+        out[name] = res
+    print(json.dumps(out))
+
+
 def main():
+    if '--align' in sys.argv:
+        mode = sys.argv[sys.argv.index('--align') + 1]
+        if mode not in ops.ALIGN_MODES + ('all',):
+            sys.exit(f'--align {mode}: one of {ops.ALIGN_MODES + ("all",)}')
+        parent = sys.argv[sys.argv.index('--parent-lib') + 1] if '--parent-lib' in sys.argv else ''
+        return main_align(mode, parent)
     n_records = int(sys.argv[1]) if len(sys.argv) > 1 else 320
     if len(sys.argv) > 2 and sys.argv[2] == 'dcnf':
         return main_dcnf(n_records)
