@@ -34,7 +34,7 @@ inline unsigned grid_for(size_t total, int per_block = 256, unsigned cap = 8192)
   return (unsigned)std::min<size_t>(std::max<size_t>(g, 1), cap);
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+__host__ __device__ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // ---- implicit-GEMM launch layer (igemm_launch.hip) under the front end (igemm_host.hip); the planner: igemm_plan.h, igemm_plan.cc ----
 struct IgemmParams;

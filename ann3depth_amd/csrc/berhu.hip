@@ -1,77 +1,37 @@
 // berhu.hip — the reverse Huber loss on linear depth, NON-REFERENCE (include/a3d_berhu.h, --loss berhu): L1 up to a threshold
 // taken from each sample's own largest error, quadratic beyond it.  Three launches on the step's critical path: the
-// per-sample maxima, the sums, the gradient.  The two forward launches keep the structure of pointwise.hip's silog kernels:
-// A3D_SILOG_PARTS blocks per sample, wavefront-shuffle reductions, partials that cross CUs as write-through stores drained
-// before an integer ticket, and the block that arrives last adds the parts in part order.  No block waits for another.
-// Compiled with -ffp-contract=off like pointwise.hip: every rounding the header names is a rounding of its own.
+// per-sample maxima, the sums, the gradient.  The two forward launches are built from loss_common.h like the silog kernels:
+// A3D_SILOG_PARTS blocks per sample (chunks rounded up to 4 pixels), the block reduction, the hand-off to the block that
+// arrives last, which folds the parts in part order.  No block waits for another.
+// Compiled with -ffp-contract=off: every rounding include/a3d_berhu.h names is a rounding of its own.
 // The kernels stream 2 x 4 bytes per pixel (the backward writes 4 to 6 more): 16-byte accesses where the addresses allow.
 // -Rpass-analysis=kernel-resource-usage (gfx950, ROCm 7.2), plain / masked:
-//   berhu_max_kernel             VGPRs 27 / 34, SGPRs 32 / 36, scratch 0, LDS 52 bytes
-//   berhu_sum_kernel             VGPRs 32 / 36, SGPRs 38 / 42, scratch 0, LDS 36 bytes
+//   berhu_max_kernel             VGPRs 28 / 37, SGPRs 32 / 36, scratch 0, LDS 52 bytes
+//   berhu_sum_kernel             VGPRs 36 / 40, SGPRs 38 / 42, scratch 0, LDS 36 bytes
 //   berhu_bwd_kernel, 16 bytes   VGPRs 28 / 40, SGPRs 58 / 58, scratch 0, LDS 0
 //   berhu_bwd_kernel, 4 bytes    VGPRs 20 / 28, SGPRs 44 / 45, scratch 0, LDS 0
+// all at 8 waves per SIMD.
 #include "a3d_internal.h"
-#include "silog_common.h"
+#include "loss_common.h"
 #include "../../include/a3d_berhu.h"
 
 namespace a3d {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kBerhuK = 3;                      // per sample: c, n, poison; per block: max / count / poison, then S / nq
 constexpr int kBerhuRound = 4 * 256;            // pixels of one round of a block's walk over its chunk
-
-__device__ __forceinline__ bool on16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-__device__ __forceinline__ int berhu_chunk(int npix) { return ((npix + kSilogParts - 1) / kSilogParts + 3) & ~3; }
-
-// pixels [i, i + 4) of a row, i a multiple of 4: one 16-byte load where the row starts on a 16-byte address and all four lie
-// below hi, one by one otherwise (what lies at or past hi reads as 0 and is never used)
-__device__ __forceinline__ void load4(const float* __restrict__ row, int i, int hi, bool vec, float (&v)[4]) {
-  if (vec && i + 4 <= hi) {
-    const f32x4 q = *reinterpret_cast<const f32x4*>(row + i);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = i + u < hi ? row[i + u] : 0.f;
-  }
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_down(v, off, 64));
-  return v;
-}
-
-// lane 0 of the block publishes its three partials and takes a ticket; true in the block that arrived last
-__device__ __forceinline__ bool berhu_arrive(float* __restrict__ ws, float* __restrict__ partials, int nb, float p0, float p1,
-                                             float p2, unsigned* last) {
-  if (threadIdx.x == 0) {
-    const unsigned total = (unsigned)(nb * kSilogParts);
-    __hip_atomic_store(&partials[kBerhuK * blockIdx.x], p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&partials[kBerhuK * blockIdx.x + 1], p1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&partials[kBerhuK * blockIdx.x + 2], p2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    *last = atomicInc(reinterpret_cast<unsigned*>(ws), total - 1u) == total - 1u;
-  }
-  __syncthreads();
-  return *last != 0u;
-}
 
 // First forward launch: block (b, part) leaves the largest |o - t| of its chunk's counting pixels, their number and whether
 // one of them is not finite; the last block writes c, n and the poison flag of every sample to ws[1 + 3 b ..].
 template <bool MASKED>
 __global__ __launch_bounds__(256) void berhu_max_kernel(const float* __restrict__ out, const float* __restrict__ tgt,
                                                         float* __restrict__ ws, int npix, int nb, float fraction) {
+  constexpr int K = kBerhuK;
   __shared__ float red[3][4];
-  __shared__ unsigned last;
-  const int b = blockIdx.x / kSilogParts, part = blockIdx.x % kSilogParts;
-  const int chunk = berhu_chunk(npix);
-  const int lo = min(npix, part * chunk), hi = min(npix, lo + chunk);
+  const auto [b, lo, hi] = loss_part<true>(npix);
   const float* o = out + (size_t)b * npix;
   const float* t = tgt + (size_t)b * npix;
-  const bool ovec = on16(o), tvec = on16(t);
-  float* partials = ws + kBerhuK * nb + 1;
+  const bool ovec = aligned16(o), tvec = aligned16(t);
+  float* partials = ws + K * nb + 1;
   float mx = 0.f, cnt = 0.f, bad = 0.f;
   for (int i0 = lo + 4 * threadIdx.x; i0 < hi; i0 += kBerhuRound) {
     float ov[4], tv[4];
@@ -91,30 +51,19 @@ __global__ __launch_bounds__(256) void berhu_max_kernel(const float* __restrict_
   }
   mx = wave_max(mx);
   bad = wave_max(bad);
-  if constexpr (MASKED) cnt = wave_sum(cnt);            // whole numbers below 2^24: exact in any order
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = mx;
-    red[1][threadIdx.x >> 6] = cnt;
-    red[2][threadIdx.x >> 6] = bad;
-  }
+  if constexpr (MASKED) cnt = wave_sum(cnt);            // whole numbers below 2^24: exact in any order; unmasked: zeros
+  block_put(red[0], mx);
+  block_put(red[1], cnt);
+  block_put(red[2], bad);
   __syncthreads();
-  const bool is_last = berhu_arrive(ws, partials, nb, fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3])),
-                                    red[1][0] + red[1][1] + red[1][2] + red[1][3],
-                                    fmaxf(fmaxf(red[2][0], red[2][1]), fmaxf(red[2][2], red[2][3])), &last);
-  if (!is_last || threadIdx.x >= 64) return;
+  constexpr unsigned kMaxes = (1u << 0) | (1u << 2);
+  if (!publish_and_arrive<K, kMaxes, 0>(ws, partials, nb, red) || threadIdx.x >= 64) return;
   for (int i = threadIdx.x; i < nb; i += 64) {
-    float m = 0.f, n = 0.f, p = 0.f;
-#pragma unroll
-    for (int q = 0; q < kSilogParts; ++q) {
-      const float* pp = &partials[kBerhuK * (i * kSilogParts + q)];
-      m = fmaxf(m, __hip_atomic_load(pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      n += __hip_atomic_load(pp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      p = fmaxf(p, __hip_atomic_load(pp + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    }
-    if constexpr (!MASKED) n = (float)npix;
-    ws[1 + kBerhuK * i] = p != 0.f ? __builtin_nanf("") : __fmul_rn(fraction, m);
-    ws[2 + kBerhuK * i] = n;
-    ws[3 + kBerhuK * i] = p;
+    const float m = fold_parts<K, float, true>(partials, i, 0), poison = fold_parts<K, float, true>(partials, i, 2);
+    const float n = MASKED ? fold_parts<K>(partials, i, 1) : (float)npix;
+    ws[1 + K * i] = poison != 0.f ? __builtin_nanf("") : __fmul_rn(fraction, m);
+    ws[2 + K * i] = n;
+    ws[3 + K * i] = poison;
   }
 }
 
@@ -124,16 +73,14 @@ __global__ __launch_bounds__(256) void berhu_max_kernel(const float* __restrict_
 template <bool MASKED>
 __global__ __launch_bounds__(256) void berhu_sum_kernel(const float* __restrict__ out, const float* __restrict__ tgt,
                                                         float* __restrict__ ws, float* __restrict__ loss, int npix, int nb) {
-  __shared__ float red[2][4];
-  __shared__ unsigned last;
-  const int b = blockIdx.x / kSilogParts, part = blockIdx.x % kSilogParts;
-  const int chunk = berhu_chunk(npix);
-  const int lo = min(npix, part * chunk), hi = min(npix, lo + chunk);
+  constexpr int K = kBerhuK;
+  __shared__ float red[2][4];                           // S and nq; the third word of a block's partials is stored as 0
+  const auto [b, lo, hi] = loss_part<true>(npix);
   const float* o = out + (size_t)b * npix;
   const float* t = tgt + (size_t)b * npix;
-  const bool ovec = on16(o), tvec = on16(t);
-  float* partials = ws + kBerhuK * nb + 1;
-  const float c = ws[1 + kBerhuK * b];
+  const bool ovec = aligned16(o), tvec = aligned16(t);
+  float* partials = ws + K * nb + 1;
+  const float c = ws[1 + K * b];
   const float cc = __fmul_rn(c, c), c2 = __fmul_rn(2.f, c);
   float s = 0.f, nq = 0.f;
   for (int i0 = lo + 4 * threadIdx.x; i0 < hi; i0 += kBerhuRound) {
@@ -157,30 +104,21 @@ __global__ __launch_bounds__(256) void berhu_sum_kernel(const float* __restrict_
   }
   s = wave_sum(s);
   nq = wave_sum(nq);                                    // whole numbers below 2^24: exact in any order
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = s;
-    red[1][threadIdx.x >> 6] = nq;
-  }
+  block_put(red[0], s);
+  block_put(red[1], nq);
   __syncthreads();
-  const bool is_last = berhu_arrive(ws, partials, nb, ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3],
-                                    red[1][0] + red[1][1] + red[1][2] + red[1][3], 0.f, &last);
-  if (!is_last || threadIdx.x >= 64) return;
+  if (!publish_and_arrive<K, 0, 0>(ws, partials, nb, red) || threadIdx.x >= 64) return;
   float sum_per = 0.f, sum_c = 0.f, poisoned = 0.f;
   double sum_n = 0.0, sum_q = 0.0;
   for (int base = 0; base < nb; base += 64) {
     const int i = base + threadIdx.x;
     float per = 0.f, ci = 0.f, ni = 0.f, qi = 0.f, pi = 0.f;
     if (i < nb) {
-      float as = 0.f;
-#pragma unroll
-      for (int q = 0; q < kSilogParts; ++q) {
-        const float* pp = &partials[kBerhuK * (i * kSilogParts + q)];
-        as += __hip_atomic_load(pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        qi += __hip_atomic_load(pp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      ci = ws[1 + kBerhuK * i];
-      ni = ws[2 + kBerhuK * i];
-      pi = ws[3 + kBerhuK * i];
+      const float as = fold_parts<K>(partials, i, 0);
+      qi = fold_parts<K>(partials, i, 1);
+      ci = ws[1 + K * i];
+      ni = ws[2 + K * i];
+      pi = ws[3 + K * i];
       if (ni > 0.f) per = __fmul_rn(MASKED ? (float)((double)npix / (double)ni) : 1.f, as);
     }
     const int live = min(64, nb - base);
@@ -250,7 +188,7 @@ __global__ __launch_bounds__(256) void berhu_bwd_kernel(const float* __restrict_
         }
         const float g = berhu_grad(ov[u], tv[u], c, s, !MASKED || isfinite(tv[u]), ws[3 + kBerhuK * smp] != 0.f);
         gv[u] = g;
-        if (dout16) dout16[(size_t)smp * ld16 + col] = (__bf16)g;
+        write_grad16(dout16, ld16, smp, col, g);
         if (++col == npix) {
           col = 0;
           ++smp;
@@ -269,15 +207,6 @@ __global__ __launch_bounds__(256) void berhu_bwd_kernel(const float* __restrict_
   }
 }
 
-static int berhu_check(const char* who, int b, int npix, bool pointers, int masked, float fraction) {
-  A3D_CHECK_ARG(pointers, "%s: a NULL pointer", who);
-  A3D_CHECK_ARG(b > 0 && npix > 0, "%s: a batch of %d samples of %d pixels: both must be positive", who, b, npix);
-  A3D_CHECK_ARG(npix <= (1 << 24), "%s: %d pixels per sample, the counts are kept in floats", who, npix);
-  A3D_CHECK_ARG(masked == 0 || masked == 1, "%s: masked = %d is neither 0 nor 1", who, masked);
-  A3D_CHECK_ARG(fraction > 0.f && fraction <= 1.f, "%s: a threshold fraction of %g, outside (0, 1]", who, (double)fraction);
-  return A3D_OK;
-}
-
 }  // namespace a3d
 using namespace a3d;
 
@@ -285,37 +214,31 @@ extern "C" {
 
 int a3dh_berhu_loss_fwd(int b, int npix, const float* out, const float* tgt, int masked, float fraction, float* loss, float* ws,
                         void* stream) {
-  if (int rc = berhu_check("berhu_fwd", b, npix, out && tgt && loss && ws, masked, fraction)) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = loss_check("berhu_fwd", b, npix, out && tgt && loss && ws, true)) return rc;
+  A3D_CHECK_ARG(masked == 0 || masked == 1, "berhu_fwd: masked = %d is neither 0 nor 1", masked);
+  A3D_CHECK_ARG(fraction > 0.f && fraction <= 1.f, "berhu_fwd: a threshold fraction of %g, outside (0, 1]", (double)fraction);
   clear_stale_error();
-  if (masked) {
-    hipLaunchKernelGGL(berhu_max_kernel<true>, dim3(b * kSilogParts), dim3(256), 0, st, out, tgt, ws, npix, b, fraction);
-    hipLaunchKernelGGL(berhu_sum_kernel<true>, dim3(b * kSilogParts), dim3(256), 0, st, out, tgt, ws, loss, npix, b);
-  } else {
-    hipLaunchKernelGGL(berhu_max_kernel<false>, dim3(b * kSilogParts), dim3(256), 0, st, out, tgt, ws, npix, b, fraction);
-    hipLaunchKernelGGL(berhu_sum_kernel<false>, dim3(b * kSilogParts), dim3(256), 0, st, out, tgt, ws, loss, npix, b);
-  }
+  launch_masked(masked, berhu_max_kernel<false>, berhu_max_kernel<true>, b * kSilogParts, stream, out, tgt, ws, npix, b, fraction);
+  launch_masked(masked, berhu_sum_kernel<false>, berhu_sum_kernel<true>, b * kSilogParts, stream, out, tgt, ws, loss, npix, b);
   return check_launch("berhu_fwd");
 }
 
 int a3dh_berhu_loss_bwd_ex(int b, int npix, const float* out, const float* tgt, int masked, float fraction, const float* ws,
                            float* dout, void* dout_bf16, int ld_bf16, void* stream) {
-  if (int rc = berhu_check("berhu_bwd", b, npix, out && tgt && ws && dout, masked, fraction)) return rc;
-  A3D_CHECK_ARG(!dout_bf16 || ld_bf16 >= npix, "berhu_bwd: a bf16 pitch of %d below %d pixels", ld_bf16, npix);
+  if (int rc = loss_check("berhu_bwd", b, npix, out && tgt && ws && dout, true, dout_bf16, ld_bf16)) return rc;
+  A3D_CHECK_ARG(masked == 0 || masked == 1, "berhu_bwd: masked = %d is neither 0 nor 1", masked);
+  A3D_CHECK_ARG(fraction > 0.f && fraction <= 1.f, "berhu_bwd: a threshold fraction of %g, outside (0, 1]", (double)fraction);
   const size_t total = (size_t)b * npix;
   const bool vec = aligned16(out) && aligned16(tgt) && aligned16(dout);
-  const unsigned grid = grid_for(vec ? (total + 3) / 4 : total);
   const float inv_b = 1.0f / (float)b;
   __bf16* d16 = static_cast<__bf16*>(dout_bf16);
-  hipStream_t st = static_cast<hipStream_t>(stream);
   clear_stale_error();
-  if (masked) {
-    if (vec) hipLaunchKernelGGL((berhu_bwd_kernel<true, true>), dim3(grid), dim3(256), 0, st, out, tgt, ws, dout, b, npix, inv_b, d16, ld_bf16);
-    else hipLaunchKernelGGL((berhu_bwd_kernel<true, false>), dim3(grid), dim3(256), 0, st, out, tgt, ws, dout, b, npix, inv_b, d16, ld_bf16);
-  } else {
-    if (vec) hipLaunchKernelGGL((berhu_bwd_kernel<false, true>), dim3(grid), dim3(256), 0, st, out, tgt, ws, dout, b, npix, inv_b, d16, ld_bf16);
-    else hipLaunchKernelGGL((berhu_bwd_kernel<false, false>), dim3(grid), dim3(256), 0, st, out, tgt, ws, dout, b, npix, inv_b, d16, ld_bf16);
-  }
+  if (vec)
+    launch_masked(masked, berhu_bwd_kernel<false, true>, berhu_bwd_kernel<true, true>, grid_for((total + 3) / 4), stream, out, tgt,
+                  ws, dout, b, npix, inv_b, d16, ld_bf16);
+  else
+    launch_masked(masked, berhu_bwd_kernel<false, false>, berhu_bwd_kernel<true, false>, grid_for(total), stream, out, tgt, ws,
+                  dout, b, npix, inv_b, d16, ld_bf16);
   return check_launch("berhu_bwd");
 }
 

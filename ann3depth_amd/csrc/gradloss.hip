@@ -1,30 +1,31 @@
 // gradloss.hip — the scale-invariant log loss with the gradient-matching term of Eigen & Fergus 2015 (eq. 4), NON-REFERENCE
 // (include/a3d_gradloss.h, --loss-gradient): sum over the horizontal and vertical neighbour pairs of (d_j - d_i)^2 beside the
-// per-sample term of pointwise.hip's silog kernels, in the same two launches — both sit on the step's critical path.
-// Compiled with -ffp-contract=off like pointwise.hip: every rounding the header names is a rounding of its own, and d, s2, s1
-// and n come out of the same operations in the same order as there (silog_common.h), so that the silog part of the loss and,
-// with grad_weight = 0, the gradient are the bits of the plain / masked kernels.
+// per-sample silog term, in the same two launches — both sit on the step's critical path.  The parts, the block reduction, the
+// hand-off to the block that arrives last and the silog arithmetic are loss_common.h's, which pointwise.hip's plain and masked
+// silog kernels use too: d, s2, s1 and n come out of the same operations in the same order, so that the silog part of the
+// loss and, with grad_weight = 0, the gradient are the bits of those kernels.
+// Compiled with -ffp-contract=off: every rounding include/a3d_gradloss.h names is a rounding of its own.
 #include "a3d_internal.h"
-#include "silog_common.h"
+#include "loss_common.h"
 #include "../../include/a3d_gradloss.h"
 
 namespace a3d {
 
 constexpr int kGradK = 5;                      // s2, s1, n, sg, m per block and per sample
-constexpr int kGradRound = 4 * 256;            // pixels of one round of the block's walk over its chunk (silog_fwd_kernel's)
+constexpr int kGradRound = 4 * 256;            // pixels of one round of the block's walk over its chunk (the silog kernels')
 constexpr int kGradRing = 4096;                // power of two >= kGradRound + A3DG_MAX_W
 constexpr int kGradTile = 8192;                // values of d a backward block stages: at least 3 rows of A3DG_MAX_W
 constexpr int kGradGrid = 4096;                // blocks of the backward launch at most (40 KB of LDS each: ~4 resident per CU); the rest by grid stride
 static_assert(kGradRing >= kGradRound + A3DG_MAX_W && (kGradRing & (kGradRing - 1)) == 0, "forward window");
 static_assert(kGradTile >= 3 * A3DG_MAX_W, "backward tile");
 
-// Block (b, part) walks its chunk [lo, hi) of the sample in rounds of 1024 pixels with silog_fwd_kernel's thread-to-pixel
-// mapping, and owns the pairs whose FIRST pixel lies in the chunk.  The second pixel lies up to w further on, possibly several
+// Block (b, part) walks its chunk [lo, hi) of the sample in rounds of 1024 pixels with the silog kernels' thread-to-pixel
+// mapping (i0 + u * 256), and owns the pairs whose FIRST pixel lies in the chunk.  The second pixel lies up to w further on, possibly several
 // chunks away: before a round the block brings d over [round start, round end + w) — what is not there yet, so one logarithm
 // pair per pixel of chunk + halo — from global memory into a ring in LDS (the window is at most 1024 + w <= kGradRing values;
 // a slot is overwritten only by a pixel kGradRing further on, which lies behind the round).  Then every thread takes its four
-// pixels of the round from the ring: s2, s1, n exactly as silog_fwd_kernel adds them, and the pair right of and the pair below
-// each pixel.  Five partials per block; stores, drain, ticket and last block as in silog_fwd_kernel.
+// pixels of the round from the ring: s2, s1, n exactly as the silog kernels add them, and the pair right of and the pair below
+// each pixel.  Five partials per block (unmasked, n = npix and m = M are not counted and words 2 and 4 not published).
 template <bool MASKED>
 __global__ __launch_bounds__(256) void gradloss_fwd_kernel(const float* __restrict__ out, const float* __restrict__ tgt,
                                                            float* __restrict__ ws, float* __restrict__ loss, int h, int w, int nb,
@@ -33,11 +34,8 @@ __global__ __launch_bounds__(256) void gradloss_fwd_kernel(const float* __restri
   __shared__ float dring[kGradRing];
   __shared__ unsigned char cring[MASKED ? kGradRing : 4];      // 1: the pixel counts
   __shared__ float red[K][4];
-  __shared__ unsigned last;
   const int npix = h * w;
-  const int b = blockIdx.x / kSilogParts, part = blockIdx.x % kSilogParts;
-  const int chunk = (npix + kSilogParts - 1) / kSilogParts;
-  const int lo = part * chunk, hi = min(npix, lo + chunk);
+  const auto [b, lo, hi] = loss_part<false>(npix);
   const float* o = out + (size_t)b * npix;
   const float* t = tgt + (size_t)b * npix;
   float* partials = ws + K * nb + 1;
@@ -103,54 +101,26 @@ __global__ __launch_bounds__(256) void gradloss_fwd_kernel(const float* __restri
   s2 = wave_sum(s2);
   s1 = wave_sum(s1);
   sg = wave_sum(sg);
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = s2;
-    red[1][threadIdx.x >> 6] = s1;
-    red[3][threadIdx.x >> 6] = sg;
-  }
+  block_put(red[0], s2);
+  block_put(red[1], s1);
+  block_put(red[3], sg);
   if constexpr (MASKED) {
     cnt = wave_sum(cnt);            // whole numbers below 2^24: exact in any order
     mp = wave_sum(mp);
-    if ((threadIdx.x & 63) == 0) {
-      red[2][threadIdx.x >> 6] = cnt;
-      red[4][threadIdx.x >> 6] = mp;
-    }
+    block_put(red[2], cnt);
+    block_put(red[4], mp);
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned total = (unsigned)(nb * kSilogParts);
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      if (!MASKED && (k == 2 || k == 4)) continue;      // n = npix and m = M: nothing to count
-      __hip_atomic_store(&partials[K * blockIdx.x + k], red[k][0] + red[k][1] + red[k][2] + red[k][3], __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    last = atomicInc(reinterpret_cast<unsigned*>(ws), total - 1u) == total - 1u;
-  }
-  __syncthreads();
-  if (!last || threadIdx.x >= 64) return;
+  constexpr unsigned kNotCounted = MASKED ? 0u : (1u << 2) | (1u << 4);      // n = npix and m = M: nothing to count
+  if (!publish_and_arrive<K, 0, kNotCounted>(ws, partials, nb, red) || threadIdx.x >= 64) return;
   const double pairs = (double)h * (double)(w - 1) + (double)(h - 1) * (double)w;      // M
   float s = 0.f, sgrad = 0.f;
   double valid = 0.0;
   for (int i = threadIdx.x; i < nb; i += 64) {
-    float a2 = 0.f, a1 = 0.f, an = 0.f, ag = 0.f;
-    double am = 0.0;                // up to 2^25 pairs: the parts (each below 2^24) are added exactly, then rounded once
-#pragma unroll
-    for (int q = 0; q < kSilogParts; ++q) {
-      const float* p = &partials[K * (i * kSilogParts + q)];
-      a2 += __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      a1 += __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      ag += __hip_atomic_load(p + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if constexpr (MASKED) {
-        an += __hip_atomic_load(p + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        am += (double)__hip_atomic_load(p + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    if constexpr (!MASKED) {
-      an = (float)npix;
-      am = pairs;
-    }
+    const float a2 = fold_parts<K>(partials, i, 0), a1 = fold_parts<K>(partials, i, 1), ag = fold_parts<K>(partials, i, 3);
+    // up to 2^25 pairs: the parts (each below 2^24) are added exactly in a double, then rounded once
+    const float an = MASKED ? fold_parts<K>(partials, i, 2) : (float)npix;
+    const double am = MASKED ? fold_parts<K, double>(partials, i, 4) : pairs;
     const float m = (float)am;
     ws[1 + K * i] = a2;
     ws[2 + K * i] = a1;
@@ -159,13 +129,10 @@ __global__ __launch_bounds__(256) void gradloss_fwd_kernel(const float* __restri
     ws[5 + K * i] = m;
     if constexpr (MASKED) {
       valid += (double)an;
-      if (an > 0.f) {
-        const float cn = (float)(0.5 / (double)an), rn = (float)((double)npix / (double)an);
-        s += rn * (a2 - cn * (a1 * a1));
-      }
+      if (an > 0.f) s += silog_term_masked(a2, a1, an, npix);
       if (m > 0.f) sgrad += (float)(pairs / (double)m) * ag;
     } else {
-      s += a2 - c * (a1 * a1);
+      s += silog_term(a2, a1, c);
       sgrad += ag;
     }
   }
@@ -217,12 +184,8 @@ __global__ __launch_bounds__(256) void gradloss_bwd_kernel(const float* __restri
     }
     __syncthreads();
     const float sd = ws[1 + K * smp + 1];
-    float two_c = __fmul_rn(2.f, c), rn = 1.f, two_gwr = 0.f;
-    if constexpr (MASKED) {
-      const double n = (double)ws[1 + K * smp + 2];           // used only at a pixel that counts: then n >= 1
-      two_c = __fmul_rn(2.f, (float)(0.5 / n));
-      rn = (float)((double)npix / n);
-    }
+    const SilogCoef coef = silog_coef<MASKED>(c, MASKED ? ws[1 + K * smp + 2] : 0.f, npix);      // used only at a pixel that counts
+    float two_gwr = 0.f;
     if (gw != 0.f) {
       float rm = 1.f;
       if constexpr (MASKED) {
@@ -240,8 +203,7 @@ __global__ __launch_bounds__(256) void gradloss_bwd_kernel(const float* __restri
       if (ft[li] == 1) {                                       // counts, and its logarithm is a number
         const float d = dt[li];
         const float arg = __fadd_rn(o[pi], 1e-8f);
-        float a = __fmul_rn(__fsub_rn(__fmul_rn(2.f, d), __fmul_rn(two_c, sd)), inv_b);
-        if constexpr (MASKED) a = __fmul_rn(a, rn);
+        float a = silog_pull<MASKED>(d, sd, coef, inv_b);
         if (gw != 0.f) {
           float lap = 0.f;
           if (col > 0 && (ft[li - 1] & 1)) lap = __fadd_rn(lap, __fsub_rn(d, dt[li - 1]));
@@ -252,8 +214,7 @@ __global__ __launch_bounds__(256) void gradloss_bwd_kernel(const float* __restri
         }
         g = __fdiv_rn(a, arg);
       }
-      dout[(size_t)smp * npix + pi] = g;
-      if (dout16) dout16[(size_t)smp * ld16 + pi] = (__bf16)g;
+      write_grad(dout, dout16, ld16, smp, npix, pi, g);
     }
   }
 }
@@ -268,39 +229,28 @@ extern "C" {
 
 int a3dg_silog_grad_loss_fwd(int b, int h, int w, const float* out, const float* tgt, int masked, float grad_weight, float* loss,
                              float* ws, void* stream) {
-  A3D_CHECK_ARG(b > 0 && h > 0 && w > 0 && out && tgt && loss && ws, "silog_grad_fwd: bad arguments");
   A3D_CHECK_ARG(w <= A3DG_MAX_W, "silog_grad_fwd: rows of %d pixels, at most A3DG_MAX_W = %d", w, A3DG_MAX_W);
-  A3D_CHECK_ARG((long long)h * w <= (1 << 24), "silog_grad_fwd: %d x %d pixels per sample, the counts are kept in floats", h, w);
+  const long long npix = h > 0 && w > 0 ? (long long)h * w : 0;      // 0, which loss_check refuses, unless both are positive
+  if (int rc = loss_check("silog_grad_fwd", b, npix, out && tgt && loss && ws, true)) return rc;
   A3D_CHECK_ARG(grad_weight >= 0.f, "silog_grad_fwd: grad_weight must be a number >= 0");
-  hipStream_t st = static_cast<hipStream_t>(stream);
   clear_stale_error();
-  if (masked)
-    hipLaunchKernelGGL(gradloss_fwd_kernel<true>, dim3(b * kSilogParts), dim3(256), 0, st, out, tgt, ws, loss, h, w, b, 0.f,
-                       grad_weight);
-  else
-    hipLaunchKernelGGL(gradloss_fwd_kernel<false>, dim3(b * kSilogParts), dim3(256), 0, st, out, tgt, ws, loss, h, w, b, kSilogC,
-                       grad_weight);
+  launch_masked(masked, gradloss_fwd_kernel<false>, gradloss_fwd_kernel<true>, b * kSilogParts, stream, out, tgt, ws, loss, h, w,
+                b, masked ? 0.f : kSilogC, grad_weight);
   return check_launch("silog_grad_fwd");
 }
 
 int a3dg_silog_grad_loss_bwd_ex(int b, int h, int w, const float* out, const float* tgt, int masked, float grad_weight,
                                 const float* ws, float* dout, void* dout_bf16, int ld_bf16, void* stream) {
-  A3D_CHECK_ARG(b > 0 && h > 0 && w > 0 && out && tgt && ws && dout, "silog_grad_bwd: bad arguments");
   A3D_CHECK_ARG(w <= A3DG_MAX_W, "silog_grad_bwd: rows of %d pixels, at most A3DG_MAX_W = %d", w, A3DG_MAX_W);
-  A3D_CHECK_ARG((long long)h * w <= (1 << 24), "silog_grad_bwd: %d x %d pixels per sample, the counts are kept in floats", h, w);
+  const long long npix = h > 0 && w > 0 ? (long long)h * w : 0;      // 0, which loss_check refuses, unless both are positive
+  if (int rc = loss_check("silog_grad_bwd", b, npix, out && tgt && ws && dout, true, dout_bf16, ld_bf16)) return rc;
   A3D_CHECK_ARG(grad_weight >= 0.f, "silog_grad_bwd: grad_weight must be a number >= 0");
-  A3D_CHECK_ARG(!dout_bf16 || ld_bf16 >= h * w, "silog_grad_bwd: a bf16 pitch of %d below %d pixels", ld_bf16, h * w);
   const int band = gradloss_band(w);
   const long long items = (long long)b * ((h + band - 1) / band);
   const unsigned grid = (unsigned)std::min<long long>(items, kGradGrid);
-  hipStream_t st = static_cast<hipStream_t>(stream);
   clear_stale_error();
-  if (masked)
-    hipLaunchKernelGGL(gradloss_bwd_kernel<true>, dim3(grid), dim3(256), 0, st, out, tgt, ws, dout, b, h, w, band, 0.f,
-                       1.0f / (float)b, grad_weight, static_cast<__bf16*>(dout_bf16), ld_bf16);
-  else
-    hipLaunchKernelGGL(gradloss_bwd_kernel<false>, dim3(grid), dim3(256), 0, st, out, tgt, ws, dout, b, h, w, band, kSilogC,
-                       1.0f / (float)b, grad_weight, static_cast<__bf16*>(dout_bf16), ld_bf16);
+  launch_masked(masked, gradloss_bwd_kernel<false>, gradloss_bwd_kernel<true>, grid, stream, out, tgt, ws, dout, b, h, w, band,
+                masked ? 0.f : kSilogC, 1.0f / (float)b, grad_weight, static_cast<__bf16*>(dout_bf16), ld_bf16);
   return check_launch("silog_grad_bwd");
 }
 

@@ -7,25 +7,19 @@
 #include <algorithm>
 
 #include "a3d_internal.h"
-#include "silog_common.h"
+#include "loss_common.h"
 #include "../../include/a3d_valid.h"
 
-namespace a3d {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-}  // namespace a3d
 using namespace a3d;
 
 namespace a3d {
 // ------------------------------------------------------------------ scale-invariant log loss
-// (masked_log, the wavefront sums, kSilogParts and kSilogC: silog_common.h, shared with gradloss.hip)
+// The parts, the block reduction, the hand-off to the block that arrives last and the silog arithmetic: loss_common.h,
+// shared with gradloss.hip and berhu.hip.
 // kSilogParts blocks per sample (one sample is 4070 pixels at MSDN's size: with one block per sample 32 CUs each walked a
 // chain of load latencies and logarithms — 29 us on the step's critical path; now every CU holds one short piece).  Block
-// (b, part) leaves its partial sums in ws[2nb+1 + 2(b*parts+part) ..]; the block that finishes last (ticket in ws[0],
-// which wraps back to 0: nothing to re-initialise between calls, and no batch size puts a sum there, so one workspace
-// serves calls of different batch sizes) adds each sample's parts in part order — the same sum whatever the timing —
-// writes ws[1+2b] = sum d^2, ws[2+2b] = sum d for the backward kernel, and the batch mean.  The
-// partials cross CUs as write-through stores, drained before the ticket, and are read back past the L1
-// (MI355X_MICROARCH.md, inter-workgroup visibility).
+// (b, part) leaves its partial sums in ws[2nb+1 + 2(b*parts+part) ..]; the block that finishes last adds each sample's
+// parts in part order, writes ws[1+2b] = sum d^2, ws[2+2b] = sum d for the backward kernel, and the batch mean.
 //
 // MASKED (NON-REFERENCE, a3dx_silog_masked_loss_fwd): a target that is not finite is a hole and is left out of the sums;
 // a third value per block and per sample, the number n of pixels that count, travels beside the two sums (K = 3 floats
@@ -37,10 +31,7 @@ __global__ __launch_bounds__(256) void silog_fwd_kernel(const float* __restrict_
                                                         float c) {
   constexpr int K = MASKED ? 3 : 2;
   __shared__ float red[K][4];
-  __shared__ unsigned last;
-  const int b = blockIdx.x / kSilogParts, part = blockIdx.x % kSilogParts;
-  const int chunk = (npix + kSilogParts - 1) / kSilogParts;
-  const int lo = part * chunk, hi = min(npix, lo + chunk);
+  const auto [b, lo, hi] = loss_part<false>(npix);
   const float* o = out + (size_t)b * npix;
   const float* t = tgt + (size_t)b * npix;
   float* partials = ws + K * nb + 1;
@@ -68,51 +59,24 @@ __global__ __launch_bounds__(256) void silog_fwd_kernel(const float* __restrict_
   }
   s2 = wave_sum(s2);
   s1 = wave_sum(s1);
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = s2;
-    red[1][threadIdx.x >> 6] = s1;
-  }
-  if constexpr (MASKED) {
-    cnt = wave_sum(cnt);            // whole numbers below 2^24: exact in any order
-    if ((threadIdx.x & 63) == 0) red[2][threadIdx.x >> 6] = cnt;
-  }
+  block_put(red[0], s2);
+  block_put(red[1], s1);
+  if constexpr (MASKED) block_put(red[2], wave_sum(cnt));            // whole numbers below 2^24: exact in any order
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned total = (unsigned)(nb * kSilogParts);
-    __hip_atomic_store(&partials[K * blockIdx.x], red[0][0] + red[0][1] + red[0][2] + red[0][3], __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&partials[K * blockIdx.x + 1], red[1][0] + red[1][1] + red[1][2] + red[1][3], __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-    if constexpr (MASKED)
-      __hip_atomic_store(&partials[K * blockIdx.x + 2], red[2][0] + red[2][1] + red[2][2] + red[2][3], __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    last = atomicInc(reinterpret_cast<unsigned*>(ws), total - 1u) == total - 1u;
-  }
-  __syncthreads();
-  if (!last || threadIdx.x >= 64) return;
+  if (!publish_and_arrive<K, 0, 0>(ws, partials, nb, red) || threadIdx.x >= 64) return;
   float s = 0.f;
   double valid = 0.0;
   for (int i = threadIdx.x; i < nb; i += 64) {
-    float a2 = 0.f, a1 = 0.f, an = 0.f;
-#pragma unroll
-    for (int q = 0; q < kSilogParts; ++q) {
-      a2 += __hip_atomic_load(&partials[K * (i * kSilogParts + q)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      a1 += __hip_atomic_load(&partials[K * (i * kSilogParts + q) + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if constexpr (MASKED)
-        an += __hip_atomic_load(&partials[K * (i * kSilogParts + q) + 2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    const float a2 = fold_parts<K>(partials, i, 0), a1 = fold_parts<K>(partials, i, 1);
+    const float an = MASKED ? fold_parts<K>(partials, i, 2) : 0.f;      // every load of the partials before the first store to ws
     ws[1 + K * i] = a2;
     ws[2 + K * i] = a1;
     if constexpr (MASKED) {
       ws[3 + K * i] = an;
       valid += (double)an;
-      if (an > 0.f) {
-        const float cn = (float)(0.5 / (double)an), rn = (float)((double)npix / (double)an);
-        s += rn * (a2 - cn * (a1 * a1));
-      }
+      if (an > 0.f) s += silog_term_masked(a2, a1, an, npix);
     } else {
-      s += a2 - c * (a1 * a1);
+      s += silog_term(a2, a1, c);
     }
   }
   s = wave_sum(s);
@@ -128,6 +92,7 @@ __global__ __launch_bounds__(256) void silog_bwd_kernel(const float* __restrict_
                                                         const float* __restrict__ ws, float* __restrict__ dout, int b,
                                                         int npix, float c, float inv_b, __bf16* __restrict__ dout16 = nullptr,
                                                         int ld16 = 0) {
+  constexpr int K = MASKED ? 3 : 2;
   const size_t total = (size_t)b * npix;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const int smp = (int)(i / npix);
@@ -135,54 +100,43 @@ __global__ __launch_bounds__(256) void silog_bwd_kernel(const float* __restrict_
     const float arg = __fadd_rn(o, 1e-8f);
     const float lo = logf(arg);
     float g = 0.f;
-    if constexpr (MASKED) {
-      const float t = tgt[i];
-      if (!isnan(lo) && isfinite(t)) {          // a pixel that counts: its sample has n >= 1
-        const float d = __fsub_rn(lo, masked_log(t));
-        const float sd = ws[3 * smp + 2];
-        const double n = (double)ws[3 * smp + 3];
-        const float cn = (float)(0.5 / n), rn = (float)((double)npix / n);
-        g = __fdiv_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fmul_rn(2.f, d), __fmul_rn(__fmul_rn(2.f, cn), sd)), inv_b), rn), arg);
-      }
-    } else if (!isnan(lo)) {
-      const float d = __fsub_rn(lo, masked_log(tgt[i]));
-      const float sd = ws[2 * smp + 2];
-      g = __fdiv_rn(__fmul_rn(__fsub_rn(__fmul_rn(2.f, d), __fmul_rn(__fmul_rn(2.f, c), sd)), inv_b), arg);
+    const float t = MASKED || !isnan(lo) ? tgt[i] : 0.f;
+    if (!isnan(lo) && (!MASKED || isfinite(t))) {        // a pixel that counts: its sample has n >= 1
+      const float d = __fsub_rn(lo, masked_log(t));
+      const float sd = ws[K * smp + 2];
+      g = __fdiv_rn(silog_pull<MASKED>(d, sd, silog_coef<MASKED>(c, MASKED ? ws[K * smp + 3] : 0.f, npix), inv_b), arg);
     }
-    dout[i] = g;
-    if (dout16) dout16[(size_t)smp * ld16 + (i - (size_t)smp * npix)] = (__bf16)g;      // the copy the bf16 dense layer reads (a3d_silog_loss_bwd_ex)
+    write_grad(dout, dout16, ld16, smp, npix, i - (size_t)smp * npix, g);
   }
 }
+
 }  // namespace a3d
 
 extern "C" {
 
 int a3d_silog_loss_fwd(int b, int npix, const float* out, const float* tgt, float* loss, float* ws, void* stream) {
-  A3D_CHECK_ARG(b > 0 && npix > 0 && out && tgt && loss && ws, "silog_fwd: bad arguments");
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = loss_check("silog_fwd", b, npix, out && tgt && loss && ws, false)) return rc;
   clear_stale_error();
-  hipLaunchKernelGGL(silog_fwd_kernel<false>, dim3(b * kSilogParts), dim3(256), 0, st, out, tgt, ws, loss, npix, b, kSilogC);
+  hipLaunchKernelGGL(silog_fwd_kernel<false>, dim3(b * kSilogParts), dim3(256), 0, static_cast<hipStream_t>(stream), out, tgt,
+                     ws, loss, npix, b, kSilogC);
   return check_launch("silog_fwd");
 }
 
-int a3d_silog_loss_bwd(int b, int npix, const float* out, const float* tgt, const float* ws, float* dout,
-                       void* stream) {
+int a3d_silog_loss_bwd(int b, int npix, const float* out, const float* tgt, const float* ws, float* dout, void* stream) {
   return a3d_silog_loss_bwd_ex(b, npix, out, tgt, ws, dout, nullptr, 0, stream);
 }
 
 int a3d_silog_loss_bwd_ex(int b, int npix, const float* out, const float* tgt, const float* ws, float* dout, void* dout_bf16,
                           int ld_bf16, void* stream) {
-  A3D_CHECK_ARG(b > 0 && npix > 0 && out && tgt && ws && dout && (!dout_bf16 || ld_bf16 >= npix), "silog_bwd: bad arguments");
-  const size_t total = (size_t)b * npix;
+  if (int rc = loss_check("silog_bwd", b, npix, out && tgt && ws && dout, false, dout_bf16, ld_bf16)) return rc;
   clear_stale_error();
-  hipLaunchKernelGGL(silog_bwd_kernel<false>, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), out, tgt,
-                     ws, dout, b, npix, kSilogC, 1.0f / (float)b, static_cast<__bf16*>(dout_bf16), ld_bf16);
+  hipLaunchKernelGGL(silog_bwd_kernel<false>, dim3(grid_for((size_t)b * npix)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     out, tgt, ws, dout, b, npix, kSilogC, 1.0f / (float)b, static_cast<__bf16*>(dout_bf16), ld_bf16);
   return check_launch("silog_bwd");
 }
 
 int a3dx_silog_masked_loss_fwd(int b, int npix, const float* out, const float* tgt, float* loss, float* ws, void* stream) {
-  A3D_CHECK_ARG(b > 0 && npix > 0 && out && tgt && loss && ws, "silog_masked_fwd: bad arguments");
-  A3D_CHECK_ARG(npix <= (1 << 24), "silog_masked_fwd: %d pixels per sample, the count is kept in a float", npix);
+  if (int rc = loss_check("silog_masked_fwd", b, npix, out && tgt && loss && ws, true)) return rc;
   clear_stale_error();
   hipLaunchKernelGGL(silog_fwd_kernel<true>, dim3(b * kSilogParts), dim3(256), 0, static_cast<hipStream_t>(stream), out, tgt,
                      ws, loss, npix, b, 0.f);
@@ -191,12 +145,10 @@ int a3dx_silog_masked_loss_fwd(int b, int npix, const float* out, const float* t
 
 int a3dx_silog_masked_loss_bwd_ex(int b, int npix, const float* out, const float* tgt, const float* ws, float* dout,
                                  void* dout_bf16, int ld_bf16, void* stream) {
-  A3D_CHECK_ARG(b > 0 && npix > 0 && out && tgt && ws && dout && (!dout_bf16 || ld_bf16 >= npix),
-                "silog_masked_bwd: bad arguments");
-  const size_t total = (size_t)b * npix;
+  if (int rc = loss_check("silog_masked_bwd", b, npix, out && tgt && ws && dout, false, dout_bf16, ld_bf16)) return rc;
   clear_stale_error();
-  hipLaunchKernelGGL(silog_bwd_kernel<true>, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), out, tgt,
-                     ws, dout, b, npix, 0.f, 1.0f / (float)b, static_cast<__bf16*>(dout_bf16), ld_bf16);
+  hipLaunchKernelGGL(silog_bwd_kernel<true>, dim3(grid_for((size_t)b * npix)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     out, tgt, ws, dout, b, npix, 0.f, 1.0f / (float)b, static_cast<__bf16*>(dout_bf16), ld_bf16);
   return check_launch("silog_masked_bwd");
 }
 

@@ -160,6 +160,28 @@ class Replica:
         return [x.item() for x in st[1:]]
 
 
+# The loss launches of one MSDNReplica: the floats a forward launch writes (the loss their first), the name its four-float
+# buffers go by, the workspace factory, fwd(out, tgt, loss, ws) and bwd(out, tgt, ws, dout, dout16).  fwd and bwd hold the
+# objective's parameters from construction on: a replica's grad_weight, berhu_fraction and valid_range only report them.
+LossLaunches = collections.namedtuple('LossLaunches', 'width name ws fwd bwd')
+
+
+def msdn_loss_launches(berhu, berhu_fraction, grad_weight, masked):
+    """MSDNReplica's choice among the four objectives, made once."""
+    if berhu:                             # loss, valid fraction, mean threshold, quadratic share (ops.berhu_loss_fwd)
+        return LossLaunches(4, 'berhu', ops.berhu_ws,
+                            lambda out, tgt, loss, ws: ops.berhu_loss_fwd(out, tgt, masked, berhu_fraction, loss, ws),
+                            lambda out, tgt, ws, dout, d16: ops.berhu_loss_bwd(out, tgt, masked, berhu_fraction, ws, dout, d16))
+    if grad_weight > 0:                   # total, valid fraction, silog part, gradient part (ops.silog_grad_loss_fwd)
+        grid = (OUT_H, OUT_W, masked, grad_weight)
+        return LossLaunches(4, 'quad', ops.silog_grad_ws,
+                            lambda out, tgt, loss, ws: ops.silog_grad_loss_fwd(out, tgt, *grid, loss, ws),
+                            lambda out, tgt, ws, dout, d16: ops.silog_grad_loss_bwd(out, tgt, *grid, ws, dout, d16))
+    if masked:                            # the masked loss writes the valid fraction of the target behind the loss
+        return LossLaunches(2, None, ops.silog_masked_ws, ops.silog_masked_loss_fwd, ops.silog_masked_loss_bwd)
+    return LossLaunches(1, None, ops.silog_ws, ops.silog_loss_fwd, ops.silog_loss_bwd)
+
+
 class MSDNReplica(Replica):
     """One data-parallel replica of the MSDN training graph (src/models.py:203-367) on one GPU."""
     objective = 'silog'       # the reference's loss; an instance built with objective='berhu' carries its own (see __init__)
@@ -196,6 +218,7 @@ class MSDNReplica(Replica):
         if berhu:                         # under 'silog' the instance gains no attribute and no buffer
             self.objective, self.berhu_fraction = objective, berhu_fraction
         self.valid_range = check_valid_range(valid_range)
+        self._loss = msdn_loss_launches(berhu, berhu_fraction, grad_weight, self.valid_range is not None)
         # keep_dense_grads=False (the training driver and bench.py on one GPU): under the reference's frozen optimizer the
         # gradient of the two dense kernels (268 MB) goes straight from the matrix cores into ApplyAdam's m slot
         # (ops.dense_bwd_filter_adam_tf1) and is never written; grad('coarse/dense/...') is then stale.  A data-parallel
@@ -308,31 +331,21 @@ class MSDNReplica(Replica):
         self.cat = abuf(B, OUT_H, OUT_W, 64)
         self.f2 = buf(B, OUT_H, OUT_W, 64)
         self.fine = buf(B, OUT_H, OUT_W, 1)
-        self.loss_coarse = buf(1); self.loss_fine = buf(1)
-        if berhu:                         # loss, valid fraction, mean threshold, quadratic share (ops.berhu_loss_fwd)
-            self.loss_berhu_c = buf(4); self.loss_berhu_f = buf(4)
-            self.loss_pair_c = self.loss_berhu_c[:2]; self.loss_pair_f = self.loss_berhu_f[:2]
-            self.loss_coarse = self.loss_pair_c[:1]; self.loss_fine = self.loss_pair_f[:1]
-        elif grad_weight > 0:             # total, valid fraction, silog part, gradient part (ops.silog_grad_loss_fwd)
-            self.loss_quad_c = buf(4); self.loss_quad_f = buf(4)
-            self.loss_pair_c = self.loss_quad_c[:2]; self.loss_pair_f = self.loss_quad_f[:2]
-            self.loss_coarse = self.loss_pair_c[:1]; self.loss_fine = self.loss_pair_f[:1]
-        elif valid_range is not None:     # the masked loss writes the valid fraction of the target behind the loss
-            self.loss_pair_c = buf(2); self.loss_pair_f = buf(2)
-            self.loss_coarse = self.loss_pair_c[:1]; self.loss_fine = self.loss_pair_f[:1]
-        # what a loss launch writes: 4, 2 or 1 floats, loss_coarse / loss_fine their first
-        self.loss_out_c, self.loss_out_f = ((self.loss_berhu_c, self.loss_berhu_f) if berhu else
-                                            (self.loss_quad_c, self.loss_quad_f) if grad_weight > 0 else
-                                            (self.loss_pair_c, self.loss_pair_f) if valid_range is not None else
-                                            (self.loss_coarse, self.loss_fine))
+        # what a loss launch writes: 4, 2 or 1 floats (msdn_loss_launches).  loss_coarse / loss_fine are their first, loss_pair_*
+        # the first two where there are as many, loss_berhu_* / loss_quad_* all four
+        width, name = self._loss.width, self._loss.name
+        self.loss_out_c = buf(width); self.loss_out_f = buf(width)
+        self.loss_coarse = self.loss_out_c[:1]; self.loss_fine = self.loss_out_f[:1]
+        if width >= 2:
+            self.loss_pair_c = self.loss_out_c[:2]; self.loss_pair_f = self.loss_out_f[:2]
+        if width == 4:
+            setattr(self, f'loss_{name}_c', self.loss_out_c); setattr(self, f'loss_{name}_f', self.loss_out_f)
         # window positions of the pool maxima (all MaxPoolGrad needs besides the pooled values, see forward())
         self.a0 = torch.empty((B, 27, 37, 96), dtype=torch.uint8, device=dev)
         self.a1 = torch.empty((B, 13, 18, 256), dtype=torch.uint8, device=dev)
         self.af1 = torch.empty((B, OUT_H, OUT_W, 63), dtype=torch.uint8, device=dev)
         self.pooled_fwd = None            # which network ran conv + pool fused in the last forward
-        silog_ws = (ops.berhu_ws if berhu else ops.silog_grad_ws if grad_weight > 0 else
-                    ops.silog_ws if valid_range is None else ops.silog_masked_ws)
-        self.ws_c = silog_ws(B, dev); self.ws_f = silog_ws(B, dev)           # per-sample sums + arrival ticket + partials
+        self.ws_c = self._loss.ws(B, dev); self.ws_f = self._loss.ws(B, dev)      # per-sample sums + arrival ticket + partials
         self.t_one = buf(B, 1, 1, 1) if valid_range is not None else None    # see ops.resize_bilinear_tf1_valid
         # gradients wrt pre-activations
         self.dz1 = buf(B, OUT_H * OUT_W); self.dz0 = buf(B, 4096)
@@ -948,24 +961,10 @@ class MSDNReplica(Replica):
 
     def _loss_fwd(self, out, loss, ws):
         """One launch: the loss of `out` against self.t into `loss`, the buffer that launch writes (loss_out_c / loss_out_f)."""
-        if self.objective == 'berhu':
-            ops.berhu_loss_fwd(out, self.t, self.valid_range is not None, self.berhu_fraction, loss, ws)
-        elif self.grad_weight > 0:
-            ops.silog_grad_loss_fwd(out, self.t, OUT_H, OUT_W, self.valid_range is not None, self.grad_weight, loss, ws)
-        elif self.valid_range is None:
-            ops.silog_loss_fwd(out, self.t, loss, ws)
-        else:
-            ops.silog_masked_loss_fwd(out, self.t, loss, ws)
+        self._loss.fwd(out, self.t, loss, ws)
 
     def _loss_bwd(self, out, ws, dout, dout16=None):
-        if self.objective == 'berhu':
-            ops.berhu_loss_bwd(out, self.t, self.valid_range is not None, self.berhu_fraction, ws, dout, dout16)
-        elif self.grad_weight > 0:
-            ops.silog_grad_loss_bwd(out, self.t, OUT_H, OUT_W, self.valid_range is not None, self.grad_weight, ws, dout, dout16)
-        elif self.valid_range is None:
-            ops.silog_loss_bwd(out, self.t, ws, dout, dout16)
-        else:
-            ops.silog_masked_loss_bwd(out, self.t, ws, dout, dout16)
+        self._loss.bwd(out, self.t, ws, dout, dout16)
 
     def _sharded_in_flight(self):
         """The deferred dense bucket is a reduce-scatter feeding only the m slot: nothing in the forward needs it, it is due

@@ -430,15 +430,25 @@ def extract_patches(x, k, stride, y):
 SILOG_PARTS = 8                      # A3D_SILOG_PARTS (include/a3d.h)
 
 
+def _loss_ws_floats(k, b):
+    """Floats of a loss workspace: the ticket, k words per sample, k per block (A3D_SILOG_WS_FLOATS and its siblings)."""
+    return k * b + 1 + k * b * SILOG_PARTS
+
+
+def _ld16(dout16):
+    """The pitch argument that goes with an optional bf16 copy of the gradient."""
+    return 0 if dout16 is None else dout16.shape[-1]
+
+
 def silog_ws(b, device):
     """Workspace of silog_loss_fwd / _bwd for a batch of b (or any smaller one): A3D_SILOG_WS_FLOATS(b) zeros (the ticket, its
     first word, must start at zero)."""
-    return torch.zeros(2 * b + 1 + 2 * b * SILOG_PARTS, device=device)
+    return torch.zeros(_loss_ws_floats(2, b), device=device)
 
 
 def silog_loss_fwd(out, tgt, loss, ws):
     b = out.shape[0]
-    assert ws.numel() >= 2 * b + 1 + 2 * b * SILOG_PARTS, 'silog workspace too small: allocate it with ops.silog_ws(b, device)'
+    assert ws.numel() >= _loss_ws_floats(2, b), 'silog workspace too small: allocate it with ops.silog_ws(b, device)'
     npix = out.numel() // b
     check(_lib.load().a3d_silog_loss_fwd(b, npix, _ptr(out), _ptr(tgt), _ptr(loss), _ptr(ws), _stream()),
           'a3d_silog_loss_fwd')
@@ -450,22 +460,21 @@ def silog_loss_bwd(out, tgt, ws, dout, dout16=None):
     b = out.shape[0]
     npix = out.numel() // b
     check(_lib.load().a3d_silog_loss_bwd_ex(b, npix, _ptr(out), _ptr(tgt), _ptr(ws), _ptr(dout), _ptr(dout16),
-                                            0 if dout16 is None else dout16.shape[-1], _stream()), 'a3d_silog_loss_bwd_ex')
+                                            _ld16(dout16), _stream()), 'a3d_silog_loss_bwd_ex')
     return dout
 
 
 def silog_masked_ws(b, device):
     """Workspace of silog_masked_loss_fwd / _bwd for a batch of b (or any smaller one): A3DX_SILOG_MASKED_WS_FLOATS(b)
     zeros (the ticket, its first word, must start at zero)."""
-    return torch.zeros(3 * b + 1 + 3 * b * SILOG_PARTS, device=device)
+    return torch.zeros(_loss_ws_floats(3, b), device=device)
 
 
 def silog_masked_loss_fwd(out, tgt, loss, ws):
     """NON-REFERENCE: the loss over the finite targets only (a3dx_silog_masked_loss_fwd).  loss: 2 floats, the loss and the
     fraction of valid target pixels."""
     b = out.shape[0]
-    assert ws.numel() >= 3 * b + 1 + 3 * b * SILOG_PARTS, \
-        'silog workspace too small: allocate it with ops.silog_masked_ws(b, device)'
+    assert ws.numel() >= _loss_ws_floats(3, b), 'silog workspace too small: allocate it with ops.silog_masked_ws(b, device)'
     assert loss.numel() >= 2 and loss.is_contiguous(), 'silog_masked_loss_fwd writes two floats'
     npix = out.numel() // b
     check(_lib.load().a3dx_silog_masked_loss_fwd(b, npix, _ptr(out), _ptr(tgt), _ptr(loss), _ptr(ws), _stream()),
@@ -478,15 +487,14 @@ def silog_masked_loss_bwd(out, tgt, ws, dout, dout16=None):
     b = out.shape[0]
     npix = out.numel() // b
     check(_lib.load().a3dx_silog_masked_loss_bwd_ex(b, npix, _ptr(out), _ptr(tgt), _ptr(ws), _ptr(dout), _ptr(dout16),
-                                                   0 if dout16 is None else dout16.shape[-1], _stream()),
-          'a3dx_silog_masked_loss_bwd_ex')
+                                                   _ld16(dout16), _stream()), 'a3dx_silog_masked_loss_bwd_ex')
     return dout
 
 
 def silog_grad_ws(b, device):
     """Workspace of silog_grad_loss_fwd / _bwd for a batch of b (or any smaller one): A3DG_WS_FLOATS(b) zeros (the ticket,
     its first word, must start at zero)."""
-    return torch.zeros(5 * b + 1 + 5 * b * SILOG_PARTS, device=device)
+    return torch.zeros(_loss_ws_floats(5, b), device=device)
 
 
 def _grad_loss_args(who, out, h, w, grad_weight):
@@ -503,8 +511,7 @@ def silog_grad_loss_fwd(out, tgt, h, w, masked, grad_weight, loss, ws):
     the horizontal and vertical neighbour pairs of the h x w grid (a3dg_silog_grad_loss_fwd).  masked: only finite targets
     count, as in silog_masked_loss_fwd.  loss: 4 floats — the total, the valid fraction, the silog part, the gradient part."""
     b, grad_weight = _grad_loss_args('silog_grad_loss_fwd', out, h, w, grad_weight)
-    assert ws.numel() >= 5 * b + 1 + 5 * b * SILOG_PARTS, \
-        'silog workspace too small: allocate it with ops.silog_grad_ws(b, device)'
+    assert ws.numel() >= _loss_ws_floats(5, b), 'silog workspace too small: allocate it with ops.silog_grad_ws(b, device)'
     assert loss.numel() >= 4 and loss.is_contiguous(), 'silog_grad_loss_fwd writes four floats'
     check(_lib.load().a3dg_silog_grad_loss_fwd(b, h, w, _ptr(out), _ptr(tgt), int(bool(masked)), grad_weight, _ptr(loss),
                                                _ptr(ws), _stream()), 'a3dg_silog_grad_loss_fwd')
@@ -515,15 +522,15 @@ def silog_grad_loss_bwd(out, tgt, h, w, masked, grad_weight, ws, dout, dout16=No
     """dout16 as silog_loss_bwd's.  masked and grad_weight as in the forward call that filled ws."""
     b, grad_weight = _grad_loss_args('silog_grad_loss_bwd', out, h, w, grad_weight)
     check(_lib.load().a3dg_silog_grad_loss_bwd_ex(b, h, w, _ptr(out), _ptr(tgt), int(bool(masked)), grad_weight, _ptr(ws),
-                                                  _ptr(dout), _ptr(dout16), 0 if dout16 is None else dout16.shape[-1],
-                                                  _stream()), 'a3dg_silog_grad_loss_bwd_ex')
+                                                  _ptr(dout), _ptr(dout16), _ld16(dout16), _stream()),
+          'a3dg_silog_grad_loss_bwd_ex')
     return dout
 
 
 def berhu_ws(b, device):
     """Workspace of berhu_loss_fwd / _bwd for a batch of b (or any smaller one): A3DH_WS_FLOATS(b) zeros (the ticket, its
     first word, must start at zero)."""
-    return torch.zeros(3 * b + 1 + 3 * b * SILOG_PARTS, device=device)
+    return torch.zeros(_loss_ws_floats(3, b), device=device)
 
 
 def _berhu_args(who, out, tgt, fraction):
@@ -540,7 +547,7 @@ def berhu_loss_fwd(out, tgt, masked, fraction, loss, ws):
     error of each sample (a3dh_berhu_loss_fwd, two launches).  masked: only finite targets count, as in silog_masked_loss_fwd.
     loss: 4 floats — the loss, the valid fraction, the mean threshold, the share of the counting pixels that are quadratic."""
     b, npix, fraction = _berhu_args('berhu_loss_fwd', out, tgt, fraction)
-    assert ws.numel() >= 3 * b + 1 + 3 * b * SILOG_PARTS, 'berhu workspace too small: allocate it with ops.berhu_ws(b, device)'
+    assert ws.numel() >= _loss_ws_floats(3, b), 'berhu workspace too small: allocate it with ops.berhu_ws(b, device)'
     assert loss.numel() >= 4 and loss.is_contiguous(), 'berhu_loss_fwd writes four floats'
     check(_lib.load().a3dh_berhu_loss_fwd(b, npix, _ptr(out), _ptr(tgt), int(bool(masked)), fraction, _ptr(loss), _ptr(ws),
                                           _stream()), 'a3dh_berhu_loss_fwd')
@@ -551,8 +558,7 @@ def berhu_loss_bwd(out, tgt, masked, fraction, ws, dout, dout16=None):
     """dout16 as silog_loss_bwd's.  masked and fraction as in the forward call that filled ws."""
     b, npix, fraction = _berhu_args('berhu_loss_bwd', out, tgt, fraction)
     check(_lib.load().a3dh_berhu_loss_bwd_ex(b, npix, _ptr(out), _ptr(tgt), int(bool(masked)), fraction, _ptr(ws), _ptr(dout),
-                                             _ptr(dout16), 0 if dout16 is None else dout16.shape[-1], _stream()),
-          'a3dh_berhu_loss_bwd_ex')
+                                             _ptr(dout16), _ld16(dout16), _stream()), 'a3dh_berhu_loss_bwd_ex')
     return dout
 
 
