@@ -176,6 +176,12 @@ ALIGN_SIGNATURES = {
     'a3da_affine_apply': (c_int, [c_int, c_int, _P, _P, _P, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_ssi.h declares (NON-REFERENCE extension, prefix a3di_)
+SSI_SIGNATURES = {
+    'a3di_ssi_loss_fwd': (c_int, [c_int, c_int, _P, _P, c_int, _P, _P, _P]),
+    'a3di_ssi_loss_bwd_ex': (c_int, [c_int, c_int, _P, _P, c_int, _P, _P, _P, c_int, _P]),
+}
+
 # name -> (restype, argtypes); every symbol include/a3d_crf_valid.h declares (NON-REFERENCE extension, prefix a3dv_)
 CRF_VALID_SIGNATURES = {
     'a3dv_superpixel_mean_valid': (c_int, [c_int, c_int, c_int, _P, c_int, c_int, _P, _P, _P]),
@@ -263,7 +269,7 @@ def load():
                               + list(UPSAMPLE_SIGNATURES.items()) + list(POSTERIOR_SIGNATURES.items())
                               + list(WINO_GRAD_SIGNATURES.items()) + list(SLIC_SIGNATURES.items())
                               + list(WINO_BWD_SIGNATURES.items()) + list(BERHU_SIGNATURES.items())
-                              + list(ALIGN_SIGNATURES.items())):
+                              + list(ALIGN_SIGNATURES.items()) + list(SSI_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -10,7 +10,7 @@ replaced by synchronous RCCL data parallelism: launch one process per GPU with
 accepted and ignored.
 
 Flags that are not the reference's: --beta2, --precision, --augment, --min-depth / --max-depth, --loss-gradient,
---loss {silog,berhu}, --berhu-fraction,
+--loss {silog,berhu,ssi}, --berhu-fraction,
 --train-pairwise, --pairwise-texture, --superpixel {40,20,10}, --unary {patch,fcsp} (dcnf: the unary part over 48 patches per image, the
 reference's, or once over the whole image with superpixel pooling before the dense head), --seed, --tf-checkpoints,
 --trace-every, --profiler.
@@ -113,8 +113,17 @@ def main(argv=None):
         logger.error('--loss berhu cannot go with --loss-gradient: the gradient-matching term is defined on differences of log '
                      'depth and belongs to --loss silog.')
         return 2
+    if args.loss == 'ssi' and args.model != 'msdn':
+        logger.error(f'--loss ssi is the scale-and-shift-invariant loss on the linear depths of --model msdn: '
+                     f'{args.model or "(no model)"} has no loss over a pixel grid (dcnf regresses superpixel means through a '
+                     f'likelihood).')
+        return 2
+    if args.loss == 'ssi' and args.loss_gradient is not None:
+        logger.error('--loss ssi cannot go with --loss-gradient: the gradient-matching term is defined on differences of log '
+                     'depth and belongs to --loss silog.')
+        return 2
     if args.berhu_fraction is not None and args.loss != 'berhu':
-        logger.error('--berhu-fraction sets the threshold of --loss berhu; --loss silog has none.')
+        logger.error(f'--berhu-fraction sets the threshold of --loss berhu; --loss {args.loss} has none.')
         return 2
     if args.berhu_fraction is not None and not 0 < args.berhu_fraction <= 1:
         logger.error(f'--berhu-fraction {args.berhu_fraction}: the threshold is a fraction in (0, 1] of the largest error.')
@@ -495,11 +504,13 @@ def parse_args(argv=None):
                              'losses (msdn only): the squared horizontal and vertical differences of the log-depth error over '
                              'the 55 x 74 grid, over the pairs of valid pixels under --min-depth / --max-depth. W >= 0; 0 is '
                              'the run without the flag.')
-    parser.add_argument('--loss', default='silog', choices=['silog', 'berhu'],
+    parser.add_argument('--loss', default='silog', choices=['silog', 'berhu', 'ssi'],
                         help='NON-REFERENCE unless silog: the objective of both losses (msdn only). silog: the reference\'s '
                              'scale-invariant log loss, under which an output at or below zero gets no gradient. berhu: the reverse '
                              'Huber loss of Laina et al. 2016 on linear depth, L1 up to a threshold and quadratic beyond it, over '
-                             'the valid pixels under --min-depth / --max-depth; not with --loss-gradient.')
+                             'the valid pixels under --min-depth / --max-depth. ssi: the least-squares scale-and-shift-invariant loss of '
+                             'Ranftl et al. 2020 on linear depth, the squared error left after the best scale and shift of each '
+                             'output, the objective that matches evaluate --align affine. Neither with --loss-gradient.')
     parser.add_argument('--berhu-fraction', default=None, type=float, metavar='F',
                         help='NON-REFERENCE, --loss berhu: the threshold is F times the largest error of each sample (per sample, '
                              'not per batch, so that a sample\'s gradient does not depend on its batch). 0 < F <= 1, default 0.2.')

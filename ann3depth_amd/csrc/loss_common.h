@@ -1,10 +1,10 @@
 // loss_common.h — the machine the loss kernels share: pointwise.hip (silog, plain and masked), gradloss.hip (silog with the
-// gradient-matching term) and berhu.hip (reverse Huber).  Every forward kernel there is
+// gradient-matching term), berhu.hip (reverse Huber) and ssi.hip (scale-and-shift-invariant).  Every forward kernel there is
 //   kSilogParts blocks per sample, each on a contiguous chunk (loss_part) -> per-thread accumulators -> one value per block
 //   (wave_sum / wave_max, block_put into red[K][4]) -> published and handed to the block that arrives last (publish_and_arrive) ->
 //   that block adds each sample's parts in part order (fold_parts), the same sum whatever the timing;
 // and the silog arithmetic — masked_log, the per-sample term, the pull of the backward — is written here once, so that
-// pointwise.hip and gradloss.hip give the same bits by construction.  All three files are compiled with -ffp-contract=off.
+// pointwise.hip and gradloss.hip give the same bits by construction.  All four files are compiled with -ffp-contract=off.
 // Everything is __forceinline__: no call, no scratch.
 #pragma once
 #include "a3d_internal.h"
@@ -132,6 +132,50 @@ __device__ __forceinline__ Acc fold_parts(const float* __restrict__ partials, in
     if constexpr (MAX) a = fmaxf(a, v);
     else a += (Acc)v;
   }
+  return a;
+}
+
+// ------------------------------------------------------------------ the same hand-off for float64 values (ssi.hip)
+// A kernel whose partial sums are float64 runs the same four steps itself: block_put / block_sum64 on a red64[K][4], lane 0
+// publishes its block's words one by one (publish64 / publish32), every thread calls arrive, and the last block reads with
+// fold_parts64 (and fold_parts for its float words).  A float64 word is ONE 8-byte agent-scope relaxed store or load
+// (global_store_dwordx2 sc1): it lies at an even word offset of a workspace that starts on an 8-byte address, so it never
+// straddles and is never seen half written.
+__device__ __forceinline__ void block_put(double (&row)[4], double v) {
+  if ((threadIdx.x & 63) == 0) row[threadIdx.x >> 6] = v;
+}
+
+__device__ __forceinline__ double block_sum64(const double (&row)[4]) { return ((row[0] + row[1]) + row[2]) + row[3]; }
+
+__device__ __forceinline__ void publish64(float* __restrict__ word, double v) {
+  __hip_atomic_store(reinterpret_cast<double*>(word), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ void publish32(float* __restrict__ word, float v) {
+  __hip_atomic_store(word, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// steps 2 to 4 of publish_and_arrive, for a block whose lane 0 has just published its words itself; called by every thread
+__device__ __forceinline__ bool arrive(float* __restrict__ ws, int nb) {
+  __shared__ unsigned last_arrived;
+  if (threadIdx.x == 0) {
+    const unsigned total = (unsigned)(nb * kSilogParts);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    last_arrived = atomicInc(reinterpret_cast<unsigned*>(ws), total - 1u) == total - 1u;
+  }
+  __syncthreads();
+  return last_arrived != 0u;
+}
+
+// the float64 word at `word` (even) of the K-word partials of sample i's parts, added in ascending part order from 0.0
+template <int K>
+__device__ __forceinline__ double fold_parts64(const float* __restrict__ partials, int i, int word) {
+  static_assert(K % 2 == 0, "float64 words lie at even offsets");
+  double a = 0.0;
+#pragma unroll
+  for (int q = 0; q < kSilogParts; ++q)
+    a += __hip_atomic_load(reinterpret_cast<const double*>(&partials[K * (i * kSilogParts + q) + word]), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
   return a;
 }
 

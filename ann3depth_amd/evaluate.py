@@ -43,6 +43,10 @@ targets with the threshold F (default 0.2, 0 < F <= 1) times each image's larges
 report gains ``loss`` and ``berhu_fraction``.  Checkpoints do not record the objective: any MSDN checkpoint can be asked.
 Without the flag nothing more is launched and the report has no new key.
 
+``--loss ssi`` (NON-REFERENCE, msdn; not listed by ``--help`` either; include/a3d_ssi.h) adds ``ssi`` beside ``silog`` to
+``coarse`` and ``fine``: the plain least-squares scale-and-shift-invariant loss on the grid targets, averaged the way ``silog``
+is, and the report gains ``loss``.  A checkpoint trained under it is judged with ``--align affine``.
+
 ``--align median|scale|affine`` (NON-REFERENCE, both models; include/a3d_align.h, ops.depth_align; not listed by ``--help``):
 the depth maps the models train on are min-max scaled per image, so a checkpoint predicts depth up to an affine map per
 image.  Every output judged is judged a second time as ``<name>_aligned`` after a per-image scale (``median``: the ratio of
@@ -144,11 +148,13 @@ class Evaluator(MetricRows):
     outputs = OUTPUTS['msdn']
 
     def __init__(self, replica, resolution='grid', min_depth=0., max_depth=float('inf'), clamp_lo=1e-3,
-                 clamp_hi=float('inf'), keep_predictions=False, upsample=None, berhu_fraction=None, align=None):
+                 clamp_hi=float('inf'), keep_predictions=False, upsample=None, berhu_fraction=None, align=None,
+                 ssi=False):
         """upsample (NON-REFERENCE, --upsample joint): an ops.JointUpsampler; a third output `fine_joint`, the fine map
         brought to the record image's size under the batch's images, is judged against the same target.
         berhu_fraction (NON-REFERENCE, --loss berhu): also report `berhu`, the plain reverse Huber loss on the grid targets
-        with this threshold fraction, beside `silog`."""
+        with this threshold fraction, beside `silog`.
+        ssi (NON-REFERENCE, --loss ssi): also report `ssi`, the plain scale-and-shift-invariant loss on the grid targets."""
         from .models import OUT_H, OUT_W
         super().__init__(replica, resolution, ('fine_joint',) if upsample is not None else (), (OUT_H, OUT_W), min_depth,
                          max_depth, clamp_lo, clamp_hi, keep_predictions, align)
@@ -160,6 +166,10 @@ class Evaluator(MetricRows):
         if berhu_fraction is not None:
             self.berhu_ws = {}          # per batch size, as silog_ws
             self.berhu = {o: [] for o in OUTPUTS['msdn']}
+        self.ssi = None
+        if ssi:
+            self.ssi_ws = {}            # per batch size, as silog_ws
+            self.ssi = {o: [] for o in OUTPUTS['msdn']}
 
     def __call__(self, images, depths, n):
         coarse, fine = self.rep.predict(images, n)
@@ -180,6 +190,13 @@ class Evaluator(MetricRows):
                     ws = self.berhu_ws[n] = ops.berhu_ws(n, out.device)
                 ops.berhu_loss_fwd(out[:n], self.t[:n], 0, self.berhu_fraction, quad, ws)
                 self.berhu[name].append(quad[:1])
+            if self.ssi is not None:
+                quad = torch.empty(4, device=out.device)
+                ws = self.ssi_ws.get(n)
+                if ws is None:
+                    ws = self.ssi_ws[n] = ops.ssi_ws(n, out.device)
+                ops.ssi_loss_fwd(out[:n], self.t[:n], 0, quad, ws)
+                self.ssi[name].append(quad[:1])
         if self.upsample is not None:
             self.judge('fine_joint', self.upsample(fine[:n], images[:n]), n, target)
         self.counts.append(n)
@@ -192,6 +209,8 @@ class Evaluator(MetricRows):
             out[name]['silog'] = self.mean(losses)
             if self.berhu_fraction is not None:
                 out[name]['berhu'] = self.mean(self.berhu[name])
+            if self.ssi is not None:
+                out[name]['ssi'] = self.mean(self.ssi[name])
         return out
 
 
@@ -412,6 +431,10 @@ def main(argv=None):
         _say(f'--loss berhu reports the reverse Huber loss of the two outputs of --model msdn: {args.model} has no loss over a '
              f'pixel grid.')
         return 2
+    if args.loss == 'ssi' and args.model != 'msdn':
+        _say(f'--loss ssi reports the scale-and-shift-invariant loss of the two outputs of --model msdn: {args.model} has no '
+             f'loss over a pixel grid.')
+        return 2
     if args.berhu_fraction is not None and (args.loss != 'berhu' or not 0 < args.berhu_fraction <= 1):
         _say(f'--berhu-fraction {args.berhu_fraction} sets the threshold of --loss berhu, a fraction in (0, 1] of the largest error.')
         return 2
@@ -448,6 +471,8 @@ def main(argv=None):
         extra['condition'] = (args.condition, args.condition_seed)
     if args.loss == 'berhu':
         extra['berhu_fraction'] = 0.2 if args.berhu_fraction is None else args.berhu_fraction
+    if args.loss == 'ssi':
+        extra['ssi'] = True
     if args.align != 'none':
         extra['align'] = args.align
     ev = evaluator(replica, args.resolution, args.min_depth, args.max_depth, args.clamp_lo, args.clamp_hi,
@@ -482,6 +507,8 @@ def main(argv=None):
         out.update(condition=args.condition, condition_seed=args.condition_seed)
     if args.loss == 'berhu':
         out.update(loss='berhu', berhu_fraction=extra['berhu_fraction'])
+    if args.loss == 'ssi':
+        out.update(loss='ssi')
     if args.align != 'none':
         out['align'] = args.align
     if args.predictions:
@@ -537,9 +564,9 @@ def parse_args(argv=None):
                         'and crf_hidden (the plain MAP) are judged on the pixels of the hidden ones.')
     p.add_argument('--condition-seed', default=0, type=int,
                    help='--condition: the masks are drawn on the host from (this seed, the record\'s index).')
-    # NON-REFERENCE, msdn: --loss berhu [--berhu-fraction F] (see the module docstring).  Kept out of --help like --segmentation:
+    # NON-REFERENCE, msdn: --loss berhu [--berhu-fraction F], --loss ssi (see the module docstring).  Kept out of --help like --segmentation:
     # this driver's help text is recorded word for word (tests/golden/evaluate_help.txt).
-    p.add_argument('--loss', default='silog', choices=['silog', 'berhu'], help=argparse.SUPPRESS)
+    p.add_argument('--loss', default='silog', choices=['silog', 'berhu', 'ssi'], help=argparse.SUPPRESS)
     p.add_argument('--berhu-fraction', default=None, type=float, metavar='F', help=argparse.SUPPRESS)
     add_shared_args(p, 'segmentation')
     # NON-REFERENCE: --align (see the module docstring), kept out of --help for the same reason

@@ -166,9 +166,13 @@ class Replica:
 LossLaunches = collections.namedtuple('LossLaunches', 'width name ws fwd bwd')
 
 
-def msdn_loss_launches(berhu, berhu_fraction, grad_weight, masked):
-    """MSDNReplica's choice among the four objectives, made once."""
-    if berhu:                             # loss, valid fraction, mean threshold, quadratic share (ops.berhu_loss_fwd)
+def msdn_loss_launches(objective, berhu_fraction, grad_weight, masked):
+    """MSDNReplica's choice among the five objectives, made once."""
+    if objective == 'ssi':                # loss, valid fraction, mean scale, mean shift (ops.ssi_loss_fwd)
+        return LossLaunches(4, 'ssi', ops.ssi_ws,
+                            lambda out, tgt, loss, ws: ops.ssi_loss_fwd(out, tgt, masked, loss, ws),
+                            lambda out, tgt, ws, dout, d16: ops.ssi_loss_bwd(out, tgt, masked, ws, dout, d16))
+    if objective == 'berhu':              # loss, valid fraction, mean threshold, quadratic share (ops.berhu_loss_fwd)
         return LossLaunches(4, 'berhu', ops.berhu_ws,
                             lambda out, tgt, loss, ws: ops.berhu_loss_fwd(out, tgt, masked, berhu_fraction, loss, ws),
                             lambda out, tgt, ws, dout, d16: ops.berhu_loss_bwd(out, tgt, masked, berhu_fraction, ws, dout, d16))
@@ -184,7 +188,7 @@ def msdn_loss_launches(berhu, berhu_fraction, grad_weight, masked):
 
 class MSDNReplica(Replica):
     """One data-parallel replica of the MSDN training graph (src/models.py:203-367) on one GPU."""
-    objective = 'silog'       # the reference's loss; an instance built with objective='berhu' carries its own (see __init__)
+    objective = 'silog'       # the reference's loss; an instance built with 'berhu' or 'ssi' carries its own (see __init__)
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, global_step=0, beta2=1.0, reducer=None,
                  precision='fp32', keep_dense_grads=True, overlap=True, valid_range=None, grad_weight=0.0,
@@ -201,9 +205,12 @@ class MSDNReplica(Replica):
         targets under valid_range.  > 0: the four loss launches are ops.silog_grad_loss_fwd / _bwd.  0: today's launches.
         objective (NON-REFERENCE): 'silog', the reference's scale-invariant log loss, or 'berhu', the reverse Huber loss of
         Laina et al. 2016 on linear depth (ops.berhu_loss_fwd / _bwd), which pulls on outputs at or below zero too; its
-        threshold is berhu_fraction, in (0, 1], times the largest error of each sample.  'silog': today's launches."""
-        if objective not in ('silog', 'berhu'):
-            raise ValueError(f"objective {objective!r}: 'silog' or 'berhu'")
+        threshold is berhu_fraction, in (0, 1], times the largest error of each sample; or 'ssi', the least-squares
+        scale-and-shift-invariant loss of Ranftl et al. 2020 on linear depth (ops.ssi_loss_fwd / _bwd): per sample the squared
+        error left after the best scale and shift of the output, the objective that matches evaluate's --align affine.
+        'silog': today's launches."""
+        if objective not in ('silog', 'berhu', 'ssi'):
+            raise ValueError(f"objective {objective!r}: 'silog', 'berhu' or 'ssi'")
         berhu_fraction = float(berhu_fraction)
         if not 0 < berhu_fraction <= 1:
             raise ValueError(f'berhu_fraction {berhu_fraction!r}: the threshold is a fraction in (0, 1] of the largest error')
@@ -211,14 +218,16 @@ class MSDNReplica(Replica):
         grad_weight = float(grad_weight)
         if not grad_weight >= 0:
             raise ValueError(f'grad_weight {grad_weight!r}: the weight of the gradient-matching term is a number >= 0')
-        if berhu and grad_weight > 0:
-            raise ValueError(f"objective 'berhu' with grad_weight {grad_weight!r}: the gradient-matching term is defined on "
-                             f'log differences and belongs to the silog objective')
+        if objective != 'silog' and grad_weight > 0:
+            raise ValueError(f"objective {objective!r} with grad_weight {grad_weight!r}: the gradient-matching term is defined "
+                             f'on log differences and belongs to the silog objective')
         self.grad_weight = grad_weight
         if berhu:                         # under 'silog' the instance gains no attribute and no buffer
             self.objective, self.berhu_fraction = objective, berhu_fraction
+        elif objective == 'ssi':
+            self.objective = objective
         self.valid_range = check_valid_range(valid_range)
-        self._loss = msdn_loss_launches(berhu, berhu_fraction, grad_weight, self.valid_range is not None)
+        self._loss = msdn_loss_launches(objective, berhu_fraction, grad_weight, self.valid_range is not None)
         # keep_dense_grads=False (the training driver and bench.py on one GPU): under the reference's frozen optimizer the
         # gradient of the two dense kernels (268 MB) goes straight from the matrix cores into ApplyAdam's m slot
         # (ops.dense_bwd_filter_adam_tf1) and is never written; grad('coarse/dense/...') is then stale.  A data-parallel
@@ -332,7 +341,7 @@ class MSDNReplica(Replica):
         self.f2 = buf(B, OUT_H, OUT_W, 64)
         self.fine = buf(B, OUT_H, OUT_W, 1)
         # what a loss launch writes: 4, 2 or 1 floats (msdn_loss_launches).  loss_coarse / loss_fine are their first, loss_pair_*
-        # the first two where there are as many, loss_berhu_* / loss_quad_* all four
+        # the first two where there are as many, loss_berhu_* / loss_ssi_* / loss_quad_* all four
         width, name = self._loss.width, self._loss.name
         self.loss_out_c = buf(width); self.loss_out_f = buf(width)
         self.loss_coarse = self.loss_out_c[:1]; self.loss_fine = self.loss_out_f[:1]
@@ -741,6 +750,10 @@ class MSDNReplica(Replica):
             for name, quad in (('coarse', self.loss_berhu_c), ('fine', self.loss_berhu_f)):
                 rec[f'loss/{name}_threshold'] = float(quad[2])
                 rec[f'loss/{name}_quadratic'] = float(quad[3])
+        if self.objective == 'ssi':                      # NON-REFERENCE: the mean fitted scale and shift of the outputs
+            for name, quad in (('coarse', self.loss_ssi_c), ('fine', self.loss_ssi_f)):
+                rec[f'loss/{name}_scale'] = float(quad[2])
+                rec[f'loss/{name}_shift'] = float(quad[3])
         return rec
 
     def summary_images(self):
@@ -2088,7 +2101,7 @@ class _MultiScaleDeepNetwork:
     augment = None       # NON-REFERENCE, --augment eigen: an augment.Eigen2014 (train-time augmentation of the input batch)
     valid_range = None   # NON-REFERENCE, --min-depth / --max-depth: (min, max), the depth maps have holes (see MSDNReplica)
     grad_weight = 0.0    # NON-REFERENCE, --loss-gradient: weight of the gradient-matching term in both losses (see MSDNReplica)
-    objective = 'silog'  # NON-REFERENCE, --loss berhu: the reverse Huber loss on linear depth (see MSDNReplica)
+    objective = 'silog'  # NON-REFERENCE, --loss berhu / ssi: reverse Huber, or scale-and-shift-invariant (see MSDNReplica)
     berhu_fraction = 0.2  # --berhu-fraction: its threshold, as a fraction of each sample's largest error
 
     def __call__(self, images, depths, train=True):

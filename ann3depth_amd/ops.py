@@ -562,6 +562,44 @@ def berhu_loss_bwd(out, tgt, masked, fraction, ws, dout, dout16=None):
     return dout
 
 
+def _ssi_ws_floats(b):
+    """A3DI_WS_FLOATS(b): the ticket and a pad, four words per sample, ten per block (four of them float64 pairs)."""
+    return 4 * b + 2 + 10 * b * SILOG_PARTS
+
+
+def ssi_ws(b, device):
+    """Workspace of ssi_loss_fwd / _bwd for a batch of b (or any smaller one): A3DI_WS_FLOATS(b) zeros (the ticket, its
+    first word, must start at zero).  Word 2 + 4 i + {0, 1, 2, 3} holds sample i's scale, shift, count and flag (0 fitted,
+    1 degenerate, 2 poisoned) after a forward call."""
+    return torch.zeros(_ssi_ws_floats(b), device=device)
+
+
+def _ssi_args(who, out, tgt):
+    b = out.shape[0]
+    assert out.numel() == tgt.numel(), f'{who}: out holds {out.numel()} values, tgt {tgt.numel()}'
+    return b, out.numel() // b
+
+
+def ssi_loss_fwd(out, tgt, masked, loss, ws):
+    """NON-REFERENCE: the least-squares scale-and-shift-invariant loss of Ranftl et al. 2020 on linear depth: per sample the
+    squared error left after the best scale and shift of the output (a3di_ssi_loss_fwd, two launches).  masked: only finite
+    targets count, as in silog_masked_loss_fwd.  loss: 4 floats — the loss, the valid fraction, the mean scale, the mean shift."""
+    b, npix = _ssi_args('ssi_loss_fwd', out, tgt)
+    assert ws.numel() >= _ssi_ws_floats(b), 'ssi workspace too small: allocate it with ops.ssi_ws(b, device)'
+    assert loss.numel() >= 4 and loss.is_contiguous(), 'ssi_loss_fwd writes four floats'
+    check(_lib.load().a3di_ssi_loss_fwd(b, npix, _ptr(out), _ptr(tgt), int(bool(masked)), _ptr(loss), _ptr(ws), _stream()),
+          'a3di_ssi_loss_fwd')
+    return loss
+
+
+def ssi_loss_bwd(out, tgt, masked, ws, dout, dout16=None):
+    """dout16 as silog_loss_bwd's.  masked as in the forward call that filled ws."""
+    b, npix = _ssi_args('ssi_loss_bwd', out, tgt)
+    check(_lib.load().a3di_ssi_loss_bwd_ex(b, npix, _ptr(out), _ptr(tgt), int(bool(masked)), _ptr(ws), _ptr(dout),
+                                           _ptr(dout16), _ld16(dout16), _stream()), 'a3di_ssi_loss_bwd_ex')
+    return dout
+
+
 METRIC_COLUMNS = ('n', 'abs_rel', 'sq_rel', 'sq', 'log', 'log_sq', 'log10', 'delta1', 'delta2', 'delta3', 'nonfinite')
 # A3D_METRIC_* (include/a3d.h): the per-image sums of a3d_depth_metrics, in this column order
 
