@@ -1,4 +1,5 @@
 """ctypes binding of liba3d.so (include/a3d.h).  Fails loudly when the library is missing or lacks a symbol."""
+import collections
 import ctypes
 import os
 from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint8, c_uint32, c_void_p, POINTER
@@ -247,6 +248,30 @@ SLIC_SIGNATURES = {
     'a3ds_label_pool_bwd': (c_int, [c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P]),
 }
 
+# Every C surface of liba3d.so, in the order load() binds them: the prefix its names share, its header under include/, its
+# dict above.  A new surface is one header, one dict and one line here; tests/test_abi_surfaces.py holds the list to the
+# headers and to what load() binds.
+Surface = collections.namedtuple('Surface', 'prefix header signatures')
+SURFACES = (
+    Surface('a3d_', 'a3d.h', SIGNATURES),
+    Surface('a3dx_', 'a3d_valid.h', EXT_SIGNATURES),
+    Surface('a3dp_', 'a3d_pairwise.h', PAIR_SIGNATURES),
+    Surface('a3dt_', 'a3d_texture.h', TEXTURE_SIGNATURES),
+    Surface('a3dg_', 'a3d_gradloss.h', GRADLOSS_SIGNATURES),
+    Surface('a3dv_', 'a3d_crf_valid.h', CRF_VALID_SIGNATURES),
+    Surface('a3df_', 'a3d_fcsp.h', FCSP_SIGNATURES),
+    Surface('a3db_', 'a3d_crf_band.h', CRF_BAND_SIGNATURES),
+    Surface('a3dw_', 'a3d_wino.h', WINO_SIGNATURES),
+    Surface('a3du_', 'a3d_upsample.h', UPSAMPLE_SIGNATURES),
+    Surface('a3dc_', 'a3d_posterior.h', POSTERIOR_SIGNATURES),
+    Surface('a3dwg_', 'a3d_wino_grad.h', WINO_GRAD_SIGNATURES),
+    Surface('a3ds_', 'a3d_slic.h', SLIC_SIGNATURES),
+    Surface('a3dwb_', 'a3d_wino_bwd.h', WINO_BWD_SIGNATURES),
+    Surface('a3dh_', 'a3d_berhu.h', BERHU_SIGNATURES),
+    Surface('a3da_', 'a3d_align.h', ALIGN_SIGNATURES),
+    Surface('a3di_', 'a3d_ssi.h', SSI_SIGNATURES),
+)
+
 _lib = None
 
 
@@ -262,14 +287,7 @@ def load():
     # the runtime copy torch initialises: two HIP runtimes in one process cannot both own the device.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(PAIR_SIGNATURES.items())
-                              + list(TEXTURE_SIGNATURES.items()) + list(GRADLOSS_SIGNATURES.items())
-                              + list(CRF_VALID_SIGNATURES.items()) + list(FCSP_SIGNATURES.items())
-                              + list(CRF_BAND_SIGNATURES.items()) + list(WINO_SIGNATURES.items())
-                              + list(UPSAMPLE_SIGNATURES.items()) + list(POSTERIOR_SIGNATURES.items())
-                              + list(WINO_GRAD_SIGNATURES.items()) + list(SLIC_SIGNATURES.items())
-                              + list(WINO_BWD_SIGNATURES.items()) + list(BERHU_SIGNATURES.items())
-                              + list(ALIGN_SIGNATURES.items()) + list(SSI_SIGNATURES.items())):
+    for name, (res, args) in ((n, sig) for surface in SURFACES for n, sig in surface.signatures.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -28,6 +28,9 @@ import torch
 
 from . import _lib, augment, data, dp, models, summary, tfckpt, tracehook
 
+# --loss NAME other than silog: what a refusal calls it
+LINEAR_LOSSES = {'berhu': 'the reverse Huber loss', 'ssi': 'the scale-and-shift-invariant loss'}
+
 
 def main(argv=None):
     ini = 'logging.ini' if os.path.exists('logging.ini') else os.path.join(os.path.dirname(__file__), 'logging.ini')
@@ -105,22 +108,14 @@ def main(argv=None):
     if args.loss_gradient is not None and not args.loss_gradient >= 0:
         logger.error(f'--loss-gradient {args.loss_gradient}: the weight is a number >= 0.')
         return 2
-    if args.loss == 'berhu' and args.model != 'msdn':
-        logger.error(f'--loss berhu is the reverse Huber loss on the linear depths of --model msdn: {args.model or "(no model)"} '
-                     f'has no loss over a pixel grid (dcnf regresses superpixel means through a likelihood).')
-        return 2
-    if args.loss == 'berhu' and args.loss_gradient is not None:
-        logger.error('--loss berhu cannot go with --loss-gradient: the gradient-matching term is defined on differences of log '
-                     'depth and belongs to --loss silog.')
-        return 2
-    if args.loss == 'ssi' and args.model != 'msdn':
-        logger.error(f'--loss ssi is the scale-and-shift-invariant loss on the linear depths of --model msdn: '
+    if args.loss in LINEAR_LOSSES and args.model != 'msdn':
+        logger.error(f'--loss {args.loss} is {LINEAR_LOSSES[args.loss]} on the linear depths of --model msdn: '
                      f'{args.model or "(no model)"} has no loss over a pixel grid (dcnf regresses superpixel means through a '
                      f'likelihood).')
         return 2
-    if args.loss == 'ssi' and args.loss_gradient is not None:
-        logger.error('--loss ssi cannot go with --loss-gradient: the gradient-matching term is defined on differences of log '
-                     'depth and belongs to --loss silog.')
+    if args.loss in LINEAR_LOSSES and args.loss_gradient is not None:
+        logger.error(f'--loss {args.loss} cannot go with --loss-gradient: the gradient-matching term is defined on differences of '
+                     f'log depth and belongs to --loss silog.')
         return 2
     if args.berhu_fraction is not None and args.loss != 'berhu':
         logger.error(f'--berhu-fraction sets the threshold of --loss berhu; --loss {args.loss} has none.')

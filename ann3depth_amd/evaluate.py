@@ -61,6 +61,7 @@ Output: one JSON line on stdout, ``<ckptdir>/<model>_<id>/eval-<global_step>.jso
 evaluate (no checkpoint, no test split) or the request is unsupported (an unknown model, more than one process).
 """
 import argparse
+import collections
 import json
 import os
 import sys
@@ -73,6 +74,13 @@ from .ann3depth import add_segmentation_args, latest_checkpoint, load_checkpoint
 from .feed import DeviceFeed
 
 OUTPUTS = {'msdn': ('coarse', 'fine'), 'dcnf': ('unary', 'crf')}
+# --loss NAME beside silog: what its refusal calls it, the Evaluator's keyword arguments for it, whether the report repeats them
+ExtraLoss = collections.namedtuple('ExtraLoss', 'phrase keywords reported')
+EXTRA_LOSSES = {
+    'berhu': ExtraLoss('the reverse Huber loss',
+                       lambda args: {'berhu_fraction': 0.2 if args.berhu_fraction is None else args.berhu_fraction}, True),
+    'ssi': ExtraLoss('the scale-and-shift-invariant loss', lambda args: {'ssi': True}, False),
+}
 
 
 def _say(msg):
@@ -160,16 +168,15 @@ class Evaluator(MetricRows):
                          max_depth, clamp_lo, clamp_hi, keep_predictions, align)
         self.upsample = upsample
         self.t = torch.empty((replica.B, OUT_H, OUT_W), device=replica.device)
-        self.silog_ws = {}              # per batch size (a3d_silog_loss_fwd's per-sample sums and partials)
-        self.losses = {o: [] for o in OUTPUTS['msdn']}
-        self.berhu_fraction = berhu_fraction
+        # the plain losses reported per output, silog and what was asked for beside it: report key -> (floats a launch writes, the
+        # first the mean over the batch's images; workspace factory; launch(out, target, loss, ws))
+        self.objectives = {'silog': (1, ops.silog_ws, ops.silog_loss_fwd)}
         if berhu_fraction is not None:
-            self.berhu_ws = {}          # per batch size, as silog_ws
-            self.berhu = {o: [] for o in OUTPUTS['msdn']}
-        self.ssi = None
+            self.objectives['berhu'] = (4, ops.berhu_ws, lambda o, t, loss, ws: ops.berhu_loss_fwd(o, t, 0, berhu_fraction, loss, ws))
         if ssi:
-            self.ssi_ws = {}            # per batch size, as silog_ws
-            self.ssi = {o: [] for o in OUTPUTS['msdn']}
+            self.objectives['ssi'] = (4, ops.ssi_ws, lambda o, t, loss, ws: ops.ssi_loss_fwd(o, t, 0, loss, ws))
+        self.loss_ws = {}               # per (key, batch size): the launches' per-sample sums and partials
+        self.losses = {(o, key): [] for o in OUTPUTS['msdn'] for key in self.objectives}
 
     def __call__(self, images, depths, n):
         coarse, fine = self.rep.predict(images, n)
@@ -177,26 +184,13 @@ class Evaluator(MetricRows):
         target = self.t[:n] if self.resolution == 'grid' else depths[:n]
         for name, out in zip(OUTPUTS['msdn'], (coarse, fine)):
             self.judge(name, out, n, target)
-            loss = torch.empty(1, device=out.device)
-            ws = self.silog_ws.get(n)
-            if ws is None:
-                ws = self.silog_ws[n] = ops.silog_ws(n, out.device)
-            ops.silog_loss_fwd(out[:n], self.t[:n], loss, ws)                    # the mean over these n images
-            self.losses[name].append(loss)
-            if self.berhu_fraction is not None:
-                quad = torch.empty(4, device=out.device)
-                ws = self.berhu_ws.get(n)
+            for key, (width, ws_for, launch) in self.objectives.items():
+                loss = torch.empty(width, device=out.device)
+                ws = self.loss_ws.get((key, n))
                 if ws is None:
-                    ws = self.berhu_ws[n] = ops.berhu_ws(n, out.device)
-                ops.berhu_loss_fwd(out[:n], self.t[:n], 0, self.berhu_fraction, quad, ws)
-                self.berhu[name].append(quad[:1])
-            if self.ssi is not None:
-                quad = torch.empty(4, device=out.device)
-                ws = self.ssi_ws.get(n)
-                if ws is None:
-                    ws = self.ssi_ws[n] = ops.ssi_ws(n, out.device)
-                ops.ssi_loss_fwd(out[:n], self.t[:n], 0, quad, ws)
-                self.ssi[name].append(quad[:1])
+                    ws = self.loss_ws[key, n] = ws_for(n, out.device)
+                launch(out[:n], self.t[:n], loss, ws)                            # the mean over these n images
+                self.losses[name, key].append(loss[:1])
         if self.upsample is not None:
             self.judge('fine_joint', self.upsample(fine[:n], images[:n]), n, target)
         self.counts.append(n)
@@ -205,12 +199,8 @@ class Evaluator(MetricRows):
 
     def results(self):
         out = super().results()
-        for name, losses in self.losses.items():
-            out[name]['silog'] = self.mean(losses)
-            if self.berhu_fraction is not None:
-                out[name]['berhu'] = self.mean(self.berhu[name])
-            if self.ssi is not None:
-                out[name]['ssi'] = self.mean(self.ssi[name])
+        for (name, key), losses in self.losses.items():
+            out[name][key] = self.mean(losses)
         return out
 
 
@@ -427,13 +417,10 @@ def main(argv=None):
     if refuse_under_slic(args, _say, (('--upsample joint', args.upsample == 'joint'), ('--observed-nll', args.observed_nll),
                                       ('--condition', args.condition is not None))):
         return 2
-    if (args.loss == 'berhu' or args.berhu_fraction is not None) and args.model != 'msdn':
-        _say(f'--loss berhu reports the reverse Huber loss of the two outputs of --model msdn: {args.model} has no loss over a '
-             f'pixel grid.')
-        return 2
-    if args.loss == 'ssi' and args.model != 'msdn':
-        _say(f'--loss ssi reports the scale-and-shift-invariant loss of the two outputs of --model msdn: {args.model} has no '
-             f'loss over a pixel grid.')
+    loss = 'berhu' if args.berhu_fraction is not None else args.loss         # its own flag speaks for --loss berhu
+    if loss in EXTRA_LOSSES and args.model != 'msdn':
+        _say(f'--loss {loss} reports {EXTRA_LOSSES[loss].phrase} of the two outputs of --model msdn: {args.model} has no loss '
+             f'over a pixel grid.')
         return 2
     if args.berhu_fraction is not None and (args.loss != 'berhu' or not 0 < args.berhu_fraction <= 1):
         _say(f'--berhu-fraction {args.berhu_fraction} sets the threshold of --loss berhu, a fraction in (0, 1] of the largest error.')
@@ -469,10 +456,8 @@ def main(argv=None):
         extra['upsample'] = upsample
     if args.condition is not None:
         extra['condition'] = (args.condition, args.condition_seed)
-    if args.loss == 'berhu':
-        extra['berhu_fraction'] = 0.2 if args.berhu_fraction is None else args.berhu_fraction
-    if args.loss == 'ssi':
-        extra['ssi'] = True
+    loss_kw = EXTRA_LOSSES[args.loss].keywords(args) if args.loss in EXTRA_LOSSES else {}
+    extra.update(loss_kw)
     if args.align != 'none':
         extra['align'] = args.align
     ev = evaluator(replica, args.resolution, args.min_depth, args.max_depth, args.clamp_lo, args.clamp_hi,
@@ -505,10 +490,8 @@ def main(argv=None):
                    sigma_range=upsample.sigma_range)
     if args.condition is not None:
         out.update(condition=args.condition, condition_seed=args.condition_seed)
-    if args.loss == 'berhu':
-        out.update(loss='berhu', berhu_fraction=extra['berhu_fraction'])
-    if args.loss == 'ssi':
-        out.update(loss='ssi')
+    if args.loss in EXTRA_LOSSES:
+        out.update(loss=args.loss, **(loss_kw if EXTRA_LOSSES[args.loss].reported else {}))
     if args.align != 'none':
         out['align'] = args.align
     if args.predictions:

@@ -160,30 +160,34 @@ class Replica:
         return [x.item() for x in st[1:]]
 
 
-# The loss launches of one MSDNReplica: the floats a forward launch writes (the loss their first), the name its four-float
-# buffers go by, the workspace factory, fwd(out, tgt, loss, ws) and bwd(out, tgt, ws, dout, dout16).  fwd and bwd hold the
-# objective's parameters from construction on: a replica's grad_weight, berhu_fraction and valid_range only report them.
-LossLaunches = collections.namedtuple('LossLaunches', 'width name ws fwd bwd')
+# The loss launches of one MSDNReplica, and what else differs between the objectives: the floats a forward launch writes (the loss
+# their first), the name its four-float buffers go by (loss_<name>_c / _f), the summary tags of the words behind the valid
+# fraction as (word, tag), the instance attributes the objective leaves, the workspace factory, fwd(out, tgt, loss, ws) and
+# bwd(out, tgt, ws, dout, dout16).  fwd and bwd hold the objective's parameters from construction on: a replica's grad_weight,
+# berhu_fraction and valid_range only report them.  A new objective is one more record here.
+LossLaunches = collections.namedtuple('LossLaunches', 'width name tags attrs ws fwd bwd')
+MSDN_OBJECTIVES = ('silog', 'berhu', 'ssi')
 
 
 def msdn_loss_launches(objective, berhu_fraction, grad_weight, masked):
-    """MSDNReplica's choice among the five objectives, made once."""
+    """MSDNReplica's choice among the five launch sets, made once."""
     if objective == 'ssi':                # loss, valid fraction, mean scale, mean shift (ops.ssi_loss_fwd)
-        return LossLaunches(4, 'ssi', ops.ssi_ws,
+        return LossLaunches(4, 'ssi', ((2, 'scale'), (3, 'shift')), {'objective': objective}, ops.ssi_ws,
                             lambda out, tgt, loss, ws: ops.ssi_loss_fwd(out, tgt, masked, loss, ws),
                             lambda out, tgt, ws, dout, d16: ops.ssi_loss_bwd(out, tgt, masked, ws, dout, d16))
     if objective == 'berhu':              # loss, valid fraction, mean threshold, quadratic share (ops.berhu_loss_fwd)
-        return LossLaunches(4, 'berhu', ops.berhu_ws,
+        return LossLaunches(4, 'berhu', ((2, 'threshold'), (3, 'quadratic')),
+                            {'objective': objective, 'berhu_fraction': berhu_fraction}, ops.berhu_ws,
                             lambda out, tgt, loss, ws: ops.berhu_loss_fwd(out, tgt, masked, berhu_fraction, loss, ws),
                             lambda out, tgt, ws, dout, d16: ops.berhu_loss_bwd(out, tgt, masked, berhu_fraction, ws, dout, d16))
     if grad_weight > 0:                   # total, valid fraction, silog part, gradient part (ops.silog_grad_loss_fwd)
         grid = (OUT_H, OUT_W, masked, grad_weight)
-        return LossLaunches(4, 'quad', ops.silog_grad_ws,
+        return LossLaunches(4, 'quad', ((3, 'grad'),), {}, ops.silog_grad_ws,
                             lambda out, tgt, loss, ws: ops.silog_grad_loss_fwd(out, tgt, *grid, loss, ws),
                             lambda out, tgt, ws, dout, d16: ops.silog_grad_loss_bwd(out, tgt, *grid, ws, dout, d16))
     if masked:                            # the masked loss writes the valid fraction of the target behind the loss
-        return LossLaunches(2, None, ops.silog_masked_ws, ops.silog_masked_loss_fwd, ops.silog_masked_loss_bwd)
-    return LossLaunches(1, None, ops.silog_ws, ops.silog_loss_fwd, ops.silog_loss_bwd)
+        return LossLaunches(2, None, (), {}, ops.silog_masked_ws, ops.silog_masked_loss_fwd, ops.silog_masked_loss_bwd)
+    return LossLaunches(1, None, (), {}, ops.silog_ws, ops.silog_loss_fwd, ops.silog_loss_bwd)
 
 
 class MSDNReplica(Replica):
@@ -209,12 +213,11 @@ class MSDNReplica(Replica):
         scale-and-shift-invariant loss of Ranftl et al. 2020 on linear depth (ops.ssi_loss_fwd / _bwd): per sample the squared
         error left after the best scale and shift of the output, the objective that matches evaluate's --align affine.
         'silog': today's launches."""
-        if objective not in ('silog', 'berhu', 'ssi'):
-            raise ValueError(f"objective {objective!r}: 'silog', 'berhu' or 'ssi'")
+        if objective not in MSDN_OBJECTIVES:
+            raise ValueError(f"objective {objective!r}: {', '.join(map(repr, MSDN_OBJECTIVES[:-1]))} or {MSDN_OBJECTIVES[-1]!r}")
         berhu_fraction = float(berhu_fraction)
         if not 0 < berhu_fraction <= 1:
             raise ValueError(f'berhu_fraction {berhu_fraction!r}: the threshold is a fraction in (0, 1] of the largest error')
-        berhu = objective == 'berhu'
         grad_weight = float(grad_weight)
         if not grad_weight >= 0:
             raise ValueError(f'grad_weight {grad_weight!r}: the weight of the gradient-matching term is a number >= 0')
@@ -222,12 +225,9 @@ class MSDNReplica(Replica):
             raise ValueError(f"objective {objective!r} with grad_weight {grad_weight!r}: the gradient-matching term is defined "
                              f'on log differences and belongs to the silog objective')
         self.grad_weight = grad_weight
-        if berhu:                         # under 'silog' the instance gains no attribute and no buffer
-            self.objective, self.berhu_fraction = objective, berhu_fraction
-        elif objective == 'ssi':
-            self.objective = objective
         self.valid_range = check_valid_range(valid_range)
         self._loss = msdn_loss_launches(objective, berhu_fraction, grad_weight, self.valid_range is not None)
+        vars(self).update(self._loss.attrs)      # under 'silog' the instance gains no attribute and no buffer
         # keep_dense_grads=False (the training driver and bench.py on one GPU): under the reference's frozen optimizer the
         # gradient of the two dense kernels (268 MB) goes straight from the matrix cores into ApplyAdam's m slot
         # (ops.dense_bwd_filter_adam_tf1) and is never written; grad('coarse/dense/...') is then stale.  A data-parallel
@@ -341,7 +341,7 @@ class MSDNReplica(Replica):
         self.f2 = buf(B, OUT_H, OUT_W, 64)
         self.fine = buf(B, OUT_H, OUT_W, 1)
         # what a loss launch writes: 4, 2 or 1 floats (msdn_loss_launches).  loss_coarse / loss_fine are their first, loss_pair_*
-        # the first two where there are as many, loss_berhu_* / loss_ssi_* / loss_quad_* all four
+        # the first two where there are as many, loss_<name>_* all four
         width, name = self._loss.width, self._loss.name
         self.loss_out_c = buf(width); self.loss_out_f = buf(width)
         self.loss_coarse = self.loss_out_c[:1]; self.loss_fine = self.loss_out_f[:1]
@@ -743,17 +743,9 @@ class MSDNReplica(Replica):
                'optimizers/Phase': out['phase']}
         if self.valid_range is not None:                 # NON-REFERENCE: share of the target pixels that hold a depth
             rec['valid_fraction'] = float(self.loss_pair_c[1])
-        if self.grad_weight > 0:                         # NON-REFERENCE: the gradient-matching terms, before their weight
-            rec['loss/coarse_grad'] = float(self.loss_quad_c[3])
-            rec['loss/fine_grad'] = float(self.loss_quad_f[3])
-        if self.objective == 'berhu':                    # NON-REFERENCE: the mean threshold, the share of quadratic pixels
-            for name, quad in (('coarse', self.loss_berhu_c), ('fine', self.loss_berhu_f)):
-                rec[f'loss/{name}_threshold'] = float(quad[2])
-                rec[f'loss/{name}_quadratic'] = float(quad[3])
-        if self.objective == 'ssi':                      # NON-REFERENCE: the mean fitted scale and shift of the outputs
-            for name, quad in (('coarse', self.loss_ssi_c), ('fine', self.loss_ssi_f)):
-                rec[f'loss/{name}_scale'] = float(quad[2])
-                rec[f'loss/{name}_shift'] = float(quad[3])
+        for name, quad in (('coarse', self.loss_out_c), ('fine', self.loss_out_f)):      # NON-REFERENCE: the objective's own words
+            for word, tag in self._loss.tags:
+                rec[f'loss/{name}_{tag}'] = float(quad[word])
         return rec
 
     def summary_images(self):
@@ -1745,7 +1737,7 @@ class DCNFReplica(Replica):
         self.output = torch.empty((batchsize, DCNF_IMG_H, DCNF_IMG_W, 1), device=dev)
         self.sims = self.r = self.loss = self.loss_per_image = self.dz = self.dr = None
         self.crf = torch.empty((batchsize, self.nsp), device=dev)                          # predict(): the MAP depths
-        self.status = torch.empty((batchsize,), dtype=torch.int32, device=dev)
+        self.status = torch.zeros((batchsize,), dtype=torch.int32, device=dev)    # the dense 6 x 8 step never writes it
         self.labels = None
         if self.slic:
             self.labels = torch.empty((batchsize, DCNF_IMG_H, DCNF_IMG_W), dtype=torch.int32, device=dev)

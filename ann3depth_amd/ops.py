@@ -3,6 +3,7 @@
 PyTorch only owns memory and streams here.  Every function enqueues HIP kernels on the current stream through the
 C ABI (include/a3d.h) and returns without synchronising.  Layouts are TensorFlow's (NHWC / HWIO / [in,out]).
 """
+import collections
 import ctypes
 
 import torch
@@ -435,169 +436,165 @@ def _loss_ws_floats(k, b):
     return k * b + 1 + k * b * SILOG_PARTS
 
 
+def _ssi_ws_floats(b):
+    """A3DI_WS_FLOATS(b): the ticket and a pad, four words per sample, ten per block (four of them float64 pairs)."""
+    return 4 * b + 2 + 10 * b * SILOG_PARTS
+
+
 def _ld16(dout16):
     """The pitch argument that goes with an optional bf16 copy of the gradient."""
     return 0 if dout16 is None else dout16.shape[-1]
 
 
-def silog_ws(b, device):
-    """Workspace of silog_loss_fwd / _bwd for a batch of b (or any smaller one): A3D_SILOG_WS_FLOATS(b) zeros (the ticket, its
-    first word, must start at zero)."""
-    return torch.zeros(_loss_ws_floats(2, b), device=device)
+# What a loss launch set passes between (b, ...) and the buffers, with its checks: ((the sizes after b), (the arguments between tgt
+# and the buffers)) from who's out, tgt and the caller's own arguments.
+def _plain_args(who, out, tgt):
+    return (out.numel() // out.shape[0],), ()
 
 
-def silog_loss_fwd(out, tgt, loss, ws):
-    b = out.shape[0]
-    assert ws.numel() >= _loss_ws_floats(2, b), 'silog workspace too small: allocate it with ops.silog_ws(b, device)'
-    npix = out.numel() // b
-    check(_lib.load().a3d_silog_loss_fwd(b, npix, _ptr(out), _ptr(tgt), _ptr(loss), _ptr(ws), _stream()),
-          'a3d_silog_loss_fwd')
-    return loss
-
-
-def silog_loss_bwd(out, tgt, ws, dout, dout16=None):
-    """dout16: optional bfloat16 [b, ld >= npix], receives the same gradient (columns npix.. stay as they are: keep them zero)."""
-    b = out.shape[0]
-    npix = out.numel() // b
-    check(_lib.load().a3d_silog_loss_bwd_ex(b, npix, _ptr(out), _ptr(tgt), _ptr(ws), _ptr(dout), _ptr(dout16),
-                                            _ld16(dout16), _stream()), 'a3d_silog_loss_bwd_ex')
-    return dout
-
-
-def silog_masked_ws(b, device):
-    """Workspace of silog_masked_loss_fwd / _bwd for a batch of b (or any smaller one): A3DX_SILOG_MASKED_WS_FLOATS(b)
-    zeros (the ticket, its first word, must start at zero)."""
-    return torch.zeros(_loss_ws_floats(3, b), device=device)
-
-
-def silog_masked_loss_fwd(out, tgt, loss, ws):
-    """NON-REFERENCE: the loss over the finite targets only (a3dx_silog_masked_loss_fwd).  loss: 2 floats, the loss and the
-    fraction of valid target pixels."""
-    b = out.shape[0]
-    assert ws.numel() >= _loss_ws_floats(3, b), 'silog workspace too small: allocate it with ops.silog_masked_ws(b, device)'
-    assert loss.numel() >= 2 and loss.is_contiguous(), 'silog_masked_loss_fwd writes two floats'
-    npix = out.numel() // b
-    check(_lib.load().a3dx_silog_masked_loss_fwd(b, npix, _ptr(out), _ptr(tgt), _ptr(loss), _ptr(ws), _stream()),
-          'a3dx_silog_masked_loss_fwd')
-    return loss
-
-
-def silog_masked_loss_bwd(out, tgt, ws, dout, dout16=None):
-    """dout16 as silog_loss_bwd's."""
-    b = out.shape[0]
-    npix = out.numel() // b
-    check(_lib.load().a3dx_silog_masked_loss_bwd_ex(b, npix, _ptr(out), _ptr(tgt), _ptr(ws), _ptr(dout), _ptr(dout16),
-                                                   _ld16(dout16), _stream()), 'a3dx_silog_masked_loss_bwd_ex')
-    return dout
-
-
-def silog_grad_ws(b, device):
-    """Workspace of silog_grad_loss_fwd / _bwd for a batch of b (or any smaller one): A3DG_WS_FLOATS(b) zeros (the ticket,
-    its first word, must start at zero)."""
-    return torch.zeros(_loss_ws_floats(5, b), device=device)
-
-
-def _grad_loss_args(who, out, h, w, grad_weight):
+def _grad_loss_args(who, out, tgt, h, w, masked, grad_weight):
     b = out.shape[0]
     assert out.numel() == b * h * w, f'{who}: out holds {out.numel()} values, not {b} x {h} x {w}'
     grad_weight = float(grad_weight)
     if not grad_weight >= 0:
         raise ValueError(f'{who}: grad_weight {grad_weight!r} must be a number >= 0')
-    return b, grad_weight
+    return (h, w), (int(bool(masked)), grad_weight)
+
+
+def _berhu_args(who, out, tgt, masked, fraction):
+    assert out.numel() == tgt.numel(), f'{who}: out holds {out.numel()} values, tgt {tgt.numel()}'
+    fraction = float(fraction)
+    if not 0 < fraction <= 1:
+        raise ValueError(f'{who}: fraction {fraction!r} must lie in (0, 1]')
+    return (out.numel() // out.shape[0],), (int(bool(masked)), fraction)
+
+
+def _ssi_args(who, out, tgt, masked):
+    assert out.numel() == tgt.numel(), f'{who}: out holds {out.numel()} values, tgt {tgt.numel()}'
+    return (out.numel() // out.shape[0],), (int(bool(masked)),)
+
+
+# The five loss launch sets, by the name their public functions <name>_ws, <name>_loss_fwd and <name>_loss_bwd carry: the forward
+# and backward entry points, the workspace in floats for a batch of b, the floats a forward writes, and the arguments above.
+_LossLaunch = collections.namedtuple('_LossLaunch', 'fwd bwd ws_floats writes args')
+_LOSSES = {
+    'silog': _LossLaunch('a3d_silog_loss_fwd', 'a3d_silog_loss_bwd_ex', lambda b: _loss_ws_floats(2, b), 1, _plain_args),
+    'silog_masked': _LossLaunch('a3dx_silog_masked_loss_fwd', 'a3dx_silog_masked_loss_bwd_ex', lambda b: _loss_ws_floats(3, b), 2,
+                                _plain_args),
+    'silog_grad': _LossLaunch('a3dg_silog_grad_loss_fwd', 'a3dg_silog_grad_loss_bwd_ex', lambda b: _loss_ws_floats(5, b), 4,
+                              _grad_loss_args),
+    'berhu': _LossLaunch('a3dh_berhu_loss_fwd', 'a3dh_berhu_loss_bwd_ex', lambda b: _loss_ws_floats(3, b), 4, _berhu_args),
+    'ssi': _LossLaunch('a3di_ssi_loss_fwd', 'a3di_ssi_loss_bwd_ex', _ssi_ws_floats, 4, _ssi_args),
+}
+
+
+def _loss_ws(name, b, device):
+    """The workspace of one launch set for a batch of b (or any smaller one): zeros, since the ticket, its first word, must
+    start at zero."""
+    return torch.zeros(_LOSSES[name].ws_floats(b), device=device)
+
+
+def _loss_fwd(name, out, tgt, loss, ws, *more):
+    launch = _LOSSES[name]
+    b = out.shape[0]
+    dims, middle = launch.args(name + '_loss_fwd', out, tgt, *more)
+    assert ws.numel() >= launch.ws_floats(b), \
+        f'{name.split("_")[0]} workspace too small: allocate it with ops.{name}_ws(b, device)'
+    if launch.writes > 1:
+        assert loss.numel() >= launch.writes and loss.is_contiguous(), \
+            f'{name}_loss_fwd writes {("two", "four")[launch.writes // 4]} floats'
+    check(getattr(_lib.load(), launch.fwd)(b, *dims, _ptr(out), _ptr(tgt), *middle, _ptr(loss), _ptr(ws), _stream()), launch.fwd)
+    return loss
+
+
+def _loss_bwd(name, out, tgt, ws, dout, dout16, *more):
+    launch = _LOSSES[name]
+    dims, middle = launch.args(name + '_loss_bwd', out, tgt, *more)
+    check(getattr(_lib.load(), launch.bwd)(out.shape[0], *dims, _ptr(out), _ptr(tgt), *middle, _ptr(ws), _ptr(dout), _ptr(dout16),
+                                          _ld16(dout16), _stream()), launch.bwd)
+    return dout
+
+
+def silog_ws(b, device):
+    """Workspace of silog_loss_fwd / _bwd: A3D_SILOG_WS_FLOATS(b) zeros (see _loss_ws)."""
+    return _loss_ws('silog', b, device)
+
+
+def silog_loss_fwd(out, tgt, loss, ws):
+    return _loss_fwd('silog', out, tgt, loss, ws)
+
+
+def silog_loss_bwd(out, tgt, ws, dout, dout16=None):
+    """dout16: optional bfloat16 [b, ld >= npix], receives the same gradient (columns npix.. stay as they are: keep them zero)."""
+    return _loss_bwd('silog', out, tgt, ws, dout, dout16)
+
+
+def silog_masked_ws(b, device):
+    """Workspace of silog_masked_loss_fwd / _bwd: A3DX_SILOG_MASKED_WS_FLOATS(b) zeros (see _loss_ws)."""
+    return _loss_ws('silog_masked', b, device)
+
+
+def silog_masked_loss_fwd(out, tgt, loss, ws):
+    """NON-REFERENCE: the loss over the finite targets only (a3dx_silog_masked_loss_fwd).  loss: 2 floats, the loss and the
+    fraction of valid target pixels."""
+    return _loss_fwd('silog_masked', out, tgt, loss, ws)
+
+
+def silog_masked_loss_bwd(out, tgt, ws, dout, dout16=None):
+    """dout16 as silog_loss_bwd's."""
+    return _loss_bwd('silog_masked', out, tgt, ws, dout, dout16)
+
+
+def silog_grad_ws(b, device):
+    """Workspace of silog_grad_loss_fwd / _bwd: A3DG_WS_FLOATS(b) zeros (see _loss_ws)."""
+    return _loss_ws('silog_grad', b, device)
 
 
 def silog_grad_loss_fwd(out, tgt, h, w, masked, grad_weight, loss, ws):
     """NON-REFERENCE: the scale-invariant loss plus grad_weight times the gradient-matching term of Eigen & Fergus 2015 over
     the horizontal and vertical neighbour pairs of the h x w grid (a3dg_silog_grad_loss_fwd).  masked: only finite targets
     count, as in silog_masked_loss_fwd.  loss: 4 floats — the total, the valid fraction, the silog part, the gradient part."""
-    b, grad_weight = _grad_loss_args('silog_grad_loss_fwd', out, h, w, grad_weight)
-    assert ws.numel() >= _loss_ws_floats(5, b), 'silog workspace too small: allocate it with ops.silog_grad_ws(b, device)'
-    assert loss.numel() >= 4 and loss.is_contiguous(), 'silog_grad_loss_fwd writes four floats'
-    check(_lib.load().a3dg_silog_grad_loss_fwd(b, h, w, _ptr(out), _ptr(tgt), int(bool(masked)), grad_weight, _ptr(loss),
-                                               _ptr(ws), _stream()), 'a3dg_silog_grad_loss_fwd')
-    return loss
+    return _loss_fwd('silog_grad', out, tgt, loss, ws, h, w, masked, grad_weight)
 
 
 def silog_grad_loss_bwd(out, tgt, h, w, masked, grad_weight, ws, dout, dout16=None):
     """dout16 as silog_loss_bwd's.  masked and grad_weight as in the forward call that filled ws."""
-    b, grad_weight = _grad_loss_args('silog_grad_loss_bwd', out, h, w, grad_weight)
-    check(_lib.load().a3dg_silog_grad_loss_bwd_ex(b, h, w, _ptr(out), _ptr(tgt), int(bool(masked)), grad_weight, _ptr(ws),
-                                                  _ptr(dout), _ptr(dout16), _ld16(dout16), _stream()),
-          'a3dg_silog_grad_loss_bwd_ex')
-    return dout
+    return _loss_bwd('silog_grad', out, tgt, ws, dout, dout16, h, w, masked, grad_weight)
 
 
 def berhu_ws(b, device):
-    """Workspace of berhu_loss_fwd / _bwd for a batch of b (or any smaller one): A3DH_WS_FLOATS(b) zeros (the ticket, its
-    first word, must start at zero)."""
-    return torch.zeros(_loss_ws_floats(3, b), device=device)
-
-
-def _berhu_args(who, out, tgt, fraction):
-    b = out.shape[0]
-    assert out.numel() == tgt.numel(), f'{who}: out holds {out.numel()} values, tgt {tgt.numel()}'
-    fraction = float(fraction)
-    if not 0 < fraction <= 1:
-        raise ValueError(f'{who}: fraction {fraction!r} must lie in (0, 1]')
-    return b, out.numel() // b, fraction
+    """Workspace of berhu_loss_fwd / _bwd: A3DH_WS_FLOATS(b) zeros (see _loss_ws)."""
+    return _loss_ws('berhu', b, device)
 
 
 def berhu_loss_fwd(out, tgt, masked, fraction, loss, ws):
     """NON-REFERENCE: the reverse Huber loss of Laina et al. 2016 on linear depth, with the threshold fraction x the largest
     error of each sample (a3dh_berhu_loss_fwd, two launches).  masked: only finite targets count, as in silog_masked_loss_fwd.
     loss: 4 floats — the loss, the valid fraction, the mean threshold, the share of the counting pixels that are quadratic."""
-    b, npix, fraction = _berhu_args('berhu_loss_fwd', out, tgt, fraction)
-    assert ws.numel() >= _loss_ws_floats(3, b), 'berhu workspace too small: allocate it with ops.berhu_ws(b, device)'
-    assert loss.numel() >= 4 and loss.is_contiguous(), 'berhu_loss_fwd writes four floats'
-    check(_lib.load().a3dh_berhu_loss_fwd(b, npix, _ptr(out), _ptr(tgt), int(bool(masked)), fraction, _ptr(loss), _ptr(ws),
-                                          _stream()), 'a3dh_berhu_loss_fwd')
-    return loss
+    return _loss_fwd('berhu', out, tgt, loss, ws, masked, fraction)
 
 
 def berhu_loss_bwd(out, tgt, masked, fraction, ws, dout, dout16=None):
     """dout16 as silog_loss_bwd's.  masked and fraction as in the forward call that filled ws."""
-    b, npix, fraction = _berhu_args('berhu_loss_bwd', out, tgt, fraction)
-    check(_lib.load().a3dh_berhu_loss_bwd_ex(b, npix, _ptr(out), _ptr(tgt), int(bool(masked)), fraction, _ptr(ws), _ptr(dout),
-                                             _ptr(dout16), _ld16(dout16), _stream()), 'a3dh_berhu_loss_bwd_ex')
-    return dout
-
-
-def _ssi_ws_floats(b):
-    """A3DI_WS_FLOATS(b): the ticket and a pad, four words per sample, ten per block (four of them float64 pairs)."""
-    return 4 * b + 2 + 10 * b * SILOG_PARTS
+    return _loss_bwd('berhu', out, tgt, ws, dout, dout16, masked, fraction)
 
 
 def ssi_ws(b, device):
-    """Workspace of ssi_loss_fwd / _bwd for a batch of b (or any smaller one): A3DI_WS_FLOATS(b) zeros (the ticket, its
-    first word, must start at zero).  Word 2 + 4 i + {0, 1, 2, 3} holds sample i's scale, shift, count and flag (0 fitted,
-    1 degenerate, 2 poisoned) after a forward call."""
-    return torch.zeros(_ssi_ws_floats(b), device=device)
-
-
-def _ssi_args(who, out, tgt):
-    b = out.shape[0]
-    assert out.numel() == tgt.numel(), f'{who}: out holds {out.numel()} values, tgt {tgt.numel()}'
-    return b, out.numel() // b
+    """Workspace of ssi_loss_fwd / _bwd: A3DI_WS_FLOATS(b) zeros (see _loss_ws).  Word 2 + 4 i + {0, 1, 2, 3} holds sample i's
+    scale, shift, count and flag (0 fitted, 1 degenerate, 2 poisoned) after a forward call."""
+    return _loss_ws('ssi', b, device)
 
 
 def ssi_loss_fwd(out, tgt, masked, loss, ws):
     """NON-REFERENCE: the least-squares scale-and-shift-invariant loss of Ranftl et al. 2020 on linear depth: per sample the
     squared error left after the best scale and shift of the output (a3di_ssi_loss_fwd, two launches).  masked: only finite
     targets count, as in silog_masked_loss_fwd.  loss: 4 floats — the loss, the valid fraction, the mean scale, the mean shift."""
-    b, npix = _ssi_args('ssi_loss_fwd', out, tgt)
-    assert ws.numel() >= _ssi_ws_floats(b), 'ssi workspace too small: allocate it with ops.ssi_ws(b, device)'
-    assert loss.numel() >= 4 and loss.is_contiguous(), 'ssi_loss_fwd writes four floats'
-    check(_lib.load().a3di_ssi_loss_fwd(b, npix, _ptr(out), _ptr(tgt), int(bool(masked)), _ptr(loss), _ptr(ws), _stream()),
-          'a3di_ssi_loss_fwd')
-    return loss
+    return _loss_fwd('ssi', out, tgt, loss, ws, masked)
 
 
 def ssi_loss_bwd(out, tgt, masked, ws, dout, dout16=None):
     """dout16 as silog_loss_bwd's.  masked as in the forward call that filled ws."""
-    b, npix = _ssi_args('ssi_loss_bwd', out, tgt)
-    check(_lib.load().a3di_ssi_loss_bwd_ex(b, npix, _ptr(out), _ptr(tgt), int(bool(masked)), _ptr(ws), _ptr(dout),
-                                           _ptr(dout16), _ld16(dout16), _stream()), 'a3di_ssi_loss_bwd_ex')
-    return dout
+    return _loss_bwd('ssi', out, tgt, ws, dout, dout16, masked)
 
 
 METRIC_COLUMNS = ('n', 'abs_rel', 'sq_rel', 'sq', 'log', 'log_sq', 'log10', 'delta1', 'delta2', 'delta3', 'nonfinite')

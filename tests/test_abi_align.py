@@ -2,39 +2,16 @@
 points, as tests/test_abi_berhu.py holds include/a3d_berhu.h to its exports and bindings; bad arguments are refused before any
 launch (no GPU needed: the checks come first)."""
 import ctypes
-import os
 import re
-import subprocess
 
+import abi_surface
 from ann3depth_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {'a3da_depth_align_ws_bytes', 'a3da_depth_align', 'a3da_depth_metrics_aligned', 'a3da_affine_apply'}
 
 
 def test_extension_header_exports_and_bindings_agree():
-    lib = _lib.load()
-    text = open(os.path.join(ROOT, 'include', 'a3d_align.h')).read()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(a3da_[a-z0-9_]+)\s*\(', code))
-    assert declared == NAMES
-    assert not re.findall(r'\ba3d[a-z]?_[a-z0-9_]+\s*\(', re.sub(r'\ba3da_', 'a_', code))     # nothing of another surface is declared here
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r' T (a3da_[a-z0-9_]+)', out)) == declared == set(_lib.ALIGN_SIGNATURES)
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.PAIR_SIGNATURES) | set(_lib.TEXTURE_SIGNATURES)
-              | set(_lib.GRADLOSS_SIGNATURES) | set(_lib.CRF_VALID_SIGNATURES) | set(_lib.FCSP_SIGNATURES)
-              | set(_lib.CRF_BAND_SIGNATURES) | set(_lib.WINO_SIGNATURES) | set(_lib.UPSAMPLE_SIGNATURES)
-              | set(_lib.POSTERIOR_SIGNATURES) | set(_lib.WINO_GRAD_SIGNATURES) | set(_lib.SLIC_SIGNATURES)
-              | set(_lib.WINO_BWD_SIGNATURES) | set(_lib.BERHU_SIGNATURES))
-    assert not set(_lib.ALIGN_SIGNATURES) & others
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.ALIGN_SIGNATURES[name][1]
-    # the binding's argument lists are the header's: int / float / size_t / pointer, position by position
-    for name in declared:
-        params = re.search(name + r'\s*\(([^)]*)\)', code, flags=re.S).group(1).split(',')
-        kinds = [ctypes.c_void_p if '*' in p else ctypes.c_float if 'float' in p else ctypes.c_size_t if 'size_t' in p
-                 else ctypes.c_int for p in params]
-        assert kinds == _lib.ALIGN_SIGNATURES[name][1], name
+    text, code = abi_surface.check('a3da_', NAMES)
     assert _lib.ALIGN_SIGNATURES['a3da_depth_align_ws_bytes'][0] is ctypes.c_size_t
     # a3da_depth_metrics_aligned is a3d_depth_metrics with coef before rows
     plain = list(_lib.SIGNATURES['a3d_depth_metrics'][1])

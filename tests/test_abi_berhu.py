@@ -2,37 +2,14 @@
 as tests/test_abi_gradloss.py holds include/a3d_gradloss.h to its exports and bindings; bad arguments are refused before any
 launch (no GPU needed: the checks come first)."""
 import ctypes
-import os
 import re
-import subprocess
 
+import abi_surface
 from ann3depth_amd import _lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_extension_header_exports_and_bindings_agree():
-    lib = _lib.load()
-    text = open(os.path.join(ROOT, 'include', 'a3d_berhu.h')).read()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(a3dh_[a-z0-9_]+)\s*\(', code))
-    assert declared == {'a3dh_berhu_loss_fwd', 'a3dh_berhu_loss_bwd_ex'}
-    assert not re.findall(r'\ba3d[a-z]?_[a-z0-9_]+\s*\(', re.sub(r'\ba3dh_', 'h_', code))     # nothing of another surface is declared here
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r' T (a3dh_[a-z0-9_]+)', out)) == declared == set(_lib.BERHU_SIGNATURES)
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.PAIR_SIGNATURES) | set(_lib.TEXTURE_SIGNATURES)
-              | set(_lib.GRADLOSS_SIGNATURES) | set(_lib.CRF_VALID_SIGNATURES) | set(_lib.FCSP_SIGNATURES)
-              | set(_lib.CRF_BAND_SIGNATURES) | set(_lib.WINO_SIGNATURES) | set(_lib.UPSAMPLE_SIGNATURES)
-              | set(_lib.POSTERIOR_SIGNATURES) | set(_lib.WINO_GRAD_SIGNATURES) | set(_lib.SLIC_SIGNATURES)
-              | set(_lib.WINO_BWD_SIGNATURES))
-    assert not set(_lib.BERHU_SIGNATURES) & others
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.BERHU_SIGNATURES[name][1]
-    # the binding's argument lists are the header's: int / float / pointer, position by position
-    for name in declared:
-        params = re.search(name + r'\s*\(([^)]*)\)', code, flags=re.S).group(1).split(',')
-        kinds = [ctypes.c_void_p if '*' in p else ctypes.c_float if 'float' in p else ctypes.c_int for p in params]
-        assert kinds == _lib.BERHU_SIGNATURES[name][1], name
+    text, code = abi_surface.check('a3dh_', {'a3dh_berhu_loss_fwd', 'a3dh_berhu_loss_bwd_ex'})
     assert re.search(r'#define A3DH_WS_FLOATS\(b\) \(\(b\) \* 3 \+ 1 \+ \(b\) \* 3 \* A3D_SILOG_PARTS\)', text)
     for words in ('PER SAMPLE', 'A3D_EINVAL', 'POISONED', 'No workgroup waits for another', 'no floating-point atomics',
                   'ascending order', 'off = 32, 16, 8, 4, 2, 1'):

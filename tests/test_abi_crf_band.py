@@ -2,33 +2,16 @@
 entry points, as the other tests/test_abi_*.py hold their headers; bad arguments are refused before any launch (no GPU
 needed: the checks come first)."""
 import ctypes
-import os
 import re
-import subprocess
 
+import abi_surface
 from ann3depth_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {'a3db_crf_band_nll', 'a3db_crf_band_map'}
 
 
 def test_crf_band_header_exports_and_bindings_agree():
-    lib = _lib.load()
-    text = open(os.path.join(ROOT, 'include', 'a3d_crf_band.h')).read()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(a3db_[a-z0-9_]+)\s*\(', code))
-    assert declared == NAMES
-    assert not re.findall(r'\ba3d[a-z]?_[a-z0-9_]+\s*\(', re.sub(r'\ba3db_', 'b_', code))     # nothing of another surface
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r' T (a3db_[a-z0-9_]+)', out)) == declared == set(_lib.CRF_BAND_SIGNATURES)
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.PAIR_SIGNATURES) | set(_lib.TEXTURE_SIGNATURES)
-              | set(_lib.GRADLOSS_SIGNATURES) | set(_lib.CRF_VALID_SIGNATURES) | set(_lib.FCSP_SIGNATURES))
-    assert not set(_lib.CRF_BAND_SIGNATURES) & others
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.CRF_BAND_SIGNATURES[name][1]
-        assert getattr(lib, name).restype == _lib.CRF_BAND_SIGNATURES[name][0]
-        args = re.search(name + r'\s*\((.*?)\)\s*;', code, flags=re.S).group(1)
-        assert len(args.split(',')) == len(_lib.CRF_BAND_SIGNATURES[name][1]), name
+    text, code = abi_surface.check('a3db_', NAMES)
     # a3dv_crf_loss_observed's arguments with band after nsp and mu in the place of nobs
     obs = _lib.CRF_VALID_SIGNATURES['a3dv_crf_loss_observed'][1]
     assert _lib.CRF_BAND_SIGNATURES['a3db_crf_band_nll'][1] == obs[:2] + [ctypes.c_int] + obs[2:]

@@ -2,33 +2,16 @@
 points, as tests/test_abi_texture.py and its siblings hold the other headers; bad arguments are refused before any launch
 (no GPU needed: the checks come first)."""
 import ctypes
-import os
 import re
-import subprocess
 
+import abi_surface
 from ann3depth_amd import _lib, ops
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {'a3df_superpixel_pool_fwd', 'a3df_superpixel_pool_bwd'}
 
 
 def test_fcsp_header_exports_and_bindings_agree():
-    lib = _lib.load()
-    text = open(os.path.join(ROOT, 'include', 'a3d_fcsp.h')).read()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(a3df_[a-z0-9_]+)\s*\(', code))
-    assert declared == NAMES
-    assert not re.findall(r'\ba3d[a-eg-z]?_[a-z0-9_]+\s*\(', code)          # nothing of another surface is declared here
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r' T (a3df_[a-z0-9_]+)', out)) == declared == set(_lib.FCSP_SIGNATURES)
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.PAIR_SIGNATURES) | set(_lib.TEXTURE_SIGNATURES)
-              | set(_lib.GRADLOSS_SIGNATURES) | set(_lib.CRF_VALID_SIGNATURES))
-    assert not set(_lib.FCSP_SIGNATURES) & others
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.FCSP_SIGNATURES[name][1]
-        assert getattr(lib, name).restype == _lib.FCSP_SIGNATURES[name][0]
-        args = re.search(name + r'\s*\((.*?)\)\s*;', code, flags=re.S).group(1)   # one C argument per binding entry
-        assert len(args.split(',')) == len(_lib.FCSP_SIGNATURES[name][1]), name
+    text, code = abi_surface.check('a3df_', NAMES)
     assert _lib.FCSP_SIGNATURES['a3df_superpixel_pool_fwd'] == _lib.FCSP_SIGNATURES['a3df_superpixel_pool_bwd']
     cap = int(re.search(r'#define\s+A3DF_MAX_SP\s+(\d+)\b', code).group(1))
     assert cap >= 40 and cap == ops.FCSP_MAX_SP

@@ -4,31 +4,15 @@ launch (no GPU needed: the checks come first)."""
 import ctypes
 import os
 import re
-import subprocess
 
+import abi_surface
 from ann3depth_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_extension_header_exports_and_bindings_agree():
-    lib = _lib.load()
-    text = open(os.path.join(ROOT, 'include', 'a3d_gradloss.h')).read()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(a3dg_[a-z0-9_]+)\s*\(', code))
-    assert declared == {'a3dg_silog_grad_loss_fwd', 'a3dg_silog_grad_loss_bwd_ex'}
-    assert not re.findall(r'\ba3d[a-z]?_[a-z0-9_]+\s*\(', re.sub(r'\ba3dg_', 'g_', code))     # nothing of another surface is declared here
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r' T (a3dg_[a-z0-9_]+)', out)) == declared == set(_lib.GRADLOSS_SIGNATURES)
-    others = set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.PAIR_SIGNATURES) | set(_lib.TEXTURE_SIGNATURES)
-    assert not set(_lib.GRADLOSS_SIGNATURES) & others
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.GRADLOSS_SIGNATURES[name][1]
-    # the binding's argument lists are the header's: int / float / pointer, position by position
-    for name in declared:
-        params = re.search(name + r'\s*\(([^)]*)\)', code, flags=re.S).group(1).split(',')
-        kinds = [ctypes.c_void_p if '*' in p else ctypes.c_float if 'float' in p else ctypes.c_int for p in params]
-        assert kinds == _lib.GRADLOSS_SIGNATURES[name][1], name
+    text, code = abi_surface.check('a3dg_', {'a3dg_silog_grad_loss_fwd', 'a3dg_silog_grad_loss_bwd_ex'})
     assert re.search(r'#define A3DG_WS_FLOATS\(b\) \(\(b\) \* 5 \+ 1 \+ \(b\) \* 5 \* A3D_SILOG_PARTS\)', text)
     width = re.search(r'#define A3DG_MAX_W (\d+)', text)
     assert width and int(width.group(1)) >= 1024

@@ -2,35 +2,18 @@
 entry points, as tests/test_abi.py and tests/test_abi_valid.py hold the other two headers; bad arguments are refused
 before any launch (no GPU needed: the checks come first)."""
 import ctypes
-import os
-import re
-import subprocess
 
+import abi_surface
 from ann3depth_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {'a3dp_crf_loss_grad', 'a3dp_pair_dense_bwd', 'a3dp_sgd_apply_floor'}
 
 
 def test_pairwise_header_exports_and_bindings_agree():
-    lib = _lib.load()
-    text = open(os.path.join(ROOT, 'include', 'a3d_pairwise.h')).read()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(a3dp_[a-z0-9_]+)\s*\(', code))
-    assert declared == NAMES
-    assert not re.findall(r'\ba3dx?_[a-z0-9_]+\s*\(', code)                # nothing of the other two surfaces is declared here
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r' T (a3dp_[a-z0-9_]+)', out)) == declared == set(_lib.PAIR_SIGNATURES)
-    assert not set(_lib.PAIR_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES))
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.PAIR_SIGNATURES[name][1]
-        assert getattr(lib, name).restype == _lib.PAIR_SIGNATURES[name][0]
-    # a3d_crf_loss's arguments plus dr; one argument of the C declaration per binding entry
+    text, code = abi_surface.check('a3dp_', NAMES)
+    # a3d_crf_loss's arguments plus dr
     assert _lib.PAIR_SIGNATURES['a3dp_crf_loss_grad'][1] == (_lib.SIGNATURES['a3d_crf_loss'][1][:-1] + [ctypes.c_void_p] +
                                                            _lib.SIGNATURES['a3d_crf_loss'][1][-1:])
-    for name in declared:
-        args = re.search(name + r'\s*\((.*?)\)\s*;', code, flags=re.S).group(1)
-        assert len(args.split(',')) == len(_lib.PAIR_SIGNATURES[name][1]), name
     for words in ('NON-REFERENCE', 'A3D_EINVAL', 'SAME BITS', '+0.0', 'no atomics', 'A NaN stays'):
         assert words in text
 

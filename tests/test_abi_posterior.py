@@ -2,36 +2,16 @@
 entry point, as the other tests/test_abi_*.py hold their headers; bad arguments are refused before any launch (no GPU
 needed: the checks come first)."""
 import ctypes
-import os
-import re
-import subprocess
 
+import abi_surface
 from ann3depth_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {'a3dc_crf_band_posterior'}
 
 
 def test_posterior_header_exports_and_bindings_agree():
-    lib = _lib.load()
-    text = open(os.path.join(ROOT, 'include', 'a3d_posterior.h')).read()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(a3dc_[a-z0-9_]+)\s*\(', code))
-    assert declared == NAMES
-    assert not re.findall(r'\ba3d[a-z]?_[a-z0-9_]+\s*\(', re.sub(r'\ba3dc_', 'c_', code))     # nothing of another surface
+    text, code = abi_surface.check('a3dc_', NAMES)
     assert '#include "a3d_crf_band.h"' in code and '#define' not in code.replace('#define A3D_POSTERIOR_H_', '')
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r' T (a3dc_[a-z0-9_]+)', out)) == declared == set(_lib.POSTERIOR_SIGNATURES)
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.PAIR_SIGNATURES) | set(_lib.TEXTURE_SIGNATURES)
-              | set(_lib.GRADLOSS_SIGNATURES) | set(_lib.CRF_VALID_SIGNATURES) | set(_lib.FCSP_SIGNATURES)
-              | set(_lib.CRF_BAND_SIGNATURES) | set(_lib.WINO_SIGNATURES) | set(_lib.UPSAMPLE_SIGNATURES))
-    assert not set(_lib.POSTERIOR_SIGNATURES) & others
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.POSTERIOR_SIGNATURES[name][1]
-        assert getattr(lib, name).restype == _lib.POSTERIOR_SIGNATURES[name][0]
-        args = re.search(name + r'\s*\((.*?)\)\s*;', code, flags=re.S).group(1)
-        kinds = [ctypes.c_void_p if '*' in a else ctypes.c_int for a in args.split(',')]
-        assert kinds == _lib.POSTERIOR_SIGNATURES[name][1], name
     # a3db_crf_band_nll's inputs (n .. npairs), then mean, var, nobs, status and the stream
     nll = _lib.CRF_BAND_SIGNATURES['a3db_crf_band_nll'][1]
     assert _lib.POSTERIOR_SIGNATURES['a3dc_crf_band_posterior'][1] == nll[:9] + [ctypes.c_void_p] * 5

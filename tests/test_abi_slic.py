@@ -2,36 +2,17 @@
 points, as tests/test_abi_fcsp.py and its siblings hold the other headers; bad arguments are refused before any launch (no
 GPU needed: the checks come first)."""
 import ctypes
-import os
 import re
-import subprocess
 
+import abi_surface
 from ann3depth_amd import _lib, ops
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {'a3ds_label_mean', 'a3ds_label_hist', 'a3ds_slic_update', 'a3ds_slic_assign', 'a3ds_slic_segment',
          'a3ds_pair_similarity', 'a3ds_label_pool_fwd', 'a3ds_label_pool_bwd'}
 
 
 def test_slic_header_exports_and_bindings_agree():
-    lib = _lib.load()
-    text = open(os.path.join(ROOT, 'include', 'a3d_slic.h')).read()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(a3ds_[a-z0-9_]+)\s*\(', code))
-    assert declared == NAMES
-    assert not re.findall(r'\ba3d[a-rt-z]?_[a-z0-9_]+\s*\(', code)          # nothing of another surface is declared here
-    assert not any(re.fullmatch(r'a3d_[a-z0-9_]+', name) for name in declared)
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r' T (a3ds_[a-z0-9_]+)', out)) == declared == set(_lib.SLIC_SIGNATURES)
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.PAIR_SIGNATURES) | set(_lib.TEXTURE_SIGNATURES)
-              | set(_lib.GRADLOSS_SIGNATURES) | set(_lib.CRF_VALID_SIGNATURES) | set(_lib.FCSP_SIGNATURES)
-              | set(_lib.CRF_BAND_SIGNATURES) | set(_lib.UPSAMPLE_SIGNATURES) | set(_lib.POSTERIOR_SIGNATURES))
-    assert not set(_lib.SLIC_SIGNATURES) & others
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.SLIC_SIGNATURES[name][1]
-        assert getattr(lib, name).restype == _lib.SLIC_SIGNATURES[name][0]
-        args = re.search(name + r'\s*\((.*?)\)\s*;', code, flags=re.S).group(1)   # one C argument per binding entry
-        assert len(args.split(',')) == len(_lib.SLIC_SIGNATURES[name][1]), name
+    text, code = abi_surface.check('a3ds_', NAMES)
     assert _lib.SLIC_SIGNATURES['a3ds_label_pool_fwd'] == _lib.SLIC_SIGNATURES['a3ds_label_pool_bwd']
     for macro, value in (('A3DS_MAX_SP', ops.SLIC_MAX_SP), ('A3DS_MAX_CELLS', ops.SLIC_MAX_CELLS),
                          ('A3DS_MAX_SUPERPIXELS', ops.SLIC_MAX_SUPERPIXELS)):

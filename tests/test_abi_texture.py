@@ -2,37 +2,20 @@
 entry points, as tests/test_abi.py, tests/test_abi_valid.py and tests/test_abi_pairwise.py hold the other three headers;
 bad arguments are refused before any launch (no GPU needed: the checks come first)."""
 import ctypes
-import os
 import re
-import subprocess
 
+import abi_surface
 from ann3depth_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {'a3dt_superpixel_lbp_hist', 'a3dt_pair_similarity3'}
 
 
 def test_texture_header_exports_and_bindings_agree():
-    lib = _lib.load()
-    text = open(os.path.join(ROOT, 'include', 'a3d_texture.h')).read()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(a3dt_[a-z0-9_]+)\s*\(', code))
-    assert declared == NAMES
-    assert not re.findall(r'\ba3d[xp]?_[a-z0-9_]+\s*\(', code)              # nothing of the other three surfaces is declared here
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r' T (a3dt_[a-z0-9_]+)', out)) == declared == set(_lib.TEXTURE_SIGNATURES)
-    others = set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.PAIR_SIGNATURES)
-    assert not set(_lib.TEXTURE_SIGNATURES) & others
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.TEXTURE_SIGNATURES[name][1]
-        assert getattr(lib, name).restype == _lib.TEXTURE_SIGNATURES[name][0]
+    text, code = abi_surface.check('a3dt_', NAMES)
     # the siblings' arguments: a3d_superpixel_hist's own, and a3d_pair_similarity's plus lbp_hist after hist
     assert _lib.TEXTURE_SIGNATURES['a3dt_superpixel_lbp_hist'] == _lib.SIGNATURES['a3d_superpixel_hist']
     sim = _lib.SIGNATURES['a3d_pair_similarity'][1]
     assert _lib.TEXTURE_SIGNATURES['a3dt_pair_similarity3'][1] == sim[:6] + [ctypes.c_void_p] + sim[6:]
-    for name in declared:                                                   # one argument of the C declaration per binding entry
-        args = re.search(name + r'\s*\((.*?)\)\s*;', code, flags=re.S).group(1)
-        assert len(args.split(',')) == len(_lib.TEXTURE_SIGNATURES[name][1]), name
     assert re.search(r'#define\s+A3DT_MAX_SP\s+53\b', code)
     for words in ('NON-REFERENCE', 'A3D_EINVAL', 'SAME BITS', 'clamped at the image border', '-0 >= +0', '2^24'):
         assert words in text

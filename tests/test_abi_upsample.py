@@ -3,36 +3,16 @@ entry point, as tests/test_abi_fcsp.py and its siblings hold the other headers; 
 launch (no GPU needed: the checks come first)."""
 import ctypes
 import math
-import os
 import re
-import subprocess
 
+import abi_surface
 from ann3depth_amd import _lib, ops
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {'a3du_joint_bilateral_upsample'}
 
 
 def test_upsample_header_exports_and_bindings_agree():
-    lib = _lib.load()
-    text = open(os.path.join(ROOT, 'include', 'a3d_upsample.h')).read()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(a3du_[a-z0-9_]+)\s*\(', code))
-    assert declared == NAMES
-    assert not re.findall(r'\ba3d[a-z]?_[a-z0-9_]+\s*\(', re.sub(r'\ba3du_', 'u_', code))     # nothing of another surface
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r' T (a3du_[a-z0-9_]+)', out)) == declared == set(_lib.UPSAMPLE_SIGNATURES)
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.PAIR_SIGNATURES) | set(_lib.TEXTURE_SIGNATURES)
-              | set(_lib.GRADLOSS_SIGNATURES) | set(_lib.CRF_VALID_SIGNATURES) | set(_lib.FCSP_SIGNATURES)
-              | set(_lib.CRF_BAND_SIGNATURES) | set(_lib.WINO_SIGNATURES))
-    assert not set(_lib.UPSAMPLE_SIGNATURES) & others
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.UPSAMPLE_SIGNATURES[name][1]
-        assert getattr(lib, name).restype == _lib.UPSAMPLE_SIGNATURES[name][0]
-        args = re.search(name + r'\s*\((.*?)\)\s*;', code, flags=re.S).group(1)   # one C argument per binding entry
-        kinds = [ctypes.c_void_p if '*' in a else ctypes.c_float if a.split()[0] == 'float' else ctypes.c_int
-                 for a in args.split(',')]
-        assert kinds == _lib.UPSAMPLE_SIGNATURES[name][1], name
+    text, code = abi_surface.check('a3du_', NAMES)
     cap = int(re.search(r'#define\s+A3DU_MAX_RADIUS\s+(\d+)\b', code).group(1))
     assert cap == ops.UPSAMPLE_MAX_RADIUS == 4
     for words in ('NON-REFERENCE', 'A3D_EINVAL', 'SKIPPED', 'ascending (i, j)', 'EVERY element', 'One IEEE division', 'LDS',

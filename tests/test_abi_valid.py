@@ -2,28 +2,15 @@
 points, as tests/test_abi.py holds include/a3d.h, the a3d_* exports and _lib.SIGNATURES to each other; bad arguments are
 refused before any launch (no GPU needed: the checks come first)."""
 import ctypes
-import os
 import re
-import subprocess
 
+import abi_surface
 from ann3depth_amd import _lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_extension_header_exports_and_bindings_agree():
-    lib = _lib.load()
-    text = open(os.path.join(ROOT, 'include', 'a3d_valid.h')).read()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(a3dx_[a-z0-9_]+)\s*\(', code))
-    assert declared == {'a3dx_resize_bilinear_tf1_valid', 'a3dx_warp_bilinear_pair_valid', 'a3dx_silog_masked_loss_fwd',
-                        'a3dx_silog_masked_loss_bwd_ex'}
-    assert not re.findall(r'\ba3d_[a-z0-9_]+\s*\(', code)                 # nothing of the fixed surface is declared here
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r' T (a3dx_[a-z0-9_]+)', out)) == declared == set(_lib.EXT_SIGNATURES)
-    assert not set(_lib.EXT_SIGNATURES) & set(_lib.SIGNATURES)
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.EXT_SIGNATURES[name][1]
+    text, code = abi_surface.check('a3dx_', {'a3dx_resize_bilinear_tf1_valid', 'a3dx_warp_bilinear_pair_valid',
+                                               'a3dx_silog_masked_loss_fwd', 'a3dx_silog_masked_loss_bwd_ex'})
     assert re.search(r'#define A3DX_SILOG_MASKED_WS_FLOATS\(b\) \(\(b\) \* 3 \+ 1 \+ \(b\) \* 3 \* A3D_SILOG_PARTS\)', text)
     for words in ('min_depth < t <= max_depth', 'A3D_EINVAL', 'bit-identical'):
         assert words in text

@@ -4,8 +4,8 @@ arguments are refused before any launch (no GPU needed: the checks come first)."
 import ctypes
 import os
 import re
-import subprocess
 
+import abi_surface
 from ann3depth_amd import _lib, ops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,30 +13,10 @@ NAMES = {'a3dwb_sizeof_pool', 'a3dwb_conv2d_bwd_ws_bytes', 'a3dwb_conv2d_bwd'}
 
 
 def test_wino_bwd_header_exports_and_bindings_agree():
-    lib = _lib.load()
-    text = open(os.path.join(ROOT, 'include', 'a3d_wino_bwd.h')).read()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(a3dwb_[a-z0-9_]+)\s*\(', code))
-    assert declared == NAMES
-    assert not re.findall(r'\ba3d[a-z]{0,2}_[a-z0-9_]+\s*\(', re.sub(r'\ba3dwb_', 'wb_', code))     # nothing of another surface
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r' T (a3dwb_[a-z0-9_]+)', out)) == declared == set(_lib.WINO_BWD_SIGNATURES)
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.PAIR_SIGNATURES) | set(_lib.TEXTURE_SIGNATURES)
-              | set(_lib.GRADLOSS_SIGNATURES) | set(_lib.CRF_VALID_SIGNATURES) | set(_lib.FCSP_SIGNATURES)
-              | set(_lib.CRF_BAND_SIGNATURES) | set(_lib.WINO_SIGNATURES) | set(_lib.UPSAMPLE_SIGNATURES)
-              | set(_lib.POSTERIOR_SIGNATURES) | set(_lib.WINO_GRAD_SIGNATURES) | set(_lib.SLIC_SIGNATURES))
-    assert not set(_lib.WINO_BWD_SIGNATURES) & others
+    text, code = abi_surface.check('a3dwb_', NAMES)
     # the other two Winograd headers keep their symbols: the new prefix is read as neither a3dw_ nor a3dwg_
-    assert set(re.findall(r' T (a3dw_[a-z0-9_]+)', out)) == set(_lib.WINO_SIGNATURES)
-    assert set(re.findall(r' T (a3dwg_[a-z0-9_]+)', out)) == set(_lib.WINO_GRAD_SIGNATURES)
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.WINO_BWD_SIGNATURES[name][1]
-        assert getattr(lib, name).restype == _lib.WINO_BWD_SIGNATURES[name][0]
-        args = re.search(name + r'\s*\((.*?)\)\s*;', code, flags=re.S).group(1)   # one C argument per binding entry
-        kinds = [] if args.strip() == 'void' else [
-            ctypes.POINTER(_lib.ConvDesc) if 'a3d_conv_desc' in a else ctypes.POINTER(_lib.WinoBwdPool) if 'a3dwb_pool' in a
-            else ctypes.c_void_p if '*' in a else ctypes.c_size_t if a.split()[0] == 'size_t' else ctypes.c_int for a in args.split(',')]
-        assert kinds == _lib.WINO_BWD_SIGNATURES[name][1], name
+    for prefix, theirs in (('a3dw_', _lib.WINO_SIGNATURES), ('a3dwg_', _lib.WINO_GRAD_SIGNATURES)):
+        assert {n for n in abi_surface.exports() if n.startswith(prefix)} == set(theirs)
     # x, dz, then a3d_conv2d_bwd_data's w, then a3dwg_conv2d_bwd_filter's dw and db, then dx and relu_mask, the pool, ws, bytes, stream
     P, S = ctypes.c_void_p, ctypes.c_size_t
     assert _lib.WINO_BWD_SIGNATURES['a3dwb_conv2d_bwd'][1] == [ctypes.POINTER(_lib.ConvDesc), P, P, P, P, P, P, P,

@@ -2,39 +2,17 @@
 points, as tests/test_abi_upsample.py and its siblings hold the other headers; bad arguments are refused before any launch (no
 GPU needed: the checks come first)."""
 import ctypes
-import os
-import re
-import subprocess
 
+import abi_surface
 from ann3depth_amd import _lib, ops
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {'a3dwg_conv2d_bwd_filter_ws_bytes', 'a3dwg_conv2d_bwd_filter'}
 
 
 def test_wino_grad_header_exports_and_bindings_agree():
-    lib = _lib.load()
-    text = open(os.path.join(ROOT, 'include', 'a3d_wino_grad.h')).read()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    declared = set(re.findall(r'\b(a3dwg_[a-z0-9_]+)\s*\(', code))
-    assert declared == NAMES
-    assert not re.findall(r'\ba3d[a-z]{0,2}_[a-z0-9_]+\s*\(', re.sub(r'\ba3dwg_', 'wg_', code))     # nothing of another surface
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(re.findall(r' T (a3dwg_[a-z0-9_]+)', out)) == declared == set(_lib.WINO_GRAD_SIGNATURES)
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.PAIR_SIGNATURES) | set(_lib.TEXTURE_SIGNATURES)
-              | set(_lib.GRADLOSS_SIGNATURES) | set(_lib.CRF_VALID_SIGNATURES) | set(_lib.FCSP_SIGNATURES)
-              | set(_lib.CRF_BAND_SIGNATURES) | set(_lib.WINO_SIGNATURES) | set(_lib.UPSAMPLE_SIGNATURES)
-              | set(_lib.POSTERIOR_SIGNATURES))
-    assert not set(_lib.WINO_GRAD_SIGNATURES) & others
+    text, code = abi_surface.check('a3dwg_', NAMES)
     # the other Winograd header keeps its two symbols: the new prefix is not read as a3dw_
-    assert set(re.findall(r' T (a3dw_[a-z0-9_]+)', out)) == set(_lib.WINO_SIGNATURES) and len(_lib.WINO_SIGNATURES) == 2
-    for name in declared:
-        assert getattr(lib, name).argtypes == _lib.WINO_GRAD_SIGNATURES[name][1]
-        assert getattr(lib, name).restype == _lib.WINO_GRAD_SIGNATURES[name][0]
-        args = re.search(name + r'\s*\((.*?)\)\s*;', code, flags=re.S).group(1)   # one C argument per binding entry
-        kinds = [ctypes.POINTER(_lib.ConvDesc) if 'a3d_conv_desc' in a else ctypes.c_void_p if '*' in a
-                 else ctypes.c_size_t if a.split()[0] == 'size_t' else ctypes.c_int for a in args.split(',')]
-        assert kinds == _lib.WINO_GRAD_SIGNATURES[name][1], name
+    assert {n for n in abi_surface.exports() if n.startswith('a3dw_')} == set(_lib.WINO_SIGNATURES) and len(_lib.WINO_SIGNATURES) == 2
     # the calls take a3d_conv2d_bwd_filter's arguments: a caller switches by name alone
     assert _lib.WINO_GRAD_SIGNATURES['a3dwg_conv2d_bwd_filter'] == _lib.SIGNATURES['a3d_conv2d_bwd_filter']
     assert _lib.WINO_GRAD_SIGNATURES['a3dwg_conv2d_bwd_filter_ws_bytes'] == _lib.SIGNATURES['a3d_conv2d_bwd_filter_ws_bytes']
