@@ -213,6 +213,16 @@ WINO_GRAD_SIGNATURES = {
     'a3dwg_conv2d_bwd_filter': (c_int, [_D, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_wino1d.h declares (prefix a3dl_)
+WINO1D_SIGNATURES = {
+    'a3dl_conv2d_bwd_data_ws_bytes': (c_size_t, [_D]),
+    'a3dl_conv2d_bwd_data': (c_int, [_D, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'a3dl_conv2d_bwd_filter_ws_bytes': (c_size_t, [_D]),
+    'a3dl_conv2d_bwd_filter': (c_int, [_D, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'a3dl_conv2d_bwd_data_prepared_filter_bytes': (c_size_t, [_D]),
+    'a3dl_conv2d_bwd_data_prepare_filter': (c_int, [_D, _P, _P, c_size_t, _P]),
+}
+
 class WinoBwdPool(ctypes.Structure):
     """a3dwb_pool (include/a3d_wino_bwd.h): the 2x2 max pool below a layer, as the fused forward recorded it."""
     _fields_ = [('argmax', c_void_p), ('y', c_void_p), ('ldy', c_int), ('h2', c_int), ('w2', c_int)]
@@ -270,6 +280,7 @@ SURFACES = (
     Surface('a3dh_', 'a3d_berhu.h', BERHU_SIGNATURES),
     Surface('a3da_', 'a3d_align.h', ALIGN_SIGNATURES),
     Surface('a3di_', 'a3d_ssi.h', SSI_SIGNATURES),
+    Surface('a3dl_', 'a3d_wino1d.h', WINO1D_SIGNATURES),
 )
 
 _lib = None

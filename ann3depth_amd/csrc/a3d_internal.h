@@ -167,4 +167,36 @@ int wino_bwd_gemm(IgemmParams& pf, const WinoGradGeom& gg, IgemmParams& pd, cons
 int wino_bwd_finish(const a3d_conv_desc* d, const WinoGradGeom& gg, const float* slabs, const float* bparts, float* dw, float* db,
                     const float* M, float* dx, const float* mask, const WinoBwdPool* pool, hipStream_t st);
 
+// ---- 1-D Winograd F(4,5) along the width for the gradients of stride-1 convolutions 5 wide (include/a3d_wino1d.h; wino1d.hip) ----
+struct Wino1dGeom {                      // bwd-data
+  int R, tw, off;                        // window height, tiles of 4 columns of dx, a window starts at column 4 t - off of dz
+  size_t Pv, Pm;                         // pixels of one plane of V (n * ho * tw) and of M (n * h * tw)
+  int K, N, Kp, Np;                      // channels contracted / produced, and padded to whole 16-byte pieces
+  int bn, tiles_m, tiles_n, nk, blocks;  // the product's tile width (96 or 128), tiles and k-tiles of a plane, wino1d_bwd_blocks of them
+  size_t v_bytes, m_bytes, u_bytes;      // V [8][Pv][Kp], M [8][Pm][Np], U [8][R][Kp][Np]
+  size_t sk_bytes;                       // stream-K slabs [8][2 * blocks][128 * bn]
+};
+struct Wino1dGradGeom {                  // filter gradient
+  int R, tw;                             // window height, tiles of 4 columns of dz
+  size_t Px, Pz;                         // pixels of one plane of V (n * h * tw) and of Z (n * ho * tw)
+  int Cp, Kp, splits;                    // c and k padded to whole 16-byte pieces; wino1d_grad_splits(R Cp, Kp, Pz)
+  size_t v_bytes, z_bytes;               // V [8][Px][Cp], Z [8][Pz][Kp]
+  size_t slab_bytes, bias_bytes;         // raw sums [8][splits][R Cp][Kp], bias partials [splits][Kp]
+};
+int wino1d_bwd_blocks(long tiles, long nk);
+int wino1d_grad_splits(int M, int N, size_t pixels);
+Wino1dGeom wino1d_geom(const a3d_conv_desc* d);
+Wino1dGradGeom wino1d_grad_geom(const a3d_conv_desc* d);
+bool wino1d_applicable(const a3d_conv_desc* d);
+int wino1d_filter(const a3d_conv_desc* d, const float* w, float* U, hipStream_t st);
+// src [rows][W][ld] of c channels -> V [8][rows][tw][Cp], windows at column 4 t - off
+int wino1d_input(const float* src, float* V, size_t rows, int W, int c, int ld, int off, int tw, int Cp, hipStream_t st);
+int wino1d_dz(const a3d_conv_desc* d, const Wino1dGradGeom& g, const float* dz, float* Z, hipStream_t st);
+int wino1d_output(const a3d_conv_desc* d, const Wino1dGeom& g, const float* M, float* dx, const float* mask, hipStream_t st);
+int wino1d_dw(const a3d_conv_desc* d, const Wino1dGradGeom& g, const float* slabs, const float* bparts, float* dw, float* db, hipStream_t st);
+a3d_timing_record wino1d_record(const Wino1dGeom& g);
+a3d_timing_record wino1d_grad_record(const a3d_conv_desc* d, const Wino1dGradGeom& g);
+int wino1d_gemm(IgemmParams& p, const Wino1dGeom& g, float* sk, hipStream_t st);      // the eight products and their fix-up
+int wino1d_grad_gemm(IgemmParams& p, const Wino1dGradGeom& g, hipStream_t st);
+
 }  // namespace a3d

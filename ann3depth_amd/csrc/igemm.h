@@ -1243,16 +1243,16 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p, const uint32_t 
 // (wave, accumulator, register quad) of the GEMM kernel; a wave of this kernel owns one unit of one tile, so a tile is
 // finished by BM*BN/256 independent waves (grid.y = groups of four units), each reading 16 bytes per lane per slab with
 // four slabs in flight.
+// `tile` and `ygroup` are the block's two coordinates: a launch of several problems (wino1d.hip) passes its own.
 template <int MODE, int BM, int BN, int WAVES_M, int NWAVES>
-__global__ __launch_bounds__(256) void igemm_fixup_kernel(const IgemmParams p, const uint32_t nblk) {
+__device__ __forceinline__ void igemm_fixup_body(const IgemmParams& p, const uint32_t nblk, const uint32_t tile, const uint32_t ygroup) {
   constexpr int WAVES_N = NWAVES / WAVES_M, WM = BM / WAVES_M, WN = BN / WAVES_N, TM = WM / 32, TN = WN / 32;
   constexpr int UNITS = NWAVES * TM * TN * 4;
   constexpr int MAXC = 1024;                                // contributors of one tile: at most one per block (host: grid <= 1024)
   __shared__ uint32_t slots[MAXC];
   __shared__ uint32_t nslots;
   const int lane = threadIdx.x & 63;
-  const int unit = (int)blockIdx.y * 4 + (int)(threadIdx.x >> 6);
-  const uint32_t tile = blockIdx.x;
+  const int unit = (int)ygroup * 4 + (int)(threadIdx.x >> 6);
   const uint32_t nk = p.div_nk.d, tiles = (uint32_t)(p.tiles_m * p.tiles_n);
   // the tile's contributors in block order (= ascending k), as slab slots: first share of the block if that share starts
   // in this tile, else its last share.  One thread lists them; a launch with more blocks than iterations has blocks
@@ -1302,12 +1302,16 @@ __global__ __launch_bounds__(256) void igemm_fixup_kernel(const IgemmParams p, c
     store_quad<MODE>(p, s, tile_m * BM + wm * WM + a * 32 + 8 * q + 4 * lh, tile_n * BN + wn * WN + bb * 32 + li, p.C,
                      p.ldc, false);
   }
-  if (MODE == MODE_BWD_F && p.dbias != nullptr && tile_m == 0 && blockIdx.y == 0 && (int)threadIdx.x < BN) {
+  if (MODE == MODE_BWD_F && p.dbias != nullptr && tile_m == 0 && ygroup == 0 && (int)threadIdx.x < BN) {
     static_assert(BN <= 256, "bias sums by the first 256 threads");
     float bsum = 0.f;
     for (uint32_t i = 0; i < n; ++i) bsum += p.sk_bias[(size_t)slots[i] * BN + threadIdx.x];
     if (tile_n * BN + (int)threadIdx.x < p.N) p.dbias[tile_n * BN + threadIdx.x] = bsum;
   }
+}
+template <int MODE, int BM, int BN, int WAVES_M, int NWAVES>
+__global__ __launch_bounds__(256) void igemm_fixup_kernel(const IgemmParams p, const uint32_t nblk) {
+  igemm_fixup_body<MODE, BM, BN, WAVES_M, NWAVES>(p, nblk, blockIdx.x, blockIdx.y);
 }
 
 template <int MODE, int BM, int BN, int WAVES_M, int NWAVES, int BKT, int AVEC, int BVEC>

@@ -7,6 +7,7 @@
 #include "../../include/a3d_wino.h"
 #include "../../include/a3d_wino_grad.h"
 #include "../../include/a3d_wino_bwd.h"
+#include "../../include/a3d_wino1d.h"
 #include "a3d_internal.h"
 #include "igemm.h"
 #include "igemm_cfgs.h"
@@ -1069,6 +1070,125 @@ int a3dwb_conv2d_bwd(const a3d_conv_desc* d, const float* x, const float* dz, co
   WinoBwdPool wp{};
   if (pool) wp = WinoBwdPool{pool->argmax, pool->y, pool->ldy, pool->h2, pool->w2};
   return wino_bwd_finish(&e, gg, slabs, bparts, dw, db, M, dx, relu_mask, pool ? &wp : nullptr, st);
+}
+
+// ---- include/a3d_wino1d.h: the gradients of a stride-1 convolution 5 wide through 1-D Winograd F(4,5) (wino1d.hip) ----
+static bool wino1d_takes(const a3d_conv_desc* d) { return check_desc(d) == A3D_OK && wino1d_applicable(d); }
+
+// bwd-data's workspace: [U unless prepared][V][M][stream-K slabs]
+static size_t wino1d_bytes(const Wino1dGeom& g, bool prepared) { return (prepared ? 0 : g.u_bytes) + g.v_bytes + g.m_bytes + g.sk_bytes; }
+// the filter gradient's: [V][Z][slabs][bias partials]
+static size_t wino1d_grad_bytes(const Wino1dGradGeom& g) { return g.v_bytes + g.z_bytes + g.slab_bytes + g.bias_bytes; }
+
+// one of bwd-data's eight products: the forward of an r x 1 convolution over a plane of V [n][ho][tw][Kp] with vertical padding
+// r - 1 - pad_t, onto dx's rows x tiles, against U[xi] [r Kp][Np]
+static IgemmParams wino1d_product(const a3d_conv_desc* d, const Wino1dGeom& g, const float* V, const float* U, float* M) {
+  a3d_conv_desc e{};
+  e.n = d->n; e.h = d->ho; e.w = g.tw; e.ho = d->h; e.wo = g.tw; e.c = g.Kp; e.k = g.Np; e.r = g.R; e.s = 1; e.stride = 1;
+  e.pad_t = g.R - 1 - d->pad_t; e.ldx = g.Kp; e.ldy = g.Np;
+  GemmProblem gp = fwd_problem(&e);
+  IgemmParams p;
+  fill_common(p, gp);
+  p.A = V; p.B = U; p.C = M;
+  p.npix = gp.M; p.nrsc = gp.K;
+  fill_gather(p, &e, g.Kp, 1, g.Kp);
+  p.ldb = g.Np; p.ldc = g.Np;
+  fill_staging(p, MODE_FWD, (unsigned long long)g.Pv * g.Kp, (unsigned long long)g.R * g.Kp * g.Np, g.R, 1);
+  return p;
+}
+// one of the filter gradient's eight sums: the filter gradient of an r x 1 convolution from a plane of V [n][h][tw][Cp] and a
+// plane of Z [n][ho][tw][Kp]
+static IgemmParams wino1d_grad_product(const a3d_conv_desc* d, const Wino1dGradGeom& g, const float* V, const float* Z, float* slabs,
+                                       float* bparts) {
+  a3d_conv_desc e{};
+  e.n = d->n; e.h = d->h; e.w = g.tw; e.ho = d->ho; e.wo = g.tw; e.c = g.Cp; e.k = g.Kp; e.r = g.R; e.s = 1; e.stride = 1;
+  e.pad_t = d->pad_t; e.ldx = g.Cp; e.ldy = g.Kp;
+  GemmProblem gp = bwd_f_problem(&e);
+  IgemmParams p;
+  fill_common(p, gp);
+  p.A = V; p.B = Z; p.C = slabs; p.dbias = bparts;
+  p.npix = gp.K; p.nrsc = gp.M;
+  fill_gather(p, &e, g.Cp, 1, g.Cp);
+  p.ldb = g.Kp; p.ldc = g.Kp;
+  fill_staging(p, MODE_BWD_F, (unsigned long long)g.Px * g.Cp, (unsigned long long)g.Pz * g.Kp, g.R, 1);
+  return p;
+}
+
+size_t a3dl_conv2d_bwd_data_ws_bytes(const a3d_conv_desc* d) {
+  if (!wino1d_takes(d)) return a3d_conv2d_bwd_data_ws_bytes(d);
+  return wino1d_bytes(wino1d_geom(d), (d->hints & A3D_HINT_W_PREPARED) != 0);
+}
+
+int a3dl_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w, float* dx, const float* relu_mask, void* ws,
+                         size_t ws_bytes, void* stream) {
+  if (!wino1d_takes(d)) return a3d_conv2d_bwd_data(d, dz, w, dx, relu_mask, ws, ws_bytes, stream);
+  A3D_CHECK_ARG(dz && w && dx, "conv2d_bwd_data (Winograd 1-D): null tensor");
+  A3D_CHECK_WS(ws, "conv2d_bwd_data (Winograd 1-D)");
+  const bool prepared = (d->hints & A3D_HINT_W_PREPARED) != 0;
+  const Wino1dGeom g = wino1d_geom(d);
+  const size_t need = wino1d_bytes(g, prepared);
+  if (!ws || need > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd_data (Winograd 1-D): need %zu workspace bytes", need);
+  A3D_CHECK_ARG(!prepared || aligned16(w), "conv2d_bwd_data (Winograd 1-D): the prepared filter must be 16-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(ws);
+  const float* U = w;
+  int rc;
+  if (!prepared) {
+    rc = wino1d_filter(d, w, reinterpret_cast<float*>(base), st);
+    if (rc != A3D_OK) return rc;
+    U = reinterpret_cast<const float*>(base);
+    base += g.u_bytes;
+  }
+  float* V = reinterpret_cast<float*>(base);
+  float* M = reinterpret_cast<float*>(base + g.v_bytes);
+  float* sk = reinterpret_cast<float*>(base + g.v_bytes + g.m_bytes);
+  rc = wino1d_input(dz, V, (size_t)d->n * d->ho, d->wo, d->k, d->ldy, g.off, g.tw, g.Kp, st);
+  if (rc != A3D_OK) return rc;
+  IgemmParams p = wino1d_product(d, g, V, U, M);
+  rc = timed_launch(wino1d_record(g), st, [&] { return wino1d_gemm(p, g, sk, st); });
+  if (rc != A3D_OK) return rc;
+  return wino1d_output(d, g, M, dx, relu_mask, st);
+}
+
+size_t a3dl_conv2d_bwd_filter_ws_bytes(const a3d_conv_desc* d) {
+  if (!wino1d_takes(d)) return a3d_conv2d_bwd_filter_ws_bytes(d);
+  return wino1d_grad_bytes(wino1d_grad_geom(d));
+}
+
+int a3dl_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* dz, float* dw, float* db, void* ws, size_t ws_bytes,
+                           void* stream) {
+  if (!wino1d_takes(d)) return a3d_conv2d_bwd_filter(d, x, dz, dw, db, ws, ws_bytes, stream);
+  A3D_CHECK_ARG(x && dz && dw, "conv2d_bwd_filter (Winograd 1-D): null tensor");
+  A3D_CHECK_WS(ws, "conv2d_bwd_filter (Winograd 1-D)");
+  const Wino1dGradGeom g = wino1d_grad_geom(d);
+  const size_t need = wino1d_grad_bytes(g);
+  if (!ws || need > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd_filter (Winograd 1-D): need %zu workspace bytes", need);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* base = static_cast<char*>(ws);
+  float* V = reinterpret_cast<float*>(base);
+  float* Z = reinterpret_cast<float*>(base + g.v_bytes);
+  float* slabs = reinterpret_cast<float*>(base + g.v_bytes + g.z_bytes);
+  float* bparts = reinterpret_cast<float*>(base + g.v_bytes + g.z_bytes + g.slab_bytes);
+  int rc = wino1d_input(x, V, (size_t)d->n * d->h, d->w, d->c, d->ldx, d->pad_l, g.tw, g.Cp, st);
+  if (rc != A3D_OK) return rc;
+  rc = wino1d_dz(d, g, dz, Z, st);
+  if (rc != A3D_OK) return rc;
+  IgemmParams p = wino1d_grad_product(d, g, V, Z, slabs, db ? bparts : nullptr);
+  rc = timed_launch(wino1d_grad_record(d, g), st, [&] { return wino1d_grad_gemm(p, g, st); });
+  if (rc != A3D_OK) return rc;
+  return wino1d_dw(d, g, slabs, bparts, dw, db, st);
+}
+
+size_t a3dl_conv2d_bwd_data_prepared_filter_bytes(const a3d_conv_desc* d) { return wino1d_takes(d) ? wino1d_geom(d).u_bytes : 0; }
+
+int a3dl_conv2d_bwd_data_prepare_filter(const a3d_conv_desc* d, const float* w, void* prepared, size_t prepared_bytes, void* stream) {
+  int rc = check_desc(d);
+  if (rc != A3D_OK) return rc;
+  A3D_CHECK_ARG(w && prepared && aligned16(prepared), "conv2d_bwd_data_prepare_filter (Winograd 1-D): null or misaligned buffer");
+  const size_t need = a3dl_conv2d_bwd_data_prepared_filter_bytes(d);
+  A3D_CHECK_ARG(need > 0, "conv2d_bwd_data_prepare_filter (Winograd 1-D): the route does not take this descriptor");
+  if (prepared_bytes < need) return set_error(A3D_EWORKSPACE, "conv2d_bwd_data_prepare_filter (Winograd 1-D): need %zu bytes", need);
+  return wino1d_filter(d, w, static_cast<float*>(prepared), static_cast<hipStream_t>(stream));
 }
 
 // ---- dense = 1x1 conv over a 1x1 image ----

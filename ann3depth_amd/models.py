@@ -413,6 +413,17 @@ class MSDNReplica(Replica):
                 d = self.d[n]
                 if d.n * -(-d.ho // 2) * -(-d.wo // 2) >= self.WINO_GRAD_MIN_TILES:
                     self.wino_grad.add(n)
+        # ... and the two gradients of the stride-1 5x5 layer through 1-D Winograd F(4,5) along the width (include/a3d_wino1d.h),
+        # each from its own count of rows of 4-column tiles up
+        self.wino1d_bwd_d, self.wino1d_bwd_f = set(), set()
+        if precision == 'fp32' and dev.type == 'cuda':
+            for n in self.WINO1D_LAYERS:
+                d = self.d[n]
+                rows = d.n * d.h * -(-d.w // 4)
+                if rows >= self.WINO1D_BWD_D_MIN_ROWS:
+                    self.wino1d_bwd_d.add(n)
+                if rows >= self.WINO1D_BWD_F_MIN_ROWS:
+                    self.wino1d_bwd_f.add(n)
         # conv -> ReLU -> pool blocks on the 3-channel image: filter gradient straight from the POOLED map's gradient (MaxPoolGrad
         # by index + ReluGrad while the kernel stages its operand): dc0 / df1 (50 / 131 MB at B = 32) are never written or read.
         # fp32 arithmetic on the fp32 image in every precision mode but 'bf16s'.
@@ -493,6 +504,17 @@ class MSDNReplica(Replica):
     # Where both routes are on, the layer's two gradients run as one chain of three launches (include/a3d_wino_bwd.h) with the
     # bits of the separate calls; conv2d_2's also carries conv2d_1's pool gradient.  False: the separate calls (the tests' yardstick).
     WINO_BWD_CHAIN = True
+
+    # 1-D Winograd F(4,5) along the width for the two gradients of conv2d_1 (5x5, stride 1; precision 'fp32' only).
+    # A threshold counts rows of 4-column tiles, n * h * ceil(w / 4): 270 an image.  tools/bench_layers.py conv2d_1 at B = 8, 16, 32
+    # (profiles/wino1d_bench_layers.txt), direct -> route: bwd-data 105.2 -> 70.6 us, 184.9 -> 115.6, 334.5 -> 192.1; filter
+    # gradient 108.3 -> 68.6, 195.0 -> 109.1, 354.8 -> 179.7.  Both win at each, so both thresholds are the smallest count measured
+    # (B = 8).  Inside the step at B = 32 (profiles/wino1d_ab_step.txt): 2.583-2.586 -> 2.319-2.323 ms.  B <= 4 (1080 rows) stays
+    # direct whatever is measured: the pinned plans and records (tests/golden/plan_log.json, test_make_train_drop_in) are the direct kernels'.  The
+    # forward stays direct for the reason given above for conv2d_2 / conv2d_3; the two gradients reach only CoarseConv's m slots.
+    WINO1D_LAYERS = ('coarse/conv/conv2d_1',)
+    WINO1D_BWD_D_MIN_ROWS = 2160
+    WINO1D_BWD_F_MIN_ROWS = 2160
 
     def _desc(self, name, which):
         """The layer's conv descriptor for 'fwd' | 'bwd_d' | 'bwd_f', with that call's storage bits."""
@@ -984,6 +1006,10 @@ class MSDNReplica(Replica):
         d, w = self._desc(name, 'bwd_d'), self._w(name, 'bwd_d')
         if name in self.d_wino:
             d, w = self._prepared((name, 'bwd_d', 'fp32w'), self.d_wino[name], w, 'bwd_d')
+        if name in self.wino1d_bwd_d:
+            d, w = self._prepared((name, 'bwd_d', 'wino1d'), d, w, 'bwd_d_wino1d')
+            ops.conv2d_bwd_data_wino1d(d, dz, w, dx, relu_mask=relu_mask)
+            return
         ops.conv2d_bwd_data(d, dz, w, dx, relu_mask=relu_mask)
 
     def _wino_chain(self, name):
@@ -997,6 +1023,8 @@ class MSDNReplica(Replica):
     def _bwd_filter(self, name, x, dz):
         if name in self.d:
             call = ops.conv2d_bwd_filter_wino if name in self.wino_grad else ops.conv2d_bwd_filter
+            if name in self.wino1d_bwd_f:
+                call = ops.conv2d_bwd_filter_wino1d
             call(self._desc(name, 'bwd_f'), x, dz, self._g(name + '/kernel'), self._g(name + '/bias'))
         elif self._fused_dense_adam():
             g = self.groups[self.group_of[name + '/kernel']]

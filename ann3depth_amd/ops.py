@@ -77,11 +77,12 @@ class PreparedFilter:
     """The filter of a few-channel forward in the layout its kernel reads (a3d_conv2d_fwd_prepare_filter), kept beside the
     stored filter so that the repack runs when the weights change instead of on every call.  desc: the descriptor the forward
     uses WITHOUT the hint; .desc_prepared is the same descriptor with A3D_HINT_W_PREPARED, .buf the prepared copy.
-    which='bwd_d': the filter a3d_conv2d_bwd_data reads (precision 'fp32w': the transform of the flipped taps)."""
+    which='bwd_d': the filter a3d_conv2d_bwd_data reads (precision 'fp32w': the transform of the flipped taps); 'bwd_d_wino1d':
+    the one conv2d_bwd_data_wino1d reads (include/a3d_wino1d.h)."""
 
     def __init__(self, desc, device, which='fwd'):
         lib = _lib.load()
-        self.stem = {'fwd': 'a3d_conv2d_fwd', 'bwd_d': 'a3dw_conv2d_bwd_data'}[which]
+        self.stem = {'fwd': 'a3d_conv2d_fwd', 'bwd_d': 'a3dw_conv2d_bwd_data', 'bwd_d_wino1d': 'a3dl_conv2d_bwd_data'}[which]
         nbytes = getattr(lib, self.stem + '_prepared_filter_bytes')(ctypes.byref(desc))
         self.ok = nbytes > 0
         self.desc = desc
@@ -198,6 +199,26 @@ def conv2d_bwd_filter_wino(d, x, dz, dw, db=None):
     ws, n = _ws().get(lib.a3dwg_conv2d_bwd_filter_ws_bytes(ctypes.byref(d)), x.device)
     check(lib.a3dwg_conv2d_bwd_filter(ctypes.byref(d), _ptr(x), _ptr(dz), _ptr(dw), _ptr(db), ws, n, _stream()),
           'a3dwg_conv2d_bwd_filter')
+    return dw, db
+
+
+def conv2d_bwd_data_wino1d(d, dz, w, dx, relu_mask=None):
+    """The input gradient through 1-D Winograd F(4,5) along the width in fp32 (include/a3d_wino1d.h) where d is a stride-1 layer
+    of float32 tensors with a window 5 wide; for any other descriptor the library runs conv2d_bwd_data's kernels.  w: the filter,
+    or its prepared transform (PreparedFilter(..., 'bwd_d_wino1d')) when d.hints says so."""
+    lib = _lib.load()
+    ws, n = _ws().get(lib.a3dl_conv2d_bwd_data_ws_bytes(ctypes.byref(d)), dz.device)
+    check(lib.a3dl_conv2d_bwd_data(ctypes.byref(d), _ptr(dz), _ptr(w), _ptr(dx), _ptr(relu_mask), ws, n, _stream()),
+          'a3dl_conv2d_bwd_data')
+    return dx
+
+
+def conv2d_bwd_filter_wino1d(d, x, dz, dw, db=None):
+    """The filter and bias gradient through the same identity; descriptors as conv2d_bwd_data_wino1d's."""
+    lib = _lib.load()
+    ws, n = _ws().get(lib.a3dl_conv2d_bwd_filter_ws_bytes(ctypes.byref(d)), x.device)
+    check(lib.a3dl_conv2d_bwd_filter(ctypes.byref(d), _ptr(x), _ptr(dz), _ptr(dw), _ptr(db), ws, n, _stream()),
+          'a3dl_conv2d_bwd_filter')
     return dw, db
 
 

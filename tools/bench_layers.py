@@ -3,7 +3,9 @@ them (conv + pool fused where the step fuses them).  One line per op: us, TFLOP/
 fwd/wino, bwd_d/wino and bwd_f/wino: the same call through the Winograd route (precision 'fp32w' with prepared filters; the
 filter gradient through ops.conv2d_bwd_filter_wino: both transforms, the products and the final transform; TF counts the direct
 convolution's FLOPs, so the rows compare as times) — what MSDNReplica.WINO_MIN_TILES and WINO_GRAD_MIN_TILES are chosen from (the
-step uses the bwd-data and bwd-filter rows: DESIGN 3.1k); they are not part of the total.  A/B two builds of the library on one GPU box:
+step uses the bwd-data and bwd-filter rows: DESIGN 3.1k); they are not part of the total.  The stride-1 5x5 layers get bwd_d/wino and
+bwd_f/wino rows as well: 1-D Winograd F(4,5) along the width (ops.conv2d_bwd_data_wino1d with a prepared filter,
+ops.conv2d_bwd_filter_wino1d), what MSDNReplica.WINO1D_BWD_D_MIN_ROWS and WINO1D_BWD_F_MIN_ROWS are chosen from.  A/B two builds of the library on one GPU box:
     A3D_LIB=tools/ab/liba3d_old.so python tools/bench_layers.py ; python tools/bench_layers.py"""
 import json
 import os
@@ -67,6 +69,11 @@ def main():
             modes['fwd/wino'] = lambda: ops.conv2d_fwd(pf.desc_prepared, x, pf.buf, bias, y, 'relu')
             modes['bwd_d/wino'] = lambda: ops.conv2d_bwd_data(pb.desc_prepared, dz, pb.buf, dx, relu_mask=x)
             modes['bwd_f/wino'] = lambda: ops.conv2d_bwd_filter_wino(d, x, dz, dw, db)
+        if ks == 5 and st == 1 and c > 3:
+            pl = ops.PreparedFilter(d, x.device, 'bwd_d_wino1d')
+            pl.refresh(wt)
+            modes['bwd_d/wino'] = lambda: ops.conv2d_bwd_data_wino1d(pl.desc_prepared, dz, pl.buf, dx, relu_mask=x)
+            modes['bwd_f/wino'] = lambda: ops.conv2d_bwd_filter_wino1d(d, x, dz, dw, db)
         # conv + pool in one launch enumerates whole pool windows only: the last odd row / column is never computed
         flops_pooled = 2.0 * B * (d.ho // 2) * (d.wo // 2) * 4 * k * ks * ks * c
         for mode, fn in modes.items():
