@@ -36,6 +36,22 @@ inline unsigned grid_for(size_t total, int per_block = 256, unsigned cap = 8192)
 
 __host__ __device__ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// workspace segments start on 256-byte boundaries
+inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+
+// Raises a kernel's dynamic-LDS limit once per device.  The limit is a per-DEVICE attribute of the kernel: `done` is the
+// call site's `static bool[64]`, one flag per device (a benign race at worst sets it twice)
+inline int raise_lds(const void* kern, size_t bytes, bool (&done)[64]) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= 64 || !done[dev]) {
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return set_error(A3D_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+    if (dev >= 0 && dev < 64) done[dev] = true;
+  }
+  return A3D_OK;
+}
+
 // ---- implicit-GEMM launch layer (igemm_launch.hip) under the front end (igemm_host.hip); the planner: igemm_plan.h, igemm_plan.cc ----
 struct IgemmParams;
 int launch_igemm(int mode, const GemmPlan& plan, int avec, int bvec, IgemmParams& p, void* ws, hipStream_t st);
@@ -121,12 +137,25 @@ int conv3b_pack(const a3d_conv_desc* d, const float* w, void* wp, hipStream_t st
 int conv3b_fwd(const a3d_conv_desc* d, const void* x, const float* w, const float* bias, void* y, int act, int pool, int ld_out,
                uint8_t* argmax, void* ws, size_t ws_bytes, hipStream_t st, bool prepared);
 
+// ---- what the Winograd routes below share (wino.hip).  A route supplies its transform kernels, a geometry (the planes' extents,
+//      the segments of its workspace) and a surrogate descriptor of one plane's product (igemm_host.hip: plane_product, the
+//      workspace layouts); its products run here, all planes in one launch of an fp32 GEMM body ----
+struct PlaneBatch;                                                             // igemm.h: the strides between planes, the bias plane
+constexpr int kBM = 128, kBN = 128, kWavesM = 4, kNWaves = 8, kBK = 32;        // the products' tile
+constexpr int kBlockSlots = 512, kCUs = 256, kMinKTiles = 5;                   // blocks of that tile the chip holds at once; plane_splits
+void plane_tiles(IgemmParams& p, int splits);                                  // the tiles of one product and the split of its K loop
+// MODE_FWD (tile 128 x bn: 128 on eight waves, 96 on four) or MODE_BWD_F (bn = 128) on grid (blocks, planes); what: check_launch's name
+int plane_gemm(int mode, int bn, const IgemmParams& p, const PlaneBatch& bt, unsigned blocks, int planes, const char* what, hipStream_t st);
+// how many ways the pixel axis of `planes` bwd-filter products M x N is split; tuning: the variable that forces a count
+int plane_splits(int planes, int M, int N, size_t pixels, bool larger_on_tie, const char* tuning);
+
 // ---- Winograd F(2x2,3x3) route of A3D_PREC_F32_WINOGRAD (wino.hip); bwd: the bwd-data form of the descriptor ----
 struct WinoGeom {
   int oh, ow, th, tw;                    // the output grid (bwd: dx's) and its 2x2 tiles
   size_t T;                              // n * th * tw
   int K, N, Kp, Np;                      // channels contracted / produced, and padded to whole 16-byte pieces
   size_t v_bytes, m_bytes, u_bytes;      // V [16][T][Kp], M [16][T][Np], U [16][Kp][Np]
+  size_t sk_bytes;                       // 0: whole tiles, no stream-K slabs
 };
 WinoGeom wino_geom(const a3d_conv_desc* d, bool bwd);
 bool wino_applicable(const a3d_conv_desc* d);
@@ -198,5 +227,37 @@ a3d_timing_record wino1d_record(const Wino1dGeom& g);
 a3d_timing_record wino1d_grad_record(const a3d_conv_desc* d, const Wino1dGradGeom& g);
 int wino1d_gemm(IgemmParams& p, const Wino1dGeom& g, float* sk, hipStream_t st);      // the eight products and their fix-up
 int wino1d_grad_gemm(IgemmParams& p, const Wino1dGradGeom& g, hipStream_t st);
+
+// ---- the routes' workspaces.  Each layout is written once, as the order in which its segments (the *_bytes of a geometry, each
+//      a multiple of 256) are taken from a Carve.  A query carves from offset 0 and answers the end offset, a launch carves from
+//      its workspace: the two cannot disagree.  The chain's layout is the first followed by the second ----
+struct Carve {
+  uintptr_t at;
+  float* take(size_t bytes) {
+    float* p = reinterpret_cast<float*>(at);
+    at += bytes;
+    return p;
+  }
+};
+struct ProductWs { float *U, *V, *M, *sk; };           // forward, bwd-data: [U unless prepared][V][M][stream-K slabs]
+struct GradWs { float *V, *Z, *slabs, *bparts; };      // filter gradient: [V][Z][raw slabs][bias partials]
+template <typename Geom>      // WinoGeom, Wino1dGeom
+ProductWs carve_product(Carve& c, const Geom& g, bool prepared) {
+  ProductWs w{};
+  if (!prepared) w.U = c.take(g.u_bytes);
+  w.V = c.take(g.v_bytes);
+  w.M = c.take(g.m_bytes);
+  w.sk = c.take(g.sk_bytes);
+  return w;
+}
+template <typename Geom>      // WinoGradGeom, Wino1dGradGeom
+GradWs carve_grad(Carve& c, const Geom& g) {
+  GradWs w{};
+  w.V = c.take(g.v_bytes);
+  w.Z = c.take(g.z_bytes);
+  w.slabs = c.take(g.slab_bytes);
+  w.bparts = c.take(g.bias_bytes);
+  return w;
+}
 
 }  // namespace a3d

@@ -395,7 +395,7 @@ bool conv3_applicable(const a3d_conv_desc* d, unsigned x_off) {
 
 size_t conv3_ws_bytes(const a3d_conv_desc* d) {
   const Conv3Shape s = conv3_shape(d);
-  return ((size_t)s.Kp * s.Np * 4 + 255) / 256 * 256;
+  return up256((size_t)s.Kp * s.Np * 4);
 }
 
 // share: A3D_HINT_SHARE_CU — the kernel uses no LDS, so a dynamic request of 80 KiB + 1 KiB caps it at ONE block per CU:
@@ -496,7 +496,7 @@ bool conv3b_applicable(const a3d_conv_desc* d) {
 
 size_t conv3b_filter_bytes(const a3d_conv_desc* d) {
   const Conv3bShape s = conv3b_shape(d);
-  return ((size_t)s.Kp * s.Np * 2 + 255) / 256 * 256;
+  return up256((size_t)s.Kp * s.Np * 2);
 }
 
 int conv3b_pack(const a3d_conv_desc* d, const float* w, void* wp, hipStream_t st) {

@@ -1314,6 +1314,22 @@ __global__ __launch_bounds__(256) void igemm_fixup_kernel(const IgemmParams p, c
   igemm_fixup_body<MODE, BM, BN, WAVES_M, NWAVES>(p, nblk, blockIdx.x, blockIdx.y);
 }
 
+// Planes of one problem in ONE launch (the Winograd routes, wino.hip and wino1d.hip): the planes differ in the base addresses of
+// A, B, C and of their stream-K slabs alone, by whole strides; the bwd-filter body's bias partials belong to one plane of them.
+struct PlaneBatch {
+  size_t a, b, c, sk;      // elements between two planes of the three operands and of the stream-K slabs
+  int bias;                // the plane whose blocks sum dbias; -1: none
+};
+__device__ __forceinline__ IgemmParams plane_params(const IgemmParams& p, const PlaneBatch& bt, const uint32_t plane) {
+  IgemmParams q = p;
+  q.A = p.A + (size_t)plane * bt.a;
+  q.B = p.B + (size_t)plane * bt.b;
+  q.C = p.C + (size_t)plane * bt.c;
+  q.sk_ws = p.sk_ws + (size_t)plane * bt.sk;
+  if ((int)plane != bt.bias) q.dbias = nullptr;
+  return q;
+}
+
 template <int MODE, int BM, int BN, int WAVES_M, int NWAVES, int BKT, int AVEC, int BVEC>
 __global__ __launch_bounds__(64 * NWAVES, (BKT == 16 ? 3 : 2) * NWAVES / 4) void igemm_kernel(const IgemmParams p) {
   igemm_body<MODE, BM, BN, WAVES_M, NWAVES, BKT, AVEC, BVEC>(p, gridDim.x, blockIdx.x);

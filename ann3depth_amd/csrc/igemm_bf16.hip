@@ -9,13 +9,9 @@ template <int MODE, int BN, bool X3, bool A16, bool B16, bool C16>
 static int launch_bf16_one(IgemmParams& p, unsigned grid, hipStream_t st) {
   using Cfg = Bf16Cfg<MODE, 128, BN, X3>;
   auto kern = igemm_bf16_kernel<MODE, 128, BN, X3, A16, B16, C16>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-    if (e != hipSuccess) return set_error(A3D_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done = true;
-  }
+  static bool attr_done[64] = {};
+  const int rc = raise_lds(reinterpret_cast<const void*>(kern), Cfg::LDS_BYTES, attr_done);
+  if (rc != A3D_OK) return rc;
   clear_stale_error();
   hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::NT), Cfg::LDS_BYTES, st, p);
   return check_launch("igemm_bf16");
@@ -53,13 +49,9 @@ template <int BN>
 static int launch_bf16_multi_one(IgemmMulti& ps, unsigned grid_x, unsigned count, hipStream_t st) {
   using Cfg = Bf16Cfg<MODE_BWD_D, 128, BN, false>;
   auto kern = igemm_bf16_multi_kernel<MODE_BWD_D, 128, BN, false, true, true, true>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-    if (e != hipSuccess) return set_error(A3D_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done = true;
-  }
+  static bool attr_done[64] = {};
+  const int rc = raise_lds(reinterpret_cast<const void*>(kern), Cfg::LDS_BYTES, attr_done);
+  if (rc != A3D_OK) return rc;
   clear_stale_error();
   hipLaunchKernelGGL(kern, dim3(grid_x, count), dim3(Cfg::NT), Cfg::LDS_BYTES, st, ps);
   return check_launch("igemm_bf16_multi");

@@ -66,7 +66,7 @@ static bool run_form_ok(const a3d_conv_desc* d, unsigned x_off, RunForm* rf, boo
   rf->rlp = (rf->rl + vec - 1) / vec * vec;
   rf->kp = d->r * rf->rlp;
   rf->np = (d->k + 3) / 4 * 4;
-  rf->bytes = ((size_t)rf->kp * rf->np * 4 + 255) / 256 * 256;
+  rf->bytes = up256((size_t)rf->kp * rf->np * 4);
   // the padded run of the last output column stays inside its row; `anywhere`: the run itself does (no implicit padding
   // on the right / below: a SAME convolution with an even kernel has pad_t = pad_l = 0 and still pads), its padding may not
   if (anywhere) return (d->wo - 1) * step + rf->rl <= row && (d->ho - 1) * d->stride + d->r <= d->h;
@@ -321,7 +321,7 @@ static bool bf16_image_form_ok(const a3d_conv_desc* d, const Operands& o, RunFor
   rf->rlp = (d->s * 2 + 3) / 4 * 4 * 2;
   rf->kp = d->r * rf->rlp;
   rf->np = (d->k + 7) / 8 * 8;
-  rf->bytes = ((size_t)rf->kp * rf->np * 2 + 255) / 256 * 256;
+  rf->bytes = up256((size_t)rf->kp * rf->np * 2);
   if (!(d->storage & A3D_STORE_X_BF16) || d->c != 4 || d->ldx != 4) return false;
   if (!o.known) return true;
   if ((d->storage & A3D_STORE_W_BF16) || d->precision != A3D_PREC_BF16) return false;
@@ -386,52 +386,78 @@ static Route fwd_gemm(const a3d_conv_desc* d, const Operands& o, GemmForm form) 
 
 using namespace a3d;
 
-extern "C" {
-
-// The Winograd route's workspace: [U unless prepared][V][M]
-static size_t wino_bytes(const a3d_conv_desc* d, bool bwd, bool prepared) {
-  const WinoGeom g = wino_geom(d, bwd);
-  return (prepared ? 0 : g.u_bytes) + g.v_bytes + g.m_bytes;
-}
-// one of the sixteen products: T rows of Kp gathered channels (a 1x1 conv over T one-pixel images) against U[xi] [Kp][Np]
-static IgemmParams wino_product(const WinoGeom& g, const float* V, const float* U, float* M) {
+// ---- what the Winograd routes share in the front end: a plane's product, the workspace queries, the filter's transform ----
+// The surrogate descriptor of one plane's product: an r x 1 convolution (stride 1, vertical padding pad_t) of n images h x w of c
+// channels onto ho x w pixels of k, every tensor densely packed.  F(2x2,3x3) is its r = 1 case over T one-pixel images.
+static a3d_conv_desc plane_desc(int n, int h, int w, int ho, int c, int k, int r, int pad_t) {
   a3d_conv_desc e{};
-  e.n = (int)g.T; e.h = e.w = e.ho = e.wo = 1; e.c = g.Kp; e.k = g.Np; e.r = e.s = 1; e.stride = 1; e.ldx = g.Kp; e.ldy = g.Np;
-  GemmProblem gp = fwd_problem(&e);
+  e.n = n; e.h = h; e.w = w; e.ho = ho; e.wo = w; e.c = c; e.k = k; e.r = r; e.s = 1; e.stride = 1; e.pad_t = pad_t; e.ldx = c; e.ldy = k;
+  return e;
+}
+// One plane's product as the GEMM bodies take it.  MODE_FWD: C [pixels][k] = conv(A, B [r c][k]); MODE_BWD_F: C [r c][k] = the
+// filter gradient from A (the image) and B (the gradient tensor), dbias its [splits][k] bias partials or null.
+static IgemmParams plane_product(int mode, const a3d_conv_desc& e, const float* A, const float* B, float* C, float* dbias,
+                                 unsigned long long a_elems, unsigned long long b_elems, int taps_r) {
+  const bool filt = mode == MODE_BWD_F;
+  const GemmProblem gp = filt ? bwd_f_problem(&e) : fwd_problem(&e);
   IgemmParams p;
   fill_common(p, gp);
-  p.A = V; p.B = U; p.C = M;
-  p.npix = gp.M; p.nrsc = gp.K;
-  fill_gather(p, &e, g.Kp, 1, g.Kp);
-  p.ldb = g.Np; p.ldc = g.Np;
-  fill_staging(p, MODE_FWD, (unsigned long long)g.T * g.Kp, (unsigned long long)g.Kp * g.Np, 1, 1);
+  p.A = A; p.B = B; p.C = C; p.dbias = dbias;
+  p.npix = filt ? gp.K : gp.M; p.nrsc = filt ? gp.M : gp.K;
+  fill_gather(p, &e, e.c, 1, e.c);
+  p.ldb = e.k; p.ldc = e.k;
+  fill_staging(p, mode, a_elems, b_elems, taps_r, 1);
   return p;
+}
+// the bytes a layout (a3d_internal.h) takes: its carve from offset 0
+template <typename Geom>
+static size_t product_ws_bytes(const Geom& g, bool prepared) {
+  Carve c{0};
+  carve_product(c, g, prepared);
+  return c.at;
+}
+template <typename Geom>
+static size_t grad_ws_bytes(const Geom& g) {
+  Carve c{0};
+  carve_grad(c, g);
+  return c.at;
+}
+// U: the prepared transform `w` (on the 16-byte grid), or `w` transformed by xform into the workspace's head
+template <typename Xform>
+static int transformed_filter(const char* who, bool prepared, const float* w, float* head, const float*& U, Xform&& xform) {
+  A3D_CHECK_ARG(!prepared || aligned16(w), "%s: the prepared filter must be 16-byte aligned", who);
+  U = prepared ? w : head;
+  return prepared ? A3D_OK : xform(head);
+}
+
+extern "C" {
+
+// ---- A3D_PREC_F32_WINOGRAD (wino.hip): workspace [U unless prepared][V][M] ----
+
+static size_t wino_bytes(const a3d_conv_desc* d, bool bwd, bool prepared) { return product_ws_bytes(wino_geom(d, bwd), prepared); }
+// one of the sixteen products: T rows of Kp gathered channels (a 1x1 conv over T one-pixel images) against U[xi] [Kp][Np]
+static IgemmParams wino_product(const WinoGeom& g, const float* V, const float* U, float* M) {
+  return plane_product(MODE_FWD, plane_desc((int)g.T, 1, 1, 1, g.Kp, g.Np, 1, 0), V, U, M, nullptr, (unsigned long long)g.T * g.Kp,
+                       (unsigned long long)g.Kp * g.Np, 1);
 }
 // forward (dz = x, dx = y, bias + act) or bwd-data (mask) of a descriptor wino_applicable() accepted; `w`: the filter, or its
 // transform when prepared
 static int wino_conv(const a3d_conv_desc* d, bool bwd, const float* src, const float* w, float* out, const float* bias, const float* mask,
                      int act, bool prepared, void* ws, size_t ws_bytes, hipStream_t st) {
   const WinoGeom g = wino_geom(d, bwd);
-  const size_t need = wino_bytes(d, bwd, prepared);
+  Carve c{reinterpret_cast<uintptr_t>(ws)};
+  const ProductWs at = carve_product(c, g, prepared);
+  const size_t need = c.at - reinterpret_cast<uintptr_t>(ws);
   if (!ws || need > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d (Winograd): need %zu workspace bytes", need);
-  A3D_CHECK_ARG(!prepared || aligned16(w), "conv2d (Winograd): the prepared filter must be 16-byte aligned");
-  char* base = static_cast<char*>(ws);
-  const float* U = w;
-  int rc;
-  if (!prepared) {
-    rc = wino_filter(d, bwd, w, reinterpret_cast<float*>(base), st);
-    if (rc != A3D_OK) return rc;
-    U = reinterpret_cast<const float*>(base);
-    base += g.u_bytes;
-  }
-  float* V = reinterpret_cast<float*>(base);
-  float* M = reinterpret_cast<float*>(base + g.v_bytes);
-  rc = wino_input(d, bwd, src, V, st);
+  const float* U;
+  int rc = transformed_filter("conv2d (Winograd)", prepared, w, at.U, U, [&](float* u) { return wino_filter(d, bwd, w, u, st); });
   if (rc != A3D_OK) return rc;
-  IgemmParams p = wino_product(g, V, U, M);
+  rc = wino_input(d, bwd, src, at.V, st);
+  if (rc != A3D_OK) return rc;
+  IgemmParams p = wino_product(g, at.V, U, at.M);
   rc = timed_launch(wino_record(bwd ? MODE_BWD_D : MODE_FWD, g), st, [&] { return wino_gemm(p, g, st); });
   if (rc != A3D_OK) return rc;
-  return wino_output(d, bwd, M, out, bias, mask, act, st);
+  return wino_output(d, bwd, at.M, out, bias, mask, act, st);
 }
 
 size_t a3d_conv2d_fwd_ws_bytes(const a3d_conv_desc* d) {
@@ -948,23 +974,13 @@ static bool wino_grad_takes(const a3d_conv_desc* d) { return check_desc(d) == A3
 
 // one of the sixteen sums over tiles: the filter gradient of a 1x1 conv over T one-pixel images of Cp channels, Kp filters
 static IgemmParams wino_grad_product(const WinoGradGeom& g, const float* V, const float* Z, float* slabs, float* bparts) {
-  a3d_conv_desc e{};
-  e.n = (int)g.T; e.h = e.w = e.ho = e.wo = 1; e.c = g.Cp; e.k = g.Kp; e.r = e.s = 1; e.stride = 1; e.ldx = g.Cp; e.ldy = g.Kp;
-  GemmProblem gp = bwd_f_problem(&e);
-  IgemmParams p;
-  fill_common(p, gp);
-  p.A = V; p.B = Z; p.C = slabs; p.dbias = bparts;
-  p.npix = gp.K; p.nrsc = gp.M;
-  fill_gather(p, &e, g.Cp, 1, g.Cp);
-  p.ldb = g.Kp; p.ldc = g.Kp;
-  fill_staging(p, MODE_BWD_F, (unsigned long long)g.T * g.Cp, (unsigned long long)g.T * g.Kp, 1, 1);
-  return p;
+  return plane_product(MODE_BWD_F, plane_desc((int)g.T, 1, 1, 1, g.Cp, g.Kp, 1, 0), V, Z, slabs, bparts, (unsigned long long)g.T * g.Cp,
+                       (unsigned long long)g.T * g.Kp, 1);
 }
 
 size_t a3dwg_conv2d_bwd_filter_ws_bytes(const a3d_conv_desc* d) {
   if (!wino_grad_takes(d)) return a3d_conv2d_bwd_filter_ws_bytes(d);
-  const WinoGradGeom g = wino_grad_geom(d);
-  return g.v_bytes + g.z_bytes + g.slab_bytes + g.bias_bytes;
+  return grad_ws_bytes(wino_grad_geom(d));
 }
 
 int a3dwg_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* dz, float* dw, float* db, void* ws,
@@ -973,22 +989,19 @@ int a3dwg_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float*
   A3D_CHECK_ARG(x && dz && dw, "conv2d_bwd_filter (Winograd): null tensor");
   A3D_CHECK_WS(ws, "conv2d_bwd_filter (Winograd)");
   const WinoGradGeom g = wino_grad_geom(d);
-  const size_t need = g.v_bytes + g.z_bytes + g.slab_bytes + g.bias_bytes;
+  Carve c{reinterpret_cast<uintptr_t>(ws)};
+  const GradWs at = carve_grad(c, g);
+  const size_t need = c.at - reinterpret_cast<uintptr_t>(ws);
   if (!ws || need > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd_filter (Winograd): need %zu workspace bytes", need);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  float* V = reinterpret_cast<float*>(base);
-  float* Z = reinterpret_cast<float*>(base + g.v_bytes);
-  float* slabs = reinterpret_cast<float*>(base + g.v_bytes + g.z_bytes);
-  float* bparts = reinterpret_cast<float*>(base + g.v_bytes + g.z_bytes + g.slab_bytes);
-  int rc = wino_input(d, false, x, V, st);
+  int rc = wino_input(d, false, x, at.V, st);
   if (rc != A3D_OK) return rc;
-  rc = wino_dz(d, dz, Z, st);
+  rc = wino_dz(d, dz, at.Z, st);
   if (rc != A3D_OK) return rc;
-  IgemmParams p = wino_grad_product(g, V, Z, slabs, db ? bparts : nullptr);
+  IgemmParams p = wino_grad_product(g, at.V, at.Z, at.slabs, db ? at.bparts : nullptr);
   rc = timed_launch(wino_grad_record(d, g), st, [&] { return wino_grad_gemm(p, g, st); });
   if (rc != A3D_OK) return rc;
-  return wino_dw(d, g, slabs, bparts, dw, db, st);
+  return wino_dw(d, g, at.slabs, at.bparts, dw, db, st);
 }
 
 // ---- include/a3d_wino_bwd.h: both gradients as one chain; workspace [U unless prepared][V_dz][M][V_x][Z][slabs][bias partials] ----
@@ -1011,8 +1024,10 @@ size_t a3dwb_conv2d_bwd_ws_bytes(const a3d_conv_desc* d, int w_prepared, int poo
   (void)pooled;      // the pooled-size dx has no buffer
   if (!wino_bwd_takes(d)) return std::max(a3dwg_conv2d_bwd_filter_ws_bytes(d), a3d_conv2d_bwd_data_ws_bytes(d));
   const a3d_conv_desc e = as_winograd(d);
-  const WinoGradGeom g = wino_grad_geom(&e);
-  return wino_bytes(&e, true, w_prepared != 0) + g.v_bytes + g.z_bytes + g.slab_bytes + g.bias_bytes;
+  Carve c{0};
+  carve_product(c, wino_geom(&e, true), w_prepared != 0);
+  carve_grad(c, wino_grad_geom(&e));
+  return c.at;
 }
 
 int a3dwb_conv2d_bwd(const a3d_conv_desc* d, const float* x, const float* dz, const float* w_or_U, float* dw, float* db, float* dx,
@@ -1033,30 +1048,19 @@ int a3dwb_conv2d_bwd(const a3d_conv_desc* d, const float* x, const float* dz, co
   const bool prepared = (d->hints & A3D_HINT_W_PREPARED) != 0;
   const WinoGeom g = wino_geom(&e, true);
   const WinoGradGeom gg = wino_grad_geom(&e);
-  const size_t need = wino_bytes(&e, true, prepared) + gg.v_bytes + gg.z_bytes + gg.slab_bytes + gg.bias_bytes;
+  Carve c{reinterpret_cast<uintptr_t>(ws)};
+  const ProductWs ad = carve_product(c, g, prepared);      // bwd-data's
+  const GradWs af = carve_grad(c, gg);                     // the filter gradient's
+  const size_t need = c.at - reinterpret_cast<uintptr_t>(ws);
   if (!ws || need > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd (Winograd): need %zu workspace bytes", need);
-  A3D_CHECK_ARG(!prepared || aligned16(w_or_U), "conv2d_bwd (Winograd): the prepared filter must be 16-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  const float* U = w_or_U;
-  int rc;
-  if (!prepared) {
-    rc = wino_filter(&e, true, w_or_U, reinterpret_cast<float*>(base), st);
-    if (rc != A3D_OK) return rc;
-    U = reinterpret_cast<const float*>(base);
-    base += g.u_bytes;
-  }
-  auto take = [&base](size_t bytes) {
-    float* p = reinterpret_cast<float*>(base);
-    base += bytes;
-    return p;
-  };
-  float *Vdz = take(g.v_bytes), *M = take(g.m_bytes);                                                        // bwd-data's
-  float *Vx = take(gg.v_bytes), *Z = take(gg.z_bytes), *slabs = take(gg.slab_bytes), *bparts = take(gg.bias_bytes);      // the filter gradient's
-  rc = wino_bwd_transforms(&e, x, dz, Vx, Vdz, Z, st);
+  const float* U;
+  int rc = transformed_filter("conv2d_bwd (Winograd)", prepared, w_or_U, ad.U, U, [&](float* u) { return wino_filter(&e, true, w_or_U, u, st); });
   if (rc != A3D_OK) return rc;
-  IgemmParams pf = wino_grad_product(gg, Vx, Z, slabs, db ? bparts : nullptr);
-  IgemmParams pd = wino_product(g, Vdz, U, M);
+  rc = wino_bwd_transforms(&e, x, dz, af.V, ad.V, af.Z, st);
+  if (rc != A3D_OK) return rc;
+  IgemmParams pf = wino_grad_product(gg, af.V, af.Z, af.slabs, db ? af.bparts : nullptr);
+  IgemmParams pd = wino_product(g, ad.V, U, ad.M);
   // a bracket measures one kernel: when either product's record is wanted the two run as the launches those records describe
   const a3d_timing_record rf = wino_grad_record(&e, gg), rd = wino_record(MODE_BWD_D, g);
   if (timing_wanted(rf) || timing_wanted(rd) || tune_int("A3D_WINO_BWD_PAIR", 1) == 0) {      // (A3D_TUNING=1: the A/B of the pairing)
@@ -1069,54 +1073,29 @@ int a3dwb_conv2d_bwd(const a3d_conv_desc* d, const float* x, const float* dz, co
   if (rc != A3D_OK) return rc;
   WinoBwdPool wp{};
   if (pool) wp = WinoBwdPool{pool->argmax, pool->y, pool->ldy, pool->h2, pool->w2};
-  return wino_bwd_finish(&e, gg, slabs, bparts, dw, db, M, dx, relu_mask, pool ? &wp : nullptr, st);
+  return wino_bwd_finish(&e, gg, af.slabs, af.bparts, dw, db, ad.M, dx, relu_mask, pool ? &wp : nullptr, st);
 }
 
 // ---- include/a3d_wino1d.h: the gradients of a stride-1 convolution 5 wide through 1-D Winograd F(4,5) (wino1d.hip) ----
 static bool wino1d_takes(const a3d_conv_desc* d) { return check_desc(d) == A3D_OK && wino1d_applicable(d); }
 
-// bwd-data's workspace: [U unless prepared][V][M][stream-K slabs]
-static size_t wino1d_bytes(const Wino1dGeom& g, bool prepared) { return (prepared ? 0 : g.u_bytes) + g.v_bytes + g.m_bytes + g.sk_bytes; }
-// the filter gradient's: [V][Z][slabs][bias partials]
-static size_t wino1d_grad_bytes(const Wino1dGradGeom& g) { return g.v_bytes + g.z_bytes + g.slab_bytes + g.bias_bytes; }
-
 // one of bwd-data's eight products: the forward of an r x 1 convolution over a plane of V [n][ho][tw][Kp] with vertical padding
 // r - 1 - pad_t, onto dx's rows x tiles, against U[xi] [r Kp][Np]
 static IgemmParams wino1d_product(const a3d_conv_desc* d, const Wino1dGeom& g, const float* V, const float* U, float* M) {
-  a3d_conv_desc e{};
-  e.n = d->n; e.h = d->ho; e.w = g.tw; e.ho = d->h; e.wo = g.tw; e.c = g.Kp; e.k = g.Np; e.r = g.R; e.s = 1; e.stride = 1;
-  e.pad_t = g.R - 1 - d->pad_t; e.ldx = g.Kp; e.ldy = g.Np;
-  GemmProblem gp = fwd_problem(&e);
-  IgemmParams p;
-  fill_common(p, gp);
-  p.A = V; p.B = U; p.C = M;
-  p.npix = gp.M; p.nrsc = gp.K;
-  fill_gather(p, &e, g.Kp, 1, g.Kp);
-  p.ldb = g.Np; p.ldc = g.Np;
-  fill_staging(p, MODE_FWD, (unsigned long long)g.Pv * g.Kp, (unsigned long long)g.R * g.Kp * g.Np, g.R, 1);
-  return p;
+  return plane_product(MODE_FWD, plane_desc(d->n, d->ho, g.tw, d->h, g.Kp, g.Np, g.R, g.R - 1 - d->pad_t), V, U, M, nullptr,
+                       (unsigned long long)g.Pv * g.Kp, (unsigned long long)g.R * g.Kp * g.Np, g.R);
 }
 // one of the filter gradient's eight sums: the filter gradient of an r x 1 convolution from a plane of V [n][h][tw][Cp] and a
 // plane of Z [n][ho][tw][Kp]
 static IgemmParams wino1d_grad_product(const a3d_conv_desc* d, const Wino1dGradGeom& g, const float* V, const float* Z, float* slabs,
                                        float* bparts) {
-  a3d_conv_desc e{};
-  e.n = d->n; e.h = d->h; e.w = g.tw; e.ho = d->ho; e.wo = g.tw; e.c = g.Cp; e.k = g.Kp; e.r = g.R; e.s = 1; e.stride = 1;
-  e.pad_t = d->pad_t; e.ldx = g.Cp; e.ldy = g.Kp;
-  GemmProblem gp = bwd_f_problem(&e);
-  IgemmParams p;
-  fill_common(p, gp);
-  p.A = V; p.B = Z; p.C = slabs; p.dbias = bparts;
-  p.npix = gp.K; p.nrsc = gp.M;
-  fill_gather(p, &e, g.Cp, 1, g.Cp);
-  p.ldb = g.Kp; p.ldc = g.Kp;
-  fill_staging(p, MODE_BWD_F, (unsigned long long)g.Px * g.Cp, (unsigned long long)g.Pz * g.Kp, g.R, 1);
-  return p;
+  return plane_product(MODE_BWD_F, plane_desc(d->n, d->h, g.tw, d->ho, g.Cp, g.Kp, g.R, d->pad_t), V, Z, slabs, bparts,
+                       (unsigned long long)g.Px * g.Cp, (unsigned long long)g.Pz * g.Kp, g.R);
 }
 
 size_t a3dl_conv2d_bwd_data_ws_bytes(const a3d_conv_desc* d) {
   if (!wino1d_takes(d)) return a3d_conv2d_bwd_data_ws_bytes(d);
-  return wino1d_bytes(wino1d_geom(d), (d->hints & A3D_HINT_W_PREPARED) != 0);
+  return product_ws_bytes(wino1d_geom(d), (d->hints & A3D_HINT_W_PREPARED) != 0);
 }
 
 int a3dl_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w, float* dx, const float* relu_mask, void* ws,
@@ -1126,33 +1105,25 @@ int a3dl_conv2d_bwd_data(const a3d_conv_desc* d, const float* dz, const float* w
   A3D_CHECK_WS(ws, "conv2d_bwd_data (Winograd 1-D)");
   const bool prepared = (d->hints & A3D_HINT_W_PREPARED) != 0;
   const Wino1dGeom g = wino1d_geom(d);
-  const size_t need = wino1d_bytes(g, prepared);
+  Carve c{reinterpret_cast<uintptr_t>(ws)};
+  const ProductWs at = carve_product(c, g, prepared);
+  const size_t need = c.at - reinterpret_cast<uintptr_t>(ws);
   if (!ws || need > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd_data (Winograd 1-D): need %zu workspace bytes", need);
-  A3D_CHECK_ARG(!prepared || aligned16(w), "conv2d_bwd_data (Winograd 1-D): the prepared filter must be 16-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  const float* U = w;
-  int rc;
-  if (!prepared) {
-    rc = wino1d_filter(d, w, reinterpret_cast<float*>(base), st);
-    if (rc != A3D_OK) return rc;
-    U = reinterpret_cast<const float*>(base);
-    base += g.u_bytes;
-  }
-  float* V = reinterpret_cast<float*>(base);
-  float* M = reinterpret_cast<float*>(base + g.v_bytes);
-  float* sk = reinterpret_cast<float*>(base + g.v_bytes + g.m_bytes);
-  rc = wino1d_input(dz, V, (size_t)d->n * d->ho, d->wo, d->k, d->ldy, g.off, g.tw, g.Kp, st);
+  const float* U;
+  int rc = transformed_filter("conv2d_bwd_data (Winograd 1-D)", prepared, w, at.U, U, [&](float* u) { return wino1d_filter(d, w, u, st); });
   if (rc != A3D_OK) return rc;
-  IgemmParams p = wino1d_product(d, g, V, U, M);
-  rc = timed_launch(wino1d_record(g), st, [&] { return wino1d_gemm(p, g, sk, st); });
+  rc = wino1d_input(dz, at.V, (size_t)d->n * d->ho, d->wo, d->k, d->ldy, g.off, g.tw, g.Kp, st);
   if (rc != A3D_OK) return rc;
-  return wino1d_output(d, g, M, dx, relu_mask, st);
+  IgemmParams p = wino1d_product(d, g, at.V, U, at.M);
+  rc = timed_launch(wino1d_record(g), st, [&] { return wino1d_gemm(p, g, at.sk, st); });
+  if (rc != A3D_OK) return rc;
+  return wino1d_output(d, g, at.M, dx, relu_mask, st);
 }
 
 size_t a3dl_conv2d_bwd_filter_ws_bytes(const a3d_conv_desc* d) {
   if (!wino1d_takes(d)) return a3d_conv2d_bwd_filter_ws_bytes(d);
-  return wino1d_grad_bytes(wino1d_grad_geom(d));
+  return grad_ws_bytes(wino1d_grad_geom(d));
 }
 
 int a3dl_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* dz, float* dw, float* db, void* ws, size_t ws_bytes,
@@ -1161,22 +1132,19 @@ int a3dl_conv2d_bwd_filter(const a3d_conv_desc* d, const float* x, const float* 
   A3D_CHECK_ARG(x && dz && dw, "conv2d_bwd_filter (Winograd 1-D): null tensor");
   A3D_CHECK_WS(ws, "conv2d_bwd_filter (Winograd 1-D)");
   const Wino1dGradGeom g = wino1d_grad_geom(d);
-  const size_t need = wino1d_grad_bytes(g);
+  Carve c{reinterpret_cast<uintptr_t>(ws)};
+  const GradWs at = carve_grad(c, g);
+  const size_t need = c.at - reinterpret_cast<uintptr_t>(ws);
   if (!ws || need > ws_bytes) return set_error(A3D_EWORKSPACE, "conv2d_bwd_filter (Winograd 1-D): need %zu workspace bytes", need);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* base = static_cast<char*>(ws);
-  float* V = reinterpret_cast<float*>(base);
-  float* Z = reinterpret_cast<float*>(base + g.v_bytes);
-  float* slabs = reinterpret_cast<float*>(base + g.v_bytes + g.z_bytes);
-  float* bparts = reinterpret_cast<float*>(base + g.v_bytes + g.z_bytes + g.slab_bytes);
-  int rc = wino1d_input(x, V, (size_t)d->n * d->h, d->w, d->c, d->ldx, d->pad_l, g.tw, g.Cp, st);
+  int rc = wino1d_input(x, at.V, (size_t)d->n * d->h, d->w, d->c, d->ldx, d->pad_l, g.tw, g.Cp, st);
   if (rc != A3D_OK) return rc;
-  rc = wino1d_dz(d, g, dz, Z, st);
+  rc = wino1d_dz(d, g, dz, at.Z, st);
   if (rc != A3D_OK) return rc;
-  IgemmParams p = wino1d_grad_product(d, g, V, Z, slabs, db ? bparts : nullptr);
+  IgemmParams p = wino1d_grad_product(d, g, at.V, at.Z, at.slabs, db ? at.bparts : nullptr);
   rc = timed_launch(wino1d_grad_record(d, g), st, [&] { return wino1d_grad_gemm(p, g, st); });
   if (rc != A3D_OK) return rc;
-  return wino1d_dw(d, g, slabs, bparts, dw, db, st);
+  return wino1d_dw(d, g, at.slabs, at.bparts, dw, db, st);
 }
 
 size_t a3dl_conv2d_bwd_data_prepared_filter_bytes(const a3d_conv_desc* d) { return wino1d_takes(d) ? wino1d_geom(d).u_bytes : 0; }

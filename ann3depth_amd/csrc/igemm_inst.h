@@ -21,13 +21,9 @@ static int launch_one(IgemmParams& p, unsigned grid, hipStream_t st) {
   using Cfg = IgemmCfg<A3D_MODE, BM, BN, WAVES_M, NWAVES, BK, AVEC, BVEC>;
   auto kern = igemm_kernel<A3D_MODE, BM, BN, WAVES_M, NWAVES, BK, AVEC, BVEC>;
   constexpr size_t kShared = share_lds_bytes<NWAVES>(Cfg::LDS_BYTES);
-  static bool attr_done = false;   // idempotent attribute, benign if set twice
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kShared);
-    if (e != hipSuccess) return set_error(A3D_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done = true;
-  }
+  static bool attr_done[64] = {};
+  const int rc = raise_lds(reinterpret_cast<const void*>(kern), kShared, attr_done);
+  if (rc != A3D_OK) return rc;
   clear_stale_error();
   hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::NT), p.share ? kShared : Cfg::LDS_BYTES, st, p);
   return check_launch("igemm");
@@ -48,13 +44,9 @@ template <int BM, int BN, int WAVES_M, int NWAVES>
 static int launch_glds(IgemmParams& p, unsigned grid, hipStream_t st) {
   using Cfg = GldsCfg<A3D_MODE, BM, BN, WAVES_M, NWAVES>;
   auto kern = igemm_glds_kernel<A3D_MODE, BM, BN, WAVES_M, NWAVES>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-    if (e != hipSuccess) return set_error(A3D_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done = true;
-  }
+  static bool attr_done[64] = {};
+  const int rc = raise_lds(reinterpret_cast<const void*>(kern), Cfg::LDS_BYTES, attr_done);
+  if (rc != A3D_OK) return rc;
   clear_stale_error();
   hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::NT), Cfg::LDS_BYTES, st, p);
   return check_launch("igemm_glds");
@@ -74,13 +66,9 @@ template <int AVEC, int BVEC>
 static int launch_multi_one(IgemmMulti& ps, unsigned grid_x, unsigned count, hipStream_t st) {
   using Cfg = IgemmCfg<MODE_BWD_D, 64, 64, 2, 4, 32, AVEC, BVEC>;
   auto kern = igemm_multi_kernel<MODE_BWD_D, 64, 64, 2, 4, 32, AVEC, BVEC>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-    if (e != hipSuccess) return set_error(A3D_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done = true;
-  }
+  static bool attr_done[64] = {};
+  const int rc = raise_lds(reinterpret_cast<const void*>(kern), Cfg::LDS_BYTES, attr_done);
+  if (rc != A3D_OK) return rc;
   clear_stale_error();
   hipLaunchKernelGGL(kern, dim3(grid_x, count), dim3(Cfg::NT), Cfg::LDS_BYTES, st, ps);
   return check_launch("igemm_multi");

@@ -11,16 +11,9 @@ template <int MODE, int BM, int BN, int WAVES_M, bool C16>
 static int launch_ring_one(IgemmParams& p, unsigned grid, hipStream_t st) {
   using Cfg = RingCfg<MODE, BM, BN, WAVES_M>;
   auto kern = igemm_ring_kernel<MODE, BM, BN, WAVES_M, C16>;
-  // the raised LDS limit is a per-DEVICE attribute of the kernel: one flag per device (a benign race at worst sets it twice)
   static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)Cfg::LDS_BYTES);
-    if (e != hipSuccess) return set_error(A3D_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
+  const int rc = raise_lds(reinterpret_cast<const void*>(kern), Cfg::LDS_BYTES, attr_done);
+  if (rc != A3D_OK) return rc;
   clear_stale_error();
   hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::NT), Cfg::LDS_BYTES, st, p);
   return check_launch("igemm_ring");

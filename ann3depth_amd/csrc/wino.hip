@@ -184,15 +184,70 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restric
   }
 }
 
-// ---- the sixteen products: igemm_body on problem blockIdx.y of sixteen that differ in their three base addresses ----
-constexpr int kBM = 128, kBN = 128, kWavesM = 4, kNWaves = 8, kBK = 32;
-__global__ __launch_bounds__(64 * kNWaves, 2 * kNWaves / 4) void wino_gemm_kernel(const IgemmParams p, const size_t batch_a,
-                                                                                   const size_t batch_b, const size_t batch_c) {
-  IgemmParams q = p;
-  q.A = p.A + (size_t)blockIdx.y * batch_a;
-  q.B = p.B + (size_t)blockIdx.y * batch_b;
-  q.C = p.C + (size_t)blockIdx.y * batch_c;
-  igemm_body<MODE_FWD, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>(q, gridDim.x, blockIdx.x);
+// ---- the products of every route: igemm_body on plane blockIdx.y of a PlaneBatch (igemm.h) ----
+template <int MODE, int BN, int WAVES_M, int NWAVES>
+__global__ __launch_bounds__(64 * NWAVES, 2 * NWAVES / 4) void plane_gemm_kernel(const IgemmParams p, const PlaneBatch bt) {
+  igemm_body<MODE, kBM, BN, WAVES_M, NWAVES, kBK, 4, 4>(plane_params(p, bt, blockIdx.y), gridDim.x, blockIdx.x);
+}
+
+template <int MODE, int BN, int WAVES_M, int NWAVES>
+static int plane_gemm_as(const IgemmParams& p, const PlaneBatch& bt, unsigned blocks, int planes, const char* what, hipStream_t st) {
+  using Cfg = IgemmCfg<MODE, kBM, BN, WAVES_M, NWAVES, kBK, 4, 4>;
+  static bool attr_done[64] = {};
+  const int rc = raise_lds(reinterpret_cast<const void*>(plane_gemm_kernel<MODE, BN, WAVES_M, NWAVES>), Cfg::LDS_BYTES, attr_done);
+  if (rc != A3D_OK) return rc;
+  clear_stale_error();
+  hipLaunchKernelGGL((plane_gemm_kernel<MODE, BN, WAVES_M, NWAVES>), dim3(blocks, (unsigned)planes), dim3(Cfg::NT), Cfg::LDS_BYTES, st, p, bt);
+  return check_launch(what);
+}
+
+int plane_gemm(int mode, int bn, const IgemmParams& p, const PlaneBatch& bt, unsigned blocks, int planes, const char* what, hipStream_t st) {
+  if (mode == MODE_BWD_F) return plane_gemm_as<MODE_BWD_F, kBN, kWavesM, kNWaves>(p, bt, blocks, planes, what, st);
+  if (bn == 96) return plane_gemm_as<MODE_FWD, 96, 4, 4>(p, bt, blocks, planes, what, st);
+  return plane_gemm_as<MODE_FWD, kBN, kWavesM, kNWaves>(p, bt, blocks, planes, what, st);
+}
+
+void plane_tiles(IgemmParams& p, int splits) {
+  const int nk = (p.K + kBK - 1) / kBK;
+  p.splitk = splits;
+  p.ktiles_per_split = (nk + splits - 1) / splits;
+  p.tiles_m = (p.M + kBM - 1) / kBM;
+  p.tiles_n = (p.N + kBN - 1) / kBN;
+  p.slab = (size_t)p.M * p.N;
+}
+
+// How many ways the pixel axis of a route's bwd-filter products is split: a pure function of its arguments, asked by the
+// workspace query and by the launch.  The launch stays within one round of the chip's 512 slots for blocks of eight waves (two on
+// each of 256 CUs) and a split keeps at least kMinKTiles k-tiles on average (a shorter K loop is all prologue).  Among those
+// counts the one with the least work on the busiest CU wins — a CU holds ceil(blocks / 256) blocks of 1 / s of a tile's K loop
+// each, and a block that has its CU to itself runs at nearly twice the rate of two that share one.  On a tie:
+//   F(2x2,3x3), sixteen planes: the SMALLER count (fewer slabs).  Measured at B = 8, 16, 32 for conv2d_2 and conv2d_3
+//     (profiles/wino_grad_split_sweep.txt): the rule's pick is the fastest count or within 4 us (3 %) of it in all six.
+//   F(4,5), eight planes: the LARGER count.  conv2d_1's 64 tiles tie at 4 splits (one block on every CU) and 8 (two), and two
+//     short blocks on a CU hide each other's prologue and slab stores better than one long block runs alone: 62.9 / 100.7 /
+//     179.6 us against 67.2 / 113.8 / 205.4 at B = 8 / 16 / 32 (profiles/wino1d_split_sweep.txt; the rule's pick is the fastest
+//     count in all three).
+int plane_splits(int planes, int M, int N, size_t pixels, bool larger_on_tie, const char* tuning) {
+  const long blocks1 = (long)planes * ((M + kBM - 1) / kBM) * ((N + kBN - 1) / kBN);
+  const long nk = (long)((pixels + kBK - 1) / kBK);
+  const long smax = std::max(1L, std::min(kBlockSlots / blocks1, nk / kMinKTiles));
+  long s = 1, load = (blocks1 + kCUs - 1) / kCUs;      // the busiest CU's work is load / s
+  for (long t = 2; t <= smax; ++t) {
+    const long l = (blocks1 * t + kCUs - 1) / kCUs;
+    if (l * s < load * t || (larger_on_tie && l * s == load * t)) { s = t; load = l; }
+  }
+  const int forced = tune_int(tuning, 0);      // tuning processes only (A3D_TUNING=1): the sweep behind the rule
+  if (forced > 0) s = std::min((long)forced, nk);
+  const long per = (nk + s - 1) / s;
+  return (int)((nk + per - 1) / per);
+}
+
+// ---- F(2x2,3x3): sixteen planes.  The strides between the planes of V, U and M (forward, bwd-data) and of V, Z and the raw
+//      slabs (filter gradient), whose bias partials belong to plane (1,1) ----
+constexpr int kWinoPlanes = 16;
+static PlaneBatch wino_batch(const WinoGeom& g) { return {g.T * (size_t)g.Kp, (size_t)g.Kp * g.Np, g.T * (size_t)g.Np, 0, -1}; }
+static PlaneBatch wino_grad_batch(const WinoGradGeom& g) {
+  return {g.T * (size_t)g.Cp, g.T * (size_t)g.Kp, (size_t)g.splits * g.Cp * g.Kp, 0, 1 * 4 + 1};
 }
 
 WinoGeom wino_geom(const a3d_conv_desc* d, bool bwd) {
@@ -206,10 +261,9 @@ WinoGeom wino_geom(const a3d_conv_desc* d, bool bwd) {
   g.N = bwd ? d->c : d->k;
   g.Kp = (g.K + 3) / 4 * 4;
   g.Np = (g.N + 3) / 4 * 4;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  g.v_bytes = up((size_t)16 * g.T * g.Kp * 4);
-  g.m_bytes = up((size_t)16 * g.T * g.Np * 4);
-  g.u_bytes = up((size_t)16 * g.Kp * g.Np * 4);
+  g.v_bytes = up256((size_t)16 * g.T * g.Kp * 4);
+  g.m_bytes = up256((size_t)16 * g.T * g.Np * 4);
+  g.u_bytes = up256((size_t)16 * g.Kp * g.Np * 4);
   return g;
 }
 
@@ -259,32 +313,10 @@ a3d_timing_record wino_record(int mode, const WinoGeom& g) {
   return timing_record(mode, A3D_PREC_F32, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4, 0, (int)(16 * g.T), g.N, g.K);
 }
 
-// one product's tiles: no split
-static void wino_gemm_tiles(IgemmParams& p) {
-  p.splitk = 1;
-  p.ktiles_per_split = (p.K + kBK - 1) / kBK;
-  p.tiles_m = (p.M + kBM - 1) / kBM;
-  p.tiles_n = (p.N + kBN - 1) / kBN;
-  p.slab = (size_t)p.M * p.N;
-}
-
+// the sixteen products M[xi] = V[xi] . U[xi]: no split
 int wino_gemm(IgemmParams& p, const WinoGeom& g, hipStream_t st) {
-  using Cfg = IgemmCfg<MODE_FWD, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>;
-  // the raised LDS limit is a per-DEVICE attribute of the kernel: one flag per device (a benign race at worst sets it twice)
-  static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino_gemm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)Cfg::LDS_BYTES);
-    if (e != hipSuccess) return set_error(A3D_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
-  wino_gemm_tiles(p);
-  clear_stale_error();
-  hipLaunchKernelGGL(wino_gemm_kernel, dim3((unsigned)(p.tiles_m * p.tiles_n), 16), dim3(Cfg::NT), Cfg::LDS_BYTES, st, p,
-                     g.T * (size_t)g.Kp, (size_t)g.Kp * g.Np, g.T * (size_t)g.Np);
-  return check_launch("wino_gemm");
+  plane_tiles(p, 1);
+  return plane_gemm(MODE_FWD, kBN, p, wino_batch(g), (unsigned)(p.tiles_m * p.tiles_n), kWinoPlanes, "wino_gemm", st);
 }
 
 // ==== the filter gradient (include/a3d_wino_grad.h): dg = G^T [ sum over tiles (B^T d B) (.) (A dY A^T) ] G ====
@@ -396,51 +428,17 @@ __global__ __launch_bounds__(256) void wino_dw_kernel(const float* __restrict__ 
     wino_dw_item(i, slabs, bparts, dw, db, c, k, Cp, Kp, splits);
 }
 
-// ---- the sixteen sums over tiles: the bwd-filter body on problem blockIdx.y; the bias partials belong to plane (1,1) ----
-constexpr int kBiasPlane = 1 * 4 + 1;
-__global__ __launch_bounds__(64 * kNWaves, 2 * kNWaves / 4) void wino_grad_gemm_kernel(const IgemmParams p, const size_t batch_a,
-                                                                                        const size_t batch_b, const size_t batch_c) {
-  IgemmParams q = p;
-  q.A = p.A + (size_t)blockIdx.y * batch_a;
-  q.B = p.B + (size_t)blockIdx.y * batch_b;
-  q.C = p.C + (size_t)blockIdx.y * batch_c;
-  if (blockIdx.y != kBiasPlane) q.dbias = nullptr;
-  igemm_body<MODE_BWD_F, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>(q, gridDim.x, blockIdx.x);
-}
-
-// How many ways the T axis of the sixteen products is split: a pure function of (C, K, T), asked by the workspace query and by
-// the launch.  The launch stays within one round of the chip's 512 slots for blocks of eight waves (two on each of 256 CUs) and
-// a split keeps at least kMinKTiles k-tiles on average (a shorter K loop is all prologue).  Among those counts the one with the
-// least work on the busiest CU wins — a CU holds ceil(blocks / 256) blocks of 1 / s of a tile's K loop each, and a block that
-// has its CU to itself runs at nearly twice the rate of two that share one — the smaller count on a tie (fewer slabs).  Measured
-// at B = 8, 16, 32 for conv2d_2 and conv2d_3 (profiles/wino_grad_split_sweep.txt): the rule's pick is the fastest count or
-// within 4 us (3 %) of it in all six.
-constexpr int kBlockSlots = 512, kCUs = 256, kMinKTiles = 5;
-int wino_grad_splits(int C, int K, size_t T) {
-  const long blocks1 = 16L * ((C + kBM - 1) / kBM) * ((K + kBN - 1) / kBN);
-  const long nk = (long)((T + kBK - 1) / kBK);
-  const long smax = std::max(1L, std::min(kBlockSlots / blocks1, nk / kMinKTiles));
-  long s = 1, load = (blocks1 + kCUs - 1) / kCUs;      // the busiest CU's work is load / s
-  for (long t = 2; t <= smax; ++t) {
-    const long l = (blocks1 * t + kCUs - 1) / kCUs;
-    if (l * s < load * t) { s = t; load = l; }
-  }
-  const int forced = tune_int("A3D_WINO_GRAD_SPLIT", 0);      // tuning processes only (A3D_TUNING=1): the sweep behind the rule
-  if (forced > 0) s = std::min((long)forced, nk);
-  const long per = (nk + s - 1) / s;
-  return (int)((nk + per - 1) / per);
-}
+int wino_grad_splits(int C, int K, size_t T) { return plane_splits(kWinoPlanes, C, K, T, false, "A3D_WINO_GRAD_SPLIT"); }
 
 WinoGradGeom wino_grad_geom(const a3d_conv_desc* d) {
   const WinoGeom w = wino_geom(d, false);
   WinoGradGeom g{};
   g.T = w.T; g.Cp = w.Kp; g.Kp = w.Np;
   g.splits = wino_grad_splits(d->c, d->k, w.T);
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
   g.v_bytes = w.v_bytes;
   g.z_bytes = w.m_bytes;
-  g.slab_bytes = up((size_t)16 * g.splits * g.Cp * g.Kp * 4);
-  g.bias_bytes = up((size_t)g.splits * g.Kp * 4);
+  g.slab_bytes = up256((size_t)16 * g.splits * g.Cp * g.Kp * 4);
+  g.bias_bytes = up256((size_t)g.splits * g.Kp * 4);
   return g;
 }
 
@@ -475,32 +473,10 @@ a3d_timing_record wino_grad_record(const a3d_conv_desc* d, const WinoGradGeom& g
   return r;
 }
 
-// one product's tiles and the split of its T axis
-static void wino_grad_gemm_tiles(IgemmParams& p, const WinoGradGeom& g) {
-  const int nk = (p.K + kBK - 1) / kBK;
-  p.splitk = g.splits;
-  p.ktiles_per_split = (nk + g.splits - 1) / g.splits;
-  p.tiles_m = (p.M + kBM - 1) / kBM;
-  p.tiles_n = (p.N + kBN - 1) / kBN;
-  p.slab = (size_t)p.M * p.N;
-}
-
+// the sixteen sums over tiles, the T axis in g.splits pieces
 int wino_grad_gemm(IgemmParams& p, const WinoGradGeom& g, hipStream_t st) {
-  using Cfg = IgemmCfg<MODE_BWD_F, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>;
-  static bool attr_done[64] = {};      // per device, as wino_gemm's
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino_grad_gemm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)Cfg::LDS_BYTES);
-    if (e != hipSuccess) return set_error(A3D_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
-  wino_grad_gemm_tiles(p, g);
-  clear_stale_error();
-  hipLaunchKernelGGL(wino_grad_gemm_kernel, dim3((unsigned)(p.tiles_m * p.tiles_n * p.splitk), 16), dim3(Cfg::NT), Cfg::LDS_BYTES, st, p,
-                     g.T * (size_t)g.Cp, g.T * (size_t)g.Kp, (size_t)g.splits * g.Cp * g.Kp);
-  return check_launch("wino_grad_gemm");
+  plane_tiles(p, g.splits);
+  return plane_gemm(MODE_BWD_F, kBN, p, wino_grad_batch(g), (unsigned)(p.tiles_m * p.tiles_n * p.splitk), kWinoPlanes, "wino_grad_gemm", st);
 }
 
 // ==== both gradients of one layer as one chain (include/a3d_wino_bwd.h): the transforms, products and finishing transforms of
@@ -572,47 +548,29 @@ int wino_bwd_transforms(const a3d_conv_desc* d, const float* x, const float* dz,
 // ---- launch 2: the two sets of sixteen products in one grid.  Blocks [0, 16 gf) are the filter gradient's (the longer K loop
 //      first), the rest bwd-data's; within a set the block order is that of the set's own launch (plane-major), and a block runs
 //      the body of that launch on the same parameters: same tiles, same splits, same sums ----
-struct WinoBatch {
-  size_t a, b, c;      // elements between two planes of the three operands
-};
-__global__ __launch_bounds__(64 * kNWaves, 2 * kNWaves / 4) void wino_bwd_gemm_kernel(const IgemmParams pf, const WinoBatch bf, const uint32_t gf,
-                                                                                       const IgemmParams pd, const WinoBatch bd, const uint32_t gd) {
-  if (blockIdx.x < 16 * gf) {
+__global__ __launch_bounds__(64 * kNWaves, 2 * kNWaves / 4) void wino_bwd_gemm_kernel(const IgemmParams pf, const PlaneBatch bf, const uint32_t gf,
+                                                                                       const IgemmParams pd, const PlaneBatch bd, const uint32_t gd) {
+  if (blockIdx.x < kWinoPlanes * gf) {
     const uint32_t xi = blockIdx.x / gf;
-    IgemmParams q = pf;
-    q.A = pf.A + (size_t)xi * bf.a;
-    q.B = pf.B + (size_t)xi * bf.b;
-    q.C = pf.C + (size_t)xi * bf.c;
-    if (xi != kBiasPlane) q.dbias = nullptr;
-    igemm_body<MODE_BWD_F, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>(q, gf, blockIdx.x - xi * gf);
+    igemm_body<MODE_BWD_F, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>(plane_params(pf, bf, xi), gf, blockIdx.x - xi * gf);
   } else {
-    const uint32_t id = blockIdx.x - 16 * gf, xi = id / gd;
-    IgemmParams q = pd;
-    q.A = pd.A + (size_t)xi * bd.a;
-    q.B = pd.B + (size_t)xi * bd.b;
-    q.C = pd.C + (size_t)xi * bd.c;
-    igemm_body<MODE_FWD, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>(q, gd, id - xi * gd);
+    const uint32_t id = blockIdx.x - kWinoPlanes * gf, xi = id / gd;
+    igemm_body<MODE_FWD, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>(plane_params(pd, bd, xi), gd, id - xi * gd);
   }
 }
 
 int wino_bwd_gemm(IgemmParams& pf, const WinoGradGeom& gg, IgemmParams& pd, const WinoGeom& g, hipStream_t st) {
   constexpr size_t kLds = std::max(IgemmCfg<MODE_BWD_F, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>::LDS_BYTES,
                                    IgemmCfg<MODE_FWD, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>::LDS_BYTES);
-  static bool attr_done[64] = {};      // per device, as wino_gemm's
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino_bwd_gemm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds);
-    if (e != hipSuccess) return set_error(A3D_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
-  wino_grad_gemm_tiles(pf, gg);
-  wino_gemm_tiles(pd);
+  static bool attr_done[64] = {};
+  const int rc = raise_lds(reinterpret_cast<const void*>(wino_bwd_gemm_kernel), kLds, attr_done);
+  if (rc != A3D_OK) return rc;
+  plane_tiles(pf, gg.splits);
+  plane_tiles(pd, 1);
   const uint32_t gf = (uint32_t)(pf.tiles_m * pf.tiles_n * pf.splitk), gd = (uint32_t)(pd.tiles_m * pd.tiles_n);
-  const WinoBatch bf{gg.T * (size_t)gg.Cp, gg.T * (size_t)gg.Kp, (size_t)gg.splits * gg.Cp * gg.Kp};
-  const WinoBatch bd{g.T * (size_t)g.Kp, (size_t)g.Kp * g.Np, g.T * (size_t)g.Np};
   clear_stale_error();
-  hipLaunchKernelGGL(wino_bwd_gemm_kernel, dim3(16 * (gf + gd)), dim3(64 * kNWaves), kLds, st, pf, bf, gf, pd, bd, gd);
+  hipLaunchKernelGGL(wino_bwd_gemm_kernel, dim3(kWinoPlanes * (gf + gd)), dim3(64 * kNWaves), kLds, st, pf, wino_grad_batch(gg), gf, pd,
+                     wino_batch(g), gd);
   return check_launch("wino_bwd_gemm");
 }
 

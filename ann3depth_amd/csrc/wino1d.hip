@@ -189,44 +189,23 @@ __global__ __launch_bounds__(256) void wino1d_dw_kernel(const float* __restrict_
   }
 }
 
-// ---- the eight products of bwd-data: igemm_body on problem blockIdx.y of eight that differ in their base addresses, and the
-//      fix-up of the tiles that two stream-K shares of a plane meet in (blockIdx.z = plane) ----
-struct Wino1dBatch {
-  size_t a, b, c, sk;      // elements between two planes of the three operands and of the stream-K slabs
-};
-template <int BN, int WAVES_M, int NWAVES>
-__global__ __launch_bounds__(64 * NWAVES, 2 * NWAVES / 4) void wino1d_gemm_kernel(const IgemmParams p, const Wino1dBatch bt) {
-  IgemmParams q = p;
-  q.A = p.A + (size_t)blockIdx.y * bt.a;
-  q.B = p.B + (size_t)blockIdx.y * bt.b;
-  q.C = p.C + (size_t)blockIdx.y * bt.c;
-  q.sk_ws = p.sk_ws + (size_t)blockIdx.y * bt.sk;
-  igemm_body<MODE_FWD, 128, BN, WAVES_M, NWAVES, 32, 4, 4>(q, gridDim.x, blockIdx.x);
+// ---- F(4,5): eight planes.  The strides between the planes of V, U, M and the stream-K slabs [2 * blocks][128 * bn] (bwd-data)
+//      and of V, Z and the raw slabs (filter gradient), whose bias partials belong to the plane of point 1 ----
+constexpr int kPlanes = 8;
+static PlaneBatch wino1d_batch(const Wino1dGeom& g) {
+  return {g.Pv * (size_t)g.Kp, (size_t)g.R * g.Kp * g.Np, g.Pm * (size_t)g.Np, (size_t)2 * g.blocks * 128 * g.bn, -1};
 }
-template <int BN, int WAVES_M, int NWAVES>
-__global__ __launch_bounds__(256) void wino1d_fixup_kernel(const IgemmParams p, const uint32_t nblk, const Wino1dBatch bt) {
-  IgemmParams q = p;
-  q.C = p.C + (size_t)blockIdx.z * bt.c;
-  q.sk_ws = p.sk_ws + (size_t)blockIdx.z * bt.sk;
-  igemm_fixup_body<MODE_FWD, 128, BN, WAVES_M, NWAVES>(q, nblk, blockIdx.x, blockIdx.y);
+static PlaneBatch wino1d_grad_batch(const Wino1dGradGeom& g) {
+  return {g.Px * (size_t)g.Cp, g.Pz * (size_t)g.Kp, (size_t)g.splits * g.R * g.Cp * g.Kp, 0, 1};
 }
 
-// ---- the eight sums over pixels of the filter gradient: the bwd-filter body on problem blockIdx.y; the bias partials belong to
-//      the plane of point 1 ----
-constexpr int kBM = 128, kBN = 128, kWavesM = 4, kNWaves = 8, kBK = 32;
-constexpr int kBiasPlane = 1;
-__global__ __launch_bounds__(64 * kNWaves, 2 * kNWaves / 4) void wino1d_grad_gemm_kernel(const IgemmParams p, const Wino1dBatch bt) {
-  IgemmParams q = p;
-  q.A = p.A + (size_t)blockIdx.y * bt.a;
-  q.B = p.B + (size_t)blockIdx.y * bt.b;
-  q.C = p.C + (size_t)blockIdx.y * bt.c;
-  if (blockIdx.y != kBiasPlane) q.dbias = nullptr;
-  igemm_body<MODE_BWD_F, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>(q, gridDim.x, blockIdx.x);
+// the fix-up of the tiles that two stream-K shares of a plane of bwd-data's products meet in (blockIdx.z = plane)
+template <int BN, int WAVES_M, int NWAVES>
+__global__ __launch_bounds__(256) void wino1d_fixup_kernel(const IgemmParams p, const uint32_t nblk, const PlaneBatch bt) {
+  igemm_fixup_body<MODE_FWD, kBM, BN, WAVES_M, NWAVES>(plane_params(p, bt, blockIdx.z), nblk, blockIdx.x, blockIdx.y);
 }
 
 // ---- work division: two pure functions, asked by the workspace queries and by the launches ----
-constexpr int kBlockSlots = 512, kCUs = 256, kPlanes = 8;
-
 // Blocks per plane of bwd-data's products.  The eight planes share one round of the chip's 512 block slots (two blocks on each
 // of 256 CUs, for the four-wave 128 x 96 tile and the eight-wave 128 x 128 one alike), 64 blocks a plane, and a plane's (tile,
 // k-tile) iterations are dealt to them as equal stream-K shares: at B = 32 conv2d_1 has 67.5 tiles of 128 rows a plane, which as
@@ -241,29 +220,8 @@ int wino1d_bwd_blocks(long tiles, long nk) {
   return (int)b;
 }
 
-// How many ways the pixel axis of the filter gradient's eight products is split: wino_grad_splits' rule for eight planes.  The
-// launch stays within one round of the 512 slots, a split keeps at least kMinKTiles k-tiles on average, and among those counts
-// the one with the least work on the busiest CU wins — here the LARGER count on a tie: conv2d_1's 64 tiles tie at 4 splits
-// (one block on every CU) and 8 (two), and two short blocks on a CU hide each other's prologue and slab stores better than one
-// long block runs alone: 62.9 / 100.7 / 179.6 us against 67.2 / 113.8 / 205.4 at B = 8 / 16 / 32
-// (profiles/wino1d_split_sweep.txt; the rule's pick is the fastest count in all three).
-constexpr int kMinKTiles = 5;
-int wino1d_grad_splits(int M, int N, size_t pixels) {
-  const long blocks1 = (long)kPlanes * ((M + kBM - 1) / kBM) * ((N + kBN - 1) / kBN);
-  const long nk = (long)((pixels + kBK - 1) / kBK);
-  const long smax = std::max(1L, std::min(kBlockSlots / blocks1, nk / kMinKTiles));
-  long s = 1, load = (blocks1 + kCUs - 1) / kCUs;      // the busiest CU's work is load / s
-  for (long t = 2; t <= smax; ++t) {
-    const long l = (blocks1 * t + kCUs - 1) / kCUs;
-    if (l * s <= load * t) { s = t; load = l; }
-  }
-  const int forced = tune_int("A3D_WINO1D_GRAD_SPLIT", 0);      // tuning processes only: the sweep behind the rule
-  if (forced > 0) s = std::min((long)forced, nk);
-  const long per = (nk + s - 1) / s;
-  return (int)((nk + per - 1) / per);
-}
-
-static size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+// plane_splits for eight planes, the larger count on a tie
+int wino1d_grad_splits(int M, int N, size_t pixels) { return plane_splits(kPlanes, M, N, pixels, true, "A3D_WINO1D_GRAD_SPLIT"); }
 
 Wino1dGeom wino1d_geom(const a3d_conv_desc* d) {
   Wino1dGeom g{};
@@ -369,34 +327,7 @@ a3d_timing_record wino1d_grad_record(const a3d_conv_desc* d, const Wino1dGradGeo
   return r;
 }
 
-// the raised LDS limit is a per-DEVICE attribute of a kernel: one flag per device (a benign race at worst sets it twice)
-static int raise_lds(const void* kern, size_t bytes, bool (&done)[64]) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !done[dev]) {
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return set_error(A3D_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    if (dev >= 0 && dev < 64) done[dev] = true;
-  }
-  return A3D_OK;
-}
-
-template <int BN, int WAVES_M, int NWAVES>
-static int wino1d_gemm_as(IgemmParams& p, const Wino1dGeom& g, const Wino1dBatch& bt, hipStream_t st) {
-  using Cfg = IgemmCfg<MODE_FWD, 128, BN, WAVES_M, NWAVES, 32, 4, 4>;
-  static bool attr_done[64] = {};
-  int rc = raise_lds(reinterpret_cast<const void*>(wino1d_gemm_kernel<BN, WAVES_M, NWAVES>), Cfg::LDS_BYTES, attr_done);
-  if (rc != A3D_OK) return rc;
-  clear_stale_error();
-  hipLaunchKernelGGL((wino1d_gemm_kernel<BN, WAVES_M, NWAVES>), dim3((unsigned)g.blocks, kPlanes), dim3(Cfg::NT), Cfg::LDS_BYTES, st, p, bt);
-  rc = check_launch("wino1d_gemm");
-  if (rc != A3D_OK) return rc;
-  hipLaunchKernelGGL((wino1d_fixup_kernel<BN, WAVES_M, NWAVES>), dim3((unsigned)(g.tiles_m * g.tiles_n), (128 * BN / 256 + 3) / 4, kPlanes),
-                     dim3(256), 0, st, p, (uint32_t)g.blocks, bt);
-  return check_launch("wino1d_fixup");
-}
-
-// p: one product (wino1d_product); the eight differ in A, B, C and their slabs [2 * blocks][128 * bn] at sk
+// p: one product (wino1d_product); the eight planes' stream-K shares in one launch, then the fix-up of the tiles they share
 int wino1d_gemm(IgemmParams& p, const Wino1dGeom& g, float* sk, hipStream_t st) {
   p.splitk = 1;
   p.ktiles_per_split = g.nk;
@@ -406,27 +337,19 @@ int wino1d_gemm(IgemmParams& p, const Wino1dGeom& g, float* sk, hipStream_t st) 
   p.streamk = 1;
   p.sk_ws = sk;
   p.div_nk = make_fastdiv((uint32_t)g.nk);
-  const Wino1dBatch bt{g.Pv * (size_t)g.Kp, (size_t)g.R * g.Kp * g.Np, g.Pm * (size_t)g.Np, (size_t)2 * g.blocks * 128 * g.bn};
-  if (g.bn == 96) return wino1d_gemm_as<96, 4, 4>(p, g, bt, st);
-  return wino1d_gemm_as<128, 4, 8>(p, g, bt, st);
+  const PlaneBatch bt = wino1d_batch(g);
+  const int rc = plane_gemm(MODE_FWD, g.bn, p, bt, (unsigned)g.blocks, kPlanes, "wino1d_gemm", st);
+  if (rc != A3D_OK) return rc;
+  const dim3 grid((unsigned)(g.tiles_m * g.tiles_n), (128 * g.bn / 256 + 3) / 4, kPlanes);
+  if (g.bn == 96) hipLaunchKernelGGL((wino1d_fixup_kernel<96, 4, 4>), grid, dim3(256), 0, st, p, (uint32_t)g.blocks, bt);
+  else hipLaunchKernelGGL((wino1d_fixup_kernel<kBN, kWavesM, kNWaves>), grid, dim3(256), 0, st, p, (uint32_t)g.blocks, bt);
+  return check_launch("wino1d_fixup");
 }
 
 // p: one product (wino1d_grad_product), splits and tiles filled in here
 int wino1d_grad_gemm(IgemmParams& p, const Wino1dGradGeom& g, hipStream_t st) {
-  using Cfg = IgemmCfg<MODE_BWD_F, kBM, kBN, kWavesM, kNWaves, kBK, 4, 4>;
-  static bool attr_done[64] = {};
-  const int rc = raise_lds(reinterpret_cast<const void*>(wino1d_grad_gemm_kernel), Cfg::LDS_BYTES, attr_done);
-  if (rc != A3D_OK) return rc;
-  const int nk = (p.K + kBK - 1) / kBK;
-  p.splitk = g.splits;
-  p.ktiles_per_split = (nk + g.splits - 1) / g.splits;
-  p.tiles_m = (p.M + kBM - 1) / kBM;
-  p.tiles_n = (p.N + kBN - 1) / kBN;
-  p.slab = (size_t)p.M * p.N;
-  const Wino1dBatch bt{g.Px * (size_t)g.Cp, g.Pz * (size_t)g.Kp, (size_t)g.splits * p.slab, 0};
-  clear_stale_error();
-  hipLaunchKernelGGL(wino1d_grad_gemm_kernel, dim3((unsigned)(p.tiles_m * p.tiles_n * p.splitk), kPlanes), dim3(Cfg::NT), Cfg::LDS_BYTES, st, p, bt);
-  return check_launch("wino1d_grad_gemm");
+  plane_tiles(p, g.splits);
+  return plane_gemm(MODE_BWD_F, kBN, p, wino1d_grad_batch(g), (unsigned)(p.tiles_m * p.tiles_n * p.splitk), kPlanes, "wino1d_grad_gemm", st);
 }
 
 }  // namespace a3d
