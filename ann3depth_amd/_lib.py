@@ -223,6 +223,12 @@ WINO1D_SIGNATURES = {
     'a3dl_conv2d_bwd_data_prepare_filter': (c_int, [_D, _P, _P, c_size_t, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_optim.h declares (NON-REFERENCE extension, prefix a3do_)
+OPTIM_SIGNATURES = {
+    'a3do_momentum_apply': (c_int, [c_size_t, _P, _P, _P, c_float, c_float, c_float, _P]),
+    'a3do_dense_bwd_filter_momentum': (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_float, c_float, c_float, _P]),
+}
+
 class WinoBwdPool(ctypes.Structure):
     """a3dwb_pool (include/a3d_wino_bwd.h): the 2x2 max pool below a layer, as the fused forward recorded it."""
     _fields_ = [('argmax', c_void_p), ('y', c_void_p), ('ldy', c_int), ('h2', c_int), ('w2', c_int)]
@@ -281,6 +287,7 @@ SURFACES = (
     Surface('a3da_', 'a3d_align.h', ALIGN_SIGNATURES),
     Surface('a3di_', 'a3d_ssi.h', SSI_SIGNATURES),
     Surface('a3dl_', 'a3d_wino1d.h', WINO1D_SIGNATURES),
+    Surface('a3do_', 'a3d_optim.h', OPTIM_SIGNATURES),
 )
 
 _lib = None

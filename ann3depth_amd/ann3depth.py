@@ -10,7 +10,7 @@ replaced by synchronous RCCL data parallelism: launch one process per GPU with
 accepted and ignored.
 
 Flags that are not the reference's: --beta2, --precision, --augment, --min-depth / --max-depth, --loss-gradient,
---loss {silog,berhu,ssi}, --berhu-fraction,
+--loss {silog,berhu,ssi}, --berhu-fraction, --optimizer {adam,momentum}, --momentum, --lr-scale,
 --train-pairwise, --pairwise-texture, --superpixel {40,20,10}, --unary {patch,fcsp} (dcnf: the unary part over 48 patches per image, the
 reference's, or once over the whole image with superpixel pooling before the dense head), --seed, --tf-checkpoints,
 --trace-every, --profiler.
@@ -123,6 +123,25 @@ def main(argv=None):
     if args.berhu_fraction is not None and not 0 < args.berhu_fraction <= 1:
         logger.error(f'--berhu-fraction {args.berhu_fraction}: the threshold is a fraction in (0, 1] of the largest error.')
         return 2
+    given = [f for f, on in (('--optimizer', args.optimizer != 'adam'), ('--momentum', args.momentum is not None),
+                             ('--lr-scale', args.lr_scale is not None)) if on]
+    if given and args.model != 'msdn':
+        logger.error(f'{" / ".join(given)} choose the optimizer and the rates of --model msdn (Eigen et al. 2014 trained it by SGD '
+                     f'with momentum): {args.model or "(no model)"} is not trained with them (dcnf descends by plain gradient '
+                     f'descent at 0.1, as the reference does).')
+        return 2
+    if args.optimizer == 'momentum' and args.beta2 is not None:
+        logger.error('--optimizer momentum cannot go with --beta2: beta2 belongs to --optimizer adam.')
+        return 2
+    if args.momentum is not None and args.optimizer != 'momentum':
+        logger.error(f'--momentum sets the momentum of --optimizer momentum; --optimizer {args.optimizer} has none.')
+        return 2
+    if args.momentum is not None and not 0 <= args.momentum < 1:
+        logger.error(f'--momentum {args.momentum}: a number in [0, 1).')
+        return 2
+    if args.lr_scale is not None and not 0 < args.lr_scale < float('inf'):
+        logger.error(f'--lr-scale {args.lr_scale}: a finite number > 0.')
+        return 2
     if args.min_depth is not None or args.max_depth is not None:
         lo = 0. if args.min_depth is None else args.min_depth
         hi = float('inf') if args.max_depth is None else args.max_depth
@@ -191,6 +210,10 @@ def setup_model(args, rank=0, world=1):
     if hasattr(model, 'objective'):                                      # main() has refused the models that have none
         model.objective = args.loss
         model.berhu_fraction = 0.2 if args.berhu_fraction is None else float(args.berhu_fraction)
+    if hasattr(model, 'optimizer'):                                      # main() has refused the models that have none
+        model.optimizer = args.optimizer
+        model.momentum = 0.9 if args.momentum is None else float(args.momentum)
+        model.lr_scale = 1.0 if args.lr_scale is None else float(args.lr_scale)
     if hasattr(model, 'train_pairwise'):                                 # main() has refused the models that have none
         model.train_pairwise = bool(args.train_pairwise)
     if hasattr(model, 'pairwise_texture'):
@@ -363,7 +386,7 @@ class Session:
         prefix = f'model.ckpt-{rep.global_step}'
         path = os.path.join(self.dir, prefix + '.pt')
         tmp = path + '.tmp'
-        torch.save({k: v.detach().cpu() for k, v in rep.state_dict().items()}, tmp)
+        torch.save({k: v.detach().cpu() if torch.is_tensor(v) else v for k, v in rep.state_dict().items()}, tmp)
         os.replace(tmp, path)
         if self.tf_checkpoints:                               # the same state as a TensorFlow V2 checkpoint
             tfckpt.write_bundle(os.path.join(self.dir, prefix), rep.tf_variables())
@@ -509,6 +532,17 @@ def parse_args(argv=None):
     parser.add_argument('--berhu-fraction', default=None, type=float, metavar='F',
                         help='NON-REFERENCE, --loss berhu: the threshold is F times the largest error of each sample (per sample, '
                              'not per batch, so that a sample\'s gradient does not depend on its batch). 0 < F <= 1, default 0.2.')
+    parser.add_argument('--optimizer', default='adam', choices=['adam', 'momentum'],
+                        help='NON-REFERENCE unless adam: the update rule (msdn only). adam: the reference\'s AdamOptimizer(rate, 0.9, '
+                             'beta2), which at its beta2 = 1 never moves a weight. momentum: SGD with momentum without Nesterov '
+                             '(TensorFlow\'s MomentumOptimizer), the rule the per-group rates 0.001 / 0.1 / 0.001 / 0.01 were published '
+                             'for (Eigen et al. 2014); one slot per variable instead of two, and the dense layers\' filter gradient '
+                             'goes straight into the update. Not with --beta2. A checkpoint restores only under the optimizer '
+                             'that wrote it; evaluate and predict read that from the checkpoint.')
+    parser.add_argument('--momentum', default=None, type=float, metavar='M',
+                        help='NON-REFERENCE, --optimizer momentum: its momentum. 0 <= M < 1, default 0.9.')
+    parser.add_argument('--lr-scale', default=None, type=float, metavar='S',
+                        help='NON-REFERENCE: multiply every per-group rate by S (msdn only, either optimizer). S > 0, default 1.')
     parser.add_argument('--train-pairwise', action='store_true',
                         help='NON-REFERENCE: learn the pairwise dense layer of the CRF (dcnf only). The reference leaves it at '
                              'its initial draw (TF 1.3 has no gradient for scatter_nd_update); with this flag the loss is also '

@@ -1,0 +1,200 @@
+// optim.hip — SGD with momentum (include/a3d_optim.h, NON-REFERENCE, --optimizer momentum): TensorFlow 1.3's ApplyMomentum
+// without Nesterov, as a streaming kernel over a flat parameter group and fused into the dense layers' filter gradient.
+//   g' = grad_scale == 1 ? g : g * grad_scale;   accum' = accum * momentum + g';   var' = var - lr * accum'
+// This file is compiled with -ffp-contract=off (see Makefile): every operation rounds to fp32 on its own, so the kernels are
+// bit-exact against the numpy restatement (tests/momentum_ref.py) and the fused launch against the two-call form.
+// var, accum and g are hundreds of MB read once and written once: their accesses are non-temporal (igemm.h, kAuxStream),
+// so that they do not push the operands a GEMM of the other stream re-reads out of the L2.
+#include "a3d_internal.h"
+#include "igemm.h"
+#include "../../include/a3d_optim.h"
+
+using namespace a3d;
+
+namespace a3d {
+
+__device__ __forceinline__ void momentum_one(float& var, float& accum, float g, float lr, float mu) {
+  accum = __fadd_rn(__fmul_rn(accum, mu), g);
+  var = __fsub_rn(var, __fmul_rn(lr, accum));
+}
+
+// adam_kernel's shape (pointwise.hip): 16-byte vectors grid-strided, the count % 4 tail by block 0
+__global__ __launch_bounds__(256) void momentum_kernel(float* __restrict__ var, float* __restrict__ accum,
+                                                       const float* __restrict__ g, size_t count, float lr, float mu,
+                                                       float gscale) {
+  const size_t nvec = count / 4;
+  const bool use_scale = gscale != 1.f;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
+    f32x4 w4 = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(var) + i);
+    f32x4 a4 = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(accum) + i);
+    const f32x4 g4 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float wj = w4[j], aj = a4[j];
+      momentum_one(wj, aj, use_scale ? __fmul_rn(g4[j], gscale) : g4[j], lr, mu);
+      w4[j] = wj; a4[j] = aj;
+    }
+    __builtin_nontemporal_store(w4, reinterpret_cast<f32x4*>(var) + i);
+    __builtin_nontemporal_store(a4, reinterpret_cast<f32x4*>(accum) + i);
+  }
+  if (blockIdx.x == 0) {
+    const size_t i = nvec * 4 + threadIdx.x;
+    if (i < count) momentum_one(var[i], accum[i], use_scale ? __fmul_rn(g[i], gscale) : g[i], lr, mu);
+  }
+}
+
+// dense_dw_kernel<true, 2> (dense.hip) with the momentum rule in its epilogue: a wave owns 32 weight rows x 64 columns, lane li
+// takes dz[m][n0 + 2 li .. + 1] with one 8-byte load and feeds two fp32 MFMA 32x32x2 (the batch is the contraction axis, in
+// ascending order: dense_dw_launch's sum, bit for bit), and register v of the two accumulators is two adjacent columns of row
+// row_of(v).  The wave's accum AND var tiles (2 x 16 registers of two floats) are requested before the contraction starts, so
+// their HBM latency passes under the operand loads (x and dz: L2-resident) and the MFMAs.  No LDS.  Rows of an odd n are
+// 4-byte aligned only: the two-float type is aligned(4), and the lanes across the last column take the scalar path.
+// GEMM_ORDER: the batch rows reach the matrix cores in the order of the implicit-GEMM route (igemm.h: a lane half holds four
+// consecutive rows of a chunk of eight, instruction j of the chunk multiplies rows 8u + j and 8u + 4 + j), which is what
+// a3d_dense_bwd_filter runs below k n = 2^16: the two-call form's bits there too.  Rows past the batch are zeros in both.
+typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
+
+template <bool GEMM_ORDER>
+__global__ __launch_bounds__(256) void dense_dw_momentum_kernel(const float* __restrict__ x, const float* __restrict__ dz,
+                                                                float* __restrict__ var_w, float* __restrict__ acc_w,
+                                                                float* __restrict__ var_b, float* __restrict__ acc_b,
+                                                                int M, int K, int N, float lr, float mu, float gscale) {
+  constexpr int CW = 2, TILE_N = 32 * CW;
+  typedef f32x2u vec;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int li = lane & 31, lh = lane >> 5;
+  const int n0 = blockIdx.x * TILE_N, k0 = (blockIdx.y * 4 + wave) * 32;
+  const bool use_scale = gscale != 1.f;
+
+  // BiasAddGrad and its step: the blocks of the first row group, one column per thread (dense_dw_kernel's walk)
+  if (blockIdx.y == 0 && tid < TILE_N && n0 + tid < N && acc_b != nullptr) {
+    const int col = n0 + tid;
+    float s = 0.f;
+    for (int m0 = 0; m0 < M; m0 += 8) {       // eight loads in flight, added in row order
+      float t[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) t[i] = m0 + i < M ? dz[(size_t)(m0 + i) * N + col] : 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        if (m0 + i < M) s += t[i];
+    }
+    momentum_one(var_b[col], acc_b[col], use_scale ? __fmul_rn(s, gscale) : s, lr, mu);
+  }
+  if (k0 >= K) return;      // wave-uniform
+
+  const int col0 = n0 + CW * li;                  // this lane's two columns
+  const bool cfull = col0 + CW - 1 < N;           // both exist (only the last lane of the last column group may hold one)
+  auto row_of = [&](int v) -> int { return k0 + (v & 3) + 8 * (v >> 2) + 4 * lh; };
+
+  // Branch-free: a lane without a whole piece in row_of(v) reads the piece at element 0 instead and never uses it (sixteen
+  // conditional loads ahead of the loop made the register allocator spill the accumulators).  A 1 x 1 matrix has no piece.
+  vec aold[16], wold[16];
+#pragma unroll
+  for (int v = 0; v < 16; ++v) aold[v] = wold[v] = vec{0.f, 0.f};
+  if ((size_t)K * N >= 2) {      // uniform
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      const int row = row_of(v);
+      const size_t o = (row < K && cfull) ? (size_t)row * N + col0 : 0;
+      aold[v] = __builtin_nontemporal_load(reinterpret_cast<const vec*>(acc_w + o));
+      wold[v] = __builtin_nontemporal_load(reinterpret_cast<const vec*>(var_w + o));
+    }
+  }
+
+  f32x16 acc[CW];
+#pragma unroll
+  for (int j = 0; j < CW; ++j)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[j][v] = 0.f;
+
+  // A[i = weight row k0+li][kk = batch row 2t+lh] = x[2t+lh][k0+li];  B_j[kk][li] = dz[2t+lh][col0 + j]  (GEMM_ORDER: rows as above)
+  const int krow = k0 + li;
+  const bool kok = krow < K;
+  const int T = GEMM_ORDER ? (M + 7) / 8 * 4 : (M + 1) / 2;       // instructions: two batch rows each
+  for (int t0 = 0; t0 < T; t0 += 8) {
+    float a[8];
+    vec bq[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int m = GEMM_ORDER ? 8 * ((t0 + u) >> 2) + 4 * lh + ((t0 + u) & 3) : 2 * (t0 + u) + lh;
+      const bool mok = m < M;
+      a[u] = (mok && kok) ? x[(size_t)m * K + krow] : 0.f;
+      bq[u] = vec{0.f, 0.f};
+      if (mok) {
+        if (cfull) {
+          bq[u] = *reinterpret_cast<const vec*>(dz + (size_t)m * N + col0);
+        } else {
+#pragma unroll
+          for (int j = 0; j < CW; ++j)
+            if (col0 + j < N) bq[u][j] = dz[(size_t)m * N + col0 + j];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+      for (int j = 0; j < CW; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], bq[u][j], acc[j], 0, 0, 0);
+  }
+
+  // epilogue: register v of the two accumulators = two adjacent columns of row row_of(v)
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    const int row = row_of(v);
+    if (row >= K) continue;
+    const size_t o = (size_t)row * N + col0;
+    if (cfull) {
+      vec an = aold[v], wn = wold[v];
+#pragma unroll
+      for (int j = 0; j < CW; ++j) {
+        float wj = wn[j], aj = an[j];
+        momentum_one(wj, aj, use_scale ? __fmul_rn(acc[j][v], gscale) : acc[j][v], lr, mu);
+        wn[j] = wj; an[j] = aj;
+      }
+      __builtin_nontemporal_store(an, reinterpret_cast<vec*>(acc_w + o));
+      __builtin_nontemporal_store(wn, reinterpret_cast<vec*>(var_w + o));
+    } else {
+#pragma unroll
+      for (int j = 0; j < CW; ++j)
+        if (col0 + j < N) momentum_one(var_w[o + j], acc_w[o + j], use_scale ? __fmul_rn(acc[j][v], gscale) : acc[j][v], lr, mu);
+    }
+  }
+}
+
+}  // namespace a3d
+
+extern "C" {
+
+int a3do_momentum_apply(size_t count, float* var, float* accum, const float* g, float lr, float momentum, float grad_scale,
+                        void* stream) {
+  A3D_CHECK_ARG(count > 0 && var && accum && g, "momentum_apply: bad arguments");
+  A3D_CHECK_ARG(((reinterpret_cast<uintptr_t>(var) | reinterpret_cast<uintptr_t>(accum) | reinterpret_cast<uintptr_t>(g)) & 15) == 0,
+                "momentum_apply: buffers must be 16-byte aligned");
+  clear_stale_error();
+  hipLaunchKernelGGL(momentum_kernel, dim3(grid_for(count / 4 + 1, 256, 4096)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     var, accum, g, count, lr, momentum, grad_scale);
+  return check_launch("momentum_apply");
+}
+
+int a3do_dense_bwd_filter_momentum(int m, int k, int n, const float* x, const float* dz, float* var_w, float* accum_w,
+                                   float* var_b, float* accum_b, float lr, float momentum, float grad_scale, void* stream) {
+  A3D_CHECK_ARG(m > 0 && k > 0 && n > 0 && x && dz && var_w && accum_w, "dense_bwd_filter_momentum: bad arguments");
+  A3D_CHECK_ARG((var_b && accum_b) || (!var_b && !accum_b), "dense_bwd_filter_momentum: the bias and its accumulator come as a pair");
+  A3D_CHECK_ARG(dense_dw_applicable(m, k, n),
+                "dense_bwd_filter_momentum: batches of at most 64 rows only; otherwise call a3d_dense_bwd_filter and "
+                "a3do_momentum_apply");
+  A3D_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(var_w) |
+                  reinterpret_cast<uintptr_t>(accum_w) | reinterpret_cast<uintptr_t>(var_b) | reinterpret_cast<uintptr_t>(accum_b)) & 3) == 0,
+                "dense_bwd_filter_momentum: tensors must be 4-byte aligned");
+  clear_stale_error();
+  const dim3 grid((n + 63) / 64, (k + 127) / 128);
+  // a3d_dense_bwd_filter's own dispatch: the dense kernel from k n = 2^16 on, the implicit-GEMM route below
+  if ((long)k * n >= (1L << 16))
+    hipLaunchKernelGGL(dense_dw_momentum_kernel<false>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), x, dz, var_w, accum_w,
+                       var_b, accum_b, m, k, n, lr, momentum, grad_scale);
+  else
+    hipLaunchKernelGGL(dense_dw_momentum_kernel<true>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), x, dz, var_w, accum_w,
+                       var_b, accum_b, m, k, n, lr, momentum, grad_scale);
+  return check_launch("dense_dw_momentum");
+}
+
+}  // extern "C"

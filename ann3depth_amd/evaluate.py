@@ -305,7 +305,7 @@ def restore_replica(args, ckpt, say, dev=None):
     model and --superpixel cannot use.  dev: the GPU to restore to; None (the prediction driver) reads the checkpoint on
     the host and asks for the current GPU only once nothing is left to refuse."""
     from .models import (DCNF_PAIR_PREFIX, DCNF_PREFIX, DCNFReplica, MSDNReplica, check_dcnf_segmentation,
-                         check_dcnf_superpixel)
+                         check_dcnf_superpixel, checkpoint_optimizer)
     say(f'restoring {ckpt}')
     state, bundle = read_checkpoint(ckpt, 'cpu' if dev is None else dev)
     texture, unary = False, 'patch'
@@ -338,7 +338,9 @@ def restore_replica(args, ckpt, say, dev=None):
                               superpixel=args.superpixel, segmentation=args.segmentation, slic_iters=args.slic_iters,
                               slic_compactness=args.slic_compactness)
     else:
-        replica = MSDNReplica(args.batchsize, device=dev, precision=args.precision, keep_dense_grads=False)
+        # the checkpoint says which optimizer's slots it holds: a run of --optimizer momentum restores with no flag
+        replica = MSDNReplica(args.batchsize, device=dev, precision=args.precision, keep_dense_grads=False,
+                              optimizer=checkpoint_optimizer(state))
     load_checkpoint(replica, state, bundle)
     return replica, texture, unary
 

@@ -74,11 +74,17 @@ class ParamGroup:
     """All variables of one tf.train.AdamOptimizer instance in ONE flat buffer (plus gradient and the m / v slots),
     so the optimizer is a single streaming kernel and the data-parallel all-reduce a single bucket."""
     ALIGN = 64   # elements; keeps every tensor 256-byte aligned for 16-byte vector loads
+    optimizer = 'adam'      # a group built with 'momentum' carries its own, and its momentum
 
-    def __init__(self, name, lr, shapes, device, beta1=0.9, beta2=1.0, eps=1e-8, slots=True, multiple=1):
+    def __init__(self, name, lr, shapes, device, beta1=0.9, beta2=1.0, eps=1e-8, slots=True, multiple=1, optimizer='adam',
+                 momentum=0.9):
         """multiple: the flat length is padded (with zeros that stay zeros) to a multiple of multiple * ALIGN elements, so
-        that `multiple` data-parallel ranks can cut any bucket of it into equal, 256-byte-aligned slices."""
+        that `multiple` data-parallel ranks can cut any bucket of it into equal, 256-byte-aligned slices.
+        optimizer 'momentum' (NON-REFERENCE): tf.train.MomentumOptimizer(lr, momentum) without Nesterov (ops.momentum_apply):
+        `m` is its accumulator, there is no `v`, and the beta powers go unused."""
         self.name, self.lr, self.beta1, self.beta2, self.eps = name, lr, beta1, beta2, eps
+        if optimizer == 'momentum':
+            self.optimizer, self.momentum = optimizer, momentum
         self.offsets = collections.OrderedDict()
         off = 0
         for n, shp in shapes.items():
@@ -89,7 +95,7 @@ class ParamGroup:
         self.var = torch.zeros(off, device=device)
         self.grad = torch.zeros(off, device=device)
         self.m = torch.zeros(off, device=device) if slots else None      # slots=False: plain gradient descent
-        self.v = torch.zeros(off, device=device) if slots else None
+        self.v = torch.zeros(off, device=device) if slots and optimizer != 'momentum' else None
         # beta powers are host scalars, updated after each apply like AdamOptimizer._finish
         self.beta1_power = np.float32(beta1)
         self.beta2_power = np.float32(beta2)
@@ -99,6 +105,9 @@ class ParamGroup:
         return buf[off:off + int(np.prod(shp))].view(shp)
 
     def apply(self, grad_scale=1.0):
+        if self.optimizer == 'momentum':
+            ops.momentum_apply(self.var, self.m, self.grad, self.lr, self.momentum, grad_scale)
+            return
         ops.adam_apply_tf1(self.var, self.m, self.v, self.grad, self.lr, self.beta1, self.beta2, self.eps,
                            float(self.beta1_power), float(self.beta2_power), grad_scale)
         self.beta1_power = self.beta1_power * np.float32(self.beta1)
@@ -107,15 +116,21 @@ class ParamGroup:
     def apply_slice(self, a, b, grad_scale=1.0, poisoned=None):
         """ApplyAdam on elements [a, b) only (a data-parallel rank's slice of a reduce-scattered bucket); the caller
         advances the beta powers once per step with advance()."""
+        if self.optimizer == 'momentum':       # no poison flag: nothing of this rule is sharded
+            ops.momentum_apply(self.var[a:b], self.m[a:b], self.grad[a:b], self.lr, self.momentum, grad_scale)
+            return
         ops.adam_apply_tf1(self.var[a:b], self.m[a:b], self.v[a:b], self.grad[a:b], self.lr, self.beta1, self.beta2,
                            self.eps, float(self.beta1_power), float(self.beta2_power), grad_scale, poisoned=poisoned)
 
     def frozen(self):
         """True for the optimizer the reference builds, AdamOptimizer(rate, 0.9, beta2 = 1): alpha = 0, only m moves."""
-        return self.beta2 == 1.0 and float(self.beta2_power) == 1.0
+        return self.optimizer == 'adam' and self.beta2 == 1.0 and float(self.beta2_power) == 1.0
 
     def advance(self):
-        """The beta-power bookkeeping of one ApplyAdam whose tensor work was fused elsewhere (dense_bwd_filter_adam_tf1)."""
+        """The beta-power bookkeeping of one ApplyAdam whose tensor work was fused elsewhere (dense_bwd_filter_adam_tf1).
+        Momentum keeps no such scalar."""
+        if self.optimizer == 'momentum':
+            return
         self.beta1_power = self.beta1_power * np.float32(self.beta1)
         self.beta2_power = self.beta2_power * np.float32(self.beta2)
 
@@ -145,9 +160,11 @@ class Replica:
     """What the two models' replicas do alike beyond their interface (state_dict() and self.global_step are each one's own)."""
 
     def tf_variables(self):
-        """name -> ndarray in TensorFlow's naming, for tfckpt.write_bundle."""
+        """name -> ndarray in TensorFlow's naming, for tfckpt.write_bundle (a state's 'optimizer' string is not a variable)."""
         out = {}
         for k, v in self.state_dict().items():
+            if k == 'optimizer':
+                continue
             a = v.detach().cpu().numpy()
             out[k] = a.astype(np.int64) if k == 'global_step' else a.astype(np.float32)
         return out
@@ -167,6 +184,24 @@ class Replica:
 # berhu_fraction and valid_range only report them.  A new objective is one more record here.
 LossLaunches = collections.namedtuple('LossLaunches', 'width name tags attrs ws fwd bwd')
 MSDN_OBJECTIVES = ('silog', 'berhu', 'ssi')
+MSDN_OPTIMIZER_RULES = ('adam', 'momentum')
+
+
+def checkpoint_optimizer(state):
+    """The optimizer that wrote a checkpoint's state (a .pt state dict or the tensors of a TF bundle): 'momentum' when the state
+    says so, or when it holds slots '<var>/<Group>' and not one '<var>/<Group>_1' (a bundle carries no string; TensorFlow's
+    MomentumOptimizer(name=<Group>) keeps that one slot per variable, its AdamOptimizer two); otherwise 'adam'.  The slot must
+    be there for EVERY model variable the state holds: a bundle with some of Adam's first slots and none of its second (a
+    partial TensorFlow checkpoint, which an Adam replica restores with the absent slots at zero) is still Adam's."""
+    said = state.get('optimizer')
+    if isinstance(said, str):
+        return said if said == 'momentum' else 'adam'
+    slots = [k for k in state if any(k.endswith('/' + g) or k.endswith('/' + g + '_1') for g in MSDN_OPTIMIZERS)]
+    if not slots or any(k.endswith('_1') for k in slots):
+        return 'adam'
+    variables = [(n, g) for g, (_, scopes) in MSDN_OPTIMIZERS.items() for n in state
+                 if n.endswith(('/kernel', '/bias')) and any(n.startswith(sc + '/') for sc in scopes)]
+    return 'momentum' if variables and all(n + '/' + g in state for n, g in variables) else 'adam'
 
 
 def msdn_loss_launches(objective, berhu_fraction, grad_weight, masked):
@@ -193,10 +228,12 @@ def msdn_loss_launches(objective, berhu_fraction, grad_weight, masked):
 class MSDNReplica(Replica):
     """One data-parallel replica of the MSDN training graph (src/models.py:203-367) on one GPU."""
     objective = 'silog'       # the reference's loss; an instance built with 'berhu' or 'ssi' carries its own (see __init__)
+    optimizer = 'adam'        # the reference's optimizer; an instance built with 'momentum' carries its own, and its momentum
+    lr_scale = 1.0
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, global_step=0, beta2=1.0, reducer=None,
                  precision='fp32', keep_dense_grads=True, overlap=True, valid_range=None, grad_weight=0.0,
-                 objective='silog', berhu_fraction=0.2):
+                 objective='silog', berhu_fraction=0.2, optimizer='adam', momentum=0.9, lr_scale=1.0):
         """precision: arithmetic of the conv contractions — 'fp32' (exact, the parity default), 'bf16x3' (split
         operands on the bf16 matrix cores, ~1e-5) or 'bf16' (BASELINE config 5).  Tensors stay float32 in HBM; the
         Cin = 3 layers, the dense layers and everything element-wise always compute in fp32.
@@ -212,7 +249,26 @@ class MSDNReplica(Replica):
         threshold is berhu_fraction, in (0, 1], times the largest error of each sample; or 'ssi', the least-squares
         scale-and-shift-invariant loss of Ranftl et al. 2020 on linear depth (ops.ssi_loss_fwd / _bwd): per sample the squared
         error left after the best scale and shift of the output, the objective that matches evaluate's --align affine.
-        'silog': today's launches."""
+        'silog': today's launches.
+        optimizer (NON-REFERENCE): 'adam', the reference's AdamOptimizer(rate, 0.9, beta2), or 'momentum', the optimizer the
+        rates of MSDN_OPTIMIZERS were published for (Eigen et al. 2014): tf.train.MomentumOptimizer(rate, momentum) without
+        Nesterov (ops.momentum_apply).  Each group then keeps one slot, the accumulator, where Adam keeps m and v; with
+        keep_dense_grads=False the dense layers' filter gradient goes from the matrix cores straight into the update
+        (ops.dense_bwd_filter_momentum).  momentum in [0, 1).  lr_scale > 0 multiplies every rate under either optimizer.
+        'adam' and lr_scale 1.0: today's replica, bit for bit."""
+        if optimizer not in MSDN_OPTIMIZER_RULES:
+            raise ValueError(f"optimizer {optimizer!r}: {' or '.join(map(repr, MSDN_OPTIMIZER_RULES))}")
+        momentum, lr_scale = float(momentum), float(lr_scale)
+        if not 0 <= momentum < 1:
+            raise ValueError(f'momentum {momentum!r}: a number in [0, 1)')
+        if not (math.isfinite(lr_scale) and lr_scale > 0):
+            raise ValueError(f'lr_scale {lr_scale!r}: a finite number > 0')
+        if optimizer == 'momentum' and beta2 != 1.0:
+            raise ValueError(f"optimizer 'momentum' with beta2 {beta2!r}: beta2 belongs to 'adam'")
+        if optimizer == 'momentum':
+            self.optimizer, self.momentum = optimizer, momentum
+        if lr_scale != 1.0:
+            self.lr_scale = lr_scale
         if objective not in MSDN_OBJECTIVES:
             raise ValueError(f"objective {objective!r}: {', '.join(map(repr, MSDN_OBJECTIVES[:-1]))} or {MSDN_OBJECTIVES[-1]!r}")
         berhu_fraction = float(berhu_fraction)
@@ -311,7 +367,8 @@ class MSDNReplica(Replica):
             gshapes = collections.OrderedDict((n, s) for n, s in shapes.items()
                                               if any(n.startswith(sc + '/') for sc in scopes))
             world = reducer.world_size if (reducer is not None and gname == 'CoarseDense') else 1
-            self.groups[gname] = ParamGroup(gname, lr, gshapes, dev, beta2=beta2, multiple=world)
+            self.groups[gname] = ParamGroup(gname, lr if lr_scale == 1.0 else lr * lr_scale, gshapes, dev, beta2=beta2,
+                                            multiple=world, optimizer=optimizer, momentum=momentum)
             for n in gshapes:
                 self.group_of[n] = gname
         if params is None:
@@ -699,23 +756,36 @@ class MSDNReplica(Replica):
         Collective under a data-parallel reducer (gather_state)."""
         self.gather_state()
         sd = collections.OrderedDict()
+        adam = self.optimizer == 'adam'
         for n in self.shapes:
             sd[n] = self.var(n)
             sd[n + '/' + self.group_of[n]] = self.slot(n, 'm')
-            sd[n + '/' + self.group_of[n] + '_1'] = self.slot(n, 'v')
-        for gname, g in self.groups.items():
+            if adam:
+                sd[n + '/' + self.group_of[n] + '_1'] = self.slot(n, 'v')
+        for gname, g in self.groups.items() if adam else ():
             sd[gname + '/beta1_power'] = torch.tensor(float(g.beta1_power))
             sd[gname + '/beta2_power'] = torch.tensor(float(g.beta2_power))
         sd['global_step'] = torch.tensor(self.global_step, dtype=torch.int64)
+        if not adam:      # '<var>/<Group>' is then the accumulator (TensorFlow's slot name under MomentumOptimizer(name=<Group>))
+            sd['optimizer'] = self.optimizer
         return sd
 
+    def _check_checkpoint_optimizer(self, state):
+        wrote = checkpoint_optimizer(state)
+        if wrote != self.optimizer:
+            raise ValueError(f"the checkpoint was written under the {wrote!r} optimizer and this replica runs {self.optimizer!r} "
+                             f"('adam' keeps two slots per variable, 'momentum' one): restore it with --optimizer {wrote}")
+
     def load_state_dict(self, sd):
+        self._check_checkpoint_optimizer(sd)
         self.gather_state()
+        adam = self.optimizer == 'adam'
         for n in self.shapes:
             self.var(n).copy_(sd[n])
             self.slot(n, 'm').copy_(sd[n + '/' + self.group_of[n]])
-            self.slot(n, 'v').copy_(sd[n + '/' + self.group_of[n] + '_1'])
-        for gname, g in self.groups.items():
+            if adam:
+                self.slot(n, 'v').copy_(sd[n + '/' + self.group_of[n] + '_1'])
+        for gname, g in self.groups.items() if adam else ():
             g.beta1_power = np.float32(sd[gname + '/beta1_power'].item())
             g.beta2_power = np.float32(sd[gname + '/beta2_power'].item())
         self.global_step = int(sd['global_step'].item())
@@ -736,9 +806,10 @@ class MSDNReplica(Replica):
         missing = [n for n in self.shapes if n not in tensors]
         if missing:
             raise KeyError(f'TensorFlow checkpoint lacks {len(missing)} model variables, e.g. {missing[:3]}')
+        self._check_checkpoint_optimizer(tensors)
         self.load_params(tensors)
         for n in self.shapes:
-            for which, suffix in (('m', ''), ('v', '_1')):
+            for which, suffix in (('m', ''), ('v', '_1')) if self.optimizer == 'adam' else (('m', ''),):
                 key = n + '/' + self.group_of[n] + suffix
                 if key in tensors:
                     self.slot(n, which).copy_(torch.from_numpy(np.ascontiguousarray(tensors[key], np.float32)))
@@ -781,7 +852,8 @@ class MSDNReplica(Replica):
         self.gather_state()
         for g in self.groups.values():
             for buf in (g.var, g.m, g.v):
-                dist.broadcast(buf, src)
+                if buf is not None:        # 'momentum' keeps no v
+                    dist.broadcast(buf, src)
         powers = self._broadcast_step(dist, src, [float(x) for g in self.groups.values()
                                                   for x in (g.beta1_power, g.beta2_power)])
         for i, g in enumerate(self.groups.values()):
@@ -1002,6 +1074,9 @@ class MSDNReplica(Replica):
     def _fused_dense_adam(self):
         return not self.keep_dense_grads and self.groups['CoarseDense'].frozen()
 
+    def _fused_dense_momentum(self):
+        return not self.keep_dense_grads and self.optimizer == 'momentum'
+
     def _bwd_data(self, name, dz, dx, relu_mask=None):
         d, w = self._desc(name, 'bwd_d'), self._w(name, 'bwd_d')
         if name in self.d_wino:
@@ -1032,6 +1107,10 @@ class MSDNReplica(Replica):
             kb = [g.view(buf, name + '/bias') for buf in (g.var, g.m, g.v)]
             ops.dense_bwd_filter_adam_tf1(x, dz, *kw, *kb, g.lr, g.beta1, g.beta2, float(g.beta1_power),
                                           float(g.beta2_power), 1.0, precision='bf16' if self.bf16s else 'fp32')
+        elif self._fused_dense_momentum():
+            g = self.groups[self.group_of[name + '/kernel']]
+            slots = [g.view(buf, name + which) for which in ('/kernel', '/bias') for buf in (g.var, g.m)]
+            ops.dense_bwd_filter_momentum(x, dz, *slots, g.lr, g.momentum, 1.0)
         else:
             ops.dense_bwd_filter(x, dz, self._g(name + '/kernel'), self._g(name + '/bias'))
 
@@ -1043,7 +1122,11 @@ class MSDNReplica(Replica):
                        dout16=self.dz1_16 if bf16_x else None)   # (dz1 a second time as bf16 rows of 4072: dense_1's bwd-data)
         self.settle()              # a reduce-scatter of the previous step may still be reading the dense gradient buffer
         n = 'coarse/dense/dense_1'
-        self._bwd_filter(n, self.drop, self.dz1)
+        # the fused momentum launch moves the layer's kernel: it runs after the bwd-data that must still read the old one
+        # (the reference's frozen Adam never moves it, and every other path applies after the backward)
+        late = self._fused_dense_momentum()
+        if not late:
+            self._bwd_filter(n, self.drop, self.dz1)
         if after_dense1 is not None:
             after_dense1()         # dense_1's gradient (67 MB) is complete: first piece of the dense bucket
         # dropout-grad (x2 on kept units) and dense_0's ReluGrad in one mask: drop > 0  <=>  kept and relu active
@@ -1054,11 +1137,14 @@ class MSDNReplica(Replica):
                                   out2=ops.second_output(self.dz0_16))     # dz0 as bf16 too: dense_0's bwd-data
         else:
             ops.dense_bwd_data(self.dz1, self._v(n + '/kernel'), self.dz0, mask=self.drop, scale=2.0 if self.dropout_on else 1.0)
+        if late:
+            self._bwd_filter(n, self.drop, self.dz1)
         n = 'coarse/dense/dense_0'
         if bf16_x and not self._c4_32_fresh:    # the filter gradient takes c4 on the dense layers' fp32 side
             ops.cast_bf16(self.c4, self.c4_32)      # (B > 64: the forward already made this copy; phase 1: conv2d_4's reduction did)
         flat = (self.c4_32 if self.bf16s else self.c4).view(B, -1)
-        self._bwd_filter(n, flat, self.dz0)
+        if not late:
+            self._bwd_filter(n, flat, self.dz0)
         if bf16_x:      # dc4 leaves as bf16, masked by the bf16 c4: no fp32 detour
             ops.dense_bwd_data_ex(self.dz0_16, self.wcopy[n], self.dc4.view(B, -1), mask=self.c4.view(B, -1), scale=1.0,
                                   precision='bf16', storage=ops.STORE_W | ops.STORE_X | ops.STORE_Y)
@@ -1068,6 +1154,8 @@ class MSDNReplica(Replica):
             ops.cast_bf16(self.dc4_32, self.dc4)
         else:
             ops.dense_bwd_data(self.dz0, self._v(n + '/kernel'), self.dc4.view(B, -1), mask=flat, scale=1.0)
+        if late:
+            self._bwd_filter(n, flat, self.dz0)
         if after_dense is not None:
             after_dense()          # dense gradients are complete: their all-reduce can overlap the conv backward
         n = 'coarse/conv/conv2d_4'
@@ -1165,11 +1253,11 @@ class MSDNReplica(Replica):
         if phase == 1:
             gc, gd = self.groups['CoarseConv'], self.groups['CoarseDense']
             if red is None:
-                fused = self._fused_dense_adam()       # decided before the backward: it is what the dense layers ran
+                fused = self._fused_dense_adam() or self._fused_dense_momentum()      # decided before the backward: it is what the dense layers ran
                 self.backward_coarse()
                 gc.apply(scale)
                 if fused:
-                    gd.advance()                       # ApplyAdam of coarse/dense/* already happened inside the backward
+                    gd.advance()                       # the update of coarse/dense/* already happened inside the backward
                 else:
                     gd.apply(scale)
                 self._weights_moved(gc, gd)
@@ -2123,6 +2211,9 @@ class _MultiScaleDeepNetwork:
     grad_weight = 0.0    # NON-REFERENCE, --loss-gradient: weight of the gradient-matching term in both losses (see MSDNReplica)
     objective = 'silog'  # NON-REFERENCE, --loss berhu / ssi: reverse Huber, or scale-and-shift-invariant (see MSDNReplica)
     berhu_fraction = 0.2  # --berhu-fraction: its threshold, as a fraction of each sample's largest error
+    optimizer = 'adam'   # NON-REFERENCE, --optimizer momentum: SGD with momentum, the rule the rates were published for (see MSDNReplica)
+    momentum = 0.9       # --momentum: its momentum
+    lr_scale = 1.0       # NON-REFERENCE, --lr-scale: a factor on every rate of MSDN_OPTIMIZERS
 
     def __call__(self, images, depths, train=True):
         assert images.pipeline is depths.pipeline, 'inputs and targets must come from the same data.inputs() call'
@@ -2131,7 +2222,8 @@ class _MultiScaleDeepNetwork:
                               seed=self.seed, beta2=self.beta2, reducer=self.reducer, precision=self.precision,
                               keep_dense_grads=False,        # one GPU + the reference's optimizer: dW feeds ApplyAdam directly
                               valid_range=self.valid_range, grad_weight=self.grad_weight, objective=self.objective,
-                              berhu_fraction=self.berhu_fraction)
+                              berhu_fraction=self.berhu_fraction, optimizer=self.optimizer, momentum=self.momentum,
+                              lr_scale=self.lr_scale)
         replica.uses_dropout = bool(train)                   # train=False: tf.layers.dropout(training=False), src/models.py:230
         if self.reducer is not None:                         # replicas start from rank 0's weights
             for g in replica.groups.values():

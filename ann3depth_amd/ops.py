@@ -864,6 +864,50 @@ def sgd_apply_floor(var, g, lr, floor=0.0):
     check(_lib.load().a3dp_sgd_apply_floor(var.numel(), _ptr(var), _ptr(g), lr, floor, _stream()), 'a3dp_sgd_apply_floor')
 
 
+def _check_momentum(who, f32, names):
+    """TypeError unless every tensor is float32; ValueError unless all are contiguous and on one device."""
+    if any(t.dtype != torch.float32 for t in f32):
+        raise TypeError(f'{who}: {names} float32')
+    if not all(t.is_contiguous() for t in f32):
+        raise ValueError(f'{who}: contiguous tensors only')
+    if any(t.device != f32[0].device for t in f32):
+        raise ValueError(f'{who}: all tensors on one device')
+
+
+def momentum_apply(var, accum, g, lr, momentum, grad_scale=1.0):
+    """NON-REFERENCE (a3do_momentum_apply): TF 1.3's MomentumOptimizer step without Nesterov, every operation rounded to float32
+    on its own: g' = g * grad_scale (skipped at 1), accum = accum * momentum + g', var = var - lr * accum.  var, accum, g:
+    float32 tensors of one size, starting on 16-byte boundaries."""
+    if var.numel() == 0 or accum.numel() != var.numel() or g.numel() != var.numel():
+        raise ValueError(f'momentum_apply: var {tuple(var.shape)}, accum {tuple(accum.shape)} and g {tuple(g.shape)} must hold '
+                         f'the same number of values')
+    _check_momentum('momentum_apply', (var, accum, g), 'var, accum, g')
+    check(_lib.load().a3do_momentum_apply(var.numel(), _ptr(var), _ptr(accum), _ptr(g), lr, momentum, grad_scale, _stream()),
+          'a3do_momentum_apply')
+
+
+def dense_bwd_filter_momentum(x, dz, var_w, accum_w, var_b, accum_b, lr, momentum, grad_scale=1.0):
+    """NON-REFERENCE (a3do_dense_bwd_filter_momentum): dense_bwd_filter + momentum_apply of one dense layer's kernel and bias in
+    one launch, bit for bit the two calls; the gradient is not materialised.  x [m, k], dz [m, n] with m <= 64, var_w and
+    accum_w [k, n]; var_b and accum_b [n], or both None."""
+    if x.dim() != 2 or dz.dim() != 2 or x.shape[0] != dz.shape[0]:
+        raise ValueError(f'dense_bwd_filter_momentum: x {tuple(x.shape)} and dz {tuple(dz.shape)} are [m, k] and [m, n]')
+    m, k = x.shape
+    n = dz.shape[1]
+    if tuple(var_w.shape) != (k, n) or tuple(accum_w.shape) != (k, n):
+        raise ValueError(f'dense_bwd_filter_momentum: var_w {tuple(var_w.shape)} and accum_w {tuple(accum_w.shape)} must be '
+                         f'[{k}, {n}]')
+    if (var_b is None) != (accum_b is None):
+        raise ValueError('dense_bwd_filter_momentum: var_b and accum_b come as a pair or not at all')
+    bias = () if var_b is None else (var_b, accum_b)
+    if any(t.numel() != n for t in bias):
+        raise ValueError(f'dense_bwd_filter_momentum: var_b and accum_b must hold {n} values')
+    _check_momentum('dense_bwd_filter_momentum', (x, dz, var_w, accum_w) + bias, 'x, dz, var_w, accum_w, var_b, accum_b')
+    check(_lib.load().a3do_dense_bwd_filter_momentum(m, k, n, _ptr(x), _ptr(dz), _ptr(var_w), _ptr(accum_w), _ptr(var_b),
+                                                     _ptr(accum_b), lr, momentum, grad_scale, _stream()),
+          'a3do_dense_bwd_filter_momentum')
+
+
 def superpixel_mean(x, sp, out=None):
     """[n,h,w,c] -> [n,(h/sp)*(w/sp),c] block means (src/models.py:110,132)."""
     n, h, w, c = x.shape
