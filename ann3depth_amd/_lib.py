@@ -229,6 +229,20 @@ OPTIM_SIGNATURES = {
     'a3do_dense_bwd_filter_momentum': (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_float, c_float, c_float, _P]),
 }
 
+# name -> (restype, argtypes); every symbol include/a3d_clip.h declares (NON-REFERENCE extension, prefix a3dn_)
+CLIP_SIGNATURES = {
+    'a3dn_grad_norm_ws_bytes': (c_size_t, [c_size_t]),
+    'a3dn_grad_norm_scale': (c_int, [c_size_t, _P, c_float, c_float, _P, _P, c_size_t, _P]),
+    'a3dn_momentum_apply_ctl': (c_int, [c_size_t, _P, _P, _P, c_float, c_float, _P, _P]),
+    'a3dn_adam_apply_tf1_ctl': (c_int, [c_size_t, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, c_float, _P, _P,
+                                        _P]),
+    'a3dn_sgd_apply_ctl': (c_int, [c_size_t, _P, _P, c_float, _P, _P]),
+    'a3dn_sgd_apply_floor_ctl': (c_int, [c_size_t, _P, _P, c_float, c_float, _P, _P]),
+}
+CLIP_CTL_BYTES = 32                          # A3DN_CTL_BYTES: sumsq f64, norm f32, scale f32, skip u32, skipped u32, 8 reserved
+CLIP_BLOCK_ELEMS, CLIP_MAX_BLOCKS = 4096, 1024      # A3DN_BLOCK_ELEMS, A3DN_MAX_BLOCKS
+
+
 class WinoBwdPool(ctypes.Structure):
     """a3dwb_pool (include/a3d_wino_bwd.h): the 2x2 max pool below a layer, as the fused forward recorded it."""
     _fields_ = [('argmax', c_void_p), ('y', c_void_p), ('ldy', c_int), ('h2', c_int), ('w2', c_int)]
@@ -288,6 +302,7 @@ SURFACES = (
     Surface('a3di_', 'a3d_ssi.h', SSI_SIGNATURES),
     Surface('a3dl_', 'a3d_wino1d.h', WINO1D_SIGNATURES),
     Surface('a3do_', 'a3d_optim.h', OPTIM_SIGNATURES),
+    Surface('a3dn_', 'a3d_clip.h', CLIP_SIGNATURES),
 )
 
 _lib = None

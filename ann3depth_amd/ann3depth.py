@@ -10,7 +10,7 @@ replaced by synchronous RCCL data parallelism: launch one process per GPU with
 accepted and ignored.
 
 Flags that are not the reference's: --beta2, --precision, --augment, --min-depth / --max-depth, --loss-gradient,
---loss {silog,berhu,ssi}, --berhu-fraction, --optimizer {adam,momentum}, --momentum, --lr-scale,
+--loss {silog,berhu,ssi}, --berhu-fraction, --optimizer {adam,momentum}, --momentum, --lr-scale, --clip-norm,
 --train-pairwise, --pairwise-texture, --superpixel {40,20,10}, --unary {patch,fcsp} (dcnf: the unary part over 48 patches per image, the
 reference's, or once over the whole image with superpixel pooling before the dense head), --seed, --tf-checkpoints,
 --trace-every, --profiler.
@@ -142,6 +142,17 @@ def main(argv=None):
     if args.lr_scale is not None and not 0 < args.lr_scale < float('inf'):
         logger.error(f'--lr-scale {args.lr_scale}: a finite number > 0.')
         return 2
+    if args.clip_norm is not None:
+        if not hasattr(getattr(models, args.model, None), 'clip_norm'):
+            logger.error(f'--clip-norm bounds the gradient norm of every optimizer group of --model msdn or dcnf: '
+                         f'{args.model or "(no model)"} has no optimizer group.')
+            return 2
+        try:
+            models.check_clip_norm(args.clip_norm)
+        except ValueError:
+            logger.error(f'--clip-norm {args.clip_norm}: a number > 0 (inf: measure the norms and skip non-finite steps, never '
+                         f'clip).')
+            return 2
     if args.min_depth is not None or args.max_depth is not None:
         lo = 0. if args.min_depth is None else args.min_depth
         hi = float('inf') if args.max_depth is None else args.max_depth
@@ -214,6 +225,8 @@ def setup_model(args, rank=0, world=1):
         model.optimizer = args.optimizer
         model.momentum = 0.9 if args.momentum is None else float(args.momentum)
         model.lr_scale = 1.0 if args.lr_scale is None else float(args.lr_scale)
+    if hasattr(model, 'clip_norm'):                                      # main() has refused the models that have none
+        model.clip_norm = args.clip_norm
     if hasattr(model, 'train_pairwise'):                                 # main() has refused the models that have none
         model.train_pairwise = bool(args.train_pairwise)
     if hasattr(model, 'pairwise_texture'):
@@ -543,6 +556,13 @@ def parse_args(argv=None):
                         help='NON-REFERENCE, --optimizer momentum: its momentum. 0 <= M < 1, default 0.9.')
     parser.add_argument('--lr-scale', default=None, type=float, metavar='S',
                         help='NON-REFERENCE: multiply every per-group rate by S (msdn only, either optimizer). S > 0, default 1.')
+    parser.add_argument('--clip-norm', default=None, type=float, metavar='C',
+                        help='NON-REFERENCE: bound the gradient of every optimizer group (msdn: CoarseConv, CoarseDense, FineA, '
+                             'FineB; dcnf: unary, pairwise) by its own global norm C, as tf.clip_by_global_norm over one '
+                             'optimizer\'s gradients, and skip a group\'s step when its gradient is not finite. C > 0; inf measures '
+                             'and skips without clipping. The norms, scales and skipped steps go to the summaries. msdn: the dense '
+                             'layers\' filter gradient is written out for its norm instead of going straight into the update. '
+                             'Not stored in checkpoints: a run resumes under the flag it is given.')
     parser.add_argument('--train-pairwise', action='store_true',
                         help='NON-REFERENCE: learn the pairwise dense layer of the CRF (dcnf only). The reference leaves it at '
                              'its initial draw (TF 1.3 has no gradient for scatter_nd_update); with this flag the loss is also '

@@ -19,6 +19,7 @@
 #include "a3d_pairwise.h"
 #include "a3d_texture.h"
 #include "crf_common.h"
+#include "optim_rules.h"
 
 namespace a3d {
 
@@ -619,19 +620,16 @@ __global__ __launch_bounds__(64) void crf_observed_kernel(const float* __restric
 }
 
 // tf.train.GradientDescentOptimizer(lr) (src/models.py:198): var -= lr * g
+// the two descents' walks: optim_rules.h, shared with the launches that scale lr by a gradient-norm control block (clip.hip)
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ var, const float* __restrict__ g, size_t count,
                                                   float lr) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256)
-    var[i] = __fsub_rn(var[i], __fmul_rn(lr, g[i]));
+  sgd_body(var, g, count, lr);
 }
 
 // projected gradient descent: sgd_kernel's step, then no lower than `floor`.  The comparison keeps a NaN a NaN.
 __global__ __launch_bounds__(256) void sgd_floor_kernel(float* __restrict__ var, const float* __restrict__ g, size_t count,
                                                         float lr, float floor) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) {
-    const float v = __fsub_rn(var[i], __fmul_rn(lr, g[i]));
-    var[i] = v < floor ? floor : v;
-  }
+  sgd_floor_body(var, g, count, lr, floor);
 }
 
 }  // namespace a3d
@@ -769,7 +767,7 @@ int a3dv_crf_loss_observed(int n, int nsp, const float* z, const float* y, const
 int a3d_sgd_apply(size_t count, float* var, const float* g, float lr, void* stream) {
   A3D_CHECK_ARG(count > 0 && var && g, "sgd: bad arguments");
   clear_stale_error();
-  hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)std::min<size_t>((count + 255) / 256, 4096)), dim3(256), 0,
+  hipLaunchKernelGGL(sgd_kernel, dim3(rule_grid_scalar(count)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), var, g, count, lr);
   return check_launch("sgd");
 }
@@ -777,7 +775,7 @@ int a3d_sgd_apply(size_t count, float* var, const float* g, float lr, void* stre
 int a3dp_sgd_apply_floor(size_t count, float* var, const float* g, float lr, float floor, void* stream) {
   A3D_CHECK_ARG(count > 0 && var && g, "sgd_floor: bad arguments");
   clear_stale_error();
-  hipLaunchKernelGGL(sgd_floor_kernel, dim3((unsigned)std::min<size_t>((count + 255) / 256, 4096)), dim3(256), 0,
+  hipLaunchKernelGGL(sgd_floor_kernel, dim3(rule_grid_scalar(count)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), var, g, count, lr, floor);
   return check_launch("sgd_floor");
 }

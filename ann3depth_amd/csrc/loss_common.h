@@ -156,15 +156,19 @@ __device__ __forceinline__ void publish32(float* __restrict__ word, float v) {
 }
 
 // steps 2 to 4 of publish_and_arrive, for a block whose lane 0 has just published its words itself; called by every thread
-__device__ __forceinline__ bool arrive(float* __restrict__ ws, int nb) {
+// (arrive_of: the same for a grid of `total` blocks that is not nb * kSilogParts — clip.hip's)
+__device__ __forceinline__ bool arrive_of(unsigned* __restrict__ ticket, unsigned total) {
   __shared__ unsigned last_arrived;
   if (threadIdx.x == 0) {
-    const unsigned total = (unsigned)(nb * kSilogParts);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    last_arrived = atomicInc(reinterpret_cast<unsigned*>(ws), total - 1u) == total - 1u;
+    last_arrived = atomicInc(ticket, total - 1u) == total - 1u;
   }
   __syncthreads();
   return last_arrived != 0u;
+}
+
+__device__ __forceinline__ bool arrive(float* __restrict__ ws, int nb) {
+  return arrive_of(reinterpret_cast<unsigned*>(ws), (unsigned)(nb * kSilogParts));
 }
 
 // the float64 word at `word` (even) of the K-word partials of sample i's parts, added in ascending part order from 0.0

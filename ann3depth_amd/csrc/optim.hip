@@ -7,40 +7,19 @@
 // so that they do not push the operands a GEMM of the other stream re-reads out of the L2.
 #include "a3d_internal.h"
 #include "igemm.h"
+#include "optim_rules.h"
 #include "../../include/a3d_optim.h"
 
 using namespace a3d;
 
 namespace a3d {
 
-__device__ __forceinline__ void momentum_one(float& var, float& accum, float g, float lr, float mu) {
-  accum = __fadd_rn(__fmul_rn(accum, mu), g);
-  var = __fsub_rn(var, __fmul_rn(lr, accum));
-}
-
-// adam_kernel's shape (pointwise.hip): 16-byte vectors grid-strided, the count % 4 tail by block 0
+// momentum_one and the walk of a flat group (momentum_body): optim_rules.h, shared with the launch that takes its scale from a
+// gradient-norm control block (clip.hip)
 __global__ __launch_bounds__(256) void momentum_kernel(float* __restrict__ var, float* __restrict__ accum,
                                                        const float* __restrict__ g, size_t count, float lr, float mu,
                                                        float gscale) {
-  const size_t nvec = count / 4;
-  const bool use_scale = gscale != 1.f;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
-    f32x4 w4 = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(var) + i);
-    f32x4 a4 = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(accum) + i);
-    const f32x4 g4 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float wj = w4[j], aj = a4[j];
-      momentum_one(wj, aj, use_scale ? __fmul_rn(g4[j], gscale) : g4[j], lr, mu);
-      w4[j] = wj; a4[j] = aj;
-    }
-    __builtin_nontemporal_store(w4, reinterpret_cast<f32x4*>(var) + i);
-    __builtin_nontemporal_store(a4, reinterpret_cast<f32x4*>(accum) + i);
-  }
-  if (blockIdx.x == 0) {
-    const size_t i = nvec * 4 + threadIdx.x;
-    if (i < count) momentum_one(var[i], accum[i], use_scale ? __fmul_rn(g[i], gscale) : g[i], lr, mu);
-  }
+  momentum_body(var, accum, g, count, lr, mu, gscale);
 }
 
 // dense_dw_kernel<true, 2> (dense.hip) with the momentum rule in its epilogue: a wave owns 32 weight rows x 64 columns, lane li
@@ -170,7 +149,7 @@ int a3do_momentum_apply(size_t count, float* var, float* accum, const float* g, 
   A3D_CHECK_ARG(((reinterpret_cast<uintptr_t>(var) | reinterpret_cast<uintptr_t>(accum) | reinterpret_cast<uintptr_t>(g)) & 15) == 0,
                 "momentum_apply: buffers must be 16-byte aligned");
   clear_stale_error();
-  hipLaunchKernelGGL(momentum_kernel, dim3(grid_for(count / 4 + 1, 256, 4096)), dim3(256), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(momentum_kernel, dim3(rule_grid_vec(count)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      var, accum, g, count, lr, momentum, grad_scale);
   return check_launch("momentum_apply");
 }

@@ -8,6 +8,7 @@
 
 #include "a3d_internal.h"
 #include "loss_common.h"
+#include "optim_rules.h"
 #include "../../include/a3d_valid.h"
 
 using namespace a3d;
@@ -156,100 +157,20 @@ int a3dx_silog_masked_loss_bwd_ex(int b, int npix, const float* out, const float
 
 namespace a3d {
 // ------------------------------------------------------------------ ApplyAdam (TF 1.3 formula)
-__device__ __forceinline__ void adam_one(float& var, float& m, float& v, float g, float omb1, float omb2, float alpha,
-                                         float eps) {
-  m = __fadd_rn(m, __fmul_rn(__fsub_rn(g, m), omb1));
-  v = __fadd_rn(v, __fmul_rn(__fsub_rn(__fmul_rn(g, g), v), omb2));
-  // v_sqrt_f32 is 1-ulp, not correctly rounded, and hipcc emits it bare; the f64 square root rounded to f32 is
-  // correctly rounded (53 >= 2*24+2 bits), which is what the numpy/Eigen reference computes.
-  const float sq = (float)sqrt((double)v);
-  var = __fsub_rn(var, __fdiv_rn(__fmul_rn(m, alpha), __fadd_rn(sq, eps)));
-}
-
-// what a3d_adam_apply_tf1_flag reports: the update CHANGED this value into a non-finite one (a NaN that stays a NaN, an
-// infinity that stays that infinity: nothing the other ranks' copies lack)
-__device__ __forceinline__ bool turned_non_finite(float before, float after) {
-  return !isfinite(after) && !(after == before || (isnan(after) && isnan(before)));
-}
-
+// adam_one and the two walks (adam_body; adam_frozen_body, the reference's alpha == 0, beta2 == 1 case): optim_rules.h, shared with
+// the launches that take their scale from a gradient-norm control block (clip.hip)
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ var, float* __restrict__ m,
                                                    float* __restrict__ v, const float* __restrict__ g, size_t count,
                                                    float omb1, float omb2, float alpha, float eps, float gscale,
                                                    unsigned int* __restrict__ poisoned) {
-  const size_t nvec = count / 4;
-  const bool use_scale = gscale != 1.f;
-  bool bad = false;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
-    f32x4 w4 = reinterpret_cast<f32x4*>(var)[i], m4 = reinterpret_cast<f32x4*>(m)[i];
-    f32x4 v4 = reinterpret_cast<f32x4*>(v)[i], g4 = reinterpret_cast<const f32x4*>(g)[i];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float gj = use_scale ? __fmul_rn(g4[j], gscale) : g4[j];
-      float wj = w4[j], mj = m4[j], vj = v4[j];
-      adam_one(wj, mj, vj, gj, omb1, omb2, alpha, eps);
-      bad |= turned_non_finite(w4[j], wj) || turned_non_finite(v4[j], vj);
-      w4[j] = wj; m4[j] = mj; v4[j] = vj;
-    }
-    reinterpret_cast<f32x4*>(var)[i] = w4;
-    reinterpret_cast<f32x4*>(m)[i] = m4;
-    reinterpret_cast<f32x4*>(v)[i] = v4;
-  }
-  if (blockIdx.x == 0) {
-    const size_t i = nvec * 4 + threadIdx.x;
-    if (i < count) {
-      float gj = use_scale ? __fmul_rn(g[i], gscale) : g[i];
-      const float w0 = var[i], v0 = v[i];
-      adam_one(var[i], m[i], v[i], gj, omb1, omb2, alpha, eps);
-      bad |= turned_non_finite(w0, var[i]) || turned_non_finite(v0, v[i]);
-    }
-  }
-  if (poisoned && bad) atomicOr(poisoned, 1u);
+  adam_body(var, m, v, g, count, omb1, omb2, alpha, eps, gscale, poisoned);
 }
 
-// ApplyAdam specialised for alpha == 0 and 1-beta2 == 0 — what the reference's AdamOptimizer(rate, 0.9, 1) always is
-// (src/models.py:309).  Then v += (g*g - v)*0 and var -= (m*0)/(sqrt(v)+eps) leave v and var bit-identical unless a
-// non-finite value poisons them (inf*0 = NaN), so only m needs the full read-modify-write: 3 HBM streams instead of
-// 7.  Poisoned elements get exactly the NaNs the general formula would produce.  (Assumes v holds no +-inf from a
-// foreign checkpoint; v is only ever written by these two kernels, which never produce one.)
 __global__ __launch_bounds__(256) void adam_frozen_kernel(float* __restrict__ var, float* __restrict__ m,
                                                           float* __restrict__ v, const float* __restrict__ g,
                                                           size_t count, float omb1, float gscale,
                                                           unsigned int* __restrict__ poisoned) {
-  const size_t nvec = count / 4;
-  const bool use_scale = gscale != 1.f;
-  const float qnan = __builtin_nanf("");
-  bool bad = false;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
-    f32x4 m4 = reinterpret_cast<f32x4*>(m)[i], g4 = reinterpret_cast<const f32x4*>(g)[i];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float gj = use_scale ? __fmul_rn(g4[j], gscale) : g4[j];
-      m4[j] = __fadd_rn(m4[j], __fmul_rn(__fsub_rn(gj, m4[j]), omb1));
-      const bool g_poison = !isfinite(__fmul_rn(gj, gj));
-      if (g_poison || !isfinite(m4[j])) {             // rare; `bad` only when it changes something (turned_non_finite)
-        const size_t e = 4 * i + j;
-        bad |= !isnan(var[e]) || (g_poison && !isnan(v[e]));
-        if (g_poison) v[e] = qnan;
-        var[e] = qnan;
-      }
-    }
-    reinterpret_cast<f32x4*>(m)[i] = m4;
-  }
-  if (blockIdx.x == 0) {
-    const size_t i = nvec * 4 + threadIdx.x;
-    if (i < count) {
-      const float gj = use_scale ? __fmul_rn(g[i], gscale) : g[i];
-      const float mj = __fadd_rn(m[i], __fmul_rn(__fsub_rn(gj, m[i]), omb1));
-      m[i] = mj;
-      const bool g_poison = !isfinite(__fmul_rn(gj, gj));
-      if (g_poison || !isfinite(mj)) {
-        bad |= !isnan(var[i]) || (g_poison && !isnan(v[i]));
-        if (g_poison) v[i] = qnan;
-        var[i] = qnan;
-      }
-    }
-  }
-  if (poisoned && bad) atomicOr(poisoned, 1u);      // rare: a non-finite gradient reached this slice
+  adam_frozen_body(var, m, v, g, count, omb1, gscale, poisoned);
 }
 
 }  // namespace a3d
@@ -269,16 +190,16 @@ int a3d_adam_apply_tf1_flag(size_t count, float* var, float* m, float* v, const 
   A3D_CHECK_ARG(count > 0 && var && m && v && g, "adam: bad arguments");
   A3D_CHECK_ARG(((reinterpret_cast<uintptr_t>(var) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
                   reinterpret_cast<uintptr_t>(g)) & 15) == 0, "adam: buffers must be 16-byte aligned");
-  const float alpha = lr * sqrtf(1.f - beta2_power) / (1.f - beta1_power);
-  if (alpha == 0.f && 1.f - beta2 == 0.f) {
+  const AdamHost h = adam_host(lr, beta2, beta1_power, beta2_power);
+  if (h.frozen) {
     clear_stale_error();
-    hipLaunchKernelGGL(adam_frozen_kernel, dim3(grid_for(count / 4 + 1, 256, 4096)), dim3(256), 0,
+    hipLaunchKernelGGL(adam_frozen_kernel, dim3(rule_grid_vec(count)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), var, m, v, g, count, 1.f - beta1, grad_scale, poisoned);
     return check_launch("adam_frozen");
   }
   clear_stale_error();
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(count / 4 + 1, 256, 4096)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), var, m, v, g, count, 1.f - beta1, 1.f - beta2, alpha, eps,
+  hipLaunchKernelGGL(adam_kernel, dim3(rule_grid_vec(count)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), var, m, v, g, count, 1.f - beta1, 1.f - beta2, h.alpha, eps,
                      grad_scale, poisoned);
   return check_launch("adam");
 }

@@ -76,12 +76,18 @@ class ParamGroup:
     ALIGN = 64   # elements; keeps every tensor 256-byte aligned for 16-byte vector loads
     optimizer = 'adam'      # a group built with 'momentum' carries its own, and its momentum
 
+    clip_norm = None        # a group built with a clip norm carries its own, a control block and a workspace
+
     def __init__(self, name, lr, shapes, device, beta1=0.9, beta2=1.0, eps=1e-8, slots=True, multiple=1, optimizer='adam',
-                 momentum=0.9):
+                 momentum=0.9, clip_norm=None):
         """multiple: the flat length is padded (with zeros that stay zeros) to a multiple of multiple * ALIGN elements, so
         that `multiple` data-parallel ranks can cut any bucket of it into equal, 256-byte-aligned slices.
         optimizer 'momentum' (NON-REFERENCE): tf.train.MomentumOptimizer(lr, momentum) without Nesterov (ops.momentum_apply):
-        `m` is its accumulator, there is no `v`, and the beta powers go unused."""
+        `m` is its accumulator, there is no `v`, and the beta powers go unused.
+        clip_norm (NON-REFERENCE, include/a3d_clip.h): every apply* becomes two launches on the same stream, the norm of the
+        gradient it is about to apply (ops.grad_norm_scale into self.ctl) and the rule with its scale read from there
+        (ops.*_ctl): the gradient bounded by clip_norm, a step with a non-finite gradient skipped.  The beta powers advance
+        on a skipped step too: the host does not know.  None: today's launches."""
         self.name, self.lr, self.beta1, self.beta2, self.eps = name, lr, beta1, beta2, eps
         if optimizer == 'momentum':
             self.optimizer, self.momentum = optimizer, momentum
@@ -99,28 +105,37 @@ class ParamGroup:
         # beta powers are host scalars, updated after each apply like AdamOptimizer._finish
         self.beta1_power = np.float32(beta1)
         self.beta2_power = np.float32(beta2)
+        if clip_norm is not None:
+            self.clip_norm = check_clip_norm(clip_norm)
+            self.ctl = ops.clip_ctl(device)
+            self.ws = ops.grad_norm_ws(off, device)
 
     def view(self, buf, name):
         off, shp = self.offsets[name]
         return buf[off:off + int(np.prod(shp))].view(shp)
 
     def apply(self, grad_scale=1.0):
-        if self.optimizer == 'momentum':
-            ops.momentum_apply(self.var, self.m, self.grad, self.lr, self.momentum, grad_scale)
-            return
-        ops.adam_apply_tf1(self.var, self.m, self.v, self.grad, self.lr, self.beta1, self.beta2, self.eps,
-                           float(self.beta1_power), float(self.beta2_power), grad_scale)
-        self.beta1_power = self.beta1_power * np.float32(self.beta1)
-        self.beta2_power = self.beta2_power * np.float32(self.beta2)
+        self.apply_slice(0, self.count, grad_scale)
+        self.advance()
 
     def apply_slice(self, a, b, grad_scale=1.0, poisoned=None):
-        """ApplyAdam on elements [a, b) only (a data-parallel rank's slice of a reduce-scattered bucket); the caller
-        advances the beta powers once per step with advance()."""
-        if self.optimizer == 'momentum':       # no poison flag: nothing of this rule is sharded
-            ops.momentum_apply(self.var[a:b], self.m[a:b], self.grad[a:b], self.lr, self.momentum, grad_scale)
-            return
-        ops.adam_apply_tf1(self.var[a:b], self.m[a:b], self.v[a:b], self.grad[a:b], self.lr, self.beta1, self.beta2,
-                           self.eps, float(self.beta1_power), float(self.beta2_power), grad_scale, poisoned=poisoned)
+        """The rule on elements [a, b) only (a data-parallel rank's slice of a reduce-scattered bucket; apply(): all of them);
+        the caller advances the beta powers once per step with advance().  Under clip_norm the norm is that of the elements
+        applied: a clipped group is meant to be applied whole."""
+        whole = a == 0 and b == self.count
+        var, m, v, g = (t if whole or t is None else t[a:b] for t in (self.var, self.m, self.v, self.grad))
+        if self.clip_norm is not None:
+            ops.grad_norm_scale(g, grad_scale, self.clip_norm, self.ctl, self.ws)
+            if self.optimizer == 'momentum':
+                ops.momentum_apply_ctl(var, m, g, self.lr, self.momentum, self.ctl)
+            else:
+                ops.adam_apply_tf1_ctl(var, m, v, g, self.lr, self.beta1, self.beta2, self.eps, float(self.beta1_power),
+                                       float(self.beta2_power), self.ctl, poisoned=poisoned)
+        elif self.optimizer == 'momentum':       # no poison flag: nothing of this rule is sharded
+            ops.momentum_apply(var, m, g, self.lr, self.momentum, grad_scale)
+        else:
+            ops.adam_apply_tf1(var, m, v, g, self.lr, self.beta1, self.beta2, self.eps, float(self.beta1_power),
+                               float(self.beta2_power), grad_scale, poisoned=poisoned)
 
     def frozen(self):
         """True for the optimizer the reference builds, AdamOptimizer(rate, 0.9, beta2 = 1): alpha = 0, only m moves."""
@@ -134,9 +149,35 @@ class ParamGroup:
         self.beta1_power = self.beta1_power * np.float32(self.beta1)
         self.beta2_power = self.beta2_power * np.float32(self.beta2)
 
-    def apply_sgd(self, grad_scale=1.0):
-        """tf.train.GradientDescentOptimizer(lr): var -= lr * grad_scale * g."""
-        ops.sgd_apply(self.var, self.grad, self.lr * grad_scale)
+    def apply_sgd(self, grad_scale=1.0, floor=None):
+        """tf.train.GradientDescentOptimizer(lr): var -= lr * grad_scale * g; floor (NON-REFERENCE): then no element below it
+        (ops.sgd_apply_floor).  Under clip_norm the rate is fl32(lr * scale), scale from the norm launch."""
+        if self.clip_norm is not None:
+            ops.grad_norm_scale(self.grad, grad_scale, self.clip_norm, self.ctl, self.ws)
+            ops.sgd_apply_ctl(self.var, self.grad, self.lr, self.ctl, floor=floor)
+        elif floor is None:
+            ops.sgd_apply(self.var, self.grad, self.lr * grad_scale)
+        else:
+            ops.sgd_apply_floor(self.var, self.grad, self.lr * grad_scale, floor)
+
+    def clip_scalars(self, rec):
+        """This group's summary scalars of the last applied step into rec (one copy of the control block; the caller has
+        synchronised or does not mind waiting)."""
+        st = ops.clip_read(self.ctl)
+        rec[f'optimizers/GradNorm/{self.name}'] = float(st.norm)
+        rec[f'optimizers/ClipScale/{self.name}'] = float(st.scale)
+        rec[f'optimizers/SkippedSteps/{self.name}'] = st.skipped
+
+
+def check_clip_norm(clip_norm):
+    """None, or the bound on every optimizer group's gradient norm as a float: a number > 0, inf allowed (measure and skip, never
+    clip); ValueError for anything else, NaN included."""
+    if clip_norm is None:
+        return None
+    c = float(clip_norm)
+    if not c > 0:
+        raise ValueError(f'clip_norm {clip_norm!r}: a number > 0 (inf: measure the norms and skip non-finite steps, never clip)')
+    return c
 
 
 def check_valid_range(valid_range):
@@ -185,6 +226,7 @@ class Replica:
 LossLaunches = collections.namedtuple('LossLaunches', 'width name tags attrs ws fwd bwd')
 MSDN_OBJECTIVES = ('silog', 'berhu', 'ssi')
 MSDN_OPTIMIZER_RULES = ('adam', 'momentum')
+MSDN_PHASE_GROUPS = {1: ('CoarseConv', 'CoarseDense'), 2: ('FineA', 'FineB')}      # the optimizer groups a phase's step applies
 
 
 def checkpoint_optimizer(state):
@@ -230,10 +272,11 @@ class MSDNReplica(Replica):
     objective = 'silog'       # the reference's loss; an instance built with 'berhu' or 'ssi' carries its own (see __init__)
     optimizer = 'adam'        # the reference's optimizer; an instance built with 'momentum' carries its own, and its momentum
     lr_scale = 1.0
+    clip_norm = None
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, global_step=0, beta2=1.0, reducer=None,
                  precision='fp32', keep_dense_grads=True, overlap=True, valid_range=None, grad_weight=0.0,
-                 objective='silog', berhu_fraction=0.2, optimizer='adam', momentum=0.9, lr_scale=1.0):
+                 objective='silog', berhu_fraction=0.2, optimizer='adam', momentum=0.9, lr_scale=1.0, clip_norm=None):
         """precision: arithmetic of the conv contractions — 'fp32' (exact, the parity default), 'bf16x3' (split
         operands on the bf16 matrix cores, ~1e-5) or 'bf16' (BASELINE config 5).  Tensors stay float32 in HBM; the
         Cin = 3 layers, the dense layers and everything element-wise always compute in fp32.
@@ -255,7 +298,13 @@ class MSDNReplica(Replica):
         Nesterov (ops.momentum_apply).  Each group then keeps one slot, the accumulator, where Adam keeps m and v; with
         keep_dense_grads=False the dense layers' filter gradient goes from the matrix cores straight into the update
         (ops.dense_bwd_filter_momentum).  momentum in [0, 1).  lr_scale > 0 multiplies every rate under either optimizer.
-        'adam' and lr_scale 1.0: today's replica, bit for bit."""
+        'adam' and lr_scale 1.0: today's replica, bit for bit.
+        clip_norm (NON-REFERENCE, include/a3d_clip.h): a number > 0, inf allowed.  Every optimizer group's gradient is bounded
+        by its own global norm (the reduced gradient's under a reducer, at grad_scale 1 / world) and a step whose gradient is
+        not finite moves nothing of that group (ParamGroup).  The norm needs the whole gradient: keep_dense_grads is forced on
+        and no dense launch is fused with its update; under a reducer the dense bucket is all-reduced and applied on every rank,
+        as momentum's is, its norm taken in settle().  Adam's beta powers and global_step advance on a skipped step too.
+        inf on one GPU: the bits of the unfused step.  None (the default): no launch, buffer or bit differs."""
         if optimizer not in MSDN_OPTIMIZER_RULES:
             raise ValueError(f"optimizer {optimizer!r}: {' or '.join(map(repr, MSDN_OPTIMIZER_RULES))}")
         momentum, lr_scale = float(momentum), float(lr_scale)
@@ -269,6 +318,8 @@ class MSDNReplica(Replica):
             self.optimizer, self.momentum = optimizer, momentum
         if lr_scale != 1.0:
             self.lr_scale = lr_scale
+        if clip_norm is not None:
+            self.clip_norm = check_clip_norm(clip_norm)
         if objective not in MSDN_OBJECTIVES:
             raise ValueError(f"objective {objective!r}: {', '.join(map(repr, MSDN_OBJECTIVES[:-1]))} or {MSDN_OBJECTIVES[-1]!r}")
         berhu_fraction = float(berhu_fraction)
@@ -288,7 +339,7 @@ class MSDNReplica(Replica):
         # gradient of the two dense kernels (268 MB) goes straight from the matrix cores into ApplyAdam's m slot
         # (ops.dense_bwd_filter_adam_tf1) and is never written; grad('coarse/dense/...') is then stale.  A data-parallel
         # replica needs the gradient for its all-reduce and always keeps it.
-        self.keep_dense_grads = keep_dense_grads or reducer is not None or batchsize > 64
+        self.keep_dense_grads = keep_dense_grads or reducer is not None or batchsize > 64 or clip_norm is not None
         # 'bf16s' = BASELINE config 5 proper: bf16 arithmetic AND bf16 storage — the conv stacks' activations and their
         # gradients, and a bf16 copy of every kernel with at least 8 input channels, live in HBM as bf16; fp32 stay the
         # master weights, the Adam slots, all filter / bias gradients and split-K slabs, the resized input, the 3-channel
@@ -334,8 +385,10 @@ class MSDNReplica(Replica):
             want = os.environ.get('A3D_DP_DENSE', 'scatter')
             if want not in ('scatter', 'allreduce'):
                 raise ValueError(f'A3D_DP_DENSE={want!r}: scatter or allreduce')
-            self.dense_exchange = 'reduce_scatter' if (want == 'scatter' and reducer.inplace_ok(dev)) else 'all_reduce'
-            if want == 'scatter' and self.dense_exchange == 'all_reduce':
+            # (a clipped bucket is applied whole, from its own norm: nothing of it is sharded)
+            scatter = want == 'scatter' and clip_norm is None
+            self.dense_exchange = 'reduce_scatter' if (scatter and reducer.inplace_ok(dev)) else 'all_reduce'
+            if scatter and self.dense_exchange == 'all_reduce':
                 print('MSDNReplica: in-place reduce-scatter failed its self-check on this backend; the dense bucket is '
                       'all-reduced instead', flush=True)
         self._dense_pieces = None
@@ -368,7 +421,7 @@ class MSDNReplica(Replica):
                                               if any(n.startswith(sc + '/') for sc in scopes))
             world = reducer.world_size if (reducer is not None and gname == 'CoarseDense') else 1
             self.groups[gname] = ParamGroup(gname, lr if lr_scale == 1.0 else lr * lr_scale, gshapes, dev, beta2=beta2,
-                                            multiple=world, optimizer=optimizer, momentum=momentum)
+                                            multiple=world, optimizer=optimizer, momentum=momentum, clip_norm=clip_norm)
             for n in gshapes:
                 self.group_of[n] = gname
         if params is None:
@@ -839,6 +892,10 @@ class MSDNReplica(Replica):
         for name, quad in (('coarse', self.loss_out_c), ('fine', self.loss_out_f)):      # NON-REFERENCE: the objective's own words
             for word, tag in self._loss.tags:
                 rec[f'loss/{name}_{tag}'] = float(quad[word])
+        if self.clip_norm is not None:                   # NON-REFERENCE: the groups this phase applied
+            self.settle()
+            for gname in MSDN_PHASE_GROUPS.get(out['phase'], ()):
+                self.groups[gname].clip_scalars(rec)
         return rec
 
     def summary_images(self):
@@ -1788,13 +1845,20 @@ class DCNFReplica(Replica):
     of the [0, 1] RGB range) are choices, not derivations: few iterations move most of what will move, and 0.1 lets an edge
     of a tenth of the colour range outweigh a block's width.  RGB, not CIELAB, and no connectivity post-pass: the
     statistics do not need connected superpixels.  Needs unary='fcsp', no pairwise_texture, no valid_range; posterior()
-    is refused.  'grid' (the default): no launch, buffer, bit, message or refusal differs."""
+    is refused.  'grid' (the default): no launch, buffer, bit, message or refusal differs.
+
+    clip_norm (NON-REFERENCE, --clip-norm; include/a3d_clip.h): a number > 0, inf allowed.  The `unary` group's descent, and
+    under train_pairwise the `pairwise` group's floored one, each bounded by its own gradient's global norm (the reduced
+    gradient's under a reducer) through a control block of its own (ParamGroup.apply_sgd): the rate becomes fl32(lr * scale),
+    and a step whose gradient is not finite moves nothing of that group.  One place in step(): every unary form passes
+    through it.  None (the default): no launch, buffer or bit differs."""
     uses_dropout = False
+    clip_norm = None
 
     def __init__(self, batchsize, device='cuda', params=None, seed=3000, global_step=0, reducer=None,
                  precision='fp32', train_pairwise=False, pairwise_texture=False, valid_range=None, min_valid=0.5,
                  unary='patch', superpixel=DCNF_SP, segmentation='grid', slic_iters=DCNF_SLIC_ITERS,
-                 slic_compactness=DCNF_SLIC_COMPACTNESS):
+                 slic_compactness=DCNF_SLIC_COMPACTNESS, clip_norm=None):
         if unary not in ('patch', 'fcsp'):
             raise ValueError(f"unary {unary!r}: 'patch' or 'fcsp'")
         self.unary_form = unary
@@ -1831,7 +1895,10 @@ class DCNFReplica(Replica):
         self.right = torch.tensor(right, dtype=torch.int32, device=dev)
         self.band = ops.pair_band(left, right)
         pshapes = collections.OrderedDict([(DCNF_PAIR_PREFIX + 'kernel', (self.nsims, 1)), (DCNF_PAIR_PREFIX + 'bias', (1,))])
-        self.pair_group = ParamGroup('pairwise', 0.1, pshapes, dev, slots=False)
+        if clip_norm is not None:
+            self.clip_norm = check_clip_norm(clip_norm)
+        self.pair_group = ParamGroup('pairwise', 0.1, pshapes, dev, slots=False,
+                                     clip_norm=self.clip_norm if self.train_pairwise else None)
         if params is None or DCNF_PAIR_PREFIX + 'kernel' not in params:
             rng = np.random.default_rng(seed + 1)
             pw = {DCNF_PAIR_PREFIX + 'kernel': glorot_uniform(rng, (self.nsims, 1)),
@@ -1844,6 +1911,9 @@ class DCNFReplica(Replica):
                 torch.from_numpy(np.ascontiguousarray(pw[n], np.float32)))
         if self.train_pairwise or self.banded:
             ops.sgd_apply_floor(self.pair_group.var, self.pair_group.grad, 0.0, 0.0)      # beta >= 0 from the start
+        if self.clip_norm is not None:      # the unary stack builds its group itself: the control block is given here
+            g = self.unary.group
+            g.clip_norm, g.ctl, g.ws = self.clip_norm, ops.clip_ctl(dev), ops.grad_norm_ws(g.count, dev)
         self.groups = collections.OrderedDict([('unary', self.unary.group), ('pairwise', self.pair_group)])
         self.depths240 = torch.empty((batchsize, DCNF_IMG_H, DCNF_IMG_W, 1), device=dev)
         self.hist = torch.empty((batchsize, self.nsp, 256), device=dev)
@@ -2085,7 +2155,7 @@ class DCNFReplica(Replica):
             scale = 1.0 / red.world_size
         self.unary.group.apply_sgd(scale)                                                 # :198-200
         if self.train_pairwise:
-            ops.sgd_apply_floor(self.pair_group.var, self.pair_group.grad, self.pair_group.lr * scale, 0.0)
+            self.pair_group.apply_sgd(scale, floor=0.0)
         self.global_step += 1
         return {'mean_loss': self.loss}
 
@@ -2093,6 +2163,10 @@ class DCNFReplica(Replica):
         rec = {'loss/mean_loss': float(out['mean_loss'])}                                 # src/models.py:174
         if self.valid_range is not None:                 # NON-REFERENCE: share of the superpixels that were targets
             rec['loss/observed_fraction'] = float(self.nobs.sum()) / (self.B * self.nsp)
+        if self.clip_norm is not None:                   # NON-REFERENCE: the groups the step applies
+            self.unary.group.clip_scalars(rec)
+            if self.train_pairwise:
+                self.pair_group.clip_scalars(rec)
         return rec
 
     def summary_images(self):
@@ -2214,6 +2288,7 @@ class _MultiScaleDeepNetwork:
     optimizer = 'adam'   # NON-REFERENCE, --optimizer momentum: SGD with momentum, the rule the rates were published for (see MSDNReplica)
     momentum = 0.9       # --momentum: its momentum
     lr_scale = 1.0       # NON-REFERENCE, --lr-scale: a factor on every rate of MSDN_OPTIMIZERS
+    clip_norm = None     # NON-REFERENCE, --clip-norm: bound on every optimizer group's gradient norm (see MSDNReplica)
 
     def __call__(self, images, depths, train=True):
         assert images.pipeline is depths.pipeline, 'inputs and targets must come from the same data.inputs() call'
@@ -2223,7 +2298,7 @@ class _MultiScaleDeepNetwork:
                               keep_dense_grads=False,        # one GPU + the reference's optimizer: dW feeds ApplyAdam directly
                               valid_range=self.valid_range, grad_weight=self.grad_weight, objective=self.objective,
                               berhu_fraction=self.berhu_fraction, optimizer=self.optimizer, momentum=self.momentum,
-                              lr_scale=self.lr_scale)
+                              lr_scale=self.lr_scale, clip_norm=self.clip_norm)
         replica.uses_dropout = bool(train)                   # train=False: tf.layers.dropout(training=False), src/models.py:230
         if self.reducer is not None:                         # replicas start from rank 0's weights
             for g in replica.groups.values():
@@ -2249,6 +2324,7 @@ class _DistributedConvolutionalNeuralFields:
     superpixel = DCNF_SP  # NON-REFERENCE, --superpixel 20 / 10: finer grids on the banded CRF (see DCNFReplica)
     segmentation = 'grid'  # NON-REFERENCE, --segmentation slic: SLIC superpixels in place of square blocks (see DCNFReplica)
     slic_iters, slic_compactness = DCNF_SLIC_ITERS, DCNF_SLIC_COMPACTNESS
+    clip_norm = None     # NON-REFERENCE, --clip-norm: bound on every optimizer group's gradient norm (see DCNFReplica)
 
     def __call__(self, images, depths, train=True):
         assert images.pipeline is depths.pipeline, 'inputs and targets must come from the same data.inputs() call'
@@ -2258,7 +2334,7 @@ class _DistributedConvolutionalNeuralFields:
                               train_pairwise=self.train_pairwise and train, pairwise_texture=self.pairwise_texture,
                               valid_range=self.valid_range, min_valid=self.min_valid, unary=self.unary,
                               superpixel=self.superpixel, segmentation=self.segmentation, slic_iters=self.slic_iters,
-                              slic_compactness=self.slic_compactness)
+                              slic_compactness=self.slic_compactness, clip_norm=self.clip_norm if train else None)
         if self.reducer is not None:
             for g in replica.groups.values():
                 self.reducer.broadcast(g.var)

@@ -5,6 +5,7 @@ C ABI (include/a3d.h) and returns without synchronising.  Layouts are TensorFlow
 """
 import collections
 import ctypes
+import math
 
 import torch
 
@@ -906,6 +907,94 @@ def dense_bwd_filter_momentum(x, dz, var_w, accum_w, var_b, accum_b, lr, momentu
     check(_lib.load().a3do_dense_bwd_filter_momentum(m, k, n, _ptr(x), _ptr(dz), _ptr(var_w), _ptr(accum_w), _ptr(var_b),
                                                      _ptr(accum_b), lr, momentum, grad_scale, _stream()),
           'a3do_dense_bwd_filter_momentum')
+
+
+# ---- gradient clipping by global norm, per optimizer group (NON-REFERENCE, include/a3d_clip.h) ----
+ClipState = collections.namedtuple('ClipState', 'sumsq norm scale skip skipped')
+
+
+def clip_ctl(device):
+    """A control block of grad_norm_scale and the *_ctl applies: 32 zeroed bytes, as four int64 words."""
+    return torch.zeros(_lib.CLIP_CTL_BYTES // 8, dtype=torch.int64, device=device)
+
+
+def clip_read(ctl):
+    """The control block on the host, one copy: ClipState(sumsq float64, norm float32, scale float32, skip, skipped)."""
+    import numpy as np
+    raw = ctl.cpu().numpy().tobytes()
+    f = np.frombuffer(raw, np.float32)
+    u = np.frombuffer(raw, np.uint32)
+    return ClipState(float(np.frombuffer(raw, np.float64)[0]), f[2], f[3], int(u[4]), int(u[5]))
+
+
+def grad_norm_ws(count, device):
+    """Workspace of grad_norm_scale for up to `count` elements: a3dn_grad_norm_ws_bytes zeros (the arrival ticket, which every
+    launch leaves at 0 again, and one float64 per block)."""
+    return torch.zeros(_lib.load().a3dn_grad_norm_ws_bytes(int(count)) // 8, dtype=torch.int64, device=device)
+
+
+def _check_ctl(who, ctl, like):
+    if ctl.dtype != torch.int64 or ctl.numel() * 8 != _lib.CLIP_CTL_BYTES or not ctl.is_contiguous():
+        raise TypeError(f'{who}: ctl is a control block of clip_ctl()')
+    if ctl.device != like.device:
+        raise ValueError(f'{who}: all tensors on one device')
+
+
+def grad_norm_scale(g, grad_scale, clip_norm, ctl, ws):
+    """NON-REFERENCE (a3dn_grad_norm_scale): one launch that leaves in ctl the float64 sum of squares S of g, the norm
+    n = |grad_scale| sqrt(S), scale = grad_scale (n <= clip_norm) or grad_scale * clip_norm / n, and skip = 1 with scale = 0
+    where S is not finite.  g: a float32 tensor starting on a 16-byte boundary; clip_norm > 0, inf allowed."""
+    if g.numel() == 0:
+        raise ValueError('grad_norm_scale: g holds no values')
+    _check_momentum('grad_norm_scale', (g,), 'g')
+    _check_ctl('grad_norm_scale', ctl, g)
+    if ws.dtype != torch.int64 or not ws.is_contiguous() or ws.device != g.device:
+        raise TypeError('grad_norm_scale: ws is a workspace of grad_norm_ws() on the device of g')
+    grad_scale, clip_norm = float(grad_scale), float(clip_norm)
+    if not (math.isfinite(grad_scale) and grad_scale != 0):
+        raise ValueError(f'grad_norm_scale: grad_scale {grad_scale!r} must be finite and not 0')
+    if not clip_norm > 0:
+        raise ValueError(f'grad_norm_scale: clip_norm {clip_norm!r} must be > 0 (inf: measure and skip only)')
+    check(_lib.load().a3dn_grad_norm_scale(g.numel(), _ptr(g), grad_scale, clip_norm, _ptr(ctl), _ptr(ws), ws.numel() * 8,
+                                           _stream()), 'a3dn_grad_norm_scale')
+
+
+def momentum_apply_ctl(var, accum, g, lr, momentum, ctl):
+    """NON-REFERENCE (a3dn_momentum_apply_ctl): momentum_apply with grad_scale read from ctl on the device; nothing is written
+    where ctl says skip."""
+    if var.numel() == 0 or accum.numel() != var.numel() or g.numel() != var.numel():
+        raise ValueError(f'momentum_apply_ctl: var {tuple(var.shape)}, accum {tuple(accum.shape)} and g {tuple(g.shape)} must '
+                         f'hold the same number of values')
+    _check_momentum('momentum_apply_ctl', (var, accum, g), 'var, accum, g')
+    _check_ctl('momentum_apply_ctl', ctl, var)
+    check(_lib.load().a3dn_momentum_apply_ctl(var.numel(), _ptr(var), _ptr(accum), _ptr(g), lr, momentum, _ptr(ctl), _stream()),
+          'a3dn_momentum_apply_ctl')
+
+
+def adam_apply_tf1_ctl(var, m, v, g, lr, beta1, beta2, eps, beta1_power, beta2_power, ctl, poisoned=None):
+    """NON-REFERENCE (a3dn_adam_apply_tf1_ctl): adam_apply_tf1 with grad_scale read from ctl on the device; nothing is written,
+    `poisoned` included, where ctl says skip."""
+    if var.numel() == 0 or any(t.numel() != var.numel() for t in (m, v, g)):
+        raise ValueError('adam_apply_tf1_ctl: var, m, v and g must hold the same number of values')
+    _check_momentum('adam_apply_tf1_ctl', (var, m, v, g), 'var, m, v, g')
+    _check_ctl('adam_apply_tf1_ctl', ctl, var)
+    check(_lib.load().a3dn_adam_apply_tf1_ctl(var.numel(), _ptr(var), _ptr(m), _ptr(v), _ptr(g), lr, beta1, beta2, eps,
+                                              beta1_power, beta2_power, _ptr(ctl), _ptr(poisoned), _stream()),
+          'a3dn_adam_apply_tf1_ctl')
+
+
+def sgd_apply_ctl(var, g, lr, ctl, floor=None):
+    """NON-REFERENCE (a3dn_sgd_apply_ctl; with a floor a3dn_sgd_apply_floor_ctl): sgd_apply / sgd_apply_floor at the rate
+    fl32(lr * scale), the product formed on the device from ctl; nothing is written where ctl says skip."""
+    if var.numel() == 0 or g.numel() != var.numel():
+        raise ValueError(f'sgd_apply_ctl: var {tuple(var.shape)} and g {tuple(g.shape)} must hold the same number of values')
+    _check_momentum('sgd_apply_ctl', (var, g), 'var, g')
+    _check_ctl('sgd_apply_ctl', ctl, var)
+    if floor is None:
+        check(_lib.load().a3dn_sgd_apply_ctl(var.numel(), _ptr(var), _ptr(g), lr, _ptr(ctl), _stream()), 'a3dn_sgd_apply_ctl')
+    else:
+        check(_lib.load().a3dn_sgd_apply_floor_ctl(var.numel(), _ptr(var), _ptr(g), lr, floor, _ptr(ctl), _stream()),
+              'a3dn_sgd_apply_floor_ctl')
 
 
 def superpixel_mean(x, sp, out=None):
