@@ -7,36 +7,26 @@
 //   dense_dw_kernel<ADAM = false> : dw[k][n] = sum_m x[m][k] * dz[m][n]               (BiasAddGrad rides along)
 //   dense_dw_kernel<ADAM = true>  : the same sum goes straight into ApplyAdam's m slot for the reference's optimizer
 //                                   AdamOptimizer(rate, 0.9, beta2 = 1) (src/models.py:309): alpha = 0 and 1-beta2 = 0,
-//                                   so only m moves (adam_frozen_kernel, pointwise.hip); dw is never written and not
+//                                   so only m moves (the frozen-Adam rule, optim_rules.h); dw is never written and not
 //                                   re-read: 2 HBM streams (m in, m out) instead of 4 (dw out; dw, m in; m out).
 //
-// fp32 MFMA 32x32x2 with the batch as the contraction axis: D[k][n] += A[k][m] * B[m][n], A = x^T, B = dz; the sum runs
-// over m in ascending order, one fmaf per term — the order of the BiasAddGrad sum too.
+// The contraction of dense_dw_kernel (fp32 MFMA 32x32x2, the batch as the contraction axis, in ascending order) and the
+// BiasAddGrad column sum are dense_dw.h's, shared with the fused momentum launch (optim.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
 #include "a3d_internal.h"
+#include "dense_dw.h"
 #include "igemm.h"
+#include "optim_rules.h"
 
 namespace a3d {
 
-
-// A wave owns 32 weight rows x 32*CW columns.  Lane li takes dz[m][n0 + CW li .. + CW-1] with ONE 4*CW-byte load and
-// feeds the CW values to CW MFMAs, so accumulator j holds the columns n0 + CW li + j: the CW accumulators of a lane are
-// ADJACENT columns of one row, and a wave-instruction of the epilogue moves two row segments of 128*CW bytes — for the m
-// slot's read (issued before the contraction starts, so its HBM latency passes under the operand loads and the MFMAs)
-// as for the write.  No LDS.  CW = 4 for the plain gradient (16-byte accesses); the Adam form holds the m tile in
-// registers on top of the accumulators and runs CW = 2 (half the registers, twice the waves per SIMD: what hides the
-// latency of a read-modify-write stream is waves in flight).
-template <int CW>
-struct VecOf;
-template <>
-struct VecOf<4> { typedef float type __attribute__((ext_vector_type(4), aligned(4))); };   // rows of [.., 4070] are 8-byte aligned
-template <>
-struct VecOf<2> { typedef float type __attribute__((ext_vector_type(2), aligned(4))); };
-
+// The wave tile and its contraction: dense_dw.h.  Both forms run CW = 4 (16-byte accesses).  The Adam form holds the wave's m
+// tile in registers on top of the accumulators, requested before the contraction starts; it is the form of last resort (an odd
+// n, or slots off the 8-byte grid: the lanes of a row are then 4-byte aligned only), behind the rows and stream kernels below.
 template <bool ADAM, int CW>
 __global__ __launch_bounds__(256) void dense_dw_kernel(const float* __restrict__ x, const float* __restrict__ dz,
                                                        float* __restrict__ dw, float* __restrict__ db,
@@ -44,142 +34,57 @@ __global__ __launch_bounds__(256) void dense_dw_kernel(const float* __restrict__
                                                        float* __restrict__ v_w, float* __restrict__ var_b,
                                                        float* __restrict__ m_b, float* __restrict__ v_b, int M, int K,
                                                        int N, float omb1, float gscale) {
-  typedef typename VecOf<CW>::type vec;
-  constexpr int TILE_N = 32 * CW;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, lh = lane >> 5;
-  const int n0 = blockIdx.x * TILE_N, k0 = (blockIdx.y * 4 + wave) * 32;
-  const bool use_scale = gscale != 1.f;
-  const float qnan = __builtin_nanf("");
+  typedef typename VecOf<CW>::type vec;                          // as it lies in memory
+  typedef float rvec __attribute__((ext_vector_type(CW)));      // in registers
+  const DwTile<CW> t(N);
 
   // BiasAddGrad (+ its Adam step): the blocks of the first row group, one column per thread
-  if (blockIdx.y == 0 && tid < TILE_N && n0 + tid < N && (ADAM ? m_b != nullptr : db != nullptr)) {
-    const int col = n0 + tid;
-    float s = 0.f;
-    for (int m0 = 0; m0 < M; m0 += 8) {       // eight loads in flight, added in row order
-      float t[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) t[i] = m0 + i < M ? dz[(size_t)(m0 + i) * N + col] : 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        if (m0 + i < M) s += t[i];
-    }
-    if (ADAM) {
-      const float g = use_scale ? __fmul_rn(s, gscale) : s;
-      const float mo = m_b[col];
-      const float mn = __fadd_rn(mo, __fmul_rn(__fsub_rn(g, mo), omb1));
-      m_b[col] = mn;
-      const bool poison = !isfinite(__fmul_rn(g, g));
-      if (poison) v_b[col] = qnan;
-      if (poison || !isfinite(mn)) var_b[col] = qnan;
-    } else {
-      db[col] = s;
-    }
+  if (blockIdx.y == 0 && t.tid < 32 * CW && t.n0 + t.tid < N && (ADAM ? m_b != nullptr : db != nullptr)) {
+    const int col = t.n0 + t.tid;
+    const float s = colsum_rows(dz, M, N, col);
+    if (ADAM) adam_frozen_one(var_b[col], m_b[col], v_b[col], scaled(s, gscale), omb1);
+    else db[col] = s;
   }
-  if (k0 >= K) return;      // wave-uniform
+  if (t.k0 >= K) return;      // wave-uniform
 
-  const int col0 = n0 + CW * li;                  // this lane's CW columns
-  const bool cfull = col0 + CW - 1 < N;           // all exist (only the last lanes of the last column group may not)
-  auto row_of = [&](int v) -> int { return k0 + (v & 3) + 8 * (v >> 2) + 4 * lh; };
-
-  vec mold[ADAM ? 16 : 1];
+  rvec mold[ADAM ? 16 : 1];
   if (ADAM) {
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
-      const int row = row_of(v);
+      const int row = t.row_of(v);
 #pragma unroll
       for (int j = 0; j < CW; ++j) mold[v][j] = 0.f;
-      if (row < K && cfull) mold[v] = *reinterpret_cast<const vec*>(m_w + (size_t)row * N + col0);
+      if (row < K && t.cfull) mold[v] = *reinterpret_cast<const vec*>(m_w + (size_t)row * N + t.col0);
     }
   }
 
   f32x16 acc[CW];
-#pragma unroll
-  for (int j = 0; j < CW; ++j)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[j][v] = 0.f;
-
-  // A[i = weight row k0+li][kk = batch row 2t+lh] = x[2t+lh][k0+li];  B_j[kk][li] = dz[2t+lh][col0 + j]
-  const int krow = k0 + li;
-  const bool kok = krow < K;
-  const int T = (M + 1) / 2;
-  for (int t0 = 0; t0 < T; t0 += 8) {
-    float a[8];
-    vec bq[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int m = 2 * (t0 + u) + lh;
-      const bool mok = m < M;
-      a[u] = (mok && kok) ? x[(size_t)m * K + krow] : 0.f;
-#pragma unroll
-      for (int j = 0; j < CW; ++j) bq[u][j] = 0.f;
-      if (mok) {
-        if (cfull) {
-          bq[u] = *reinterpret_cast<const vec*>(dz + (size_t)m * N + col0);
-        } else {
-#pragma unroll
-          for (int j = 0; j < CW; ++j)
-            if (col0 + j < N) bq[u][j] = dz[(size_t)m * N + col0 + j];
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-#pragma unroll
-      for (int j = 0; j < CW; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], bq[u][j], acc[j], 0, 0, 0);
-  }
+  dw_contract<CW, false>(t, x, dz, M, K, N, acc);
 
   // epilogue: register v of the CW accumulators = CW adjacent columns of row row_of(v)
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int row = row_of(v);
+    const int row = t.row_of(v);
     if (row >= K) continue;
-    const size_t o = (size_t)row * N + col0;
-    if (ADAM) {
-      if (cfull) {
-        // ApplyAdam with alpha = 0, 1 - beta2 = 0 (adam_frozen_kernel): m moves; v / var only where a non-finite g or m
-        // poisons them.  The poison test is one sum per row segment here — a non-finite term makes the sum non-finite —
-        // and the per-element work happens only behind it.
-        vec mn;
-        float chk = 0.f;
+    const size_t o = (size_t)row * N + t.col0;
+    rvec g;
 #pragma unroll
-        for (int j = 0; j < CW; ++j) {
-          const float g = use_scale ? __fmul_rn(acc[j][v], gscale) : acc[j][v];
-          mn[j] = __fadd_rn(mold[v][j], __fmul_rn(__fsub_rn(g, mold[v][j]), omb1));
-          chk += __fmul_rn(g, g) + fabsf(mn[j]);
-        }
-        *reinterpret_cast<vec*>(m_w + o) = mn;
-        if (!isfinite(chk)) {
+    for (int j = 0; j < CW; ++j) g[j] = acc[j][v];
+    if (ADAM && t.cfull) {
+      rvec mn;
+      const float chk = adam_frozen_piece<CW>(g, mold[v], mn, omb1, gscale);
+      *reinterpret_cast<vec*>(m_w + o) = mn;
+      if (!isfinite(chk)) adam_frozen_piece_poison<CW>(var_w + o, v_w + o, g, mn, gscale);
+    } else if (ADAM) {
 #pragma unroll
-          for (int j = 0; j < CW; ++j) {
-            const float g = use_scale ? __fmul_rn(acc[j][v], gscale) : acc[j][v];
-            const bool poison = !isfinite(__fmul_rn(g, g));
-            if (poison) v_w[o + j] = qnan;
-            if (poison || !isfinite(mn[j])) var_w[o + j] = qnan;
-          }
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < CW; ++j) {
-          if (col0 + j >= N) continue;
-          const float g = use_scale ? __fmul_rn(acc[j][v], gscale) : acc[j][v];
-          const float mo = m_w[o + j];
-          const float mn = __fadd_rn(mo, __fmul_rn(__fsub_rn(g, mo), omb1));
-          m_w[o + j] = mn;
-          const bool poison = !isfinite(__fmul_rn(g, g));
-          if (poison) v_w[o + j] = qnan;
-          if (poison || !isfinite(mn)) var_w[o + j] = qnan;
-        }
-      }
-    } else if (cfull) {
-      vec out;
-#pragma unroll
-      for (int j = 0; j < CW; ++j) out[j] = acc[j][v];
-      *reinterpret_cast<vec*>(dw + o) = out;
+      for (int j = 0; j < CW; ++j)
+        if (t.col0 + j < N) adam_frozen_one(var_w[o + j], m_w[o + j], v_w[o + j], scaled(g[j], gscale), omb1);
+    } else if (t.cfull) {
+      *reinterpret_cast<vec*>(dw + o) = g;
     } else {
 #pragma unroll
       for (int j = 0; j < CW; ++j)
-        if (col0 + j < N) dw[o + j] = acc[j][v];
+        if (t.col0 + j < N) dw[o + j] = g[j];
     }
   }
 }
@@ -209,8 +114,6 @@ __global__ __launch_bounds__(256) void dense_dw_adam_rows_kernel(const float* __
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int nb = blockIdx.x * 512, n0 = nb + wave * 128, k0 = blockIdx.y * 32;
-  const bool use_scale = gscale != 1.f;
-  const float qnan = __builtin_nanf("");
 
 #ifdef A3D_STAMPS
   unsigned long long s_t0, s_t1, s_t2, s_t3, s_t4, s_t5;
@@ -229,24 +132,8 @@ __global__ __launch_bounds__(256) void dense_dw_adam_rows_kernel(const float* __
     }
 
   if (blockIdx.y == 0 && m_b != nullptr) {        // BiasAddGrad + its Adam step, two columns per thread
-    for (int col = nb + tid; col < nb + 512 && col < N; col += 256) {
-      float s = 0.f;
-      for (int m0 = 0; m0 < M; m0 += 8) {
-        float t[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) t[i] = m0 + i < M ? dz[(size_t)(m0 + i) * N + col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          if (m0 + i < M) s += t[i];
-      }
-      const float g = use_scale ? __fmul_rn(s, gscale) : s;
-      const float mo = m_b[col];
-      const float mn = __fadd_rn(mo, __fmul_rn(__fsub_rn(g, mo), omb1));
-      m_b[col] = mn;
-      const bool poison = !isfinite(__fmul_rn(g, g));
-      if (poison) v_b[col] = qnan;
-      if (poison || !isfinite(mn)) var_b[col] = qnan;
-    }
+    for (int col = nb + tid; col < nb + 512 && col < N; col += 256)
+      adam_frozen_one(var_b[col], m_b[col], v_b[col], scaled(colsum_rows(dz, M, N, col), gscale), omb1);
   }
 
   A3D_STAMP(s_t1);
@@ -309,26 +196,11 @@ __global__ __launch_bounds__(256) void dense_dw_adam_rows_kernel(const float* __
       const int lr = wave * 8 + r, row = k0 + lr, c = (h * 64 + lane) * CW, col = nb + c;
       if (row >= K || col >= N) continue;
       const vec g4 = *reinterpret_cast<const vec*>(&tile[lr * kRowsLd + c]);
-      const vec mo = mold[NI * r + h];
       const size_t o = (size_t)row * N + col;
       vec mn;
-      float chk = 0.f;
-#pragma unroll
-      for (int j = 0; j < CW; ++j) {
-        const float g = use_scale ? __fmul_rn(g4[j], gscale) : g4[j];
-        mn[j] = __fadd_rn(mo[j], __fmul_rn(__fsub_rn(g, mo[j]), omb1));
-        chk += __fmul_rn(g, g) + fabsf(mn[j]);
-      }
+      const float chk = adam_frozen_piece<CW>(g4, mold[NI * r + h], mn, omb1, gscale);
       *reinterpret_cast<vec*>(m_w + o) = mn;
-      if (!isfinite(chk)) {
-#pragma unroll
-        for (int j = 0; j < CW; ++j) {
-          const float g = use_scale ? __fmul_rn(g4[j], gscale) : g4[j];
-          const bool poison = !isfinite(__fmul_rn(g, g));
-          if (poison) v_w[o + j] = qnan;
-          if (poison || !isfinite(mn[j])) var_w[o + j] = qnan;
-        }
-      }
+      if (!isfinite(chk)) adam_frozen_piece_poison<CW>(var_w + o, v_w + o, g4, mn, gscale);
     }
 #ifdef A3D_STAMPS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -385,8 +257,6 @@ __global__ __launch_bounds__(256, SL == 2 ? 4 : 2) void dense_dw_adam_stream_ker
   const int li = lane & 31, lh = lane >> 5;
   const int nb = blockIdx.x * BCOLS, n0 = nb + wave * WCOLS;
   const int ngroups = (K + 31) / 32, g0 = blockIdx.y * gpb, g1 = min(g0 + gpb, ngroups);
-  const bool use_scale = gscale != 1.f;
-  const float qnan = __builtin_nanf("");
   const __amdgpu_buffer_rsrc_t rx = make_rsrc(x, (unsigned long long)M * K * 4);
   const __amdgpu_buffer_rsrc_t rz = make_rsrc(dz, (unsigned long long)M * N * 4);
 
@@ -462,24 +332,8 @@ __global__ __launch_bounds__(256, SL == 2 ? 4 : 2) void dense_dw_adam_stream_ker
   park_x(xv);
 
   if (blockIdx.y == 0 && m_b != nullptr) {        // BiasAddGrad + its Adam step, two columns per thread
-    for (int col = nb + tid; col < nb + BCOLS && col < N; col += 256) {
-      float s = 0.f;
-      for (int m0 = 0; m0 < M; m0 += 8) {
-        float t[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) t[i] = m0 + i < M ? dz[(size_t)(m0 + i) * N + col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          if (m0 + i < M) s += t[i];
-      }
-      const float g = use_scale ? __fmul_rn(s, gscale) : s;
-      const float mo = m_b[col];
-      const float mn = __fadd_rn(mo, __fmul_rn(__fsub_rn(g, mo), omb1));
-      m_b[col] = mn;
-      const bool poison = !isfinite(__fmul_rn(g, g));
-      if (poison) v_b[col] = qnan;
-      if (poison || !isfinite(mn)) var_b[col] = qnan;
-    }
+    for (int col = nb + tid; col < nb + BCOLS && col < N; col += 256)
+      adam_frozen_one(var_b[col], m_b[col], v_b[col], scaled(colsum_rows(dz, M, N, col), gscale), omb1);
   }
   __syncthreads();
 
@@ -542,30 +396,15 @@ __global__ __launch_bounds__(256, SL == 2 ? 4 : 2) void dense_dw_adam_stream_ker
           const int c = (h * 64 + lane) * CW;
           const vec g4 = *reinterpret_cast<const vec*>(&tile[(4 * wave + (r & 3)) * TLD + c]);
           const uint32_t off = piece_off(h);
-          uvec mn;
-          float chk = 0.f;
-#pragma unroll
-          for (int j = 0; j < CW; ++j) {
-            const float gr = use_scale ? __fmul_rn(g4[j], gscale) : g4[j];
-            const float mo = mreg[NI * r + h][j];
-            const float t = __fadd_rn(mo, __fmul_rn(__fsub_rn(gr, mo), omb1));
-            mn[j] = __float_as_uint(t);
-            chk += __fmul_rn(gr, gr) + fabsf(t);
-          }
-          if constexpr (CW == 4) __builtin_amdgcn_raw_buffer_store_b128(mn, rr, (int)off, 0, kAuxStream);
-          else __builtin_amdgcn_raw_buffer_store_b64(mn, rr, (int)off, 0, kAuxStream);
+          vec mn;
+          const float chk = adam_frozen_piece<CW>(g4, mreg[NI * r + h], mn, omb1, gscale);
+          if constexpr (CW == 4) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uvec, mn), rr, (int)off, 0, kAuxStream);
+          else __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uvec, mn), rr, (int)off, 0, kAuxStream);
           load_vec_buf<CW, kAuxStream>(rn, off, mreg[NI * r + h]);
-          // ApplyAdam's v and var take a NaN where g*g or the new m is not finite (adam_frozen_kernel); a non-finite
-          // term makes the piece's sum non-finite, and the per-element work happens only behind that test
+          // v and var of the piece: only where its sum is not finite, and only for a piece that exists
           if (!isfinite(chk) & (off != kOOB) & (row < K)) {
-#pragma unroll
-            for (int j = 0; j < CW; ++j) {
-              const float gr = use_scale ? __fmul_rn(g4[j], gscale) : g4[j];
-              const bool poison = !isfinite(__fmul_rn(gr, gr));
-              const size_t o = (size_t)row * N + nb + c + j;
-              if (poison) v_w[o] = qnan;
-              if (poison || !isfinite(__uint_as_float(mn[j]))) var_w[o] = qnan;
-            }
+            const size_t o = (size_t)row * N + nb + c;
+            adam_frozen_piece_poison<CW>(var_w + o, v_w + o, g4, mn, gscale);
           }
         }
       }
@@ -832,8 +671,7 @@ extern "C" int a3d_dense_bwd_filter_adam_tf1_ex(int m, int k, int n, const float
   A3D_CHECK_ARG(m > 0 && k > 0 && n > 0 && x && dz && var_w && m_w && v_w, "dense_bwd_filter_adam: bad arguments");
   A3D_CHECK_ARG((var_b && m_b && v_b) || (!var_b && !m_b && !v_b), "dense_bwd_filter_adam: bias slots come as a set");
   A3D_CHECK_ARG(dense_dw_applicable(m, k, n), "dense_bwd_filter_adam: batches of at most 64 rows only");
-  const float alpha = lr * sqrtf(1.f - beta2_power) / (1.f - beta1_power);
-  A3D_CHECK_ARG(alpha == 0.f && 1.f - beta2 == 0.f,
+  A3D_CHECK_ARG(adam_host(lr, beta2, beta1_power, beta2_power).frozen,
                 "dense_bwd_filter_adam: only the reference's frozen optimizer (beta2 == 1); otherwise call "
                 "a3d_dense_bwd_filter and a3d_adam_apply_tf1");
   clear_stale_error();
@@ -844,7 +682,7 @@ extern "C" int a3d_dense_bwd_filter_adam_tf1_ex(int m, int k, int n, const float
   // stream form: two blocks per CU, each walking down its share of the row groups; 512 columns per block for batches of
   // at most 32 rows, 256 for up to 64
   static const bool no_stream = tune_int("A3D_NO_DENSE_STREAM", 0) != 0;   // A/B aid (tuning processes only)
-  // the slim form (124 registers, four blocks per CU) for batches of at most 32 rows: measured in the step, beside the fine
+  // the slim form (122 registers, four blocks per CU) for batches of at most 32 rows: measured in the step, beside the fine
   // network's hinted GEMMs
   const bool slim = m <= 32 && n % 2 == 0;
   const bool bf_cols = precision == A3D_PREC_BF16 && m > 32;      // the bf16 form: 512 columns per block at any batch

@@ -6,6 +6,7 @@
 // var, accum and g are hundreds of MB read once and written once: their accesses are non-temporal (igemm.h, kAuxStream),
 // so that they do not push the operands a GEMM of the other stream re-reads out of the L2.
 #include "a3d_internal.h"
+#include "dense_dw.h"
 #include "igemm.h"
 #include "optim_rules.h"
 #include "../../include/a3d_optim.h"
@@ -22,48 +23,29 @@ __global__ __launch_bounds__(256) void momentum_kernel(float* __restrict__ var, 
   momentum_body(var, accum, g, count, lr, mu, gscale);
 }
 
-// dense_dw_kernel<true, 2> (dense.hip) with the momentum rule in its epilogue: a wave owns 32 weight rows x 64 columns, lane li
-// takes dz[m][n0 + 2 li .. + 1] with one 8-byte load and feeds two fp32 MFMA 32x32x2 (the batch is the contraction axis, in
-// ascending order: dense_dw_launch's sum, bit for bit), and register v of the two accumulators is two adjacent columns of row
-// row_of(v).  The wave's accum AND var tiles (2 x 16 registers of two floats) are requested before the contraction starts, so
+// dense_dw_kernel's contraction (dense_dw.h) at CW = 2, with the momentum rule in its epilogue: a wave owns 32 weight rows x 64
+// columns, lane li takes dz[m][n0 + 2 li .. + 1] with one 8-byte load and feeds two fp32 MFMA 32x32x2 (the batch is the contraction
+// axis, in ascending order: dense_dw_launch's sum, bit for bit), and register v of the two accumulators is two adjacent columns of
+// row row_of(v).  The wave's accum AND var tiles (2 x 16 registers of two floats) are requested before the contraction starts, so
 // their HBM latency passes under the operand loads (x and dz: L2-resident) and the MFMAs.  No LDS.  Rows of an odd n are
 // 4-byte aligned only: the two-float type is aligned(4), and the lanes across the last column take the scalar path.
-// GEMM_ORDER: the batch rows reach the matrix cores in the order of the implicit-GEMM route (igemm.h: a lane half holds four
-// consecutive rows of a chunk of eight, instruction j of the chunk multiplies rows 8u + j and 8u + 4 + j), which is what
-// a3d_dense_bwd_filter runs below k n = 2^16: the two-call form's bits there too.  Rows past the batch are zeros in both.
-typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
-
+// GEMM_ORDER: the batch rows in the order of the implicit-GEMM route, which is what a3d_dense_bwd_filter runs below k n = 2^16:
+// the two-call form's bits there too.
 template <bool GEMM_ORDER>
 __global__ __launch_bounds__(256) void dense_dw_momentum_kernel(const float* __restrict__ x, const float* __restrict__ dz,
                                                                 float* __restrict__ var_w, float* __restrict__ acc_w,
                                                                 float* __restrict__ var_b, float* __restrict__ acc_b,
                                                                 int M, int K, int N, float lr, float mu, float gscale) {
-  constexpr int CW = 2, TILE_N = 32 * CW;
-  typedef f32x2u vec;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, lh = lane >> 5;
-  const int n0 = blockIdx.x * TILE_N, k0 = (blockIdx.y * 4 + wave) * 32;
-  const bool use_scale = gscale != 1.f;
+  constexpr int CW = 2;
+  typedef VecOf<CW>::type vec;
+  const DwTile<CW> t(N);
 
-  // BiasAddGrad and its step: the blocks of the first row group, one column per thread (dense_dw_kernel's walk)
-  if (blockIdx.y == 0 && tid < TILE_N && n0 + tid < N && acc_b != nullptr) {
-    const int col = n0 + tid;
-    float s = 0.f;
-    for (int m0 = 0; m0 < M; m0 += 8) {       // eight loads in flight, added in row order
-      float t[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) t[i] = m0 + i < M ? dz[(size_t)(m0 + i) * N + col] : 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        if (m0 + i < M) s += t[i];
-    }
-    momentum_one(var_b[col], acc_b[col], use_scale ? __fmul_rn(s, gscale) : s, lr, mu);
+  // BiasAddGrad and its step: the blocks of the first row group, one column per thread
+  if (blockIdx.y == 0 && t.tid < 32 * CW && t.n0 + t.tid < N && acc_b != nullptr) {
+    const int col = t.n0 + t.tid;
+    momentum_one(var_b[col], acc_b[col], scaled(colsum_rows(dz, M, N, col), gscale), lr, mu);
   }
-  if (k0 >= K) return;      // wave-uniform
-
-  const int col0 = n0 + CW * li;                  // this lane's two columns
-  const bool cfull = col0 + CW - 1 < N;           // both exist (only the last lane of the last column group may hold one)
-  auto row_of = [&](int v) -> int { return k0 + (v & 3) + 8 * (v >> 2) + 4 * lh; };
+  if (t.k0 >= K) return;      // wave-uniform
 
   // Branch-free: a lane without a whole piece in row_of(v) reads the piece at element 0 instead and never uses it (sixteen
   // conditional loads ahead of the loop made the register allocator spill the accumulators).  A 1 x 1 matrix has no piece.
@@ -73,60 +55,28 @@ __global__ __launch_bounds__(256) void dense_dw_momentum_kernel(const float* __r
   if ((size_t)K * N >= 2) {      // uniform
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
-      const int row = row_of(v);
-      const size_t o = (row < K && cfull) ? (size_t)row * N + col0 : 0;
+      const int row = t.row_of(v);
+      const size_t o = (row < K && t.cfull) ? (size_t)row * N + t.col0 : 0;
       aold[v] = __builtin_nontemporal_load(reinterpret_cast<const vec*>(acc_w + o));
       wold[v] = __builtin_nontemporal_load(reinterpret_cast<const vec*>(var_w + o));
     }
   }
 
   f32x16 acc[CW];
-#pragma unroll
-  for (int j = 0; j < CW; ++j)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[j][v] = 0.f;
-
-  // A[i = weight row k0+li][kk = batch row 2t+lh] = x[2t+lh][k0+li];  B_j[kk][li] = dz[2t+lh][col0 + j]  (GEMM_ORDER: rows as above)
-  const int krow = k0 + li;
-  const bool kok = krow < K;
-  const int T = GEMM_ORDER ? (M + 7) / 8 * 4 : (M + 1) / 2;       // instructions: two batch rows each
-  for (int t0 = 0; t0 < T; t0 += 8) {
-    float a[8];
-    vec bq[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int m = GEMM_ORDER ? 8 * ((t0 + u) >> 2) + 4 * lh + ((t0 + u) & 3) : 2 * (t0 + u) + lh;
-      const bool mok = m < M;
-      a[u] = (mok && kok) ? x[(size_t)m * K + krow] : 0.f;
-      bq[u] = vec{0.f, 0.f};
-      if (mok) {
-        if (cfull) {
-          bq[u] = *reinterpret_cast<const vec*>(dz + (size_t)m * N + col0);
-        } else {
-#pragma unroll
-          for (int j = 0; j < CW; ++j)
-            if (col0 + j < N) bq[u][j] = dz[(size_t)m * N + col0 + j];
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-#pragma unroll
-      for (int j = 0; j < CW; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], bq[u][j], acc[j], 0, 0, 0);
-  }
+  dw_contract<CW, GEMM_ORDER>(t, x, dz, M, K, N, acc);
 
   // epilogue: register v of the two accumulators = two adjacent columns of row row_of(v)
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int row = row_of(v);
+    const int row = t.row_of(v);
     if (row >= K) continue;
-    const size_t o = (size_t)row * N + col0;
-    if (cfull) {
+    const size_t o = (size_t)row * N + t.col0;
+    if (t.cfull) {
       vec an = aold[v], wn = wold[v];
 #pragma unroll
       for (int j = 0; j < CW; ++j) {
         float wj = wn[j], aj = an[j];
-        momentum_one(wj, aj, use_scale ? __fmul_rn(acc[j][v], gscale) : acc[j][v], lr, mu);
+        momentum_one(wj, aj, scaled(acc[j][v], gscale), lr, mu);
         wn[j] = wj; an[j] = aj;
       }
       __builtin_nontemporal_store(an, reinterpret_cast<vec*>(acc_w + o));
@@ -134,7 +84,7 @@ __global__ __launch_bounds__(256) void dense_dw_momentum_kernel(const float* __r
     } else {
 #pragma unroll
       for (int j = 0; j < CW; ++j)
-        if (col0 + j < N) momentum_one(var_w[o + j], acc_w[o + j], use_scale ? __fmul_rn(acc[j][v], gscale) : acc[j][v], lr, mu);
+        if (t.col0 + j < N) momentum_one(var_w[o + j], acc_w[o + j], scaled(acc[j][v], gscale), lr, mu);
     }
   }
 }

@@ -83,6 +83,7 @@ ADAM_ONE_GROUP = [      # gpb == 1, and the three forms outside the stream kerne
     adam(64, 130, 516, ROWS4, (2, 5), 'k % 4 == 2 leaves the stream kernels; n % 512 == 4, k % 32 == 2'),
     adam(1, 132, 518, ROWS2, (2, 5), 'x one float off the 16-byte grid leaves the stream kernels; n % 4 == 2', align={'x': 4}),
     adam(64, 130, 517, PLAIN_ADAM, (5, 2), 'odd n: no vector form of the m slot at all'),
+    adam(64, 132, 518, ROWS2, (2, 5), 'the 8-byte rows form at a batch the poisoned gradient can use; n % 512 == 6, k % 32 == 4', align={'x': 4}),
 ]
 # gpb == 2 on 33 row groups: grid y 17, the last block walks ONE group, and that group has 4 rows (k = 1028)
 ADAM_SLIM_MULTI = [
@@ -112,6 +113,9 @@ GROUPS = {
 }
 # run-to-run bits and the poison semantics: one multi-group row of each stream instantiation, in that row's group
 REPEATED = [ADAM_SLIM_MULTI[0], ADAM_WIDE_MULTI[1], ADAM_BF16_MULTI[0], ADAM_BF16_MULTI[1]]
+# the poison semantics alone (one poisoned launch, no three-run bit check) on the three forms outside the stream kernels too: the
+# smallest rows that reach their tails with a batch of more than one row
+POISONED = REPEATED + [ADAM_ONE_GROUP[6], ADAM_ONE_GROUP[8], ADAM_ONE_GROUP[9]]
 ALL = FORWARD_SPLIT + FORWARD_UNSPLIT + FILTER_GRADIENT + ADAM_ONE_GROUP + ADAM_SLIM_MULTI + ADAM_WIDE_MULTI + ADAM_BF16_MULTI
 
 
@@ -125,7 +129,8 @@ def launches(row):
         return 1 if is_sigmoid(row) else len(FORWARD_VARIANTS)
     if row.entry == DW:
         return 2
-    return 2 * len(ADAM_VARIANTS) + (3 + 1 if row in REPEATED else 0)      # two steps each; repeated: 3 launches for the bits, 1 poisoned
+    # two steps each; repeated: 3 launches for the bits; poisoned: 1 launch
+    return 2 * len(ADAM_VARIANTS) + (3 if row in REPEATED else 0) + (1 if row in POISONED else 0)
 
 
 def case(row):
@@ -159,7 +164,7 @@ def adam_steps(cs):
     return out
 
 
-# ---- poison (the REPEATED rows): an inf in dz, and a finite value whose scaled square is not finite ----
+# ---- poison (the POISONED rows): an inf in dz, and a finite value whose scaled square is not finite ----
 POISON_COLUMN = 3
 HUGE = 2.0 ** 66          # exact in bf16; (0.5 * 2^66)^2 = 2^130 is not finite, 2^65 and the new m are
 

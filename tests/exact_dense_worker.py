@@ -8,7 +8,8 @@ arguments, grid and splits / span / gpb is a MISMATCH — a row that silently la
 output lies in a NaN-filled allocation with guard elements in front and guard rows behind, and the WHOLE allocation must equal
 the float64 reference (integer operands: no tolerance).  The sigmoid rows are held to the float64 sigmoid of the exact
 pre-activation within 8 x the largest error of the numpy float32 restatement, at least one ulp of the output.  The rows of
-dense_cases.REPEATED also run three times from the same slots (the same bits each time) and once on a poisoned gradient.
+dense_cases.REPEATED also run three times from the same slots (the same bits each time), and those of dense_cases.POISONED (the
+repeated ones and one row of each Adam form outside the stream kernels) once on a poisoned gradient.
 
 stdout: `ROUTE | ...` per verified launch, `SIGMOID | ...` figures, `MISMATCH ...` per failure, then `verified N launches`; exit
 status 1 on any failure.  A device error ends the process at once: nothing more is launched on a GPU that has faulted."""
@@ -218,6 +219,7 @@ class Worker:
                     break
         if row in D.REPEATED:
             self.repeated(row, cs, x, steps[0][0])
+        if row in D.POISONED:
             self.poisoned(row, cs, x)
 
     def repeated(self, row, cs, x, dz):

@@ -32,12 +32,15 @@ def test_the_table_names_exactly_the_kernels_dense_hip_can_launch():
     expected = {row.route['kernel'] for row in D.ALL}
     assert launched == expected, f'launched without a row: {sorted(launched - expected)}; rows without a launch: {sorted(expected - launched)}'
     assert len(launched) == 10      # 2 forward, 2 plain, 2 rows and 4 stream forms
-    assert len(D.ALL) == 31 and len({(r.entry, r.shape, r.precision) for r in D.ALL}) == 31      # a row leaves or arrives on purpose, with this count
-    # ... and every row is run by some pytest case of the GPU file, the repeated ones among them
+    assert len(D.ALL) == 32 and len({(r.entry, r.shape, r.precision) for r in D.ALL}) == 32      # a row leaves or arrives on purpose, with this count
+    # ... and every row is run by some pytest case of the GPU file, the repeated and the poisoned ones among them
     grouped = [row for rows in D.GROUPS.values() for row in rows]
-    assert all(row in grouped for row in D.ALL) and all(row in D.ALL for row in D.REPEATED)
+    assert all(row in grouped for row in D.ALL) and all(row in D.ALL for row in D.POISONED)
     assert {row.route['kernel'] for row in D.REPEATED} == {D.SLIM, D.WIDE, D.BF4, D.BF2}
     assert all(row.route['gpb'] >= 2 for row in D.REPEATED)
+    # the poisoned gradient reaches every instantiation that holds the frozen-Adam rule
+    assert all(row in D.POISONED for row in D.REPEATED) and len(D.POISONED) == len(D.REPEATED) + 3
+    assert {row.route['kernel'] for row in D.POISONED} == {D.SLIM, D.WIDE, D.BF4, D.BF2, D.ROWS4, D.ROWS2, D.PLAIN_ADAM}
 
 
 def test_the_collector_sees_a_launch_that_is_put_back():
@@ -104,7 +107,7 @@ def test_every_row_keeps_its_headroom(row):
         # the second step moves much of m (one batch row: 4/9 of the ternary products are non-zero), and what it leaves depends on
         # the first step's m: a kernel that dropped the slot's old value, or the new gradient, differs
         assert (steps[1][3] != steps[0][3]).mean() > 0.25 and (steps[1][3] != dense_half_gradient(cs, steps[1][0])).mean() > 0.25
-        if row in D.REPEATED:
+        if row in D.POISONED:
             w, b = D.poison_masks(cs)
             assert w.sum() > k and b.sum() == 2
     E.dense_case.cache_clear()

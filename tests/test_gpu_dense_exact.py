@@ -51,9 +51,11 @@ def test_rows_are_exact_on_the_route_they_expect(group):
     if any(D.is_sigmoid(row) for row in D.GROUPS[group]):
         assert any('act sigmoid' in r[4] for r in routes)
     for row in D.GROUPS[group]:
+        mine = [r[4] for r in routes if r[2] == ' '.join(map(str, row.shape))]
         if row in D.REPEATED:
-            mine = [r[4] for r in routes if r[2] == ' '.join(map(str, row.shape))]
             assert 'three runs' in mine and 'poisoned gradient' in mine, mine
+        if row in D.POISONED:
+            assert 'poisoned gradient' in mine, mine
 
 
 def test_every_instantiation_and_regime_was_shown_by_a_route_line():

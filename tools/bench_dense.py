@@ -26,6 +26,9 @@ for name, k, n in (('dense_0', 12288, 4096), ('dense_1', 4096, 4070)):
             ('bwd_d', lambda: ops.dense_bwd_data(dz, w, dx, mask=x, scale=1.0), mb_w),
             ('bwd_f', lambda: ops.dense_bwd_filter(x, dz, dw, db), mb_w),
             ('bwd_f+adam', lambda: ops.dense_bwd_filter_adam_tf1(x, dz, w, mw, vw, b, mb, vb, 0.1, 0.9, 1.0, 0.9, 1.0, 1.0), 2 * mb_w)]
+    if B > 32:      # the bf16 stream form runs above 32 rows only
+        rows.append(('bwd_f+adam16', lambda: ops.dense_bwd_filter_adam_tf1(x, dz, w, mw, vw, b, mb, vb, 0.1, 0.9, 1.0, 0.9, 1.0, 1.0,
+                                                                            precision='bf16'), 2 * mb_w))
     for mode, fn, mbytes in rows:
         t = timeit(fn)
         print(f'{name} {mode:11s} {t:8.1f} us  {mbytes / t:6.2f} TB/s of weight-sized traffic', flush=True)
